@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- the hot path of SubspaceInference.jl on MI355X at BASELINE.json's configurations.
 
-    python bench.py --gpus N --steps K --warmup W [--mode chains|construct-sharded|data-sharded]
+    python bench.py --gpus N --steps K --warmup W [--mode chains|construct-sharded|data-sharded] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  Everything else the benchmark measures
+(construction breakdowns and variants, the output map, the 1000-step chain, the fp32 chain, the "next" rows, the CPU
+baseline, per-kernel breakdown passes) runs only with --full.  --dump-outputs DIR writes what the timed call returned, its
+last timed step included, as DIR/<name>.npy in float64 (rank 0's; a chain longer than 65536 steps as its last 65536), so
+that two builds can be compared output for output.
 
 With N > 1 and no RANK in the environment the parent process -- BEFORE importing torch or touching HIP -- starts the N
 ranks itself (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`), relays
@@ -22,8 +28,8 @@ rank 0's JSON line and exits non-zero when any rank fails.  Started under torchr
     replicated and device-resident, ONE 8-byte in-place RCCL all-reduce per transition.  A step = one transition.
 
 One JSON line on stdout (rank 0).  `roofline` is computed live from the library's own hipEvent pairs around the
-dominant kernel inside the timed region; `cpu_baseline` (N = 1, chains mode) times the CPU restatement on this box's
-host cores (bounded sample): the C/OpenMP port single-core and all-core, and the NumPy/OpenBLAS port.
+dominant kernel inside the timed region; `cpu_baseline` (--full, N = 1, chains mode) times the CPU restatement on this
+box's host cores (bounded sample): the C/OpenMP port single-core and all-core, and the NumPy/OpenBLAS port.
 """
 import argparse
 import hashlib
@@ -83,8 +89,13 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--mode", choices=["chains", "construct-sharded", "data-sharded"], default="chains")
     ap.add_argument("--config", choices=sorted(CFG), default="cfg5", help="construct-sharded: which N / K / M")
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU-baseline work (rank 0, N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: construction breakdowns and variants, output map, 1000-step "
+                         "and fp32 chains, next rows, CPU baseline, per-kernel breakdown passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed call returned (its last timed step included) as DIR/<name>.npy, float64 (rank 0)")
+    ap.add_argument("--cpu-budget", type=float, default=15.0, help="(--full) seconds of CPU-baseline work (rank 0, N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave the CPU baseline out")
     ap.add_argument("--dry-run-launcher", action="store_true",
                     help="ranks join a gloo group, count themselves and print a line with value null: exercises the "
                          "launch / relay / failure logic on a machine without GPUs (tests/test_bench_launcher.py)")
@@ -95,6 +106,8 @@ def parse_args(argv=None):
     dflt = {"chains": (100, 10), "construct-sharded": (5, 2), "data-sharded": (20, 3)}[args.mode]
     args.steps = dflt[0] if args.steps is None else args.steps
     args.warmup = dflt[1] if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
 
 
@@ -382,6 +395,23 @@ class Rank:
             os._exit(0)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_MAX_STEPS = 65536   # a longer chain is dumped as its last 65536 steps (the last timed step is always in)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float64) per array the timed call returned, 64 MB at most in all"""
+    import numpy as np
+    out = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log("bench.py: wrote %s to %s (%d bytes)" % (", ".join("%s%s" % (k, list(a.shape)) for k, a in out.items()), dirname, total))
+
+
 def emit(real_stdout, out):
     if REHEARSAL:
         out["rehearsal"] = "tools/bench_rehearsal.py: the ranks share the visible GPU(s) over gloo -- flow check, NOT a measurement"
@@ -471,34 +501,38 @@ def run_chains(args, rk, real_stdout):
             ctx.synchronize()
             runs.append((time.perf_counter() - t0) * 1e3)
         return sorted(runs)[1], [round(t, 4) for t in runs]
-    phase("construct: per-push and batched")
-    ctx.set_profiling(True)
+    full = args.full   # everything beside the headline (value, ms_per_step, construct_wall_ms) runs only with --full
+    phase("construct: per-push and batched" if full else "construct: per-push")
+    if full:
+        ctx.set_profiling(True)
     construct("per_push")  # warm-up (allocations, code-object load)
-    ctx.reset_stats()
-    construct("per_push")  # per-kernel breakdown (hipEvent pairs around every launch: ~5 us of stream time each)
-    ctx.synchronize()
-    cst = ctx.stats()
-    ctx.reset_stats()
-    construct("batched")
-    ctx.synchronize()
-    cst_b = ctx.stats()
-    ctx.set_profiling(False)
+    if full:
+        ctx.reset_stats()
+        construct("per_push")  # per-kernel breakdown (hipEvent pairs around every launch: ~5 us of stream time each)
+        ctx.synchronize()
+        cst = ctx.stats()
+        ctx.reset_stats()
+        construct("batched")
+        ctx.synchronize()
+        cst_b = ctx.stats()
+        ctx.set_profiling(False)
     construct_ms, construct_runs = wall3("per_push")
-    construct_b_ms, construct_b_runs = wall3("batched")
-    # the same with the deviation matrix stored in fp32 (opt-in; W_swa, G, the eigen-decomposition and P stay fp64)
-    phase("construct: fp32-stored A")
-    ctx.set_profiling(True)
-    construct("per_push", True)
-    ctx.reset_stats()
-    construct("per_push", True)
-    ctx.synchronize()
-    cst32 = ctx.stats()
-    ctx.set_profiling(False)
-    construct32_ms, construct32_runs = wall3("per_push", True)
-    construct32_b_ms, _ = wall3("batched", True)
-    phase("construct: host push")
+    if full:
+        construct_b_ms, construct_b_runs = wall3("batched")
+        # the same with the deviation matrix stored in fp32 (opt-in; W_swa, G, the eigen-decomposition and P stay fp64)
+        phase("construct: fp32-stored A")
+        ctx.set_profiling(True)
+        construct("per_push", True)
+        ctx.reset_stats()
+        construct("per_push", True)
+        ctx.synchronize()
+        cst32 = ctx.stats()
+        ctx.set_profiling(False)
+        construct32_ms, construct32_runs = wall3("per_push", True)
+        construct32_b_ms, _ = wall3("batched", True)
+        phase("construct: host push")
     host_push = None
-    if rank == 0:
+    if full and rank == 0:
         snaps_host = snaps[:, :n_par].cpu().numpy()   # 100 pageable Float32 vectors (419 MB)
         construct("host")                             # warm-up: pinned staging, copy pool
         hruns, pruns = [], []
@@ -536,11 +570,12 @@ def run_chains(args, rk, real_stdout):
                      "note": "100 x si_construct_push of a pageable 4.19 MB Float32 vector: host copy pool -> pinned double "
                              "buffer -> async H2D + K1, no synchronisation per push; then Gram + eig + projection"}
         del snaps_host
-    phase("construct: end to end through api.subspace_construction")
+    if full:
+        phase("construct: end to end through api.subspace_construction")
     # end to end through the drop-in call itself: subspace_construction(model, mse, data, ADAM; T = 100, M = 20) with the
     # training step on the device (src/subspace_construction.jl:37-59 as a whole: 100 x [gradient + update! + push] + psvd)
     e2e = e2e_f32 = None
-    if rank == 0:
+    if full and rank == 0:
         wr = np.random.default_rng(1)
         mdl = flux.Chain(*[flux.Dense(i, o, a, rng=wr) for i, o, a in zip(DIMS[:-1], DIMS[1:], ACTS)])
         data = flux.DataLoader(x, y, batchsize=B)
@@ -567,7 +602,7 @@ def run_chains(args, rk, real_stdout):
         ctx.bcast_subspace(0, n_par, M)   # cfg3: (W_swa, P) device to device over RCCL inside the library, once
 
     # ---- sampling.  The timed region carries event pairs around the DOMINANT kernel only (roofline.achieved is its
-    # live average launch duration); the per-class breakdown comes from a short untimed pass afterwards.
+    # live average launch duration); the per-class breakdown comes from a short untimed pass afterwards (--full).
     phase("sampling: the timed region (fp64)")
     ctx.infer_setup(table, n_par, M, None, None, x, y, SIGMA_M)
     # every rank evaluates the density at the same point: identical (W_swa, P) after the broadcast <=> identical bits
@@ -586,57 +621,62 @@ def run_chains(args, rk, real_stdout):
     per_rank_ms = rk.gather_floats(dt_local / args.steps * 1e3)
     lp_per_rank = rk.gather_floats(float(lp[-1, 0]))
     ctx.set_profiling(False)
-    # the same K transitions WITH the reference's output map (a13, src/space_inference.jl:125): every weight sample
-    # delivered to a fresh pageable host array while the chain runs -- what the drop-in sub_inference call does
-    phase("sampling: with the output map")
-    ctx.sample_rwmh_weights(5, SIGMA_Z, seed=100, chain_id0=rank)   # warm-up: weight ring, pinned staging, copy pool
-    barrier()
-    t0 = time.perf_counter()
-    zw, lpw, _, wmap = ctx.sample_rwmh_weights(args.steps, SIGMA_Z, seed=100, chain_id0=rank)
-    barrier()
-    dt_map = rk.max_over_ranks(time.perf_counter() - t0)
-    map_ok = bool(np.array_equal(zw, z) and np.array_equal(wmap[:, -1, 0], ctx.reconstruct(z[:, -1:, 0])[:, 0]))
-    del wmap
-    # one long chain, reported beside `value`: itr = 1000 is what BASELINE's cfg2 names; a short --steps run is corroborated
-    phase("sampling: 1000-step chain")
-    barrier()
-    t0 = time.perf_counter()
-    z1k, lp1k, _ = ctx.sample_rwmh(1000, SIGMA_Z, seed=100, chain_id0=rank)
-    barrier()
-    dt_1000 = rk.max_over_ranks(time.perf_counter() - t0)
-    bsteps = 20
-    ctx.set_profiling(True)
-    ctx.reset_stats()
-    ctx.sample_rwmh(bsteps, SIGMA_Z, seed=100, chain_id0=rank, want_z=False)
-    ctx.synchronize()
-    bst = ctx.stats()
-    ctx.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed call receives (z, lp, acceptance rate), and the weights W_swa + P z of the last sample
+        dump_outputs(args.dump_outputs, {"z": z[:, -DUMP_MAX_STEPS:, :], "lp": lp[-DUMP_MAX_STEPS:, :], "accept_rate": acc,
+                                         "w_last": ctx.reconstruct(z[:, -1:, 0])[:, 0]})
+    if full:
+        # the same K transitions WITH the reference's output map (a13, src/space_inference.jl:125): every weight sample
+        # delivered to a fresh pageable host array while the chain runs -- what the drop-in sub_inference call does
+        phase("sampling: with the output map")
+        ctx.sample_rwmh_weights(5, SIGMA_Z, seed=100, chain_id0=rank)   # warm-up: weight ring, pinned staging, copy pool
+        barrier()
+        t0 = time.perf_counter()
+        zw, lpw, _, wmap = ctx.sample_rwmh_weights(args.steps, SIGMA_Z, seed=100, chain_id0=rank)
+        barrier()
+        dt_map = rk.max_over_ranks(time.perf_counter() - t0)
+        map_ok = bool(np.array_equal(zw, z) and np.array_equal(wmap[:, -1, 0], ctx.reconstruct(z[:, -1:, 0])[:, 0]))
+        del wmap
+        # one long chain, reported beside `value`: itr = 1000 is what BASELINE's cfg2 names; a short --steps run is corroborated
+        phase("sampling: 1000-step chain")
+        barrier()
+        t0 = time.perf_counter()
+        z1k, lp1k, _ = ctx.sample_rwmh(1000, SIGMA_Z, seed=100, chain_id0=rank)
+        barrier()
+        dt_1000 = rk.max_over_ranks(time.perf_counter() - t0)
+        bsteps = 20
+        ctx.set_profiling(True)
+        ctx.reset_stats()
+        ctx.sample_rwmh(bsteps, SIGMA_Z, seed=100, chain_id0=rank, want_z=False)
+        ctx.synchronize()
+        bst = ctx.stats()
+        ctx.set_profiling(False)
 
-    # ---- compute_dtype = SI_F32 (SURVEY section 0 Q6 / 8(b),(d)): the same chain with X, the per-step weights and the activations
-    # in fp32 on v_mfma_f32_32x32x2_f32 (head + SSE in fp64), reported BESIDE the fp64 headline, never instead of it
-    phase("sampling: compute_dtype = SI_F32")
-    from subspaceinference_jl_amd import _capi
-    ctx.infer_setup(table, n_par, M, None, None, x, y, SIGMA_M, compute_dtype=_capi.SI_F32)
-    ctx.set_profiling(True, classes=["dense_main"])
-    ctx.sample_rwmh(max(1, args.warmup), SIGMA_Z, seed=100, chain_id0=rank, want_z=False)
-    barrier()
-    ctx.reset_stats()
-    t0 = time.perf_counter()
-    z32, lp32, acc32 = ctx.sample_rwmh(args.steps, SIGMA_Z, seed=100, chain_id0=rank)
-    barrier()
-    dt32 = rk.max_over_ranks(time.perf_counter() - t0)
-    st32 = ctx.stats()
-    ctx.set_profiling(False)
-    z32k, lp32k, acc32k = ctx.sample_rwmh(1000, SIGMA_Z, seed=100, chain_id0=rank)   # divergence from the fp64 chain, same Philox stream
-    same = np.all(z32k[:, :, 0] == z1k[:, :, 0], axis=0)
-    f32_first_diff = -1 if bool(same.all()) else int(np.argmin(same))
-    nsame = int(same.sum()) if f32_first_diff < 0 else f32_first_diff
-    f32_lp_rel = float(np.max(np.abs(lp32k[:nsame, 0] - lp1k[:nsame, 0]) / np.abs(lp1k[:nsame, 0]))) if nsame else None
-    ctx.infer_setup(table, n_par, M, None, None, x, y, SIGMA_M)   # back to the reference's arithmetic for what follows
+        # ---- compute_dtype = SI_F32 (SURVEY section 0 Q6 / 8(b),(d)): the same chain with X, the per-step weights and the activations
+        # in fp32 on v_mfma_f32_32x32x2_f32 (head + SSE in fp64), reported BESIDE the fp64 headline, never instead of it
+        phase("sampling: compute_dtype = SI_F32")
+        from subspaceinference_jl_amd import _capi
+        ctx.infer_setup(table, n_par, M, None, None, x, y, SIGMA_M, compute_dtype=_capi.SI_F32)
+        ctx.set_profiling(True, classes=["dense_main"])
+        ctx.sample_rwmh(max(1, args.warmup), SIGMA_Z, seed=100, chain_id0=rank, want_z=False)
+        barrier()
+        ctx.reset_stats()
+        t0 = time.perf_counter()
+        z32, lp32, acc32 = ctx.sample_rwmh(args.steps, SIGMA_Z, seed=100, chain_id0=rank)
+        barrier()
+        dt32 = rk.max_over_ranks(time.perf_counter() - t0)
+        st32 = ctx.stats()
+        ctx.set_profiling(False)
+        z32k, lp32k, acc32k = ctx.sample_rwmh(1000, SIGMA_Z, seed=100, chain_id0=rank)   # divergence from the fp64 chain, same Philox stream
+        same = np.all(z32k[:, :, 0] == z1k[:, :, 0], axis=0)
+        f32_first_diff = -1 if bool(same.all()) else int(np.argmin(same))
+        nsame = int(same.sum()) if f32_first_diff < 0 else f32_first_diff
+        f32_lp_rel = float(np.max(np.abs(lp32k[:nsame, 0] - lp1k[:nsame, 0]) / np.abs(lp1k[:nsame, 0]))) if nsame else None
+        ctx.infer_setup(table, n_par, M, None, None, x, y, SIGMA_M)   # back to the reference's arithmetic for what follows
 
-    phase("next rows: gradient, training step")
+        phase("next rows: gradient, training step")
     extras = {}
-    if rank == 0:
+    if full and rank == 0:
         # the "next" rows at the same workload (outside every timed region above)
         ctx.reset_stats()
         ctx.set_profiling(True)
@@ -723,6 +763,37 @@ def run_chains(args, rk, real_stdout):
         ms_step = dt / args.steps * 1e3
         step_flops = 2.0 * B * sum(a * b for a, b in zip(DIMS[:-1], DIMS[1:]))
         step_tflops = step_flops / (ms_step * 1e-3) / 1e12
+        # the headline and what the timed region itself yields (its event pairs around the dominant kernel included)
+        out = {
+            "metric": METRIC, "value": value, "unit": "samples/s", "n_gpus": n_seen, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": full,
+            "config": {"workload": "cfg2: Chain(Dense(128,960,relu),Dense(960,960,relu),Dense(960,1)) N=1047361, "
+                                   "X 128x100000 Y 1x100000 fp64, M=20, K=100 fp32 snapshots, RWMH sigma_z=0.1 sigma_m=1",
+                       "chains_per_gpu": 1, "mode": "chains",
+                       "parallelism": "independent chains x%d (one per GPU; chain id = rank), subspace broadcast once over RCCL "
+                                      "inside the library, no data-path collective per step" % n_seen},
+            "comm": ("in-library RCCL (si_comm_*), world %d" % n_seen) if rk.ctx is not None else
+                    ("none (one rank)" if rk.dist is None else "gloo control plane only"),
+            "comm_error": getattr(rk, "comm_error", None),
+            "per_rank_ms_per_step": [round(t, 4) for t in per_rank_ms], "lp_last_per_rank": lp_per_rank,
+            "chains_are_independent": bool(len(set(lp_per_rank)) == len(lp_per_rank)),
+            "subspace_identical_on_all_ranks": bool(len(set(lp0_per_rank)) == 1),   # lp at a fixed z, bit for bit, after si_bcast_subspace
+            "construct_wall_ms": construct_ms, "construct_wall_ms_runs": construct_runs,
+            "construct_wall_ms_note": "100 x si_construct_push_dev (one K1 launch per batch, the entry point api.py / the .jl "
+                                      "wrapper use) + Gram + host eigensolve + projection",
+            "accept_rate": float(acc[0]), "lp_last": float(lp[-1, 0]),
+            "roofline": {"kernel": "dense_f64_kernel<96,128> layer 960x960 + fused 960->1 tail (v_mfma_f64_16x16x4_f64)", "bound": "mfma",
+                         "achieved": achieved, "peak": PEAK_F64_TFLOPS, "unit": "TFLOP/s",
+                         "frac": achieved / PEAK_F64_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+                         "avg_launch_ms": avg_ms, "flops_per_launch": fl, "launches": dm["launches"]},
+            "step_roofline": {"bound": "mfma", "flops_per_step": step_flops, "achieved": step_tflops, "peak": PEAK_F64_TFLOPS,
+                              "unit": "TFLOP/s", "frac": step_tflops / PEAK_F64_TFLOPS,
+                              "note": "ALL of a transition (propose, reconstruct, 3 layers, SSE, accept) against the fp64 matrix peak"},
+            "device": ctx.device_name(),
+            "cpu_baseline": None,
+        }
+    if full and rank == 0:
 
         def frac(stats, cls, bound):
             v = stats[cls]
@@ -739,29 +810,12 @@ def run_chains(args, rk, real_stdout):
         ach32 = fl32 / (avg32 * 1e-3) / 1e12 if avg32 > 0 else 0.0
         traffic32, traffic32_src = pmc_traffic(PMC_PROFILE_F32, ["kernels_gemm_f32.hip"])
         ms_step32 = dt32 / args.steps * 1e3
-        out = {
-            "metric": METRIC, "value": value, "unit": "samples/s", "n_gpus": n_seen, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "cfg2: Chain(Dense(128,960,relu),Dense(960,960,relu),Dense(960,1)) N=1047361, "
-                                   "X 128x100000 Y 1x100000 fp64, M=20, K=100 fp32 snapshots, RWMH sigma_z=0.1 sigma_m=1",
-                       "chains_per_gpu": 1, "mode": "chains",
-                       "parallelism": "independent chains x%d (one per GPU; chain id = rank), subspace broadcast once over RCCL "
-                                      "inside the library, no data-path collective per step" % n_seen},
+        out.update({
             "value_with_output_map": n_seen * args.steps / dt_map,
             "output_map_note": "the same %d transitions through si_sample_rwmh_weights (what sub_inference calls): every weight "
                                "sample (8.4 MB) streamed to a fresh pageable host array under the following transitions; "
                                "bit-identical to si_reconstruct: %s" % (args.steps, map_ok),
             "chain_1000_steps_samples_per_s": n_seen * 1000 / dt_1000,
-            "comm": ("in-library RCCL (si_comm_*), world %d" % n_seen) if rk.ctx is not None else
-                    ("none (one rank)" if rk.dist is None else "gloo control plane only"),
-            "comm_error": getattr(rk, "comm_error", None),
-            "per_rank_ms_per_step": [round(t, 4) for t in per_rank_ms], "lp_last_per_rank": lp_per_rank,
-            "chains_are_independent": bool(len(set(lp_per_rank)) == len(lp_per_rank)),
-            "subspace_identical_on_all_ranks": bool(len(set(lp0_per_rank)) == 1),   # lp at a fixed z, bit for bit, after si_bcast_subspace
-            "construct_wall_ms": construct_ms, "construct_wall_ms_runs": construct_runs,
-            "construct_wall_ms_note": "100 x si_construct_push_dev (one K1 launch per batch, the entry point api.py / the .jl "
-                                      "wrapper use) + Gram + host eigensolve + projection",
             "construct_wall_ms_batched": construct_b_ms, "construct_wall_ms_batched_runs": construct_b_runs,
             "construct_a_fp32": {"note": "si_construct_set_storage(SI_F32): the deviation columns formed in fp64 and stored rounded once to fp32 "
                                          "(opt-in, SURVEY section 0 Q6); W_swa bit-exact, s rtol 1e-6, P 1e-5 of its scale vs the fp64 oracle "
@@ -784,14 +838,6 @@ def run_chains(args, rk, real_stdout):
             "construct_roofline": {"push": frac(cst, "push", "hbm"), "push_batched": frac(cst_b, "push", "hbm"),
                                    "gram": frac(cst, "gram", "mfma"), "project": frac(cst, "project", "hbm")},
             "sample_device_ms_per_step": {k: round(bst[k]["ms"] / bsteps, 4) for k in ("reconstruct", "dense", "sse", "rwmh")},
-            "accept_rate": float(acc[0]), "lp_last": float(lp[-1, 0]),
-            "roofline": {"kernel": "dense_f64_kernel<96,128> layer 960x960 + fused 960->1 tail (v_mfma_f64_16x16x4_f64)", "bound": "mfma",
-                         "achieved": achieved, "peak": PEAK_F64_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / PEAK_F64_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-                         "avg_launch_ms": avg_ms, "flops_per_launch": fl, "launches": dm["launches"]},
-            "step_roofline": {"bound": "mfma", "flops_per_step": step_flops, "achieved": step_tflops, "peak": PEAK_F64_TFLOPS,
-                              "unit": "TFLOP/s", "frac": step_tflops / PEAK_F64_TFLOPS,
-                              "note": "ALL of a transition (propose, reconstruct, 3 layers, SSE, accept) against the fp64 matrix peak"},
             "value_f32": n_seen * args.steps / dt32, "ms_per_step_f32": ms_step32,
             "roofline_f32": {"kernel": "dense_f32_dma_kernel<192,128> layer 960x960 + fused 960->1 head (v_mfma_f32_32x32x2_f32)",
                              "bound": "mfma", "achieved": ach32, "peak": PEAK_F32_TFLOPS, "unit": "TFLOP/s", "frac": ach32 / PEAK_F32_TFLOPS,
@@ -805,17 +851,15 @@ def run_chains(args, rk, real_stdout):
                     "first_transition_of_1000_where_the_chain_leaves_the_f64_chain": f32_first_diff,
                     "max_lp_rel_diff_vs_f64_chain_while_identical": f32_lp_rel,
                     "tolerance_stated": "lp rtol 1e-5 vs the fp64 oracle in tests/test_gpu_f32.py (north_star: 1e-4)"},
-            "device": ctx.device_name(),
             "next_rows": extras,
-        }
+        })
         if n_seen == 1 and not args.no_cpu_baseline:
             # W_swa / P the chains sampled in, brought to the host only for the CPU leg (outside all timers)
             w_swa, p, _ = ctx.construct_get_result()
             cb, lp_cpu = cpu_baseline(table, w_swa, p, x, y, z[:, 0, 0], args.cpu_budget)
             out["cpu_baseline"] = cb
             out["parity_lp_rel_err_vs_oracle"] = abs(lp_cpu - float(lp[0, 0])) / abs(lp_cpu)
-        else:
-            out["cpu_baseline"] = None
+    if rank == 0:
         emit(real_stdout, out)
     ctx.close()
     rk.finish()
@@ -865,12 +909,13 @@ def run_construct_sharded(args, rk, real_stdout):
             rk.dist.barrier()
     for _ in range(max(1, args.warmup)):
         construct()
-    ctx.set_profiling(True)
-    ctx.reset_stats()
-    construct()
-    ctx.synchronize()
-    cst = ctx.stats()
-    ctx.set_profiling(False)
+    if args.full:   # per-kernel breakdown: one construction with event pairs around every launch
+        ctx.set_profiling(True)
+        ctx.reset_stats()
+        construct()
+        ctx.synchronize()
+        cst = ctx.stats()
+        ctx.set_profiling(False)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -878,7 +923,10 @@ def run_construct_sharded(args, rk, real_stdout):
     barrier()
     dt = rk.max_over_ranks(time.perf_counter() - t0, dev)
     ms = dt / args.steps * 1e3
-    dev_ms = {kk: rk.gather_floats(cst[kk]["ms"], dev) for kk in ("push", "gram", "gram_reduce", "project", "eig_host")}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"s": s})   # the singular values the last construction returned
+    if args.full:
+        dev_ms = {kk: rk.gather_floats(cst[kk]["ms"], dev) for kk in ("push", "gram", "gram_reduce", "project", "eig_host")}
     if rank == 0:
         total_bytes = float(n) * (k * (4 + 8) + 16) + float(n) * k * 8 + float(n) * (k + m) * 8   # K1 + K2 + K3, algorithmic
         total_flops = float(n) * k * (k + 1) + 2.0 * n * k * m
@@ -892,21 +940,25 @@ def run_construct_sharded(args, rk, real_stdout):
                 return {"bound": "hbm", "achieved": a, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": a / PEAK_HBM_GBS, "rank0_ms": v["ms"]}
             a = v["flops"] / (v["ms"] * 1e-3) / 1e12
             return {"bound": "mfma", "achieved": a, "peak": PEAK_F64_TFLOPS, "unit": "TFLOP/s", "frac": a / PEAK_F64_TFLOPS, "rank0_ms": v["ms"]}
-        gram = blk("gram", "mfma")
-        emit(real_stdout, {
+        out = {
             "metric": "subspace-construct wall-clock, row-sharded (%s)" % args.config, "value": ms, "unit": "ms",
             "n_gpus": n_seen, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": False,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": "%s construct-only: N=%d rows sharded %d-way (%d on rank 0), K=%d fp32 snapshots (device-resident), M=%d"
                                    % (args.config, n, n_seen, n_loc, k, m), "mode": "construct-sharded",
                        "parallelism": "row shards; K1/K2/K3 row-local, ONE in-place RCCL all-reduce of the %dx%d fp64 Gram (%d B)"
                                       % (k, k, 8 * k * k)},
             "aggregate": {"algorithmic_GBs": total_bytes / (ms * 1e-3) / 1e9, "algorithmic_TFLOPs": total_flops / (ms * 1e-3) / 1e12},
-            "per_rank_device_ms": dev_ms,
-            "roofline": dict(gram or {}, kernel="gram A'A (v_mfma_f64_16x16x4_f64), rank 0", traffic=None),
-            "roofline_push": blk("push", "hbm"), "roofline_project": blk("project", "mfma" if m > 32 else "hbm"),
             "s1": float(s[0]), "device": ctx.device_name(), "cpu_baseline": None,
-        })
+        }
+        if args.full:
+            gram = blk("gram", "mfma")
+            out.update({
+                "per_rank_device_ms": dev_ms,
+                "roofline": dict(gram or {}, kernel="gram A'A (v_mfma_f64_16x16x4_f64), rank 0", traffic=None),
+                "roofline_push": blk("push", "hbm"), "roofline_project": blk("project", "mfma" if m > 32 else "hbm"),
+            })
+        emit(real_stdout, out)
     ctx.close()
     rk.finish()
 
@@ -956,11 +1008,14 @@ def run_data_sharded(args, rk, real_stdout):
     barrier()
     dt = rk.max_over_ranks(time.perf_counter() - t0, dev)
     st = ctx.stats()
-    ctx.set_profiling(True)
-    ctx.reset_stats()
-    sd.sample_data_sharded(ctx, 5, 1e-3, seed=5, d_total=d_total)
-    ctx.synchronize()
-    bst = ctx.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"z": z[:, -DUMP_MAX_STEPS:], "lp": lp[-DUMP_MAX_STEPS:], "accept_rate": acc})
+    if args.full:   # per-stage breakdown: 5 more transitions with event pairs around every launch
+        ctx.set_profiling(True)
+        ctx.reset_stats()
+        sd.sample_data_sharded(ctx, 5, 1e-3, seed=5, d_total=d_total)
+        ctx.synchronize()
+        bst = ctx.stats()
     ms = dt / args.steps * 1e3
     lps = rk.gather_floats(float(lp[-1, 0]), dev)
     if rank == 0:
@@ -968,29 +1023,33 @@ def run_data_sharded(args, rk, real_stdout):
         avg_ms = dm["ms"] / max(1, dm["launches"])
         fl = dm["flops"] / max(1, dm["launches"])
         achieved = fl / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
-        rec = bst["reconstruct"]
-        rec_gbs = rec["bytes"] / max(rec["ms"], 1e-9) / 1e6
         step_flops = 2.0 * B5_TOTAL * sum(a * b for a, b in zip(DIMS5[:-1], DIMS5[1:]))
-        emit(real_stdout, {
+        out = {
             "metric": "posterior samples/sec, data-sharded density (cfg5 wide MLP, M=64)", "value": args.steps / dt,
             "unit": "samples/s", "n_gpus": n_seen, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": "cfg5: Chain(Dense(1024,6656,relu),Dense(6656,6656,relu),Dense(6656,1)) N=51138049, M=64, "
                                    "B_total=%d split %d-way (%d on rank 0), W_swa/P (26 GB) replicated, device-resident" % (B5_TOTAL, n_seen, b_loc),
                        "mode": "data-sharded",
                        "parallelism": "observations sharded; every rank runs the same Philox stream; ONE 8-byte in-place RCCL all-reduce per transition"},
             "ranks_agree_on_lp": bool(len(set(lps)) == 1),
-            "per_step_device_ms": {k: round(bst[k]["ms"] / 5, 4) for k in ("reconstruct", "dense", "sse", "rwmh")},
             "roofline": {"kernel": "dense_f64_kernel layer 6656x6656 + fused 6656->1 tail, rank 0's share", "bound": "mfma",
                          "achieved": achieved, "peak": PEAK_F64_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_F64_TFLOPS,
                          "traffic": None, "avg_launch_ms": avg_ms, "flops_per_launch": fl, "launches": dm["launches"]},
-            "roofline_reconstruct": {"kernel": "reconstruct_kernel over the 26 GB P (K4)", "bound": "hbm", "achieved": rec_gbs,
-                                     "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": rec_gbs / PEAK_HBM_GBS},
             "step_roofline": {"bound": "mfma", "flops_per_step": step_flops, "achieved": step_flops / (ms * 1e-3) / 1e12 / n_seen,
                               "peak": PEAK_F64_TFLOPS, "unit": "TFLOP/s per GPU",
                               "frac": step_flops / (ms * 1e-3) / 1e12 / n_seen / PEAK_F64_TFLOPS},
             "lp_last": lps[0], "device": ctx.device_name(), "cpu_baseline": None,
-        })
+        }
+        if args.full:
+            rec = bst["reconstruct"]
+            rec_gbs = rec["bytes"] / max(rec["ms"], 1e-9) / 1e6
+            out.update({
+                "per_step_device_ms": {k: round(bst[k]["ms"] / 5, 4) for k in ("reconstruct", "dense", "sse", "rwmh")},
+                "roofline_reconstruct": {"kernel": "reconstruct_kernel over the 26 GB P (K4)", "bound": "hbm", "achieved": rec_gbs,
+                                         "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": rec_gbs / PEAK_HBM_GBS},
+            })
+        emit(real_stdout, out)
     ctx.close()
     rk.finish()
 

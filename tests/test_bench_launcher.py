@@ -55,3 +55,25 @@ def test_parent_imports_neither_torch_nor_the_hip_library():
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr
     assert json.loads(r.stdout.strip()) == {"n_gpus": 2}
+
+
+def test_full_and_dump_outputs_options(tmp_path):
+    """A plain run is the headline alone (--full adds the rest); --dump-outputs writes float64 .npy files, 64 MB at most."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--steps", "3", "--full", "--dump-outputs", str(tmp_path)])
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    z = np.arange(12, dtype=np.float32).reshape(2, 3, 2, order="F")
+    bench.dump_outputs(str(tmp_path / "out"), {"z": z, "lp": np.ones((3, 1))})
+    zz = np.load(str(tmp_path / "out" / "z.npy"))
+    assert zz.dtype == np.float64 and np.array_equal(zz, z) and np.load(str(tmp_path / "out" / "lp.npy")).shape == (3, 1)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"w": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    assert not os.path.exists(str(tmp_path / "big"))

@@ -235,6 +235,8 @@ def test_chain_loops_trace_exact_lp(si, gpu_ctx, m):
     chain of si_sample_rwmh is the exact lp.  All five set_chain_loop modes; nchains 1, 8, 64; the narrow class, whose mode-1
     runs of up to 8 chains must take the loop specialised to the chain's shapes at every M (above M = 64 only its tid < M guards
     keep it right)"""
+    # (z never moves here and only its size is looked at: the draws, the z + sigma_z eps update, the reject branch and the layout of
+    #  the z trace are held, transition by transition at M up to 1025, by tests/test_gpu_rwmh_audit.py)
     dims, acts, b = [2, 200, 50, 50, 50, 1], [R, R, R, R, I], 1000
     pb = lat.dense(dims, acts, b, m=m, ncols=1, seed=m, nonzero_swa=True, w_range=1, x_range=1)
     yh, _, _ = lat.forward_certified(pb.table, pb.w_swa, pb.x, lat.F64_LIMIT)

@@ -18,6 +18,18 @@
 
 namespace si {
 
+// The one way to device memory (dev_buf.h).  The development build hands out the library's own buffers from the guard-page
+// allocator (guard_alloc.hip; SI_GUARD_ALLOC=end|begin).
+#ifdef SI_DEV_KNOBS
+hipError_t guard_malloc(void** out, size_t bytes);
+hipError_t guard_free(void* p);
+hipError_t raw_dev_malloc(void** out, size_t bytes) { return guard_malloc(out, bytes); }
+hipError_t raw_dev_free(void* p) { return guard_free(p); }
+#else
+hipError_t raw_dev_malloc(void** out, size_t bytes) { return hipMalloc(out, bytes); }
+hipError_t raw_dev_free(void* p) { return hipFree(p); }
+#endif
+
 static thread_local std::string g_create_err;
 
 int32_t fail(Ctx* c, int32_t code, const std::string& msg) {
@@ -70,116 +82,19 @@ static void resolve_events(Ctx* c) {
 static void free_construct(Ctx* c) {
   // an inference set up on the construction's own W_swa / P dies with it
   if (c->i_ready && c->i_swa == c->d_swa && c->d_swa != nullptr) free_infer(c);
-  dev_free(c->d_swa);
-  dev_free(c->d_A);
-  dev_free(c->d_G);
-  c->g_cap = 0;
-  c->v_cap = 0;
-  dev_free(c->d_Gpart);
-  dev_free(c->d_V);
-  dev_free(c->d_P);
-  dev_free(c->d_B);
-  dev_free(c->d_At);
-  c->at_cap = 0;
-  c->refine_stage = 0;
-  c->gpart_bytes = 0;
-  c->c_active = c->c_finished = c->gram_valid = false;
-  c->K = c->Kcap = c->N = c->ldA = 0;
-  c->a_cols_alloc = 0;
-  c->a_bytes = 0;
-  c->a_zero_dtype = -1;
-  c->a_zero_cols = 0;
-  c->a_pending = false;
-  c->a_dtype = SI_F64;
-  c->npush = 0;
-  c->M_built = 0;
+  static_cast<ConstructState&>(*c) = ConstructState();
 }
 
-void free_infer(Ctx* c) {
-  dev_free(c->d_iswa);
-  dev_free(c->d_iP);
-  dev_free(c->d_X);
-  dev_free(c->d_Y);
-  dev_free(c->d_w);
-  dev_free(c->d_act[0]);
-  dev_free(c->d_act[1]);
-  dev_free(c->d_ssepart);
-  dev_free(c->d_part);
-  dev_free(c->d_outZ);
-  dev_free(c->d_outlp);
-  c->outZ_cap = c->outlp_cap = 0;
-  dev_free(c->d_gridsync);
-  c->gridsync_chains = 0;
-  dev_free(c->d_cgprog);
-  c->fused_ok = false;
-  dev_free(c->d_specw);
-  dev_free(c->d_specy);
-  dev_free(c->d_specperm);
-  c->specperm_for = nullptr;
-  c->spec_chains = c->spec_fo = 0;
-  c->last_density_spec = c->last_loop_spec = 0;
-  dev_free(c->d_yhat);
-  dev_free(c->d_X32);
-  dev_free(c->d_w32);
-  dev_free(c->d_act32[0]);
-  dev_free(c->d_act32[1]);
-  c->f32 = false;
-  c->fuse_slots32 = 0;
-  for (auto& h : c->d_hs) dev_free(h);
-  c->d_hs.clear();
-  for (auto& h : c->d_pidx) dev_free(h);
-  c->d_pidx.clear();
-  c->g_scratch.pidx = nullptr;
-  dev_free(c->d_delta[0]);
-  dev_free(c->d_delta[1]);
-  dev_free(c->d_gw);
-  dev_free(c->d_bwpart);
-  dev_free(c->d_rspart);
-  dev_free(c->d_ptgpart);
-  dev_free(c->d_gz);
-  if (c->g_ws32) {
-    sweep_f32_free(*c->g_ws32);
-    delete c->g_ws32;
-    c->g_ws32 = nullptr;
-  }
-  c->g_ready = false;
-  c->fuse_tail = false;
-  dev_free(c->d_Xc);
-  dev_free(c->d_wpack);
-  dev_free(c->d_wpack32);
-  dev_free(c->d_wsq);
-  dev_free(c->d_wsqpart);
-  c->sigma_p = 0.0;
-  dev_free(c->g_scratch.bwpart);
-  dev_free(c->g_scratch.rspart);
-  dev_free(c->g_scratch.wt);
-  dev_free(c->g_scratch.dbtmp);
-  c->plan = NetPlan();
-  dev_free(c->d_zcur);
-  dev_free(c->d_zprop);
-  dev_free(c->d_lpcur);
-  dev_free(c->d_sse);
-  dev_free(c->d_nacc);
-  dev_free(c->d_steps);
-  dev_free(c->sw_Z);
-  dev_free(c->sw_lp);
-  c->chains_cap = 0;
-  c->fw_slots = 0;
-  c->i_ready = false;
-  c->i_swa = c->i_P = nullptr;
-}
+void free_infer(Ctx* c) { static_cast<InferState&>(*c) = InferState(); }
 
 int32_t construct_adopt(Ctx* c, int64_t N, int32_t M) {
   const int64_t ld = pad_ld(N);
-  double *w = nullptr, *p = nullptr;
-  if (dev_alloc(&w, (size_t)ld) != hipSuccess || dev_alloc(&p, (size_t)ld * (size_t)M) != hipSuccess) {
-    dev_free(w);
-    dev_free(p);
+  DevBuf<double> w, p;
+  if (!w.alloc((size_t)ld) || !p.alloc((size_t)ld * (size_t)M))
     return fail(c, SI_ERR_NOMEM, "allocation of W_swa / P for a received subspace failed");
-  }
   SI_HIP(c, hipMemsetAsync(w, 0, (size_t)ld * sizeof(double), c->stream));
   SI_HIP(c, hipMemsetAsync(p, 0, (size_t)ld * (size_t)M * sizeof(double), c->stream));
-  construct_install(c, N, M, w, p);
+  construct_install(c, N, M, w.release(), p.release());
   return SI_OK;
 }
 
@@ -188,8 +103,8 @@ void construct_install(Ctx* c, int64_t N, int32_t M, double* w_swa, double* P) {
   free_construct(c);  // also drops an inference bound to the old W_swa / P
   c->N = N;
   c->ldA = pad_ld(N);
-  c->d_swa = w_swa;
-  c->d_P = P;
+  c->d_swa.adopt(w_swa, (size_t)c->ldA);
+  c->d_P.adopt(P, (size_t)c->ldA * (size_t)M);
   c->M_built = M;
   c->svals.assign((size_t)M, 0.0);
   c->c_active = false;  // no deviation matrix: nothing can be pushed or re-finished
@@ -234,8 +149,6 @@ int32_t dense_reverse_sweep(Ctx* ctx, hipStream_t st, const DenseSweep& s) {
 
 using namespace si;
 
-
-static void free_push_staging(si_ctx* ctx);
 
 extern "C" {
 
@@ -289,25 +202,11 @@ int32_t si_destroy(si_ctx* ctx) {
   resolve_events(ctx);
   for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
   comm_release(ctx);
-  free_train(ctx);
-  free_construct(ctx);
-  free_infer(ctx);
-  dev_free(ctx->d_wstage);
-  free_push_staging(ctx);
-  free_wstream(ctx);
-  dev_free(ctx->d_nvals);
-  if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
-  if (ctx->h_outpin) (void)hipHostFree(ctx->h_outpin);
-  for (int b = 0; b < 2; ++b) {
-    if (ctx->h_stage[b]) (void)hipHostFree(ctx->h_stage[b]);
-    dev_free(ctx->d_stage[b]);
-    dev_free(ctx->d_zstage[b]);
-  }
-  if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-  if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-  if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
-  if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-  delete ctx;
+  if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
+  const hipStream_t stream2 = ctx->stream2, own_stream = ctx->own_stream;
+  delete ctx;   // every buffer, pinned buffer and event of the context and of its training state
+  if (stream2) (void)hipStreamDestroy(stream2);   // (the streams go after the buffers)
+  if (own_stream) (void)hipStreamDestroy(own_stream);
   return SI_OK;
 }
 
@@ -378,22 +277,17 @@ static int32_t ensure_A(si_ctx* ctx) {
   ctx->a_pending = false;
   const size_t esz = ctx->a_dtype == SI_F32 ? 4 : 8;
   const size_t need = (size_t)ctx->ldA * (size_t)ctx->Kcap * esz;
-  if (ctx->d_A == nullptr || ctx->a_bytes < need) {
+  if (ctx->d_A.size() < need) {   // (bytes; an empty owner has size 0)
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->d_A);
-    ctx->a_bytes = 0;
-    if (dev_alloc(reinterpret_cast<char**>(&ctx->d_A), need) != hipSuccess) {
-      ctx->d_A = nullptr;
+    if (!ctx->d_A.alloc(need))
       return fail(ctx, SI_ERR_NOMEM, "si_construct_begin: device allocation of the deviation matrix failed");
-    }
-    ctx->a_bytes = need;
     ctx->a_zero_dtype = -1;
     ctx->a_zero_cols = 0;
   }
   if (ctx->a_zero_dtype != ctx->a_dtype || ctx->a_zero_cols < ctx->Kcap) {
     // only the padding rows [N, ldA) of every column (a strided fill of < 64 elements per column, not the whole matrix)
     if (ctx->ldA > ctx->N)
-      SI_HIP(ctx, hipMemset2DAsync(reinterpret_cast<char*>(ctx->d_A) + (size_t)ctx->N * esz, (size_t)ctx->ldA * esz, 0,
+      SI_HIP(ctx, hipMemset2DAsync(ctx->d_A + (size_t)ctx->N * esz, (size_t)ctx->ldA * esz, 0,
                                    (size_t)(ctx->ldA - ctx->N) * esz, (size_t)ctx->Kcap, ctx->stream));
     ctx->a_zero_dtype = ctx->a_dtype;
     ctx->a_zero_cols = ctx->Kcap;
@@ -418,7 +312,7 @@ int32_t si_construct_begin(si_ctx* ctx, int64_t N, int64_t K_capacity, int32_t m
     free_construct(ctx);
     ctx->N = N;
     ctx->ldA = pad_ld(N);
-    if (dev_alloc(&ctx->d_swa, (size_t)ctx->ldA) != hipSuccess) {
+    if (!ctx->d_swa.alloc((size_t)ctx->ldA)) {
       free_construct(ctx);
       return fail(ctx, SI_ERR_NOMEM, "si_construct_begin: device allocation of W_swa failed");
     }
@@ -456,15 +350,12 @@ int32_t si_construct_set_mean(si_ctx* ctx, const void* w_host, int32_t w_dtype) 
     SI_HIP(ctx, hipMemcpyAsync(ctx->d_swa, w_host, (size_t)ctx->N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   } else {
     const size_t bytes = (size_t)ctx->N * 4;
-    if (ctx->wstage_bytes < bytes) {
+    if (ctx->d_wstage.size() < (size_t)ctx->N) {
       SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      dev_free(ctx->d_wstage);
-      ctx->wstage_bytes = 0;
-      if (hipMalloc(&ctx->d_wstage, bytes) != hipSuccess) return fail(ctx, SI_ERR_NOMEM, "si_construct_set_mean: staging allocation failed");
-      ctx->wstage_bytes = bytes;
+      if (!ctx->d_wstage.reserve((size_t)ctx->N)) return fail(ctx, SI_ERR_NOMEM, "si_construct_set_mean: staging allocation failed");
     }
     SI_HIP(ctx, hipMemcpyAsync(ctx->d_wstage, w_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    launch_widen_f32(ctx->stream, static_cast<const float*>(ctx->d_wstage), ctx->d_swa, ctx->N, ctx->num_cu);
+    launch_widen_f32(ctx->stream, ctx->d_wstage, ctx->d_swa, ctx->N, ctx->num_cu);
   }
   SI_HIP(ctx, hipGetLastError());
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // w_host is caller-owned
@@ -488,7 +379,7 @@ static int32_t push_common(si_ctx* ctx, const void* w_dev, int32_t w_dtype, doub
   const size_t wsz = w_dtype == SI_F32 ? 4 : 8, asz = ctx->a_dtype == SI_F32 ? 4 : 8;
   {
     ProfScope ps(ctx, SI_K_PUSH, 4.0 * (double)ctx->N, (double)ctx->N * (double)(wsz + 16 + asz));
-    launch_swa_dev_push(ctx->stream, w_dev, w_dtype, ctx->d_swa, reinterpret_cast<char*>(ctx->d_A) + (size_t)slot * ctx->ldA * asz,
+    launch_swa_dev_push(ctx->stream, w_dev, w_dtype, ctx->d_swa, ctx->d_A + (size_t)slot * ctx->ldA * asz,
                         ctx->N, n, ctx->num_cu, ctx->a_dtype);
   }
   SI_HIP(ctx, hipGetLastError());
@@ -521,14 +412,9 @@ int32_t si_construct_push_batch_dev(si_ctx* ctx, const void* w_dev, int32_t w_dt
     const int32_t arc = ensure_A(ctx);
     if (arc != SI_OK) return arc;
   }
-  if (ctx->nvals_cap < count) {
+  if (ctx->d_nvals.size() < (size_t)count) {
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->d_nvals);
-    if (dev_alloc(&ctx->d_nvals, (size_t)count) != hipSuccess) {
-      ctx->nvals_cap = 0;
-      return fail(ctx, SI_ERR_NOMEM, "si_construct_push_batch_dev: allocation failed");
-    }
-    ctx->nvals_cap = count;
+    if (!ctx->d_nvals.reserve((size_t)count)) return fail(ctx, SI_ERR_NOMEM, "si_construct_push_batch_dev: allocation failed");
   }
   SI_HIP(ctx, hipMemcpyAsync(ctx->d_nvals, n_host, (size_t)count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // n_host is caller-owned and only valid during the call
@@ -553,15 +439,12 @@ int32_t si_construct_push_batch_dev(si_ctx* ctx, const void* w_dev, int32_t w_dt
 static void free_push_staging(si_ctx* ctx) {
   if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
   for (int b = 0; b < 2; ++b) {
-    if (ctx->h_wpin[b]) (void)hipHostFree(ctx->h_wpin[b]);
-    ctx->h_wpin[b] = nullptr;
-    dev_free(ctx->d_wpush[b]);
-    if (ctx->ev_wpin[b]) (void)hipEventDestroy(ctx->ev_wpin[b]);
-    if (ctx->ev_wk1[b]) (void)hipEventDestroy(ctx->ev_wk1[b]);
-    ctx->ev_wpin[b] = ctx->ev_wk1[b] = nullptr;
+    ctx->h_wpin[b].reset();
+    ctx->d_wpush[b].reset();
+    ctx->ev_wpin[b].reset();
+    ctx->ev_wk1[b].reset();
     ctx->wpin_busy[b] = false;
   }
-  ctx->wpin_bytes = 0;
 }
 
 int32_t si_construct_push(si_ctx* ctx, const void* w_host, int32_t w_dtype, double n) {
@@ -573,19 +456,17 @@ int32_t si_construct_push(si_ctx* ctx, const void* w_host, int32_t w_dtype, doub
   BIND(ctx);
   const size_t bytes = (size_t)ctx->N * (w_dtype == SI_F32 ? 4 : 8);
   if (!ctx->stream2) SI_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-  if (ctx->wpin_bytes < bytes) {
+  // (h_wpin / d_wpush / the events are allocated together below and dropped together on any failure, and d_wpush[1] is
+  //  the last buffer of the group: its size is the group's, 0 when there is none)
+  if (ctx->d_wpush[1].size() < bytes) {
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     free_push_staging(ctx);
     for (int b = 0; b < 2; ++b) {
-      if (hipHostMalloc(&ctx->h_wpin[b], bytes, hipHostMallocDefault) != hipSuccess ||
-          hipMalloc(&ctx->d_wpush[b], bytes) != hipSuccess ||
-          hipEventCreateWithFlags(&ctx->ev_wpin[b], hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&ctx->ev_wk1[b], hipEventDisableTiming) != hipSuccess) {
+      if (!ctx->h_wpin[b].alloc(bytes) || !ctx->d_wpush[b].alloc(bytes) || !ctx->ev_wpin[b].create() || !ctx->ev_wk1[b].create()) {
         free_push_staging(ctx);
         return fail(ctx, SI_ERR_NOMEM, "si_construct_push: staging allocation failed");
       }
     }
-    ctx->wpin_bytes = bytes;
   }
   // Three stages in flight: the host copy pool fills pinned buffer b (push i), the copy stream moves pinned -> device
   // buffer b, the compute stream runs K1 on it.  Buffer b of two pushes ago must be done: its H2D (host side: the pinned
@@ -611,29 +492,20 @@ int32_t si_construct_gram(si_ctx* ctx) {
   BIND(ctx);
   const int64_t K = ctx->K;
   const size_t need = launch_gram(ctx->stream, ctx->d_A, ctx->ldA, ctx->N, K, nullptr, nullptr, ctx->num_cu, nullptr, ctx->a_dtype);
-  if (ctx->gpart_bytes < need) {
+  if (ctx->d_Gpart.size() < need / sizeof(double)) {   // (`need` is whole doubles)
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->d_Gpart);
-    if (hipMalloc(reinterpret_cast<void**>(&ctx->d_Gpart), need) != hipSuccess) {
-      ctx->gpart_bytes = 0;
-      return fail(ctx, SI_ERR_NOMEM, "si_construct_gram: partial-slab allocation failed");
-    }
-    ctx->gpart_bytes = need;
+    if (!ctx->d_Gpart.reserve(need / sizeof(double))) return fail(ctx, SI_ERR_NOMEM, "si_construct_gram: partial-slab allocation failed");
   }
-  if (ctx->g_cap < K * K) {
+  if (ctx->d_G.size() < (size_t)(K * K)) {
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->d_G);
-    ctx->g_cap = 0;
-    if (dev_alloc(&ctx->d_G, (size_t)K * K) != hipSuccess)
-      return fail(ctx, SI_ERR_NOMEM, "si_construct_gram: G allocation failed");
-    ctx->g_cap = K * K;
+    if (!ctx->d_G.reserve((size_t)K * K)) return fail(ctx, SI_ERR_NOMEM, "si_construct_gram: G allocation failed");
   }
   launch_gram(ctx->stream, ctx->d_A, ctx->ldA, ctx->N, K, ctx->d_Gpart, ctx->d_G, ctx->num_cu, ctx, ctx->a_dtype);
   SI_HIP(ctx, hipGetLastError());
   ctx->gram_valid = true;
   if (ctx->refine_stage != 0 || ctx->d_B) {  // a fresh first-stage Gram: drop the second stage of an earlier finish
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->d_B);
+    ctx->d_B.reset();
     ctx->refine_stage = 0;
   }
   return SI_OK;
@@ -685,24 +557,16 @@ static constexpr double SI_GRAM_ROUTE_MIN = 1e-9;
 static constexpr double SI_EPS = 2.220446049250313e-16;
 
 static int32_t ensure_pin(si_ctx* ctx, size_t elems) {
-  if (ctx->h_pin_cap >= elems) return SI_OK;
+  if (ctx->h_pin.size() >= elems) return SI_OK;
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
-  ctx->h_pin = nullptr;
-  ctx->h_pin_cap = 0;
-  if (hipHostMalloc(reinterpret_cast<void**>(&ctx->h_pin), elems * sizeof(double), hipHostMallocDefault) != hipSuccess)
-    return fail(ctx, SI_ERR_NOMEM, "si_construct_finish: pinned staging allocation failed");
-  ctx->h_pin_cap = elems;
+  if (!ctx->h_pin.reserve(elems)) return fail(ctx, SI_ERR_NOMEM, "si_construct_finish: pinned staging allocation failed");
   return SI_OK;
 }
 
 static int32_t ensure_V(si_ctx* ctx, size_t v_elems) {
-  if (ctx->v_cap >= (int64_t)v_elems) return SI_OK;
+  if (ctx->d_V.size() >= v_elems) return SI_OK;
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  dev_free(ctx->d_V);
-  ctx->v_cap = 0;
-  if (dev_alloc(&ctx->d_V, v_elems) != hipSuccess) return fail(ctx, SI_ERR_NOMEM, "si_construct_finish: allocation of V failed");
-  ctx->v_cap = (int64_t)v_elems;
+  if (!ctx->d_V.reserve(v_elems)) return fail(ctx, SI_ERR_NOMEM, "si_construct_finish: allocation of V failed");
   return SI_OK;
 }
 
@@ -781,7 +645,7 @@ int32_t si_construct_refine(si_ctx* ctx) {
   if ((rc = ensure_V(ctx, (size_t)K * Kpad)) != SI_OK) return rc;
   if (ctx->d_B == nullptr) {
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (dev_alloc(&ctx->d_B, (size_t)ctx->ldA * K) != hipSuccess)
+    if (!ctx->d_B.alloc((size_t)ctx->ldA * K))
       return fail(ctx, SI_ERR_NOMEM, "si_construct_refine: allocation of the second-stage matrix (N x K) failed");
     SI_HIP(ctx, hipMemsetAsync(ctx->d_B, 0, (size_t)ctx->ldA * K * sizeof(double), ctx->stream));  // padding rows stay zero
   }
@@ -802,9 +666,8 @@ static int32_t alloc_P(si_ctx* ctx, int32_t M) {
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // P is re-allocated: an inference bound to the old P of this construction must not outlive it
   if (ctx->i_ready && ctx->i_P == ctx->d_P && ctx->d_P != nullptr) free_infer(ctx);
-  dev_free(ctx->d_P);
   ctx->M_built = 0;
-  if (dev_alloc(&ctx->d_P, (size_t)ctx->ldA * M) != hipSuccess)
+  if (!ctx->d_P.alloc((size_t)ctx->ldA * M))
     return fail(ctx, SI_ERR_NOMEM, "si_construct_finish: allocation of P failed");
   // zeroed once, for the padding rows [N, ldA): every row < N of every column is written on each finish
   SI_HIP(ctx, hipMemsetAsync(ctx->d_P, 0, (size_t)ctx->ldA * M * sizeof(double), ctx->stream));
@@ -818,30 +681,20 @@ static int32_t finish_wide(si_ctx* ctx, int32_t M, bool* done) {
   *done = false;
   const int64_t K = ctx->K, N = ctx->N, ldt = pad_ld(K);
   int32_t rc;
-  if (ctx->at_cap < ldt * N) {
+  if (ctx->d_At.size() < (size_t)(ldt * N)) {
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->d_At);
-    ctx->at_cap = 0;
-    if (dev_alloc(&ctx->d_At, (size_t)ldt * N) != hipSuccess) return fail(ctx, SI_ERR_NOMEM, "si_construct_finish: allocation of A' failed");
-    ctx->at_cap = ldt * N;
+    if (!ctx->d_At.reserve((size_t)ldt * N)) return fail(ctx, SI_ERR_NOMEM, "si_construct_finish: allocation of A' failed");
   }
   // the Gram kernel reads whole 64-row slabs: rows [K, ldt) of every column must be zero (K differs between constructions)
   SI_HIP(ctx, hipMemsetAsync(ctx->d_At, 0, (size_t)ldt * N * sizeof(double), ctx->stream));
   const size_t need = launch_gram(ctx->stream, ctx->d_At, ldt, K, N, nullptr, nullptr, ctx->num_cu, nullptr);
-  if (ctx->gpart_bytes < need) {
+  if (ctx->d_Gpart.size() < need / sizeof(double)) {
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->d_Gpart);
-    ctx->gpart_bytes = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&ctx->d_Gpart), need) != hipSuccess)
-      return fail(ctx, SI_ERR_NOMEM, "si_construct_finish: partial-slab allocation failed");
-    ctx->gpart_bytes = need;
+    if (!ctx->d_Gpart.reserve(need / sizeof(double))) return fail(ctx, SI_ERR_NOMEM, "si_construct_finish: partial-slab allocation failed");
   }
-  if (ctx->g_cap < N * N) {
+  if (ctx->d_G.size() < (size_t)(N * N)) {
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->d_G);
-    ctx->g_cap = 0;
-    if (dev_alloc(&ctx->d_G, (size_t)N * N) != hipSuccess) return fail(ctx, SI_ERR_NOMEM, "si_construct_finish: G allocation failed");
-    ctx->g_cap = N * N;
+    if (!ctx->d_G.reserve((size_t)N * N)) return fail(ctx, SI_ERR_NOMEM, "si_construct_finish: G allocation failed");
   }
   {
     ProfScope ps(ctx, SI_K_PUSH, 0.0, 16.0 * (double)N * (double)K);
@@ -927,7 +780,7 @@ int32_t si_construct_finish(si_ctx* ctx, int32_t M, double* W_swa_out, double* P
   if (!ctx->gram_valid && (rc = si_construct_gram(ctx)) != SI_OK) return rc;
   const int Mpad = project_mpad(M);
   const size_t v_elems = (size_t)K * Mpad;
-  const double* src = ctx->d_A;  // matrix the projection reads: A (Gram route) or B (two-stage route)
+  const void* src = ctx->d_A;  // matrix the projection reads: A (Gram route) or B (two-stage route)
   std::vector<double> vcols((size_t)K * M);  // right factor in the basis of `src`, columns m < M
   ctx->svals.assign((size_t)M, 0.0);
   if (ctx->refine_stage == 0) {
@@ -1034,14 +887,14 @@ int32_t si_construct_get_A(si_ctx* ctx, int64_t k0, int64_t nk, double* A_out) {
   if (nk == 0) return SI_OK;
   if (ctx->a_dtype == SI_F32) {   // fp32 storage: read the floats back and widen them (exact)
     std::vector<float> tmp((size_t)ctx->N * (size_t)nk);
-    SI_HIP(ctx, hipMemcpy2DAsync(tmp.data(), (size_t)ctx->N * sizeof(float), reinterpret_cast<const float*>(ctx->d_A) + k0 * ctx->ldA,
+    SI_HIP(ctx, hipMemcpy2DAsync(tmp.data(), (size_t)ctx->N * sizeof(float), reinterpret_cast<const float*>(ctx->d_A.get()) + k0 * ctx->ldA,
                                  (size_t)ctx->ldA * sizeof(float), (size_t)ctx->N * sizeof(float), (size_t)nk, hipMemcpyDeviceToHost,
                                  ctx->stream));
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < tmp.size(); ++i) A_out[i] = (double)tmp[i];
     return SI_OK;
   }
-  SI_HIP(ctx, hipMemcpy2DAsync(A_out, (size_t)ctx->N * sizeof(double), ctx->d_A + k0 * ctx->ldA,
+  SI_HIP(ctx, hipMemcpy2DAsync(A_out, (size_t)ctx->N * sizeof(double), reinterpret_cast<const double*>(ctx->d_A.get()) + k0 * ctx->ldA,
                                (size_t)ctx->ldA * sizeof(double), (size_t)ctx->N * sizeof(double), (size_t)nk,
                                hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -1,6 +1,7 @@
 // Declarations shared by the translation units of the C ABI (capi.hip: context + construction; capi_infer.hip: inference set-up,
-// density, gradient, predictive forward; capi_sample.hip: the RWMH samplers and the output map).  Round 5 split the 2 200-line
-// capi.hip along these seams; nothing here is part of the public interface (include/subspace_hip.h).
+// density, gradient, predictive forward; capi_sample.hip: the RWMH samplers and the output map).  Nothing here is part of the
+// public interface (include/subspace_hip.h).  Buffers are owned by the types of dev_buf.h (through si_internal.h): no file of
+// the C ABI calls hipMalloc / hipFree / hipHostMalloc / hipHostFree or creates an event by hand.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -11,30 +12,13 @@
 
 #include "si_internal.h"
 
-#ifdef SI_DEV_KNOBS   // development build: the library's own buffers through the guard-page allocator (guard_alloc.hip; SI_GUARD_ALLOC=end|begin)
 namespace si {
-hipError_t guard_malloc(void** out, size_t bytes);
-hipError_t guard_free(void* p);
-}
-#define hipMalloc(p, n) si::guard_malloc((void**)(p), (n))
-#define hipFree(p) si::guard_free((void*)(p))
-#endif
-
-namespace si {
-
-template <typename T>
-static inline hipError_t dev_alloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) count = 1;
-  return hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-}
-template <typename T>
-static inline void dev_free(T*& p) {
-  if (p) (void)hipFree((void*)p);
-  p = nullptr;
-}
 
 void free_infer(Ctx* c);   // capi.hip: everything si_infer_setup allocated
+// the acceptance rates of a finished chain from its per-chain accept counts (one place for all sampler forms and si_rwmh_end)
+inline void accept_rates(const std::vector<int64_t>& nacc, int64_t itr, double* out) {
+  for (size_t c = 0; out && c < nacc.size(); ++c) out[c] = itr > 1 ? (double)nacc[c] / (double)(itr - 1) : 0.0;
+}
 
 }  // namespace si
 
@@ -50,6 +34,4 @@ int32_t eval_density_all(si_ctx* ctx, int C);
 double mvnormal_c0(double d, double sigma);
 double prior_c0(const si_ctx* ctx);
 void fused_fill_program(const si_ctx* ctx, si::ChainFusedPlan& fp);
-// capi_sample.hip
-void free_wstream(si_ctx* ctx);
 }

@@ -59,26 +59,23 @@ static size_t fused_plan_for(const si_ctx* ctx, int nchains, ChainFusedPlan& fp,
 
 // forward workspace for `slots` chains evaluated in one launch (grid.y = chain slot)
 static bool alloc_forward(si_ctx* ctx, int slots) {
-  dev_free(ctx->d_w); dev_free(ctx->d_act[0]); dev_free(ctx->d_act[1]); dev_free(ctx->d_ssepart); dev_free(ctx->d_part);
-  dev_free(ctx->d_yhat); dev_free(ctx->d_w32); dev_free(ctx->d_act32[0]); dev_free(ctx->d_act32[1]);
+  for (DevBuf<double>* b : {&ctx->d_w, &ctx->d_act[0], &ctx->d_act[1], &ctx->d_ssepart, &ctx->d_part, &ctx->d_yhat}) b->reset();
+  for (DevBuf<float>* b : {&ctx->d_w32, &ctx->d_act32[0], &ctx->d_act32[1]}) b->reset();
   ctx->fw_slots = 0;
   const size_t S = (size_t)slots, dB = (size_t)ctx->out_dim * (size_t)ctx->B;
   // SI_F32: fp32 weights + fp32 ping-pong activations INSTEAD of the fp64 activations (the fp64 weights stay: K4 writes
   // both, the output map / prior / gradient read them); the head partials serve both paths (the larger slot count)
   const size_t pslots = (size_t)std::max(ctx->fuse_slots, ctx->fuse_slots32);
-  if (dev_alloc(&ctx->d_w, S * (size_t)pad_ld(ctx->iN)) != hipSuccess ||
-      (!ctx->f32 && (dev_alloc(&ctx->d_act[0], S * (size_t)ctx->act_elems) != hipSuccess ||
-                     dev_alloc(&ctx->d_act[1], S * (size_t)ctx->act_elems) != hipSuccess)) ||
-      (ctx->f32 && (dev_alloc(&ctx->d_w32, S * (size_t)pad_ld(ctx->iN)) != hipSuccess ||
-                    dev_alloc(&ctx->d_act32[0], S * (size_t)ctx->act_elems) != hipSuccess ||
-                    dev_alloc(&ctx->d_act32[1], S * (size_t)ctx->act_elems) != hipSuccess)) ||
-      dev_alloc(&ctx->d_ssepart, S * (size_t)ctx->sse_blocks) != hipSuccess ||
-      (ctx->fuse_tail && dev_alloc(&ctx->d_part, S * pslots * dB) != hipSuccess) ||
-      ((ctx->fuse_tail || ctx->f32 || ctx->fused_ok) && dev_alloc(&ctx->d_yhat, S * dB) != hipSuccess))
+  if (!ctx->d_w.alloc(S * (size_t)pad_ld(ctx->iN)) ||
+      (!ctx->f32 && (!ctx->d_act[0].alloc(S * (size_t)ctx->act_elems) || !ctx->d_act[1].alloc(S * (size_t)ctx->act_elems))) ||
+      (ctx->f32 && (!ctx->d_w32.alloc(S * (size_t)pad_ld(ctx->iN)) || !ctx->d_act32[0].alloc(S * (size_t)ctx->act_elems) ||
+                    !ctx->d_act32[1].alloc(S * (size_t)ctx->act_elems))) ||
+      !ctx->d_ssepart.alloc(S * (size_t)ctx->sse_blocks) ||
+      (ctx->fuse_tail && !ctx->d_part.alloc(S * pslots * dB)) ||
+      ((ctx->fuse_tail || ctx->f32 || ctx->fused_ok) && !ctx->d_yhat.alloc(S * dB)))
     return false;
-  dev_free(ctx->d_wsqpart);
   ctx->wsq_blocks = sse_num_blocks(ctx->iN, ctx->num_cu);
-  if (dev_alloc(&ctx->d_wsqpart, S * (size_t)ctx->wsq_blocks) != hipSuccess) return false;
+  if (!ctx->d_wsqpart.alloc(S * (size_t)ctx->wsq_blocks)) return false;
   ctx->fw_slots = slots;
   return true;
 }
@@ -135,8 +132,7 @@ static int32_t infer_setup_common(si_ctx* ctx, const si_layer* layers, int32_t L
     } else {
       const hipMemcpyKind kind = src == SRC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
       ctx->ldP = pad_ld(N);
-      if (dev_alloc(&ctx->d_iswa, (size_t)ctx->ldP) != hipSuccess ||
-          dev_alloc(&ctx->d_iP, (size_t)ctx->ldP * M) != hipSuccess) {
+      if (!ctx->d_iswa.alloc((size_t)ctx->ldP) || !ctx->d_iP.alloc((size_t)ctx->ldP * M)) {
         free_infer(ctx);
         return fail(ctx, SI_ERR_NOMEM, "si_infer_setup: allocation of W_swa / P failed");
       }
@@ -174,18 +170,18 @@ static int32_t infer_setup_common(si_ctx* ctx, const si_layer* layers, int32_t L
   if (ctx->fused_ok) {   // the chain's tile program (64 bytes per 16-feature tile), uploaded once
     std::vector<CgTileD> prog;
     chain_fused_program(ctx->layers.data(), L, ctx->fuse_tail, prog, ctx->cg_start, ctx->cg_count, ctx->cg_chunks);
-    if (dev_alloc(&ctx->d_cgprog, prog.size()) != hipSuccess) {
+    if (!ctx->d_cgprog.alloc(prog.size())) {
       free_infer(ctx);
       return fail(ctx, SI_ERR_NOMEM, "si_infer_setup: device allocation failed");
     }
     SI_HIP(ctx, hipMemcpy(ctx->d_cgprog, prog.data(), prog.size() * sizeof(CgTileD), hipMemcpyHostToDevice));
   }
-  if (dev_alloc(&ctx->d_X, (size_t)in_dim * B) != hipSuccess || dev_alloc(&ctx->d_Y, (size_t)out_dim * B) != hipSuccess ||
-      (ctx->f32 && dev_alloc(&ctx->d_X32, (size_t)pad_ld(std::max<int64_t>((int64_t)in_dim * B, plan.input_spatial ? plan.in_elems * B : 0))) != hipSuccess) ||
-      (ctx->f32 && plan.has_conv && dev_alloc(&ctx->d_wpack32, plan.wpack_elems) != hipSuccess) ||
+  if (!ctx->d_X.alloc((size_t)in_dim * B) || !ctx->d_Y.alloc((size_t)out_dim * B) ||
+      (ctx->f32 && !ctx->d_X32.alloc((size_t)pad_ld(std::max<int64_t>((int64_t)in_dim * B, plan.input_spatial ? plan.in_elems * B : 0)))) ||
+      (ctx->f32 && plan.has_conv && !ctx->d_wpack32.alloc(plan.wpack_elems)) ||
       !alloc_forward(ctx, 1) ||
-      (plan.has_conv && dev_alloc(&ctx->d_wpack, plan.wpack_elems) != hipSuccess) ||
-      (plan.input_spatial && dev_alloc(&ctx->d_Xc, (size_t)plan.in_elems * B) != hipSuccess)) {
+      (plan.has_conv && !ctx->d_wpack.alloc(plan.wpack_elems)) ||
+      (plan.input_spatial && !ctx->d_Xc.alloc((size_t)plan.in_elems * B))) {
     free_infer(ctx);
     return fail(ctx, SI_ERR_NOMEM, "si_infer_setup: device allocation failed");
   }
@@ -268,17 +264,12 @@ int32_t ensure_chains(si_ctx* ctx, int32_t C) {
   }
   if (ctx->chains_cap >= C) return SI_OK;
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  dev_free(ctx->d_zcur);
-  dev_free(ctx->d_zprop);
-  dev_free(ctx->d_lpcur);
-  dev_free(ctx->d_sse);
-  dev_free(ctx->d_nacc);
-  dev_free(ctx->d_steps);
-  dev_free(ctx->d_wsq);
+  for (DevBuf<double>* b : {&ctx->d_zcur, &ctx->d_zprop, &ctx->d_lpcur, &ctx->d_sse, &ctx->d_wsq}) b->reset();
+  ctx->d_nacc.reset();
+  ctx->d_steps.reset();
   ctx->chains_cap = 0;
-  if (dev_alloc(&ctx->d_wsq, (size_t)C) != hipSuccess || dev_alloc(&ctx->d_zcur, (size_t)ctx->iM * C) != hipSuccess || dev_alloc(&ctx->d_zprop, (size_t)ctx->iM * C) != hipSuccess ||
-      dev_alloc(&ctx->d_lpcur, (size_t)C) != hipSuccess || dev_alloc(&ctx->d_sse, (size_t)C) != hipSuccess ||
-      dev_alloc(&ctx->d_nacc, (size_t)C) != hipSuccess || dev_alloc(&ctx->d_steps, (size_t)C) != hipSuccess)
+  if (!ctx->d_wsq.alloc((size_t)C) || !ctx->d_zcur.alloc((size_t)ctx->iM * C) || !ctx->d_zprop.alloc((size_t)ctx->iM * C) ||
+      !ctx->d_lpcur.alloc((size_t)C) || !ctx->d_sse.alloc((size_t)C) || !ctx->d_nacc.alloc((size_t)C) || !ctx->d_steps.alloc((size_t)C))
     return fail(ctx, SI_ERR_NOMEM, "sampler state allocation failed");
   ctx->chains_cap = C;
   return SI_OK;
@@ -398,8 +389,8 @@ int32_t eval_density(si_ctx* ctx, int c0, int nc, const double** yhat_out) {
     // in one buffer with the full-B pitch and ONE tail_sse launch sums them in the usual fixed order: lp is bit-identical.
     // (each under its own null check: si_reconstruct / the streamed output map create stream2 by themselves -- ADVICE r2)
     if (!ctx->stream2) SI_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-    if (!ctx->ev_fork) SI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    if (!ctx->ev_join) SI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+    if (!ctx->ev_fork) SI_HIP(ctx, ctx->ev_fork.try_create());
+    if (!ctx->ev_join) SI_HIP(ctx, ctx->ev_join.try_create());
     const int64_t b1 = ((B / 2 + 127) / 128) * 128;
     SI_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
     SI_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
@@ -593,6 +584,16 @@ int32_t si_logdensity(si_ctx* ctx, const double* Z, int32_t C, double* lp_out) {
   return SI_OK;
 }
 
+// a gradient workspace that could not be allocated in full is dropped whole
+static int32_t drop_grad(si_ctx* ctx) {
+  ctx->d_hs.clear();
+  ctx->d_pidx.clear();
+  ctx->g_scratch = NetScratch();
+  ctx->g_ws32 = SweepF32Ws();
+  for (DevBuf<double>* b : {&ctx->d_delta[0], &ctx->d_delta[1], &ctx->d_gw, &ctx->d_bwpart, &ctx->d_rspart, &ctx->d_ptgpart, &ctx->d_gz}) b->reset();
+  return fail(ctx, SI_ERR_NOMEM, "si_logdensity_grad: workspace allocation failed");
+}
+
 static int32_t ensure_grad(si_ctx* ctx) {
   if (ctx->g_ready) return SI_OK;
   const int64_t B = ctx->B;
@@ -602,75 +603,48 @@ static int32_t ensure_grad(si_ctx* ctx) {
     const NetPlan& p = ctx->plan;
     size_t nb, nr, nw, nd;
     net_scratch_sizes(p, B, ctx->num_cu, &nb, &nr, &nw, &nd);
-    ctx->d_hs.assign(p.L.size(), nullptr);
-    ctx->d_pidx.assign(p.L.size(), nullptr);
+    ctx->d_hs = std::vector<DevBuf<double>>(p.L.size());
+    ctx->d_pidx = std::vector<DevBuf<uint8_t>>(p.L.size());
     bool ok = true;
     for (size_t l = 0; l < p.L.size() && ok; ++l) {
       if (net_grad_fused(p, l))   // Conv + MaxPool as one kernel: a byte index instead of the un-pooled activation
-        ok = dev_alloc(&ctx->d_pidx[l], net_pidx_bytes(p, l, B)) == hipSuccess;
+        ok = ctx->d_pidx[l].alloc(net_pidx_bytes(p, l, B));
       else
-        ok = dev_alloc(&ctx->d_hs[l], (size_t)p.L[l].out_elems * B) == hipSuccess;
+        ok = ctx->d_hs[l].alloc((size_t)p.L[l].out_elems * B);
     }
     ctx->g_scratch.pidx = ctx->d_pidx.data();
-    ok = ok && dev_alloc(&ctx->d_delta[0], (size_t)p.max_elems * B) == hipSuccess &&
-         dev_alloc(&ctx->d_delta[1], (size_t)p.max_elems * B) == hipSuccess &&
-         dev_alloc(&ctx->d_gw, (size_t)pad_ld(ctx->iN)) == hipSuccess && dev_alloc(&ctx->g_scratch.bwpart, nb) == hipSuccess &&
-         dev_alloc(&ctx->g_scratch.rspart, nr) == hipSuccess && dev_alloc(&ctx->g_scratch.wt, nw) == hipSuccess &&
-         dev_alloc(&ctx->g_scratch.dbtmp, nd) == hipSuccess &&
-         dev_alloc(&ctx->d_ptgpart, (size_t)ptg_blocks() * ctx->iM) == hipSuccess && dev_alloc(&ctx->d_gz, (size_t)ctx->iM) == hipSuccess;
-    if (!ok) {
-      for (auto& h : ctx->d_hs) dev_free(h);
-      ctx->d_hs.clear();
-      for (auto& h : ctx->d_pidx) dev_free(h);
-      ctx->d_pidx.clear();
-      ctx->g_scratch.pidx = nullptr;
-      dev_free(ctx->d_delta[0]); dev_free(ctx->d_delta[1]); dev_free(ctx->d_gw); dev_free(ctx->g_scratch.bwpart);
-      dev_free(ctx->g_scratch.rspart); dev_free(ctx->g_scratch.wt); dev_free(ctx->g_scratch.dbtmp); dev_free(ctx->d_ptgpart);
-      dev_free(ctx->d_gz);
-      return fail(ctx, SI_ERR_NOMEM, "si_logdensity_grad: workspace allocation failed");
-    }
+    ok = ok && ctx->d_delta[0].alloc((size_t)p.max_elems * B) && ctx->d_delta[1].alloc((size_t)p.max_elems * B) &&
+         ctx->d_gw.alloc((size_t)pad_ld(ctx->iN)) && ctx->g_scratch.bwpart.alloc(nb) && ctx->g_scratch.rspart.alloc(nr) &&
+         ctx->g_scratch.wt.alloc(nw) && ctx->g_scratch.dbtmp.alloc(nd) && ctx->d_ptgpart.alloc((size_t)ptg_blocks() * ctx->iM) &&
+         ctx->d_gz.alloc((size_t)ctx->iM);
+    if (!ok) return drop_grad(ctx);
     ctx->g_ready = true;
     return SI_OK;
   }
   if (ctx->f32) {   // compute_dtype = SI_F32: the fp32 forward + reverse sweep (kernels_bwd_f32.hip), P' g in fp64
-    ctx->g_ws32 = new SweepF32Ws();
-    const bool ok32 = sweep_f32_alloc(ctx, *ctx->g_ws32, ctx->layers.data(), (int)ctx->layers.size(), ctx->fuse_tail, ctx->iN, ctx->in_dim,
+    const bool ok32 = sweep_f32_alloc(ctx, ctx->g_ws32, ctx->layers.data(), (int)ctx->layers.size(), ctx->fuse_tail, ctx->iN, ctx->in_dim,
                                       ctx->out_dim, B) &&
-                      dev_alloc(&ctx->d_gw, (size_t)pad_ld(ctx->iN)) == hipSuccess &&
-                      dev_alloc(&ctx->d_ptgpart, (size_t)ptg_blocks() * ctx->iM) == hipSuccess && dev_alloc(&ctx->d_gz, (size_t)ctx->iM) == hipSuccess;
-    if (!ok32) {
-      sweep_f32_free(*ctx->g_ws32);
-      delete ctx->g_ws32;
-      ctx->g_ws32 = nullptr;
-      dev_free(ctx->d_gw); dev_free(ctx->d_ptgpart); dev_free(ctx->d_gz);
-      return fail(ctx, SI_ERR_NOMEM, "si_logdensity_grad: workspace allocation failed");
-    }
+                      ctx->d_gw.alloc((size_t)pad_ld(ctx->iN)) && ctx->d_ptgpart.alloc((size_t)ptg_blocks() * ctx->iM) &&
+                      ctx->d_gz.alloc((size_t)ctx->iM);
+    if (!ok32) return drop_grad(ctx);
     ctx->g_ready = true;
     return SI_OK;
   }
   int64_t maxw = 1;
   size_t maxpart = 1;
-  ctx->d_hs.assign(ctx->layers.size(), nullptr);
+  ctx->d_hs = std::vector<DevBuf<double>>(ctx->layers.size());
   bool ok = true;
   for (size_t l = 0; l < ctx->layers.size() && ok; ++l) {
     const si_layer& ly = ctx->layers[l];
     maxw = std::max<int64_t>(maxw, ly.out);
     maxpart = std::max(maxpart, backward_weight_part_elems(ly.out, ly.in, B, ctx->num_cu));
-    ok = dev_alloc(&ctx->d_hs[l], (size_t)ly.out * B) == hipSuccess;
+    ok = ctx->d_hs[l].alloc((size_t)ly.out * B);
   }
   if (ctx->fuse_tail) maxpart = std::max(maxpart, tail_bwd_part_elems(ctx->layers.back().out, ctx->layers.back().in));
-  ok = ok && dev_alloc(&ctx->d_delta[0], (size_t)maxw * B) == hipSuccess &&
-       dev_alloc(&ctx->d_delta[1], (size_t)maxw * B) == hipSuccess &&
-       dev_alloc(&ctx->d_gw, (size_t)pad_ld(ctx->iN)) == hipSuccess && dev_alloc(&ctx->d_bwpart, maxpart) == hipSuccess &&
-       dev_alloc(&ctx->d_rspart, (size_t)rowsum_chunks() * maxw) == hipSuccess &&
-       dev_alloc(&ctx->d_ptgpart, (size_t)ptg_blocks() * ctx->iM) == hipSuccess && dev_alloc(&ctx->d_gz, (size_t)ctx->iM) == hipSuccess;
-  if (!ok) {
-    for (auto& h : ctx->d_hs) dev_free(h);
-    ctx->d_hs.clear();
-    dev_free(ctx->d_delta[0]); dev_free(ctx->d_delta[1]); dev_free(ctx->d_gw); dev_free(ctx->d_bwpart);
-    dev_free(ctx->d_rspart); dev_free(ctx->d_ptgpart); dev_free(ctx->d_gz);
-    return fail(ctx, SI_ERR_NOMEM, "si_logdensity_grad: workspace allocation failed");
-  }
+  ok = ok && ctx->d_delta[0].alloc((size_t)maxw * B) && ctx->d_delta[1].alloc((size_t)maxw * B) &&
+       ctx->d_gw.alloc((size_t)pad_ld(ctx->iN)) && ctx->d_bwpart.alloc(maxpart) && ctx->d_rspart.alloc((size_t)rowsum_chunks() * maxw) &&
+       ctx->d_ptgpart.alloc((size_t)ptg_blocks() * ctx->iM) && ctx->d_gz.alloc((size_t)ctx->iM);
+  if (!ok) return drop_grad(ctx);
   ctx->g_ready = true;
   return SI_OK;
 }
@@ -700,10 +674,10 @@ int32_t si_logdensity_grad(si_ctx* ctx, const double* z, double* lp_out, double*
     // compute_dtype = SI_F32: value and gradient on the fp32 density's own arithmetic (fp32 operands and activations, fp64 head
     // partials / SSE / batch sums; W_swa + P z rounded once), the pull-back P' g and the optional prior term in fp64
     const int64_t d = (int64_t)ctx->out_dim * B;
-    DenseSweepF32 sw{ctx->layers.data(), nl, ctx->fuse_tail, ctx->d_w32, ctx->d_w, ctx->d_X32, ctx->d_Y, ctx->g_ws32, ctx->d_part,
+    DenseSweepF32 sw{ctx->layers.data(), nl, ctx->fuse_tail, ctx->d_w32, ctx->d_w, ctx->d_X32, ctx->d_Y, &ctx->g_ws32, ctx->d_part,
                      ctx->d_ssepart, ctx->d_sse, ctx->sse_blocks, B, N, 1.0 / s2};   // d lp / d yhat = (y - yhat) / sigma^2
     if ((rc = dense_value_and_grad_f32(ctx, ctx->stream, sw)) != SI_OK) return rc;
-    launch_widen_f32_to_f64(ctx->stream, ctx->g_ws32->gw32, N, ctx->d_gw, ctx->num_cu);
+    launch_widen_f32_to_f64(ctx->stream, ctx->g_ws32.gw32, N, ctx->d_gw, ctx->num_cu);
     if (prior) launch_prior_grad(ctx->stream, ctx->d_gw, ctx->d_w, N, 1.0 / (ctx->sigma_p * ctx->sigma_p), ctx->num_cu);
     launch_ptg(ctx->stream, ctx->i_P, ctx->ldP, N, M, ctx->d_gw, ctx->d_ptgpart, ctx->d_gz);
     SI_HIP(ctx, hipGetLastError());
@@ -832,12 +806,8 @@ int32_t si_predict(si_ctx* ctx, const double* Z, int32_t C, const double* Xnew, 
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // run the ordinary forward path on temporary data buffers sized for Bn (the density's own X, Y stay untouched);
   // like the density, up to `wb` samples share one pass of launches (grid.y), within the same workspace cap
-  struct Saved {
-    double *X, *Y, *act0, *act1, *ssepart, *part, *yhat, *Xc;
-    int64_t B, act_elems;
-    int sse_blocks;
-  } sv{ctx->d_X, ctx->d_Y, ctx->d_act[0], ctx->d_act[1], ctx->d_ssepart, ctx->d_part, ctx->d_yhat, ctx->d_Xc,
-       ctx->B, ctx->act_elems, ctx->sse_blocks};
+  const int64_t B_saved = ctx->B, act_elems_saved = ctx->act_elems;
+  const int sse_blocks_saved = ctx->sse_blocks;
   // (with compute_dtype = SI_F32 the predictive forward still runs in fp64: it owns its fp64 workspace below, and the fp64
   //  weights are what K4 writes in either mode -- the fp32 option covers the density / the RWMH samplers)
   const bool f32_saved = ctx->f32;
@@ -847,22 +817,25 @@ int32_t si_predict(si_ctx* ctx, const double* Z, int32_t C, const double* Xnew, 
   const size_t dB = (size_t)ctx->out_dim * (size_t)Bn;
   const double per = 8.0 * (2.0 * (double)act_elems + ((double)ctx->fuse_slots + 1.0) * (double)dB + (double)sse_blocks);
   const size_t wb = (size_t)std::max(1.0, std::min({(double)C, (double)ctx->fw_slots, std::floor(SI_BATCH_BYTES / per)}));
-  double *tX = nullptr, *tY = nullptr, *tA0 = nullptr, *tA1 = nullptr, *tS = nullptr, *tP = nullptr, *tYh = nullptr, *tXc = nullptr;
-  bool ok = dev_alloc(&tX, (size_t)ctx->in_dim * Bn) == hipSuccess && dev_alloc(&tY, dB) == hipSuccess &&
-            (!ctx->plan.input_spatial || dev_alloc(&tXc, (size_t)ctx->plan.in_elems * Bn) == hipSuccess) &&
-            dev_alloc(&tA0, wb * (size_t)act_elems) == hipSuccess && dev_alloc(&tA1, wb * (size_t)act_elems) == hipSuccess &&
-            dev_alloc(&tS, wb * (size_t)sse_blocks) == hipSuccess &&
-            (!ctx->fuse_tail || (dev_alloc(&tP, wb * (size_t)ctx->fuse_slots * dB) == hipSuccess &&
-                                 dev_alloc(&tYh, wb * dB) == hipSuccess));
+  DevBuf<double> tX, tY, tA0, tA1, tS, tP, tYh, tXc;
+  // the temporaries and the density's own buffers change places for the evaluations, and change back
+  auto exchange = [&]() {
+    std::swap(ctx->d_X, tX); std::swap(ctx->d_Y, tY); std::swap(ctx->d_act[0], tA0); std::swap(ctx->d_act[1], tA1);
+    std::swap(ctx->d_ssepart, tS); std::swap(ctx->d_part, tP); std::swap(ctx->d_yhat, tYh); std::swap(ctx->d_Xc, tXc);
+  };
+  bool ok = tX.alloc((size_t)ctx->in_dim * Bn) && tY.alloc(dB) &&
+            (!ctx->plan.input_spatial || tXc.alloc((size_t)ctx->plan.in_elems * Bn)) &&
+            tA0.alloc(wb * (size_t)act_elems) && tA1.alloc(wb * (size_t)act_elems) && tS.alloc(wb * (size_t)sse_blocks) &&
+            (!ctx->fuse_tail || (tP.alloc(wb * (size_t)ctx->fuse_slots * dB) && tYh.alloc(wb * dB)));
   hipError_t e = hipSuccess;
   if (ok) {
     e = hipMemcpyAsync(tX, Xnew, (size_t)ctx->in_dim * Bn * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(tY, 0, dB * sizeof(double), ctx->stream);
     if (e == hipSuccess)
       e = hipMemcpyAsync(ctx->d_zprop, Z, (size_t)ctx->iM * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    ctx->d_X = tX; ctx->d_Y = tY; ctx->d_act[0] = tA0; ctx->d_act[1] = tA1; ctx->d_ssepart = tS; ctx->d_part = tP;
-    ctx->d_yhat = tYh; ctx->B = Bn; ctx->act_elems = act_elems; ctx->sse_blocks = sse_blocks; ctx->d_Xc = tXc;
-    if (ctx->plan.input_spatial) net_input(ctx, ctx->plan, tX, tXc, Bn);
+    exchange();
+    ctx->B = Bn; ctx->act_elems = act_elems; ctx->sse_blocks = sse_blocks;
+    if (ctx->plan.input_spatial) net_input(ctx, ctx->plan, ctx->d_X, ctx->d_Xc, Bn);
     for (int c0 = 0; c0 < C && e == hipSuccess && rc == SI_OK; c0 += (int)wb) {
       const int nc = std::min<int>((int)wb, C - c0);
       const double* yh = nullptr;
@@ -875,13 +848,12 @@ int32_t si_predict(si_ctx* ctx, const double* Z, int32_t C, const double* Xnew, 
       }
       if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the outputs are overwritten by the next batch
     }
-    ctx->d_X = sv.X; ctx->d_Y = sv.Y; ctx->d_act[0] = sv.act0; ctx->d_act[1] = sv.act1; ctx->d_ssepart = sv.ssepart;
-    ctx->d_part = sv.part; ctx->d_yhat = sv.yhat; ctx->B = sv.B; ctx->act_elems = sv.act_elems; ctx->sse_blocks = sv.sse_blocks;
-    ctx->d_Xc = sv.Xc;
+    exchange();
+    ctx->B = B_saved; ctx->act_elems = act_elems_saved; ctx->sse_blocks = sse_blocks_saved;
   }
   ctx->f32 = f32_saved;
   (void)hipStreamSynchronize(ctx->stream);
-  dev_free(tX); dev_free(tY); dev_free(tA0); dev_free(tA1); dev_free(tS); dev_free(tP); dev_free(tYh); dev_free(tXc);
+  for (DevBuf<double>* b : {&tX, &tY, &tA0, &tA1, &tS, &tP, &tYh, &tXc}) b->reset();
   if (!ok) return fail(ctx, SI_ERR_NOMEM, "si_predict: device allocation failed");
   if (rc != SI_OK) return rc;
   if (e != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string("si_predict: ") + hipGetErrorString(e));

@@ -146,8 +146,8 @@ void net_input(Ctx* c, const NetPlan& p, const double* X, double* Xc, int64_t B)
   launch_whcn_to_cwhn(c->stream, X, Xc, p.in_W, p.in_H, p.in_C, p.in_Cp, B);
 }
 
-int32_t net_forward(Ctx* c, const NetPlan& p, const double* w, const double* xin, int64_t B, double* const* outs, double* wpack,
-                    bool pingpong, double** final_out, uint8_t* const* pidx) {
+int32_t net_forward(Ctx* c, const NetPlan& p, const double* w, const double* xin, int64_t B, const DevBuf<double>* outs, double* wpack,
+                    bool pingpong, double** final_out, const DevBuf<uint8_t>* pidx) {
   hipStream_t st = c->stream;
   const double* h = xin;
   size_t executed = 0;
@@ -219,7 +219,7 @@ int32_t net_forward(Ctx* c, const NetPlan& p, const double* w, const double* xin
 // compute_dtype = SI_F32 on a Conv chain: the forward pass of net_forward (ping-pong activations, Conv + 2x2 MaxPool fused where it
 // applies) on fp32 operands -- the conv kernels compiled for float (kernels_conv.hip -DSI_CONV_F32: v_mfma_f32_16x16x4_f32), the
 // Dense layers behind `flatten` on kernels_gemm_f32.hip.  w32: the evaluation's weights rounded once from the fp64 sum (K4).
-int32_t net_forward_f32(Ctx* c, const NetPlan& p, const float* w, const float* xin, int64_t B, float* const* outs, float* wpack,
+int32_t net_forward_f32(Ctx* c, const NetPlan& p, const float* w, const float* xin, int64_t B, const DevBuf<float>* outs, float* wpack,
                         float** final_out) {
   hipStream_t st = c->stream;
   const float* h = xin;
@@ -292,7 +292,7 @@ void net_scratch_sizes(const NetPlan& p, int64_t B, int num_cu, size_t* bwpart, 
   *dbtmp = (size_t)p.max_rows;
 }
 
-int32_t net_backward(Ctx* c, const NetPlan& p, const double* w, const double* xin, int64_t B, double* const* hs, double* g0,
+int32_t net_backward(Ctx* c, const NetPlan& p, const double* w, const double* xin, int64_t B, const DevBuf<double>* hs, double* g0,
                      double* g1, double* gw, const NetScratch& s) {
   hipStream_t st = c->stream;
   double* g = g0;      // gradient with respect to the OUTPUT of the layer being processed (device layout)

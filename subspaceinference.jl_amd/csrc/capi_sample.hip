@@ -20,15 +20,13 @@ extern "C" {
 // moves it into the caller's array R-1 transitions later.  The chain never waits for PCIe.
 static constexpr int SI_WRING = 4;
 
-void free_wstream(si_ctx* ctx) {
-  dev_free(ctx->d_wring);
-  dev_free(ctx->d_accflag);
+static void free_wstream(si_ctx* ctx) {
+  ctx->d_wring.reset();
+  ctx->d_accflag.reset();
   for (int r = 0; r < SI_WRING; ++r) {
-    if (ctx->h_wring[r]) (void)hipHostFree(ctx->h_wring[r]);
-    ctx->h_wring[r] = nullptr;
-    if (ctx->ev_wcomp[r]) (void)hipEventDestroy(ctx->ev_wcomp[r]);
-    if (ctx->ev_wcopy[r]) (void)hipEventDestroy(ctx->ev_wcopy[r]);
-    ctx->ev_wcomp[r] = ctx->ev_wcopy[r] = nullptr;
+    ctx->h_wring[r].reset();
+    ctx->ev_wcomp[r].reset();
+    ctx->ev_wcopy[r].reset();
   }
   ctx->wring_N = 0;
   ctx->wring_C = 0;
@@ -40,11 +38,9 @@ static int32_t ensure_wstream(si_ctx* ctx, int32_t C) {
   if (ctx->wring_N == ctx->iN && ctx->wring_C >= C) return SI_OK;
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   free_wstream(ctx);
-  bool ok = dev_alloc(&ctx->d_wring, need * SI_WRING) == hipSuccess && dev_alloc(&ctx->d_accflag, (size_t)C) == hipSuccess;
+  bool ok = ctx->d_wring.alloc(need * SI_WRING) && ctx->d_accflag.alloc((size_t)C);
   for (int r = 0; r < SI_WRING && ok; ++r)
-    ok = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_wring[r]), (size_t)C * (size_t)ctx->iN * sizeof(double), hipHostMallocDefault) == hipSuccess &&
-         hipEventCreateWithFlags(&ctx->ev_wcomp[r], hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&ctx->ev_wcopy[r], hipEventDisableTiming) == hipSuccess;
+    ok = ctx->h_wring[r].alloc((size_t)C * (size_t)ctx->iN) && ctx->ev_wcomp[r].create() && ctx->ev_wcopy[r].create();
   if (!ok) {
     free_wstream(ctx);
     return fail(ctx, SI_ERR_NOMEM, "si_sample_rwmh_weights: allocation of the weight ring / pinned staging failed");
@@ -67,6 +63,48 @@ static bool chain_loop_applies(const si_ctx* ctx) {
   return 2.0 * (double)ctx->iN * (double)ctx->B <= 3.0e6;
 }
 
+// The common end of the three sampler forms.  `e` is the state of what the form has queued so far.  Z / lp (from d_outZ /
+// d_outlp) and the accept counts come down -- Z and lp through the pinned `stage` where the form hands one in; with W_out the
+// weight samples of the finished chains come from ONE K4 pass over all itr * C samples into a temporary (the kernel
+// si_reconstruct runs: same bits) and a 2-D copy; one synchronisation; the first error is reported; a raised barrier word
+// of the grid loop (grid_status) is one; the accept rates are filled in.
+static int32_t finish_chains(si_ctx* ctx, const char* who, hipError_t e, int64_t itr, int32_t C, double* Z_out, double* lp_out,
+                             double* accept_rate_out, double* W_out, size_t wall_elems, char* stage, const unsigned* grid_status) {
+  const int32_t M = ctx->iM;
+  const int64_t N = ctx->iN, ldw = pad_ld(N);
+  const size_t zbytes = Z_out ? (size_t)M * itr * C * sizeof(double) : 0, lbytes = lp_out ? (size_t)itr * C * sizeof(double) : 0;
+  std::vector<int64_t> nacc((size_t)C);
+  if (e == hipSuccess && Z_out) e = hipMemcpyAsync(stage ? (void*)stage : (void*)Z_out, ctx->d_outZ, zbytes, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && lp_out)
+    e = hipMemcpyAsync(stage ? (void*)(stage + zbytes) : (void*)lp_out, ctx->d_outlp, lbytes, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(nacc.data(), ctx->d_nacc, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
+  DevBuf<double> dW;
+  if (e == hipSuccess && W_out) {   // src/space_inference.jl:125 for every sample of every chain
+    if (!dW.alloc(wall_elems)) e = hipErrorOutOfMemory;   // (ldw * itr * C: the caller has held it to its 512 MB gate)
+    if (e == hipSuccess) {
+      ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * (double)itr * C, (double)N * (M + 1 + (double)itr * C) * 8.0);
+      launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, ctx->d_outZ, (int32_t)(itr * C), dW, ldw, ctx->num_cu);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+      e = hipMemcpy2DAsync(W_out, (size_t)N * sizeof(double), dW, (size_t)ldw * sizeof(double), (size_t)N * sizeof(double),
+                           (size_t)itr * C, hipMemcpyDeviceToHost, ctx->stream);
+  }
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  dW.reset();
+  if (e != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  if (e2 != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e2));
+  if (stage) {
+    if (Z_out) std::memcpy(Z_out, stage, zbytes);
+    if (lp_out) std::memcpy(lp_out, stage + zbytes, lbytes);
+  }
+  if (grid_status && *grid_status != 0)
+    return fail(ctx, SI_ERR_HIP, std::string(who) + ": the grid barrier of the device-resident loop timed out (its workgroups were not all resident: "
+                                 "is another process holding compute units of this GPU?); si_set_chain_loop(ctx, 2) runs the launch-per-step loop");
+  accept_rates(nacc, itr, accept_rate_out);
+  return SI_OK;
+}
+
 static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, double sigma_z, uint64_t seed, int32_t chain_id0,
                                 int32_t nchains, double* Z_out, double* lp_out, double* accept_rate_out, double* W_out) {
   CHECK_CTX(ctx);
@@ -82,21 +120,8 @@ static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, doubl
   if (rc != SI_OK) return rc;
   if (W_out && (rc = ensure_wstream(ctx, C)) != SI_OK) return rc;
   // the device-side output arrays stay with the ctx (grown on demand, released with the inference set-up)
-  {
-    const size_t needZ = (size_t)M * itr * C, needlp = (size_t)itr * C;
-    if (ctx->outZ_cap < needZ) {
-      dev_free(ctx->d_outZ);
-      ctx->outZ_cap = 0;
-      if (dev_alloc(&ctx->d_outZ, needZ) != hipSuccess) return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
-      ctx->outZ_cap = needZ;
-    }
-    if (ctx->outlp_cap < needlp) {
-      dev_free(ctx->d_outlp);
-      ctx->outlp_cap = 0;
-      if (dev_alloc(&ctx->d_outlp, needlp) != hipSuccess) return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
-      ctx->outlp_cap = needlp;
-    }
-  }
+  if (!ctx->d_outZ.reserve((size_t)M * itr * C) || !ctx->d_outlp.reserve((size_t)itr * C))
+    return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
   double* const dZ = ctx->d_outZ;
   double* const dlp = ctx->d_outlp;
   const double d = (double)ctx->out_dim * (double)ctx->B;
@@ -124,30 +149,7 @@ static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, doubl
         ProfScope ps(ctx, SI_K_RWMH, fl, 0.0);
         launch_chain_loop(ctx->stream, a, C, lds);
       }
-      hipError_t e = hipGetLastError();
-      std::vector<int64_t> nacc((size_t)C);
-      if (e == hipSuccess && Z_out) e = hipMemcpyAsync(Z_out, dZ, (size_t)M * itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess && lp_out) e = hipMemcpyAsync(lp_out, dlp, (size_t)itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(nacc.data(), ctx->d_nacc, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
-      double* dW = nullptr;
-      if (e == hipSuccess && W_out) {   // src/space_inference.jl:125 for every sample of every chain
-        if (dev_alloc(&dW, wall_elems) != hipSuccess) e = hipErrorOutOfMemory;
-        if (e == hipSuccess) {
-          ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * (double)itr * C, (double)N * (M + 1 + (double)itr * C) * 8.0);
-          launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, dZ, (int32_t)(itr * C), dW, ldw, ctx->num_cu);
-          e = hipGetLastError();
-        }
-        if (e == hipSuccess)
-          e = hipMemcpy2DAsync(W_out, (size_t)N * sizeof(double), dW, (size_t)ldw * sizeof(double), (size_t)N * sizeof(double),
-                               (size_t)itr * C, hipMemcpyDeviceToHost, ctx->stream);
-      }
-      const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-      dev_free(dW);
-      if (e != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-      if (e2 != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e2));
-      if (accept_rate_out)
-        for (int c = 0; c < C; ++c) accept_rate_out[c] = itr > 1 ? (double)nacc[(size_t)c] / (double)(itr - 1) : 0.0;
-      return SI_OK;
+      return finish_chains(ctx, who, hipGetLastError(), itr, C, Z_out, lp_out, accept_rate_out, W_out, wall_elems, nullptr, nullptr);
     }
   }
   // ---- K6 as a persistent loop over a GRID of workgroups (kernels_chain_grid.hip): a narrow chain too large for one
@@ -203,11 +205,11 @@ static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, doubl
         if (lds_spec > (size_t)160 * 1024 - 256) sk = nullptr;
       }
       if (sk && (ctx->spec_chains < C || ctx->spec_fo != sk->fo_total)) {
-        dev_free(ctx->d_specw);
-        dev_free(ctx->d_specy);
+        ctx->d_specw.reset();
+        ctx->d_specy.reset();
         ctx->spec_chains = 0;
-        if (dev_alloc(&ctx->d_specw, (size_t)4 * (size_t)sk->fo_total * (size_t)C) != hipSuccess ||
-            dev_alloc(&ctx->d_specy, (size_t)2 * (size_t)ctx->out_dim * (size_t)ctx->B * (size_t)C) != hipSuccess)
+        if (!ctx->d_specw.alloc((size_t)4 * (size_t)sk->fo_total * (size_t)C) ||
+            !ctx->d_specy.alloc((size_t)2 * (size_t)ctx->out_dim * (size_t)ctx->B * (size_t)C))
           return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": allocation failed");
         // (the padding elements of the fragment-ordered vectors are never written by K4: they must be finite)
         if (hipMemsetAsync(ctx->d_specw, 0, (size_t)4 * (size_t)sk->fo_total * (size_t)C * sizeof(double), ctx->stream) != hipSuccess)
@@ -216,9 +218,8 @@ static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, doubl
         ctx->spec_fo = sk->fo_total;
       }
       if (sk && ctx->specperm_for != (const void*)sk) {
-        dev_free(ctx->d_specperm);
         ctx->specperm_for = nullptr;
-        if (dev_alloc(&ctx->d_specperm, (size_t)N) != hipSuccess) return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": allocation failed");
+        if (!ctx->d_specperm.alloc((size_t)N)) return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": allocation failed");
         int* pp = ctx->d_specperm;
         void* pargs[] = {&pp};
         if (hipModuleLaunchKernel(sk->perm, (unsigned)((sk->max_wn + 255) / 256), 1, 1, 256, 1, 1, 0, ctx->stream, pargs, nullptr) != hipSuccess)
@@ -228,12 +229,7 @@ static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, doubl
     }
     const size_t sync_lines = sk ? (size_t)8 * (size_t)C + 1 : (size_t)C + 1;   // (the specialised loop shards each chain's counter over 8 lines)
     if (nb != 0) {
-      if ((size_t)ctx->gridsync_chains < sync_lines) {
-        dev_free(ctx->d_gridsync);
-        ctx->gridsync_chains = 0;
-        if (dev_alloc(&ctx->d_gridsync, (size_t)32 * sync_lines) != hipSuccess) return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": allocation failed");
-        ctx->gridsync_chains = (int)sync_lines;
-      }
+      if (!ctx->d_gridsync.reserve((size_t)32 * sync_lines)) return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": allocation failed");
       a.swa = ctx->i_swa; a.P = ctx->i_P; a.X = ctx->d_X; a.Y = ctx->d_Y;
       a.wbuf = ctx->d_w; a.w_stride = ldw;
       a.ybuf = ctx->d_yhat; a.y_stride = (int64_t)ctx->out_dim * ctx->B;
@@ -250,7 +246,7 @@ static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, doubl
           sa.wbuf = ctx->d_specw; sa.w_stride = sk->fo_total;
           sa.ybuf = ctx->d_specy; sa.y_stride = a.y_stride;
           sa.cnt = a.cnt; sa.status = a.status;
-          sa.Z_out = dZ; sa.lp_out = dlp; sa.nacc_out = (long long*)ctx->d_nacc;
+          sa.Z_out = dZ; sa.lp_out = dlp; sa.nacc_out = (long long*)ctx->d_nacc.get();
           sa.ldP = a.ldP; sa.itr = itr; sa.seed = seed; sa.sigma_z = sigma_z; sa.c0 = c0; sa.sigma2 = s2;
           sa.N = (int)N; sa.M = M; sa.G = a.G; sa.B = (int)ctx->B; sa.chain_id0 = chain_id0; sa.nblocks = ctx->sse_blocks;
           void* gargs[] = {&sa};
@@ -260,53 +256,15 @@ static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, doubl
           e = launch_chain_grid(ctx->stream, a, nb, C, lds);
         }
       }
-      std::vector<int64_t> nacc((size_t)C);
       unsigned status = 0;
       if (e == hipSuccess) e = hipMemcpyAsync(&status, a.status, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
       // the samples and lp go through pinned staging: a device-to-host copy straight into the caller's array pins its pages on the
       // fly, and for an array nobody has touched yet (np.empty, Matrix{Float64}(undef, ...)) that costs ~9 us per page -- 7 ms for the
       // 3.4 MB of a 20 000-transition chain, 0.35 us per transition of a 9.8 us loop
       const size_t zbytes = Z_out ? (size_t)M * itr * C * sizeof(double) : 0, lbytes = lp_out ? (size_t)itr * C * sizeof(double) : 0;
-      bool staged = zbytes + lbytes >= ((size_t)128 << 10) && zbytes + lbytes <= ((size_t)128 << 20);
-      if (staged && ctx->h_outpin_cap < zbytes + lbytes) {
-        if (ctx->h_outpin) (void)hipHostFree(ctx->h_outpin);
-        ctx->h_outpin = nullptr;
-        ctx->h_outpin_cap = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&ctx->h_outpin), zbytes + lbytes, hipHostMallocDefault) == hipSuccess)
-          ctx->h_outpin_cap = zbytes + lbytes;
-        else
-          staged = false;   // (the direct copy is always possible)
-      }
-      if (e == hipSuccess && Z_out) e = hipMemcpyAsync(staged ? (void*)ctx->h_outpin : (void*)Z_out, dZ, zbytes, hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess && lp_out)
-        e = hipMemcpyAsync(staged ? (void*)(ctx->h_outpin + zbytes) : (void*)lp_out, dlp, lbytes, hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(nacc.data(), ctx->d_nacc, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
-      double* dW = nullptr;
-      if (e == hipSuccess && W_out) {   // src/space_inference.jl:125 for every sample of every chain (one K4 pass, as above)
-        if (dev_alloc(&dW, wall_elems) != hipSuccess) e = hipErrorOutOfMemory;
-        if (e == hipSuccess) {
-          ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * (double)itr * C, (double)N * (M + 1 + (double)itr * C) * 8.0);
-          launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, dZ, (int32_t)(itr * C), dW, ldw, ctx->num_cu);
-          e = hipGetLastError();
-        }
-        if (e == hipSuccess)
-          e = hipMemcpy2DAsync(W_out, (size_t)N * sizeof(double), dW, (size_t)ldw * sizeof(double), (size_t)N * sizeof(double),
-                               (size_t)itr * C, hipMemcpyDeviceToHost, ctx->stream);
-      }
-      const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-      dev_free(dW);
-      if (e != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-      if (e2 != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e2));
-      if (staged) {
-        if (Z_out) std::memcpy(Z_out, ctx->h_outpin, zbytes);
-        if (lp_out) std::memcpy(lp_out, ctx->h_outpin + zbytes, lbytes);
-      }
-      if (status != 0)
-        return fail(ctx, SI_ERR_HIP, std::string(who) + ": the grid barrier of the device-resident loop timed out (its workgroups were not all resident: "
-                                     "is another process holding compute units of this GPU?); si_set_chain_loop(ctx, 2) runs the launch-per-step loop");
-      if (accept_rate_out)
-        for (int c = 0; c < C; ++c) accept_rate_out[c] = itr > 1 ? (double)nacc[(size_t)c] / (double)(itr - 1) : 0.0;
-      return SI_OK;
+      const bool staged = zbytes + lbytes >= ((size_t)128 << 10) && zbytes + lbytes <= ((size_t)128 << 20) &&
+                          ctx->h_outpin.reserve(zbytes + lbytes);   // (the direct copy is always possible)
+      return finish_chains(ctx, who, e, itr, C, Z_out, lp_out, accept_rate_out, W_out, wall_elems, staged ? ctx->h_outpin.get() : nullptr, &status);
     }
   }
   {
@@ -383,20 +341,7 @@ static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, doubl
     if (rc != SI_OK) return rc;
     return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
   }
-  e = hipGetLastError();
-  std::vector<int64_t> nacc((size_t)C);
-  if (e == hipSuccess && Z_out)
-    e = hipMemcpyAsync(Z_out, dZ, (size_t)M * itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && lp_out)
-    e = hipMemcpyAsync(lp_out, dlp, (size_t)itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(nacc.data(), ctx->d_nacc, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
-  hipError_t e2 = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-  if (e2 != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e2));
-  if (accept_rate_out)
-    for (int c = 0; c < C; ++c) accept_rate_out[c] = itr > 1 ? (double)nacc[(size_t)c] / (double)(itr - 1) : 0.0;
-  return SI_OK;
+  return finish_chains(ctx, who, hipGetLastError(), itr, C, Z_out, lp_out, accept_rate_out, nullptr, 0, nullptr, nullptr);
 }
 
 int32_t si_sample_rwmh(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, int32_t chain_id0, int32_t nchains,
@@ -444,12 +389,11 @@ int32_t si_rwmh_begin(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, i
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   int32_t rc = ensure_chains(ctx, nchains);
   if (rc != SI_OK) return rc;
-  dev_free(ctx->sw_Z);
-  dev_free(ctx->sw_lp);
-  if (dev_alloc(&ctx->sw_Z, (size_t)ctx->iM * itr * nchains) != hipSuccess ||
-      dev_alloc(&ctx->sw_lp, (size_t)itr * nchains) != hipSuccess) {
-    dev_free(ctx->sw_Z);
-    dev_free(ctx->sw_lp);
+  ctx->sw_Z.reset();
+  ctx->sw_lp.reset();
+  if (!ctx->sw_Z.alloc((size_t)ctx->iM * itr * nchains) || !ctx->sw_lp.alloc((size_t)itr * nchains)) {
+    ctx->sw_Z.reset();
+    ctx->sw_lp.reset();
     return fail(ctx, SI_ERR_NOMEM, "si_rwmh_begin: output allocation failed");
   }
   ctx->sw_itr = itr; ctx->sw_sigma_z = sigma_z; ctx->sw_seed = seed; ctx->sw_chain0 = chain_id0; ctx->sw_C = nchains;
@@ -512,8 +456,8 @@ int32_t si_rwmh_abort(si_ctx* ctx) {
   CHECK_CTX(ctx);
   BIND(ctx);
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  dev_free(ctx->sw_Z);
-  dev_free(ctx->sw_lp);
+  ctx->sw_Z.reset();
+  ctx->sw_lp.reset();
   ctx->sw_evaluated = false;
   ctx->sw_next = ctx->sw_itr = 0;
   return SI_OK;
@@ -531,10 +475,9 @@ int32_t si_rwmh_end(si_ctx* ctx, double* Z_out, double* lp_out, double* accept_r
   if (lp_out) SI_HIP(ctx, hipMemcpyAsync(lp_out, ctx->sw_lp, (size_t)itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipMemcpyAsync(nacc.data(), ctx->d_nacc, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  dev_free(ctx->sw_Z);
-  dev_free(ctx->sw_lp);
-  if (accept_rate_out)
-    for (int c = 0; c < C; ++c) accept_rate_out[c] = itr > 1 ? (double)nacc[(size_t)c] / (double)(itr - 1) : 0.0;
+  ctx->sw_Z.reset();
+  ctx->sw_lp.reset();
+  accept_rates(nacc, itr, accept_rate_out);
   return SI_OK;
 }
 
@@ -553,41 +496,30 @@ int32_t si_reconstruct(si_ctx* ctx, const double* Z, int64_t C, double* W_out) {
   // samples per pipeline stage: ~32 MB of output, at most 64 samples, and at least four stages when C allows it
   const int64_t group_cap = std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)32 << 20) / (N * 8)));   // sizes the buffers once per N
   const int64_t group = std::max<int64_t>(1, std::min<int64_t>((C + 3) / 4, group_cap));
-  hipEvent_t ev_comp[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+  Event ev_comp[2], ev_copy[2];
   hipError_t e = hipSuccess;
   if (!ctx->stream2) e = hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking);
-  if (e == hipSuccess && (ctx->d_stage_cap < (size_t)ldw * (size_t)group_cap || ctx->d_zstage_cap < (size_t)M * (size_t)group_cap)) {
+  // (the last buffer of each group tells whether all of the group are there and large enough)
+  if (e == hipSuccess && (ctx->d_stage[1].size() < (size_t)ldw * (size_t)group_cap || ctx->d_zstage[1].size() < (size_t)M * (size_t)group_cap)) {
     (void)hipStreamSynchronize(ctx->stream);
     for (int b = 0; b < 2; ++b) {
-      dev_free(ctx->d_stage[b]);
-      dev_free(ctx->d_zstage[b]);
-      ctx->d_stage[b] = ctx->d_zstage[b] = nullptr;
+      ctx->d_stage[b].reset();
+      ctx->d_zstage[b].reset();
     }
-    ctx->d_stage_cap = ctx->d_zstage_cap = 0;
     for (int b = 0; b < 2 && e == hipSuccess; ++b)
-      if (dev_alloc(&ctx->d_stage[b], (size_t)ldw * group_cap) != hipSuccess || dev_alloc(&ctx->d_zstage[b], (size_t)M * group_cap) != hipSuccess)
-        e = hipErrorOutOfMemory;
-    if (e == hipSuccess) {
-      ctx->d_stage_cap = (size_t)ldw * (size_t)group_cap;
-      ctx->d_zstage_cap = (size_t)M * (size_t)group_cap;
-    }
+      if (!ctx->d_stage[b].alloc((size_t)ldw * group_cap) || !ctx->d_zstage[b].alloc((size_t)M * group_cap)) e = hipErrorOutOfMemory;
+    if (e != hipSuccess) ctx->d_stage[1].reset(), ctx->d_zstage[1].reset();
   }
-  double* const* dW = ctx->d_stage;
-  double* const* dZ = ctx->d_zstage;
-  if (e == hipSuccess && ctx->h_stage_cap < (size_t)N * (size_t)group_cap) {   // the staging buffers stay with the context
-    for (int b = 0; b < 2; ++b) {
-      if (ctx->h_stage[b]) (void)hipHostFree(ctx->h_stage[b]);
-      ctx->h_stage[b] = nullptr;
-    }
-    ctx->h_stage_cap = 0;
-    for (int b = 0; b < 2 && e == hipSuccess; ++b)
-      e = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_stage[b]), (size_t)N * group_cap * sizeof(double), hipHostMallocDefault);
-    if (e == hipSuccess) ctx->h_stage_cap = (size_t)N * (size_t)group_cap;
+  const DevBuf<double>* dW = ctx->d_stage;
+  const DevBuf<double>* dZ = ctx->d_zstage;
+  if (e == hipSuccess && ctx->h_stage[1].size() < (size_t)N * (size_t)group_cap) {   // the staging buffers stay with the context
+    for (int b = 0; b < 2; ++b) ctx->h_stage[b].reset();
+    for (int b = 0; b < 2 && e == hipSuccess; ++b) e = ctx->h_stage[b].try_alloc((size_t)N * group_cap);
   }
-  double* const* hp = ctx->h_stage;
+  const PinBuf<double>* hp = ctx->h_stage;
   for (int b = 0; b < 2 && e == hipSuccess; ++b) {
-    e = hipEventCreateWithFlags(&ev_comp[b], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_copy[b], hipEventDisableTiming);
+    e = ev_comp[b].try_create();
+    if (e == hipSuccess) e = ev_copy[b].try_create();
   }
   auto drain = [&](int64_t g) {   // group g has been DMA'd into its staging buffer: move it into the caller's array
     const int b = (int)(g & 1);
@@ -619,10 +551,6 @@ int32_t si_reconstruct(si_ctx* ctx, const double* Z, int64_t C, double* W_out) {
   if (e == hipSuccess) e = drain(ngroups - 1);
   (void)hipStreamSynchronize(ctx->stream2);
   (void)hipStreamSynchronize(ctx->stream);
-  for (int b = 0; b < 2; ++b) {
-    if (ev_comp[b]) (void)hipEventDestroy(ev_comp[b]);
-    if (ev_copy[b]) (void)hipEventDestroy(ev_copy[b]);
-  }
   if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? SI_ERR_NOMEM : SI_ERR_HIP, std::string("si_reconstruct: ") + hipGetErrorString(e));
   return SI_OK;
 }

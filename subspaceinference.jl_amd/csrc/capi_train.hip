@@ -11,15 +11,6 @@
 
 #include "si_internal.h"
 
-#ifdef SI_DEV_KNOBS   // development build: the library's own buffers through the guard-page allocator (guard_alloc.hip; SI_GUARD_ALLOC=end|begin)
-namespace si {
-hipError_t guard_malloc(void** out, size_t bytes);
-hipError_t guard_free(void* p);
-}
-#define hipMalloc(p, n) si::guard_malloc((void**)(p), (n))
-#define hipFree(p) si::guard_free((void*)(p))
-#endif
-
 namespace si {
 
 __global__ __launch_bounds__(256) void gather_cols_kernel(const double* __restrict__ src, int rows, const int64_t* __restrict__ idx,
@@ -91,47 +82,12 @@ static int grid_for(int64_t n, int num_cu) {
   return (int)(b < 1 ? 1 : b);
 }
 
-template <typename T>
-static bool alloc(T** p, size_t count) {
-  *p = nullptr;
-  return hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T)) == hipSuccess;
-}
-template <typename T>
-static void release(T*& p) {
-  if (p) (void)hipFree((void*)p);
-  p = nullptr;
-}
-
 void free_train(Ctx* c) {
-  TrainState* t = c->train;
-  if (!t) return;
-  release(t->X); release(t->Y); release(t->Xb); release(t->Yb); release(t->idx); release(t->w32); release(t->m32);
-  release(t->v32); release(t->w64); release(t->gw); release(t->delta[0]); release(t->delta[1]); release(t->bwpart);
-  release(t->rspart); release(t->ssepart); release(t->sse); release(t->part); release(t->Xc); release(t->wpack);
-  release(t->scratch.bwpart); release(t->scratch.rspart); release(t->scratch.wt); release(t->scratch.dbtmp);
-  for (auto& h : t->hs) release(h);
-  release(t->X32); release(t->Xb32);
-  if (t->ws32) {
-    sweep_f32_free(*t->ws32);
-    delete t->ws32;
-    t->ws32 = nullptr;
-  }
-  for (auto& h : t->pidx) release(h);
-  for (int b = 0; b < 2; ++b) {
-    if (t->idx_pin[b]) (void)hipHostFree(t->idx_pin[b]);
-    if (t->idx_ev[b]) (void)hipEventDestroy(t->idx_ev[b]);
-  }
-  delete t;
+  delete c->train;
   c->train = nullptr;
 }
 
 // ---- the fp32 forward + reverse sweep shared by the training step and si_logdensity_grad (compute_dtype = SI_F32) --------------
-void sweep_f32_free(SweepF32Ws& ws) {
-  for (auto& h : ws.hs32) release(h);
-  ws.hs32.clear();
-  release(ws.delta32[0]); release(ws.delta32[1]); release(ws.gw32); release(ws.wt32); release(ws.zero32); release(ws.part32);
-  release(ws.rspart64); release(ws.tailpart64); release(ws.yhat64);
-}
 bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const si_layer* layers, int L, bool fuse_tail, int64_t N, int32_t in_dim, int32_t out_dim,
                      int64_t Bmax) {
   size_t maxpart32 = 1, maxwt = 1, maxin = (size_t)in_dim, maxw = 1;
@@ -142,15 +98,15 @@ bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const si_layer* layers, int L, bo
     maxw = std::max(maxw, (size_t)layers[l].out);
   }
   const size_t wide = std::max(maxin, maxw);
-  ws.hs32.assign((size_t)L, nullptr);
-  bool ok = alloc(&ws.delta32[0], maxw * (size_t)Bmax) && alloc(&ws.delta32[1], maxw * (size_t)Bmax) && alloc(&ws.gw32, (size_t)pad_ld(N)) &&
-            alloc(&ws.wt32, maxwt) && alloc(&ws.zero32, wide) && alloc(&ws.part32, maxpart32) &&
-            alloc(&ws.rspart64, rowsum_f32_part_elems((int)wide)) && alloc(&ws.yhat64, (size_t)out_dim * (size_t)Bmax) &&
-            (!fuse_tail || alloc(&ws.tailpart64, tail_bwd_f32_part_elems(layers[L - 1].out, layers[L - 1].in)));
+  ws.hs32 = std::vector<DevBuf<float>>((size_t)L);
+  bool ok = ws.delta32[0].alloc(maxw * (size_t)Bmax) && ws.delta32[1].alloc(maxw * (size_t)Bmax) && ws.gw32.alloc((size_t)pad_ld(N)) &&
+            ws.wt32.alloc(maxwt) && ws.zero32.alloc(wide) && ws.part32.alloc(maxpart32) &&
+            ws.rspart64.alloc(rowsum_f32_part_elems((int)wide)) && ws.yhat64.alloc((size_t)out_dim * (size_t)Bmax) &&
+            (!fuse_tail || ws.tailpart64.alloc(tail_bwd_f32_part_elems(layers[L - 1].out, layers[L - 1].in)));
   for (int l = 0; l < L && ok; ++l)   // (a fused head's own output lives in yhat64)
-    if (!(fuse_tail && l == L - 1)) ok = alloc(&ws.hs32[(size_t)l], (size_t)layers[l].out * (size_t)Bmax);
+    if (!(fuse_tail && l == L - 1)) ok = ws.hs32[(size_t)l].alloc((size_t)layers[l].out * (size_t)Bmax);
   if (ok) ok = hipMemsetAsync(ws.zero32, 0, wide * sizeof(float), ctx->stream) == hipSuccess;
-  if (!ok) sweep_f32_free(ws);
+  if (!ok) ws = SweepF32Ws();
   return ok;
 }
 
@@ -278,37 +234,33 @@ static int32_t train_setup_impl(si_ctx* ctx, const si_layer* layers, int32_t L, 
   t->f32 = f32;
   if (f32 && fuse_tail)   // (w32 is 256-byte aligned: a layer's W is 16-byte aligned iff w_off % 4 == 0)
     t->fuse_slots = std::max(t->fuse_slots, dense_f32_fused_slots(layers[L - 2].out, layers[L - 2].in, layers[L - 2].w_off % 4 == 0));
-  t->hs.assign((size_t)L, nullptr);
+  t->hs = std::vector<DevBuf<double>>((size_t)L);
   t->plan = plan;
   size_t nb = 1, nr = 1, nw = 1, nd = 1;
   if (plan.has_conv) net_scratch_sizes(plan, batch_max, ctx->num_cu, &nb, &nr, &nw, &nd);
-  bool ok = (!plan.has_conv || (alloc(&t->wpack, plan.wpack_elems) && alloc(&t->scratch.bwpart, nb) && alloc(&t->scratch.rspart, nr) &&
-                                alloc(&t->scratch.wt, nw) && alloc(&t->scratch.dbtmp, nd))) &&
-            (!plan.input_spatial || alloc(&t->Xc, (size_t)plan.in_elems * batch_max)) &&
-            (f32 || (alloc(&t->X, (size_t)in_dim * B_total) && alloc(&t->Xb, (size_t)in_dim * batch_max))) &&
-            alloc(&t->Y, (size_t)out_dim * B_total) && alloc(&t->Yb, (size_t)out_dim * batch_max) &&
-            alloc(&t->idx, (size_t)batch_max) &&
-            hipHostMalloc((void**)&t->idx_pin[0], (size_t)batch_max * sizeof(int64_t), hipHostMallocDefault) == hipSuccess &&
-            hipHostMalloc((void**)&t->idx_pin[1], (size_t)batch_max * sizeof(int64_t), hipHostMallocDefault) == hipSuccess &&
-            hipEventCreateWithFlags(&t->idx_ev[0], hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&t->idx_ev[1], hipEventDisableTiming) == hipSuccess &&
-            alloc(&t->w32, (size_t)N) && alloc(&t->m32, (size_t)N) &&
-            alloc(&t->v32, (size_t)N) && alloc(&t->w64, (size_t)pad_ld(N)) && alloc(&t->gw, (size_t)pad_ld(N)) &&
-            (f32 || (alloc(&t->delta[0], (size_t)maxw * batch_max) && alloc(&t->delta[1], (size_t)maxw * batch_max) &&
-                     alloc(&t->bwpart, maxpart) && alloc(&t->rspart, (size_t)rowsum_chunks() * maxw))) &&
-            alloc(&t->ssepart, (size_t)t->sse_blocks) && alloc(&t->sse, 1) &&
-            (!fuse_tail || alloc(&t->part, (size_t)t->fuse_slots * out_dim * batch_max));
-  t->pidx.assign((size_t)L, nullptr);
-  if (f32 && ok) {
-    t->ws32 = new SweepF32Ws();
-    ok = alloc(&t->X32, (size_t)in_dim * B_total) && alloc(&t->Xb32, (size_t)in_dim * batch_max) &&
-         sweep_f32_alloc(ctx, *t->ws32, layers, L, fuse_tail, N, in_dim, out_dim, batch_max);
-  }
+  bool ok = (!plan.has_conv || (t->wpack.alloc(plan.wpack_elems) && t->scratch.bwpart.alloc(nb) && t->scratch.rspart.alloc(nr) &&
+                                t->scratch.wt.alloc(nw) && t->scratch.dbtmp.alloc(nd))) &&
+            (!plan.input_spatial || t->Xc.alloc((size_t)plan.in_elems * batch_max)) &&
+            (f32 || (t->X.alloc((size_t)in_dim * B_total) && t->Xb.alloc((size_t)in_dim * batch_max))) &&
+            t->Y.alloc((size_t)out_dim * B_total) && t->Yb.alloc((size_t)out_dim * batch_max) &&
+            t->idx.alloc((size_t)batch_max) &&
+            t->idx_pin[0].alloc((size_t)batch_max) && t->idx_pin[1].alloc((size_t)batch_max) &&
+            t->idx_ev[0].create() && t->idx_ev[1].create() &&
+            t->w32.alloc((size_t)N) && t->m32.alloc((size_t)N) &&
+            t->v32.alloc((size_t)N) && t->w64.alloc((size_t)pad_ld(N)) && t->gw.alloc((size_t)pad_ld(N)) &&
+            (f32 || (t->delta[0].alloc((size_t)maxw * batch_max) && t->delta[1].alloc((size_t)maxw * batch_max) &&
+                     t->bwpart.alloc(maxpart) && t->rspart.alloc((size_t)rowsum_chunks() * maxw))) &&
+            t->ssepart.alloc((size_t)t->sse_blocks) && t->sse.alloc(1) &&
+            (!fuse_tail || t->part.alloc((size_t)t->fuse_slots * out_dim * batch_max));
+  t->pidx = std::vector<DevBuf<uint8_t>>((size_t)L);
+  if (f32 && ok)
+    ok = t->X32.alloc((size_t)in_dim * B_total) && t->Xb32.alloc((size_t)in_dim * batch_max) &&
+         sweep_f32_alloc(ctx, t->ws32, layers, L, fuse_tail, N, in_dim, out_dim, batch_max);
   for (int l = 0; l < L && ok && !f32; ++l) {
     if (plan.has_conv && net_grad_fused(plan, (size_t)l))   // Conv + MaxPool as one kernel: a byte index instead of the activation
-      ok = alloc(&t->pidx[(size_t)l], net_pidx_bytes(plan, (size_t)l, batch_max));
+      ok = t->pidx[(size_t)l].alloc(net_pidx_bytes(plan, (size_t)l, batch_max));
     else
-      ok = alloc(&t->hs[(size_t)l], (size_t)plan.L[(size_t)l].out_elems * batch_max);
+      ok = t->hs[(size_t)l].alloc((size_t)plan.L[(size_t)l].out_elems * batch_max);
   }
   t->scratch.pidx = t->pidx.data();
   if (!ok) {
@@ -320,21 +272,21 @@ static int32_t train_setup_impl(si_ctx* ctx, const si_layer* layers, int32_t L, 
     // the caller's type differs (Float32 -> Float64 is exact; Float64 -> Float32 rounds once, as `Float32.(X)` would)
     const size_t nx = (size_t)in_dim * B_total, ny = (size_t)out_dim * B_total;
     const size_t esz = data_dtype == SI_F32 ? 4 : 8;
-    void* stage = nullptr;
+    DevBuf<char> stage;
     const bool x_conv = (data_dtype == SI_F32) != f32, y_conv = data_dtype == SI_F32;
-    if ((x_conv || y_conv) && hipMalloc(&stage, std::max(nx, ny) * esz) != hipSuccess) {
+    if ((x_conv || y_conv) && !stage.alloc(std::max(nx, ny) * esz)) {
       free_train(ctx);
       return fail(ctx, SI_ERR_NOMEM, "si_train_setup: device allocation failed");
     }
     hipError_t e = hipSuccess;
     const int gx = grid_for((int64_t)nx, ctx->num_cu), gy = grid_for((int64_t)ny, ctx->num_cu);
     if (!x_conv) {
-      e = hipMemcpyAsync(f32 ? (void*)t->X32 : (void*)t->X, Xv, nx * esz, hipMemcpyHostToDevice, ctx->stream);
+      e = hipMemcpyAsync(f32 ? (void*)t->X32.get() : (void*)t->X.get(), Xv, nx * esz, hipMemcpyHostToDevice, ctx->stream);
     } else {
       e = hipMemcpyAsync(stage, Xv, nx * esz, hipMemcpyHostToDevice, ctx->stream);
       if (e == hipSuccess) {
-        if (f32) hipLaunchKernelGGL(narrow_kernel, dim3(gx), dim3(256), 0, ctx->stream, static_cast<const double*>(stage), (int64_t)nx, t->X32);
-        else hipLaunchKernelGGL(widen_kernel, dim3(gx), dim3(256), 0, ctx->stream, static_cast<const float*>(stage), (int64_t)nx, t->X);
+        if (f32) hipLaunchKernelGGL(narrow_kernel, dim3(gx), dim3(256), 0, ctx->stream, reinterpret_cast<const double*>(stage.get()), (int64_t)nx, t->X32);
+        else hipLaunchKernelGGL(widen_kernel, dim3(gx), dim3(256), 0, ctx->stream, reinterpret_cast<const float*>(stage.get()), (int64_t)nx, t->X);
       }
     }
     if (e == hipSuccess) {
@@ -343,11 +295,11 @@ static int32_t train_setup_impl(si_ctx* ctx, const si_layer* layers, int32_t L, 
       } else {
         e = hipStreamSynchronize(ctx->stream);   // (the staging buffer is reused)
         if (e == hipSuccess) e = hipMemcpyAsync(stage, Yv, ny * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) hipLaunchKernelGGL(widen_kernel, dim3(gy), dim3(256), 0, ctx->stream, static_cast<const float*>(stage), (int64_t)ny, t->Y);
+        if (e == hipSuccess) hipLaunchKernelGGL(widen_kernel, dim3(gy), dim3(256), 0, ctx->stream, reinterpret_cast<const float*>(stage.get()), (int64_t)ny, t->Y);
       }
     }
     const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (stage) (void)hipFree(stage);
+    stage.reset();
     if (e != hipSuccess || e2 != hipSuccess) {
       free_train(ctx);
       return fail(ctx, SI_ERR_HIP, std::string("si_train_setup: ") + hipGetErrorString(e != hipSuccess ? e : e2));
@@ -429,12 +381,12 @@ static int32_t train_gradient(si_ctx* ctx, const char* who, const int64_t* idx, 
     // (src/subspace_construction.jl:39-43).  fp32 operands and activations on v_mfma_f32_32x32x2_f32; fp64 for the head's
     // partial sums, the loss and every sum over the batch (rounded once into the Float32 gradient).
     const int64_t d = (int64_t)t->out_dim * nb;
-    DenseSweepF32 sw{t->layers.data(), nl, t->fuse_tail, t->w32, t->w64, Xb32, Yb, t->ws32, t->part, t->ssepart, t->sse,
+    DenseSweepF32 sw{t->layers.data(), nl, t->fuse_tail, t->w32, t->w64, Xb32, Yb, &t->ws32, t->part, t->ssepart, t->sse,
                      sse_num_blocks(d, ctx->num_cu), nb, N, -2.0 / d_total};   // d mse / d yhat = 2 (yhat - y) / d
     const int32_t rcs = dense_value_and_grad_f32(ctx, st, sw);
     if (rcs != SI_OK) return rcs;
     // the gradient as the optimiser and the data-parallel all-reduce see it: fp64 words holding the Float32 values
-    hipLaunchKernelGGL(widen_kernel, dim3(grid_for(N, ctx->num_cu)), dim3(256), 0, st, t->ws32->gw32, N, t->gw);
+    hipLaunchKernelGGL(widen_kernel, dim3(grid_for(N, ctx->num_cu)), dim3(256), 0, st, t->ws32.gw32, N, t->gw);
     SI_HIP(ctx, hipGetLastError());
     t->grad_ready = true;
     return SI_OK;

@@ -1,4 +1,6 @@
-// Internal declarations shared by the C-ABI translation unit and the kernel launchers.
+// Internal declarations shared by the translation units of the C ABI and the kernel launchers: the plans of a Chain, the
+// training state and the context (every buffer in them held by an owner type of dev_buf.h, grouped by who releases it),
+// and the launchers of kernels_*.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,6 +9,7 @@
 #include <vector>
 
 #include "../../include/subspace_hip.h"
+#include "dev_buf.h"
 
 namespace si {
 
@@ -65,9 +68,17 @@ struct NetPlan {
   int max_rows = 1;             // largest row count handed to the row-sum kernels
 };
 struct NetScratch {             // reverse-sweep workspaces (sized by net_scratch_sizes)
-  double *bwpart = nullptr, *rspart = nullptr, *wt = nullptr, *dbtmp = nullptr;
-  // gradient mode: pidx[l] = byte index tensor of conv layer l whose MaxPool ran fused with it (net_grad_fused), else nullptr
-  uint8_t* const* pidx = nullptr;
+  DevBuf<double> bwpart, rspart, wt, dbtmp;
+  // gradient mode: pidx[l] = byte index tensor of conv layer l whose MaxPool ran fused with it (net_grad_fused), else empty
+  // (a view of the owning vector beside it: TrainState::pidx / InferState::d_pidx)
+  const DevBuf<uint8_t>* pidx = nullptr;
+};
+// workspace of one fp32 sweep at up to Bmax observations (sweep_f32_alloc; see dense_value_and_grad_f32 below)
+struct SweepF32Ws {
+  std::vector<DevBuf<float>> hs32;
+  DevBuf<float> delta32[2];
+  DevBuf<float> gw32, wt32, zero32, part32;
+  DevBuf<double> rspart64, tailpart64, yhat64;
 };
 
 // on-device training (capi_train.hip)
@@ -75,39 +86,41 @@ struct TrainState {
   std::vector<si_layer> layers;
   int64_t N = 0, Btot = 0, Bmax = 0;
   int32_t in_dim = 0, out_dim = 0;
-  double *X = nullptr, *Y = nullptr, *Xb = nullptr, *Yb = nullptr;
-  int64_t* idx = nullptr;
+  DevBuf<double> X, Y, Xb, Yb;
+  DevBuf<int64_t> idx;
   // batch indices travel through two pinned buffers (copy in, async H2D, event): a step never synchronises the stream, so the
   // caller's work between two steps (its next batch, the K1 push) overlaps the GPU's
-  int64_t* idx_pin[2] = {nullptr, nullptr};
-  hipEvent_t idx_ev[2] = {nullptr, nullptr};
+  PinBuf<int64_t> idx_pin[2];
+  Event idx_ev[2];
   bool idx_busy[2] = {false, false};
   int idx_slot = 0;
-  float *w32 = nullptr, *m32 = nullptr, *v32 = nullptr;
-  double *w64 = nullptr, *gw = nullptr;
-  std::vector<double*> hs;
-  double* delta[2] = {nullptr, nullptr};
-  double *bwpart = nullptr, *rspart = nullptr, *ssepart = nullptr, *sse = nullptr;
+  DevBuf<float> w32, m32, v32;
+  DevBuf<double> w64, gw;
+  std::vector<DevBuf<double>> hs;
+  DevBuf<double> delta[2];
+  DevBuf<double> bwpart, rspart, ssepart, sse;
   int sse_blocks = 0;
   int opt = 0;
   double eta = 0.0, p1 = 0.0, p2 = 0.0, bp1 = 0.0, bp2 = 0.0;
   bool grad_ready = false;  // gw holds a gradient that has not been applied yet
   bool fuse_tail = false;   // narrow head: folded into the epilogue of the layer in front of it (forward and reverse)
   int fuse_slots = 0;
-  double* part = nullptr;   // [fuse_slots][out_last][Bmax] partial head products
+  DevBuf<double> part;      // [fuse_slots][out_last][Bmax] partial head products
   // compute_dtype = SI_F32 (Dense chains; reference src/subspace_construction.jl:39-43 with a Float32 model AND Float32 data):
   // fp32 data, activations, deltas and gradient; fp64 only for the loss, the head's partial sums and the sums over the batch
   bool f32 = false;
-  float *X32 = nullptr, *Xb32 = nullptr;
-  struct SweepF32Ws* ws32 = nullptr;   // kept outputs, deltas, gradient, scratch of the fp32 sweep
+  DevBuf<float> X32, Xb32;
+  SweepF32Ws ws32;          // kept outputs, deltas, gradient, scratch of the fp32 sweep (empty unless f32)
   // chains with Conv / MaxPool / flatten layers (generic path, capi_net.hip)
   NetPlan plan;
-  double *Xc = nullptr, *wpack = nullptr;
+  DevBuf<double> Xc, wpack;
   NetScratch scratch;
-  std::vector<uint8_t*> pidx;   // per layer: window-index bytes of a Conv layer fused with its MaxPool (net_grad_fused)
+  std::vector<DevBuf<uint8_t>> pidx;   // per layer: window-index bytes of a Conv layer fused with its MaxPool (net_grad_fused)
 };
 
-struct Ctx {
+// ---- the context.  Its members are split by WHO RELEASES THEM: assigning a fresh ConstructState / InferState is
+// free_construct / free_infer, everything in CtxCore lives until si_destroy deletes the context.
+struct CtxCore {
   int device = -1;
   TrainState* train = nullptr;
   hipStream_t own_stream = nullptr;
@@ -115,7 +128,8 @@ struct Ctx {
   std::string err;
   char devname[256] = {0};
   int num_cu = 256;
-  // R1: RCCL communicator of this ctx (comm.hip; an ncclComm_t, kept opaque here), one rank per ctx
+  // R1: RCCL communicator of this ctx (comm.hip; an ncclComm_t, kept opaque here), one rank per ctx.  Its two scratch buffers
+  // are comm.hip's own (plain hipMalloc / hipFree, released by comm_release)
   void* comm = nullptr;
   int comm_world = 0, comm_rank = 0;
   double* d_commtmp = nullptr;  // device scratch of the host-value collectives
@@ -125,160 +139,161 @@ struct Ctx {
   // development build only (-DSI_DEV_KNOBS, SI_OVERLAP_HALVES=1): the two halves of the batch of ONE chain on two streams
   bool overlap_halves = false;
   hipStream_t stream2 = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // profiling
+  Event ev_fork, ev_join;
   // pinned host staging for the small construct-time transfers (G down, V up): pageable copies cost tens of us each
-  double* h_pin = nullptr;
-  size_t h_pin_cap = 0;
-  char* h_outpin = nullptr;      // pinned staging of the samples / lp of a device-resident loop on their way to the caller's arrays
-  size_t h_outpin_cap = 0;
-  double* h_stage[2] = {nullptr, nullptr};   // pinned staging of si_reconstruct's output pipeline (kept between calls)
-  size_t h_stage_cap = 0;
-  double *d_stage[2] = {nullptr, nullptr}, *d_zstage[2] = {nullptr, nullptr};   // its device-side double buffer
-  size_t d_stage_cap = 0, d_zstage_cap = 0;
+  PinBuf<double> h_pin;
+  PinBuf<char> h_outpin;         // pinned staging of the samples / lp of a device-resident loop on their way to the caller's arrays
+  PinBuf<double> h_stage[2];     // pinned staging of si_reconstruct's output pipeline (kept between calls)
+  DevBuf<double> d_stage[2], d_zstage[2];   // its device-side double buffer
   // streamed output map (si_sample_rwmh_weights): device ring of the chains' CURRENT weights, pinned twin, events
-  double* d_wring = nullptr;
-  int32_t* d_accflag = nullptr;
-  double* h_wring[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_wcomp[4] = {nullptr, nullptr, nullptr, nullptr}, ev_wcopy[4] = {nullptr, nullptr, nullptr, nullptr};
+  DevBuf<double> d_wring;
+  DevBuf<int32_t> d_accflag;
+  PinBuf<double> h_wring[4];
+  Event ev_wcomp[4], ev_wcopy[4];
   int64_t wring_N = 0;
   int32_t wring_C = 0;
+  // profiling
   bool profiling = false;
   uint32_t prof_mask = 0xffffffffu;  // classes that get event pairs while profiling is on
   std::vector<EventPair> pending;
   std::vector<hipEvent_t> event_pool;
   si_stats stats{};
 
-  // ---- construction state (reference src/subspace_construction.jl:31-33,45-52,61-65)
-  bool c_active = false, c_finished = false, gram_valid = false;
-  int64_t N = 0, ldA = 0, Kcap = 0, K = 0;  // K = columns held
+  // construction: what outlives a construction
   int32_t max_cols = 0;
-  int64_t npush = 0;
-  double* d_swa = nullptr;    // N (padded) fp64
-  double* d_A = nullptr;      // ldA x Kcap, column-major (fp64; FLOATS behind the same pointer when a_dtype == SI_F32); with max_cols>0 a ring of max_cols columns
-  int32_t a_dtype = SI_F64;   // storage of the deviation matrix (si_construct_set_storage)
-  size_t a_bytes = 0;         // bytes allocated behind d_A
-  int32_t a_zero_dtype = -1;  // element type for which the padding rows of d_A are known to be zero (-1: unknown)
-  int64_t a_zero_cols = 0;    // ... in the first a_zero_cols columns
-  bool a_pending = false;     // si_construct_begin ran, the matrix is allocated / checked by the first push or si_construct_set_storage
-  void* d_wstage = nullptr;   // staging of si_construct_set_mean
+  DevBuf<float> d_wstage;     // staging of si_construct_set_mean
   // pipelined host pushes (si_construct_push): two pinned host buffers -> two device buffers, events mark the H2D of each
-  void* h_wpin[2] = {nullptr, nullptr};
-  void* d_wpush[2] = {nullptr, nullptr};
-  hipEvent_t ev_wpin[2] = {nullptr, nullptr};   // H2D of buffer b done (copy stream)
-  hipEvent_t ev_wk1[2] = {nullptr, nullptr};    // K1 on buffer b done (compute stream)
+  PinBuf<char> h_wpin[2];
+  DevBuf<char> d_wpush[2];
+  Event ev_wpin[2];           // H2D of buffer b done (copy stream)
+  Event ev_wk1[2];            // K1 on buffer b done (compute stream)
   bool wpin_busy[2] = {false, false};
-  size_t wpin_bytes = 0;
   uint64_t wpin_next = 0;
-  double* d_nvals = nullptr;  // per-push n values of a batched push
-  int64_t nvals_cap = 0;
-  size_t wstage_bytes = 0;
-  double* d_G = nullptr;      // K x K
-  int64_t g_cap = 0, v_cap = 0, a_cols_alloc = 0;
-  double* d_Gpart = nullptr;  // partial slabs
-  size_t gpart_bytes = 0;
-  double* d_V = nullptr;      // K x Mpad (row k contiguous)
-  double* d_P = nullptr;      // ldA x M
-  int32_t M_built = 0;
+  DevBuf<double> d_nvals;     // per-push n values of a batched push
   std::vector<double> svals;
-  // ill-conditioned route (second-stage Gram): B = A * V_full, d_G then holds G2 = B'B
-  int refine_stage = 0;           // 0: d_G = A'A;  1: d_B valid and d_G = B'B (possibly all-reduced by the caller)
-  double* d_At = nullptr;         // K > N route: A' (pad_ld(K) x N), kept between finishes of one shape
-  int64_t at_cap = 0;
-  double* d_B = nullptr;          // ldA x K
   std::vector<double> vfull;      // K x K eigenvectors of A'A, columns DESCENDING by eigenvalue (host)
 
-  // ---- inference state (reference src/space_inference.jl:88-95,111-116,125)
-  bool i_ready = false;
-  bool i_owns_swaP = false;
+  // inference: the shapes and settings that a new si_infer_setup overwrites or keeps, never frees
   std::vector<si_layer> layers;
   int64_t iN = 0, ldP = 0;
   int32_t iM = 0;
-  const double* i_swa = nullptr;  // device
-  const double* i_P = nullptr;    // device, ldP x M
-  double* d_iswa = nullptr;       // owned copies when set from host
-  double* d_iP = nullptr;
-  double* d_X = nullptr;
-  double* d_Y = nullptr;
   int32_t in_dim = 0, out_dim = 0;
   int64_t B = 0;
   double sigma_m = 1.0;
-  double sigma_p = 0.0;          // > 0: the prior term the reference leaves dead is added (si_infer_set_prior; non-default)
-  double* d_wsq = nullptr;       // ||W_swa + P z_c||^2 per chain (chains_cap), only with the prior on
-  double* d_wsqpart = nullptr;   // its block partials (fw_slots x wsq_blocks)
   int wsq_blocks = 0;
-  // forward workspace: `fw_slots` chain slots (1 after si_infer_setup; grown by ensure_batch for multi-chain calls)
-  int fw_slots = 0;
-  double* d_w = nullptr;       // reconstructed weights, fw_slots x pad_ld(N)
-  double* d_act[2] = {nullptr, nullptr};  // ping-pong activations, fw_slots x act_elems (maxwidth x B padded)
   int64_t act_elems = 0, max_stored = 0;  // act_elems = pad_ld(max_stored * B): slot stride of d_act
-  double* d_ssepart = nullptr;  // per-block SSE partials, fw_slots x sse_blocks
-  bool fuse_tail = false;       // last layer folded into the epilogue of the layer in front of it
   int fuse_slots = 0;
-  double* d_part = nullptr;     // fw_slots x [slots][out_last][B] partial last-layer products
-  double* d_yhat = nullptr;     // fw_slots x out_dim x B, only filled on request (si_forward)
-  // compute_dtype = SI_F32 (Dense chains): X rounded once, weights rounded once per evaluation (K4 writes both), fp32 activations
-  bool f32 = false;
-  int fuse_slots32 = 0;                      // feature slots of the fp32 fused head (fuse_slots stays the fp64 path's count)
-  float* d_X32 = nullptr;
-  float* d_w32 = nullptr;                    // fw_slots x pad_ld(N)
-  float* d_act32[2] = {nullptr, nullptr};    // fw_slots x act_elems
   int sse_blocks = 0;
   int main_layer = 0;
-  // gradient workspace (allocated on the first si_logdensity_grad)
-  bool g_ready = false;
-  std::vector<double*> d_hs;   // post-activation output of every layer, out_l x B
-  double* d_delta[2] = {nullptr, nullptr};
-  double* d_gw = nullptr;      // gradient w.r.t. the flat weight vector
-  double* d_bwpart = nullptr;  // split-K partials of dW
-  double* d_rspart = nullptr;  // row-sum partials
-  double* d_ptgpart = nullptr;
-  double* d_gz = nullptr;
-  struct SweepF32Ws* g_ws32 = nullptr;   // compute_dtype = SI_F32: the fp32 sweep's workspace (si_logdensity_grad)
-  // chains with Conv / MaxPool / flatten layers (generic path, capi_net.hip)
-  NetPlan plan;
-  double* d_Xc = nullptr;      // X re-laid channel-fastest (input_spatial)
-  double* d_wpack = nullptr;   // packed conv weights of the current evaluation
-  float* d_wpack32 = nullptr;  // the same in fp32 (compute_dtype = SI_F32 on a Conv chain)
-  NetScratch g_scratch;
-  std::vector<uint8_t*> d_pidx;  // per layer: window-index bytes of a Conv layer fused with its MaxPool (gradient workspace)
-  // sampler state (device)
-  double* d_zcur = nullptr;   // M x C
-  double* d_zprop = nullptr;  // M x C
-  double* d_lpcur = nullptr;  // C
-  double* d_sse = nullptr;    // C
-  int64_t* d_nacc = nullptr;  // C
-  uint64_t* d_steps = nullptr;  // C: transition counter of every chain (device-resident)
-  int32_t chains_cap = 0;
   // step-wise sampler session (si_rwmh_begin .. si_rwmh_end)
-  double* sw_Z = nullptr;
-  double* sw_lp = nullptr;
   int64_t sw_itr = 0, sw_next = 0;
   double sw_sigma_z = 0.0, sw_d = 0.0;
   uint64_t sw_seed = 0;
   int32_t sw_chain0 = 0, sw_C = 0;
   bool sw_evaluated = false;
-  double *d_outZ = nullptr, *d_outlp = nullptr;   // device-side sample / lp arrays of si_sample_rwmh*, kept between calls
-  size_t outZ_cap = 0, outlp_cap = 0;             // (a hipMalloc / hipFree pair per call was 0.4 ms of a 20-transition call)
   bool defer_sse_final = false;   // eval_density leaves the SSE block partials in d_ssepart (sample_rwmh_impl's fused tail sums them)
   bool chain_loop_enabled = true;   // si_set_chain_loop: 0 forces the launch-per-step loop (the parity tests compare the two)
   // narrow Dense chains (kernels_chain_grid.hip): every layer of the density in ONE launch, and K6 as a persistent grid loop
   int chain_mode = 1;               // si_set_chain_loop: 0 per-layer launches, 1 automatic, 2 the fused forward without the persistent loops
-  bool fused_ok = false;            // the chain set up is of that class (infer_setup_common)
-  unsigned* d_gridsync = nullptr;   // grid loop: one 128-byte counter line per chain + the status line
-  int gridsync_chains = 0;
-  CgTileD* d_cgprog = nullptr;      // the chain's tile program (chain_fused_program)
   int cg_start[5] = {0}, cg_count[5] = {0}, cg_chunks[5] = {0};
-  // the same two kernels specialised to the chain's shapes at run time (chain_spec_rtc.cpp); buffers of the specialised loop
   bool chain_spec = true;           // si_set_chain_loop 3 / 4: generic kernels only
-  double* d_specw = nullptr;        // 4 weight vectors in fragment order per chain ([parity][accepted, rejected])
-  double* d_specy = nullptr;        // 2 output vectors per chain ([parity])
-  int* d_specperm = nullptr;        // natural weight index -> fragment order
+  std::string spec_message;         // why the specialised kernels did not run, when they did not (hiprtc log, class limits)
+
+  CtxCore() = default;
+  CtxCore(const CtxCore&) = delete;
+  CtxCore& operator=(const CtxCore&) = delete;
+  ~CtxCore() { delete train; }
+};
+
+// ---- construction state (reference src/subspace_construction.jl:31-33,45-52,61-65): what free_construct drops
+struct ConstructState {
+  bool c_active = false, c_finished = false, gram_valid = false;
+  int64_t N = 0, ldA = 0, Kcap = 0, K = 0;  // K = columns held
+  int64_t npush = 0;
+  DevBuf<double> d_swa;       // N (padded) fp64
+  DevBuf<char> d_A;           // BYTES of the ldA x Kcap column-major matrix of a_dtype elements (doubles, or floats with SI_F32); with max_cols>0 a ring of max_cols columns
+  int32_t a_dtype = SI_F64;   // storage of the deviation matrix (si_construct_set_storage)
+  int32_t a_zero_dtype = -1;  // element type for which the padding rows of d_A are known to be zero (-1: unknown)
+  int64_t a_zero_cols = 0;    // ... in the first a_zero_cols columns
+  bool a_pending = false;     // si_construct_begin ran, the matrix is allocated / checked by the first push or si_construct_set_storage
+  DevBuf<double> d_G;         // K x K
+  DevBuf<double> d_Gpart;     // partial slabs
+  DevBuf<double> d_V;         // K x Mpad (row k contiguous)
+  DevBuf<double> d_P;         // ldA x M
+  int32_t M_built = 0;
+  // ill-conditioned route (second-stage Gram): B = A * V_full, d_G then holds G2 = B'B
+  int refine_stage = 0;           // 0: d_G = A'A;  1: d_B valid and d_G = B'B (possibly all-reduced by the caller)
+  DevBuf<double> d_At;            // K > N route: A' (pad_ld(K) x N), kept between finishes of one shape
+  DevBuf<double> d_B;             // ldA x K
+};
+
+// ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops
+struct InferState {
+  bool i_ready = false;
+  const double* i_swa = nullptr;  // device; borrowed (the construction's, the caller's) or d_iswa
+  const double* i_P = nullptr;    // device, ldP x M; likewise
+  DevBuf<double> d_iswa;          // owned copies when set from host
+  DevBuf<double> d_iP;
+  DevBuf<double> d_X;
+  DevBuf<double> d_Y;
+  double sigma_p = 0.0;          // > 0: the prior term the reference leaves dead is added (si_infer_set_prior; non-default)
+  DevBuf<double> d_wsq;          // ||W_swa + P z_c||^2 per chain (chains_cap), only with the prior on
+  DevBuf<double> d_wsqpart;      // its block partials (fw_slots x wsq_blocks)
+  // forward workspace: `fw_slots` chain slots (1 after si_infer_setup; grown by ensure_batch for multi-chain calls)
+  int fw_slots = 0;
+  DevBuf<double> d_w;          // reconstructed weights, fw_slots x pad_ld(N)
+  DevBuf<double> d_act[2];     // ping-pong activations, fw_slots x act_elems (maxwidth x B padded)
+  DevBuf<double> d_ssepart;    // per-block SSE partials, fw_slots x sse_blocks
+  bool fuse_tail = false;      // last layer folded into the epilogue of the layer in front of it
+  DevBuf<double> d_part;       // fw_slots x [slots][out_last][B] partial last-layer products
+  DevBuf<double> d_yhat;       // fw_slots x out_dim x B, only filled on request (si_forward)
+  // compute_dtype = SI_F32 (Dense chains): X rounded once, weights rounded once per evaluation (K4 writes both), fp32 activations
+  bool f32 = false;
+  int fuse_slots32 = 0;                      // feature slots of the fp32 fused head (fuse_slots stays the fp64 path's count)
+  DevBuf<float> d_X32;
+  DevBuf<float> d_w32;                       // fw_slots x pad_ld(N)
+  DevBuf<float> d_act32[2];                  // fw_slots x act_elems
+  // gradient workspace (allocated on the first si_logdensity_grad)
+  bool g_ready = false;
+  std::vector<DevBuf<double>> d_hs;   // post-activation output of every layer, out_l x B
+  DevBuf<double> d_delta[2];
+  DevBuf<double> d_gw;      // gradient w.r.t. the flat weight vector
+  DevBuf<double> d_bwpart;  // split-K partials of dW
+  DevBuf<double> d_rspart;  // row-sum partials
+  DevBuf<double> d_ptgpart;
+  DevBuf<double> d_gz;
+  SweepF32Ws g_ws32;        // compute_dtype = SI_F32: the fp32 sweep's workspace (si_logdensity_grad)
+  // chains with Conv / MaxPool / flatten layers (generic path, capi_net.hip)
+  NetPlan plan;
+  DevBuf<double> d_Xc;      // X re-laid channel-fastest (input_spatial)
+  DevBuf<double> d_wpack;   // packed conv weights of the current evaluation
+  DevBuf<float> d_wpack32;  // the same in fp32 (compute_dtype = SI_F32 on a Conv chain)
+  NetScratch g_scratch;
+  std::vector<DevBuf<uint8_t>> d_pidx;  // per layer: window-index bytes of a Conv layer fused with its MaxPool (gradient workspace)
+  // sampler state (device)
+  DevBuf<double> d_zcur;   // M x C
+  DevBuf<double> d_zprop;  // M x C
+  DevBuf<double> d_lpcur;  // C
+  DevBuf<double> d_sse;    // C
+  DevBuf<int64_t> d_nacc;  // C
+  DevBuf<uint64_t> d_steps;  // C: transition counter of every chain (device-resident)
+  int32_t chains_cap = 0;
+  DevBuf<double> sw_Z, sw_lp;     // step-wise sampler session (si_rwmh_begin .. si_rwmh_end): its sample / lp arrays
+  DevBuf<double> d_outZ, d_outlp;   // device-side sample / lp arrays of si_sample_rwmh*, kept between calls
+                                    // (a hipMalloc / hipFree pair per call was 0.4 ms of a 20-transition call)
+  bool fused_ok = false;            // narrow Dense chain: the chain set up is of the fused class (infer_setup_common)
+  DevBuf<unsigned> d_gridsync;      // grid loop: one 128-byte counter line per chain + the status line (size() = 32 words per line)
+  DevBuf<CgTileD> d_cgprog;         // the chain's tile program (chain_fused_program)
+  // the same two kernels specialised to the chain's shapes at run time (chain_spec_rtc.cpp); buffers of the specialised loop
+  DevBuf<double> d_specw;           // 4 weight vectors in fragment order per chain ([parity][accepted, rejected])
+  DevBuf<double> d_specy;           // 2 output vectors per chain ([parity])
+  DevBuf<int> d_specperm;           // natural weight index -> fragment order
   const void* specperm_for = nullptr;   // (the SpecKernels the permutation was generated by)
   int spec_chains = 0, spec_fo = 0;
   int last_density_spec = 0, last_loop_spec = 0;   // si_chain_kernel_info: did the last density / sampling call run specialised kernels
-  std::string spec_message;         // why not, when they did not (hiprtc log, class limits)
 };
+
+struct Ctx : CtxCore, ConstructState, InferState {};
 
 void free_train(Ctx* c);
 void comm_release(Ctx* c);  // comm.hip: destroy the communicator (si_destroy / si_comm_destroy)
@@ -416,7 +431,7 @@ struct DenseSweep {
   bool fuse_tail;
   const double* w;          // flat fp64 weights
   const double* X;          // input of layer 0, in_0 x B
-  double* const* hs;        // kept outputs of every layer
+  const DevBuf<double>* hs;  // kept outputs of every layer
   double* delta[2];
   double* gw;
   double* rspart;
@@ -428,15 +443,8 @@ int32_t dense_reverse_sweep(Ctx* ctx, hipStream_t st, const DenseSweep& s);
 // layer's output kept, the SSE (fp64), Delta_L = scale * (y - yhat) * act_L'(yhat), reverse sweep; on return gw32 holds
 // d (scale/2 * -SSE) / dw rounded to fp32 and *sse the sum of squared errors.  Shared by the training step and si_logdensity_grad
 // with compute_dtype = SI_F32.
-struct SweepF32Ws {   // workspace of one sweep at up to Bmax observations (sweep_f32_alloc / _free)
-  std::vector<float*> hs32;
-  float* delta32[2] = {nullptr, nullptr};
-  float *gw32 = nullptr, *wt32 = nullptr, *zero32 = nullptr, *part32 = nullptr;
-  double *rspart64 = nullptr, *tailpart64 = nullptr, *yhat64 = nullptr;
-};
 bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const si_layer* layers, int L, bool fuse_tail, int64_t N, int32_t in_dim, int32_t out_dim,
                      int64_t Bmax);
-void sweep_f32_free(SweepF32Ws& ws);
 struct DenseSweepF32 {
   const si_layer* layers;
   size_t nl;
@@ -545,17 +553,17 @@ void net_input(Ctx* c, const NetPlan& p, const double* X, double* Xc, int64_t B)
 // kernel, and *final_out is the buffer that holds the last layer's output.
 // pidx != nullptr (gradient mode, outs[l] per layer): a Conv layer with net_grad_fused(p, l) runs fused with its MaxPool, writes
 // outs[l + 1] and pidx[l] and leaves outs[l] untouched (it may be nullptr)
-int32_t net_forward_f32(Ctx* c, const NetPlan& p, const float* w, const float* xin, int64_t B, float* const* outs, float* wpack,
+int32_t net_forward_f32(Ctx* c, const NetPlan& p, const float* w, const float* xin, int64_t B, const DevBuf<float>* outs, float* wpack,
                         float** final_out);
-int32_t net_forward(Ctx* c, const NetPlan& p, const double* w, const double* xin, int64_t B, double* const* outs, double* wpack,
-                    bool pingpong = false, double** final_out = nullptr, uint8_t* const* pidx = nullptr);
+int32_t net_forward(Ctx* c, const NetPlan& p, const double* w, const double* xin, int64_t B, const DevBuf<double>* outs, double* wpack,
+                    bool pingpong = false, double** final_out = nullptr, const DevBuf<uint8_t>* pidx = nullptr);
 // Conv layer l directly followed by MaxPool((2, 2), stride 2) on even sizes, activation carried by the GEMM epilogue: in
 // gradient mode the pair runs as one kernel that keeps a byte index instead of the un-pooled activation
 bool net_grad_fused(const NetPlan& p, size_t l);
 size_t net_pidx_bytes(const NetPlan& p, size_t l, int64_t B);
 void net_scratch_sizes(const NetPlan& p, int64_t B, int num_cu, size_t* bwpart, size_t* rspart, size_t* wt, size_t* dbtmp);
 // g0 holds d / d(output of the last layer) (out_feat x B) on entry; g0 / g1: max_elems * B doubles each; hs[l]: kept outputs
-int32_t net_backward(Ctx* c, const NetPlan& p, const double* w, const double* xin, int64_t B, double* const* hs, double* g0,
+int32_t net_backward(Ctx* c, const NetPlan& p, const double* w, const double* xin, int64_t B, const DevBuf<double>* hs, double* g0,
                      double* g1, double* gw, const NetScratch& s);
 // K6, device-resident loop (kernels_chain.hip): all `itr` transitions of `nchains` small Dense chains in ONE launch, one
 // workgroup per chain, weights / data / activations in LDS; bit-identical to the launch-per-step loop of si_sample_rwmh

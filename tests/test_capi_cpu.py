@@ -79,6 +79,36 @@ def test_shipped_library_has_no_development_knobs(si):
                 assert "SI_HOST_COPY_THREADS" in t or "SI_RCCL_LIB" in t, (f, t)
 
 
+def test_one_allocation_path():
+    """Every buffer, pinned buffer and event of the C ABI's host side is held by an owner type of csrc/dev_buf.h, and device
+    memory is reached through the one seam raw_dev_malloc / raw_dev_free (defined once in capi.hip, where the development
+    build switches to the guard-page allocator).  So no other line of these files calls the runtime's allocation, release or
+    event-creation functions.  Exempt by name: dev_buf.h (the owners), guard_alloc.hip (the development allocator), comm.hip
+    (its two scratch buffers stay on the plain runtime calls)."""
+    csrc = os.path.join(ROOT, "subspaceinference.jl_amd", "csrc")
+    banned = ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(", "hipEventCreate", "hipEventDestroy")
+    allowed = {   # (file, stripped line): the seam's definition and the profiling event pool
+        ("capi.hip", "hipError_t raw_dev_malloc(void** out, size_t bytes) { return hipMalloc(out, bytes); }"),
+        ("capi.hip", "hipError_t raw_dev_free(void* p) { return hipFree(p); }"),
+        ("capi.hip", "if (hipEventCreate(&e) != hipSuccess) return nullptr;"),
+        ("capi.hip", "for (auto e : ctx->event_pool) (void)hipEventDestroy(e);"),
+    }
+    files = [f for f in sorted(os.listdir(csrc))
+             if (f.startswith("capi") and f.endswith(".hip")) or (f.startswith("kernels_") and f.endswith(".hip"))
+             or f in ("si_internal.h", "capi_common.h")]
+    assert {"capi.hip", "capi_infer.hip", "capi_sample.hip", "capi_train.hip", "capi_net.hip", "si_internal.h", "capi_common.h"} <= set(files)
+    seen = set()
+    for f in files:
+        for ln in open(os.path.join(csrc, f)):
+            code = ln.split("//")[0]
+            if any(b in code for b in banned):
+                assert (f, ln.strip()) in allowed, (f, ln.strip())
+                seen.add((f, ln.strip()))
+    assert seen == allowed, allowed - seen
+    for f in files:   # and the allocator switch of the development build is not spelt as a macro anywhere any more
+        assert "#define hipMalloc" not in open(os.path.join(csrc, f)).read(), f
+
+
 def test_host_eigensolver(si):
     rng = np.random.default_rng(0)
     for n in (1, 2, 5, 33, 100):

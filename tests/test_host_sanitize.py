@@ -1,7 +1,8 @@
 """The library's host-only code built with sanitizers and run on the CPU (GPU-side sanitizers are not available on the MI355X
 pool): csrc/eig.cpp (both eigensolver routes) under AddressSanitizer + UBSan, csrc/host_copy.cpp (the persistent copy pool
 of si_construct_push / the output map: atomics, a spin-then-sleep hand-over, two caller threads) under ThreadSanitizer and
-under AddressSanitizer."""
+under AddressSanitizer, csrc/dev_buf.h (the owner types of every buffer of a context) under AddressSanitizer + UBSan with the
+leak checker, over a malloc-backed allocator seam."""
 import os
 import shutil
 import subprocess
@@ -41,6 +42,25 @@ def test_eigensolver_under_asan_ubsan(tmp_path):
                          env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
     assert run.returncode == 0 and "EIG_SANITIZE_OK" in run.stdout, run.stdout[-2000:] + run.stderr[-4000:]
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+
+
+@pytest.mark.timeout(300)
+def test_owner_types_under_asan_ubsan(tmp_path):
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path / "dev_buf_sanitize")
+    src = os.path.join(HERE, "native", "dev_buf_sanitize_main.cpp")
+    build = subprocess.run([gxx, "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                            "-fno-omit-frame-pointer", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", src, "-o", exe],
+                           capture_output=True, text=True)
+    if build.returncode != 0 and "sanitize" in build.stderr and "cannot find" in build.stderr:
+        pytest.skip("sanitizer runtime not installed")
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=240,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert run.returncode == 0 and "DEV_BUF_OK" in run.stdout, run.stdout[-2000:] + run.stderr[-4000:]
+    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr and "LeakSanitizer" not in run.stderr
 
 
 @pytest.mark.timeout(600)

@@ -237,6 +237,15 @@ int32_t si_logdensity(si_ctx* ctx, const double* Z, int32_t C, double* lp_out /*
  * Replaces `l_pi_grad(theta) = (density(theta), getbackend(backend).gradient(density, theta))`
  * (src/space_inference.jl:107): one reverse sweep through the chain instead of M-wide forward duals.         */
 int32_t si_logdensity_grad(si_ctx* ctx, const double* z /* M */, double* lp_out, double* grad_out /* M */);
+/* The same for C points at once: lp_out[c], grad_out[:, c] = what si_logdensity_grad returns for Z[:, c] (prior term as
+ * si_infer_set_prior set it); same state rules.  fp64 Dense chains with the identity / relu / tanh / sigmoid activations whose
+ * per-layer images fit a workgroup's LDS (docs/src/nn_example.md:112-118 and its class) run ONE fused forward + reverse launch
+ * and ONE reduction launch per group of points, with every sum in a fixed order: a point's result does not depend on C, on its
+ * column or on the run.  Every other chain walks the columns through si_logdensity_grad's own path (same bits).            */
+int32_t si_logdensity_grad_batch(si_ctx* ctx, const double* Z /* M x C */, int32_t C, double* lp_out /* C */,
+                                 double* grad_out /* M x C, column-major */);
+/* 1 when the last si_logdensity_grad_batch ran the fused narrow-chain kernel, 0 when it walked the per-point path */
+int32_t si_grad_kernel_info(si_ctx* ctx, int32_t* fused_out);
 /* same, additionally returning the model output (out_dim x B) of the LAST z -- forward-pass parity  */
 int32_t si_forward(si_ctx* ctx, const double* z /* M */, double* Yhat_out /* out_dim x B */);
 /* posterior predictive on NEW inputs: Yhat_out[:, :, c] = f_{W_swa + P*Z[:, c]}(Xnew), out_dim x Bn x C column-major.

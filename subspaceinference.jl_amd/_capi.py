@@ -87,6 +87,8 @@ SIGNATURES = {
     "si_infer_set_prior": (c_int32, [c_void_p, c_double]),
     "si_logdensity": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p]),
     "si_logdensity_grad": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "si_logdensity_grad_batch": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "si_grad_kernel_info": (c_int32, [c_void_p, POINTER(c_int32)]),
     "si_forward": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "si_predict": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     "si_sample_rwmh": (c_int32, [c_void_p, c_int64, c_double, c_uint64, c_int32, c_int32, c_void_p, c_void_p,
@@ -564,6 +566,24 @@ class Context:
         g = np.empty(self._m, dtype=np.float64)
         self._check(self.lib.si_logdensity_grad(self.h, _ptr(z), _ptr(lp), _ptr(g)))
         return float(lp[0]), g
+
+    def logdensity_grad_batch(self, z):
+        """(lp[C], G[M, C]): value and gradient at every column of the M x C matrix z in ONE call (si_logdensity_grad_batch)"""
+        z = _f64(z)
+        if z.ndim == 1:
+            z = z.reshape(-1, 1, order="F")
+        if z.ndim != 2 or z.shape[0] != self._m:
+            raise SubspaceError("DimensionMismatch: z has %d rows, M = %d" % (z.shape[0], self._m))
+        lp = np.empty(z.shape[1], dtype=np.float64)
+        g = np.empty((self._m, z.shape[1]), dtype=np.float64, order="F")
+        self._check(self.lib.si_logdensity_grad_batch(self.h, _ptr(z), z.shape[1], _ptr(lp), _ptr(g)))
+        return lp, g
+
+    def grad_kernel_info(self):
+        """1 when the last logdensity_grad_batch ran the fused narrow-chain kernel, 0 when it walked the per-point path"""
+        f = c_int32(0)
+        self._check(self.lib.si_grad_kernel_info(self.h, byref(f)))
+        return int(f.value)
 
     def forward(self, z):
         z = _f64(z).reshape(-1)

@@ -147,8 +147,9 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
     of subspace samples).  σ_p is accepted and unused, exactly as in the reference (quirk Q4), unless
     `include_prior=True` (non-default) asks for the term the reference's source writes after its `return`.
 
-    `nchains > 1` (RWMH only; not in the reference, which runs one chain per call) runs the independent chains
-    chain_id .. chain_id+nchains-1 stacked in every launch of the forward pass: chn becomes a list over chains
+    `nchains > 1` (RWMH and :mala; not in the reference, which runs one chain per call) runs the independent chains
+    chain_id .. chain_id+nchains-1 stacked in every launch of the forward pass (:mala: of the stacked value + gradient,
+    si_logdensity_grad_batch, with the host logic of `samplers.mala_chains`): chn becomes a list over chains
     (or the M x itr x nchains array with return_z) and lp is itr x nchains.
 
     `compute_dtype="f32"` (non-default; SURVEY section 0 Q6: "forward fp64 with fp32 as a measured option") evaluates the
@@ -184,8 +185,8 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
             ctx.infer_setup(table, n_par, M, W_swa, P, x, y, σ_m, compute_dtype=cdt)
         # include_prior=True adds the term the reference leaves dead after its `return` (quirk Q4); default: as the reference
         ctx.set_prior(σ_p if include_prior else 0.0)
-        if nchains != 1 and a not in _RWMH_ALGS:
-            raise SubspaceError("nchains > 1 is available for alg = :rwmh / :mh only")
+        if nchains != 1 and a not in _RWMH_ALGS and a != "mala":
+            raise SubspaceError("nchains > 1 is available for alg = :rwmh / :mh / :mala only")
         if a in _RWMH_ALGS:
             if return_z:
                 z, lp, _ = ctx.sample_rwmh(itr, σ_z, seed, chain_id, nchains)
@@ -199,6 +200,14 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
         else:
             # :mala (:117-120) / :hmc, :nuts (:139-160): the sampler logic is host control flow, every density + gradient
             # evaluation is the device reverse sweep (si_logdensity_grad) instead of M-wide ForwardDiff duals (:107)
+            if a == "mala" and nchains > 1:
+                # the chains chain_id .. chain_id + nchains - 1 in lock-step: one stacked gradient call per transition
+                # (si_logdensity_grad_batch); chain c is the single-chain run with chain_id + c
+                rngs = [np.random.default_rng([int(seed), int(chain_id) + c]) for c in range(nchains)]
+                z, lp, _ = samplers.mala_chains(ctx.logdensity_grad_batch, M, itr, σ_z, rngs)
+                if return_z:
+                    return z, lp
+                return [[w[:, t] for t in range(itr)] for w in (ctx.reconstruct(z[:, :, c]) for c in range(nchains))], lp
             rng = np.random.default_rng([int(seed), int(chain_id)])
             fn = {"mala": samplers.mala, "hmc": samplers.hmc, "nuts": samplers.nuts}[a]
             z, lp, _ = fn(ctx.logdensity_grad, M, itr, σ_z, rng)

@@ -649,12 +649,9 @@ static int32_t ensure_grad(si_ctx* ctx) {
   return SI_OK;
 }
 
-int32_t si_logdensity_grad(si_ctx* ctx, const double* z, double* lp_out, double* grad_out) {
-  CHECK_CTX(ctx);
-  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_logdensity_grad: call si_infer_setup first");
-  if (!z || !lp_out || !grad_out) return fail(ctx, SI_ERR_INVALID, "si_logdensity_grad: bad argument");
-  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_logdensity_grad: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
-  BIND(ctx);
+// value and gradient at ONE point through the per-layer launches: the body of si_logdensity_grad, and what
+// si_logdensity_grad_batch walks column by column for every chain outside the fused class (checked and bound by the caller)
+static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* grad_out) {
   int32_t rc = ensure_chains(ctx, 1);
   if (rc != SI_OK) return rc;
   if ((rc = ensure_grad(ctx)) != SI_OK) return rc;
@@ -776,6 +773,124 @@ int32_t si_logdensity_grad(si_ctx* ctx, const double* z, double* lp_out, double*
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   *lp_out = mvnormal_c0((double)d, ctx->sigma_m) - (sse / s2) / 2.0;
   if (prior) *lp_out += prior_c0(ctx) - (wsq / (ctx->sigma_p * ctx->sigma_p)) / 2.0;
+  return SI_OK;
+}
+
+// the state rules and error texts shared by the two gradient entry points
+static int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok) {
+  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_infer_setup first");
+  if (!args_ok) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": bad argument");
+  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, std::string(who) + ": a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
+  return SI_OK;
+}
+
+int32_t si_logdensity_grad(si_ctx* ctx, const double* z, double* lp_out, double* grad_out) {
+  CHECK_CTX(ctx);
+  const int32_t rc = grad_entry_check(ctx, "si_logdensity_grad", z && lp_out && grad_out);
+  if (rc != SI_OK) return rc;
+  BIND(ctx);
+  return logdensity_grad_point(ctx, z, lp_out, grad_out);
+}
+
+// ---- many points in one call: narrow Dense chains on the fused forward + reverse kernel (kernels_chain_grad.hip) ---------------
+// The class: compute_dtype = SI_F64, every layer Dense with one of the four MFMA-epilogue activations, at most
+// SI_CHAIN_MAX_LAYERS layers, an LDS plan (every layer's image + two Delta buffers) within 160 KiB at 16 observations per
+// workgroup, and a flat weight vector that the layers' W / b ranges cover exactly once (every workgroup writes every element
+// of its partial).  32 observations per workgroup where that plan leaves room for two workgroups per CU (half the partials).
+// The choice depends on the chain and B only -- never on C -- so a point's bits do not depend on the call it arrives in.
+static int vgrad_class(si_ctx* ctx) {
+  if (ctx->vg_class >= 0) return ctx->vg_class;
+  ctx->vg_class = 0;
+  if (ctx->f32 || ctx->plan.has_conv) return 0;
+  const int L = (int)ctx->layers.size();
+  ChainVgradPlan vp;
+  if (chain_vgrad_plan(vp, ctx->layers.data(), L, ctx->B, 1) == 0) return 0;
+  if (ctx->layers[0].in != ctx->in_dim || ctx->layers[(size_t)L - 1].out != ctx->out_dim) return 0;
+  std::vector<char> seen((size_t)ctx->iN, 0);
+  auto mark = [&](int64_t off, int64_t n) {
+    if (off < 0 || off + n > ctx->iN) return false;
+    for (int64_t i = off; i < off + n; ++i) {
+      if (seen[(size_t)i]) return false;
+      seen[(size_t)i] = 1;
+    }
+    return true;
+  };
+  int64_t total = 0;
+  for (const si_layer& ly : ctx->layers) {
+    if (!mark(ly.w_off, (int64_t)ly.in * ly.out) || !mark(ly.b_off, ly.out)) return 0;
+    total += (int64_t)ly.in * ly.out + ly.out;
+  }
+  if (total != ctx->iN) return 0;
+  const size_t lds2 = chain_vgrad_plan(vp, ctx->layers.data(), L, ctx->B, 2);
+  ctx->vg_class = (lds2 != 0 && lds2 <= (size_t)64 * 1024) ? 2 : 1;
+  return ctx->vg_class;
+}
+
+int32_t si_logdensity_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double* lp_out, double* grad_out) {
+  CHECK_CTX(ctx);
+  int32_t rc = grad_entry_check(ctx, "si_logdensity_grad_batch", Z && C >= 1 && lp_out && grad_out);
+  if (rc != SI_OK) return rc;
+  BIND(ctx);
+  ctx->last_grad_fused = 0;
+  const int64_t N = ctx->iN, B = ctx->B, ldw = pad_ld(N);
+  const int32_t M = ctx->iM;
+  const int nb = vgrad_class(ctx);
+  const int64_t G = nb > 0 ? (B + 16 * nb - 1) / (16 * nb) : 0;
+  // points per pass of launches: the workspace (weights, G partials of grad_w, grad_w per point) is capped like the forward
+  // workspace of the stacked density (SI_BATCH_BYTES), and a launch carries at most 65535 points in grid.y
+  const double per = 8.0 * ((double)ldw * ((double)G + 2.0) + (double)G + 2.0 * M + 1.0);
+  const int64_t fit = nb > 0 ? (int64_t)std::min(65535.0, std::floor(SI_BATCH_BYTES / per)) : 0;
+  if (fit < 1) {
+    // every other chain (Conv / MaxPool / flatten, SI_F32, the four later activations, wide layers): column by column through the
+    // single-point path -- the same code, the same bits as C calls of si_logdensity_grad
+    for (int32_t c = 0; c < C; ++c)
+      if ((rc = logdensity_grad_point(ctx, Z + (size_t)M * c, lp_out + c, grad_out + (size_t)M * c)) != SI_OK) return rc;
+    return SI_OK;
+  }
+  const int cap = (int)std::min<int64_t>(fit, C);
+  if (ctx->vg_cap < cap) {
+    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t S = (size_t)cap;
+    ctx->vg_cap = 0;
+    if (!ctx->d_vg_z.alloc(S * M) || !ctx->d_vg_w.alloc(S * (size_t)ldw) || !ctx->d_vg_part.alloc(S * (size_t)G * (size_t)ldw) ||
+        !ctx->d_vg_ssepart.alloc(S * (size_t)G) || !ctx->d_vg_gw.alloc(S * (size_t)ldw) || !ctx->d_vg_lp.alloc(S) ||
+        !ctx->d_vg_gz.alloc(S * M)) {
+      for (DevBuf<double>* b : {&ctx->d_vg_z, &ctx->d_vg_w, &ctx->d_vg_part, &ctx->d_vg_ssepart, &ctx->d_vg_gw, &ctx->d_vg_lp, &ctx->d_vg_gz})
+        b->reset();
+      return fail(ctx, SI_ERR_NOMEM, "si_logdensity_grad_batch: workspace allocation failed");
+    }
+    ctx->vg_cap = cap;
+  }
+  ChainVgradPlan vp;
+  const size_t lds = chain_vgrad_plan(vp, ctx->layers.data(), (int)ctx->layers.size(), B, nb);
+  const double s2 = ctx->sigma_m * ctx->sigma_m;
+  const double c0 = mvnormal_c0((double)ctx->out_dim * (double)B, ctx->sigma_m);
+  for (int32_t p0 = 0; p0 < C; p0 += ctx->vg_cap) {
+    const int n = std::min<int32_t>(ctx->vg_cap, C - p0);
+    SI_HIP(ctx, hipMemcpyAsync(ctx->d_vg_z, Z + (size_t)M * p0, (size_t)M * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    {
+      ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * n, (double)N * (M + 1 + n) * 8.0);
+      launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, ctx->d_vg_z, n, ctx->d_vg_w, ldw, ctx->num_cu);
+    }
+    {
+      ProfScope ps(ctx, SI_K_BACKWARD, 6.0 * (double)N * (double)B * n, 0.0);
+      launch_chain_vgrad(ctx->stream, vp, nb, lds, ctx->d_vg_w, ldw, ctx->d_X, ctx->d_Y, 1.0 / s2, ctx->d_vg_part, ldw, ctx->d_vg_ssepart, n);
+      launch_chain_vgrad_reduce(ctx->stream, ctx->d_vg_part, (int)G, N, ldw, ctx->d_vg_ssepart, ctx->d_vg_w, ldw, ctx->i_P, ctx->ldP, M,
+                                ctx->sigma_p, prior_c0(ctx), c0, s2, ctx->d_vg_gw, ctx->d_vg_lp, ctx->d_vg_gz, n);
+    }
+    SI_HIP(ctx, hipGetLastError());
+    SI_HIP(ctx, hipMemcpyAsync(lp_out + p0, ctx->d_vg_lp, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SI_HIP(ctx, hipMemcpyAsync(grad_out + (size_t)M * p0, ctx->d_vg_gz, (size_t)M * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->last_grad_fused = 1;
+  return SI_OK;
+}
+
+int32_t si_grad_kernel_info(si_ctx* ctx, int32_t* fused_out) {
+  CHECK_CTX(ctx);
+  if (!fused_out) return fail(ctx, SI_ERR_INVALID, "si_grad_kernel_info: bad argument");
+  *fused_out = ctx->last_grad_fused;
   return SI_OK;
 }
 

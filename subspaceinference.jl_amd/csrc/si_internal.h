@@ -291,6 +291,11 @@ struct InferState {
   const void* specperm_for = nullptr;   // (the SpecKernels the permutation was generated by)
   int spec_chains = 0, spec_fo = 0;
   int last_density_spec = 0, last_loop_spec = 0;   // si_chain_kernel_info: did the last density / sampling call run specialised kernels
+  // si_logdensity_grad_batch, fused route (kernels_chain_grad.hip): workspace for vg_cap points, allocated on the first call
+  int vg_class = -1;                // -1: not looked at yet; 0: the chain is not of the fused class; 1 / 2: it is, with batch tiles of 16 * vg_class
+  int vg_cap = 0;
+  DevBuf<double> d_vg_z, d_vg_w, d_vg_part, d_vg_ssepart, d_vg_gw, d_vg_lp, d_vg_gz;
+  int last_grad_fused = 0;          // si_grad_kernel_info
 };
 
 struct Ctx : CtxCore, ConstructState, InferState {};
@@ -621,6 +626,23 @@ struct ChainGridArgs {
 };
 size_t chain_grid_plan(ChainGridArgs& a, size_t lds_fused);
 hipError_t launch_chain_grid(hipStream_t st, const ChainGridArgs& a, int NB, int nchains, size_t lds);
+// value + gradient of a narrow Dense chain for many points in one launch + one reduction (kernels_chain_grad.hip)
+struct ChainVgradPlan {
+  si_layer lay[SI_CHAIN_MAX_LAYERS];
+  int L, B;
+  int ld[SI_CHAIN_MAX_LAYERS + 1];      // pitch of image l (the input of layer l; image L: the model outputs); Delta_l has ld[l + 1]
+  int o_img[SI_CHAIN_MAX_LAYERS + 1];   // LDS offsets (doubles): every image is kept for the reverse sweep
+  int o_delta[2], o_red;
+  int lds_doubles;
+};
+size_t chain_vgrad_plan(ChainVgradPlan& p, const si_layer* layers, int L, int64_t B, int NB);   // LDS bytes; 0 = not of this class
+// part: per (point, workgroup) a partial of grad_w, part_stride apart; ssepart: per (point, workgroup); npoints <= 65535
+void launch_chain_vgrad(hipStream_t st, const ChainVgradPlan& p, int NB, size_t lds, const double* w, int64_t w_stride, const double* X,
+                        const double* Y, double inv_s2, double* part, int64_t part_stride, double* ssepart, int npoints);
+// per point: grad_w = the G partials in order (- w / sigma_p^2 with the prior on) into gw, gz = P' grad_w, lp
+void launch_chain_vgrad_reduce(hipStream_t st, const double* part, int G, int64_t N, int64_t part_stride, const double* ssepart,
+                               const double* w, int64_t w_stride, const double* P, int64_t ldP, int M, double sigma_p, double c0p,
+                               double c0, double sigma2, double* gw, double* lp_out, double* gz_out, int npoints);
 int dense_fused_slot_feats(int32_t out);   // features per head slot of the fused fp64 layer (kernels_gemm.hip: BM / WM)
 // K6
 void launch_rwmh_init(hipStream_t st, double* zcur, double* lpcur, int64_t* nacc, uint64_t* steps, int32_t M, int32_t C);

@@ -303,6 +303,22 @@ function logdensity_grad(ctx::Ctx, z::AbstractVector{<:Real})
     return lp[], g
 end
 
+# the same for the columns of Z in ONE call (si_logdensity_grad_batch): lp[c], G[:, c] at Z[:, c].  Narrow Float64 Dense chains
+# (docs/src/nn_example.md:112-118) run one fused forward + reverse launch and one reduction launch for all columns.
+function logdensity_grad_batch(ctx::Ctx, Z::AbstractMatrix{<:Real})
+    ZZ = Matrix{Float64}(Z); lp = Vector{Float64}(undef, size(ZZ, 2)); G = Matrix{Float64}(undef, size(ZZ, 1), size(ZZ, 2))
+    GC.@preserve ZZ lp G check(ctx, ccall((:si_logdensity_grad_batch, LIB), Int32,
+                                          (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}), ctx.h, ZZ, size(ZZ, 2), lp, G))
+    return lp, G
+end
+
+# did the last logdensity_grad_batch run the fused narrow-chain kernel?
+function grad_kernel_info(ctx::Ctx)
+    fused = Ref{Int32}(0)
+    check(ctx, ccall((:si_grad_kernel_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), ctx.h, fused))
+    return fused[] != 0
+end
+
 # callable handed to AdvancedMH's DensityModel; MALA asks the model for value + gradient through
 # AdvancedMH.logdensity_and_gradient, which defaults to ForwardDiff on the closure [upstream AdvancedMH 0.6.2 src/MALA.jl]
 # -- dual numbers cannot enter a ccall, so the device gradient is plugged in at that hook.

@@ -48,6 +48,40 @@ def mala(logdensity_grad, m, itr, sigma_z, rng):
     return zs, lps, nacc / max(1, itr - 1)
 
 
+def mala_chains(logdensity_grad_batch, m, itr, sigma_z, rngs):
+    """`mala` for len(rngs) independent chains in lock-step: ONE `logdensity_grad_batch(Z) -> (lp[C], G[M, C])` call per
+    transition (the stacked device gradient, `Context.logdensity_grad_batch`) instead of one gradient call per chain.
+    Chain c draws from rngs[c] in exactly the order `mala` draws, so given the same gradients it IS `mala(..., rngs[c])`.
+    Returns (zs[M, itr, C], lps[itr, C], accept_rate[C])."""
+    nc = len(rngs)
+    z = np.empty((m, nc), order="F")
+    for c in range(nc):
+        z[:, c] = sigma_z * rngs[c].standard_normal(m)
+    lp, g = logdensity_grad_batch(z)
+    lp, g = np.array(lp, dtype=np.float64), np.array(g, dtype=np.float64, order="F")
+    zs = np.empty((m, itr, nc), order="F")
+    lps = np.empty((itr, nc), order="F")
+    zs[:, 0, :], lps[0, :] = z, lp
+    nacc = np.zeros(nc, dtype=np.int64)
+    h = 0.5 * sigma_z * sigma_z
+    inv2s2 = 1.0 / (2.0 * sigma_z * sigma_z)
+    for t in range(1, itr):
+        zp = np.empty((m, nc), order="F")
+        for c in range(nc):
+            zp[:, c] = z[:, c] + h * g[:, c] + sigma_z * rngs[c].standard_normal(m)
+        lpp, gp = logdensity_grad_batch(zp)
+        for c in range(nc):
+            # log q(z | z') - log q(z' | z)
+            fwd = zp[:, c] - z[:, c] - h * g[:, c]
+            bwd = z[:, c] - zp[:, c] - h * gp[:, c]
+            logq = -inv2s2 * (float(bwd @ bwd) - float(fwd @ fwd))
+            if -rngs[c].exponential() < lpp[c] - lp[c] + logq:
+                z[:, c], lp[c], g[:, c] = zp[:, c], lpp[c], gp[:, c]
+                nacc[c] += 1
+        zs[:, t, :], lps[t, :] = z, lp
+    return zs, lps, nacc / max(1, itr - 1)
+
+
 def _leapfrog(logdensity_grad, z, r, g, eps, minv=1.0):
     """One leapfrog step of H(z, r) = -lp(z) + r' M⁻¹ r / 2 with the diagonal M⁻¹ = minv."""
     r = r + 0.5 * eps * g

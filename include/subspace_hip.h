@@ -246,6 +246,28 @@ int32_t si_logdensity_grad_batch(si_ctx* ctx, const double* Z /* M x C */, int32
                                  double* grad_out /* M x C, column-major */);
 /* 1 when the last si_logdensity_grad_batch ran the fused narrow-chain kernel, 0 when it walked the per-point path */
 int32_t si_grad_kernel_info(si_ctx* ctx, int32_t* fused_out);
+/* :117-120  MALA(x -> MvNormal((sigma_z^2 / 2) .* x, sigma_z)) with the chain state on the device.  Shapes, column-major layout,
+ * `itr` (samples INCLUDING the initial state), accept_rate = accepts / (itr - 1) and the chain ids are si_sample_rwmh's; the state
+ * rules and the prior term are si_logdensity_grad_batch's.  G_out (may be NULL) receives d lp / d z at every returned state.
+ * Chain c draws from Philox chain chain_id0 + c: purpose 0 at step t gives the M normals n_t, purpose 1 at step t gives e_t.  With
+ * h = sigma_z^2 / 2:
+ *     t = 0:   z = sigma_z n_0;  (lp, g) = value and gradient at z
+ *     t >= 1:  zp = z + h g + sigma_z n_t;  (lpp, gp) at zp
+ *              fwd = zp - z - h g;  bwd = z - zp - h gp;  logq = -(bwd.bwd - fwd.fwd) / (2 sigma_z^2)
+ *              accept iff -e_t < lpp - lp + logq (a NaN rejects);  accept: (z, lp, g) = (zp, lpp, gp);  sample t = (z, lp, g)
+ * Chains of si_logdensity_grad_batch's fused class: every transition is four launches per pass queued on the stream (the K4
+ * launch, the fused forward + reverse kernel, its reduction, the accept kernel, which also forms the next proposal); the state stays
+ * on the device and the host synchronises ONCE, at the end.  More chains than the gradient workspace carries are walked in passes
+ * inside each transition.  Every sum has a fixed order: a chain's bits do not depend on nchains, on its column or on the run.
+ * EVERY OTHER CHAIN (Conv / MaxPool / flatten, SI_F32, the four later activations, wide layers) runs the same two MALA kernels, but
+ * the value and gradient of every proposal come column by column from si_logdensity_grad's path through the host: that route is
+ * slow and synchronises once per chain and transition.  It has the same definition.                                             */
+int32_t si_sample_mala(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, int32_t chain_id0, int32_t nchains,
+                       double* Z_out /* M x itr x C */, double* lp_out /* itr x C */, double* accept_rate_out /* C */,
+                       double* G_out /* M x itr x C or NULL */);
+/* the last si_sample_mala call: fused_out = 1 when it took the device-resident route, passes_out = gradient passes per transition
+ * (fused: ceil(nchains / points per pass); other route: one per chain)                                                          */
+int32_t si_mala_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out);
 /* same, additionally returning the model output (out_dim x B) of the LAST z -- forward-pass parity  */
 int32_t si_forward(si_ctx* ctx, const double* z /* M */, double* Yhat_out /* out_dim x B */);
 /* posterior predictive on NEW inputs: Yhat_out[:, :, c] = f_{W_swa + P*Z[:, c]}(Xnew), out_dim x Bn x C column-major.

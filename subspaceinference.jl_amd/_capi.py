@@ -95,6 +95,9 @@ SIGNATURES = {
                                  c_void_p]),
     "si_sample_rwmh_weights": (c_int32, [c_void_p, c_int64, c_double, c_uint64, c_int32, c_int32, c_void_p, c_void_p,
                                          c_void_p, c_void_p]),
+    "si_sample_mala": (c_int32, [c_void_p, c_int64, c_double, c_uint64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
+    "si_mala_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
     "si_rwmh_begin": (c_int32, [c_void_p, c_int64, c_double, c_uint64, c_int32, c_int32, c_int64]),
     "si_rwmh_step_eval": (c_int32, [c_void_p, c_void_p]),
     "si_rwmh_step_accept": (c_int32, [c_void_p, c_void_p]),
@@ -625,6 +628,23 @@ class Context:
         self._check(self.lib.si_sample_rwmh_weights(self.h, int(itr), float(sigma_z), int(seed), int(chain_id0), int(nchains),
                                                     _ptr(z), _ptr(lp), _ptr(acc), _ptr(w)))
         return z, lp, acc, w
+
+    def sample_mala(self, itr, sigma_z, seed, chain_id0=0, nchains=1, grad=False):
+        """si_sample_mala: MALA with the chain state on the device, on the library's Philox streams.  Returns (z, lp, acc), and
+        with grad=True (z, lp, acc, G) where G[:, t, c] = d lp / d z at z[:, t, c]."""
+        z = np.empty((self._m, int(itr), int(nchains)), dtype=np.float64, order="F")
+        lp = np.empty((int(itr), int(nchains)), dtype=np.float64, order="F")
+        acc = np.empty(int(nchains), dtype=np.float64)
+        g = np.empty((self._m, int(itr), int(nchains)), dtype=np.float64, order="F") if grad else None
+        self._check(self.lib.si_sample_mala(self.h, int(itr), float(sigma_z), int(seed), int(chain_id0), int(nchains),
+                                            _ptr(z), _ptr(lp), _ptr(acc), _ptr(g)))
+        return (z, lp, acc, g) if grad else (z, lp, acc)
+
+    def mala_kernel_info(self):
+        """(fused, passes) of the last sample_mala: did it take the device-resident route, gradient passes per transition"""
+        f, p = c_int32(0), c_int32(0)
+        self._check(self.lib.si_mala_kernel_info(self.h, byref(f), byref(p)))
+        return int(f.value), int(p.value)
 
     def set_chain_loop(self, on):
         """False / 0: one launch per layer and per step of si_sample_rwmh; True / 1 (default): small and narrow Dense chains run

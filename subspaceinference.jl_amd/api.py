@@ -138,7 +138,8 @@ def subspace_construction(model, cost, data, opt, T=10, c=1, M=3, print_freq=1, 
 
 def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=100, M=3, alg="rwmh",
                   backend="forwarddiff", *, sigma_z=None, sigma_m=None, sigma_p=None, device=0, ctx=None,
-                  seed=0, chain_id=0, return_z=False, nchains=1, include_prior=False, compute_dtype="f64"):
+                  seed=0, chain_id=0, return_z=False, nchains=1, include_prior=False, compute_dtype="f64",
+                  device_loop=False):
     """src/space_inference.jl:82-164 for a Chain model and alg = :rwmh.
 
     `density(z)` (:90-95: W_swa + P*z -> model_re -> forward over the FULL data -> Gaussian log-likelihood,
@@ -156,6 +157,10 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
     density of a Dense chain on the fp32 matrix instruction: X rounded once, W_swa + P*z formed in fp64 and rounded once per
     transition, fp32 activations, head + sum of squared errors in fp64 (lp within 1e-5 of the fp64 value, tests/test_gpu_f32.py).
     The gradient samplers (:mala / :hmc / :nuts) keep the fp64 reverse sweep either way.
+
+    `device_loop=True` (alg = :mala only; non-default) runs the chains with their state on the device (si_sample_mala): the
+    transition of `samplers.mala` on the library's Philox streams (seed, chain_id + c) instead of NumPy's PCG64, one host
+    synchronisation per call instead of one round trip per transition.  The default keeps the host loop and its results.
     """
     σ_z = σ_z if sigma_z is None else sigma_z
     σ_m = σ_m if sigma_m is None else sigma_m
@@ -185,6 +190,8 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
             ctx.infer_setup(table, n_par, M, W_swa, P, x, y, σ_m, compute_dtype=cdt)
         # include_prior=True adds the term the reference leaves dead after its `return` (quirk Q4); default: as the reference
         ctx.set_prior(σ_p if include_prior else 0.0)
+        if device_loop and a != "mala":
+            raise SubspaceError("device_loop=True is available for alg = :mala only")
         if nchains != 1 and a not in _RWMH_ALGS and a != "mala":
             raise SubspaceError("nchains > 1 is available for alg = :rwmh / :mh / :mala only")
         if a in _RWMH_ALGS:
@@ -200,7 +207,14 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
         else:
             # :mala (:117-120) / :hmc, :nuts (:139-160): the sampler logic is host control flow, every density + gradient
             # evaluation is the device reverse sweep (si_logdensity_grad) instead of M-wide ForwardDiff duals (:107)
-            if a == "mala" and nchains > 1:
+            if a == "mala" and device_loop:
+                z, lp, _ = ctx.sample_mala(itr, σ_z, seed, chain_id, nchains)
+                if nchains > 1:
+                    if return_z:
+                        return z, lp
+                    return [[w[:, t] for t in range(itr)] for w in (ctx.reconstruct(z[:, :, c]) for c in range(nchains))], lp
+                z, lp = z[:, :, 0], lp[:, 0]
+            elif a == "mala" and nchains > 1:
                 # the chains chain_id .. chain_id + nchains - 1 in lock-step: one stacked gradient call per transition
                 # (si_logdensity_grad_batch); chain c is the single-chain run with chain_id + c
                 rngs = [np.random.default_rng([int(seed), int(chain_id) + c]) for c in range(nchains)]
@@ -208,9 +222,10 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
                 if return_z:
                     return z, lp
                 return [[w[:, t] for t in range(itr)] for w in (ctx.reconstruct(z[:, :, c]) for c in range(nchains))], lp
-            rng = np.random.default_rng([int(seed), int(chain_id)])
-            fn = {"mala": samplers.mala, "hmc": samplers.hmc, "nuts": samplers.nuts}[a]
-            z, lp, _ = fn(ctx.logdensity_grad, M, itr, σ_z, rng)
+            else:
+                rng = np.random.default_rng([int(seed), int(chain_id)])
+                fn = {"mala": samplers.mala, "hmc": samplers.hmc, "nuts": samplers.nuts}[a]
+                z, lp, _ = fn(ctx.logdensity_grad, M, itr, σ_z, rng)
         if return_z:
             return z, lp
         w = ctx.reconstruct(z)  # :125  map(z -> W_swa + P*z.params, chm)

@@ -1,5 +1,5 @@
 // Declarations shared by the translation units of the C ABI (capi.hip: context + construction; capi_infer.hip: inference set-up,
-// density, gradient, predictive forward; capi_sample.hip: the RWMH samplers and the output map).  Nothing here is part of the
+// density, gradient, predictive forward; capi_sample.hip: the RWMH samplers and the output map; capi_mala.hip: the MALA sampler).  Nothing here is part of the
 // public interface (include/subspace_hip.h).  Buffers are owned by the types of dev_buf.h (through si_internal.h): no file of
 // the C ABI calls hipMalloc / hipFree / hipHostMalloc / hipHostFree or creates an event by hand.
 #pragma once
@@ -34,4 +34,11 @@ int32_t eval_density_all(si_ctx* ctx, int C);
 double mvnormal_c0(double d, double sigma);
 double prior_c0(const si_ctx* ctx);
 void fused_fill_program(const si_ctx* ctx, si::ChainFusedPlan& fp);
+// the gradient entry points' state rules; value and gradient at one point through the per-layer launches (synchronises); the fused
+// route of si_logdensity_grad_batch: its class / workgroups per point / points per pass, its workspace, one queued pass
+int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok);
+int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* grad_out);
+int vgrad_route(si_ctx* ctx, int64_t* G_out, int64_t* fit_out);
+int32_t vgrad_ensure(si_ctx* ctx, const char* who, int cap, int64_t G);
+void vgrad_pass(si_ctx* ctx, int nb, int64_t G, const double* z_dev, int n, double* lp_dev, double* gz_dev);
 }

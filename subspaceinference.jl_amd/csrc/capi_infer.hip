@@ -650,8 +650,9 @@ static int32_t ensure_grad(si_ctx* ctx) {
 }
 
 // value and gradient at ONE point through the per-layer launches: the body of si_logdensity_grad, and what
-// si_logdensity_grad_batch walks column by column for every chain outside the fused class (checked and bound by the caller)
-static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* grad_out) {
+// si_logdensity_grad_batch and si_sample_mala walk column by column for every chain outside the fused class (checked and bound
+// by the caller)
+int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* grad_out) {
   int32_t rc = ensure_chains(ctx, 1);
   if (rc != SI_OK) return rc;
   if ((rc = ensure_grad(ctx)) != SI_OK) return rc;
@@ -777,7 +778,7 @@ static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_ou
 }
 
 // the state rules and error texts shared by the two gradient entry points
-static int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok) {
+int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok) {
   if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_infer_setup first");
   if (!args_ok) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": bad argument");
   if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, std::string(who) + ": a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
@@ -826,20 +827,69 @@ static int vgrad_class(si_ctx* ctx) {
   return ctx->vg_class;
 }
 
+// The fused route as si_logdensity_grad_batch and si_sample_mala (capi_mala.hip) share it.  vgrad_route: the batch-tile class of
+// the chain set up (0: not of the fused class), the workgroups per point and the points one pass of launches may carry.
+int vgrad_route(si_ctx* ctx, int64_t* G_out, int64_t* fit_out) {
+  const int64_t B = ctx->B, ldw = pad_ld(ctx->iN);
+  const int nb = vgrad_class(ctx);
+  const int64_t G = nb > 0 ? (B + 16 * nb - 1) / (16 * nb) : 0;
+  // points per pass of launches: the workspace (weights, G partials of grad_w, grad_w per point) is capped like the forward
+  // workspace of the stacked density (SI_BATCH_BYTES), and a launch carries at most 65535 points in grid.y
+  const double per = 8.0 * ((double)ldw * ((double)G + 2.0) + (double)G + 2.0 * ctx->iM + 1.0);
+  *G_out = G;
+  *fit_out = nb > 0 ? (int64_t)std::min(65535.0, std::floor(SI_BATCH_BYTES / per)) : 0;
+  return nb;
+}
+
+// its workspace for `cap` points per pass
+int32_t vgrad_ensure(si_ctx* ctx, const char* who, int cap, int64_t G) {
+  if (ctx->vg_cap >= cap) return SI_OK;
+  const int64_t ldw = pad_ld(ctx->iN);
+  const int32_t M = ctx->iM;
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const size_t S = (size_t)cap;
+  ctx->vg_cap = 0;
+  if (!ctx->d_vg_z.alloc(S * M) || !ctx->d_vg_w.alloc(S * (size_t)ldw) || !ctx->d_vg_part.alloc(S * (size_t)G * (size_t)ldw) ||
+      !ctx->d_vg_ssepart.alloc(S * (size_t)G) || !ctx->d_vg_gw.alloc(S * (size_t)ldw) || !ctx->d_vg_lp.alloc(S) ||
+      !ctx->d_vg_gz.alloc(S * M)) {
+    for (DevBuf<double>* b : {&ctx->d_vg_z, &ctx->d_vg_w, &ctx->d_vg_part, &ctx->d_vg_ssepart, &ctx->d_vg_gw, &ctx->d_vg_lp, &ctx->d_vg_gz})
+      b->reset();
+    return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": workspace allocation failed");
+  }
+  ctx->vg_cap = cap;
+  return SI_OK;
+}
+
+// one pass of launches: value and gradient at the n <= vg_cap points z_dev[:, 0 .. n) (device) into lp_dev[n] / gz_dev[M x n]
+// (device).  Queued on the stream; nothing is copied, nothing synchronises.
+void vgrad_pass(si_ctx* ctx, int nb, int64_t G, const double* z_dev, int n, double* lp_dev, double* gz_dev) {
+  const int64_t N = ctx->iN, B = ctx->B, ldw = pad_ld(N);
+  const int32_t M = ctx->iM;
+  ChainVgradPlan vp;
+  const size_t lds = chain_vgrad_plan(vp, ctx->layers.data(), (int)ctx->layers.size(), B, nb);
+  const double s2 = ctx->sigma_m * ctx->sigma_m;
+  const double c0 = mvnormal_c0((double)ctx->out_dim * (double)B, ctx->sigma_m);
+  {
+    ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * n, (double)N * (M + 1 + n) * 8.0);
+    launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, z_dev, n, ctx->d_vg_w, ldw, ctx->num_cu);
+  }
+  {
+    ProfScope ps(ctx, SI_K_BACKWARD, 6.0 * (double)N * (double)B * n, 0.0);
+    launch_chain_vgrad(ctx->stream, vp, nb, lds, ctx->d_vg_w, ldw, ctx->d_X, ctx->d_Y, 1.0 / s2, ctx->d_vg_part, ldw, ctx->d_vg_ssepart, n);
+    launch_chain_vgrad_reduce(ctx->stream, ctx->d_vg_part, (int)G, N, ldw, ctx->d_vg_ssepart, ctx->d_vg_w, ldw, ctx->i_P, ctx->ldP, M,
+                              ctx->sigma_p, prior_c0(ctx), c0, s2, ctx->d_vg_gw, lp_dev, gz_dev, n);
+  }
+}
+
 int32_t si_logdensity_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double* lp_out, double* grad_out) {
   CHECK_CTX(ctx);
   int32_t rc = grad_entry_check(ctx, "si_logdensity_grad_batch", Z && C >= 1 && lp_out && grad_out);
   if (rc != SI_OK) return rc;
   BIND(ctx);
   ctx->last_grad_fused = 0;
-  const int64_t N = ctx->iN, B = ctx->B, ldw = pad_ld(N);
   const int32_t M = ctx->iM;
-  const int nb = vgrad_class(ctx);
-  const int64_t G = nb > 0 ? (B + 16 * nb - 1) / (16 * nb) : 0;
-  // points per pass of launches: the workspace (weights, G partials of grad_w, grad_w per point) is capped like the forward
-  // workspace of the stacked density (SI_BATCH_BYTES), and a launch carries at most 65535 points in grid.y
-  const double per = 8.0 * ((double)ldw * ((double)G + 2.0) + (double)G + 2.0 * M + 1.0);
-  const int64_t fit = nb > 0 ? (int64_t)std::min(65535.0, std::floor(SI_BATCH_BYTES / per)) : 0;
+  int64_t G = 0, fit = 0;
+  const int nb = vgrad_route(ctx, &G, &fit);
   if (fit < 1) {
     // every other chain (Conv / MaxPool / flatten, SI_F32, the four later activations, wide layers): column by column through the
     // single-point path -- the same code, the same bits as C calls of si_logdensity_grad
@@ -847,37 +897,11 @@ int32_t si_logdensity_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double
       if ((rc = logdensity_grad_point(ctx, Z + (size_t)M * c, lp_out + c, grad_out + (size_t)M * c)) != SI_OK) return rc;
     return SI_OK;
   }
-  const int cap = (int)std::min<int64_t>(fit, C);
-  if (ctx->vg_cap < cap) {
-    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t S = (size_t)cap;
-    ctx->vg_cap = 0;
-    if (!ctx->d_vg_z.alloc(S * M) || !ctx->d_vg_w.alloc(S * (size_t)ldw) || !ctx->d_vg_part.alloc(S * (size_t)G * (size_t)ldw) ||
-        !ctx->d_vg_ssepart.alloc(S * (size_t)G) || !ctx->d_vg_gw.alloc(S * (size_t)ldw) || !ctx->d_vg_lp.alloc(S) ||
-        !ctx->d_vg_gz.alloc(S * M)) {
-      for (DevBuf<double>* b : {&ctx->d_vg_z, &ctx->d_vg_w, &ctx->d_vg_part, &ctx->d_vg_ssepart, &ctx->d_vg_gw, &ctx->d_vg_lp, &ctx->d_vg_gz})
-        b->reset();
-      return fail(ctx, SI_ERR_NOMEM, "si_logdensity_grad_batch: workspace allocation failed");
-    }
-    ctx->vg_cap = cap;
-  }
-  ChainVgradPlan vp;
-  const size_t lds = chain_vgrad_plan(vp, ctx->layers.data(), (int)ctx->layers.size(), B, nb);
-  const double s2 = ctx->sigma_m * ctx->sigma_m;
-  const double c0 = mvnormal_c0((double)ctx->out_dim * (double)B, ctx->sigma_m);
+  if ((rc = vgrad_ensure(ctx, "si_logdensity_grad_batch", (int)std::min<int64_t>(fit, C), G)) != SI_OK) return rc;
   for (int32_t p0 = 0; p0 < C; p0 += ctx->vg_cap) {
     const int n = std::min<int32_t>(ctx->vg_cap, C - p0);
     SI_HIP(ctx, hipMemcpyAsync(ctx->d_vg_z, Z + (size_t)M * p0, (size_t)M * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    {
-      ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * n, (double)N * (M + 1 + n) * 8.0);
-      launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, ctx->d_vg_z, n, ctx->d_vg_w, ldw, ctx->num_cu);
-    }
-    {
-      ProfScope ps(ctx, SI_K_BACKWARD, 6.0 * (double)N * (double)B * n, 0.0);
-      launch_chain_vgrad(ctx->stream, vp, nb, lds, ctx->d_vg_w, ldw, ctx->d_X, ctx->d_Y, 1.0 / s2, ctx->d_vg_part, ldw, ctx->d_vg_ssepart, n);
-      launch_chain_vgrad_reduce(ctx->stream, ctx->d_vg_part, (int)G, N, ldw, ctx->d_vg_ssepart, ctx->d_vg_w, ldw, ctx->i_P, ctx->ldP, M,
-                                ctx->sigma_p, prior_c0(ctx), c0, s2, ctx->d_vg_gw, ctx->d_vg_lp, ctx->d_vg_gz, n);
-    }
+    vgrad_pass(ctx, nb, G, ctx->d_vg_z, n, ctx->d_vg_lp, ctx->d_vg_gz);
     SI_HIP(ctx, hipGetLastError());
     SI_HIP(ctx, hipMemcpyAsync(lp_out + p0, ctx->d_vg_lp, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SI_HIP(ctx, hipMemcpyAsync(grad_out + (size_t)M * p0, ctx->d_vg_gz, (size_t)M * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

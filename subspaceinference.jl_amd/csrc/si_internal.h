@@ -296,6 +296,14 @@ struct InferState {
   int vg_cap = 0;
   DevBuf<double> d_vg_z, d_vg_w, d_vg_part, d_vg_ssepart, d_vg_gw, d_vg_lp, d_vg_gz;
   int last_grad_fused = 0;          // si_grad_kernel_info
+  // si_sample_mala (capi_mala.hip, kernels_mala.hip): the chains' state, the proposals with their values and gradients, and the
+  // device-side gradient samples; its own buffers, so that the per-point gradient path may use d_zprop between the two kernels
+  int mala_cap = 0;
+  DevBuf<double> d_mala_z, d_mala_g, d_mala_zp, d_mala_gp;   // M x C each
+  DevBuf<double> d_mala_lp, d_mala_lpp;                      // C each
+  DevBuf<int64_t> d_mala_nacc;                               // C
+  DevBuf<double> d_outG;                                     // M x itr x C, kept between calls like d_outZ
+  int last_mala_fused = 0, last_mala_passes = 0;             // si_mala_kernel_info
 };
 
 struct Ctx : CtxCore, ConstructState, InferState {};
@@ -645,6 +653,13 @@ void launch_chain_vgrad_reduce(hipStream_t st, const double* part, int G, int64_
                                double c0, double sigma2, double* gw, double* lp_out, double* gz_out, int npoints);
 int dense_fused_slot_feats(int32_t out);   // features per head slot of the fused fp64 layer (kernels_gemm.hip: BM / WM)
 // K6
+// kernels_mala.hip: zprop = z + (sigma_z^2 / 2) g + sigma_z n_step for C chains (first: sigma_z n_0); transition `step` of C chains
+// given the proposals' lpp / gp, sample `step` written to Z_out / lp_out / G_out (G_out may be NULL), the next proposal formed
+void launch_mala_propose(hipStream_t st, const double* z, const double* g, double* zprop, int32_t M, int32_t C, double sigma_z,
+                         uint64_t seed, int32_t chain_id0, uint64_t step, bool first);
+void launch_mala_accept(hipStream_t st, double* z, double* lp, double* g, double* zprop, const double* lpp, const double* gp,
+                        int64_t* nacc, int32_t M, int32_t C, double sigma_z, uint64_t seed, int32_t chain_id0, uint64_t step,
+                        double* Z_out, double* lp_out, double* G_out, int64_t itr, bool propose_next);
 void launch_rwmh_init(hipStream_t st, double* zcur, double* lpcur, int64_t* nacc, uint64_t* steps, int32_t M, int32_t C);
 void launch_rwmh_propose(hipStream_t st, const double* zcur, double* zprop, int32_t M, int32_t C,
                          double sigma_z, uint64_t seed, int32_t chain_id0, const uint64_t* steps);

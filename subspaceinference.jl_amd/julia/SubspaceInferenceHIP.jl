@@ -319,6 +319,25 @@ function grad_kernel_info(ctx::Ctx)
     return fused[] != 0
 end
 
+# :117-120 with the chain state on the device (si_sample_mala): the transition of the reference's MALA on the library's Philox streams
+# (seed, chain_id + c).  Narrow Float64 Dense chains queue every transition on the stream and synchronise once, at the end.
+# Returns Z (M x itr x nchains), lp (itr x nchains), the acceptance rates, and with grad = true the gradients at every state.
+function sample_mala(ctx::Ctx, itr, σ_z, M; seed = 0, chain_id = 0, nchains = 1, grad = false)
+    Z = Array{Float64}(undef, M, itr, nchains); lp = Matrix{Float64}(undef, itr, nchains); acc = Vector{Float64}(undef, nchains)
+    G = grad ? Array{Float64}(undef, M, itr, nchains) : nothing
+    GC.@preserve Z lp acc G check(ctx, ccall((:si_sample_mala, LIB), Int32,
+        (Ptr{Cvoid}, Int64, Float64, UInt64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        ctx.h, itr, σ_z, seed, chain_id, nchains, Z, lp, acc, G === nothing ? C_NULL : pointer(G)))
+    return grad ? (Z, lp, acc, G) : (Z, lp, acc)
+end
+
+# (fused, passes) of the last sample_mala: did it take the device-resident route; gradient passes per transition
+function mala_kernel_info(ctx::Ctx)
+    fused = Ref{Int32}(0); passes = Ref{Int32}(0)
+    check(ctx, ccall((:si_mala_kernel_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}), ctx.h, fused, passes))
+    return fused[] != 0, Int(passes[])
+end
+
 # callable handed to AdvancedMH's DensityModel; MALA asks the model for value + gradient through
 # AdvancedMH.logdensity_and_gradient, which defaults to ForwardDiff on the closure [upstream AdvancedMH 0.6.2 src/MALA.jl]
 # -- dual numbers cannot enter a ccall, so the device gradient is plugged in at that hook.
@@ -338,10 +357,13 @@ end
 # include_prior = true adds the term the reference writes after its `return` (dead code, :95); default: as the reference
 # compute_dtype = :f32 (non-default; SURVEY section 0 Q6): the density of a Dense or Conv chain on the fp32 matrix instructions -- X rounded
 # once, W_swa + P*z formed in Float64 and rounded once per transition, Float32 activations, head + sum of squared errors in Float64
+# device_loop = true (alg = :mala only; non-default): the chain runs with its state on the device (sample_mala) instead of
+# AdvancedMH's host loop; the default keeps the reference's own sampler calls
 function sub_inference(in_model, data, W_swa, P; σ_z = 1.0, σ_m = 1.0, σ_p = 1.0, itr = 100, M = 3, alg = :rwmh,
                        backend = :forwarddiff, device = 0, ctx = Ctx(device), seed = 0, chain_id = 0, include_prior = false,
-                       compute_dtype = :f64)
+                       compute_dtype = :f64, device_loop = false)
     alg == :mh && (alg = :rwmh)                                     # README.md:153-154
+    (device_loop && alg != :mala) && throw("device_loop = true is available for alg = :mala only")
     alg in (:rwmh, :mala, :hmc, :nuts) || throw("$alg is not available")       # :162 (:advi is outside this build)
     in_model isa Chain || throw("Error: density function is not avaliable for this model")
     compute_dtype in (:f64, :f32) || throw("compute_dtype must be :f64 (the reference's arithmetic) or :f32")
@@ -364,6 +386,10 @@ function sub_inference(in_model, data, W_swa, P; σ_z = 1.0, σ_m = 1.0, σ_p = 
             (Ptr{Cvoid}, Int64, Float64, UInt64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}),
             ctx.h, itr, σ_z, seed, chain_id, 1, Z, lp, acc, Wm))
         return [Wm[:, t] for t in 1:itr], lp
+    end
+    if alg == :mala && device_loop
+        Z, lp, _ = sample_mala(ctx, itr, σ_z, M; seed = seed, chain_id = chain_id)
+        return reconstruct(ctx, Z[:, :, 1], N), lp[:, 1]
     end
     density = DeviceDensity(ctx)
     ℓπ_grad(θ) = logdensity_grad(ctx, θ)

@@ -268,6 +268,46 @@ int32_t si_sample_mala(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, 
 /* the last si_sample_mala call: fused_out = 1 when it took the device-resident route, passes_out = gradient passes per transition
  * (fused: ceil(nchains / points per pass); other route: one per chain)                                                          */
 int32_t si_mala_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out);
+/* :126-138  ADVI with its state on the device.  Restates
+ *     AdvancedVI.vi(density, ADVI(S, T), theta -> TuringDiagMvNormal(theta[1:M], exp.(theta[M+1:2M])), rand(MvNormal(zeros(2M), sigma_z)))
+ * followed by rand(q, D) (AdvancedVI 0.1.3), with that version's default optimiser TruncatedADAGrad(eta = 0.1, tau = 1.0,
+ * n_iter = 100) [upstream, from memory, unverifiable offline] and its ELBO = mean of the density at S draws of q + the entropy of
+ * q, differentiated through z = mu + exp(omega) .* eta [upstream, from memory, unverifiable offline].  THE DEFINITION:
+ * run r draws from Philox chain chain_id0 + r.  Purposes 0 and 1 are RWMH's and MALA's; here purpose 2 is the initial point,
+ * 3 the step draws, 4 the final draws; in all of them block j gives components 2j and 2j + 1.  nblk = ceil(M / 2).
+ *     theta = [mu; omega] in R^2M
+ *     init      theta_0 = sigma_z n,  n = the 2M normals of (purpose 2, step 0, blocks 0 .. M-1)
+ *     step t = 0 .. T-1, with sigma = exp(omega) taken from theta_t:
+ *        eta_k = the M normals of (purpose 3, step t, block k nblk + j),  k = 0 .. S-1
+ *        z_k   = mu + sigma .* eta_k;  (lp_k, g_k) = value and gradient at z_k  (prior term as si_infer_set_prior set it)
+ *        H     = M (log 2 pi + 1) / 2 + sum_m omega_m
+ *        elbo_t = (((lp_0 / S + H) + lp_1 / S) + ...) + lp_{S-1} / S
+ *        dmu_m    = -(sum_k g_k[m]) / S                           (k ascending, from 0.0)
+ *        domega_m = -(sum_k (g_k[m] eta_k[m]) sigma_m) / S - 1    (k ascending, from 0.0)
+ *        ring     slot t mod W of component p is set to d_p^2
+ *        s_p      = sum over slots 0 .. W-1 in slot order (from 0.0); unwritten slots are 0
+ *        theta_{t+1,p} = theta_{t,p} - d_p (eta / (tau + sqrt(s_p)))
+ *     draws     z_i = mu_T + exp(omega_T) .* n_i,  n_i = the M normals of (purpose 4, step i),  i = 0 .. D-1
+ * There is no guard against a non-finite lp: theta goes NaN as the reference's would, and elbo_out shows it.  Every sum has the
+ * order written above; sum_m omega_m has si_sample_mala's order (thread i of 256 adds its components 2j, 2j + 1 for j = i,
+ * i + 256, ..., then the wave sums, then (r0 + r1) + (r2 + r3)); log 2 pi is the literal 1.8378770664093453.  A run's bits therefore
+ * depend on nothing but (seed, chain, M, S, T, W, eta, tau, sigma_z) and the density -- not on nruns, its column, the pass split
+ * or the run.
+ * State rules: si_logdensity_grad_batch's.  SI_ERR_INVALID: T < 1, S < 1, S nblk >= 2^24, W outside 1 .. 1024, R < 1,
+ * chain_id0 < 0, sigma_z <= 0, tau <= 0, eta <= 0, D < 0, theta_out NULL, Z_out NULL with D > 0.
+ * Chains of si_logdensity_grad_batch's fused class: per step the R S points go through the fused value + gradient launches in
+ * passes of the workspace's capacity, then ONE update launch, which also forms the next step's points; nothing is copied and the
+ * host synchronises ONCE, at the end.  EVERY OTHER CHAIN (Conv / MaxPool / flatten, SI_F32, the four later activations, wide
+ * layers) runs the same two kernels, but the points go to the host and their values and gradients come back column by column
+ * through si_logdensity_grad's path: slow, one round trip per point and step.  It has the same definition.                      */
+int32_t si_fit_advi(si_ctx* ctx, int64_t max_iters /* T */, int32_t samples_per_step /* S */, double sigma_z, double eta, double tau,
+                    int32_t window /* W */, uint64_t seed, int32_t chain_id0, int32_t nruns /* R */, int64_t ndraws /* D */,
+                    double* theta_out /* 2M x R */, double* Z_out /* M x D x R, NULL iff D == 0 */,
+                    double* elbo_out /* T x R or NULL */, double* theta_trace_out /* 2M x (T+1) x R or NULL */,
+                    double* points_out /* M x S x T x R or NULL */);
+/* the last si_fit_advi call: fused_out = 1 when it took the device-resident route, passes_out = gradient passes per step
+ * (fused: ceil(R S / points per pass); other route: one per point)                                                               */
+int32_t si_advi_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out);
 /* same, additionally returning the model output (out_dim x B) of the LAST z -- forward-pass parity  */
 int32_t si_forward(si_ctx* ctx, const double* z /* M */, double* Yhat_out /* out_dim x B */);
 /* posterior predictive on NEW inputs: Yhat_out[:, :, c] = f_{W_swa + P*Z[:, c]}(Xnew), out_dim x Bn x C column-major.

@@ -98,6 +98,9 @@ SIGNATURES = {
     "si_sample_mala": (c_int32, [c_void_p, c_int64, c_double, c_uint64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                  c_void_p]),
     "si_mala_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
+    "si_fit_advi": (c_int32, [c_void_p, c_int64, c_int32, c_double, c_double, c_double, c_int32, c_uint64, c_int32, c_int32, c_int64,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "si_advi_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
     "si_rwmh_begin": (c_int32, [c_void_p, c_int64, c_double, c_uint64, c_int32, c_int32, c_int64]),
     "si_rwmh_step_eval": (c_int32, [c_void_p, c_void_p]),
     "si_rwmh_step_accept": (c_int32, [c_void_p, c_void_p]),
@@ -148,6 +151,27 @@ SIGNATURES = {
 }
 
 _lib = None
+
+# What si_fit_advi refuses with SI_ERR_INVALID (include/subspace_hip.h), mirrored: (the refusal, its test).  The comparisons are
+# written so that a NaN refuses, as the library's are.
+ADVI_REFUSALS = (
+    ("max_iters < 1", lambda a: not a["T"] >= 1),
+    ("samples_per_step < 1", lambda a: not a["S"] >= 1),
+    ("samples_per_step * ceil(M / 2) >= 2^24", lambda a: a["S"] * ((a["M"] + 1) // 2) >= 2 ** 24),
+    ("window outside 1 .. 1024", lambda a: not 1 <= a["W"] <= 1024),
+    ("nruns < 1", lambda a: not a["R"] >= 1),
+    ("chain_id0 < 0", lambda a: not a["chain_id0"] >= 0),
+    ("sigma_z <= 0", lambda a: not a["sigma_z"] > 0.0),
+    ("tau <= 0", lambda a: not a["tau"] > 0.0),
+    ("eta <= 0", lambda a: not a["eta"] > 0.0),
+    ("ndraws < 0", lambda a: not a["D"] >= 0),
+)
+
+
+def advi_refusal(m, max_iters, samples_per_step, sigma_z, eta, tau, window, chain_id0, nruns, ndraws):
+    """the first refusal of ADVI_REFUSALS that holds, or None"""
+    a = dict(M=m, T=max_iters, S=samples_per_step, sigma_z=sigma_z, eta=eta, tau=tau, W=window, chain_id0=chain_id0, R=nruns, D=ndraws)
+    return next((what for what, bad in ADVI_REFUSALS if bad(a)), None)
 
 
 def load():
@@ -644,6 +668,33 @@ class Context:
         """(fused, passes) of the last sample_mala: did it take the device-resident route, gradient passes per transition"""
         f, p = c_int32(0), c_int32(0)
         self._check(self.lib.si_mala_kernel_info(self.h, byref(f), byref(p)))
+        return int(f.value), int(p.value)
+
+    def fit_advi(self, max_iters, sigma_z, seed, samples_per_step=10, eta=0.1, tau=1.0, window=100, chain_id0=0, nruns=1,
+                 ndraws=None, trace=False):
+        """si_fit_advi: the reference's ADVI (src/space_inference.jl:126-138) with its state on the device, on the library's Philox
+        streams; the defaults are the reference's ADVI(10, itr) and AdvancedVI's TruncatedADAGrad(0.1, 1.0, 100).  ndraws=None
+        draws max_iters points from the fitted q, as the reference's rand(q, itr).  Returns (theta [2M, R], Z [M, D, R],
+        elbo [T, R]), and with trace=True also (theta_trace [2M, T+1, R], points [M, S, T, R])."""
+        t, s, w, r = int(max_iters), int(samples_per_step), int(window), int(nruns)
+        d = t if ndraws is None else int(ndraws)
+        why = advi_refusal(self._m, t, s, float(sigma_z), float(eta), float(tau), w, int(chain_id0), r, d)
+        if why is not None:   # (before any array is sized by a refused value; the library refuses the same arguments)
+            raise SubspaceError("si_fit_advi: bad argument (%s)" % why, SI_ERR_INVALID)
+        m = self._m
+        theta = np.empty((2 * m, r), dtype=np.float64, order="F")
+        z = np.empty((m, d, r), dtype=np.float64, order="F")
+        elbo = np.empty((t, r), dtype=np.float64, order="F")
+        tr = np.empty((2 * m, t + 1, r), dtype=np.float64, order="F") if trace else None
+        pts = np.empty((m, s, t, r), dtype=np.float64, order="F") if trace else None
+        self._check(self.lib.si_fit_advi(self.h, t, s, float(sigma_z), float(eta), float(tau), w, int(seed), int(chain_id0), r, d,
+                                         _ptr(theta), _ptr(z) if d > 0 else None, _ptr(elbo), _ptr(tr), _ptr(pts)))
+        return (theta, z, elbo, tr, pts) if trace else (theta, z, elbo)
+
+    def advi_kernel_info(self):
+        """(fused, passes) of the last fit_advi: did it take the device-resident route, gradient passes per step"""
+        f, p = c_int32(0), c_int32(0)
+        self._check(self.lib.si_advi_kernel_info(self.h, byref(f), byref(p)))
         return int(f.value), int(p.value)
 
     def set_chain_loop(self, on):

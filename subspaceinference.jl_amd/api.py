@@ -158,17 +158,20 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
     transition, fp32 activations, head + sum of squared errors in fp64 (lp within 1e-5 of the fp64 value, tests/test_gpu_f32.py).
     The gradient samplers (:mala / :hmc / :nuts) keep the fp64 reverse sweep either way.
 
-    `device_loop=True` (alg = :mala only; non-default) runs the chains with their state on the device (si_sample_mala): the
+    `device_loop=True` (alg = :mala and :advi; non-default) runs the chains with their state on the device (si_sample_mala): the
     transition of `samplers.mala` on the library's Philox streams (seed, chain_id + c) instead of NumPy's PCG64, one host
     synchronisation per call instead of one round trip per transition.  The default keeps the host loop and its results.
+    alg = :advi exists as the device loop only (si_fit_advi: the reference's ADVI(10, itr) fit and its `rand(q, itr)` on the Philox
+    streams, one run per call): without the keyword it raises, as it always has; lp is zeros(itr), as in the reference (:136).
     """
     σ_z = σ_z if sigma_z is None else sigma_z
     σ_m = σ_m if sigma_m is None else sigma_m
     σ_p = σ_p if sigma_p is None else sigma_p
     a = _alg_name(alg)
-    if a == "advi":
-        raise SubspaceError("advi is outside what this build accelerates (SURVEY section 2)")
-    if a not in _RWMH_ALGS and a not in ("mala", "hmc", "nuts"):
+    if a == "advi" and (not device_loop or nchains != 1):
+        # (this build has no host ADVI loop for a default to fall back to: the fit exists as the device loop only, one run per call)
+        raise SubspaceError("alg = :advi is available with device_loop=True and nchains = 1 only (si_fit_advi; DESIGN section 13)")
+    if a not in _RWMH_ALGS and a not in ("mala", "hmc", "nuts", "advi"):
         raise SubspaceError("%s is not available" % a)  # reference :162
     if not isinstance(in_model, flux.Chain):
         raise SubspaceError("Error: density function is not avaliable for this model")  # [sic] reference :103
@@ -190,8 +193,8 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
             ctx.infer_setup(table, n_par, M, W_swa, P, x, y, σ_m, compute_dtype=cdt)
         # include_prior=True adds the term the reference leaves dead after its `return` (quirk Q4); default: as the reference
         ctx.set_prior(σ_p if include_prior else 0.0)
-        if device_loop and a != "mala":
-            raise SubspaceError("device_loop=True is available for alg = :mala only")
+        if device_loop and a not in ("mala", "advi"):
+            raise SubspaceError("device_loop=True is available for alg = :mala and :advi only")
         if nchains != 1 and a not in _RWMH_ALGS and a != "mala":
             raise SubspaceError("nchains > 1 is available for alg = :rwmh / :mh / :mala only")
         if a in _RWMH_ALGS:
@@ -207,7 +210,11 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
         else:
             # :mala (:117-120) / :hmc, :nuts (:139-160): the sampler logic is host control flow, every density + gradient
             # evaluation is the device reverse sweep (si_logdensity_grad) instead of M-wide ForwardDiff duals (:107)
-            if a == "mala" and device_loop:
+            if a == "advi":
+                # :126-138: vi(density, ADVI(10, itr), q, theta_0), then rand(q, itr); the reference returns zeros(itr) for lp
+                _, z, _ = ctx.fit_advi(itr, σ_z, seed, chain_id0=chain_id)
+                z, lp = z[:, :, 0], np.zeros(itr)
+            elif a == "mala" and device_loop:
                 z, lp, _ = ctx.sample_mala(itr, σ_z, seed, chain_id, nchains)
                 if nchains > 1:
                     if return_z:
@@ -243,7 +250,7 @@ def inference(*args, **kwargs):
 def subspace_inference(model, cost, data, opt, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=1000, T=25, c=1, M=20,
                        print_freq=1, alg="rwmh", backend="forwarddiff", method="subspace", *, sigma_z=None,
                        sigma_m=None, sigma_p=None, device=0, ctx=None, seed=0, verbose=True, return_z=False,
-                       compute_dtype="f64"):
+                       compute_dtype="f64", device_loop=False):
     """src/space_inference.jl:33-54: construction, then sampling; returns (chn, lp, W_swa).
     W_swa and P stay on the device between the two stages (no host round trip)."""
     m = _alg_name(method)
@@ -260,7 +267,7 @@ def subspace_inference(model, cost, data, opt, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr
                                          verbose=verbose, keep_on_device=True)
         chn, lp = sub_inference(model, data, None, None, σ_z=σ_z, σ_m=σ_m, σ_p=σ_p, itr=itr, M=M, alg=alg,
                                 backend=backend, sigma_z=sigma_z, sigma_m=sigma_m, ctx=ctx, seed=seed,
-                                return_z=return_z, compute_dtype=compute_dtype)
+                                return_z=return_z, compute_dtype=compute_dtype, device_loop=device_loop)
         return chn, lp, w_swa
     finally:
         if own:

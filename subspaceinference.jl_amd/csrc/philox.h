@@ -45,16 +45,22 @@ __host__ __device__ inline Philox4 philox_draw(uint64_t seed, uint32_t chain, ui
                        (uint32_t)(seed >> 32));
 }
 
-// two standard normals (components 2*block, 2*block+1 of the proposal noise of `step`)
-__device__ inline void philox_normal2(uint64_t seed, uint32_t chain, uint64_t step, uint32_t block,
-                                      double& n0, double& n1) {
-  const Philox4 x = philox_draw(seed, chain, step, 0u, block);
+// two standard normals from the stream of `purpose`, block `block` (Box-Muller on the block's two 53-bit uniforms)
+__device__ inline void philox_normal2_purpose(uint64_t seed, uint32_t chain, uint64_t step, uint32_t purpose, uint32_t block,
+                                              double& n0, double& n1) {
+  const Philox4 x = philox_draw(seed, chain, step, purpose, block);
   const double u1 = u53(x.v[1], x.v[0]);
   const double u2 = u53(x.v[3], x.v[2]);
   const double r = sqrt(-2.0 * log(u1));
   const double t = (2.0 * 3.14159265358979323846) * u2;
   n0 = r * cos(t);
   n1 = r * sin(t);
+}
+
+// purpose 0: components 2*block, 2*block+1 of the proposal noise of `step` (the same operations as ever: the same bits)
+__device__ inline void philox_normal2(uint64_t seed, uint32_t chain, uint64_t step, uint32_t block,
+                                      double& n0, double& n1) {
+  philox_normal2_purpose(seed, chain, step, 0u, block, n0, n1);
 }
 
 __device__ inline double philox_randexp(uint64_t seed, uint32_t chain, uint64_t step) {

@@ -304,6 +304,15 @@ struct InferState {
   DevBuf<int64_t> d_mala_nacc;                               // C
   DevBuf<double> d_outG;                                     // M x itr x C, kept between calls like d_outZ
   int last_mala_fused = 0, last_mala_passes = 0;             // si_mala_kernel_info
+  // si_fit_advi (capi_advi.hip, kernels_advi.hip): the state theta = [mu; omega] of R runs, the optimiser's ring of squared
+  // gradients, the step's draws eta with the points made from them, the points' values and gradients, and the device-side traces
+  // (grown on demand and kept between calls; every call ends synchronised, so none is in use when it is replaced)
+  DevBuf<double> d_advi_theta;                              // 2M x R
+  DevBuf<double> d_advi_ring;                                // W x 2M x R (component fastest, then slot)
+  DevBuf<double> d_advi_eta, d_advi_z, d_advi_g;             // M x S x R each
+  DevBuf<double> d_advi_lp;                                  // S x R
+  DevBuf<double> d_advi_trace, d_advi_pts;                   // 2M x (T+1) x R, M x S x T x R: only when asked for, kept between calls
+  int last_advi_fused = 0, last_advi_passes = 0;             // si_advi_kernel_info
 };
 
 struct Ctx : CtxCore, ConstructState, InferState {};
@@ -660,6 +669,19 @@ void launch_mala_propose(hipStream_t st, const double* z, const double* g, doubl
 void launch_mala_accept(hipStream_t st, double* z, double* lp, double* g, double* zprop, const double* lpp, const double* gp,
                         int64_t* nacc, int32_t M, int32_t C, double sigma_z, uint64_t seed, int32_t chain_id0, uint64_t step,
                         double* Z_out, double* lp_out, double* G_out, int64_t itr, bool propose_next);
+// kernels_advi.hip (the step is defined in its header comment): R runs, one workgroup each.  AdviRun: what both kernels share.
+struct AdviRun {
+  double *theta, *ring, *eta, *z;       // 2M x R, W x 2M x R, M x S x R, M x S x R
+  double *trace_out, *pts_out;          // 2M x (T+1) x R, M x S x T x R, or NULL
+  int32_t M, S, W, chain_id0;
+  int64_t T;
+  uint64_t seed;
+};
+// first: theta_0, the cleared ring and the points of step 0;  final: the D draws from theta as it stands
+void launch_advi_draw(hipStream_t st, const AdviRun& a, int32_t R, double sigma_z, bool first, bool final, double* Z_out, int64_t D);
+// step t given (lp, g) at its points: elbo_t, d, the ring, s, theta_{t+1}, the traces and (form_next) the points of step t + 1
+void launch_advi_update(hipStream_t st, const AdviRun& a, int32_t R, const double* lp, const double* g, double eta_opt, double tau,
+                        int64_t t, double* elbo_out, bool form_next);
 void launch_rwmh_init(hipStream_t st, double* zcur, double* lpcur, int64_t* nacc, uint64_t* steps, int32_t M, int32_t C);
 void launch_rwmh_propose(hipStream_t st, const double* zcur, double* zprop, int32_t M, int32_t C,
                          double sigma_z, uint64_t seed, int32_t chain_id0, const uint64_t* steps);

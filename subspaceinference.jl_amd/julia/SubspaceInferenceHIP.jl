@@ -25,6 +25,7 @@
 #   * :rwmh / :mh sampler loop (:111-116)                                                        -> GPU (si_sample_rwmh)
 #   * :mala / :hmc / :nuts sampler logic (:117-120, :139-160)                                    -> the reference's own
 #       AdvancedMH / AdvancedHMC calls, unchanged, driven by the two device callbacks above
+#   * :advi (:126-138), with device_loop = true only                                             -> GPU (si_fit_advi)
 #   * output map :125                                                                            -> GPU (si_reconstruct)
 #   * more than one GPU: one Julia process per GPU (Distributed workers), one Ctx each, joined by the RCCL communicator
 #       INSIDE the library (si_comm_*): `init_gpus()`, then `subspace_inference(...; ngpu = 8, nchains = 8)`,
@@ -338,6 +339,30 @@ function mala_kernel_info(ctx::Ctx)
     return fused[] != 0, Int(passes[])
 end
 
+# :126-138 with the variational state on the device (si_fit_advi): vi(density, ADVI(S, T), q, θ_0) and rand(q, D) restated on the
+# library's Philox streams (seed, chain_id + r), with AdvancedVI 0.1.3's default TruncatedADAGrad(η, τ, window).  Narrow Float64
+# Dense chains queue every step on the stream and synchronise once, at the end.  Returns θ (2M x nruns), Z (M x D x nruns) and
+# the ELBO estimates (T x nruns); with trace = true also θ_0 .. θ_T (2M x (T+1) x nruns) and every step's points (M x S x T x nruns).
+function fit_advi(ctx::Ctx, max_iters, σ_z, M; seed = 0, samples_per_step = 10, η = 0.1, τ = 1.0, window = 100, chain_id = 0,
+                  nruns = 1, ndraws = max_iters, trace = false)
+    θ = Matrix{Float64}(undef, 2M, nruns); Z = Array{Float64}(undef, M, ndraws, nruns); elbo = Matrix{Float64}(undef, max_iters, nruns)
+    tr = trace ? Array{Float64}(undef, 2M, max_iters + 1, nruns) : nothing
+    pts = trace ? Array{Float64}(undef, M, samples_per_step, max_iters, nruns) : nothing
+    GC.@preserve θ Z elbo tr pts check(ctx, ccall((:si_fit_advi, LIB), Int32,
+        (Ptr{Cvoid}, Int64, Int32, Float64, Float64, Float64, Int32, UInt64, Int32, Int32, Int64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        ctx.h, max_iters, samples_per_step, σ_z, η, τ, window, seed, chain_id, nruns, ndraws, θ, ndraws == 0 ? C_NULL : pointer(Z), elbo,
+        tr === nothing ? C_NULL : pointer(tr), pts === nothing ? C_NULL : pointer(pts)))
+    return trace ? (θ, Z, elbo, tr, pts) : (θ, Z, elbo)
+end
+
+# (fused, passes) of the last fit_advi: did it take the device-resident route; gradient passes per step
+function advi_kernel_info(ctx::Ctx)
+    fused = Ref{Int32}(0); passes = Ref{Int32}(0)
+    check(ctx, ccall((:si_advi_kernel_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}), ctx.h, fused, passes))
+    return fused[] != 0, Int(passes[])
+end
+
 # callable handed to AdvancedMH's DensityModel; MALA asks the model for value + gradient through
 # AdvancedMH.logdensity_and_gradient, which defaults to ForwardDiff on the closure [upstream AdvancedMH 0.6.2 src/MALA.jl]
 # -- dual numbers cannot enter a ccall, so the device gradient is plugged in at that hook.
@@ -357,14 +382,16 @@ end
 # include_prior = true adds the term the reference writes after its `return` (dead code, :95); default: as the reference
 # compute_dtype = :f32 (non-default; SURVEY section 0 Q6): the density of a Dense or Conv chain on the fp32 matrix instructions -- X rounded
 # once, W_swa + P*z formed in Float64 and rounded once per transition, Float32 activations, head + sum of squared errors in Float64
-# device_loop = true (alg = :mala only; non-default): the chain runs with its state on the device (sample_mala) instead of
-# AdvancedMH's host loop; the default keeps the reference's own sampler calls
+# device_loop = true (alg = :mala and :advi; non-default): the chain runs with its state on the device (sample_mala) instead of
+# AdvancedMH's host loop; the default keeps the reference's own sampler calls.  alg = :advi exists as the device loop only
+# (fit_advi): without the keyword it throws, as it always has; lp is zeros(itr), as in the reference (:138)
 function sub_inference(in_model, data, W_swa, P; σ_z = 1.0, σ_m = 1.0, σ_p = 1.0, itr = 100, M = 3, alg = :rwmh,
                        backend = :forwarddiff, device = 0, ctx = Ctx(device), seed = 0, chain_id = 0, include_prior = false,
                        compute_dtype = :f64, device_loop = false)
     alg == :mh && (alg = :rwmh)                                     # README.md:153-154
-    (device_loop && alg != :mala) && throw("device_loop = true is available for alg = :mala only")
-    alg in (:rwmh, :mala, :hmc, :nuts) || throw("$alg is not available")       # :162 (:advi is outside this build)
+    (device_loop && !(alg in (:mala, :advi))) && throw("device_loop = true is available for alg = :mala and :advi only")
+    (alg == :advi && !device_loop) && throw("alg = :advi is available with device_loop = true only (fit_advi)")
+    alg in (:rwmh, :mala, :hmc, :nuts, :advi) || throw("$alg is not available")       # :162
     in_model isa Chain || throw("Error: density function is not avaliable for this model")
     compute_dtype in (:f64, :f32) || throw("compute_dtype must be :f64 (the reference's arithmetic) or :f32")
     X, Y, insize = data_matrices(data)                              # split_data (src/libs.jl:75-77)
@@ -390,6 +417,10 @@ function sub_inference(in_model, data, W_swa, P; σ_z = 1.0, σ_m = 1.0, σ_p = 
     if alg == :mala && device_loop
         Z, lp, _ = sample_mala(ctx, itr, σ_z, M; seed = seed, chain_id = chain_id)
         return reconstruct(ctx, Z[:, :, 1], N), lp[:, 1]
+    end
+    if alg == :advi
+        _, Z, _ = fit_advi(ctx, itr, σ_z, M; seed = seed, chain_id = chain_id)   # :133-137 ADVI(10, itr), rand(q, itr)
+        return reconstruct(ctx, Z[:, :, 1], N), zeros(itr)                       # :138
     end
     density = DeviceDensity(ctx)
     ℓπ_grad(θ) = logdensity_grad(ctx, θ)
@@ -615,7 +646,7 @@ end
 # independent chains on the GPUs prepared by init_gpus and returns a Vector of chains / lps (chain order)
 function subspace_inference(model, cost, data, opt; σ_z = 1.0, σ_m = 1.0, σ_p = 1.0, itr = 1000, T = 25, c = 1, M = 20,
                             print_freq = 1, alg = :rwmh, backend = :forwarddiff, method = :subspace, device = 0,
-                            device_training = false, ngpu = 1, nchains = ngpu)
+                            device_training = false, ngpu = 1, nchains = ngpu, device_loop = false)
     method == :subspace || throw("Error: No method found")
     ngpu > 1 && return subspace_inference_multi(model, cost, data, opt; ngpu = ngpu, nchains = nchains, σ_z = σ_z, σ_m = σ_m,
                                                 σ_p = σ_p, itr = itr, T = T, c = c, M = M, print_freq = print_freq, alg = alg,
@@ -624,7 +655,7 @@ function subspace_inference(model, cost, data, opt; σ_z = 1.0, σ_m = 1.0, σ_p
     W_swa, _ = subspace_construction(model, cost, data, opt; T = T, c = c, M = M, print_freq = print_freq, ctx = ctx,
                                      keep_on_device = true, device_training = device_training)
     chn, lp = sub_inference(model, data, nothing, nothing; σ_z = σ_z, σ_m = σ_m, σ_p = σ_p, itr = itr, M = M,
-                            alg = alg, backend = backend, ctx = ctx)   # W_swa / P taken in place on the device
+                            alg = alg, backend = backend, ctx = ctx, device_loop = device_loop)   # W_swa / P taken in place on the device
     return chn, lp, W_swa
 end
 

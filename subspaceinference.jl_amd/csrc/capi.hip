@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "capi_common.h"
@@ -111,8 +112,76 @@ void construct_install(Ctx* c, int64_t N, int32_t M, double* w_swa, double* P) {
   c->c_finished = true;
 }
 
-// The reverse sweep of a Dense chain, shared by si_logdensity_grad and the training step (capi_train.hip).
-// Measured and not kept (round 3, tools/bwd_side_ab.py): the weight-gradient GEMM of a layer on a side stream beside the
+// ---- Dense chains: the forward pass, the reverse sweep and value + gradient, each written once for every entry point ------------
+// flops / bytes of one Dense launch over n chain slots in element type T; head: the narrow last layer computed in this layer's
+// epilogue (the layer then writes `slots` fp64 partial products per output instead of its activation, unless it is kept as well)
+struct DenseCost {
+  double flops, bytes;
+};
+template <typename T>
+static DenseCost dense_cost(const si_layer& ly, const si_layer* head, int slots, bool kept, int64_t B, int n) {
+  const double es = (double)sizeof(T), w = (double)ly.in * ly.out, dB = (double)B, dn = (double)n;
+  if (!head) return {2.0 * w * dB * dn, (w + ly.out + (double)(ly.in + ly.out) * dB) * es * dn};
+  const double wh = (double)head->in * head->out;
+  return {2.0 * (w + wh) * dB * dn, kept ? (w + ly.out + (double)(ly.in + ly.out) * dB) * es * dn
+                                         : ((w + ly.out + (double)ly.in * dB + wh) * es + (double)slots * head->out * dB * 8.0) * dn};
+}
+
+template <typename T>
+const T* dense_forward(Ctx* ctx, hipStream_t st, const DenseForward<T>& a) {
+  constexpr bool f64 = std::is_same<T, double>::value;
+  const size_t nl = a.nl, nplain = a.fuse_tail ? nl - 2 : nl;
+  const int64_t B = a.B;
+  ChainBatch cb = a.cb;
+  cb.hin = 0;
+  const T* h = a.X;
+  for (size_t l = 0; l < nplain; ++l) {
+    const si_layer& ly = a.layers[l];
+    T* o = a.kept ? a.kept[l].get() : a.pingpong[l & 1];
+    const DenseCost c = dense_cost<T>(ly, nullptr, 0, false, B, cb.n);
+    {
+      ProfScope ps(ctx, SI_K_DENSE, c.flops, a.traffic ? c.bytes : 0.0);
+      ProfScope pm((int)l == a.main_layer ? ctx : nullptr, SI_K_DENSE_MAIN, c.flops, c.bytes);
+      if constexpr (f64)
+        launch_dense_f64(st, a.w + ly.w_off, a.w + ly.b_off, h, o, ly.out, ly.in, B, ly.act, cb);
+      else
+        launch_dense_f32(st, a.w + ly.w_off, a.w + ly.b_off, h, o, ly.out, ly.in, B, ly.act, cb);
+    }
+    h = o;
+    cb.hin = cb.hout;
+  }
+  const si_layer& ll = a.layers[nl - 1];
+  const int64_t di = (int64_t)ll.out * B;
+  const double d = (double)di, dn = (double)cb.n;
+  Ctx* sse_prof = a.traffic ? ctx : nullptr;
+  if (a.fuse_tail) {
+    const si_layer& ly = a.layers[nl - 2];
+    const DenseCost c = dense_cost<T>(ly, &ll, a.slots, a.kept != nullptr, B, cb.n);
+    {
+      ProfScope ps(ctx, SI_K_DENSE, c.flops, a.traffic ? c.bytes : 0.0);
+      ProfScope pm(((int)nl - 2 == a.main_layer || (int)nl - 1 == a.main_layer) ? ctx : nullptr, SI_K_DENSE_MAIN, c.flops, c.bytes);
+      T* keep = a.kept ? a.kept[nl - 2].get() : nullptr;
+      if constexpr (f64)
+        launch_dense_f64_fused(st, a.w + ly.w_off, a.w + ly.b_off, h, ly.out, ly.in, B, ly.act, a.w + ll.w_off, ll.out, a.part, cb, keep);
+      else
+        launch_dense_f32_fused(st, a.w + ly.w_off, a.w + ly.b_off, h, ly.out, ly.in, B, ly.act, a.w + ll.w_off, ll.out, a.part, cb, keep);
+    }
+    ProfScope ps(sse_prof, SI_K_SSE, (3.0 + a.slots) * d * dn, (16.0 + 8.0 * a.slots) * d * dn);
+    launch_tail_sse(st, a.part, a.slots, ll.out, B, a.w64 + ll.b_off, ll.act, a.Y, a.yhat, a.ssepart, a.sse_blocks, cb);
+    if (!a.defer_sse_final) launch_sse_final(st, a.ssepart, a.sse_blocks, a.sse, cb.n);
+  } else {
+    ProfScope ps(sse_prof, SI_K_SSE, 3.0 * d * dn, (8.0 + (double)sizeof(T)) * d * dn);
+    if constexpr (f64)
+      launch_sse(st, h, a.Y, di, a.ssepart, a.sse_blocks, a.sse, cb.n, cb.hout, !a.defer_sse_final);
+    else
+      launch_sse_f32(st, h, a.Y, di, a.ssepart, a.sse_blocks, a.sse, cb.n, cb.hout, a.yhat, a.yhat ? di : 0, !a.defer_sse_final);
+  }
+  return h;
+}
+template const double* dense_forward<double>(Ctx*, hipStream_t, const DenseForward<double>&);
+template const float* dense_forward<float>(Ctx*, hipStream_t, const DenseForward<float>&);
+
+// The reverse sweep.  Measured and not kept (round 3, tools/bwd_side_ab.py): the weight-gradient GEMM of a layer on a side stream beside the
 // data-gradient GEMM of the critical path (nothing in the sweep reads dW; the split-K dW launch fills 480 of 512 slots)
 // -- 3 % SLOWER at cfg2 (10.2-10.9 -> 10.5-11.1 ms per value + gradient): two GEMMs sharing the CUs lose more in the
 // caches than the idle slots and the fill / drain phases return.
@@ -143,6 +212,22 @@ int32_t dense_reverse_sweep(Ctx* ctx, hipStream_t st, const DenseSweep& s) {
     }
   }
   return SI_OK;
+}
+
+int32_t dense_value_and_grad_f64(Ctx* ctx, hipStream_t st, const DenseValueGrad& s) {
+  const DenseSweep& sw = s.sw;
+  const size_t nl = sw.nl;
+  // a narrow head is fed from the epilogue of the layer in front of it, which stores its own output as well; the head's
+  // outputs land in hs[nl - 1] either way
+  const DenseForward<double> fw{sw.layers, nl, sw.fuse_tail, sw.w, sw.w, sw.X, s.Y, sw.B, sw.hs, {nullptr, nullptr}, ChainBatch(), s.slots,
+                                s.part, sw.hs[nl - 1], s.ssepart, s.sse_blocks, s.sse, false, -1, s.traffic};
+  dense_forward(ctx, st, fw);
+  double bflops = 0.0;
+  for (size_t l = 0; l < nl; ++l) bflops += 4.0 * (double)sw.layers[l].in * sw.layers[l].out * (double)sw.B;
+  ProfScope ps(ctx, SI_K_BACKWARD, bflops, 0.0);
+  SI_HIP(ctx, hipMemsetAsync(sw.gw, 0, (size_t)pad_ld(s.N) * sizeof(double), st));
+  launch_delta_out(st, s.Y, sw.hs[nl - 1], (int64_t)sw.layers[nl - 1].out * sw.B, s.scale, sw.layers[nl - 1].act, sw.delta[0]);
+  return dense_reverse_sweep(ctx, st, sw);
 }
 
 }  // namespace si
@@ -188,9 +273,6 @@ int32_t si_create(si_ctx** out, int32_t device_id) {
     delete c;
     return fail(nullptr, SI_ERR_NODEVICE, m);
   }
-#ifdef SI_DEV_KNOBS
-  if (const char* e = getenv("SI_OVERLAP_HALVES")) c->overlap_halves = e[0] == '1';
-#endif
   *out = c;
   return SI_OK;
 }

@@ -1,6 +1,8 @@
 // C ABI, inference side: si_infer_setup*, the density (si_logdensity, si_forward, si_predict) and its gradient
 // (si_logdensity_grad) -- reference src/space_inference.jl:88-95,107 and src/libs.jl:55-57,75-77.  Host-side orchestration only:
-// every arithmetic step runs in the kernels of kernels_*.hip.  No CPU fallback anywhere in this file.
+// every arithmetic step runs in the kernels of kernels_*.hip.  No CPU fallback anywhere in this file.  The per-layer passes over a
+// chain are shared with the training step: dense_forward / dense_value_and_grad_f64 (capi.hip), dense_value_and_grad_f32
+// (capi_train.hip), net_forward / net_value_and_grad (capi_net.hip).
 #include "capi_common.h"
 #include "chain_spec_rtc.h"
 
@@ -275,66 +277,6 @@ int32_t ensure_chains(si_ctx* ctx, int32_t C) {
   return SI_OK;
 }
 
-// compute_dtype = SI_F32: the Dense chain of eval_density on the fp32 matrix instruction (kernels_gemm_f32.hip).  K4 has
-// left W_swa + P z in d_w (fp64) AND rounded once in d_w32; X32 / activations are fp32; the narrow head's partial sums, the
-// last bias + activation (tail_sse_kernel, unchanged) and the sum of squared errors are fp64.  Replaces the same reference
-// lines as the fp64 path, src/space_inference.jl:92-94, with the precision option of SURVEY section 0 Q6.
-static int32_t eval_density_f32(si_ctx* ctx, int c0, int nc, const double** yhat_out) {
-  const int64_t N = ctx->iN, B = ctx->B, ldw = pad_ld(N);
-  const double dn = (double)nc;
-  ChainBatch cb;
-  cb.n = nc;
-  cb.w = ldw;
-  cb.hin = 0;  // X is shared by all chains
-  cb.hout = ctx->act_elems;
-  cb.part = (int64_t)ctx->fuse_slots32 * ctx->out_dim * B;
-  const float* h = ctx->d_X32;
-  const float* w = ctx->d_w32;
-  const size_t nl = ctx->layers.size();
-  const size_t nstored = ctx->fuse_tail ? nl - 2 : nl;
-  for (size_t l = 0; l < nstored; ++l) {
-    const si_layer& ly = ctx->layers[l];
-    float* o = ctx->d_act32[l & 1];
-    const double fl = 2.0 * (double)ly.in * (double)ly.out * (double)B * dn;
-    const double by = ((double)ly.in * ly.out + ly.out + (double)(ly.in + ly.out) * (double)B) * 4.0 * dn;
-    {
-      ProfScope ps(ctx, SI_K_DENSE, fl, by);
-      ProfScope pm((int)l == ctx->main_layer ? ctx : nullptr, SI_K_DENSE_MAIN, fl, by);
-      launch_dense_f32(ctx->stream, w + ly.w_off, w + ly.b_off, h, o, ly.out, ly.in, B, ly.act, cb);
-    }
-    h = o;
-    cb.hin = ctx->act_elems;
-  }
-  const int64_t d = (int64_t)ctx->out_dim * B;
-  if (ctx->fuse_tail) {
-    const si_layer& ly = ctx->layers[nl - 2];
-    const si_layer& ll = ctx->layers[nl - 1];
-    const double fl = (2.0 * (double)ly.in * (double)ly.out * (double)B + 2.0 * (double)ll.in * (double)ll.out * (double)B) * dn;
-    const double by = (((double)ly.in * ly.out + ly.out + (double)ly.in * (double)B + (double)ll.in * ll.out) * 4.0 +
-                       (double)ctx->fuse_slots32 * ll.out * (double)B * 8.0) * dn;
-    {
-      ProfScope ps(ctx, SI_K_DENSE, fl, by);
-      ProfScope pm(((int)nl - 2 == ctx->main_layer || (int)nl - 1 == ctx->main_layer) ? ctx : nullptr, SI_K_DENSE_MAIN, fl, by);
-      launch_dense_f32_fused(ctx->stream, w + ly.w_off, w + ly.b_off, h, ly.out, ly.in, B, ly.act, w + ll.w_off, ll.out,
-                             ctx->d_part, cb);
-    }
-    {
-      ProfScope ps(ctx, SI_K_SSE, (3.0 + ctx->fuse_slots32) * (double)d * dn, (16.0 + 8.0 * ctx->fuse_slots32) * (double)d * dn);
-      // the head's bias is added in fp64 from the fp64 weight vector (same number the fp32 copy was rounded from)
-      launch_tail_sse(ctx->stream, ctx->d_part, ctx->fuse_slots32, ll.out, B, ctx->d_w + ll.b_off, ll.act, ctx->d_Y,
-                      yhat_out ? ctx->d_yhat : nullptr, ctx->d_ssepart, ctx->sse_blocks, cb);
-      if (!ctx->defer_sse_final) launch_sse_final(ctx->stream, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse + c0, nc);
-    }
-  } else {
-    ProfScope ps(ctx, SI_K_SSE, 3.0 * (double)d * dn, 12.0 * (double)d * dn);
-    launch_sse_f32(ctx->stream, h, ctx->d_Y, d, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse + c0, nc, ctx->act_elems,
-                   yhat_out ? ctx->d_yhat : nullptr, d, !ctx->defer_sse_final);
-  }
-  SI_HIP(ctx, hipGetLastError());
-  if (yhat_out) *yhat_out = ctx->d_yhat;   // slot j at + j * out_dim*B
-  return SI_OK;
-}
-
 // density evaluations for chain slots [c0, c0 + nc), nc <= fw_slots, in ONE pass of launches:
 // d_zprop[:, c] -> d_sse[c]; optionally leaves the model outputs at *yhat_out (slot j at + j * out_dim*B after the fused
 // tail, at + j * act_elems otherwise)
@@ -351,9 +293,9 @@ int32_t eval_density(si_ctx* ctx, int c0, int nc, const double** yhat_out) {
   if (ctx->sigma_p > 0.0)  // ||new_W||^2 per chain for the optional prior term (same fixed-order reduction as the SSE)
     launch_sse(ctx->stream, ctx->d_w, nullptr, N, ctx->d_wsqpart, ctx->wsq_blocks, ctx->d_wsq + c0, nc, ldw);
   if (ctx->plan.has_conv && ctx->f32) {
-    // compute_dtype = SI_F32 on a Conv chain: the same pass on fp32 operands (net_forward_f32); the squared errors in fp64
+    // compute_dtype = SI_F32 on a Conv chain: the same pass on fp32 operands; the squared errors in fp64
     float* last32 = nullptr;
-    const int32_t rc = net_forward_f32(ctx, ctx->plan, ctx->d_w32, ctx->d_X32, B, ctx->d_act32, ctx->d_wpack32, &last32);
+    const int32_t rc = net_forward<float>(ctx, ctx->plan, ctx->d_w32, ctx->d_X32, B, ctx->d_act32, ctx->d_wpack32, /*pingpong=*/true, &last32);
     if (rc != SI_OK) return rc;
     const int64_t d = (int64_t)ctx->out_dim * B;
     {
@@ -368,8 +310,8 @@ int32_t eval_density(si_ctx* ctx, int c0, int nc, const double** yhat_out) {
   if (ctx->plan.has_conv) {
     // generic path (capi_net.hip): Conv / MaxPool / flatten / Dense layers one after the other, ping-pong activations
     double* last = nullptr;
-    const int32_t rc = net_forward(ctx, ctx->plan, ctx->d_w, ctx->plan.input_spatial ? ctx->d_Xc : ctx->d_X, B, ctx->d_act,
-                                   ctx->d_wpack, /*pingpong=*/true, &last);
+    const int32_t rc = net_forward<double>(ctx, ctx->plan, ctx->d_w, ctx->plan.input_spatial ? ctx->d_Xc : ctx->d_X, B, ctx->d_act,
+                                           ctx->d_wpack, /*pingpong=*/true, &last);
     if (rc != SI_OK) return rc;
     const int64_t d = (int64_t)ctx->out_dim * B;
     {
@@ -380,61 +322,7 @@ int32_t eval_density(si_ctx* ctx, int c0, int nc, const double** yhat_out) {
     if (yhat_out) *yhat_out = last;
     return SI_OK;
   }
-#ifdef SI_DEV_KNOBS   // development build only: measured 1 % slower, not shipped
-  const size_t nl_all = ctx->layers.size();
-  if (ctx->overlap_halves && nc == 1 && ctx->fuse_tail && !yhat_out && B >= 4096) {
-    // EXPERIMENT: the batch in two halves on two streams -- layer 1 of half B runs beside layer 2 of
-    // half A, so the output-store drain of one overlaps the MFMAs of the other inside ONE chain.  The halves meet on whole
-    // 128-column tiles, so every tile is computed exactly as in the single launch; the head partials of both halves land
-    // in one buffer with the full-B pitch and ONE tail_sse launch sums them in the usual fixed order: lp is bit-identical.
-    // (each under its own null check: si_reconstruct / the streamed output map create stream2 by themselves -- ADVICE r2)
-    if (!ctx->stream2) SI_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-    if (!ctx->ev_fork) SI_HIP(ctx, ctx->ev_fork.try_create());
-    if (!ctx->ev_join) SI_HIP(ctx, ctx->ev_join.try_create());
-    const int64_t b1 = ((B / 2 + 127) / 128) * 128;
-    SI_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-    SI_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-    auto run_half = [&](hipStream_t st, int64_t b0, int64_t bh, bool prof) {
-      const double* h = ctx->d_X + (size_t)ctx->in_dim * b0;
-      const size_t nst = nl_all - 2;
-      for (size_t l = 0; l < nst; ++l) {
-        const si_layer& ly = ctx->layers[l];
-        double* o = ctx->d_act[l & 1] + (size_t)ly.out * b0;
-        ProfScope ps(prof ? ctx : nullptr, SI_K_DENSE, 2.0 * (double)ly.in * ly.out * (double)bh, 0.0);
-        launch_dense_f64(st, ctx->d_w + ly.w_off, ctx->d_w + ly.b_off, h, o, ly.out, ly.in, bh, ly.act);
-        h = o;
-      }
-      const si_layer& ly = ctx->layers[nl_all - 2];
-      const si_layer& ll = ctx->layers[nl_all - 1];
-      ChainBatch hb;
-      hb.part_ld = B;
-      const double fl = (2.0 * (double)ly.in * ly.out + 2.0 * (double)ll.in * ll.out) * (double)bh;
-      ProfScope ps(prof ? ctx : nullptr, SI_K_DENSE, fl, 0.0);
-      ProfScope pm(prof ? ctx : nullptr, SI_K_DENSE_MAIN, fl, 0.0);
-      launch_dense_f64_fused(st, ctx->d_w + ly.w_off, ctx->d_w + ly.b_off, h, ly.out, ly.in, bh, ly.act, ctx->d_w + ll.w_off, ll.out,
-                             ctx->d_part + b0, hb);
-    };
-    run_half(ctx->stream2, b1, B - b1, false);
-    run_half(ctx->stream, 0, b1, true);
-    SI_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-    SI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-    const si_layer& ll = ctx->layers[nl_all - 1];
-    const int64_t d = (int64_t)ctx->out_dim * B;
-    ChainBatch cb1;
-    cb1.part = (int64_t)ctx->fuse_slots * ctx->out_dim * B;
-    cb1.w = ldw;
-    {
-      ProfScope ps(ctx, SI_K_SSE, (3.0 + ctx->fuse_slots) * (double)d, (16.0 + 8.0 * ctx->fuse_slots) * (double)d);
-      launch_tail_sse(ctx->stream, ctx->d_part, ctx->fuse_slots, ll.out, B, ctx->d_w + ll.b_off, ll.act, ctx->d_Y, nullptr,
-                      ctx->d_ssepart, ctx->sse_blocks, cb1);
-      if (!ctx->defer_sse_final) launch_sse_final(ctx->stream, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse + c0, 1);
-    }
-    SI_HIP(ctx, hipGetLastError());
-    return SI_OK;
-  }
-#endif  // SI_DEV_KNOBS
-  if (ctx->f32) return eval_density_f32(ctx, c0, nc, yhat_out);
-  if (ctx->fused_ok && ctx->chain_mode != 0 && !yhat_out) {
+  if (ctx->fused_ok && ctx->chain_mode != 0 && !yhat_out) {   // (never with compute_dtype = SI_F32: fused_chain_class)
     // narrow chain: every layer of all nc chains in ONE launch, activations in LDS; the model outputs go through the plain
     // SSE kernels (one squared error per thread: the same partial sums as tail_sse_kernel's)
     ChainFusedPlan fp;
@@ -482,54 +370,32 @@ int32_t eval_density(si_ctx* ctx, int c0, int nc, const double** yhat_out) {
       return SI_OK;
     }
   }
+  // the per-layer launches (dense_forward), nc chain slots per launch, outputs ping-pong.  compute_dtype = SI_F32 runs them on the
+  // fp32 matrix instruction (kernels_gemm_f32.hip): K4 has left W_swa + P z in d_w (fp64) AND rounded once in d_w32; X32 /
+  // activations are fp32; the narrow head's partial sums, the last bias + activation (tail_sse_kernel) and the sum of squared
+  // errors are fp64 -- the precision option of SURVEY section 0 Q6 on the same reference lines, src/space_inference.jl:92-94
+  const int slots = ctx->f32 ? ctx->fuse_slots32 : ctx->fuse_slots;
   ChainBatch cb;
   cb.n = nc;
   cb.w = ldw;
-  cb.hin = 0;  // X is shared by all chains
   cb.hout = ctx->act_elems;
-  cb.part = (int64_t)ctx->fuse_slots * ctx->out_dim * B;
-  const double* h = ctx->d_X;
-  const size_t nl = ctx->layers.size();
-  const size_t nstored = ctx->fuse_tail ? nl - 2 : nl;
-  for (size_t l = 0; l < nstored; ++l) {
-    const si_layer& ly = ctx->layers[l];
-    double* o = ctx->d_act[l & 1];
-    const double fl = 2.0 * (double)ly.in * (double)ly.out * (double)B * dn;
-    const double by = ((double)ly.in * ly.out + ly.out + (double)(ly.in + ly.out) * (double)B) * 8.0 * dn;
-    {
-      ProfScope ps(ctx, SI_K_DENSE, fl, by);
-      ProfScope pm((int)l == ctx->main_layer ? ctx : nullptr, SI_K_DENSE_MAIN, fl, by);
-      launch_dense_f64(ctx->stream, ctx->d_w + ly.w_off, ctx->d_w + ly.b_off, h, o, ly.out, ly.in, B, ly.act, cb);
-    }
-    h = o;
-    cb.hin = ctx->act_elems;
-  }
-  const int64_t d = (int64_t)ctx->out_dim * B;
-  if (ctx->fuse_tail) {
-    const si_layer& ly = ctx->layers[nl - 2];
-    const si_layer& ll = ctx->layers[nl - 1];
-    const double fl = (2.0 * (double)ly.in * (double)ly.out * (double)B + 2.0 * (double)ll.in * (double)ll.out * (double)B) * dn;
-    const double by = (((double)ly.in * ly.out + ly.out + (double)ly.in * (double)B + (double)ll.in * ll.out) * 8.0 +
-                       (double)ctx->fuse_slots * ll.out * (double)B * 8.0) * dn;
-    {
-      ProfScope ps(ctx, SI_K_DENSE, fl, by);
-      ProfScope pm(((int)nl - 2 == ctx->main_layer || (int)nl - 1 == ctx->main_layer) ? ctx : nullptr, SI_K_DENSE_MAIN, fl, by);
-      launch_dense_f64_fused(ctx->stream, ctx->d_w + ly.w_off, ctx->d_w + ly.b_off, h, ly.out, ly.in, B, ly.act,
-                             ctx->d_w + ll.w_off, ll.out, ctx->d_part, cb);
-    }
-    {
-      ProfScope ps(ctx, SI_K_SSE, (3.0 + ctx->fuse_slots) * (double)d * dn, (16.0 + 8.0 * ctx->fuse_slots) * (double)d * dn);
-      launch_tail_sse(ctx->stream, ctx->d_part, ctx->fuse_slots, ll.out, B, ctx->d_w + ll.b_off, ll.act, ctx->d_Y,
-                      yhat_out ? ctx->d_yhat : nullptr, ctx->d_ssepart, ctx->sse_blocks, cb);
-      if (!ctx->defer_sse_final) launch_sse_final(ctx->stream, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse + c0, nc);
-    }
-    h = ctx->d_yhat;
+  cb.part = (int64_t)slots * ctx->out_dim * B;
+  const double* yh = ctx->d_yhat;
+  double* yhat = yhat_out ? ctx->d_yhat.get() : nullptr;
+  if (ctx->f32) {
+    const DenseForward<float> fw{ctx->layers.data(), ctx->layers.size(), ctx->fuse_tail, ctx->d_w32, ctx->d_w, ctx->d_X32, ctx->d_Y, B, nullptr,
+                                 {ctx->d_act32[0], ctx->d_act32[1]}, cb, slots, ctx->d_part, yhat, ctx->d_ssepart, ctx->sse_blocks,
+                                 ctx->d_sse + c0, ctx->defer_sse_final, ctx->main_layer, true};
+    dense_forward(ctx, ctx->stream, fw);
   } else {
-    ProfScope ps(ctx, SI_K_SSE, 3.0 * (double)d * dn, 16.0 * (double)d * dn);
-    launch_sse(ctx->stream, h, ctx->d_Y, d, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse + c0, nc, ctx->act_elems, !ctx->defer_sse_final);
+    const DenseForward<double> fw{ctx->layers.data(), ctx->layers.size(), ctx->fuse_tail, ctx->d_w, ctx->d_w, ctx->d_X, ctx->d_Y, B, nullptr,
+                                  {ctx->d_act[0], ctx->d_act[1]}, cb, slots, ctx->d_part, yhat, ctx->d_ssepart, ctx->sse_blocks,
+                                  ctx->d_sse + c0, ctx->defer_sse_final, ctx->main_layer, true};
+    const double* h = dense_forward(ctx, ctx->stream, fw);
+    if (!ctx->fuse_tail) yh = h;   // without the fused tail the outputs stay in the last activation buffer
   }
   SI_HIP(ctx, hipGetLastError());
-  if (yhat_out) *yhat_out = h;
+  if (yhat_out) *yhat_out = yh;
   return SI_OK;
 }
 
@@ -668,110 +534,38 @@ int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_out, doub
   }
   const bool prior = ctx->sigma_p > 0.0;
   if (prior) launch_sse(ctx->stream, ctx->d_w, nullptr, N, ctx->d_wsqpart, ctx->wsq_blocks, ctx->d_wsq, 1, pad_ld(N));
+  // every route leaves d (-SSE / (2 sigma^2)) / dw in d_gw and the SSE in d_sse: Delta_L = d lp / d yhat = (y - yhat) / sigma^2
   if (ctx->f32) {
     // compute_dtype = SI_F32: value and gradient on the fp32 density's own arithmetic (fp32 operands and activations, fp64 head
     // partials / SSE / batch sums; W_swa + P z rounded once), the pull-back P' g and the optional prior term in fp64
-    const int64_t d = (int64_t)ctx->out_dim * B;
     DenseSweepF32 sw{ctx->layers.data(), nl, ctx->fuse_tail, ctx->d_w32, ctx->d_w, ctx->d_X32, ctx->d_Y, &ctx->g_ws32, ctx->d_part,
-                     ctx->d_ssepart, ctx->d_sse, ctx->sse_blocks, B, N, 1.0 / s2};   // d lp / d yhat = (y - yhat) / sigma^2
+                     ctx->d_ssepart, ctx->d_sse, ctx->sse_blocks, B, N, 1.0 / s2};
     if ((rc = dense_value_and_grad_f32(ctx, ctx->stream, sw)) != SI_OK) return rc;
     launch_widen_f32_to_f64(ctx->stream, ctx->g_ws32.gw32, N, ctx->d_gw, ctx->num_cu);
-    if (prior) launch_prior_grad(ctx->stream, ctx->d_gw, ctx->d_w, N, 1.0 / (ctx->sigma_p * ctx->sigma_p), ctx->num_cu);
-    launch_ptg(ctx->stream, ctx->i_P, ctx->ldP, N, M, ctx->d_gw, ctx->d_ptgpart, ctx->d_gz);
-    SI_HIP(ctx, hipGetLastError());
-    double sse = 0.0, wsq = 0.0;
-    SI_HIP(ctx, hipMemcpyAsync(&sse, ctx->d_sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SI_HIP(ctx, hipMemcpyAsync(grad_out, ctx->d_gz, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (prior) SI_HIP(ctx, hipMemcpyAsync(&wsq, ctx->d_wsq, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *lp_out = mvnormal_c0((double)d, ctx->sigma_m) - (sse / s2) / 2.0;
-    if (prior) *lp_out += prior_c0(ctx) - (wsq / (ctx->sigma_p * ctx->sigma_p)) / 2.0;
-    return SI_OK;
-  }
-  if (ctx->plan.has_conv) {
-    // generic path: forward with every output kept, d lp / d yhat = (y - yhat) / sigma^2, reverse sweep, P' g_w
+  } else if (ctx->plan.has_conv) {
     const NetPlan& p = ctx->plan;
-    const double* xin = p.input_spatial ? ctx->d_Xc : ctx->d_X;
-    if ((rc = net_forward(ctx, p, ctx->d_w, xin, B, ctx->d_hs.data(), ctx->d_wpack, false, nullptr, ctx->d_pidx.data())) != SI_OK) return rc;
-    const int64_t d = (int64_t)ctx->out_dim * B;
-    const double* yhat = ctx->d_hs[nl - 1];
-    launch_sse(ctx->stream, yhat, ctx->d_Y, d, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse);
-    {
-      double bflops = 0.0;
-      for (const auto& q : p.L)
-        bflops += q.kind == SI_LAYER_DENSE ? 4.0 * (double)q.in_feat * q.out_feat * (double)B
-                  : q.kind == SI_LAYER_CONV ? 4.0 * (double)q.KW * q.KH * q.C * q.Co * (double)q.Wo * q.Ho * (double)B : 0.0;
-      ProfScope ps(ctx, SI_K_BACKWARD, bflops, 0.0);
-      SI_HIP(ctx, hipMemsetAsync(ctx->d_gw, 0, (size_t)pad_ld(N) * sizeof(double), ctx->stream));
-      launch_delta_out(ctx->stream, ctx->d_Y, yhat, d, 1.0 / s2, SI_ACT_IDENTITY, ctx->d_delta[0]);
-      if ((rc = net_backward(ctx, p, ctx->d_w, xin, B, ctx->d_hs.data(), ctx->d_delta[0], ctx->d_delta[1], ctx->d_gw,
-                             ctx->g_scratch)) != SI_OK)
-        return rc;
-      if (prior) launch_prior_grad(ctx->stream, ctx->d_gw, ctx->d_w, N, 1.0 / (ctx->sigma_p * ctx->sigma_p), ctx->num_cu);
-      launch_ptg(ctx->stream, ctx->i_P, ctx->ldP, N, M, ctx->d_gw, ctx->d_ptgpart, ctx->d_gz);
-    }
-    SI_HIP(ctx, hipGetLastError());
-    double sse = 0.0;
-    SI_HIP(ctx, hipMemcpyAsync(&sse, ctx->d_sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SI_HIP(ctx, hipMemcpyAsync(grad_out, ctx->d_gz, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    double wsq = 0.0;
-    if (prior) SI_HIP(ctx, hipMemcpyAsync(&wsq, ctx->d_wsq, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *lp_out = mvnormal_c0((double)d, ctx->sigma_m) - (sse / s2) / 2.0;
-    if (prior) *lp_out += prior_c0(ctx) - (wsq / (ctx->sigma_p * ctx->sigma_p)) / 2.0;
-    return SI_OK;
-  }
-  // forward with every layer's output kept for the reverse sweep.  With a narrow head (fuse_tail) the layer in front
-  // of it stores its output AND feeds the head from its epilogue, so the head costs no pass over that activation.
-  const double* h = ctx->d_X;
-  const size_t nplain = ctx->fuse_tail ? nl - 2 : nl;
-  for (size_t l = 0; l < nplain; ++l) {
-    const si_layer& ly = ctx->layers[l];
-    ProfScope ps(ctx, SI_K_DENSE, 2.0 * (double)ly.in * ly.out * (double)B,
-                 ((double)ly.in * ly.out + ly.out + (double)(ly.in + ly.out) * (double)B) * 8.0);
-    launch_dense_f64(ctx->stream, ctx->d_w + ly.w_off, ctx->d_w + ly.b_off, h, ctx->d_hs[l], ly.out, ly.in, B, ly.act);
-    h = ctx->d_hs[l];
-  }
-  const int64_t d = (int64_t)ctx->out_dim * B;
-  if (ctx->fuse_tail) {
-    const si_layer& ly = ctx->layers[nl - 2];
-    const si_layer& ll = ctx->layers[nl - 1];
-    {
-      ProfScope ps(ctx, SI_K_DENSE, 2.0 * ((double)ly.in * ly.out + (double)ll.in * ll.out) * (double)B,
-                   ((double)ly.in * ly.out + ly.out + (double)(ly.in + ly.out) * (double)B) * 8.0);
-      launch_dense_f64_fused(ctx->stream, ctx->d_w + ly.w_off, ctx->d_w + ly.b_off, h, ly.out, ly.in, B, ly.act,
-                             ctx->d_w + ll.w_off, ll.out, ctx->d_part, ChainBatch(), ctx->d_hs[nl - 2]);
-    }
-    ProfScope ps(ctx, SI_K_SSE, (3.0 + ctx->fuse_slots) * (double)d, (16.0 + 8.0 * ctx->fuse_slots) * (double)d);
-    launch_tail_sse(ctx->stream, ctx->d_part, ctx->fuse_slots, ll.out, B, ctx->d_w + ll.b_off, ll.act, ctx->d_Y,
-                    ctx->d_hs[nl - 1], ctx->d_ssepart, ctx->sse_blocks);
-    launch_sse_final(ctx->stream, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse);
-    h = ctx->d_hs[nl - 1];
-  } else {
-    ProfScope ps(ctx, SI_K_SSE, 3.0 * (double)d, 16.0 * (double)d);
-    launch_sse(ctx->stream, h, ctx->d_Y, d, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse);
-  }
-  {
     double bflops = 0.0;
-    for (const auto& ly : ctx->layers) bflops += 4.0 * (double)ly.in * ly.out * (double)B;
-    ProfScope ps(ctx, SI_K_BACKWARD, bflops, 0.0);
-    SI_HIP(ctx, hipMemsetAsync(ctx->d_gw, 0, (size_t)pad_ld(N) * sizeof(double), ctx->stream));
-    // d lp / d yhat = (y - yhat) / sigma^2
-    launch_delta_out(ctx->stream, ctx->d_Y, h, d, 1.0 / s2, ctx->layers[nl - 1].act, ctx->d_delta[0]);
-    DenseSweep sw{ctx->layers.data(), nl, ctx->fuse_tail, ctx->d_w, ctx->d_X, ctx->d_hs.data(), {ctx->d_delta[0], ctx->d_delta[1]},
-                  ctx->d_gw, ctx->d_rspart, ctx->d_bwpart, B};
-    const int32_t rcs = dense_reverse_sweep(ctx, ctx->stream, sw);
-    if (rcs != SI_OK) return rcs;
-    if (prior) launch_prior_grad(ctx->stream, ctx->d_gw, ctx->d_w, N, 1.0 / (ctx->sigma_p * ctx->sigma_p), ctx->num_cu);
-    launch_ptg(ctx->stream, ctx->i_P, ctx->ldP, N, M, ctx->d_gw, ctx->d_ptgpart, ctx->d_gz);
+    for (const auto& q : p.L)
+      bflops += q.kind == SI_LAYER_DENSE ? 4.0 * (double)q.in_feat * q.out_feat * (double)B
+                : q.kind == SI_LAYER_CONV ? 4.0 * (double)q.KW * q.KH * q.C * q.Co * (double)q.Wo * q.Ho * (double)B : 0.0;
+    const NetValueGrad vg{&p, ctx->d_w, p.input_spatial ? ctx->d_Xc : ctx->d_X, ctx->d_Y, B, ctx->d_hs.data(), ctx->d_wpack, ctx->d_ssepart,
+                          ctx->sse_blocks, ctx->d_sse, {ctx->d_delta[0], ctx->d_delta[1]}, ctx->d_gw, &ctx->g_scratch, N, 1.0 / s2, bflops};
+    if ((rc = net_value_and_grad(ctx, vg)) != SI_OK) return rc;
+  } else {
+    const DenseValueGrad vg{{ctx->layers.data(), nl, ctx->fuse_tail, ctx->d_w, ctx->d_X, ctx->d_hs.data(), {ctx->d_delta[0], ctx->d_delta[1]},
+                             ctx->d_gw, ctx->d_rspart, ctx->d_bwpart, B},
+                            ctx->d_Y, ctx->fuse_slots, ctx->d_part, ctx->d_ssepart, ctx->d_sse, ctx->sse_blocks, N, 1.0 / s2, true};
+    if ((rc = dense_value_and_grad_f64(ctx, ctx->stream, vg)) != SI_OK) return rc;
   }
+  if (prior) launch_prior_grad(ctx->stream, ctx->d_gw, ctx->d_w, N, 1.0 / (ctx->sigma_p * ctx->sigma_p), ctx->num_cu);
+  launch_ptg(ctx->stream, ctx->i_P, ctx->ldP, N, M, ctx->d_gw, ctx->d_ptgpart, ctx->d_gz);
   SI_HIP(ctx, hipGetLastError());
-  double sse = 0.0;
+  double sse = 0.0, wsq = 0.0;
   SI_HIP(ctx, hipMemcpyAsync(&sse, ctx->d_sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipMemcpyAsync(grad_out, ctx->d_gz, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  double wsq = 0.0;
   if (prior) SI_HIP(ctx, hipMemcpyAsync(&wsq, ctx->d_wsq, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const int64_t d = (int64_t)ctx->out_dim * B;
   *lp_out = mvnormal_c0((double)d, ctx->sigma_m) - (sse / s2) / 2.0;
   if (prior) *lp_out += prior_c0(ctx) - (wsq / (ctx->sigma_p * ctx->sigma_p)) / 2.0;
   return SI_OK;

@@ -1,9 +1,11 @@
 // Host side of chains that contain Conv / MaxPool / flatten layers: validation of the caller's layer
-// table, the geometry every kernel launch needs, and the generic forward pass / reverse sweep over such a chain.
+// table, the geometry every kernel launch needs, and the generic forward pass (fp64 and fp32) / reverse sweep / value and gradient
+// over such a chain.
 // The reference's `model_re` restructures ANY Flux Chain (src/libs.jl:55-57) and `density` evaluates it on the full data
 // (src/space_inference.jl:94); pure Dense chains keep their tuned path in capi_infer.hip / capi_train.hip (fused narrow tail,
 // chain batching) and only pass through net_plan() for validation.  No arithmetic happens on the host.
 #include <algorithm>
+#include <type_traits>
 
 #include "kernels_gemm.h"
 #include "si_internal.h"
@@ -146,14 +148,20 @@ void net_input(Ctx* c, const NetPlan& p, const double* X, double* Xc, int64_t B)
   launch_whcn_to_cwhn(c->stream, X, Xc, p.in_W, p.in_H, p.in_C, p.in_Cp, B);
 }
 
-int32_t net_forward(Ctx* c, const NetPlan& p, const double* w, const double* xin, int64_t B, const DevBuf<double>* outs, double* wpack,
-                    bool pingpong, double** final_out, const DevBuf<uint8_t>* pidx) {
+// T = float is compute_dtype = SI_F32 on a Conv chain: the same pass on fp32 operands -- the conv kernels compiled for float
+// (kernels_conv.hip -DSI_CONV_F32: v_mfma_f32_16x16x4_f32), the Dense layers behind `flatten` on kernels_gemm_f32.hip; w: the
+// evaluation's weights rounded once from the fp64 sum (K4).  Gradient mode (kept outputs + pidx) exists for double only.
+template <typename T>
+int32_t net_forward(Ctx* c, const NetPlan& p, const T* w, const T* xin, int64_t B, const DevBuf<T>* outs, T* wpack, bool pingpong,
+                    T** final_out, const DevBuf<uint8_t>* pidx) {
+  constexpr bool f64 = std::is_same<T, double>::value;
+  constexpr double es = (double)sizeof(T);
   hipStream_t st = c->stream;
-  const double* h = xin;
+  const T* h = xin;
   size_t executed = 0;
   for (size_t l = 0; l < p.L.size(); ++l) {
     const LayerPlan& q = p.L[l];
-    double* o = pingpong ? outs[executed & 1] : outs[l];
+    T* o = pingpong ? outs[executed & 1] : outs[l];
     ++executed;
     if (final_out) *final_out = o;
     if ((double)std::max(q.in_elems, q.out_elems) * (double)B >= 2147483648.0)
@@ -161,50 +169,54 @@ int32_t net_forward(Ctx* c, const NetPlan& p, const double* w, const double* xin
     switch (q.kind) {
       case SI_LAYER_DENSE: {
         ProfScope ps(c, SI_K_DENSE, 2.0 * (double)q.in_feat * q.out_feat * (double)B,
-                     ((double)q.in_feat * q.out_feat + q.out_feat + (double)(q.in_feat + q.out_feat) * (double)B) * 8.0);
+                     ((double)q.in_feat * q.out_feat + q.out_feat + (double)(q.in_feat + q.out_feat) * (double)B) * es);
         if (dense_narrow_applies(q.out_feat, q.in_feat, B, c->num_cu))
           launch_dense_narrow(st, w + q.w_off, w + q.b_off, h, o, q.out_feat, q.in_feat, B, q.act);
-        else
+        else if constexpr (f64)
           launch_dense_f64(st, w + q.w_off, w + q.b_off, h, o, q.out_feat, q.in_feat, B, q.act);
+        else
+          launch_dense_f32(st, w + q.w_off, w + q.b_off, h, o, q.out_feat, q.in_feat, B, q.act);
         break;
       }
       case SI_LAYER_CONV: {
         const int64_t npos = (int64_t)q.Wo * q.Ho * B;
         {
-          ProfScope ps(c, SI_K_CONV_AUX, 0.0, ((double)q.KW * q.KH * q.C * q.Co + (double)q.Cop * q.Kp) * 8.0);
+          ProfScope ps(c, SI_K_CONV_AUX, 0.0, ((double)q.KW * q.KH * q.C * q.Co + (double)q.Cop * q.Kp) * es);
           launch_conv_pack(st, w + q.w_off, w + q.b_off, wpack + q.wp_off, wpack + q.bp_off, q.KW, q.KH, q.C, q.Co, q.Cp, q.Cop, q.Kp);
         }
-        if (!pingpong && pidx && pidx[l] && net_grad_fused(p, l)) {
-          // gradient mode: conv + pool in one kernel; the pooled output and a byte index are all the reverse sweep needs
-          o = outs[l + 1];
-          if (final_out) *final_out = o;
-          ProfScope ps(c, SI_K_CONV, 2.0 * (double)q.KW * q.KH * q.C * q.Co * (double)npos,
-                       ((double)q.in_elems + (double)p.L[l + 1].out_elems * 1.125) * (double)B * 8.0 + (double)q.Cop * q.Kp * 8.0);
-          launch_conv_forward_pool2_idx(st, wpack + q.wp_off, wpack + q.bp_off, h, o, pidx[l], q.g, q.Cop, q.Kp, npos, q.act);
-          ++l;
-          ++executed;
-          break;
+        if constexpr (f64) {
+          if (!pingpong && pidx && pidx[l] && net_grad_fused(p, l)) {
+            // gradient mode: conv + pool in one kernel; the pooled output and a byte index are all the reverse sweep needs
+            o = outs[l + 1];
+            if (final_out) *final_out = o;
+            ProfScope ps(c, SI_K_CONV, 2.0 * (double)q.KW * q.KH * q.C * q.Co * (double)npos,
+                         ((double)q.in_elems + (double)p.L[l + 1].out_elems * 1.125) * (double)B * 8.0 + (double)q.Cop * q.Kp * 8.0);
+            launch_conv_forward_pool2_idx(st, wpack + q.wp_off, wpack + q.bp_off, h, o, pidx[l], q.g, q.Cop, q.Kp, npos, q.act);
+            ++l;
+            ++executed;
+            break;
+          }
         }
         const bool fuse_pool = pingpong && net_pool_fusable(p, l);
         if (fuse_pool) {   // the pooled tensor is all the next layer reads: skip the MaxPool layer
           ProfScope ps(c, SI_K_CONV, 2.0 * (double)q.KW * q.KH * q.C * q.Co * (double)npos,
-                       ((double)q.in_elems + (double)p.L[l + 1].out_elems) * (double)B * 8.0 + (double)q.Cop * q.Kp * 8.0);
+                       ((double)q.in_elems + (double)p.L[l + 1].out_elems) * (double)B * es + (double)q.Cop * q.Kp * es);
           launch_conv_forward_pool2(st, wpack + q.wp_off, wpack + q.bp_off, h, o, q.g, q.Cop, q.Kp, npos, q.act);
           ++l;
           break;
         }
         ProfScope ps(c, SI_K_CONV, 2.0 * (double)q.KW * q.KH * q.C * q.Co * (double)npos,
-                     ((double)q.in_elems + (double)q.out_elems) * (double)B * 8.0 + (double)q.Cop * q.Kp * 8.0);
+                     ((double)q.in_elems + (double)q.out_elems) * (double)B * es + (double)q.Cop * q.Kp * es);
         launch_conv_forward(st, wpack + q.wp_off, wpack + q.bp_off, h, o, q.g, q.Cop, q.Kp, npos, q.act);
         break;
       }
       case SI_LAYER_MAXPOOL: {
-        ProfScope ps(c, SI_K_CONV_AUX, 0.0, ((double)q.in_elems + (double)q.out_elems) * (double)B * 8.0);
+        ProfScope ps(c, SI_K_CONV_AUX, 0.0, ((double)q.in_elems + (double)q.out_elems) * (double)B * es);
         launch_maxpool(st, h, o, q.Cp, q.Wi, q.Hi, q.Wo, q.Ho, q.KW, q.KH, q.sw, q.sh, B);
         break;
       }
       default: {  // flatten: channel-fastest -> the reference's (W, H, C) feature order
-        ProfScope ps(c, SI_K_CONV_AUX, 0.0, ((double)q.in_elems + (double)q.out_elems) * (double)B * 8.0);
+        ProfScope ps(c, SI_K_CONV_AUX, 0.0, ((double)q.in_elems + (double)q.out_elems) * (double)B * es);
         launch_cwhn_to_whcn(st, h, o, q.Wi, q.Hi, q.C, q.Cp, B);
         break;
       }
@@ -215,67 +227,10 @@ int32_t net_forward(Ctx* c, const NetPlan& p, const double* w, const double* xin
   if (e != hipSuccess) return fail(c, SI_ERR_HIP, std::string("net_forward: ") + hipGetErrorString(e));
   return SI_OK;
 }
-
-// compute_dtype = SI_F32 on a Conv chain: the forward pass of net_forward (ping-pong activations, Conv + 2x2 MaxPool fused where it
-// applies) on fp32 operands -- the conv kernels compiled for float (kernels_conv.hip -DSI_CONV_F32: v_mfma_f32_16x16x4_f32), the
-// Dense layers behind `flatten` on kernels_gemm_f32.hip.  w32: the evaluation's weights rounded once from the fp64 sum (K4).
-int32_t net_forward_f32(Ctx* c, const NetPlan& p, const float* w, const float* xin, int64_t B, const DevBuf<float>* outs, float* wpack,
-                        float** final_out) {
-  hipStream_t st = c->stream;
-  const float* h = xin;
-  size_t executed = 0;
-  for (size_t l = 0; l < p.L.size(); ++l) {
-    const LayerPlan& q = p.L[l];
-    float* o = outs[executed & 1];
-    ++executed;
-    if (final_out) *final_out = o;
-    if ((double)std::max(q.in_elems, q.out_elems) * (double)B >= 2147483648.0)
-      return fail(c, SI_ERR_INVALID, "activation tensors of 2^31 elements or more are not supported by the conv kernels");
-    switch (q.kind) {
-      case SI_LAYER_DENSE: {
-        ProfScope ps(c, SI_K_DENSE, 2.0 * (double)q.in_feat * q.out_feat * (double)B,
-                     ((double)q.in_feat * q.out_feat + q.out_feat + (double)(q.in_feat + q.out_feat) * (double)B) * 4.0);
-        if (dense_narrow_applies(q.out_feat, q.in_feat, B, c->num_cu))
-          launch_dense_narrow(st, w + q.w_off, w + q.b_off, h, o, q.out_feat, q.in_feat, B, q.act);
-        else
-          launch_dense_f32(st, w + q.w_off, w + q.b_off, h, o, q.out_feat, q.in_feat, B, q.act);
-        break;
-      }
-      case SI_LAYER_CONV: {
-        const int64_t npos = (int64_t)q.Wo * q.Ho * B;
-        {
-          ProfScope ps(c, SI_K_CONV_AUX, 0.0, ((double)q.KW * q.KH * q.C * q.Co + (double)q.Cop * q.Kp) * 4.0);
-          launch_conv_pack(st, w + q.w_off, w + q.b_off, wpack + q.wp_off, wpack + q.bp_off, q.KW, q.KH, q.C, q.Co, q.Cp, q.Cop, q.Kp);
-        }
-        if (net_pool_fusable(p, l)) {   // the pooled tensor is all the next layer reads: skip the MaxPool layer
-          ProfScope ps(c, SI_K_CONV, 2.0 * (double)q.KW * q.KH * q.C * q.Co * (double)npos,
-                       ((double)q.in_elems + (double)p.L[l + 1].out_elems) * (double)B * 4.0 + (double)q.Cop * q.Kp * 4.0);
-          launch_conv_forward_pool2(st, wpack + q.wp_off, wpack + q.bp_off, h, o, q.g, q.Cop, q.Kp, npos, q.act);
-          ++l;
-          break;
-        }
-        ProfScope ps(c, SI_K_CONV, 2.0 * (double)q.KW * q.KH * q.C * q.Co * (double)npos,
-                     ((double)q.in_elems + (double)q.out_elems) * (double)B * 4.0 + (double)q.Cop * q.Kp * 4.0);
-        launch_conv_forward(st, wpack + q.wp_off, wpack + q.bp_off, h, o, q.g, q.Cop, q.Kp, npos, q.act);
-        break;
-      }
-      case SI_LAYER_MAXPOOL: {
-        ProfScope ps(c, SI_K_CONV_AUX, 0.0, ((double)q.in_elems + (double)q.out_elems) * (double)B * 4.0);
-        launch_maxpool(st, h, o, q.Cp, q.Wi, q.Hi, q.Wo, q.Ho, q.KW, q.KH, q.sw, q.sh, B);
-        break;
-      }
-      default: {  // flatten: channel-fastest -> the reference's (W, H, C) feature order
-        ProfScope ps(c, SI_K_CONV_AUX, 0.0, ((double)q.in_elems + (double)q.out_elems) * (double)B * 4.0);
-        launch_cwhn_to_whcn(st, h, o, q.Wi, q.Hi, q.C, q.Cp, B);
-        break;
-      }
-    }
-    h = o;
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(c, SI_ERR_HIP, std::string("net_forward_f32: ") + hipGetErrorString(e));
-  return SI_OK;
-}
+template int32_t net_forward<double>(Ctx*, const NetPlan&, const double*, const double*, int64_t, const DevBuf<double>*, double*, bool, double**,
+                                     const DevBuf<uint8_t>*);
+template int32_t net_forward<float>(Ctx*, const NetPlan&, const float*, const float*, int64_t, const DevBuf<float>*, float*, bool, float**,
+                                    const DevBuf<uint8_t>*);
 
 void net_scratch_sizes(const NetPlan& p, int64_t B, int num_cu, size_t* bwpart, size_t* rspart, size_t* wt, size_t* dbtmp) {
   size_t part = 1;
@@ -350,6 +305,20 @@ int32_t net_backward(Ctx* c, const NetPlan& p, const double* w, const double* xi
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(c, SI_ERR_HIP, std::string("net_backward: ") + hipGetErrorString(e));
   return SI_OK;
+}
+
+int32_t net_value_and_grad(Ctx* c, const NetValueGrad& s) {
+  const NetPlan& p = *s.plan;
+  hipStream_t st = c->stream;
+  int32_t rc = net_forward<double>(c, p, s.w, s.xin, s.B, s.hs, s.wpack, false, nullptr, s.scratch->pidx);
+  if (rc != SI_OK) return rc;
+  const int64_t d = (int64_t)p.L.back().out_feat * s.B;
+  const double* yhat = s.hs[p.L.size() - 1];
+  launch_sse(st, yhat, s.Y, d, s.ssepart, s.sse_blocks, s.sse);
+  ProfScope ps(c, SI_K_BACKWARD, s.bwd_flops, 0.0);
+  SI_HIP(c, hipMemsetAsync(s.gw, 0, (size_t)pad_ld(s.N) * sizeof(double), st));
+  launch_delta_out(st, s.Y, yhat, d, s.scale, SI_ACT_IDENTITY, s.delta[0]);
+  return net_backward(c, p, s.w, s.xin, s.B, s.hs, s.delta[0], s.delta[1], s.gw, *s.scratch);
 }
 
 }  // namespace si

@@ -3,7 +3,9 @@
 //     gs = gradient(ps) do training_loss = cost(model, d...) end ;  Flux.update!(opt, ps, gs)
 // for `cost = (m, x, y) -> Flux.Losses.mse(m(x), y)` and opt in {Descent, Momentum, ADAM} (Flux 0.11.2 semantics:
 // Float32 parameters and Float32 optimiser state, Float64 arithmetic because the data are Float64).  The weights never
-// leave the GPU: si_train_push feeds K1 from the device-resident Float32 vector.
+// leave the GPU: si_train_push feeds K1 from the device-resident Float32 vector.  The gradient is one of the value-and-gradient
+// passes shared with si_logdensity_grad: dense_value_and_grad_f64 (capi.hip), dense_value_and_grad_f32 (below), net_value_and_grad
+// (capi_net.hip), each with the mse scale -2 / d.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -87,7 +89,7 @@ void free_train(Ctx* c) {
   c->train = nullptr;
 }
 
-// ---- the fp32 forward + reverse sweep shared by the training step and si_logdensity_grad (compute_dtype = SI_F32) --------------
+// ---- value and gradient in fp32 (dense_forward<float> + the fp32 reverse sweep), shared by the training step and si_logdensity_grad
 bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const si_layer* layers, int L, bool fuse_tail, int64_t N, int32_t in_dim, int32_t out_dim,
                      int64_t Bmax) {
   size_t maxpart32 = 1, maxwt = 1, maxin = (size_t)in_dim, maxw = 1;
@@ -115,29 +117,13 @@ int32_t dense_value_and_grad_f32(Ctx* ctx, hipStream_t st, const DenseSweepF32& 
   const size_t nl = s.nl;
   const int64_t nb = s.B;
   const float* w = s.w32;
-  const float* h = s.X32;
-  const size_t nplain = s.fuse_tail ? nl - 2 : nl;
-  for (size_t l = 0; l < nplain; ++l) {
-    const si_layer& ly = s.layers[l];
-    ProfScope ps(ctx, SI_K_DENSE, 2.0 * (double)ly.in * ly.out * (double)nb, 0.0);
-    launch_dense_f32(st, w + ly.w_off, w + ly.b_off, h, ws.hs32[l], ly.out, ly.in, nb, ly.act);
-    h = ws.hs32[l];
-  }
   const si_layer& ll = s.layers[nl - 1];
   const int64_t d = (int64_t)ll.out * nb;
-  if (s.fuse_tail) {
-    const si_layer& ly = s.layers[nl - 2];
-    const int slots = dense_f32_fused_slots(ly.out, ly.in, ly.w_off % 4 == 0);
-    {
-      ProfScope ps(ctx, SI_K_DENSE, 2.0 * ((double)ly.in * ly.out + (double)ll.in * ll.out) * (double)nb, 0.0);
-      launch_dense_f32_fused(st, w + ly.w_off, w + ly.b_off, h, ly.out, ly.in, nb, ly.act, w + ll.w_off, ll.out, s.part, ChainBatch(),
-                             ws.hs32[nl - 2]);
-    }
-    launch_tail_sse(st, s.part, slots, ll.out, nb, s.w64 + ll.b_off, ll.act, s.Y, ws.yhat64, s.ssepart, s.sse_blocks);
-    launch_sse_final(st, s.ssepart, s.sse_blocks, s.sse);
-  } else {
-    launch_sse_f32(st, h, s.Y, d, s.ssepart, s.sse_blocks, s.sse);
-  }
+  // (a fused head's own output lives in yhat64; its slot count follows the alignment of the fused layer's W in w32)
+  const int slots = s.fuse_tail ? dense_f32_fused_slots(s.layers[nl - 2].out, s.layers[nl - 2].in, s.layers[nl - 2].w_off % 4 == 0) : 0;
+  const DenseForward<float> fw{s.layers, nl, s.fuse_tail, w, s.w64, s.X32, s.Y, nb, ws.hs32.data(), {nullptr, nullptr}, ChainBatch(), slots,
+                               s.part, s.fuse_tail ? ws.yhat64.get() : nullptr, s.ssepart, s.sse_blocks, s.sse, false, -1, false};
+  const float* h = dense_forward(ctx, st, fw);
   double bflops = 0.0;
   for (size_t l = 0; l < nl; ++l) bflops += 4.0 * (double)s.layers[l].in * s.layers[l].out * (double)nb;
   ProfScope ps(ctx, SI_K_BACKWARD, bflops, 0.0);
@@ -376,13 +362,14 @@ static int32_t train_gradient(si_ctx* ctx, const char* who, const int64_t* idx, 
     Yb = t->Yb;
   }
   hipLaunchKernelGGL(widen_kernel, dim3(grid_for(N, ctx->num_cu)), dim3(256), 0, st, t->w32, N, t->w64);
+  const int sse_blocks = sse_num_blocks((int64_t)t->out_dim * nb, ctx->num_cu);
+  const double scale = -2.0 / d_total;   // d mse / d yhat = 2 (yhat - y) / d
   if (t->f32) {
     // ---- the step in the caller's precision: a Float32 model on Float32 data is a Float32 Zygote pass in the reference
     // (src/subspace_construction.jl:39-43).  fp32 operands and activations on v_mfma_f32_32x32x2_f32; fp64 for the head's
     // partial sums, the loss and every sum over the batch (rounded once into the Float32 gradient).
-    const int64_t d = (int64_t)t->out_dim * nb;
-    DenseSweepF32 sw{t->layers.data(), nl, t->fuse_tail, t->w32, t->w64, Xb32, Yb, &t->ws32, t->part, t->ssepart, t->sse,
-                     sse_num_blocks(d, ctx->num_cu), nb, N, -2.0 / d_total};   // d mse / d yhat = 2 (yhat - y) / d
+    DenseSweepF32 sw{t->layers.data(), nl, t->fuse_tail, t->w32, t->w64, Xb32, Yb, &t->ws32, t->part, t->ssepart, t->sse, sse_blocks, nb, N,
+                     scale};
     const int32_t rcs = dense_value_and_grad_f32(ctx, st, sw);
     if (rcs != SI_OK) return rcs;
     // the gradient as the optimiser and the data-parallel all-reduce see it: fp64 words holding the Float32 values
@@ -399,56 +386,16 @@ static int32_t train_gradient(si_ctx* ctx, const char* who, const int64_t* idx, 
       net_input(ctx, p, Xb, t->Xc, nb);
       xin = t->Xc;
     }
-    int32_t rc = net_forward(ctx, p, t->w64, xin, nb, t->hs.data(), t->wpack, false, nullptr, t->pidx.data());
+    const NetValueGrad vg{&p, t->w64, xin, Yb, nb, t->hs.data(), t->wpack, t->ssepart, sse_blocks, t->sse, {t->delta[0], t->delta[1]}, t->gw,
+                          &t->scratch, N, scale, 0.0};
+    const int32_t rc = net_value_and_grad(ctx, vg);
     if (rc != SI_OK) return rc;
-    const int64_t d = (int64_t)t->out_dim * nb;
-    const double* yhat = t->hs[nl - 1];
-    launch_sse(st, yhat, Yb, d, t->ssepart, sse_num_blocks(d, ctx->num_cu), t->sse);
-    ProfScope ps(ctx, SI_K_BACKWARD, 0.0, 0.0);
-    SI_HIP(ctx, hipMemsetAsync(t->gw, 0, (size_t)pad_ld(N) * sizeof(double), st));
-    launch_delta_out(st, Yb, yhat, d, -2.0 / d_total, SI_ACT_IDENTITY, t->delta[0]);   // d mse / d yhat = 2 (yhat - y) / d
-    if ((rc = net_backward(ctx, p, t->w64, xin, nb, t->hs.data(), t->delta[0], t->delta[1], t->gw, t->scratch)) != SI_OK) return rc;
-    SI_HIP(ctx, hipGetLastError());
-    t->grad_ready = true;
-    return SI_OK;
-  }
-  // forward with every layer's output kept; a narrow head is fed from the epilogue of the layer in front of it
-  const double* h = Xb;
-  const size_t nplain = t->fuse_tail ? nl - 2 : nl;
-  for (size_t l = 0; l < nplain; ++l) {
-    const si_layer& ly = t->layers[l];
-    ProfScope ps(ctx, SI_K_DENSE, 2.0 * (double)ly.in * ly.out * (double)nb, 0.0);
-    launch_dense_f64(st, t->w64 + ly.w_off, t->w64 + ly.b_off, h, t->hs[l], ly.out, ly.in, nb, ly.act);
-    h = t->hs[l];
-  }
-  const int64_t d = (int64_t)t->out_dim * nb;
-  const int sse_blocks = sse_num_blocks(d, ctx->num_cu);
-  if (t->fuse_tail) {
-    const si_layer& ly = t->layers[nl - 2];
-    const si_layer& ll = t->layers[nl - 1];
-    {
-      ProfScope ps(ctx, SI_K_DENSE, 2.0 * ((double)ly.in * ly.out + (double)ll.in * ll.out) * (double)nb, 0.0);
-      launch_dense_f64_fused(st, t->w64 + ly.w_off, t->w64 + ly.b_off, h, ly.out, ly.in, nb, ly.act, t->w64 + ll.w_off, ll.out,
-                             t->part, ChainBatch(), t->hs[nl - 2]);
-    }
-    launch_tail_sse(st, t->part, t->fuse_slots, ll.out, nb, t->w64 + ll.b_off, ll.act, Yb, t->hs[nl - 1], t->ssepart,
-                    sse_blocks);
-    launch_sse_final(st, t->ssepart, sse_blocks, t->sse);
-    h = t->hs[nl - 1];
   } else {
-    launch_sse(st, h, Yb, d, t->ssepart, sse_blocks, t->sse);
-  }
-  {
-    double bflops = 0.0;
-    for (const auto& ly : t->layers) bflops += 4.0 * (double)ly.in * ly.out * (double)nb;
-    ProfScope ps(ctx, SI_K_BACKWARD, bflops, 0.0);
-    SI_HIP(ctx, hipMemsetAsync(t->gw, 0, (size_t)pad_ld(N) * sizeof(double), st));
-    // d mse / d yhat = 2 (yhat - y) / d
-    launch_delta_out(st, Yb, h, d, -2.0 / d_total, t->layers[nl - 1].act, t->delta[0]);
-    DenseSweep sw{t->layers.data(), nl, t->fuse_tail, t->w64, Xb, t->hs.data(), {t->delta[0], t->delta[1]}, t->gw, t->rspart,
-                  t->bwpart, nb};
-    const int32_t rcs = dense_reverse_sweep(ctx, st, sw);
-    if (rcs != SI_OK) return rcs;
+    const DenseValueGrad vg{{t->layers.data(), nl, t->fuse_tail, t->w64, Xb, t->hs.data(), {t->delta[0], t->delta[1]}, t->gw, t->rspart,
+                             t->bwpart, nb},
+                            Yb, t->fuse_slots, t->part, t->ssepart, t->sse, sse_blocks, N, scale, false};
+    const int32_t rc = dense_value_and_grad_f64(ctx, st, vg);
+    if (rc != SI_OK) return rc;
   }
   SI_HIP(ctx, hipGetLastError());
   t->grad_ready = true;

@@ -136,10 +136,7 @@ struct CtxCore {
   double* d_gathertmp = nullptr;  // device scratch of si_comm_allgather_host, kept between calls
   size_t gathertmp_cap = 0;
 
-  // development build only (-DSI_DEV_KNOBS, SI_OVERLAP_HALVES=1): the two halves of the batch of ONE chain on two streams
-  bool overlap_halves = false;
-  hipStream_t stream2 = nullptr;
-  Event ev_fork, ev_join;
+  hipStream_t stream2 = nullptr;   // side stream (pipelined pushes, si_reconstruct's output pipeline, the streamed output map), created on first use
   // pinned host staging for the small construct-time transfers (G down, V up): pageable copies cost tens of us each
   PinBuf<double> h_pin;
   PinBuf<char> h_outpin;         // pinned staging of the samples / lp of a device-resident loop on their way to the caller's arrays
@@ -390,7 +387,7 @@ void launch_reconstruct(hipStream_t st, const double* swa, const double* P, int6
 struct ChainBatch {
   int n = 1;
   int64_t w = 0, hin = 0, hout = 0, part = 0;
-  int64_t part_ld = 0;  // column pitch of the fused-tail partials when a launch covers only a column range of B (0 = B)
+  int64_t part_ld = 0;  // column pitch of the fused-tail partials, 0 = B: nothing sets it (kept: the kernels' SGPR counts move without it)
 };
 // K5: Hout[i + out*b] = act(sum_k W[i + out*k] * Hin[k + in*b] + bias[i])
 void launch_dense_f64(hipStream_t st, const double* W, const double* bias, const double* Hin,
@@ -444,9 +441,39 @@ void launch_sse(hipStream_t st, const double* yhat, const double* y, int64_t d, 
 // backward pass (kernels_bwd.hip): gradient of the log-density w.r.t. the flat weights and its pull-back P' g
 void launch_backward_data(hipStream_t st, const double* W, const double* Delta, const double* Hprev, double* DeltaPrev,
                           int32_t out, int32_t in, int64_t B, int32_t act_prev);
-// Reverse sweep through a Dense chain shared by si_logdensity_grad (capi_infer.hip) and the training step (capi_train.hip).
-// On entry delta[0] holds Delta_L (launch_delta_out) and gw is zeroed, both on `st`; on return every dW / db of the
-// chain is in gw.
+// ---- Dense chains, host side (capi.hip): the one forward pass, the reverse sweep, and the two together -------------------------
+// Forward pass of a Dense chain on `st`, T = double / float: the plain layers, then either the fused layer (the narrow head in
+// its epilogue) + launch_tail_sse + launch_sse_final, or launch_sse / launch_sse_f32 on the last layer's output.  Returns the last
+// plain layer's output (X when there is none): without a fused head these are the model outputs in T.
+template <typename T>
+struct DenseForward {
+  const si_layer* layers;
+  size_t nl;
+  bool fuse_tail;
+  const T* w;             // flat weights in the compute type
+  const double* w64;      // the same in fp64 (the head's bias is added in fp64; == w for T = double)
+  const T* X;             // input of layer 0, in_0 x B, shared by the chain slots
+  const double* Y;
+  int64_t B;
+  // where layer l writes: kept[l] (one buffer per layer, one chain; the fused layer stores its output there as well), or with
+  // kept == nullptr pingpong[l & 1], chain slots cb.hout apart
+  const DevBuf<T>* kept;
+  T* pingpong[2];
+  ChainBatch cb;          // slot count and strides (hin is the pass's own: 0 into layer 0, hout behind it)
+  int slots;              // feature slots of the fused head
+  double* part;           // its partial products, cb.part per chain slot
+  double* yhat;           // fp64 model outputs or nullptr: written by launch_tail_sse / launch_sse_f32, chain slots out * B apart
+  double* ssepart;
+  int sse_blocks;
+  double* sse;            // cb.n sums of squared errors
+  bool defer_sse_final;   // the block partials stay in ssepart (the caller's next kernel sums them)
+  int main_layer;         // the layer whose launch is also counted as SI_K_DENSE_MAIN (the head counts with its fused layer), or -1
+  bool traffic;           // profile: bytes of the SI_K_DENSE scopes and the SI_K_SSE scope (false: flops of SI_K_DENSE only)
+};
+template <typename T>
+const T* dense_forward(Ctx* ctx, hipStream_t st, const DenseForward<T>& a);
+// Reverse sweep through a Dense chain.  On entry delta[0] holds Delta_L (launch_delta_out) and gw is zeroed, both on `st`; on
+// return every dW / db of the chain is in gw.
 struct DenseSweep {
   const si_layer* layers;
   size_t nl;
@@ -461,10 +488,24 @@ struct DenseSweep {
   int64_t B;
 };
 int32_t dense_reverse_sweep(Ctx* ctx, hipStream_t st, const DenseSweep& s);
-// The same in fp32 together with the forward pass (capi_train.hip; kernels_gemm_f32.hip + kernels_bwd_f32.hip): forward with every
-// layer's output kept, the SSE (fp64), Delta_L = scale * (y - yhat) * act_L'(yhat), reverse sweep; on return gw32 holds
-// d (scale/2 * -SSE) / dw rounded to fp32 and *sse the sum of squared errors.  Shared by the training step and si_logdensity_grad
-// with compute_dtype = SI_F32.
+// Value and gradient in fp64, shared by si_logdensity_grad and the training step: dense_forward with every output kept in sw.hs,
+// gw zeroed, Delta_L = scale * (y - yhat) * act_L'(yhat), dense_reverse_sweep; on return gw holds d (scale/2 * -SSE) / dw and
+// *sse the sum of squared errors.
+struct DenseValueGrad {
+  DenseSweep sw;
+  const double* Y;
+  int slots;            // feature slots of the fused head
+  double* part;         // head partials [slots][out_last][B]
+  double *ssepart, *sse;
+  int sse_blocks;
+  int64_t N;
+  double scale;         // of Delta_L: -2 / d for the mse loss, 1 / sigma^2 for the log-density
+  bool traffic;         // as DenseForward::traffic
+};
+int32_t dense_value_and_grad_f64(Ctx* ctx, hipStream_t st, const DenseValueGrad& s);
+// The same in fp32 (capi_train.hip; kernels_gemm_f32.hip + kernels_bwd_f32.hip): dense_forward<float> with every output kept, the
+// SSE (fp64), Delta_L, the fp32 reverse sweep; on return gw32 holds the gradient rounded to fp32 and *sse the sum of squared
+// errors.  Shared by the training step and si_logdensity_grad with compute_dtype = SI_F32.
 bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const si_layer* layers, int L, bool fuse_tail, int64_t N, int32_t in_dim, int32_t out_dim,
                      int64_t Bmax);
 struct DenseSweepF32 {
@@ -573,12 +614,12 @@ void net_input(Ctx* c, const NetPlan& p, const double* X, double* Xc, int64_t B)
 // `outs[l]` receives layer l's output.  pingpong = true (density path: nothing but the last output is needed): `outs` holds TWO
 // buffers used alternately per EXECUTED layer, a Conv directly followed by MaxPool((2, 2)) on even sizes runs as one fused
 // kernel, and *final_out is the buffer that holds the last layer's output.
-// pidx != nullptr (gradient mode, outs[l] per layer): a Conv layer with net_grad_fused(p, l) runs fused with its MaxPool, writes
-// outs[l + 1] and pidx[l] and leaves outs[l] untouched (it may be nullptr)
-int32_t net_forward_f32(Ctx* c, const NetPlan& p, const float* w, const float* xin, int64_t B, const DevBuf<float>* outs, float* wpack,
-                        float** final_out);
-int32_t net_forward(Ctx* c, const NetPlan& p, const double* w, const double* xin, int64_t B, const DevBuf<double>* outs, double* wpack,
-                    bool pingpong = false, double** final_out = nullptr, const DevBuf<uint8_t>* pidx = nullptr);
+// pidx != nullptr (gradient mode, outs[l] per layer, T = double only): a Conv layer with net_grad_fused(p, l) runs fused with its
+// MaxPool, writes outs[l + 1] and pidx[l] and leaves outs[l] untouched (it may be nullptr).
+// T = float (compute_dtype = SI_F32): the pingpong pass on fp32 weights, input and activations.
+template <typename T>
+int32_t net_forward(Ctx* c, const NetPlan& p, const T* w, const T* xin, int64_t B, const DevBuf<T>* outs, T* wpack, bool pingpong = false,
+                    T** final_out = nullptr, const DevBuf<uint8_t>* pidx = nullptr);
 // Conv layer l directly followed by MaxPool((2, 2), stride 2) on even sizes, activation carried by the GEMM epilogue: in
 // gradient mode the pair runs as one kernel that keeps a byte index instead of the un-pooled activation
 bool net_grad_fused(const NetPlan& p, size_t l);
@@ -587,6 +628,25 @@ void net_scratch_sizes(const NetPlan& p, int64_t B, int num_cu, size_t* bwpart, 
 // g0 holds d / d(output of the last layer) (out_feat x B) on entry; g0 / g1: max_elems * B doubles each; hs[l]: kept outputs
 int32_t net_backward(Ctx* c, const NetPlan& p, const double* w, const double* xin, int64_t B, const DevBuf<double>* hs, double* g0,
                      double* g1, double* gw, const NetScratch& s);
+// Value and gradient of such a chain on c->stream, shared by si_logdensity_grad and the training step: net_forward in gradient mode
+// (outputs kept in hs, pool indices in scratch->pidx), the SSE, gw zeroed, Delta = scale * (y - yhat), net_backward.
+struct NetValueGrad {
+  const NetPlan* plan;
+  const double *w, *xin, *Y;
+  int64_t B;
+  const DevBuf<double>* hs;
+  double* wpack;
+  double* ssepart;
+  int sse_blocks;
+  double* sse;
+  double* delta[2];     // max_elems * B doubles each
+  double* gw;
+  const NetScratch* scratch;
+  int64_t N;
+  double scale;         // -2 / d for the mse loss, 1 / sigma^2 for the log-density
+  double bwd_flops;     // what the caller reports for its SI_K_BACKWARD scope
+};
+int32_t net_value_and_grad(Ctx* c, const NetValueGrad& s);
 // K6, device-resident loop (kernels_chain.hip): all `itr` transitions of `nchains` small Dense chains in ONE launch, one
 // workgroup per chain, weights / data / activations in LDS; bit-identical to the launch-per-step loop of si_sample_rwmh
 constexpr int SI_CHAIN_MAX_LAYERS = 8;

@@ -269,6 +269,26 @@ def pool_ties_are_exact(pb, c):
         h = so._layer_forward(row, w, h)
 
 
+def pool_tie_count(pb, c):
+    """(windows whose maximum is attained by more than one input, windows) over every MaxPool row at column c"""
+    w = pb.w_swa + pb.p @ pb.z[:, c]
+    h, ties, wins = pb.x, 0, 0
+    for row in pb.table:
+        if row[0] == "maxpool":
+            _, win, ch, (wi, hi), stride = row
+            x4 = h.reshape((wi, hi, ch, -1), order="F")
+            y = so.maxpool_forward(x4, win, stride)
+            wo, ho = y.shape[:2]
+            cnt = np.zeros(y.shape)
+            for a in range(win[0]):
+                for d in range(win[1]):
+                    cnt += x4[a: a + (wo - 1) * stride[0] + 1: stride[0], d: d + (ho - 1) * stride[1] + 1: stride[1]] == y
+            ties += int(np.sum(cnt > 1))
+            wins += y.size
+        h = so._layer_forward(row, w, h)
+    return ties, wins
+
+
 def mse_grad_exact(table, w, x, y, nb_total, limit=F64_LIMIT):
     """the training gradient of si_train_grad: d/dw of sum((f(x) - y)^2) / (out * nb_total) over the observations in x
     (the rank's share of a batch of nb_total).  out * nb_total must be a power of two so the scale is exact.

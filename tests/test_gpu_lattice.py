@@ -182,6 +182,8 @@ def test_train_grad_exact(si, gpu_ctx, dims, nbt, f32):
 
 
 # ----------------------------------------------------------------------------------------------- Conv
+# (these shapes are the ragged ones of tests/test_gpu_conv.py, picked for raggedness and not for dispatch: they reach 32 of the 82
+#  conv instantiations.  tests/test_gpu_conv_exact.py holds every reachable one, route by route, with the whole weight gradient.)
 def _conv_cases():
     from tests.test_gpu_conv import CASES
     out = []

@@ -268,6 +268,40 @@ int32_t si_sample_mala(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, 
 /* the last si_sample_mala call: fused_out = 1 when it took the device-resident route, passes_out = gradient passes per transition
  * (fused: ceil(nchains / points per pass); other route: one per chain)                                                          */
 int32_t si_mala_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out);
+/* :139-160  HMC: StaticTrajectory(Leapfrog(eps), 1) under StanHMCAdaptor(MassMatrixAdaptor(DiagEuclideanMetric), StepSizeAdaptor(delta))
+ * after find_good_stepsize (AdvancedHMC 0.2.27) [upstream, unverifiable offline], with position, momentum, step size, metric and
+ * adaptor state on the device.  State rules and prior term: si_logdensity_grad_batch's.  Chain c draws from Philox chain
+ * chain_id0 + c: purpose 0 at step 0 = the initial point's normals (si_sample_mala's z_0); purpose 1 at step t, block 0 = the
+ * uniform u_t = u53(x1, x0); purpose 5 at step t = the momentum normals n_t; purpose 6 at step 0 = the search's momentum rho.
+ *     z_0 = sigma_z n_0;  (lp_0, g_0) at z_0;  Minv = 1
+ *     search   h0 = lp_0 - rho.rho / 2;  dH(e) = lpp - rp.rp / 2 - h0 after one leapfrog step of size e from (z_0, rho)
+ *              eps = 0.1;  direction = dH(eps) > log 0.5 ? +1 : -1
+ *              at most 100 times: eps' = 2 eps or eps / 2;  d = dH(eps) (at the OLD eps);  stop when d has left the starting side of
+ *              log 0.5, else eps = eps'.  Then (lo, hi) = (eps, eps') sorted and at most 100 times: mid = (lo + hi) / 2,
+ *              a = exp(dH(mid));  a > 0.75: lo = mid;  a < 0.25: hi = mid;  else lo = mid and stop.  eps_0 = lo.
+ *     t = 1 .. itr, with the adaptor's current (eps, Minv):
+ *              r = n_t / sqrt(Minv);  K0 = sum((Minv r) r) / 2;  rh = r + (eps / 2) g;  zp = z + eps (Minv rh);  (lpp, gp) at zp
+ *              rp = rh + (eps / 2) gp;  K1 = sum((Minv rp) rp) / 2;  dH = (lpp - K1) - (lp - K0)
+ *              a = 0 if lpp - K1 is not finite, 1 if dH >= 0, else exp(dH);  accept iff u_t < a:  (z, lp, g) = (zp, lpp, gp)
+ *              column t of Z / lp / G = the state;  alpha[t] = a;  eps[t] and Minv[:, t] = those USED by transition t
+ *              t <= n_adapts: dual averaging (gamma 0.05, t0 10, kappa 0.75, mu = log 10 eps) of log eps towards delta; inside a
+ *              window (si_host_hmc_windows) the Welford update with the KEPT z; at a window's close
+ *              Minv = n / (n + 5) var + 1e-3 5 / (n + 5), the window emptied, the dual averaging restarted at the current eps;
+ *              after step n_adapts eps = exp(the averaged log eps)
+ * Column 0 of the outputs is the initial state with alpha = 0, eps = eps_0 and Minv = 1.  Every sum over m has si_sample_mala's
+ * order: a chain's bits depend on M alone, not on nchains, its column, the pass split or the run.
+ * SI_ERR_INVALID unless itr > 0, 0 <= n_adapts <= itr, nchains > 0, chain_id0 >= 0, sigma_z > 0 and 0 < delta < 1 (a NaN is refused).
+ * Routes as si_sample_mala's: chains of the fused class queue the gradient's launches and ONE accept launch (which also forms the
+ * next proposal) per transition and synchronise once, at the end; every other chain takes the slow per-point route through the host.
+ * THE SEARCH IS A SYNCHRONISING PREAMBLE on both routes: after each of its rounds (at most 203) the host reads back one 4-byte count
+ * of the chains still searching.                                                                                                 */
+int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z, double delta, uint64_t seed, int32_t chain_id0,
+                      int32_t nchains, double* Z_out /* M x (itr+1) x C */, double* lp_out /* (itr+1) x C */,
+                      double* alpha_out /* (itr+1) x C */, double* eps_out /* (itr+1) x C */,
+                      double* G_out /* like Z_out, or NULL */, double* Minv_out /* like Z_out, or NULL */);
+/* the last si_sample_hmc call: fused_out = 1 when it took the device-resident route, passes_out = gradient passes per transition
+ * (as si_mala_kernel_info), search_rounds_out = rounds of the step-size search, the one at z_0 included                           */
+int32_t si_hmc_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out, int32_t* search_rounds_out);
 /* :126-138  ADVI with its state on the device.  Restates
  *     AdvancedVI.vi(density, ADVI(S, T), theta -> TuringDiagMvNormal(theta[1:M], exp.(theta[M+1:2M])), rand(MvNormal(zeros(2M), sigma_z)))
  * followed by rand(q, D) (AdvancedVI 0.1.3), with that version's default optimiser TruncatedADAGrad(eta = 0.1, tau = 1.0,
@@ -499,6 +533,11 @@ int si_host_sym_eig_top(int n, const double* g, int m, double* w_top, double* V)
  * |a_pq| <= eps*sqrt(a_pp*a_qq) for a symmetric positive semi-definite matrix (eigenvalues accurate relative to
  * themselves for graded matrices).  a: n x n column-major, destroyed; w: eigenvalues DESCENDING; v: eigenvectors.   */
 int si_host_jacobi_eig_psd(int n, double* a, double* w, double* v);
+/* the window schedule of si_sample_hmc's metric adaptation for n_adapts steps (host only): *window_start .. *window_end are the
+ * steps inside a window, splits[0 .. count) the steps that close one (at most `cap` are written).  Init buffer 75, terminal buffer
+ * 50, windows doubling from 25, the last stretched to window_end; 15 % / 75 % / 10 % for 20 <= n_adapts < 150; below 20 no step is
+ * inside a window.  Returns count.                                                                                              */
+int32_t si_host_hmc_windows(int64_t n_adapts, int64_t* window_start, int64_t* window_end, int64_t* splits, int32_t cap);
 /* The host copy pool (si_construct_push, si_reconstruct, si_sample_rwmh_weights) sizes itself from the CPUs the process may
  * really use: the affinity mask capped by the cgroup CPU quota (si_host_cpu_budget; a container that shows 256 CPUs and
  * grants 16 gets 16).  Threads per process = SI_HOST_COPY_THREADS if set, else min(8, budget / (2 * nproc)) with nproc = the

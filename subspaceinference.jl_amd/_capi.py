@@ -98,6 +98,9 @@ SIGNATURES = {
     "si_sample_mala": (c_int32, [c_void_p, c_int64, c_double, c_uint64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                  c_void_p]),
     "si_mala_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
+    "si_sample_hmc": (c_int32, [c_void_p, c_int64, c_int64, c_double, c_double, c_uint64, c_int32, c_int32, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "si_hmc_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "si_fit_advi": (c_int32, [c_void_p, c_int64, c_int32, c_double, c_double, c_double, c_int32, c_uint64, c_int32, c_int32, c_int64,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "si_advi_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
@@ -145,6 +148,7 @@ SIGNATURES = {
     "si_chain_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
     "si_chain_spec_message": (c_char_p, [c_void_p]),
     "si_construct_set_storage": (c_int32, [c_void_p, c_int32]),
+    "si_host_hmc_windows": (c_int32, [c_int64, POINTER(c_int64), POINTER(c_int64), c_void_p, c_int32]),
     "si_host_cpu_budget": (c_int, []),
     "si_host_parse_cpu_max": (c_double, [c_char_p]),
     "si_host_copy_plan": (c_int, [c_int, c_int, c_char_p]),
@@ -670,6 +674,30 @@ class Context:
         self._check(self.lib.si_mala_kernel_info(self.h, byref(f), byref(p)))
         return int(f.value), int(p.value)
 
+    def sample_hmc(self, itr, sigma_z, seed, chain_id0=0, nchains=1, n_adapts=None, delta=0.8, grad=False, metric=False):
+        """si_sample_hmc: the reference's one-step HMC under the Stan adaptor with position, momentum, step size, metric and adaptor
+        state on the device, on the library's Philox streams.  n_adapts=None is the reference's Int(round(itr / 2)) (ties to even,
+        like Python's round).  Returns (z, lp, alpha, eps) with itr + 1 columns -- column 0 is the initial state, alpha[t] the
+        acceptance probability of transition t and eps[t] the step size it used -- then G (grad=True: d lp / d z at every state)
+        and Minv (metric=True: the diagonal metric transition t used), each of z's shape."""
+        itr, c = int(itr), int(nchains)
+        na = int(round(itr / 2)) if n_adapts is None else int(n_adapts)
+        cols = max(itr, 0) + 1
+        z = np.empty((self._m, cols, max(c, 0)), dtype=np.float64, order="F")
+        lp, alpha, eps = (np.empty((cols, max(c, 0)), dtype=np.float64, order="F") for _ in range(3))
+        g = np.empty_like(z, order="F") if grad else None
+        mi = np.empty_like(z, order="F") if metric else None
+        self._check(self.lib.si_sample_hmc(self.h, itr, na, float(sigma_z), float(delta), int(seed), int(chain_id0), c, _ptr(z),
+                                           _ptr(lp), _ptr(alpha), _ptr(eps), _ptr(g), _ptr(mi)))
+        return (z, lp, alpha, eps) + ((g,) if grad else ()) + ((mi,) if metric else ())
+
+    def hmc_kernel_info(self):
+        """(fused, passes, search_rounds) of the last sample_hmc: did it take the device-resident route, gradient passes per
+        transition, rounds of the synchronising step-size search (the evaluation at z_0 included)"""
+        f, p, r = c_int32(0), c_int32(0), c_int32(0)
+        self._check(self.lib.si_hmc_kernel_info(self.h, byref(f), byref(p), byref(r)))
+        return int(f.value), int(p.value), int(r.value)
+
     def fit_advi(self, max_iters, sigma_z, seed, samples_per_step=10, eta=0.1, tau=1.0, window=100, chain_id0=0, nruns=1,
                  ndraws=None, trace=False):
         """si_fit_advi: the reference's ADVI (src/space_inference.jl:126-138) with its state on the device, on the library's Philox
@@ -780,6 +808,17 @@ def row_shard(n_total, rank, world):
     if load().si_row_shard(int(n_total), int(rank), int(world), byref(r0), byref(r1)) != SI_OK:
         raise SubspaceError("si_row_shard: bad argument")
     return int(r0.value), int(r1.value)
+
+
+def host_hmc_windows(n_adapts):
+    """si_host_hmc_windows: (window_start, window_end, [steps that close a window]) of si_sample_hmc's metric adaptation -- the
+    schedule of samplers.StanAdaptor (needs no GPU)."""
+    lib = load()
+    ws, we = c_int64(), c_int64()
+    n = lib.si_host_hmc_windows(int(n_adapts), byref(ws), byref(we), None, 0)
+    splits = np.zeros(max(1, n), dtype=np.int64)
+    lib.si_host_hmc_windows(int(n_adapts), byref(ws), byref(we), _ptr(splits), n)
+    return int(ws.value), int(we.value), [int(v) for v in splits[:n]]
 
 
 def host_sym_eig(g):

@@ -139,7 +139,7 @@ def subspace_construction(model, cost, data, opt, T=10, c=1, M=3, print_freq=1, 
 def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=100, M=3, alg="rwmh",
                   backend="forwarddiff", *, sigma_z=None, sigma_m=None, sigma_p=None, device=0, ctx=None,
                   seed=0, chain_id=0, return_z=False, nchains=1, include_prior=False, compute_dtype="f64",
-                  device_loop=False):
+                  device_loop=False, device_sampler=False):
     """src/space_inference.jl:82-164 for a Chain model and alg = :rwmh.
 
     `density(z)` (:90-95: W_swa + P*z -> model_re -> forward over the FULL data -> Gaussian log-likelihood,
@@ -163,6 +163,11 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
     synchronisation per call instead of one round trip per transition.  The default keeps the host loop and its results.
     alg = :advi exists as the device loop only (si_fit_advi: the reference's ADVI(10, itr) fit and its `rand(q, itr)` on the Philox
     streams, one run per call): without the keyword it raises, as it always has; lp is zeros(itr), as in the reference (:136).
+
+    `device_sampler=True` (alg = :hmc; non-default) runs the reference's one-step HMC with position, momentum, step size, metric
+    and adaptor state on the device (si_sample_hmc): the transition, adaptor and step-size search of `samplers.hmc` on the Philox
+    streams (seed, chain_id + c), n_adapts = round(itr / 2); the initial state is dropped, so itr samples and lp come back like
+    the host path's.  It allows nchains > 1, with :mala's shapes.  The default :hmc stays `samplers.hmc` on PCG64, bit for bit.
     """
     σ_z = σ_z if sigma_z is None else sigma_z
     σ_m = σ_m if sigma_m is None else sigma_m
@@ -193,10 +198,13 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
             ctx.infer_setup(table, n_par, M, W_swa, P, x, y, σ_m, compute_dtype=cdt)
         # include_prior=True adds the term the reference leaves dead after its `return` (quirk Q4); default: as the reference
         ctx.set_prior(σ_p if include_prior else 0.0)
+        if device_sampler and a != "hmc":
+            raise SubspaceError("device_sampler=True is available for alg = :hmc only" + (
+                " (alg = :%s runs on the device with device_loop=True)" % a if a in ("mala", "advi") else ""))
         if device_loop and a not in ("mala", "advi"):
             raise SubspaceError("device_loop=True is available for alg = :mala and :advi only")
-        if nchains != 1 and a not in _RWMH_ALGS and a != "mala":
-            raise SubspaceError("nchains > 1 is available for alg = :rwmh / :mh / :mala only")
+        if nchains != 1 and a not in _RWMH_ALGS and a != "mala" and not (a == "hmc" and device_sampler):
+            raise SubspaceError("nchains > 1 is available for alg = :rwmh / :mh / :mala (and :hmc with device_sampler=True) only")
         if a in _RWMH_ALGS:
             if return_z:
                 z, lp, _ = ctx.sample_rwmh(itr, σ_z, seed, chain_id, nchains)
@@ -214,8 +222,12 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
                 # :126-138: vi(density, ADVI(10, itr), q, theta_0), then rand(q, itr); the reference returns zeros(itr) for lp
                 _, z, _ = ctx.fit_advi(itr, σ_z, seed, chain_id0=chain_id)
                 z, lp = z[:, :, 0], np.zeros(itr)
-            elif a == "mala" and device_loop:
-                z, lp, _ = ctx.sample_mala(itr, σ_z, seed, chain_id, nchains)
+            elif (a == "mala" and device_loop) or (a == "hmc" and device_sampler):
+                if a == "hmc":
+                    # :139-160 with the state on the device; column 0 (the initial state) is not a sample of the reference's
+                    z, lp = (np.asfortranarray(v[..., 1:, :]) for v in ctx.sample_hmc(itr, σ_z, seed, chain_id, nchains)[:2])
+                else:
+                    z, lp, _ = ctx.sample_mala(itr, σ_z, seed, chain_id, nchains)
                 if nchains > 1:
                     if return_z:
                         return z, lp
@@ -250,7 +262,7 @@ def inference(*args, **kwargs):
 def subspace_inference(model, cost, data, opt, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=1000, T=25, c=1, M=20,
                        print_freq=1, alg="rwmh", backend="forwarddiff", method="subspace", *, sigma_z=None,
                        sigma_m=None, sigma_p=None, device=0, ctx=None, seed=0, verbose=True, return_z=False,
-                       compute_dtype="f64", device_loop=False):
+                       compute_dtype="f64", device_loop=False, device_sampler=False):
     """src/space_inference.jl:33-54: construction, then sampling; returns (chn, lp, W_swa).
     W_swa and P stay on the device between the two stages (no host round trip)."""
     m = _alg_name(method)
@@ -267,7 +279,8 @@ def subspace_inference(model, cost, data, opt, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr
                                          verbose=verbose, keep_on_device=True)
         chn, lp = sub_inference(model, data, None, None, σ_z=σ_z, σ_m=σ_m, σ_p=σ_p, itr=itr, M=M, alg=alg,
                                 backend=backend, sigma_z=sigma_z, sigma_m=sigma_m, ctx=ctx, seed=seed,
-                                return_z=return_z, compute_dtype=compute_dtype, device_loop=device_loop)
+                                return_z=return_z, compute_dtype=compute_dtype, device_loop=device_loop,
+                                device_sampler=device_sampler)
         return chn, lp, w_swa
     finally:
         if own:

@@ -1,5 +1,5 @@
 // Declarations shared by the translation units of the C ABI (capi.hip: context + construction; capi_infer.hip: inference set-up,
-// density, gradient, predictive forward; capi_sample.hip: the RWMH samplers and the output map; capi_mala.hip: the MALA sampler; capi_advi.hip: the ADVI fit).  Nothing here is part of the
+// density, gradient, predictive forward; capi_sample.hip: the RWMH samplers and the output map; capi_mala.hip: the MALA sampler; capi_hmc.hip: the HMC sampler; capi_advi.hip: the ADVI fit).  Nothing here is part of the
 // public interface (include/subspace_hip.h).  Buffers are owned by the types of dev_buf.h (through si_internal.h): no file of
 // the C ABI calls hipMalloc / hipFree / hipHostMalloc / hipHostFree or creates an event by hand.
 #pragma once

@@ -1,0 +1,192 @@
+// C ABI, HMC (reference src/space_inference.jl:139-160): si_sample_hmc, si_hmc_kernel_info, si_host_hmc_windows.  The transition, the
+// adaptor update and the step-size search are defined once, in kernels_hmc.hip; this file queues them.  Host-side orchestration
+// only; no CPU fallback anywhere in this file.
+//
+// Two routes, one definition, one audit (tests/hmc_audit.py), as si_sample_mala's:
+//   fused   chains of si_logdensity_grad_batch's fused class: per transition the gradient's launches (once per pass of vg_cap chains,
+//           outputs left on the device) and hmc_accept_kernel are queued on the stream; position, momentum, step size, metric and
+//           adaptor state never leave the device.  A launch-queued loop: no persistent kernel, no grid barrier, nothing that can spin.
+//   other   every other chain (Conv / MaxPool / flatten, SI_F32, the four later activations, wide layers): the same kernels, but the
+//           proposals come down to the host and their values and gradients go back up column by column through si_logdensity_grad's
+//           own path.  SLOW AND SYNCHRONISING: one round trip per chain and transition.
+// THE PREAMBLE SYNCHRONISES on both routes: the step-size search is data dependent, so after every round (search kernel, value and
+// gradient at the trial points) the host reads back ONE 4-byte count of the chains still searching.  It is a one-off before the
+// first transition, bounded by the restatement's own limits (1 + 100 + 100 evaluations after the one at z_0), and the only place
+// where the call reads back before its tail.
+#include "capi_common.h"
+
+using namespace si;
+
+namespace si {
+
+// samplers.StanAdaptor.__init__: init buffer 75, terminal buffer 50, windows doubling from 25 with the last one stretched to the end
+// of the slow phase; 15 % / 75 % / 10 % when the three do not fit and n_adapts >= 20; below 20 no step is inside a window
+int32_t hmc_windows(int64_t n_adapts, int64_t* window_start, int64_t* window_end, int64_t* splits, int32_t cap) {
+  int64_t init_buffer = 75, term_buffer = 50, window_size = 25;
+  if (init_buffer + window_size + term_buffer > n_adapts) {
+    if (n_adapts >= 20) {
+      init_buffer = (int64_t)(0.15 * (double)n_adapts);
+      term_buffer = (int64_t)(0.1 * (double)n_adapts);
+      window_size = n_adapts - init_buffer - term_buffer;
+    } else {
+      init_buffer = n_adapts + 1;
+      term_buffer = 0;
+      window_size = 1;
+    }
+  }
+  if (window_start) *window_start = init_buffer + 1;
+  const int64_t end = n_adapts - term_buffer;
+  if (window_end) *window_end = end;
+  int32_t count = 0;
+  for (int64_t nxt = init_buffer + window_size; nxt <= end;) {
+    if (nxt + 2 * window_size > end) nxt = end;
+    if (splits && count < cap) splits[count] = nxt;
+    ++count;
+    window_size *= 2;
+    nxt += window_size;
+  }
+  return count;
+}
+
+}  // namespace si
+
+extern "C" {
+
+int32_t si_host_hmc_windows(int64_t n_adapts, int64_t* window_start, int64_t* window_end, int64_t* splits, int32_t cap) {
+  if (n_adapts < 0) return 0;
+  return hmc_windows(n_adapts, window_start, window_end, splits, cap);
+}
+
+int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z, double delta, uint64_t seed, int32_t chain_id0,
+                      int32_t nchains, double* Z_out, double* lp_out, double* alpha_out, double* eps_out, double* G_out,
+                      double* Minv_out) {
+  CHECK_CTX(ctx);
+  const char* who = "si_sample_hmc";
+  ctx->last_hmc_fused = ctx->last_hmc_passes = ctx->last_hmc_rounds = 0;   // (si_hmc_kernel_info reports THIS call)
+  // (every comparison is false for a NaN: refused)
+  int32_t rc = grad_entry_check(ctx, who, itr > 0 && n_adapts >= 0 && n_adapts <= itr && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0 &&
+                                              delta > 0.0 && delta < 1.0);
+  if (rc != SI_OK) return rc;
+  BIND(ctx);
+  const int32_t C = nchains, M = ctx->iM;
+  const int64_t cols = itr + 1;
+  if (ctx->hmc_cap < C) {
+    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->hmc_cap = 0;
+    const size_t mc = (size_t)M * (size_t)C;
+    if (!ctx->d_hmc_z.alloc(mc) || !ctx->d_hmc_g.alloc(mc) || !ctx->d_hmc_zp.alloc(mc) || !ctx->d_hmc_gp.alloc(mc) ||
+        !ctx->d_hmc_rh.alloc(mc) || !ctx->d_hmc_minv.alloc(mc) || !ctx->d_hmc_wmean.alloc(mc) || !ctx->d_hmc_wm2.alloc(mc) ||
+        !ctx->d_hmc_lp.alloc((size_t)C) || !ctx->d_hmc_lpp.alloc((size_t)C) || !ctx->d_hmc_chain.alloc((size_t)C) ||
+        !ctx->d_hmc_open.alloc(1))
+      return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": sampler state allocation failed");
+    ctx->hmc_cap = C;
+  }
+  const size_t zelems = (size_t)M * (size_t)cols * (size_t)C, selems = (size_t)cols * (size_t)C;
+  if (!ctx->d_outZ.reserve(zelems) || !ctx->d_outlp.reserve(selems) || !ctx->d_outalpha.reserve(selems) || !ctx->d_outeps.reserve(selems) ||
+      (G_out && !ctx->d_outG.reserve(zelems)) || (Minv_out && !ctx->d_outMinv.reserve(zelems)))
+    return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
+  int64_t ws = 0, we = 0;
+  std::vector<int64_t> splits((size_t)std::max<int32_t>(1, hmc_windows(n_adapts, nullptr, nullptr, nullptr, 0)));
+  const int32_t nsplits = hmc_windows(n_adapts, &ws, &we, splits.data(), (int32_t)splits.size());
+  HmcRun a{ctx->d_hmc_z, ctx->d_hmc_lp, ctx->d_hmc_g, ctx->d_hmc_zp, ctx->d_hmc_rh, ctx->d_hmc_minv, ctx->d_hmc_wmean, ctx->d_hmc_wm2,
+           ctx->d_hmc_lpp, ctx->d_hmc_gp, ctx->d_hmc_chain, ctx->d_outZ, ctx->d_outlp, ctx->d_outalpha, ctx->d_outeps,
+           G_out ? ctx->d_outG.get() : nullptr, Minv_out ? ctx->d_outMinv.get() : nullptr, M, chain_id0, itr, seed, sigma_z, delta};
+  int64_t G = 0, fit = 0;
+  const int nb = vgrad_route(ctx, &G, &fit);
+  const bool fused = fit >= 1;
+  if (fused && (rc = vgrad_ensure(ctx, who, (int)std::min<int64_t>(fit, C), G)) != SI_OK) return rc;
+  const int passes = fused ? (C + ctx->vg_cap - 1) / ctx->vg_cap : C;
+  std::vector<double> hz, hlp, hg;   // the other route's host images of the proposals, their values and gradients
+  if (!fused) {
+    hz.resize((size_t)M * C);
+    hlp.resize((size_t)C);
+    hg.resize((size_t)M * C);
+  }
+  hipError_t e = hipSuccess;
+  // value and gradient at d_hmc_zp into d_hmc_lpp / d_hmc_gp, on the call's route
+  auto value_grad = [&]() {
+    if (fused) {
+      for (int32_t p0 = 0; p0 < C; p0 += ctx->vg_cap)
+        vgrad_pass(ctx, nb, G, ctx->d_hmc_zp + (size_t)M * p0, std::min<int32_t>(ctx->vg_cap, C - p0), ctx->d_hmc_lpp + p0,
+                   ctx->d_hmc_gp + (size_t)M * p0);
+      e = hipGetLastError();
+      return;
+    }
+    e = hipMemcpyAsync(hz.data(), ctx->d_hmc_zp, hz.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (also: the uploads of the evaluation before have left hlp / hg)
+    for (int32_t c = 0; c < C && e == hipSuccess && rc == SI_OK; ++c)
+      rc = logdensity_grad_point(ctx, hz.data() + (size_t)M * c, hlp.data() + c, hg.data() + (size_t)M * c);
+    if (rc != SI_OK) return;
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_hmc_lpp, hlp.data(), hlp.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_hmc_gp, hg.data(), hg.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+  };
+  {
+    ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+    launch_hmc_init(ctx->stream, a, C);
+    e = hipGetLastError();
+  }
+  // the preamble: z_0's value and gradient, then the search, round by round (at most 1 + 1 + 100 + 100 rounds: the start, the
+  // direction, the crossings, the bisections)
+  int rounds = 0;
+  int32_t open = 1;
+  while (open > 0 && e == hipSuccess && rc == SI_OK && rounds < 2 * 100 + 3) {
+    value_grad();
+    if (e != hipSuccess || rc != SI_OK) break;
+    e = hipMemsetAsync(ctx->d_hmc_open, 0, sizeof(int32_t), ctx->stream);
+    if (e != hipSuccess) break;
+    {
+      ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+      launch_hmc_search(ctx->stream, a, C, ctx->d_hmc_open);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&open, ctx->d_hmc_open, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    ++rounds;
+  }
+  if (e == hipSuccess && rc == SI_OK && open > 0) rc = fail(ctx, SI_ERR_STATE, std::string(who) + ": the step-size search did not finish within its own limits");
+  if (e == hipSuccess && rc == SI_OK) {
+    ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+    launch_hmc_propose(ctx->stream, a, C, 1);
+    e = hipGetLastError();
+  }
+  size_t next_split = 0;
+  for (int64_t t = 1; t <= itr && e == hipSuccess && rc == SI_OK; ++t) {
+    value_grad();
+    if (e != hipSuccess || rc != SI_OK) break;
+    const bool adapting = t <= n_adapts, in_window = adapting && ws <= t && t <= we;
+    while (next_split < (size_t)nsplits && splits[next_split] < t) ++next_split;
+    const bool window_close = in_window && next_split < (size_t)nsplits && splits[next_split] == t;
+    ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+    launch_hmc_accept(ctx->stream, a, C, (uint64_t)t, adapting, in_window, window_close, t == n_adapts, t < itr);
+    e = hipGetLastError();
+  }
+  // the common tail (the pattern of si_sample_mala): the downloads, ONE synchronisation, the first error reported
+  const bool ok = e == hipSuccess && rc == SI_OK;
+  auto down = [&](double* dst, const double* src, size_t n) {
+    if (ok && e == hipSuccess && dst) e = hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  };
+  down(Z_out, ctx->d_outZ, zelems);
+  down(lp_out, ctx->d_outlp, selems);
+  down(alpha_out, ctx->d_outalpha, selems);
+  down(eps_out, ctx->d_outeps, selems);
+  down(G_out, a.G_out, zelems);
+  down(Minv_out, a.Minv_out, zelems);
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  if (rc != SI_OK) return rc;
+  if (e != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  if (e2 != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e2));
+  ctx->last_hmc_fused = fused ? 1 : 0;
+  ctx->last_hmc_passes = passes;
+  ctx->last_hmc_rounds = rounds;
+  return SI_OK;
+}
+
+int32_t si_hmc_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out, int32_t* search_rounds_out) {
+  CHECK_CTX(ctx);
+  if (fused_out) *fused_out = ctx->last_hmc_fused;
+  if (passes_out) *passes_out = ctx->last_hmc_passes;
+  if (search_rounds_out) *search_rounds_out = ctx->last_hmc_rounds;
+  return SI_OK;
+}
+
+}  // extern "C"

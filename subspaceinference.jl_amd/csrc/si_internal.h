@@ -224,6 +224,15 @@ struct ConstructState {
   DevBuf<double> d_B;             // ldA x K
 };
 
+// per-chain scalars of si_sample_hmc (kernels_hmc.hip): the adaptor's dual averaging and Welford count, the kinetic energy of the
+// proposal's momentum, and the state machine of the step-size search
+struct HmcChain {
+  double eps, mu, hbar, log_eps_bar, k0;
+  int64_t da_t, wn;
+  double s_eps, s_next, s_lo, s_hi, s_h0, s_trial;   // search: current / candidate step size, the bracket, H at z_0, the trial's step
+  int32_t s_phase, s_dir, s_iter, s_done;
+};
+
 // ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops
 struct InferState {
   bool i_ready = false;
@@ -301,6 +310,16 @@ struct InferState {
   DevBuf<int64_t> d_mala_nacc;                               // C
   DevBuf<double> d_outG;                                     // M x itr x C, kept between calls like d_outZ
   int last_mala_fused = 0, last_mala_passes = 0;             // si_mala_kernel_info
+  // si_sample_hmc (capi_hmc.hip, kernels_hmc.hip): the chains' state as MALA's, the half-kicked momentum of the proposal, the metric
+  // with its Welford window, the per-chain scalars (HmcChain) and the device-side alpha / eps / Minv samples
+  int hmc_cap = 0;
+  DevBuf<double> d_hmc_z, d_hmc_g, d_hmc_zp, d_hmc_gp, d_hmc_rh;   // M x C each
+  DevBuf<double> d_hmc_minv, d_hmc_wmean, d_hmc_wm2;               // M x C each
+  DevBuf<double> d_hmc_lp, d_hmc_lpp;                              // C each
+  DevBuf<HmcChain> d_hmc_chain;                                    // C
+  DevBuf<int32_t> d_hmc_open;                                      // 1: chains whose step-size search is not finished
+  DevBuf<double> d_outalpha, d_outeps, d_outMinv;                  // (itr+1) x C twice, M x (itr+1) x C; kept between calls like d_outZ
+  int last_hmc_fused = 0, last_hmc_passes = 0, last_hmc_rounds = 0;   // si_hmc_kernel_info
   // si_fit_advi (capi_advi.hip, kernels_advi.hip): the state theta = [mu; omega] of R runs, the optimiser's ring of squared
   // gradients, the step's draws eta with the points made from them, the points' values and gradients, and the device-side traces
   // (grown on demand and kept between calls; every call ends synchronised, so none is in use when it is replaced)
@@ -729,6 +748,27 @@ void launch_mala_propose(hipStream_t st, const double* z, const double* g, doubl
 void launch_mala_accept(hipStream_t st, double* z, double* lp, double* g, double* zprop, const double* lpp, const double* gp,
                         int64_t* nacc, int32_t M, int32_t C, double sigma_z, uint64_t seed, int32_t chain_id0, uint64_t step,
                         double* Z_out, double* lp_out, double* G_out, int64_t itr, bool propose_next);
+// kernels_hmc.hip (the transition, the adaptor update and the step-size search are defined in its header comment): C chains, one
+// workgroup each.  HmcRun: what the three kernels share.
+struct HmcRun {
+  double *z, *lp, *g, *zp, *rh, *minv, *wmean, *wm2;   // state: M x C (lp: C)
+  const double *lpp, *gp;                              // value and gradient at zp
+  HmcChain* chain;                                     // C
+  double *Z_out, *lp_out, *alpha_out, *eps_out, *G_out, *Minv_out;   // M x (itr+1) x C / (itr+1) x C; G_out, Minv_out may be NULL
+  int32_t M, chain_id0;
+  int64_t itr;
+  uint64_t seed;
+  double sigma_z, delta;
+};
+void launch_hmc_init(hipStream_t st, const HmcRun& a, int32_t C);   // zp = sigma_z n_0, the search's state machine at its start
+// one round of the step-size search given (lpp, gp) at the last trial point; open: the chains still searching are counted into it
+void launch_hmc_search(hipStream_t st, const HmcRun& a, int32_t C, int32_t* open);
+void launch_hmc_propose(hipStream_t st, const HmcRun& a, int32_t C, uint64_t step);
+// transition `step` given (lpp, gp) at zp, column `step` of the outputs, the adaptor update the flags name, the proposal of step + 1
+void launch_hmc_accept(hipStream_t st, const HmcRun& a, int32_t C, uint64_t step, bool adapting, bool in_window, bool window_close,
+                       bool last_adapt, bool propose_next);
+// the window schedule of the Stan adaptor for n_adapts steps (host only): first and last step inside a window, the steps that close one
+int32_t hmc_windows(int64_t n_adapts, int64_t* window_start, int64_t* window_end, int64_t* splits, int32_t cap);
 // kernels_advi.hip (the step is defined in its header comment): R runs, one workgroup each.  AdviRun: what both kernels share.
 struct AdviRun {
   double *theta, *ring, *eta, *z;       // 2M x R, W x 2M x R, M x S x R, M x S x R

@@ -26,6 +26,7 @@
 #   * :mala / :hmc / :nuts sampler logic (:117-120, :139-160)                                    -> the reference's own
 #       AdvancedMH / AdvancedHMC calls, unchanged, driven by the two device callbacks above
 #   * :advi (:126-138), with device_loop = true only                                             -> GPU (si_fit_advi)
+#   * :hmc (:139-160), with device_sampler = true only                                           -> GPU (si_sample_hmc)
 #   * output map :125                                                                            -> GPU (si_reconstruct)
 #   * more than one GPU: one Julia process per GPU (Distributed workers), one Ctx each, joined by the RCCL communicator
 #       INSIDE the library (si_comm_*): `init_gpus()`, then `subspace_inference(...; ngpu = 8, nchains = 8)`,
@@ -339,6 +340,40 @@ function mala_kernel_info(ctx::Ctx)
     return fused[] != 0, Int(passes[])
 end
 
+# :139-160 (alg = :hmc) with position, momentum, step size, metric and adaptor state on the device (si_sample_hmc): the one-step HMC,
+# StanHMCAdaptor and find_good_stepsize restated on the library's Philox streams (seed, chain_id + c).  Returns Z (M x (itr+1) x
+# nchains), lp, alpha and eps ((itr+1) x nchains): column 1 is the initial state, alpha[t] / eps[t] the acceptance probability and the
+# step size of transition t - 1; with grad / metric = true also the gradients and the diagonal metric used, each of Z's shape.
+function sample_hmc(ctx::Ctx, itr, σ_z, M; seed = 0, chain_id = 0, nchains = 1, n_adapts = Int(round(itr / 2)), δ = 0.8,
+                    grad = false, metric = false)
+    Z = Array{Float64}(undef, M, itr + 1, nchains); lp = Matrix{Float64}(undef, itr + 1, nchains)
+    alpha = Matrix{Float64}(undef, itr + 1, nchains); eps = Matrix{Float64}(undef, itr + 1, nchains)
+    G = grad ? Array{Float64}(undef, M, itr + 1, nchains) : nothing
+    Minv = metric ? Array{Float64}(undef, M, itr + 1, nchains) : nothing
+    GC.@preserve Z lp alpha eps G Minv check(ctx, ccall((:si_sample_hmc, LIB), Int32,
+        (Ptr{Cvoid}, Int64, Int64, Float64, Float64, UInt64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}),
+        ctx.h, itr, n_adapts, σ_z, δ, seed, chain_id, nchains, Z, lp, alpha, eps, G === nothing ? C_NULL : pointer(G),
+        Minv === nothing ? C_NULL : pointer(Minv)))
+    return (Z, lp, alpha, eps, (grad ? (G,) : ())..., (metric ? (Minv,) : ())...)
+end
+
+# (fused, passes, search_rounds) of the last sample_hmc: the route, gradient passes per transition, rounds of the step-size search
+function hmc_kernel_info(ctx::Ctx)
+    fused = Ref{Int32}(0); passes = Ref{Int32}(0); rounds = Ref{Int32}(0)
+    check(ctx, ccall((:si_hmc_kernel_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}), ctx.h, fused, passes, rounds))
+    return fused[] != 0, Int(passes[]), Int(rounds[])
+end
+
+# the window schedule of sample_hmc's metric adaptation (host only): (window_start, window_end, the steps that close a window)
+function host_hmc_windows(n_adapts)
+    ws = Ref{Int64}(0); we = Ref{Int64}(0)
+    n = ccall((:si_host_hmc_windows, LIB), Int32, (Int64, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Int32), n_adapts, ws, we, C_NULL, 0)
+    splits = Vector{Int64}(undef, n)
+    ccall((:si_host_hmc_windows, LIB), Int32, (Int64, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Int32), n_adapts, ws, we, splits, n)
+    return Int(ws[]), Int(we[]), splits
+end
+
 # :126-138 with the variational state on the device (si_fit_advi): vi(density, ADVI(S, T), q, θ_0) and rand(q, D) restated on the
 # library's Philox streams (seed, chain_id + r), with AdvancedVI 0.1.3's default TruncatedADAGrad(η, τ, window).  Narrow Float64
 # Dense chains queue every step on the stream and synchronise once, at the end.  Returns θ (2M x nruns), Z (M x D x nruns) and
@@ -385,10 +420,14 @@ end
 # device_loop = true (alg = :mala and :advi; non-default): the chain runs with its state on the device (sample_mala) instead of
 # AdvancedMH's host loop; the default keeps the reference's own sampler calls.  alg = :advi exists as the device loop only
 # (fit_advi): without the keyword it throws, as it always has; lp is zeros(itr), as in the reference (:138)
+# device_sampler = true (alg = :hmc; non-default): the one-step HMC runs with its state on the device (sample_hmc) and the initial
+# state is dropped; the default keeps the reference's own AdvancedHMC calls
 function sub_inference(in_model, data, W_swa, P; σ_z = 1.0, σ_m = 1.0, σ_p = 1.0, itr = 100, M = 3, alg = :rwmh,
                        backend = :forwarddiff, device = 0, ctx = Ctx(device), seed = 0, chain_id = 0, include_prior = false,
-                       compute_dtype = :f64, device_loop = false)
+                       compute_dtype = :f64, device_loop = false, device_sampler = false)
     alg == :mh && (alg = :rwmh)                                     # README.md:153-154
+    (device_sampler && alg != :hmc) && throw("device_sampler = true is available for alg = :hmc only" *
+        (alg in (:mala, :advi) ? " (alg = :$alg runs on the device with device_loop = true)" : ""))
     (device_loop && !(alg in (:mala, :advi))) && throw("device_loop = true is available for alg = :mala and :advi only")
     (alg == :advi && !device_loop) && throw("alg = :advi is available with device_loop = true only (fit_advi)")
     alg in (:rwmh, :mala, :hmc, :nuts, :advi) || throw("$alg is not available")       # :162
@@ -417,6 +456,10 @@ function sub_inference(in_model, data, W_swa, P; σ_z = 1.0, σ_m = 1.0, σ_p = 
     if alg == :mala && device_loop
         Z, lp, _ = sample_mala(ctx, itr, σ_z, M; seed = seed, chain_id = chain_id)
         return reconstruct(ctx, Z[:, :, 1], N), lp[:, 1]
+    end
+    if alg == :hmc && device_sampler
+        Z, lp, _, _ = sample_hmc(ctx, itr, σ_z, M; seed = seed, chain_id = chain_id)
+        return reconstruct(ctx, Z[:, 2:end, 1], N), lp[2:end, 1]
     end
     if alg == :advi
         _, Z, _ = fit_advi(ctx, itr, σ_z, M; seed = seed, chain_id = chain_id)   # :133-137 ADVI(10, itr), rand(q, itr)

@@ -19,6 +19,11 @@ vendored.  What is restated [upstream, unverifiable offline]:
     threshold ΔH > 1000 (the published algorithm of Betancourt 2017 / Stan that AdvancedHMC implements); same step-size
     search and adaptor as above.
 The random stream is NumPy's PCG64 seeded by the caller (the reference uses Julia's global MersenneTwister).
+
+`mala` and `hmc` (with `StanAdaptor` and `find_good_stepsize`) are also THE DEFINITION of the device samplers si_sample_mala and
+si_sample_hmc (csrc/kernels_mala.hip, csrc/kernels_hmc.hip), which run the same statements on the library's Philox streams with
+the chain state on the device; tests/mala_audit.py and tests/hmc_audit.py hold the device's traces to these functions transition
+by transition.  A change here changes what those kernels must compute.  `nuts` exists as this host loop only.
 """
 import math
 

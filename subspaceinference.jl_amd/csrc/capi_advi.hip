@@ -2,16 +2,8 @@
 // kernels_advi.hip (the contract: include/subspace_hip.h); this file queues it.  Host-side orchestration only; no CPU fallback
 // anywhere in this file.
 //
-// Two routes, one definition, one audit (tests/advi_audit.py):
-//   fused   chains of si_logdensity_grad_batch's fused class: per step the R S points go through vgrad_pass (launch_reconstruct,
-//           launch_chain_vgrad, launch_chain_vgrad_reduce) once per pass of vg_cap points, outputs left on the device, then ONE
-//           advi_update_kernel launch, which also forms the next step's points: 3 passes + 1 launches per step.  The state never
-//           leaves the device, nothing is copied and nothing synchronises until the tail.  A launch-queued loop: no persistent
-//           kernel, no grid barrier, nothing that can spin.
-//   other   every other chain (Conv / MaxPool / flatten, SI_F32, the four later activations, wide layers): the same two kernels,
-//           but the points come down to the host, their values and gradients are computed column by column by
-//           si_logdensity_grad's own path and go back up before the update kernel.  SLOW AND SYNCHRONISING: one round trip per
-//           point and step; it exists so that every chain the gradient covers has the device fit's definition.
+// One definition, one audit (tests/advi_audit.py), on the two routes of the stacked evaluator (StackedVgrad, capi_infer.hip): per
+// step one evaluation at the R S points, then ONE advi_update_kernel launch, which also forms the next step's points.
 #include "capi_common.h"
 
 using namespace si;
@@ -51,17 +43,8 @@ int32_t si_fit_advi(si_ctx* ctx, int64_t max_iters, int32_t samples_per_step, do
   a.pts_out = points_out ? ctx->d_advi_pts.get() : nullptr;
   a.M = M, a.S = S, a.W = W, a.chain_id0 = chain_id0, a.T = T, a.seed = seed;
   const int32_t C = R * S;   // the points of one step, run by run
-  int64_t G = 0, fit = 0;
-  const int nb = vgrad_route(ctx, &G, &fit);
-  const bool fused = fit >= 1;
-  if (fused && (rc = vgrad_ensure(ctx, who, (int)std::min<int64_t>(fit, C), G)) != SI_OK) return rc;
-  const int passes = fused ? (C + ctx->vg_cap - 1) / ctx->vg_cap : C;
-  std::vector<double> hz, hlp, hg;   // the other route's host images of the points, their values and gradients
-  if (!fused) {
-    hz.resize(pts);
-    hlp.resize((size_t)C);
-    hg.resize(pts);
-  }
+  StackedVgrad vg;
+  if ((rc = vg.open(ctx, who, C)) != SI_OK) return rc;
   hipError_t e = hipSuccess;
   {
     ProfScope ps(ctx, SI_K_RWMH, 0, 0);
@@ -69,20 +52,8 @@ int32_t si_fit_advi(si_ctx* ctx, int64_t max_iters, int32_t samples_per_step, do
     e = hipGetLastError();
   }
   for (int64_t t = 0; t < T && e == hipSuccess && rc == SI_OK; ++t) {
-    if (fused) {
-      for (int32_t p0 = 0; p0 < C; p0 += ctx->vg_cap)
-        vgrad_pass(ctx, nb, G, ctx->d_advi_z + m * p0, std::min<int32_t>(ctx->vg_cap, C - p0), ctx->d_advi_lp + p0, ctx->d_advi_g + m * p0);
-      e = hipGetLastError();
-    } else {
-      e = hipMemcpyAsync(hz.data(), ctx->d_advi_z, pts * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (also: the uploads of step t - 1 have left hlp / hg)
-      for (int32_t c = 0; c < C && e == hipSuccess && rc == SI_OK; ++c)
-        rc = logdensity_grad_point(ctx, hz.data() + m * c, hlp.data() + c, hg.data() + m * c);
-      if (rc != SI_OK) break;
-      if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_advi_lp, hlp.data(), hlp.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_advi_g, hg.data(), hg.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e != hipSuccess) break;
+    vg.eval(ctx->d_advi_z, ctx->d_advi_lp, ctx->d_advi_g, e, rc);
+    if (e != hipSuccess || rc != SI_OK) break;
     ProfScope ps(ctx, SI_K_RWMH, 0, 0);
     launch_advi_update(ctx->stream, a, R, ctx->d_advi_lp, ctx->d_advi_g, eta, tau, t, d_elbo, t + 1 < T);
     e = hipGetLastError();
@@ -92,22 +63,15 @@ int32_t si_fit_advi(si_ctx* ctx, int64_t max_iters, int32_t samples_per_step, do
     launch_advi_draw(ctx->stream, a, R, sigma_z, false, true, ctx->d_outZ, D);
     e = hipGetLastError();
   }
-  // the common tail (the pattern of si_sample_mala): the downloads, ONE synchronisation, the first error reported
-  const bool ok = e == hipSuccess && rc == SI_OK;
-  auto down = [&](double* dst, const double* src, size_t n) {
-    if (ok && e == hipSuccess && dst) e = hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  };
-  down(theta_out, ctx->d_advi_theta, 2 * m * R);
-  if (D > 0) down(Z_out, ctx->d_outZ, z_elems);
-  down(elbo_out, d_elbo, (size_t)T * R);
-  down(theta_trace_out, a.trace_out, trace_elems);
-  down(points_out, a.pts_out, ptsout_elems);
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  const size_t f64 = sizeof(double);
+  rc = finish_downloads(ctx, who, e, rc, {{theta_out, ctx->d_advi_theta, 2 * m * R * f64},
+                                          {D > 0 ? Z_out : nullptr, ctx->d_outZ, z_elems * f64},
+                                          {elbo_out, d_elbo, (size_t)T * R * f64},
+                                          {theta_trace_out, a.trace_out, trace_elems * f64},
+                                          {points_out, a.pts_out, ptsout_elems * f64}});
   if (rc != SI_OK) return rc;
-  if (e != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-  if (e2 != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e2));
-  ctx->last_advi_fused = fused ? 1 : 0;
-  ctx->last_advi_passes = passes;
+  ctx->last_advi_fused = vg.fused ? 1 : 0;
+  ctx->last_advi_passes = vg.passes;
   return SI_OK;
 }
 

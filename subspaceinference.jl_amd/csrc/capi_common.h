@@ -1,12 +1,16 @@
-// Declarations shared by the translation units of the C ABI (capi.hip: context + construction; capi_infer.hip: inference set-up,
-// density, gradient, predictive forward; capi_sample.hip: the RWMH samplers and the output map; capi_mala.hip: the MALA sampler; capi_hmc.hip: the HMC sampler; capi_advi.hip: the ADVI fit).  Nothing here is part of the
-// public interface (include/subspace_hip.h).  Buffers are owned by the types of dev_buf.h (through si_internal.h): no file of
-// the C ABI calls hipMalloc / hipFree / hipHostMalloc / hipHostFree or creates an event by hand.
+// Declarations shared by the translation units of the C ABI:
+//   capi.hip         context + construction
+//   capi_infer.hip   inference set-up, density, gradient, predictive forward, the stacked value-and-gradient evaluator
+//   capi_sample.hip  the RWMH samplers and the output map
+//   capi_mala.hip / capi_hmc.hip / capi_advi.hip   the MALA sampler / the HMC sampler / the ADVI fit
+// Nothing here is part of the public interface (include/subspace_hip.h).  Buffers are owned by the types of dev_buf.h (through
+// si_internal.h): no file of the C ABI calls hipMalloc / hipFree / hipHostMalloc / hipHostFree or creates an event by hand.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -34,11 +38,32 @@ int32_t eval_density_all(si_ctx* ctx, int C);
 double mvnormal_c0(double d, double sigma);
 double prior_c0(const si_ctx* ctx);
 void fused_fill_program(const si_ctx* ctx, si::ChainFusedPlan& fp);
-// the gradient entry points' state rules; value and gradient at one point through the per-layer launches (synchronises); the fused
-// route of si_logdensity_grad_batch: its class / workgroups per point / points per pass, its workspace, one queued pass
-int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok);
-int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* grad_out);
-int vgrad_route(si_ctx* ctx, int64_t* G_out, int64_t* fit_out);
-int32_t vgrad_ensure(si_ctx* ctx, const char* who, int cap, int64_t G);
-void vgrad_pass(si_ctx* ctx, int nb, int64_t G, const double* z_dev, int n, double* lp_dev, double* gz_dev);
+int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok);   // the gradient entry points' state rules and error texts
 }
+
+namespace si {
+
+// Value and gradient at C stacked points that live on the device, for the gradient-driven entry points (si_sample_mala,
+// si_sample_hmc, si_fit_advi); defined in capi_infer.hip, where the two routes are described.
+struct StackedVgrad {
+  bool fused = false;   // the route of this call
+  int passes = 0;       // per evaluation: passes of launches (fused) / single-point evaluations (other)
+  // once per call, after the caller's own allocations: the route, then the fused workspace or the other route's host images
+  int32_t open(si_ctx* ctx, const char* who, int32_t C);
+  // lp_dev[C], g_dev[M x C] at z_dev[M x C].  e and rc are the call's own, both fine on entry; it stops at the first failure of either
+  void eval(const double* z_dev, double* lp_dev, double* g_dev, hipError_t& e, int32_t& rc);
+
+ private:
+  si_ctx* ctx = nullptr;
+  int32_t C = 0;
+  int nb = 0;
+  int64_t G = 0;
+  std::vector<double> hz, hlp, hg;   // the other route's host images of the points, their values and gradients
+};
+
+// The tail of such a call: the downloads (queued only while everything so far succeeded; a null dst is an output not asked
+// for), ONE synchronisation -- also after a failure -- and the first error reported: rc, then e, then the synchronisation's.
+struct Download { void* dst; const void* src; size_t bytes; };
+int32_t finish_downloads(si_ctx* ctx, const char* who, hipError_t e, int32_t rc, std::initializer_list<Download> downs);
+
+}  // namespace si

@@ -2,13 +2,9 @@
 // adaptor update and the step-size search are defined once, in kernels_hmc.hip; this file queues them.  Host-side orchestration
 // only; no CPU fallback anywhere in this file.
 //
-// Two routes, one definition, one audit (tests/hmc_audit.py), as si_sample_mala's:
-//   fused   chains of si_logdensity_grad_batch's fused class: per transition the gradient's launches (once per pass of vg_cap chains,
-//           outputs left on the device) and hmc_accept_kernel are queued on the stream; position, momentum, step size, metric and
-//           adaptor state never leave the device.  A launch-queued loop: no persistent kernel, no grid barrier, nothing that can spin.
-//   other   every other chain (Conv / MaxPool / flatten, SI_F32, the four later activations, wide layers): the same kernels, but the
-//           proposals come down to the host and their values and gradients go back up column by column through si_logdensity_grad's
-//           own path.  SLOW AND SYNCHRONISING: one round trip per chain and transition.
+// One definition, one audit (tests/hmc_audit.py), on the two routes of the stacked evaluator (StackedVgrad, capi_infer.hip): per
+// transition one evaluation at the proposals, then hmc_accept_kernel; position, momentum, step size, metric and adaptor state
+// never leave the device.
 // THE PREAMBLE SYNCHRONISES on both routes: the step-size search is data dependent, so after every round (search kernel, value and
 // gradient at the trial points) the host reads back ONE 4-byte count of the chains still searching.  It is a one-off before the
 // first transition, bounded by the restatement's own limits (1 + 100 + 100 evaluations after the one at z_0), and the only place
@@ -91,35 +87,9 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
   HmcRun a{ctx->d_hmc_z, ctx->d_hmc_lp, ctx->d_hmc_g, ctx->d_hmc_zp, ctx->d_hmc_rh, ctx->d_hmc_minv, ctx->d_hmc_wmean, ctx->d_hmc_wm2,
            ctx->d_hmc_lpp, ctx->d_hmc_gp, ctx->d_hmc_chain, ctx->d_outZ, ctx->d_outlp, ctx->d_outalpha, ctx->d_outeps,
            G_out ? ctx->d_outG.get() : nullptr, Minv_out ? ctx->d_outMinv.get() : nullptr, M, chain_id0, itr, seed, sigma_z, delta};
-  int64_t G = 0, fit = 0;
-  const int nb = vgrad_route(ctx, &G, &fit);
-  const bool fused = fit >= 1;
-  if (fused && (rc = vgrad_ensure(ctx, who, (int)std::min<int64_t>(fit, C), G)) != SI_OK) return rc;
-  const int passes = fused ? (C + ctx->vg_cap - 1) / ctx->vg_cap : C;
-  std::vector<double> hz, hlp, hg;   // the other route's host images of the proposals, their values and gradients
-  if (!fused) {
-    hz.resize((size_t)M * C);
-    hlp.resize((size_t)C);
-    hg.resize((size_t)M * C);
-  }
+  StackedVgrad vg;
+  if ((rc = vg.open(ctx, who, C)) != SI_OK) return rc;
   hipError_t e = hipSuccess;
-  // value and gradient at d_hmc_zp into d_hmc_lpp / d_hmc_gp, on the call's route
-  auto value_grad = [&]() {
-    if (fused) {
-      for (int32_t p0 = 0; p0 < C; p0 += ctx->vg_cap)
-        vgrad_pass(ctx, nb, G, ctx->d_hmc_zp + (size_t)M * p0, std::min<int32_t>(ctx->vg_cap, C - p0), ctx->d_hmc_lpp + p0,
-                   ctx->d_hmc_gp + (size_t)M * p0);
-      e = hipGetLastError();
-      return;
-    }
-    e = hipMemcpyAsync(hz.data(), ctx->d_hmc_zp, hz.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (also: the uploads of the evaluation before have left hlp / hg)
-    for (int32_t c = 0; c < C && e == hipSuccess && rc == SI_OK; ++c)
-      rc = logdensity_grad_point(ctx, hz.data() + (size_t)M * c, hlp.data() + c, hg.data() + (size_t)M * c);
-    if (rc != SI_OK) return;
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_hmc_lpp, hlp.data(), hlp.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_hmc_gp, hg.data(), hg.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-  };
   {
     ProfScope ps(ctx, SI_K_RWMH, 0, 0);
     launch_hmc_init(ctx->stream, a, C);
@@ -130,7 +100,7 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
   int rounds = 0;
   int32_t open = 1;
   while (open > 0 && e == hipSuccess && rc == SI_OK && rounds < 2 * 100 + 3) {
-    value_grad();
+    vg.eval(ctx->d_hmc_zp, ctx->d_hmc_lpp, ctx->d_hmc_gp, e, rc);
     if (e != hipSuccess || rc != SI_OK) break;
     e = hipMemsetAsync(ctx->d_hmc_open, 0, sizeof(int32_t), ctx->stream);
     if (e != hipSuccess) break;
@@ -151,7 +121,7 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
   }
   size_t next_split = 0;
   for (int64_t t = 1; t <= itr && e == hipSuccess && rc == SI_OK; ++t) {
-    value_grad();
+    vg.eval(ctx->d_hmc_zp, ctx->d_hmc_lpp, ctx->d_hmc_gp, e, rc);
     if (e != hipSuccess || rc != SI_OK) break;
     const bool adapting = t <= n_adapts, in_window = adapting && ws <= t && t <= we;
     while (next_split < (size_t)nsplits && splits[next_split] < t) ++next_split;
@@ -160,23 +130,12 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
     launch_hmc_accept(ctx->stream, a, C, (uint64_t)t, adapting, in_window, window_close, t == n_adapts, t < itr);
     e = hipGetLastError();
   }
-  // the common tail (the pattern of si_sample_mala): the downloads, ONE synchronisation, the first error reported
-  const bool ok = e == hipSuccess && rc == SI_OK;
-  auto down = [&](double* dst, const double* src, size_t n) {
-    if (ok && e == hipSuccess && dst) e = hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  };
-  down(Z_out, ctx->d_outZ, zelems);
-  down(lp_out, ctx->d_outlp, selems);
-  down(alpha_out, ctx->d_outalpha, selems);
-  down(eps_out, ctx->d_outeps, selems);
-  down(G_out, a.G_out, zelems);
-  down(Minv_out, a.Minv_out, zelems);
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  const size_t zbytes = zelems * sizeof(double), sbytes = selems * sizeof(double);
+  rc = finish_downloads(ctx, who, e, rc, {{Z_out, ctx->d_outZ, zbytes}, {lp_out, ctx->d_outlp, sbytes}, {alpha_out, ctx->d_outalpha, sbytes},
+                                          {eps_out, ctx->d_outeps, sbytes}, {G_out, a.G_out, zbytes}, {Minv_out, a.Minv_out, zbytes}});
   if (rc != SI_OK) return rc;
-  if (e != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-  if (e2 != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e2));
-  ctx->last_hmc_fused = fused ? 1 : 0;
-  ctx->last_hmc_passes = passes;
+  ctx->last_hmc_fused = vg.fused ? 1 : 0;
+  ctx->last_hmc_passes = vg.passes;
   ctx->last_hmc_rounds = rounds;
   return SI_OK;
 }

@@ -515,10 +515,10 @@ static int32_t ensure_grad(si_ctx* ctx) {
   return SI_OK;
 }
 
-// value and gradient at ONE point through the per-layer launches: the body of si_logdensity_grad, and what
-// si_logdensity_grad_batch and si_sample_mala walk column by column for every chain outside the fused class (checked and bound
+// value and gradient at ONE point through the per-layer launches (synchronises): the body of si_logdensity_grad, and what
+// si_logdensity_grad_batch and StackedVgrad walk column by column for every chain outside the fused class (checked and bound
 // by the caller)
-int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* grad_out) {
+static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* grad_out) {
   int32_t rc = ensure_chains(ctx, 1);
   if (rc != SI_OK) return rc;
   if ((rc = ensure_grad(ctx)) != SI_OK) return rc;
@@ -621,9 +621,10 @@ static int vgrad_class(si_ctx* ctx) {
   return ctx->vg_class;
 }
 
-// The fused route as si_logdensity_grad_batch and si_sample_mala (capi_mala.hip) share it.  vgrad_route: the batch-tile class of
-// the chain set up (0: not of the fused class), the workgroups per point and the points one pass of launches may carry.
-int vgrad_route(si_ctx* ctx, int64_t* G_out, int64_t* fit_out) {
+// The fused route's pieces, for si_logdensity_grad_batch (points from the host, staged per pass) and StackedVgrad (points on the
+// device) below.  vgrad_route: the batch-tile class of the chain set up (0: not of the fused class), the workgroups per point and
+// the points one pass of launches may carry.
+static int vgrad_route(si_ctx* ctx, int64_t* G_out, int64_t* fit_out) {
   const int64_t B = ctx->B, ldw = pad_ld(ctx->iN);
   const int nb = vgrad_class(ctx);
   const int64_t G = nb > 0 ? (B + 16 * nb - 1) / (16 * nb) : 0;
@@ -636,7 +637,7 @@ int vgrad_route(si_ctx* ctx, int64_t* G_out, int64_t* fit_out) {
 }
 
 // its workspace for `cap` points per pass
-int32_t vgrad_ensure(si_ctx* ctx, const char* who, int cap, int64_t G) {
+static int32_t vgrad_ensure(si_ctx* ctx, const char* who, int cap, int64_t G) {
   if (ctx->vg_cap >= cap) return SI_OK;
   const int64_t ldw = pad_ld(ctx->iN);
   const int32_t M = ctx->iM;
@@ -656,7 +657,7 @@ int32_t vgrad_ensure(si_ctx* ctx, const char* who, int cap, int64_t G) {
 
 // one pass of launches: value and gradient at the n <= vg_cap points z_dev[:, 0 .. n) (device) into lp_dev[n] / gz_dev[M x n]
 // (device).  Queued on the stream; nothing is copied, nothing synchronises.
-void vgrad_pass(si_ctx* ctx, int nb, int64_t G, const double* z_dev, int n, double* lp_dev, double* gz_dev) {
+static void vgrad_pass(si_ctx* ctx, int nb, int64_t G, const double* z_dev, int n, double* lp_dev, double* gz_dev) {
   const int64_t N = ctx->iN, B = ctx->B, ldw = pad_ld(N);
   const int32_t M = ctx->iM;
   ChainVgradPlan vp;
@@ -674,6 +675,69 @@ void vgrad_pass(si_ctx* ctx, int nb, int64_t G, const double* z_dev, int n, doub
                               ctx->sigma_p, prior_c0(ctx), c0, s2, ctx->d_vg_gw, lp_dev, gz_dev, n);
   }
 }
+
+}  // extern "C"
+
+namespace si {
+
+// ---- value and gradient at C stacked points that already live on the device (si_sample_mala, si_sample_hmc, si_fit_advi) ---------
+// Two routes, chosen by the chain set up, never by the caller:
+//   fused   chains of the class above: per evaluation launch_reconstruct, launch_chain_vgrad and launch_chain_vgrad_reduce are
+//           queued once per pass of vg_cap points, outputs left on the device.  Nothing is copied and nothing synchronises, so a
+//           caller that queues its own kernel between evaluations keeps its state on the device until its tail.  A launch-queued
+//           loop: no persistent kernel, no grid barrier, nothing that can spin.
+//   other   every other chain (Conv / MaxPool / flatten, SI_F32, the four later activations, wide layers): the points come down
+//           to the host, their values and gradients are computed column by column by si_logdensity_grad's own path and go back up.
+//           SLOW AND SYNCHRONISING: one round trip per point and evaluation; it exists so that every chain the gradient covers
+//           has the device samplers' definitions.
+int32_t StackedVgrad::open(si_ctx* c, const char* who, int32_t npoints) {
+  ctx = c, C = npoints;
+  int64_t fit = 0;
+  nb = vgrad_route(ctx, &G, &fit);
+  fused = fit >= 1;
+  if (fused) {
+    const int32_t rc = vgrad_ensure(ctx, who, (int)std::min<int64_t>(fit, C), G);
+    if (rc != SI_OK) return rc;
+  } else {
+    hz.resize((size_t)ctx->iM * C);
+    hlp.resize((size_t)C);
+    hg.resize((size_t)ctx->iM * C);
+  }
+  passes = fused ? (C + ctx->vg_cap - 1) / ctx->vg_cap : C;
+  return SI_OK;
+}
+
+void StackedVgrad::eval(const double* z_dev, double* lp_dev, double* g_dev, hipError_t& e, int32_t& rc) {
+  const size_t M = (size_t)ctx->iM;
+  if (fused) {
+    for (int32_t p0 = 0; p0 < C; p0 += ctx->vg_cap)
+      vgrad_pass(ctx, nb, G, z_dev + M * p0, std::min<int32_t>(ctx->vg_cap, C - p0), lp_dev + p0, g_dev + M * p0);
+    e = hipGetLastError();
+    return;
+  }
+  e = hipMemcpyAsync(hz.data(), z_dev, hz.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (also: the uploads of the evaluation before have left hlp / hg)
+  for (int32_t c = 0; c < C && e == hipSuccess && rc == SI_OK; ++c)
+    rc = logdensity_grad_point(ctx, hz.data() + M * c, hlp.data() + c, hg.data() + M * c);
+  if (rc != SI_OK) return;
+  // (hlp / hg outlive these uploads: the caller's tail synchronises before the evaluator goes)
+  if (e == hipSuccess) e = hipMemcpyAsync(lp_dev, hlp.data(), hlp.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(g_dev, hg.data(), hg.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+}
+
+int32_t finish_downloads(si_ctx* ctx, const char* who, hipError_t e, int32_t rc, std::initializer_list<Download> downs) {
+  for (const Download& d : downs)
+    if (e == hipSuccess && rc == SI_OK && d.dst) e = hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  if (rc != SI_OK) return rc;
+  if (e != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  if (e2 != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e2));
+  return SI_OK;
+}
+
+}  // namespace si
+
+extern "C" {
 
 int32_t si_logdensity_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double* lp_out, double* grad_out) {
   CHECK_CTX(ctx);

@@ -302,6 +302,40 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
 /* the last si_sample_hmc call: fused_out = 1 when it took the device-resident route, passes_out = gradient passes per transition
  * (as si_mala_kernel_info), search_rounds_out = rounds of the step-size search, the one at z_0 included                           */
 int32_t si_hmc_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out, int32_t* search_rounds_out);
+/* :139-160  NUTS: NUTS{MultinomialTS, GeneralisedNoUTurn}(Leapfrog(eps)) under the same StanHMCAdaptor after the same
+ * find_good_stepsize (AdvancedHMC 0.2.27) [upstream, unverifiable offline], with the trajectory tree, step size, metric and adaptor
+ * state on the device.  THE DEFINITION is samplers.nuts_iter (the leaf-by-leaf restatement of samplers.nuts) on the Philox streams:
+ * purposes 0, 5, 6 and column 0, the search and the adaptor exactly as si_sample_hmc; purpose 7 at step t, block j = the doubling at
+ * depth j: direction +1 iff u53(x1, x0) < 0.5, progressive pick with u53(x3, x2); purpose 8 at step t, block 16 leaf + level = the
+ * pick of the merge at `level` (1 ..) after leaf `leaf` (the running leaf count of the transition, 1 ..), u53(x1, x0).
+ *     t = 1 .. itr:  r0 = n_t / sqrt(Minv);  h0 = lp - sum((Minv r0) r0) / 2;  the tree = the state, logw = 0, rho = r0
+ *              doubling j = 0 .. max_depth - 1 in direction v: 2^j leapfrog steps of size v eps from the tree's end on that side; a
+ *              leaf has dh = (lp1 - K1, or -inf if that is not finite) - h0, weight exp(dh), alpha = min(1, exp(dh)), and is divergent
+ *              iff -dh > max_dh; after leaf k of the doubling the top two sub-trees merge once per trailing zero bit of k:
+ *              logw = logaddexp, proposal = the later one's iff log u < logw_later - logw, rho and alpha and n add, and the merged
+ *              sub-tree stops iff rho . (Minv r) <= 0 at either of its ends.  A divergent leaf or a stopped sub-tree ends the
+ *              transition (its leaves still count into alpha); else the candidate becomes the doubling's proposal iff
+ *              log u < logw_doubling - logw_tree, the tree takes the doubling, and the transition ends on the whole tree's U-turn
+ *              or after doubling max_depth - 1.  state = candidate;  alpha[t] = sum of the leaves' alpha / max(1, leaves counted)
+ *              the adaptor's update with (z, alpha[t]), as si_sample_hmc
+ * Outputs as si_sample_hmc (column 0 = the initial state), and per transition depth_out = doublings started, nleaf_out = leapfrog
+ * steps, sel_out = the leaf (1-based within the transition) that became the state, 0 = the previous state was kept (column 0: 0).
+ * leaf_out (the audit's trace): for chain c the call's leaves in build order, each as (z[M], r[M], lp, g[M]); logging stops
+ * silently at leaf_cap, the counts go on; slots no leaf reaches are NaN (all bits set).  A chain's bits depend on M alone, as si_sample_hmc's.
+ * SI_ERR_INVALID for what si_sample_hmc refuses, and unless 1 <= max_depth <= 10, max_dh > 0 (a NaN is refused) and leaf_cap >= 1
+ * when leaf_out is given.  EVERY ROUND SYNCHRONISES on both routes: one evaluation at the chains' pending points, one kernel, one
+ * 4-byte read-back of the chains still building.  Chains advance in lock-step within a transition (a finished chain waits); a
+ * transition takes at most 2^max_depth - 1 rounds (SI_ERR_STATE beyond).                                                           */
+int32_t si_sample_nuts(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z, double delta, int32_t max_depth, double max_dh,
+                       uint64_t seed, int32_t chain_id0, int32_t nchains, double* Z_out /* M x (itr+1) x C */,
+                       double* lp_out /* (itr+1) x C */, double* alpha_out /* (itr+1) x C */, double* eps_out /* (itr+1) x C */,
+                       int32_t* depth_out /* (itr+1) x C or NULL */, int32_t* nleaf_out /* likewise */, int32_t* sel_out /* likewise */,
+                       double* G_out /* like Z_out, or NULL */, double* Minv_out /* like Z_out, or NULL */,
+                       double* leaf_out /* (3M+1) x leaf_cap x C or NULL */, int64_t leaf_cap);
+/* the last si_sample_nuts call: route, passes and search rounds as si_hmc_kernel_info; rounds_out = rounds of all transitions,
+ * leaves_out = sum of nleaf over chains and transitions (rounds x nchains - leaves = the lock-step waste)                        */
+int32_t si_nuts_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out, int32_t* search_rounds_out, int64_t* rounds_out,
+                            int64_t* leaves_out);
 /* :126-138  ADVI with its state on the device.  Restates
  *     AdvancedVI.vi(density, ADVI(S, T), theta -> TuringDiagMvNormal(theta[1:M], exp.(theta[M+1:2M])), rand(MvNormal(zeros(2M), sigma_z)))
  * followed by rand(q, D) (AdvancedVI 0.1.3), with that version's default optimiser TruncatedADAGrad(eta = 0.1, tau = 1.0,

@@ -101,6 +101,11 @@ SIGNATURES = {
     "si_sample_hmc": (c_int32, [c_void_p, c_int64, c_int64, c_double, c_double, c_uint64, c_int32, c_int32, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "si_hmc_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "si_sample_nuts": (c_int32, [c_void_p, c_int64, c_int64, c_double, c_double, c_int32, c_double, c_uint64, c_int32, c_int32,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int64]),
+    "si_nuts_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int64),
+                                      POINTER(c_int64)]),
     "si_fit_advi": (c_int32, [c_void_p, c_int64, c_int32, c_double, c_double, c_double, c_int32, c_uint64, c_int32, c_int32, c_int64,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "si_advi_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
@@ -697,6 +702,38 @@ class Context:
         f, p, r = c_int32(0), c_int32(0), c_int32(0)
         self._check(self.lib.si_hmc_kernel_info(self.h, byref(f), byref(p), byref(r)))
         return int(f.value), int(p.value), int(r.value)
+
+    def sample_nuts(self, itr, sigma_z, seed, chain_id0=0, nchains=1, n_adapts=None, delta=0.8, max_depth=10, max_dh=1000.0,
+                    tree=True, grad=False, metric=False, leaf_cap=0):
+        """si_sample_nuts: the reference's NUTS (multinomial sampling, generalised no-U-turn criterion) under the Stan adaptor with
+        the trajectory tree, step size, metric and adaptor state on the device, on the library's Philox streams -- the transition
+        of `samplers.nuts_iter`.  n_adapts=None is the reference's Int(round(itr / 2)).  Returns (z, lp, alpha, eps) with itr + 1
+        columns as sample_hmc (alpha[t] = the mean acceptance over the leaves of transition t), then with tree=True (depth, nleaf,
+        sel) -- doublings started, leapfrog steps, the leaf (1-based) that became the state or 0 -- then G (grad=True), Minv
+        (metric=True) and, with leaf_cap > 0, the leaf log [3M+1, leaf_cap, C]: chain c's leaves in build order as (z, r, lp, g),
+        NaN where nothing was logged."""
+        itr, c = int(itr), int(nchains)
+        na = int(round(itr / 2)) if n_adapts is None else int(n_adapts)
+        cols = max(itr, 0) + 1
+        z = np.empty((self._m, cols, max(c, 0)), dtype=np.float64, order="F")
+        lp, alpha, eps = (np.empty((cols, max(c, 0)), dtype=np.float64, order="F") for _ in range(3))
+        depth, nleaf, sel = (np.zeros((cols, max(c, 0)), dtype=np.int32, order="F") if tree else None for _ in range(3))
+        g = np.empty_like(z, order="F") if grad else None
+        mi = np.empty_like(z, order="F") if metric else None
+        leaf = np.full((3 * self._m + 1, int(leaf_cap), max(c, 0)), np.nan, dtype=np.float64, order="F") if leaf_cap else None
+        self._check(self.lib.si_sample_nuts(self.h, itr, na, float(sigma_z), float(delta), int(max_depth), float(max_dh), int(seed),
+                                            int(chain_id0), c, _ptr(z), _ptr(lp), _ptr(alpha), _ptr(eps), _ptr(depth), _ptr(nleaf),
+                                            _ptr(sel), _ptr(g), _ptr(mi), _ptr(leaf), int(leaf_cap)))
+        return ((z, lp, alpha, eps) + ((depth, nleaf, sel) if tree else ()) + ((g,) if grad else ()) + ((mi,) if metric else ())
+                + ((leaf,) if leaf_cap else ()))
+
+    def nuts_kernel_info(self):
+        """(fused, passes, search_rounds, rounds, leaves) of the last sample_nuts: route and passes as hmc_kernel_info, the rounds
+        of all transitions and the leapfrog steps of all chains -- rounds * nchains - leaves is the lock-step waste"""
+        f, p, r = c_int32(0), c_int32(0), c_int32(0)
+        n, lv = c_int64(0), c_int64(0)
+        self._check(self.lib.si_nuts_kernel_info(self.h, byref(f), byref(p), byref(r), byref(n), byref(lv)))
+        return int(f.value), int(p.value), int(r.value), int(n.value), int(lv.value)
 
     def fit_advi(self, max_iters, sigma_z, seed, samples_per_step=10, eta=0.1, tau=1.0, window=100, chain_id0=0, nruns=1,
                  ndraws=None, trace=False):

@@ -139,7 +139,7 @@ def subspace_construction(model, cost, data, opt, T=10, c=1, M=3, print_freq=1, 
 def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=100, M=3, alg="rwmh",
                   backend="forwarddiff", *, sigma_z=None, sigma_m=None, sigma_p=None, device=0, ctx=None,
                   seed=0, chain_id=0, return_z=False, nchains=1, include_prior=False, compute_dtype="f64",
-                  device_loop=False, device_sampler=False):
+                  device_loop=False, device_sampler=False, device_nuts=False):
     """src/space_inference.jl:82-164 for a Chain model and alg = :rwmh.
 
     `density(z)` (:90-95: W_swa + P*z -> model_re -> forward over the FULL data -> Gaussian log-likelihood,
@@ -168,6 +168,11 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
     and adaptor state on the device (si_sample_hmc): the transition, adaptor and step-size search of `samplers.hmc` on the Philox
     streams (seed, chain_id + c), n_adapts = round(itr / 2); the initial state is dropped, so itr samples and lp come back like
     the host path's.  It allows nchains > 1, with :mala's shapes.  The default :hmc stays `samplers.hmc` on PCG64, bit for bit.
+
+    `device_nuts=True` (alg = :nuts; non-default) runs NUTS with its trajectory tree, step size, metric and adaptor state on the
+    device (si_sample_nuts; `Context.sample_nuts` / `Context.nuts_kernel_info`): the transition of `samplers.nuts_iter` on the
+    Philox streams (seed, chain_id + c), n_adapts = round(itr / 2), max_depth = 10, max_dh = 1000; the initial state is dropped.
+    It allows nchains > 1, with :hmc's shapes.  The default :nuts stays `samplers.nuts` on PCG64, bit for bit.
     """
     σ_z = σ_z if sigma_z is None else sigma_z
     σ_m = σ_m if sigma_m is None else sigma_m
@@ -201,10 +206,14 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
         if device_sampler and a != "hmc":
             raise SubspaceError("device_sampler=True is available for alg = :hmc only" + (
                 " (alg = :%s runs on the device with device_loop=True)" % a if a in ("mala", "advi") else ""))
+        if device_nuts and a != "nuts":
+            raise SubspaceError("device_nuts=True is available for alg = :nuts only")
         if device_loop and a not in ("mala", "advi"):
             raise SubspaceError("device_loop=True is available for alg = :mala and :advi only")
-        if nchains != 1 and a not in _RWMH_ALGS and a != "mala" and not (a == "hmc" and device_sampler):
-            raise SubspaceError("nchains > 1 is available for alg = :rwmh / :mh / :mala (and :hmc with device_sampler=True) only")
+        if nchains != 1 and a not in _RWMH_ALGS and a != "mala" and not (a == "hmc" and device_sampler) and not (
+                a == "nuts" and device_nuts):
+            raise SubspaceError("nchains > 1 is available for alg = :rwmh / :mh / :mala (and :hmc with device_sampler=True, "
+                                ":nuts with device_nuts=True) only")
         if a in _RWMH_ALGS:
             if return_z:
                 z, lp, _ = ctx.sample_rwmh(itr, σ_z, seed, chain_id, nchains)
@@ -222,8 +231,10 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
                 # :126-138: vi(density, ADVI(10, itr), q, theta_0), then rand(q, itr); the reference returns zeros(itr) for lp
                 _, z, _ = ctx.fit_advi(itr, σ_z, seed, chain_id0=chain_id)
                 z, lp = z[:, :, 0], np.zeros(itr)
-            elif (a == "mala" and device_loop) or (a == "hmc" and device_sampler):
-                if a == "hmc":
+            elif (a == "mala" and device_loop) or (a == "hmc" and device_sampler) or (a == "nuts" and device_nuts):
+                if a == "nuts":
+                    z, lp = (np.asfortranarray(v[..., 1:, :]) for v in ctx.sample_nuts(itr, σ_z, seed, chain_id, nchains, tree=False)[:2])
+                elif a == "hmc":
                     # :139-160 with the state on the device; column 0 (the initial state) is not a sample of the reference's
                     z, lp = (np.asfortranarray(v[..., 1:, :]) for v in ctx.sample_hmc(itr, σ_z, seed, chain_id, nchains)[:2])
                 else:
@@ -262,7 +273,7 @@ def inference(*args, **kwargs):
 def subspace_inference(model, cost, data, opt, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=1000, T=25, c=1, M=20,
                        print_freq=1, alg="rwmh", backend="forwarddiff", method="subspace", *, sigma_z=None,
                        sigma_m=None, sigma_p=None, device=0, ctx=None, seed=0, verbose=True, return_z=False,
-                       compute_dtype="f64", device_loop=False, device_sampler=False):
+                       compute_dtype="f64", device_loop=False, device_sampler=False, device_nuts=False):
     """src/space_inference.jl:33-54: construction, then sampling; returns (chn, lp, W_swa).
     W_swa and P stay on the device between the two stages (no host round trip)."""
     m = _alg_name(method)
@@ -280,7 +291,7 @@ def subspace_inference(model, cost, data, opt, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr
         chn, lp = sub_inference(model, data, None, None, σ_z=σ_z, σ_m=σ_m, σ_p=σ_p, itr=itr, M=M, alg=alg,
                                 backend=backend, sigma_z=sigma_z, sigma_m=sigma_m, ctx=ctx, seed=seed,
                                 return_z=return_z, compute_dtype=compute_dtype, device_loop=device_loop,
-                                device_sampler=device_sampler)
+                                device_sampler=device_sampler, device_nuts=device_nuts)
         return chn, lp, w_swa
     finally:
         if own:

@@ -2,7 +2,7 @@
 //   capi.hip         context + construction
 //   capi_infer.hip   inference set-up, density, gradient, predictive forward, the stacked value-and-gradient evaluator
 //   capi_sample.hip  the RWMH samplers and the output map
-//   capi_mala.hip / capi_hmc.hip / capi_advi.hip   the MALA sampler / the HMC sampler / the ADVI fit
+//   capi_mala.hip / capi_hmc.hip / capi_nuts.hip / capi_advi.hip   the MALA / HMC / NUTS samplers / the ADVI fit
 // Nothing here is part of the public interface (include/subspace_hip.h).  Buffers are owned by the types of dev_buf.h (through
 // si_internal.h): no file of the C ABI calls hipMalloc / hipFree / hipHostMalloc / hipHostFree or creates an event by hand.
 #pragma once
@@ -65,5 +65,23 @@ struct StackedVgrad {
 // for), ONE synchronisation -- also after a failure -- and the first error reported: rc, then e, then the synchronisation's.
 struct Download { void* dst; const void* src; size_t bytes; };
 int32_t finish_downloads(si_ctx* ctx, const char* who, hipError_t e, int32_t rc, std::initializer_list<Download> downs);
+
+// capi_hmc.hip: what si_sample_hmc and si_sample_nuts share.  The chains' state for C chains (grown on demand); the kernels' shared
+// arguments over that state and the output arrays (reserved by the caller); the preamble -- hmc_init, then the step-size search
+// round by round with one 4-byte read-back each -- returning its rounds, with e / rc as StackedVgrad::eval treats them; and the
+// adaptation phase of every step t = 1, 2, ... in turn (the host's knowledge, handed to the kernels as flags).
+int32_t hmc_reserve_state(si_ctx* ctx, const char* who, int32_t C);
+HmcRun hmc_run_args(si_ctx* ctx, int64_t itr, double sigma_z, double delta, uint64_t seed, int32_t chain_id0, bool want_G, bool want_Minv);
+int hmc_preamble(si_ctx* ctx, const char* who, const HmcRun& a, StackedVgrad& vg, int32_t C, hipError_t& e, int32_t& rc);
+struct HmcPhases {
+  explicit HmcPhases(int64_t n_adapts);
+  void at(int64_t t, bool& adapting, bool& in_window, bool& window_close, bool& last_adapt);   // t must not decrease between calls
+
+ private:
+  int64_t n_adapts, ws = 0, we = 0;
+  std::vector<int64_t> splits;
+  int32_t nsplits = 0;
+  size_t next_split = 0;
+};
 
 }  // namespace si

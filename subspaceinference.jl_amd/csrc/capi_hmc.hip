@@ -5,6 +5,8 @@
 // One definition, one audit (tests/hmc_audit.py), on the two routes of the stacked evaluator (StackedVgrad, capi_infer.hip): per
 // transition one evaluation at the proposals, then hmc_accept_kernel; position, momentum, step size, metric and adaptor state
 // never leave the device.
+// The state's allocation, the preamble (hmc_init and the search) and the adaptation phases of a step are functions of namespace si
+// here, declared in capi_common.h: si_sample_nuts (capi_nuts.hip) runs the same ones.
 // THE PREAMBLE SYNCHRONISES on both routes: the step-size search is data dependent, so after every round (search kernel, value and
 // gradient at the trial points) the host reads back ONE 4-byte count of the chains still searching.  It is a one-off before the
 // first transition, bounded by the restatement's own limits (1 + 100 + 100 evaluations after the one at z_0), and the only place
@@ -44,6 +46,65 @@ int32_t hmc_windows(int64_t n_adapts, int64_t* window_start, int64_t* window_end
   return count;
 }
 
+int32_t hmc_reserve_state(si_ctx* ctx, const char* who, int32_t C) {
+  if (ctx->hmc_cap >= C) return SI_OK;
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->hmc_cap = 0;
+  const size_t mc = (size_t)ctx->iM * (size_t)C;
+  if (!ctx->d_hmc_z.alloc(mc) || !ctx->d_hmc_g.alloc(mc) || !ctx->d_hmc_zp.alloc(mc) || !ctx->d_hmc_gp.alloc(mc) ||
+      !ctx->d_hmc_rh.alloc(mc) || !ctx->d_hmc_minv.alloc(mc) || !ctx->d_hmc_wmean.alloc(mc) || !ctx->d_hmc_wm2.alloc(mc) ||
+      !ctx->d_hmc_lp.alloc((size_t)C) || !ctx->d_hmc_lpp.alloc((size_t)C) || !ctx->d_hmc_chain.alloc((size_t)C) ||
+      !ctx->d_hmc_open.alloc(1))
+    return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": sampler state allocation failed");
+  ctx->hmc_cap = C;
+  return SI_OK;
+}
+
+HmcRun hmc_run_args(si_ctx* ctx, int64_t itr, double sigma_z, double delta, uint64_t seed, int32_t chain_id0, bool want_G, bool want_Minv) {
+  return HmcRun{ctx->d_hmc_z, ctx->d_hmc_lp, ctx->d_hmc_g, ctx->d_hmc_zp, ctx->d_hmc_rh, ctx->d_hmc_minv, ctx->d_hmc_wmean, ctx->d_hmc_wm2,
+                ctx->d_hmc_lpp, ctx->d_hmc_gp, ctx->d_hmc_chain, ctx->d_outZ, ctx->d_outlp, ctx->d_outalpha, ctx->d_outeps,
+                want_G ? ctx->d_outG.get() : nullptr, want_Minv ? ctx->d_outMinv.get() : nullptr, ctx->iM, chain_id0, itr, seed, sigma_z, delta};
+}
+
+int hmc_preamble(si_ctx* ctx, const char* who, const HmcRun& a, StackedVgrad& vg, int32_t C, hipError_t& e, int32_t& rc) {
+  {
+    ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+    launch_hmc_init(ctx->stream, a, C);
+    e = hipGetLastError();
+  }
+  // z_0's value and gradient, then the search, round by round (at most 1 + 1 + 100 + 100 rounds: the start, the direction, the
+  // crossings, the bisections)
+  int rounds = 0;
+  int32_t open = 1;
+  while (open > 0 && e == hipSuccess && rc == SI_OK && rounds < 2 * 100 + 3) {
+    vg.eval(ctx->d_hmc_zp, ctx->d_hmc_lpp, ctx->d_hmc_gp, e, rc);
+    if (e != hipSuccess || rc != SI_OK) break;
+    e = hipMemsetAsync(ctx->d_hmc_open, 0, sizeof(int32_t), ctx->stream);
+    if (e != hipSuccess) break;
+    {
+      ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+      launch_hmc_search(ctx->stream, a, C, ctx->d_hmc_open);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&open, ctx->d_hmc_open, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    ++rounds;
+  }
+  if (e == hipSuccess && rc == SI_OK && open > 0) rc = fail(ctx, SI_ERR_STATE, std::string(who) + ": the step-size search did not finish within its own limits");
+  return rounds;
+}
+
+HmcPhases::HmcPhases(int64_t n_adapts_) : n_adapts(n_adapts_), splits((size_t)std::max<int32_t>(1, hmc_windows(n_adapts_, nullptr, nullptr, nullptr, 0))) {
+  nsplits = hmc_windows(n_adapts, &ws, &we, splits.data(), (int32_t)splits.size());
+}
+
+void HmcPhases::at(int64_t t, bool& adapting, bool& in_window, bool& window_close, bool& last_adapt) {
+  adapting = t <= n_adapts, in_window = adapting && ws <= t && t <= we;
+  while (next_split < (size_t)nsplits && splits[next_split] < t) ++next_split;
+  window_close = in_window && next_split < (size_t)nsplits && splits[next_split] == t;
+  last_adapt = t == n_adapts;
+}
+
 }  // namespace si
 
 extern "C" {
@@ -66,68 +127,29 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
   BIND(ctx);
   const int32_t C = nchains, M = ctx->iM;
   const int64_t cols = itr + 1;
-  if (ctx->hmc_cap < C) {
-    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->hmc_cap = 0;
-    const size_t mc = (size_t)M * (size_t)C;
-    if (!ctx->d_hmc_z.alloc(mc) || !ctx->d_hmc_g.alloc(mc) || !ctx->d_hmc_zp.alloc(mc) || !ctx->d_hmc_gp.alloc(mc) ||
-        !ctx->d_hmc_rh.alloc(mc) || !ctx->d_hmc_minv.alloc(mc) || !ctx->d_hmc_wmean.alloc(mc) || !ctx->d_hmc_wm2.alloc(mc) ||
-        !ctx->d_hmc_lp.alloc((size_t)C) || !ctx->d_hmc_lpp.alloc((size_t)C) || !ctx->d_hmc_chain.alloc((size_t)C) ||
-        !ctx->d_hmc_open.alloc(1))
-      return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": sampler state allocation failed");
-    ctx->hmc_cap = C;
-  }
+  if ((rc = hmc_reserve_state(ctx, who, C)) != SI_OK) return rc;
   const size_t zelems = (size_t)M * (size_t)cols * (size_t)C, selems = (size_t)cols * (size_t)C;
   if (!ctx->d_outZ.reserve(zelems) || !ctx->d_outlp.reserve(selems) || !ctx->d_outalpha.reserve(selems) || !ctx->d_outeps.reserve(selems) ||
       (G_out && !ctx->d_outG.reserve(zelems)) || (Minv_out && !ctx->d_outMinv.reserve(zelems)))
     return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
-  int64_t ws = 0, we = 0;
-  std::vector<int64_t> splits((size_t)std::max<int32_t>(1, hmc_windows(n_adapts, nullptr, nullptr, nullptr, 0)));
-  const int32_t nsplits = hmc_windows(n_adapts, &ws, &we, splits.data(), (int32_t)splits.size());
-  HmcRun a{ctx->d_hmc_z, ctx->d_hmc_lp, ctx->d_hmc_g, ctx->d_hmc_zp, ctx->d_hmc_rh, ctx->d_hmc_minv, ctx->d_hmc_wmean, ctx->d_hmc_wm2,
-           ctx->d_hmc_lpp, ctx->d_hmc_gp, ctx->d_hmc_chain, ctx->d_outZ, ctx->d_outlp, ctx->d_outalpha, ctx->d_outeps,
-           G_out ? ctx->d_outG.get() : nullptr, Minv_out ? ctx->d_outMinv.get() : nullptr, M, chain_id0, itr, seed, sigma_z, delta};
+  HmcPhases phases(n_adapts);
+  const HmcRun a = hmc_run_args(ctx, itr, sigma_z, delta, seed, chain_id0, G_out != nullptr, Minv_out != nullptr);
   StackedVgrad vg;
   if ((rc = vg.open(ctx, who, C)) != SI_OK) return rc;
   hipError_t e = hipSuccess;
-  {
-    ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-    launch_hmc_init(ctx->stream, a, C);
-    e = hipGetLastError();
-  }
-  // the preamble: z_0's value and gradient, then the search, round by round (at most 1 + 1 + 100 + 100 rounds: the start, the
-  // direction, the crossings, the bisections)
-  int rounds = 0;
-  int32_t open = 1;
-  while (open > 0 && e == hipSuccess && rc == SI_OK && rounds < 2 * 100 + 3) {
-    vg.eval(ctx->d_hmc_zp, ctx->d_hmc_lpp, ctx->d_hmc_gp, e, rc);
-    if (e != hipSuccess || rc != SI_OK) break;
-    e = hipMemsetAsync(ctx->d_hmc_open, 0, sizeof(int32_t), ctx->stream);
-    if (e != hipSuccess) break;
-    {
-      ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-      launch_hmc_search(ctx->stream, a, C, ctx->d_hmc_open);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&open, ctx->d_hmc_open, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    ++rounds;
-  }
-  if (e == hipSuccess && rc == SI_OK && open > 0) rc = fail(ctx, SI_ERR_STATE, std::string(who) + ": the step-size search did not finish within its own limits");
+  const int rounds = hmc_preamble(ctx, who, a, vg, C, e, rc);
   if (e == hipSuccess && rc == SI_OK) {
     ProfScope ps(ctx, SI_K_RWMH, 0, 0);
     launch_hmc_propose(ctx->stream, a, C, 1);
     e = hipGetLastError();
   }
-  size_t next_split = 0;
   for (int64_t t = 1; t <= itr && e == hipSuccess && rc == SI_OK; ++t) {
     vg.eval(ctx->d_hmc_zp, ctx->d_hmc_lpp, ctx->d_hmc_gp, e, rc);
     if (e != hipSuccess || rc != SI_OK) break;
-    const bool adapting = t <= n_adapts, in_window = adapting && ws <= t && t <= we;
-    while (next_split < (size_t)nsplits && splits[next_split] < t) ++next_split;
-    const bool window_close = in_window && next_split < (size_t)nsplits && splits[next_split] == t;
+    bool adapting, in_window, window_close, last_adapt;
+    phases.at(t, adapting, in_window, window_close, last_adapt);
     ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-    launch_hmc_accept(ctx->stream, a, C, (uint64_t)t, adapting, in_window, window_close, t == n_adapts, t < itr);
+    launch_hmc_accept(ctx->stream, a, C, (uint64_t)t, adapting, in_window, window_close, last_adapt, t < itr);
     e = hipGetLastError();
   }
   const size_t zbytes = zelems * sizeof(double), sbytes = selems * sizeof(double);

@@ -1,0 +1,124 @@
+// C ABI, NUTS (reference src/space_inference.jl:139-160): si_sample_nuts, si_nuts_kernel_info.  The transition is defined once, in
+// kernels_nuts.hip; the initial point, the step-size search, the adaptor's phases and the chains' HMC state are si_sample_hmc's own
+// functions (capi_hmc.hip, declared in capi_common.h).  Host-side orchestration only; no CPU fallback anywhere in this file.
+//
+// The trajectory of a transition is a data-dependent tree, so EVERY ROUND SYNCHRONISES, on both routes of the stacked evaluator: a
+// round is one evaluation at the chains' pending points, a memset of the open word, nuts_leaf_kernel and a 4-byte read-back of how
+// many chains are still building -- the pattern of the step-size search.  Chains advance in lock-step within a transition: a chain
+// whose tree is finished waits for the others, its slot is evaluated and ignored.  A transition takes at most 2^max_depth - 1 rounds.
+#include "capi_common.h"
+
+using namespace si;
+
+extern "C" {
+
+int32_t si_sample_nuts(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z, double delta, int32_t max_depth, double max_dh,
+                       uint64_t seed, int32_t chain_id0, int32_t nchains, double* Z_out, double* lp_out, double* alpha_out,
+                       double* eps_out, int32_t* depth_out, int32_t* nleaf_out, int32_t* sel_out, double* G_out, double* Minv_out,
+                       double* leaf_out, int64_t leaf_cap) {
+  CHECK_CTX(ctx);
+  const char* who = "si_sample_nuts";
+  ctx->last_nuts_fused = ctx->last_nuts_passes = ctx->last_nuts_search = 0;   // (si_nuts_kernel_info reports THIS call)
+  ctx->last_nuts_rounds = ctx->last_nuts_leaves = 0;
+  // (every comparison is false for a NaN: refused)
+  int32_t rc = grad_entry_check(ctx, who, itr > 0 && n_adapts >= 0 && n_adapts <= itr && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0 &&
+                                              delta > 0.0 && delta < 1.0 && max_depth >= 1 && max_depth <= NUTS_MAX_DEPTH && max_dh > 0.0 &&
+                                              (!leaf_out || leaf_cap >= 1));
+  if (rc != SI_OK) return rc;
+  BIND(ctx);
+  const int32_t C = nchains, M = ctx->iM;
+  const int64_t cols = itr + 1;
+  if ((rc = hmc_reserve_state(ctx, who, C)) != SI_OK) return rc;
+  if (ctx->nuts_cap < C) {
+    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->nuts_cap = 0;
+    const size_t mc = (size_t)M * (size_t)C;
+    for (DevBuf<double>* b : {&ctx->d_nuts_zm, &ctx->d_nuts_rm, &ctx->d_nuts_gm, &ctx->d_nuts_zq, &ctx->d_nuts_rq, &ctx->d_nuts_gq,
+                              &ctx->d_nuts_rho, &ctx->d_nuts_zc, &ctx->d_nuts_gc})
+      if (!b->alloc(mc)) return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": sampler state allocation failed");
+    if (!ctx->d_nuts_stack.alloc(4 * mc * NUTS_MAX_DEPTH) || !ctx->d_nuts_tree.alloc((size_t)C))
+      return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": sampler state allocation failed");
+    ctx->nuts_cap = C;
+  }
+  const size_t zelems = (size_t)M * (size_t)cols * (size_t)C, selems = (size_t)cols * (size_t)C;
+  const size_t lelems = leaf_out ? (3 * (size_t)M + 1) * (size_t)leaf_cap * (size_t)C : 0;
+  if (!ctx->d_outZ.reserve(zelems) || !ctx->d_outlp.reserve(selems) || !ctx->d_outalpha.reserve(selems) || !ctx->d_outeps.reserve(selems) ||
+      !ctx->d_outdepth.reserve(selems) || !ctx->d_outnleaf.reserve(selems) || !ctx->d_outsel.reserve(selems) ||
+      (G_out && !ctx->d_outG.reserve(zelems)) || (Minv_out && !ctx->d_outMinv.reserve(zelems)) || (leaf_out && !ctx->d_outleaf.reserve(lelems)))
+    return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
+  HmcPhases phases(n_adapts);
+  const HmcRun a = hmc_run_args(ctx, itr, sigma_z, delta, seed, chain_id0, G_out != nullptr, Minv_out != nullptr);
+  const NutsRun n{ctx->d_nuts_zm, ctx->d_nuts_rm, ctx->d_nuts_gm, ctx->d_nuts_zq, ctx->d_nuts_rq, ctx->d_nuts_gq, ctx->d_nuts_rho,
+                  ctx->d_nuts_zc, ctx->d_nuts_gc, ctx->d_nuts_stack, ctx->d_nuts_tree, ctx->d_outdepth, ctx->d_outnleaf, ctx->d_outsel,
+                  leaf_out ? ctx->d_outleaf.get() : nullptr, leaf_cap, max_depth, max_dh};
+  StackedVgrad vg;
+  if ((rc = vg.open(ctx, who, C)) != SI_OK) return rc;
+  // (log slots that no leaf reaches read as NaN: all bits set)
+  hipError_t e = leaf_out ? hipMemsetAsync(ctx->d_outleaf, 0xFF, lelems * sizeof(double), ctx->stream) : hipSuccess;
+  const int search_rounds = e == hipSuccess ? hmc_preamble(ctx, who, a, vg, C, e, rc) : 0;
+  const int64_t round_cap = ((int64_t)1 << max_depth) - 1;
+  int64_t rounds = 0;
+  for (int64_t t = 1; t <= itr && e == hipSuccess && rc == SI_OK; ++t) {
+    {
+      ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+      launch_nuts_begin(ctx->stream, a, n, C, (uint64_t)t, t == 1);
+      e = hipGetLastError();
+    }
+    int32_t open = 1;
+    int64_t r = 0;
+    for (; open > 0 && e == hipSuccess && rc == SI_OK && r < round_cap; ++r) {
+      vg.eval(ctx->d_hmc_zp, ctx->d_hmc_lpp, ctx->d_hmc_gp, e, rc);
+      if (e != hipSuccess || rc != SI_OK) break;
+      e = hipMemsetAsync(ctx->d_hmc_open, 0, sizeof(int32_t), ctx->stream);
+      if (e != hipSuccess) break;
+      {
+        ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+        launch_nuts_leaf(ctx->stream, a, n, C, (uint64_t)t, ctx->d_hmc_open);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = hipMemcpyAsync(&open, ctx->d_hmc_open, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    rounds += r;
+    if (e != hipSuccess || rc != SI_OK) break;
+    if (open > 0) {
+      rc = fail(ctx, SI_ERR_STATE, std::string(who) + ": a trajectory tree did not finish within 2^max_depth - 1 leaves");
+      break;
+    }
+    bool adapting, in_window, window_close, last_adapt;
+    phases.at(t, adapting, in_window, window_close, last_adapt);
+    ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+    launch_nuts_end(ctx->stream, a, n, C, (uint64_t)t, adapting, in_window, window_close, last_adapt);
+    e = hipGetLastError();
+  }
+  const size_t zbytes = zelems * sizeof(double), sbytes = selems * sizeof(double), ibytes = selems * sizeof(int32_t);
+  std::vector<int32_t> nleaf(selems);   // (always fetched: si_nuts_kernel_info's leaves)
+  rc = finish_downloads(ctx, who, e, rc, {{Z_out, ctx->d_outZ, zbytes}, {lp_out, ctx->d_outlp, sbytes}, {alpha_out, ctx->d_outalpha, sbytes},
+                                          {eps_out, ctx->d_outeps, sbytes}, {depth_out, ctx->d_outdepth, ibytes},
+                                          {nleaf.data(), ctx->d_outnleaf, ibytes}, {sel_out, ctx->d_outsel, ibytes},
+                                          {G_out, a.G_out, zbytes}, {Minv_out, a.Minv_out, zbytes},
+                                          {leaf_out, n.leaf_out, lelems * sizeof(double)}});
+  if (rc != SI_OK) return rc;
+  int64_t leaves = 0;
+  for (int32_t v : nleaf) leaves += v;
+  if (nleaf_out) std::memcpy(nleaf_out, nleaf.data(), ibytes);
+  ctx->last_nuts_fused = vg.fused ? 1 : 0;
+  ctx->last_nuts_passes = vg.passes;
+  ctx->last_nuts_search = search_rounds;
+  ctx->last_nuts_rounds = rounds;
+  ctx->last_nuts_leaves = leaves;
+  return SI_OK;
+}
+
+int32_t si_nuts_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out, int32_t* search_rounds_out, int64_t* rounds_out,
+                            int64_t* leaves_out) {
+  CHECK_CTX(ctx);
+  if (fused_out) *fused_out = ctx->last_nuts_fused;
+  if (passes_out) *passes_out = ctx->last_nuts_passes;
+  if (search_rounds_out) *search_rounds_out = ctx->last_nuts_search;
+  if (rounds_out) *rounds_out = ctx->last_nuts_rounds;
+  if (leaves_out) *leaves_out = ctx->last_nuts_leaves;
+  return SI_OK;
+}
+
+}  // extern "C"

@@ -24,40 +24,20 @@
 //            window the Welford update with the KEPT state; at a window's close Minv = n / (n + 5) var + 1e-3 5 / (n + 5) (n >= 2),
 //            the window emptied and the dual averaging restarted at the current eps; after step n_adapts eps = exp(log_eps_bar)
 //
+// The helpers that si_sample_nuts shares (the fixed-order sum, the half kick and drift, the adaptor's update) are hmc_device.h's.
 // Kernels: one workgroup of 256 threads per chain; the value and gradient at the trial points and proposals come from the caller's
 // launches between them (si_sample_hmc, capi_hmc.hip).  Component ownership and the order of every sum over m are kernels_mala.hip's:
 // thread i owns the components 2j, 2j + 1 of its Philox blocks j = i, i + 256, ... and adds them in that order, the wave sums are
 // chain_wave_sum's, the four wave sums are added as (r0 + r1) + (r2 + r3) -- a chain's bits depend on M alone, not on the number of
 // chains, its column, the pass or the run.  Which phase of the adaptation a step is in is the host's knowledge and arrives as kernel
 // arguments; there is no schedule on the device.  Compiled without contraction of a * b + c, like kernels_mala.hip.
-#include "chain_common.h"
+#include "hmc_device.h"
 #include "philox.h"
-#include "si_internal.h"
 
 namespace si {
 
-static constexpr int HMC_NT = 256;
-static constexpr uint32_t HMC_P_MOMENTUM = 5u, HMC_P_SEARCH = 6u;
 static constexpr int HMC_MAX_ITER = 100;
 enum { HMC_S_START = 0, HMC_S_DIRECTION = 1, HMC_S_CROSS = 2, HMC_S_BISECT = 3 };
-
-// the sum of every thread's v in the fixed order; every thread gets it.  (Two barriers: red may be reused right after.)
-__device__ __forceinline__ double hmc_block_sum(double v, double* red) {
-  v = chain_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// rh = r + (e / 2) g,  zp = z + e (minv rh)  for the thread's components; returns its share of 1/2-less sum (minv r) r
-__device__ __forceinline__ double hmc_kick_drift(int m, double r, double e, double mi, const double* __restrict__ z,
-                                                 const double* __restrict__ g, double* __restrict__ rh, double* __restrict__ zp) {
-  const double h = r + (0.5 * e) * g[m];
-  rh[m] = h;
-  zp[m] = z[m] + e * (mi * h);
-  return (mi * r) * r;
-}
 
 // the proposal of transition `step` from the chain's state: r, K0 (into ch->k0 by thread 0), rh, zp
 __device__ __forceinline__ void hmc_propose_chain(const double* __restrict__ z, const double* __restrict__ g, double* __restrict__ zp,
@@ -306,32 +286,9 @@ __global__ __launch_bounds__(HMC_NT) void hmc_accept_kernel(HmcRun a, uint64_t s
     a.alpha_out[col] = alpha;
     a.eps_out[col] = eps;
     accept_s = accept ? 1 : 0;
-    double e_next = eps;
-    int64_t wn = ch->wn;
-    if (adapting) {
-      // Nesterov dual averaging of log eps towards the acceptance delta
-      const double gamma = 0.05, t0 = 10.0, kappa = 0.75;
-      const int64_t t = ++ch->da_t;
-      const double acc = alpha < 1.0 ? alpha : 1.0;
-      const double td = (double)t;
-      ch->hbar = (1.0 - 1.0 / (td + t0)) * ch->hbar + (a.delta - acc) / (td + t0);
-      const double log_eps = ch->mu - sqrt(td) / gamma * ch->hbar;
-      const double eta = pow(td, -kappa);
-      ch->log_eps_bar = eta * log_eps + (1.0 - eta) * ch->log_eps_bar;
-      e_next = exp(700.0 < log_eps ? 700.0 : log_eps);   // (min(log_eps, 700) as the host forms it: a NaN stays)
-      if (in_window) {
-        wn += 1;
-        if (window_close) {   // (the restart: at the eps just set)
-          ch->mu = log(10.0 * e_next);
-          ch->hbar = 0.0;
-          ch->log_eps_bar = 0.0;
-          ch->da_t = 0;
-        }
-      }
-      if (last_adapt && ch->da_t > 0) e_next = exp(700.0 < ch->log_eps_bar ? 700.0 : ch->log_eps_bar);
-      ch->eps = e_next;
-      ch->wn = (in_window && window_close) ? 0 : wn;
-    }
+    double e_next;
+    int64_t wn;
+    hmc_adapt_scalars(ch, a.delta, alpha, eps, adapting, in_window, window_close, last_adapt, e_next, wn);
     eps_next_s = e_next;
     wn_s = (double)wn;
   }
@@ -352,19 +309,7 @@ __global__ __launch_bounds__(HMC_NT) void hmc_accept_kernel(HmcRun a, uint64_t s
         a.Z_out[obase + m] = zv;
         if (a.G_out) a.G_out[obase + m] = gv;
         if (a.Minv_out) a.Minv_out[obase + m] = mi;
-        if (adapting && in_window) {
-          const double dlt = zv - wmean[m];
-          const double mean = wmean[m] + dlt / wn;
-          const double m2 = wm2[m] + dlt * (zv - mean);
-          if (window_close) {
-            if (wn >= 2.0) minv[m] = (wn / (wn + 5.0)) * (m2 / (wn - 1.0)) + 1e-3 * (5.0 / (wn + 5.0));
-            wmean[m] = 0.0;
-            wm2[m] = 0.0;
-          } else {
-            wmean[m] = mean;
-            wm2[m] = m2;
-          }
-        }
+        if (adapting && in_window) hmc_adapt_component(m, zv, wn, window_close, minv, wmean, wm2);
       }
     }
   }

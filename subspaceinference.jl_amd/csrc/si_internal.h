@@ -233,6 +233,18 @@ struct HmcChain {
   int32_t s_phase, s_dir, s_iter, s_done;
 };
 
+// per-chain scalars of si_sample_nuts (kernels_nuts.hip): the trajectory tree of the transition under way and the scalars of the
+// stack of sub-tree summaries of the doubling under way (their vectors live in NutsRun::stack)
+static constexpr int NUTS_MAX_DEPTH = 10;
+struct NutsChain {
+  double h0, logw, lpc, alpha_sum;   // H at the transition's start, the tree's log weight, the candidate's lp, the sum of the leaves' alpha
+  double s_lp[NUTS_MAX_DEPTH], s_logw[NUTS_MAX_DEPTH], s_alpha[NUTS_MAX_DEPTH];   // per stack entry: lp of its proposal, log weight, sum of alpha
+  int32_t s_n[NUTS_MAX_DEPTH], s_sel[NUTS_MAX_DEPTH];                             // its leaves, the leaf that is its proposal
+  int64_t nlog;                      // leaves of this call so far (the leaf log's next slot)
+  int32_t n_alpha, depth, ndoub, dir, k, sp, nleaf, selc, open;   // leaves counted into alpha_sum; doublings completed / started;
+                                     // direction; leaves of the doubling; stack entries; leaves; the candidate's leaf; still building
+};
+
 // ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops
 struct InferState {
   bool i_ready = false;
@@ -320,6 +332,17 @@ struct InferState {
   DevBuf<int32_t> d_hmc_open;                                      // 1: chains whose step-size search is not finished
   DevBuf<double> d_outalpha, d_outeps, d_outMinv;                  // (itr+1) x C twice, M x (itr+1) x C; kept between calls like d_outZ
   int last_hmc_fused = 0, last_hmc_passes = 0, last_hmc_rounds = 0;   // si_hmc_kernel_info
+  // si_sample_nuts (capi_nuts.hip, kernels_nuts.hip), on top of si_sample_hmc's state: both ends of the tree (z, r, g), the sum of its
+  // momenta, the candidate (z, g), the stack of sub-tree summaries (4 M doubles per entry, NUTS_MAX_DEPTH entries per chain), the
+  // per-chain scalars, the device-side depth / leaf count / selected leaf samples and, when asked for, the leaf log
+  int nuts_cap = 0;
+  DevBuf<double> d_nuts_zm, d_nuts_rm, d_nuts_gm, d_nuts_zq, d_nuts_rq, d_nuts_gq, d_nuts_rho, d_nuts_zc, d_nuts_gc;   // M x C each
+  DevBuf<double> d_nuts_stack;                                     // 4 M x NUTS_MAX_DEPTH x C
+  DevBuf<NutsChain> d_nuts_tree;                                   // C
+  DevBuf<int32_t> d_outdepth, d_outnleaf, d_outsel;                // (itr+1) x C each, kept between calls like d_outZ
+  DevBuf<double> d_outleaf;                                        // (3M+1) x leaf_cap x C, only when asked for
+  int last_nuts_fused = 0, last_nuts_passes = 0, last_nuts_search = 0;   // si_nuts_kernel_info
+  int64_t last_nuts_rounds = 0, last_nuts_leaves = 0;
   // si_fit_advi (capi_advi.hip, kernels_advi.hip): the state theta = [mu; omega] of R runs, the optimiser's ring of squared
   // gradients, the step's draws eta with the points made from them, the points' values and gradients, and the device-side traces
   // (grown on demand and kept between calls; every call ends synchronised, so none is in use when it is replaced)
@@ -767,6 +790,25 @@ void launch_hmc_propose(hipStream_t st, const HmcRun& a, int32_t C, uint64_t ste
 // transition `step` given (lpp, gp) at zp, column `step` of the outputs, the adaptor update the flags name, the proposal of step + 1
 void launch_hmc_accept(hipStream_t st, const HmcRun& a, int32_t C, uint64_t step, bool adapting, bool in_window, bool window_close,
                        bool last_adapt, bool propose_next);
+// kernels_nuts.hip (the transition is defined in its header comment): what its three kernels share on top of HmcRun
+struct NutsRun {
+  double *zm, *rm, *gm, *zq, *rq, *gq, *rho, *zc, *gc;   // M x C each: the tree's minus / plus end, its momentum sum, the candidate
+  double* stack;                                         // 4 M x NUTS_MAX_DEPTH x C: per entry r of its first leaf, rho, z and g of its proposal
+  NutsChain* tree;                                       // C
+  int32_t *depth_out, *nleaf_out, *sel_out;              // (itr+1) x C each
+  double* leaf_out;                                      // (3M+1) x leaf_cap x C or NULL
+  int64_t leaf_cap;
+  int32_t max_depth;
+  double max_dh;
+};
+// transition `step` begins: momentum, H, the tree reset, the first direction, the first pending point in HmcRun::zp; first: the call's first
+void launch_nuts_begin(hipStream_t st, const HmcRun& a, const NutsRun& n, int32_t C, uint64_t step, bool first);
+// one round given (lpp, gp) at the pending points: the leaf, its merges, the end of a doubling, the next pending point; the chains
+// still building are counted into open
+void launch_nuts_leaf(hipStream_t st, const HmcRun& a, const NutsRun& n, int32_t C, uint64_t step, int32_t* open);
+// transition `step` ends: the candidate becomes the state, column `step` of the outputs, the adaptor update the flags name
+void launch_nuts_end(hipStream_t st, const HmcRun& a, const NutsRun& n, int32_t C, uint64_t step, bool adapting, bool in_window,
+                     bool window_close, bool last_adapt);
 // the window schedule of the Stan adaptor for n_adapts steps (host only): first and last step inside a window, the steps that close one
 int32_t hmc_windows(int64_t n_adapts, int64_t* window_start, int64_t* window_end, int64_t* splits, int32_t cap);
 // kernels_advi.hip (the step is defined in its header comment): R runs, one workgroup each.  AdviRun: what both kernels share.

@@ -27,6 +27,7 @@
 #       AdvancedMH / AdvancedHMC calls, unchanged, driven by the two device callbacks above
 #   * :advi (:126-138), with device_loop = true only                                             -> GPU (si_fit_advi)
 #   * :hmc (:139-160), with device_sampler = true only                                           -> GPU (si_sample_hmc)
+#   * :nuts (:139-160), with device_nuts = true only                                             -> GPU (si_sample_nuts)
 #   * output map :125                                                                            -> GPU (si_reconstruct)
 #   * more than one GPU: one Julia process per GPU (Distributed workers), one Ctx each, joined by the RCCL communicator
 #       INSIDE the library (si_comm_*): `init_gpus()`, then `subspace_inference(...; ngpu = 8, nchains = 8)`,
@@ -365,6 +366,37 @@ function hmc_kernel_info(ctx::Ctx)
     return fused[] != 0, Int(passes[]), Int(rounds[])
 end
 
+# :139-160 (alg = :nuts) with the trajectory tree, step size, metric and adaptor state on the device (si_sample_nuts): NUTS with
+# multinomial sampling and the generalised no-U-turn criterion under the same adaptor and step-size search as sample_hmc, on the
+# library's Philox streams (seed, chain_id + c).  Returns Z, lp, alpha, eps as sample_hmc (alpha[t] = the mean acceptance over the
+# leaves of transition t - 1), then depth (doublings started), nleaf (leapfrog steps) and sel (the leaf that became the state, 0 =
+# the previous state was kept), each (itr+1) x nchains; with grad / metric = true also the gradients and the diagonal metric used.
+function sample_nuts(ctx::Ctx, itr, σ_z, M; seed = 0, chain_id = 0, nchains = 1, n_adapts = Int(round(itr / 2)), δ = 0.8,
+                     max_depth = 10, max_dh = 1000.0, grad = false, metric = false)
+    Z = Array{Float64}(undef, M, itr + 1, nchains); lp = Matrix{Float64}(undef, itr + 1, nchains)
+    alpha = Matrix{Float64}(undef, itr + 1, nchains); eps = Matrix{Float64}(undef, itr + 1, nchains)
+    depth = Matrix{Int32}(undef, itr + 1, nchains); nleaf = Matrix{Int32}(undef, itr + 1, nchains)
+    sel = Matrix{Int32}(undef, itr + 1, nchains)
+    G = grad ? Array{Float64}(undef, M, itr + 1, nchains) : nothing
+    Minv = metric ? Array{Float64}(undef, M, itr + 1, nchains) : nothing
+    GC.@preserve Z lp alpha eps depth nleaf sel G Minv check(ctx, ccall((:si_sample_nuts, LIB), Int32,
+        (Ptr{Cvoid}, Int64, Int64, Float64, Float64, Int32, Float64, UInt64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
+        ctx.h, itr, n_adapts, Float64(σ_z), Float64(δ), max_depth, Float64(max_dh), UInt64(seed), chain_id, nchains, Z, lp, alpha, eps,
+        depth, nleaf, sel, grad ? pointer(G) : Ptr{Float64}(C_NULL), metric ? pointer(Minv) : Ptr{Float64}(C_NULL),
+        Ptr{Float64}(C_NULL), 0))
+    return Z, lp, alpha, eps, depth, nleaf, sel, G, Minv
+end
+
+# (fused, passes, search_rounds, rounds, leaves) of the last sample_nuts: route and passes as hmc_kernel_info, the rounds of all
+# transitions and the leapfrog steps of all chains (rounds * nchains - leaves = the lock-step waste)
+function nuts_kernel_info(ctx::Ctx)
+    fused = Ref{Int32}(0); passes = Ref{Int32}(0); search = Ref{Int32}(0); rounds = Ref{Int64}(0); leaves = Ref{Int64}(0)
+    check(ctx, ccall((:si_nuts_kernel_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int64}, Ref{Int64}),
+                     ctx.h, fused, passes, search, rounds, leaves))
+    return fused[] != 0, Int(passes[]), Int(search[]), Int(rounds[]), Int(leaves[])
+end
+
 # the window schedule of sample_hmc's metric adaptation (host only): (window_start, window_end, the steps that close a window)
 function host_hmc_windows(n_adapts)
     ws = Ref{Int64}(0); we = Ref{Int64}(0)
@@ -422,10 +454,13 @@ end
 # (fit_advi): without the keyword it throws, as it always has; lp is zeros(itr), as in the reference (:138)
 # device_sampler = true (alg = :hmc; non-default): the one-step HMC runs with its state on the device (sample_hmc) and the initial
 # state is dropped; the default keeps the reference's own AdvancedHMC calls
+# device_nuts = true (alg = :nuts; non-default): NUTS runs with its tree and adaptation on the device (sample_nuts), max_depth 10 and
+# max_dh 1000, and the initial state is dropped; the default keeps the reference's own AdvancedHMC calls
 function sub_inference(in_model, data, W_swa, P; σ_z = 1.0, σ_m = 1.0, σ_p = 1.0, itr = 100, M = 3, alg = :rwmh,
                        backend = :forwarddiff, device = 0, ctx = Ctx(device), seed = 0, chain_id = 0, include_prior = false,
-                       compute_dtype = :f64, device_loop = false, device_sampler = false)
+                       compute_dtype = :f64, device_loop = false, device_sampler = false, device_nuts = false)
     alg == :mh && (alg = :rwmh)                                     # README.md:153-154
+    (device_nuts && alg != :nuts) && throw("device_nuts = true is available for alg = :nuts only")
     (device_sampler && alg != :hmc) && throw("device_sampler = true is available for alg = :hmc only" *
         (alg in (:mala, :advi) ? " (alg = :$alg runs on the device with device_loop = true)" : ""))
     (device_loop && !(alg in (:mala, :advi))) && throw("device_loop = true is available for alg = :mala and :advi only")
@@ -459,6 +494,10 @@ function sub_inference(in_model, data, W_swa, P; σ_z = 1.0, σ_m = 1.0, σ_p = 
     end
     if alg == :hmc && device_sampler
         Z, lp, _, _ = sample_hmc(ctx, itr, σ_z, M; seed = seed, chain_id = chain_id)
+        return reconstruct(ctx, Z[:, 2:end, 1], N), lp[2:end, 1]
+    end
+    if alg == :nuts && device_nuts
+        Z, lp = sample_nuts(ctx, itr, σ_z, M; seed = seed, chain_id = chain_id)
         return reconstruct(ctx, Z[:, 2:end, 1], N), lp[2:end, 1]
     end
     if alg == :advi

@@ -23,7 +23,9 @@ The random stream is NumPy's PCG64 seeded by the caller (the reference uses Juli
 `mala` and `hmc` (with `StanAdaptor` and `find_good_stepsize`) are also THE DEFINITION of the device samplers si_sample_mala and
 si_sample_hmc (csrc/kernels_mala.hip, csrc/kernels_hmc.hip), which run the same statements on the library's Philox streams with
 the chain state on the device; tests/mala_audit.py and tests/hmc_audit.py hold the device's traces to these functions transition
-by transition.  A change here changes what those kernels must compute.  `nuts` exists as this host loop only.
+by transition.  A change here changes what those kernels must compute.  `nuts` is the definition of NUTS; `nuts_iter` restates it
+leaf by leaf with an explicit stack (bit for bit the same results on the same generator, tests/test_nuts_audit_cpu.py) and is, on
+the Philox streams, THE DEFINITION of si_sample_nuts (csrc/kernels_nuts.hip), which tests/nuts_audit.py holds to it.
 """
 import math
 
@@ -321,5 +323,121 @@ def nuts(logdensity_grad, m, itr, sigma_z, rng, delta=0.8, max_depth=10, max_dh=
         z, lp, g = zn, lpn, gn
         a = alpha_sum / max(1, n_alpha)
         zs[:, t], lps[t], acc[t] = z, lp, a
+        ad.adapt(z, a)
+    return zs, lps, float(acc.mean())
+
+
+# the kinds of draw of `nuts_iter`, the first argument of its callback
+NUTS_DRAW_INITIAL, NUTS_DRAW_SEARCH, NUTS_DRAW_MOMENTUM, NUTS_DRAW_DIRECTION, NUTS_DRAW_PROGRESSIVE, NUTS_DRAW_MERGE = (
+    "initial", "search", "momentum", "direction", "progressive", "merge")
+
+
+def sequential_draw(rng, m):
+    """the callback of `nuts_iter` that ignores the address and pulls from `rng` in call order: m standard normals for the three
+    vector kinds, one uniform for the others -- what `nuts` draws, in the order it draws"""
+    def draw(kind, t, depth, leaf, level):
+        if kind in (NUTS_DRAW_INITIAL, NUTS_DRAW_SEARCH, NUTS_DRAW_MOMENTUM):
+            return rng.standard_normal(m)
+        return rng.random()
+    return draw
+
+
+class _SearchDraw:
+    """the generator `find_good_stepsize` draws its one momentum from, on the callback"""
+
+    def __init__(self, draw):
+        self._draw = draw
+
+    def standard_normal(self, n):
+        return self._draw(NUTS_DRAW_SEARCH, 0, 0, 0, 0)
+
+
+def nuts_iter(logdensity_grad, m, itr, sigma_z, draw, delta=0.8, max_depth=10, max_dh=1000.0, n_adapts=None, stats=None):
+    """`nuts` without recursion: every doubling builds its sub-tree LEAF BY LEAF with an explicit stack of at most `depth`
+    sub-tree summaries.  After leaf number k (1-based within the doubling) the top two entries merge once for every trailing
+    zero bit of k -- the statements of `build` -- so the stack holds one complete sub-tree per set bit of k.  On a stop (a
+    divergent leaf, or the U-turn of a merged sub-tree) the entries under the stopped one fold into it from the top down, which
+    gives alpha and n the recursion's own association; nothing else of a stopped sub-tree is used.
+
+    Every random number comes through `draw(kind, t, depth, leaf, level)`: kind one of the NUTS_DRAW_* names, t the transition
+    (0-based; the device's step is t + 1), depth the doubling, leaf the running leaf count of the transition (1 ..), level the
+    merge level (1 ..).  The merge uniform is drawn only when the later sub-tree has not stopped (it never has, here: a stop folds
+    at once), as in `build`.  With `sequential_draw(rng, m)` the results equal `nuts(..., rng)` bit for bit.
+
+    n_adapts=None is round(itr / 2).  stats: a list that receives per transition (doublings started, leaves, the leaf that became
+    the state -- 1-based within the transition, 0 = the previous state was kept)."""
+    z = sigma_z * draw(NUTS_DRAW_INITIAL, 0, 0, 0, 0)
+    lp, g = logdensity_grad(z)
+    ad = StanAdaptor(m, int(round(itr / 2)) if n_adapts is None else int(n_adapts),
+                     find_good_stepsize(logdensity_grad, z, lp, g, _SearchDraw(draw)), delta)
+    zs = np.empty((m, itr), order="F")
+    lps = np.empty(itr)
+    acc = np.empty(itr)
+    for t in range(itr):
+        minv, eps = ad.minv, ad.eps
+        r0 = draw(NUTS_DRAW_MOMENTUM, t, 0, 0, 0) / np.sqrt(minv)
+        h0 = lp - _kinetic(r0, minv)
+        tree = dict(zm=z, rm=r0, gm=g, zp=z, rp=r0, gp=g, rho=r0.copy(), logw=0.0)
+        zn, lpn, gn, sel = z, lp, g, 0
+        alpha_sum, n_alpha = 0.0, 0
+        nleaf = ndoub = 0
+        for depth in range(max_depth):
+            ndoub += 1
+            v = 1.0 if draw(NUTS_DRAW_DIRECTION, t, depth, nleaf, 0) < 0.5 else -1.0
+            ze, re, ge = (tree["zp"], tree["rp"], tree["gp"]) if v > 0 else (tree["zm"], tree["rm"], tree["gm"])
+            stack = []
+            stopped = False
+            for k in range(1, 2 ** depth + 1):
+                ze, re, lp1, ge = _leapfrog(logdensity_grad, ze, re, ge, v * eps, minv)
+                nleaf += 1
+                h1 = lp1 - _kinetic(re, minv)
+                if not np.isfinite(h1):
+                    h1 = -np.inf
+                dh = h1 - h0
+                stack.append(dict(rfirst=re, zprop=ze, lpprop=lp1, gprop=ge, sel=nleaf, logw=dh, rho=re.copy(),
+                                  alpha=min(1.0, math.exp(dh)) if dh < 0 else 1.0, n=1))
+                stopped = (-dh) > max_dh
+                level = 0
+                while not stopped and (k >> level) & 1 == 0:
+                    level += 1
+                    b = stack.pop()
+                    a = stack.pop()
+                    logw = np.logaddexp(a["logw"], b["logw"])
+                    out = dict(a)
+                    if math.log(draw(NUTS_DRAW_MERGE, t, depth, nleaf, level)) < b["logw"] - logw:   # multinomial sampling inside the sub-tree
+                        out.update(zprop=b["zprop"], lpprop=b["lpprop"], gprop=b["gprop"], sel=b["sel"])
+                    out["rho"] = a["rho"] + b["rho"]
+                    out["logw"] = logw
+                    out["alpha"] = a["alpha"] + b["alpha"]
+                    out["n"] = a["n"] + b["n"]
+                    # the merged sub-tree's ends: its first leaf and the leaf just made, ordered by the direction
+                    rm, rp = (out["rfirst"], re) if v > 0 else (re, out["rfirst"])
+                    stopped = _uturn(out["rho"], minv * rm, minv * rp)
+                    stack.append(out)
+                if stopped:
+                    break
+            sub = stack.pop()
+            while stack:                     # (only after a stop: the rest of the stack, top to bottom)
+                a = stack.pop()
+                sub = dict(alpha=a["alpha"] + sub["alpha"], n=a["n"] + sub["n"])
+            alpha_sum += sub["alpha"]
+            n_alpha += sub["n"]
+            if stopped:
+                break
+            if math.log(draw(NUTS_DRAW_PROGRESSIVE, t, depth, nleaf, 0)) < sub["logw"] - tree["logw"]:   # biased progressive sampling
+                zn, lpn, gn, sel = sub["zprop"], sub["lpprop"], sub["gprop"], sub["sel"]
+            if v > 0:
+                tree.update(zp=ze, rp=re, gp=ge)
+            else:
+                tree.update(zm=ze, rm=re, gm=ge)
+            tree["rho"] = tree["rho"] + sub["rho"]
+            tree["logw"] = np.logaddexp(tree["logw"], sub["logw"])
+            if _uturn(tree["rho"], minv * tree["rm"], minv * tree["rp"]):
+                break
+        z, lp, g = zn, lpn, gn
+        a = alpha_sum / max(1, n_alpha)
+        zs[:, t], lps[t], acc[t] = z, lp, a
+        if stats is not None:
+            stats.append((ndoub, nleaf, sel))
         ad.adapt(z, a)
     return zs, lps, float(acc.mean())

@@ -6,7 +6,9 @@ column of P, a wrong chain slot or a lost bias shows in any element however smal
 
 Which kernel each case reaches (from the dispatch: launch_dense_f64 / launch_dense_f64_fused in kernels_gemm.hip,
 dense_small_applies in kernels_gemm_small.hip, dense_panel_applies in kernels_gemm_panel.hip, launch_f32_any in
-kernels_gemm_f32.hip, launch_reconstruct in kernels_stream.hip) is written next to it."""
+kernels_gemm_f32.hip, launch_reconstruct in kernels_stream.hip) is written next to it; tests/dense_routes.py restates that
+dispatch and tests/test_dense_exact_cpu.py computes what these cases reach from it (the cases here reach 41 of the 87 fp64 Dense
+instantiations the table lists; tests/test_gpu_dense_exact.py holds all of them)."""
 import functools
 
 import numpy as np
@@ -25,7 +27,8 @@ SI_F32, SI_F64 = 0, 1
 # (sparse weights: w_density, one nonzero per row of P, one-hot z) so every partial sum stays below 2^24 units.
 _F32 = dict(f32=True, w_density=0.03, p_nnz=1, z_nnz=1, w_range=2, x_range=1)
 _SPECS = {
-    # dense_f64_kernel (tile): 2 x 71 feature/batch tiles > 128 -> not the small kernel; ragged out (130, 65, 3), B, in (37)
+    # dense_f64_kernel (tile) for layer 1: 2 x 71 feature/batch tiles > 128 -> not the small kernel; ragged out (130), B, in (37).
+    # Layer 2 (65 rows, the fused head) has 1 x 71 tiles: the small kernel for one chain, the tile kernel with three stacked
     "tile_ragged": (([37, 130, 65, 3], [R, R, I], 9001), dict(m=4, ncols=3, w_density=0.15)),
     # dense_f64_panel (single chain): layer 1 with in <= 128, even out in 64..1024, 64 x 129 tiles >= 16 x 512 workgroups, W at
     # offset 0, and a stored layer (not the one fused with the head: launch_dense_f64_fused has no panel form)
@@ -137,7 +140,11 @@ def test_logdensity_grad_exact(gpu_ctx, name):
         lat.assert_exact(g, dz, "d lp / d z, column %d" % c)
 
 
-# shapes of test_gpu_parity.py::test_weight_gradient_dma_kernel (the LDS-DMA weight-gradient kernel), made lattice
+# shapes of test_gpu_parity.py::test_weight_gradient_dma_kernel, made lattice.  At every batch used below (nbt, nbt - 37,
+# nbt / 2 + 5) plan_dw gives each of their layers 64 x 128 tiles, so they run the register-staged weight gradient
+# gemm_f64_kernel<64, 128, .., EPI_RAW> and never the LDS-DMA kernel (tests/test_dense_exact_cpu.py asserts it from the route
+# table); dw_f64_dma_kernel<96, 128 | 192> and the 96- and 128-row register-staged tiles are held bit for bit by
+# tests/test_gpu_dense_exact.py.
 TRAIN_CASES = [
     ([6, 100, 190, 2], 4096),
     ([20, 386, 98, 1], 1024),

@@ -1074,15 +1074,17 @@ def test_random_shape_sweep_training_gradient(si, gpu_ctx):
 
 
 @pytest.mark.parametrize("dims,nb", [
-    ([6, 100, 190, 2], 4096),       # 190 x 100 and 100 x 6: one ragged 96-row / 192-column tile each
-    ([20, 386, 98, 1], 1024),       # in = 386: three 192-column tiles, the last with two live columns
-    ([128, 960, 960, 1], 3200),     # cfg2's layers: 96 x 192 tiles, no padding
-    ([64, 192, 96, 3], 160),        # exactly one tile, ten k tiles
-    ([30, 130, 258, 2], 2064),      # 16 | B, ragged rows and columns, pairs at the clamp
+    # (which kernel plan_dw picks, from tests/dense_routes.py: only cfg2's 960 x 960 layer reaches the LDS-DMA kernel here)
+    ([6, 100, 190, 2], 4096),       # 190 x 100 and 100 x 6: 64 x 128 tiles, 16 splits, the register-staged kernel
+    ([20, 386, 98, 1], 1024),       # 98 x 386 and 386 x 20: 64 x 128 tiles, 4 splits, the register-staged kernel
+    ([128, 960, 960, 1], 3200),     # cfg2's layers: 960 x 960 dw_f64_dma_kernel<96, 192>, 50 tiles x 10 splits; 960 x 128 64 x 128 tiles x 13
+    ([64, 192, 96, 3], 160),        # one split of ten k tiles, 64 x 128 tiles, the register-staged kernel
+    ([30, 130, 258, 2], 2064),      # 16 | B, ragged rows and columns: 64 x 128 tiles, 9 splits, the register-staged kernel
 ])
 def test_weight_gradient_dma_kernel(si, gpu_ctx, dims, nb):
-    """The LDS-DMA weight-gradient kernel (kernels_bwd.hip dw_f64_dma_kernel: batches that are whole 16-deep k tiles, even
-    widths) -- the FULL weight gradient of si_train_grad, entry by entry, against the host stand-in of Zygote's gradient."""
+    """Shapes the LDS-DMA weight-gradient kernel accepts (kernels_bwd.hip dw_dma_ok: batches that are whole 16-deep k tiles, even
+    widths; whether it runs is plan_dw's choice of tile, see above) -- the FULL weight gradient of si_train_grad, entry by entry,
+    against the host stand-in of Zygote's gradient.  tests/test_gpu_dense_exact.py holds both DMA instantiations to the bit."""
     from subspaceinference_jl_amd import flux
     wr = np.random.default_rng(sum(dims) + nb)
     acts = [flux.relu, flux.tanh, flux.identity]

@@ -30,11 +30,37 @@ inline void accept_rates(const std::vector<int64_t>& nacc, int64_t itr, double* 
   if (!(ctx)) return SI_ERR_INVALID
 #define BIND(ctx) SI_HIP(ctx, hipSetDevice((ctx)->device))
 
+namespace si {
+
+// What a density evaluation reads that depends on WHICH data set and WHICH workspace the call is for.  What belongs to the chain
+// set up stays on the context: layers and plan, fuse_tail, the slot counts, d_w / d_w32 / d_wpack*, d_zprop, d_sse, d_wsq, the
+// tile program.  setup_view is the view of the set-up's own data; si_predict builds one over its temporaries.
+struct DensityView {
+  const double *X, *Xc;           // Xc: X re-laid channel-fastest (spatial input), else null
+  const float* X32;               // X rounded to fp32 (f32), else null
+  const double* Y;
+  int64_t B;
+  const DevBuf<double>* act;      // the two ping-pong activation buffers, chain slots act_elems apart
+  const DevBuf<float>* act32;     // (f32)
+  double* ssepart;
+  int sse_blocks;
+  double *part, *yhat;            // partial products of the fused head; fp64 model outputs
+  int64_t act_elems;
+  bool f32;                       // the forward pass runs on fp32 operands
+  bool defer_sse_final;           // the SSE block partials stay in ssepart (the RWMH tail kernel sums them)
+  bool is_setup_data;             // X, Y, B are the set-up's: what the narrow chain's plan and tile program were built for
+};
+constexpr int32_t SI_NOT_TAKEN = INT32_MIN;   // a density route's or a sampler form's answer "does not apply": the next one is tried
+
+}  // namespace si
+
 extern "C" {   // (defined inside the extern "C" blocks of their translation units; not exported by include/subspace_hip.h)
 // capi_infer.hip
 int32_t ensure_chains(si_ctx* ctx, int32_t C);   // forward workspace + sampler state for C chains
-int32_t eval_density(si_ctx* ctx, int c0, int nc, const double** yhat_out);   // d_zprop[:, c0 .. c0+nc) -> d_sse
-int32_t eval_density_all(si_ctx* ctx, int C);
+si::DensityView setup_view(const si_ctx* ctx, bool defer_sse_final = false);
+// d_zprop[:, c0 .. c0+nc) -> d_sse, nc <= the view's chain slots; eval_density_all: all C chains, fw_slots at a time
+int32_t eval_density(si_ctx* ctx, const si::DensityView& v, int c0, int nc, const double** yhat_out);
+int32_t eval_density_all(si_ctx* ctx, const si::DensityView& v, int C);
 double mvnormal_c0(double d, double sigma);
 double prior_c0(const si_ctx* ctx);
 void fused_fill_program(const si_ctx* ctx, si::ChainFusedPlan& fp);

@@ -1,6 +1,8 @@
 // C ABI, inference side: si_infer_setup*, the density (si_logdensity, si_forward, si_predict) and its gradient
 // (si_logdensity_grad) -- reference src/space_inference.jl:88-95,107 and src/libs.jl:55-57,75-77.  Host-side orchestration only:
-// every arithmetic step runs in the kernels of kernels_*.hip.  No CPU fallback anywhere in this file.  The per-layer passes over a
+// every arithmetic step runs in the kernels of kernels_*.hip.  No CPU fallback anywhere in this file.  eval_density is K4, the
+// optional prior sum and ONE of three routes (density_net, density_fused, density_layers); the data and workspace it runs on
+// come in a DensityView (capi_common.h), so no caller steers it through the context -- si_predict hands it its own.  The per-layer passes over a
 // chain are shared with the training step: dense_forward / dense_value_and_grad_f64 (capi.hip), dense_value_and_grad_f32
 // (capi_train.hip), net_forward / net_value_and_grad (capi_net.hip).
 #include "capi_common.h"
@@ -277,120 +279,114 @@ int32_t ensure_chains(si_ctx* ctx, int32_t C) {
   return SI_OK;
 }
 
-// density evaluations for chain slots [c0, c0 + nc), nc <= fw_slots, in ONE pass of launches:
-// d_zprop[:, c] -> d_sse[c]; optionally leaves the model outputs at *yhat_out (slot j at + j * out_dim*B after the fused
-// tail, at + j * act_elems otherwise)
-int32_t eval_density(si_ctx* ctx, int c0, int nc, const double** yhat_out) {
-  ctx->last_density_spec = 0;   // (si_chain_kernel_info reports the last evaluation)
-  const int64_t N = ctx->iN, B = ctx->B, ldw = pad_ld(N);
-  const int32_t M = ctx->iM;
-  const double dn = (double)nc;
+DensityView setup_view(const si_ctx* ctx, bool defer_sse_final) {
+  return {ctx->d_X, ctx->d_Xc, ctx->d_X32, ctx->d_Y, ctx->B, ctx->d_act, ctx->d_act32, ctx->d_ssepart, ctx->sse_blocks,
+          ctx->d_part, ctx->d_yhat, ctx->act_elems, ctx->f32, defer_sse_final, true};
+}
+
+// ---- the three routes of a density evaluation: K4 has left the weights of chain slots [c0, c0 + nc) in d_w (and d_w32) ------------
+// Conv / MaxPool / flatten / Dense layers one after the other (capi_net.hip), ping-pong activations, one chain per pass.
+// T = float is compute_dtype = SI_F32 on a Conv chain: the same pass on fp32 operands, the squared errors in fp64 with the
+// fp64 outputs written beside them on request.  (the template has C++ linkage inside this extern "C" block)
+static void net_sse(si_ctx* ctx, const DensityView& v, const double* last, int64_t d, int c0, const double** yhat_out) {
+  launch_sse(ctx->stream, last, v.Y, d, v.ssepart, v.sse_blocks, ctx->d_sse + c0, 1, v.act_elems, !v.defer_sse_final);
+  if (yhat_out) *yhat_out = last;
+}
+static void net_sse(si_ctx* ctx, const DensityView& v, const float* last, int64_t d, int c0, const double** yhat_out) {
+  launch_sse_f32(ctx->stream, last, v.Y, d, v.ssepart, v.sse_blocks, ctx->d_sse + c0, 1, v.act_elems, yhat_out ? v.yhat : nullptr, d,
+                 !v.defer_sse_final);
+  if (yhat_out) *yhat_out = v.yhat;
+}
+extern "C++" template <typename T>
+static int32_t density_net(si_ctx* ctx, const DensityView& v, const T* w, const T* x, const DevBuf<T>* act, T* wpack, int c0,
+                           const double** yhat_out) {
+  T* last = nullptr;
+  const int32_t rc = net_forward<T>(ctx, ctx->plan, w, x, v.B, act, wpack, /*pingpong=*/true, &last);
+  if (rc != SI_OK) return rc;
+  const int64_t d = (int64_t)ctx->out_dim * v.B;
   {
-    ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * dn, (double)N * (M + 1 + dn) * 8.0);
-    launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, ctx->d_zprop + (size_t)c0 * M, nc, ctx->d_w, ldw,
-                       ctx->num_cu, ctx->f32 ? ctx->d_w32 : nullptr, ldw);
+    ProfScope ps(ctx, SI_K_SSE, 3.0 * (double)d, (8.0 + (double)sizeof(T)) * (double)d);
+    net_sse(ctx, v, last, d, c0, yhat_out);
   }
-  if (ctx->sigma_p > 0.0)  // ||new_W||^2 per chain for the optional prior term (same fixed-order reduction as the SSE)
-    launch_sse(ctx->stream, ctx->d_w, nullptr, N, ctx->d_wsqpart, ctx->wsq_blocks, ctx->d_wsq + c0, nc, ldw);
-  if (ctx->plan.has_conv && ctx->f32) {
-    // compute_dtype = SI_F32 on a Conv chain: the same pass on fp32 operands; the squared errors in fp64
-    float* last32 = nullptr;
-    const int32_t rc = net_forward<float>(ctx, ctx->plan, ctx->d_w32, ctx->d_X32, B, ctx->d_act32, ctx->d_wpack32, /*pingpong=*/true, &last32);
-    if (rc != SI_OK) return rc;
-    const int64_t d = (int64_t)ctx->out_dim * B;
-    {
-      ProfScope ps(ctx, SI_K_SSE, 3.0 * (double)d, 12.0 * (double)d);
-      launch_sse_f32(ctx->stream, last32, ctx->d_Y, d, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse + c0, 1, ctx->act_elems,
-                     yhat_out ? ctx->d_yhat : nullptr, d, !ctx->defer_sse_final);
-    }
-    SI_HIP(ctx, hipGetLastError());
-    if (yhat_out) *yhat_out = ctx->d_yhat;
-    return SI_OK;
-  }
-  if (ctx->plan.has_conv) {
-    // generic path (capi_net.hip): Conv / MaxPool / flatten / Dense layers one after the other, ping-pong activations
-    double* last = nullptr;
-    const int32_t rc = net_forward<double>(ctx, ctx->plan, ctx->d_w, ctx->plan.input_spatial ? ctx->d_Xc : ctx->d_X, B, ctx->d_act,
-                                           ctx->d_wpack, /*pingpong=*/true, &last);
-    if (rc != SI_OK) return rc;
-    const int64_t d = (int64_t)ctx->out_dim * B;
-    {
-      ProfScope ps(ctx, SI_K_SSE, 3.0 * (double)d, 16.0 * (double)d);
-      launch_sse(ctx->stream, last, ctx->d_Y, d, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse + c0, 1, ctx->act_elems, !ctx->defer_sse_final);
-    }
-    SI_HIP(ctx, hipGetLastError());
-    if (yhat_out) *yhat_out = last;
-    return SI_OK;
-  }
-  if (ctx->fused_ok && ctx->chain_mode != 0 && !yhat_out) {   // (never with compute_dtype = SI_F32: fused_chain_class)
-    // narrow chain: every layer of all nc chains in ONE launch, activations in LDS; the model outputs go through the plain
-    // SSE kernels (one squared error per thread: the same partial sums as tail_sse_kernel's)
-    ChainFusedPlan fp;
-    int nb = 1;
-    bool wave_tiles = false;
-    const size_t lds = fused_plan_for(ctx, nc, fp, &nb, &wave_tiles);
-    if (lds != 0) {
-      const int64_t d = (int64_t)ctx->out_dim * B;
-      {
-        const double fl = 2.0 * (double)N * (double)B * dn;
-        const double by = ((double)N * dn + (double)ctx->in_dim * (double)B + (double)d * dn) * 8.0;
-        ProfScope ps(ctx, SI_K_DENSE, fl, by);
-        ProfScope pm(ctx, SI_K_DENSE_MAIN, fl, by);
-        const SpecKernels* sk = nullptr;
-        if (ctx->chain_spec && ctx->fuse_tail)   // the same kernel compiled for this chain's shapes (chain_spec_rtc.cpp; same bits)
-          sk = spec_kernels(ctx->layers.data(), (int)ctx->layers.size(), nb, dense_fused_slot_feats(ctx->layers[ctx->layers.size() - 2].out), 0, false,
-                            &ctx->spec_message);
-        ctx->last_density_spec = sk != nullptr;
-        if (sk) {
-          const double* wp = ctx->d_w;
-          const double* xp = ctx->d_X;
-          double* yp = ctx->d_yhat;
-          long long ws = ldw, ys = d;
-          int Bi = (int)B;
-          void* args[] = {&wp, &ws, &xp, &yp, &ys, &Bi};
-          if (sk->stack && nc >= 16) {
-            // many chains: a wave per 16 observations with the activations in registers and the chain's weights in LDS, no barrier
-            // between layers (329 against 495 us at 512 chains of the nn_example model, 48 against 71 at 64; 24 against 14 at 8)
-            const int splits = nc >= ctx->num_cu ? 1 : std::min(8, (ctx->num_cu + nc - 1) / nc);
-            SI_HIP(ctx, hipModuleLaunchKernel(sk->stack, (unsigned)splits, (unsigned)nc, 1, 512, 1, 1,
-                                              (unsigned)((size_t)sk->wvec_doubles * sizeof(double)), ctx->stream, args, nullptr));
-          } else {
-            SI_HIP(ctx, hipModuleLaunchKernel(sk->fused, (unsigned)((B + 16 * nb - 1) / (16 * nb)), (unsigned)nc, 1, 256, 1, 1,
-                                              (unsigned)((size_t)sk->lds_doubles * sizeof(double)), ctx->stream, args, nullptr));
-          }
-        } else {
-          launch_chain_fused(ctx->stream, fp, nb, wave_tiles, lds, ctx->d_w, ldw, ctx->d_X, ctx->d_yhat, d, nc);
-        }
+  SI_HIP(ctx, hipGetLastError());
+  return SI_OK;
+}
+
+// Narrow chain: every layer of all nc chains in ONE launch, activations in LDS; the model outputs go through the plain SSE
+// kernels (one squared error per thread: the same partial sums as tail_sse_kernel's).  Its plan and tile program were built for
+// the set-up's B, so a view of other data is refused.  SI_NOT_TAKEN: no LDS plan at this nc, nothing launched.
+static int32_t density_fused(si_ctx* ctx, const DensityView& v, int c0, int nc) {
+  if (!v.is_setup_data) return fail(ctx, SI_ERR_STATE, "eval_density: the narrow-chain launch is built for the set-up's own data");
+  const int64_t N = ctx->iN, B = v.B, ldw = pad_ld(N);
+  const double dn = (double)nc;
+  ChainFusedPlan fp;
+  int nb = 1;
+  bool wave_tiles = false;
+  const size_t lds = fused_plan_for(ctx, nc, fp, &nb, &wave_tiles);
+  if (lds == 0) return SI_NOT_TAKEN;
+  const int64_t d = (int64_t)ctx->out_dim * B;
+  {
+    const double fl = 2.0 * (double)N * (double)B * dn;
+    const double by = ((double)N * dn + (double)ctx->in_dim * (double)B + (double)d * dn) * 8.0;
+    ProfScope ps(ctx, SI_K_DENSE, fl, by);
+    ProfScope pm(ctx, SI_K_DENSE_MAIN, fl, by);
+    const SpecKernels* sk = nullptr;
+    if (ctx->chain_spec && ctx->fuse_tail)   // the same kernel compiled for this chain's shapes (chain_spec_rtc.cpp; same bits)
+      sk = spec_kernels(ctx->layers.data(), (int)ctx->layers.size(), nb, dense_fused_slot_feats(ctx->layers[ctx->layers.size() - 2].out), 0, false,
+                        &ctx->spec_message);
+    ctx->last_density_spec = sk != nullptr;
+    if (sk) {
+      const double* wp = ctx->d_w;
+      const double* xp = v.X;
+      double* yp = v.yhat;
+      long long ws = ldw, ys = d;
+      int Bi = (int)B;
+      void* args[] = {&wp, &ws, &xp, &yp, &ys, &Bi};
+      if (sk->stack && nc >= 16) {
+        // many chains: a wave per 16 observations with the activations in registers and the chain's weights in LDS, no barrier
+        // between layers (329 against 495 us at 512 chains of the nn_example model, 48 against 71 at 64; 24 against 14 at 8)
+        const int splits = nc >= ctx->num_cu ? 1 : std::min(8, (ctx->num_cu + nc - 1) / nc);
+        SI_HIP(ctx, hipModuleLaunchKernel(sk->stack, (unsigned)splits, (unsigned)nc, 1, 512, 1, 1,
+                                          (unsigned)((size_t)sk->wvec_doubles * sizeof(double)), ctx->stream, args, nullptr));
+      } else {
+        SI_HIP(ctx, hipModuleLaunchKernel(sk->fused, (unsigned)((B + 16 * nb - 1) / (16 * nb)), (unsigned)nc, 1, 256, 1, 1,
+                                          (unsigned)((size_t)sk->lds_doubles * sizeof(double)), ctx->stream, args, nullptr));
       }
-      {
-        ProfScope ps(ctx, SI_K_SSE, 3.0 * (double)d * dn, 16.0 * (double)d * dn);
-        launch_sse(ctx->stream, ctx->d_yhat, ctx->d_Y, d, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse + c0, nc, d, !ctx->defer_sse_final);
-      }
-      SI_HIP(ctx, hipGetLastError());
-      return SI_OK;
+    } else {
+      launch_chain_fused(ctx->stream, fp, nb, wave_tiles, lds, ctx->d_w, ldw, v.X, v.yhat, d, nc);
     }
   }
-  // the per-layer launches (dense_forward), nc chain slots per launch, outputs ping-pong.  compute_dtype = SI_F32 runs them on the
-  // fp32 matrix instruction (kernels_gemm_f32.hip): K4 has left W_swa + P z in d_w (fp64) AND rounded once in d_w32; X32 /
-  // activations are fp32; the narrow head's partial sums, the last bias + activation (tail_sse_kernel) and the sum of squared
-  // errors are fp64 -- the precision option of SURVEY section 0 Q6 on the same reference lines, src/space_inference.jl:92-94
-  const int slots = ctx->f32 ? ctx->fuse_slots32 : ctx->fuse_slots;
+  {
+    ProfScope ps(ctx, SI_K_SSE, 3.0 * (double)d * dn, 16.0 * (double)d * dn);
+    launch_sse(ctx->stream, v.yhat, v.Y, d, v.ssepart, v.sse_blocks, ctx->d_sse + c0, nc, d, !v.defer_sse_final);
+  }
+  SI_HIP(ctx, hipGetLastError());
+  return SI_OK;
+}
+
+// The per-layer launches (dense_forward), nc chain slots per launch, outputs ping-pong.  compute_dtype = SI_F32 runs them on the
+// fp32 matrix instruction (kernels_gemm_f32.hip): K4 has left W_swa + P z in d_w (fp64) AND rounded once in d_w32; X32 /
+// activations are fp32; the narrow head's partial sums, the last bias + activation (tail_sse_kernel) and the sum of squared
+// errors are fp64 -- the precision option of SURVEY section 0 Q6 on the same reference lines, src/space_inference.jl:92-94
+static int32_t density_layers(si_ctx* ctx, const DensityView& v, int c0, int nc, const double** yhat_out) {
+  const int64_t B = v.B, ldw = pad_ld(ctx->iN);
+  const int slots = v.f32 ? ctx->fuse_slots32 : ctx->fuse_slots;
   ChainBatch cb;
   cb.n = nc;
   cb.w = ldw;
-  cb.hout = ctx->act_elems;
+  cb.hout = v.act_elems;
   cb.part = (int64_t)slots * ctx->out_dim * B;
-  const double* yh = ctx->d_yhat;
-  double* yhat = yhat_out ? ctx->d_yhat.get() : nullptr;
-  if (ctx->f32) {
-    const DenseForward<float> fw{ctx->layers.data(), ctx->layers.size(), ctx->fuse_tail, ctx->d_w32, ctx->d_w, ctx->d_X32, ctx->d_Y, B, nullptr,
-                                 {ctx->d_act32[0], ctx->d_act32[1]}, cb, slots, ctx->d_part, yhat, ctx->d_ssepart, ctx->sse_blocks,
-                                 ctx->d_sse + c0, ctx->defer_sse_final, ctx->main_layer, true};
+  const double* yh = v.yhat;
+  double* yhat = yhat_out ? v.yhat : nullptr;
+  if (v.f32) {
+    const DenseForward<float> fw{ctx->layers.data(), ctx->layers.size(), ctx->fuse_tail, ctx->d_w32, ctx->d_w, v.X32, v.Y, B, nullptr,
+                                 {v.act32[0], v.act32[1]}, cb, slots, v.part, yhat, v.ssepart, v.sse_blocks,
+                                 ctx->d_sse + c0, v.defer_sse_final, ctx->main_layer, true};
     dense_forward(ctx, ctx->stream, fw);
   } else {
-    const DenseForward<double> fw{ctx->layers.data(), ctx->layers.size(), ctx->fuse_tail, ctx->d_w, ctx->d_w, ctx->d_X, ctx->d_Y, B, nullptr,
-                                  {ctx->d_act[0], ctx->d_act[1]}, cb, slots, ctx->d_part, yhat, ctx->d_ssepart, ctx->sse_blocks,
-                                  ctx->d_sse + c0, ctx->defer_sse_final, ctx->main_layer, true};
+    const DenseForward<double> fw{ctx->layers.data(), ctx->layers.size(), ctx->fuse_tail, ctx->d_w, ctx->d_w, v.X, v.Y, B, nullptr,
+                                  {v.act[0], v.act[1]}, cb, slots, v.part, yhat, v.ssepart, v.sse_blocks,
+                                  ctx->d_sse + c0, v.defer_sse_final, ctx->main_layer, true};
     const double* h = dense_forward(ctx, ctx->stream, fw);
     if (!ctx->fuse_tail) yh = h;   // without the fused tail the outputs stay in the last activation buffer
   }
@@ -399,11 +395,36 @@ int32_t eval_density(si_ctx* ctx, int c0, int nc, const double** yhat_out) {
   return SI_OK;
 }
 
+// density evaluations for chain slots [c0, c0 + nc), nc <= fw_slots, in ONE pass of launches:
+// d_zprop[:, c] -> d_sse[c]; optionally leaves the model outputs at *yhat_out (slot j at + j * out_dim*B after the fused
+// tail, at + j * act_elems otherwise)
+int32_t eval_density(si_ctx* ctx, const DensityView& v, int c0, int nc, const double** yhat_out) {
+  ctx->last_density_spec = 0;   // (si_chain_kernel_info reports the last evaluation)
+  const int64_t N = ctx->iN, ldw = pad_ld(N);
+  const int32_t M = ctx->iM;
+  const double dn = (double)nc;
+  {
+    ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * dn, (double)N * (M + 1 + dn) * 8.0);
+    launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, ctx->d_zprop + (size_t)c0 * M, nc, ctx->d_w, ldw,
+                       ctx->num_cu, v.f32 ? ctx->d_w32.get() : nullptr, ldw);
+  }
+  if (ctx->sigma_p > 0.0)  // ||new_W||^2 per chain for the optional prior term (same fixed-order reduction as the SSE)
+    launch_sse(ctx->stream, ctx->d_w, nullptr, N, ctx->d_wsqpart, ctx->wsq_blocks, ctx->d_wsq + c0, nc, ldw);
+  if (ctx->plan.has_conv)
+    return v.f32 ? density_net<float>(ctx, v, ctx->d_w32, v.X32, v.act32, ctx->d_wpack32, c0, yhat_out)
+                 : density_net<double>(ctx, v, ctx->d_w, ctx->plan.input_spatial ? v.Xc : v.X, v.act, ctx->d_wpack, c0, yhat_out);
+  if (ctx->fused_ok && ctx->chain_mode != 0 && !yhat_out) {   // (never with compute_dtype = SI_F32: fused_chain_class)
+    const int32_t rc = density_fused(ctx, v, c0, nc);
+    if (rc != SI_NOT_TAKEN) return rc;
+  }
+  return density_layers(ctx, v, c0, nc, yhat_out);
+}
+
 // all C chain slots, fw_slots at a time
-int32_t eval_density_all(si_ctx* ctx, int C) {
+int32_t eval_density_all(si_ctx* ctx, const DensityView& v, int C) {
   const int w = std::max(1, ctx->fw_slots);
   for (int c0 = 0; c0 < C; c0 += w) {
-    const int32_t rc = eval_density(ctx, c0, std::min(w, C - c0), nullptr);
+    const int32_t rc = eval_density(ctx, v, c0, std::min(w, C - c0), nullptr);
     if (rc != SI_OK) return rc;
   }
   return SI_OK;
@@ -416,6 +437,14 @@ double mvnormal_c0(double d, double sigma) {
 
 // log N(w; 0, sigma_p^2 I) = c0p - ||w||^2 / (2 sigma_p^2): the term the reference writes AFTER its `return` (Q4)
 double prior_c0(const si_ctx* ctx) { return ctx->sigma_p > 0.0 ? mvnormal_c0((double)ctx->iN, ctx->sigma_p) : 0.0; }
+
+// the value of the log-density from the device's sums, as the host forms it: lp = c0 - (sse / s2) / 2 [+ prior_c0 - (wsq / sp2) / 2]
+static double lp_from_sums(const si_ctx* ctx, double sse, double wsq) {
+  const double c0 = mvnormal_c0((double)ctx->out_dim * (double)ctx->B, ctx->sigma_m), s2 = ctx->sigma_m * ctx->sigma_m;
+  double lp = c0 - (sse / s2) / 2.0;
+  if (ctx->sigma_p > 0.0) lp += prior_c0(ctx) - (wsq / (ctx->sigma_p * ctx->sigma_p)) / 2.0;
+  return lp;
+}
 
 int32_t si_infer_set_prior(si_ctx* ctx, double sigma_p) {
   CHECK_CTX(ctx);
@@ -435,18 +464,13 @@ int32_t si_logdensity(si_ctx* ctx, const double* Z, int32_t C, double* lp_out) {
   int32_t rc = ensure_chains(ctx, C);
   if (rc != SI_OK) return rc;
   SI_HIP(ctx, hipMemcpyAsync(ctx->d_zprop, Z, (size_t)ctx->iM * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = eval_density_all(ctx, C)) != SI_OK) return rc;
+  if ((rc = eval_density_all(ctx, setup_view(ctx), C)) != SI_OK) return rc;
   std::vector<double> sse((size_t)C), wsq((size_t)C, 0.0);
   SI_HIP(ctx, hipMemcpyAsync(sse.data(), ctx->d_sse, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (ctx->sigma_p > 0.0)
     SI_HIP(ctx, hipMemcpyAsync(wsq.data(), ctx->d_wsq, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const double d = (double)ctx->out_dim * (double)ctx->B;
-  const double c0 = mvnormal_c0(d, ctx->sigma_m), s2 = ctx->sigma_m * ctx->sigma_m;
-  for (int c = 0; c < C; ++c) {
-    lp_out[c] = c0 - (sse[(size_t)c] / s2) / 2.0;
-    if (ctx->sigma_p > 0.0) lp_out[c] += prior_c0(ctx) - (wsq[(size_t)c] / (ctx->sigma_p * ctx->sigma_p)) / 2.0;
-  }
+  for (int c = 0; c < C; ++c) lp_out[c] = lp_from_sums(ctx, sse[(size_t)c], wsq[(size_t)c]);
   return SI_OK;
 }
 
@@ -565,9 +589,7 @@ static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_ou
   SI_HIP(ctx, hipMemcpyAsync(grad_out, ctx->d_gz, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (prior) SI_HIP(ctx, hipMemcpyAsync(&wsq, ctx->d_wsq, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const int64_t d = (int64_t)ctx->out_dim * B;
-  *lp_out = mvnormal_c0((double)d, ctx->sigma_m) - (sse / s2) / 2.0;
-  if (prior) *lp_out += prior_c0(ctx) - (wsq / (ctx->sigma_p * ctx->sigma_p)) / 2.0;
+  *lp_out = lp_from_sums(ctx, sse, wsq);
   return SI_OK;
 }
 
@@ -786,7 +808,7 @@ int32_t si_forward(si_ctx* ctx, const double* z, double* Yhat_out) {
   if (rc != SI_OK) return rc;
   SI_HIP(ctx, hipMemcpyAsync(ctx->d_zprop, z, (size_t)ctx->iM * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   const double* yh = nullptr;
-  if ((rc = eval_density(ctx, 0, 1, &yh)) != SI_OK) return rc;
+  if ((rc = eval_density(ctx, setup_view(ctx), 0, 1, &yh)) != SI_OK) return rc;
   SI_HIP(ctx, hipMemcpyAsync(Yhat_out, yh, (size_t)ctx->out_dim * ctx->B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SI_OK;
@@ -801,42 +823,33 @@ int32_t si_predict(si_ctx* ctx, const double* Z, int32_t C, const double* Xnew, 
   int32_t rc = ensure_chains(ctx, C);
   if (rc != SI_OK) return rc;
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  // run the ordinary forward path on temporary data buffers sized for Bn (the density's own X, Y stay untouched);
+  // run the ordinary forward path on temporary data buffers sized for Bn, through a view of its own: the context is only read;
   // like the density, up to `wb` samples share one pass of launches (grid.y), within the same workspace cap
-  const int64_t B_saved = ctx->B, act_elems_saved = ctx->act_elems;
-  const int sse_blocks_saved = ctx->sse_blocks;
   // (with compute_dtype = SI_F32 the predictive forward still runs in fp64: it owns its fp64 workspace below, and the fp64
   //  weights are what K4 writes in either mode -- the fp32 option covers the density / the RWMH samplers)
-  const bool f32_saved = ctx->f32;
-  ctx->f32 = false;
-  const int64_t act_elems = pad_ld(ctx->max_stored * Bn);   // (eval_density with yhat_out set never takes the fused launch)
+  const int64_t act_elems = pad_ld(ctx->max_stored * Bn);
   const int sse_blocks = sse_num_blocks((int64_t)ctx->out_dim * Bn, ctx->num_cu);
   const size_t dB = (size_t)ctx->out_dim * (size_t)Bn;
   const double per = 8.0 * (2.0 * (double)act_elems + ((double)ctx->fuse_slots + 1.0) * (double)dB + (double)sse_blocks);
   const size_t wb = (size_t)std::max(1.0, std::min({(double)C, (double)ctx->fw_slots, std::floor(SI_BATCH_BYTES / per)}));
-  DevBuf<double> tX, tY, tA0, tA1, tS, tP, tYh, tXc;
-  // the temporaries and the density's own buffers change places for the evaluations, and change back
-  auto exchange = [&]() {
-    std::swap(ctx->d_X, tX); std::swap(ctx->d_Y, tY); std::swap(ctx->d_act[0], tA0); std::swap(ctx->d_act[1], tA1);
-    std::swap(ctx->d_ssepart, tS); std::swap(ctx->d_part, tP); std::swap(ctx->d_yhat, tYh); std::swap(ctx->d_Xc, tXc);
-  };
+  DevBuf<double> tX, tY, tA[2], tS, tP, tYh, tXc;
   bool ok = tX.alloc((size_t)ctx->in_dim * Bn) && tY.alloc(dB) &&
             (!ctx->plan.input_spatial || tXc.alloc((size_t)ctx->plan.in_elems * Bn)) &&
-            tA0.alloc(wb * (size_t)act_elems) && tA1.alloc(wb * (size_t)act_elems) && tS.alloc(wb * (size_t)sse_blocks) &&
+            tA[0].alloc(wb * (size_t)act_elems) && tA[1].alloc(wb * (size_t)act_elems) && tS.alloc(wb * (size_t)sse_blocks) &&
             (!ctx->fuse_tail || (tP.alloc(wb * (size_t)ctx->fuse_slots * dB) && tYh.alloc(wb * dB)));
   hipError_t e = hipSuccess;
   if (ok) {
+    const DensityView v{tX, tXc, nullptr, tY, Bn, tA, nullptr, tS, sse_blocks, tP, tYh, act_elems, /*f32=*/false,
+                        /*defer_sse_final=*/false, /*is_setup_data=*/false};
     e = hipMemcpyAsync(tX, Xnew, (size_t)ctx->in_dim * Bn * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(tY, 0, dB * sizeof(double), ctx->stream);
     if (e == hipSuccess)
       e = hipMemcpyAsync(ctx->d_zprop, Z, (size_t)ctx->iM * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    exchange();
-    ctx->B = Bn; ctx->act_elems = act_elems; ctx->sse_blocks = sse_blocks;
-    if (ctx->plan.input_spatial) net_input(ctx, ctx->plan, ctx->d_X, ctx->d_Xc, Bn);
+    if (ctx->plan.input_spatial) net_input(ctx, ctx->plan, tX, tXc, Bn);
     for (int c0 = 0; c0 < C && e == hipSuccess && rc == SI_OK; c0 += (int)wb) {
       const int nc = std::min<int>((int)wb, C - c0);
       const double* yh = nullptr;
-      rc = eval_density(ctx, c0, nc, &yh);
+      rc = eval_density(ctx, v, c0, nc, &yh);
       if (rc == SI_OK) {
         // sample j of the batch: yh + j * (out_dim*Bn) after the fused tail, yh + j * act_elems otherwise
         const size_t src_pitch = (ctx->fuse_tail ? dB : (size_t)act_elems) * sizeof(double);
@@ -845,12 +858,9 @@ int32_t si_predict(si_ctx* ctx, const double* Z, int32_t C, const double* Xnew, 
       }
       if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the outputs are overwritten by the next batch
     }
-    exchange();
-    ctx->B = B_saved; ctx->act_elems = act_elems_saved; ctx->sse_blocks = sse_blocks_saved;
   }
-  ctx->f32 = f32_saved;
   (void)hipStreamSynchronize(ctx->stream);
-  for (DevBuf<double>* b : {&tX, &tY, &tA0, &tA1, &tS, &tP, &tYh, &tXc}) b->reset();
+  for (DevBuf<double>* b : {&tX, &tY, &tA[0], &tA[1], &tS, &tP, &tYh, &tXc}) b->reset();
   if (!ok) return fail(ctx, SI_ERR_NOMEM, "si_predict: device allocation failed");
   if (rc != SI_OK) return rc;
   if (e != hipSuccess) return fail(ctx, SI_ERR_HIP, std::string("si_predict: ") + hipGetErrorString(e));

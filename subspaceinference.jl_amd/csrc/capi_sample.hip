@@ -1,7 +1,10 @@
 // C ABI, sampling side: the RWMH samplers (si_sample_rwmh*, the step-wise session si_rwmh_*), the output map
 // (si_sample_rwmh_weights, si_reconstruct) -- reference src/space_inference.jl:111-116,125.  Three sampler forms behind one
-// entry point: the one-workgroup device-resident loop (kernels_chain.hip), the persistent grid loop (kernels_chain_grid.hip)
-// and the launch-per-step loop.  Host-side orchestration only; no CPU fallback anywhere in this file.
+// entry point, one function each, tried in this order: the one-workgroup device-resident loop (rwmh_one_workgroup,
+// kernels_chain.hip), the persistent grid loop (rwmh_grid, kernels_chain_grid.hip; prepare_spec_loop readies its run-time
+// specialised variant) and the launch-per-step loop (rwmh_per_step, with WeightRing for the streamed output map).
+// sample_rwmh_impl checks and reserves once and hands them an RwmhCall; finish_chains is their common end.  Host-side
+// orchestration only; no CPU fallback anywhere in this file.
 #include <cstring>
 
 #include "capi_common.h"
@@ -105,6 +108,272 @@ static int32_t finish_chains(si_ctx* ctx, const char* who, hipError_t e, int64_t
   return SI_OK;
 }
 
+// One si_sample_rwmh* call, as sample_rwmh_impl hands it to the sampler forms: the arguments, and what the entry has checked,
+// reserved (ensure_chains / ensure_wstream, d_outZ / d_outlp) and worked out once.
+struct RwmhCall {
+  const char* who;
+  int64_t itr;
+  double sigma_z;
+  uint64_t seed;
+  int32_t chain_id0, C;
+  double *Z_out, *lp_out, *accept_rate_out, *W_out;
+  double c0, s2;
+  size_t wall_elems;   // ldw * itr * C: the output map of the whole call
+  bool map_fits;       // no output map asked for, or one within the 512 MB that finish_chains writes in ONE K4 pass: the loops' gate
+};
+
+// the fields that the argument structs of the three device-resident kernels share (a template: C++ linkage inside this block)
+extern "C++" template <typename Args>
+static void fill_common_args(Args& a, const si_ctx* ctx, const RwmhCall& k) {
+  a.swa = ctx->i_swa; a.P = ctx->i_P; a.X = ctx->d_X; a.Y = ctx->d_Y;
+  a.Z_out = ctx->d_outZ; a.lp_out = ctx->d_outlp; a.nacc_out = reinterpret_cast<decltype(a.nacc_out)>(ctx->d_nacc.get());
+  a.ldP = ctx->ldP; a.itr = k.itr; a.seed = k.seed; a.sigma_z = k.sigma_z; a.c0 = k.c0; a.sigma2 = k.s2;
+  a.N = (int)ctx->iN; a.chain_id0 = k.chain_id0;
+}
+
+// ---- K6 as a device-resident loop (kernels_chain.hip): small Dense chains whose weights, data and activations fit one
+// workgroup's LDS run ALL transitions in one launch, one workgroup per chain -- the launch-per-step loop below costs ~8
+// dependent launches (25 us) per transition whatever the size.  Same bits (tests/test_gpu_chain.py).
+// (with the output map requested -- what the drop-in sub_inference call does -- the weight samples of the finished chains
+//  come from ONE K4 pass over all itr * C samples, the kernel si_reconstruct runs: same bits, no streaming needed at this size)
+static int32_t rwmh_one_workgroup(si_ctx* ctx, const RwmhCall& k) {
+  if (!k.map_fits || !chain_loop_applies(ctx) || ctx->chain_mode != 1) return SI_NOT_TAKEN;
+  ChainLoopArgs a{};
+  const int L = (int)ctx->layers.size();
+  for (int l = 0; l < L; ++l) a.lay[l] = ctx->layers[(size_t)l];
+  fill_common_args(a, ctx, k);
+  a.M = ctx->iM; a.B = (int)ctx->B; a.L = L;
+  a.slot_feats = dense_fused_slot_feats(ctx->layers[(size_t)L - 2].out);
+  a.fuse_slots = ctx->fuse_slots;
+  const size_t lds = chain_loop_plan(a, SI_CHAIN_LDS_LIMIT);
+  if (lds == 0) return SI_NOT_TAKEN;
+  {
+    const double fl = 2.0 * (double)ctx->iN * (double)ctx->B * (double)k.itr * k.C;
+    ProfScope ps(ctx, SI_K_RWMH, fl, 0.0);
+    launch_chain_loop(ctx->stream, a, k.C, lds);
+  }
+  return finish_chains(ctx, k.who, hipGetLastError(), k.itr, k.C, k.Z_out, k.lp_out, k.accept_rate_out, k.W_out, k.wall_elems, nullptr, nullptr);
+}
+
+// The grid loop specialised to this chain's shapes (chain_spec.inc through hiprtc; same bits): ONE barrier per transition, the
+// weights handed over in fragment order.  Class: a narrow head, at most 1024 model outputs (four blocks of the SSE tree),
+// every weight fragment in registers (spec_applies).  Lays out its LDS behind the images of the forward (sa, *lds_spec), keeps
+// d_specw / d_specy for C chains and the fragment-order permutation of these kernels.  Returns the kernels, or null with *rc
+// SI_OK (not of the class: the generic loop runs) or the call's error.
+static const SpecKernels* prepare_spec_loop(si_ctx* ctx, const RwmhCall& k, int G, int nb, int sf, SiSpecGridArgs& sa, size_t* lds_spec,
+                                            int32_t* rc) {
+  const int32_t C = k.C, M = ctx->iM;
+  const int64_t N = ctx->iN, d = (int64_t)ctx->out_dim * ctx->B;
+  *rc = SI_OK;
+  auto bad = [&](int32_t code, const char* what) {
+    *rc = fail(ctx, code, std::string(k.who) + what);
+    return (const SpecKernels*)nullptr;
+  };
+  if (!ctx->chain_spec || !ctx->fuse_tail || d > 1024 || M > 256) return nullptr;
+  const int rs = (int)((((N + G - 1) / G) + 15) & ~(int64_t)15);
+  const SpecKernels* sk = spec_kernels(ctx->layers.data(), (int)ctx->layers.size(), nb, sf, M, rs <= 256 && M <= 32, &ctx->spec_message);
+  if (!sk) return nullptr;
+  auto even = [](int64_t v) { return (v + 1) & ~(int64_t)1; };
+  int64_t off = sk->lds_doubles;
+  sa.y_in_lds = 1;
+  sa.o_y = (int)off;
+  off += even(d);
+  sa.o_blk = (int)off;
+  off += even(ctx->sse_blocks);
+  sa.o_z = (int)off;
+  off += even(5 * (int64_t)M);
+  sa.o_red = (int)off;
+  off += 24;
+  sa.o_flag = (int)off;
+  off += 2;
+  *lds_spec = std::max((size_t)off * sizeof(double), (size_t)(81 * 1024));   // (more than half a CU's LDS: one workgroup per CU)
+  if (*lds_spec > (size_t)160 * 1024 - 256) return nullptr;
+  if (ctx->spec_chains < C || ctx->spec_fo != sk->fo_total) {
+    ctx->d_specw.reset();
+    ctx->d_specy.reset();
+    ctx->spec_chains = 0;
+    if (!ctx->d_specw.alloc((size_t)4 * (size_t)sk->fo_total * (size_t)C) || !ctx->d_specy.alloc((size_t)2 * (size_t)d * (size_t)C))
+      return bad(SI_ERR_NOMEM, ": allocation failed");
+    // (the padding elements of the fragment-ordered vectors are never written by K4: they must be finite)
+    if (hipMemsetAsync(ctx->d_specw, 0, (size_t)4 * (size_t)sk->fo_total * (size_t)C * sizeof(double), ctx->stream) != hipSuccess)
+      return bad(SI_ERR_HIP, ": hipMemsetAsync failed");
+    ctx->spec_chains = C;
+    ctx->spec_fo = sk->fo_total;
+  }
+  if (ctx->specperm_for != (const void*)sk) {
+    ctx->specperm_for = nullptr;
+    if (!ctx->d_specperm.alloc((size_t)N)) return bad(SI_ERR_NOMEM, ": allocation failed");
+    int* pp = ctx->d_specperm;
+    void* pargs[] = {&pp};
+    if (hipModuleLaunchKernel(sk->perm, (unsigned)((sk->max_wn + 255) / 256), 1, 1, 256, 1, 1, 0, ctx->stream, pargs, nullptr) != hipSuccess)
+      return bad(SI_ERR_HIP, ": launch of the fragment-order permutation failed");
+    ctx->specperm_for = (const void*)sk;
+  }
+  return sk;
+}
+
+// ---- K6 as a persistent loop over a GRID of workgroups (kernels_chain_grid.hip): a narrow chain too large for one
+// workgroup (docs/src/nn_example.md's MLP) runs all transitions in one launch, G = ceil(B / tile) resident workgroups per
+// chain, two bounded grid barriers per transition.  Same bits as the launch-per-step loop (tests/test_gpu_chain_grid.py).
+static int32_t rwmh_grid(si_ctx* ctx, const RwmhCall& k) {
+  const int32_t C = k.C, M = ctx->iM;
+  if (!k.map_fits || !ctx->fused_ok || ctx->chain_mode != 1 || ctx->sigma_p > 0.0 || C > ctx->fw_slots || k.itr >= ((int64_t)1 << 24))
+    return SI_NOT_TAKEN;
+  ChainGridArgs a{};
+  const int L = (int)ctx->layers.size();
+  const int sf = ctx->fuse_tail ? dense_fused_slot_feats(ctx->layers[(size_t)L - 2].out) : 0;
+  int nb = 0;
+  size_t lds = 0;
+  for (int cand : {1, 2, 4}) {   // the smallest tile whose grid is resident: one workgroup per CU
+    const int64_t G = (ctx->B + 16 * cand - 1) / (16 * cand);
+    if (G * C > ctx->num_cu) continue;
+    const size_t lf = chain_fused_plan(a.p, ctx->layers.data(), L, ctx->B, cand, ctx->fuse_tail, sf, ctx->fuse_slots);
+    fused_fill_program(ctx, a.p);
+    a.M = M;
+    a.nblocks = ctx->sse_blocks;
+    a.G = (int)G;
+    lds = chain_grid_plan(a, lf);
+    if (lds != 0) {
+      nb = cand;
+      break;
+    }
+  }
+  if (nb == 0) return SI_NOT_TAKEN;
+  SiSpecGridArgs sa{};
+  size_t lds_spec = 0;
+  int32_t rc = SI_OK;
+  const SpecKernels* sk = prepare_spec_loop(ctx, k, a.G, nb, sf, sa, &lds_spec, &rc);
+  if (rc != SI_OK) return rc;
+  const size_t sync_lines = sk ? (size_t)8 * (size_t)C + 1 : (size_t)C + 1;   // (the specialised loop shards each chain's counter over 8 lines)
+  if (!ctx->d_gridsync.reserve((size_t)32 * sync_lines)) return fail(ctx, SI_ERR_NOMEM, std::string(k.who) + ": allocation failed");
+  fill_common_args(a, ctx, k);
+  a.wbuf = ctx->d_w; a.w_stride = pad_ld(ctx->iN);
+  a.ybuf = ctx->d_yhat; a.y_stride = (int64_t)ctx->out_dim * ctx->B;
+  a.cnt = ctx->d_gridsync; a.status = ctx->d_gridsync + (size_t)32 * (sync_lines - 1);
+  hipError_t e = hipMemsetAsync(ctx->d_gridsync, 0, (size_t)32 * sync_lines * sizeof(unsigned), ctx->stream);
+  if (e == hipSuccess) {
+    const double fl = 2.0 * (double)ctx->iN * (double)ctx->B * (double)k.itr * C;
+    ProfScope ps(ctx, SI_K_RWMH, fl, 0.0);
+    if (sk) {
+      fill_common_args(sa, ctx, k);
+      sa.perm = ctx->d_specperm;
+      sa.wbuf = ctx->d_specw; sa.w_stride = sk->fo_total;
+      sa.ybuf = ctx->d_specy; sa.y_stride = a.y_stride;
+      sa.cnt = a.cnt; sa.status = a.status;
+      sa.M = M; sa.G = a.G; sa.B = (int)ctx->B; sa.nblocks = ctx->sse_blocks;
+      void* gargs[] = {&sa};
+      e = hipModuleLaunchKernel(sk->grid, (unsigned)(a.G * C), 1, 1, 256, 1, 1, (unsigned)lds_spec, ctx->stream, gargs, nullptr);
+      ctx->last_loop_spec = e == hipSuccess;
+    } else {
+      e = launch_chain_grid(ctx->stream, a, nb, C, lds);
+    }
+  }
+  unsigned status = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&status, a.status, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
+  // the samples and lp go through pinned staging: a device-to-host copy straight into the caller's array pins its pages on the
+  // fly, and for an array nobody has touched yet (np.empty, Matrix{Float64}(undef, ...)) that costs ~9 us per page -- 7 ms for the
+  // 3.4 MB of a 20 000-transition chain, 0.35 us per transition of a 9.8 us loop
+  const size_t zbytes = k.Z_out ? (size_t)M * k.itr * C * sizeof(double) : 0, lbytes = k.lp_out ? (size_t)k.itr * C * sizeof(double) : 0;
+  const bool staged = zbytes + lbytes >= ((size_t)128 << 10) && zbytes + lbytes <= ((size_t)128 << 20) &&
+                      ctx->h_outpin.reserve(zbytes + lbytes);   // (the direct copy is always possible)
+  return finish_chains(ctx, k.who, e, k.itr, C, k.Z_out, k.lp_out, k.accept_rate_out, k.W_out, k.wall_elems,
+                       staged ? ctx->h_outpin.get() : nullptr, &status);
+}
+
+// The streamed output map of the launch-per-step loop (the note at the top of this file): after transition t, push(t) puts the
+// chains' current weights into ring slot t -- K4's own output where the proposal was accepted, the previous slot otherwise --
+// and queues its DMA into pinned memory on the second stream; the host moves sample t - (R - 1) into the caller's array meanwhile.
+struct WeightRing {
+  si_ctx* ctx;
+  const RwmhCall& k;
+  bool select_path;   // the proposal weights of ALL chains are still in d_w at accept time: one pass of launches carries them all
+  double* slot(int64_t t) const { return ctx->d_wring + (size_t)(t % SI_WRING) * (size_t)k.C * (size_t)pad_ld(ctx->iN); }
+  hipError_t drain(int64_t u) const {   // sample u of every chain: pinned slot -> the caller's (pageable) N x itr x C array
+    const int64_t N = ctx->iN;
+    const int r = (int)(u % SI_WRING);
+    hipError_t w = hipEventSynchronize(ctx->ev_wcopy[r]);
+    for (int c = 0; c < k.C && w == hipSuccess; ++c)
+      host_copy(k.W_out + (size_t)N * ((size_t)u + (size_t)k.itr * c), ctx->h_wring[r] + (size_t)c * N, (size_t)N * sizeof(double));
+    return w;
+  }
+  hipError_t push(int64_t t) const {
+    const int64_t N = ctx->iN, ldw = pad_ld(N);
+    const int32_t C = k.C;
+    const int r = (int)(t % SI_WRING);
+    hipError_t e = hipSuccess;
+    if (t >= SI_WRING) e = hipStreamWaitEvent(ctx->stream, ctx->ev_wcopy[r], 0);  // the DMA of sample t - R has read this slot
+    if (e != hipSuccess) return e;
+    {
+      ProfScope ps(ctx, SI_K_RECON, 0.0, 16.0 * (double)N * C);
+      if (select_path)
+        launch_weights_select(ctx->stream, ctx->d_accflag, ctx->d_w, ldw, t > 0 ? slot(t - 1) : nullptr, slot(t), ldw, N, C, ctx->num_cu);
+      else  // more chains than one pass of launches carries: K4 on the current states (same kernel, same bits)
+        launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, ctx->iM, ctx->d_zcur, C, slot(t), ldw, ctx->num_cu);
+    }
+    e = hipEventRecord(ctx->ev_wcomp[r], ctx->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream2, ctx->ev_wcomp[r], 0);
+    if (e == hipSuccess)
+      e = hipMemcpy2DAsync(ctx->h_wring[r], (size_t)N * sizeof(double), slot(t), (size_t)ldw * sizeof(double), (size_t)N * sizeof(double),
+                           (size_t)C, hipMemcpyDeviceToHost, ctx->stream2);
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev_wcopy[r], ctx->stream2);
+    if (e == hipSuccess && t >= SI_WRING - 1) e = drain(t - (SI_WRING - 1));   // frees the pinned slot sample t + 1 will use
+    return e;
+  }
+};
+
+// ---- the launch-per-step loop: every chain the two loops above do not take.  One transition for all chains per pass; the
+// transition index is a device-side counter, so the launches are identical.  When one pass of launches carries all chains (and
+// the prior term is off) the tail of a transition is ONE launch: the last stage of the SSE reduction, the accept step and the
+// next transition's proposal (rwmh_tail_kernel) -- same functions, same order, same bits; otherwise sse_final / accept / propose
+// stay separate kernels.
+// Replaying one captured transition as a hipGraph was measured and dropped: the README-toy transition takes 27.8 us graphed vs
+// 25.7 us eager -- it is bound by the serial latency of its 8 dependent small kernels, not by host launches -- and at cfg2 a
+// transition is 3.3 ms of kernel time.
+static int32_t rwmh_per_step(si_ctx* ctx, const RwmhCall& k) {
+  const int32_t C = k.C, M = ctx->iM;
+  double* const dZ = ctx->d_outZ;
+  double* const dlp = ctx->d_outlp;
+  {
+    ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+    launch_rwmh_init(ctx->stream, ctx->d_zcur, ctx->d_lpcur, ctx->d_nacc, ctx->d_steps, M, C);
+  }
+  const WeightRing ring{ctx, k, k.W_out && C <= ctx->fw_slots};
+  int* const accflag = ring.select_path ? ctx->d_accflag.get() : nullptr;
+  const bool fused_tail = C <= ctx->fw_slots && !(ctx->sigma_p > 0.0) && ctx->chain_loop_enabled;
+  const DensityView view = setup_view(ctx, /*defer_sse_final=*/fused_tail);   // the tail kernel sums the SSE block partials
+  int32_t rc = SI_OK;
+  hipError_t e = hipSuccess;
+  for (int64_t t = 0; t < k.itr && rc == SI_OK && e == hipSuccess; ++t) {
+    if (!fused_tail || t == 0) {
+      ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+      launch_rwmh_propose(ctx->stream, ctx->d_zcur, ctx->d_zprop, M, C, k.sigma_z, k.seed, k.chain_id0, ctx->d_steps);
+    }
+    if ((rc = eval_density_all(ctx, view, C)) != SI_OK) break;
+    {
+      ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+      if (fused_tail)
+        launch_rwmh_tail(ctx->stream, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse, ctx->d_zcur, ctx->d_zprop, ctx->d_lpcur, ctx->d_nacc, M,
+                         C, k.c0, k.s2, k.sigma_z, k.seed, k.chain_id0, ctx->d_steps, dZ, dlp, k.itr, accflag, t + 1 < k.itr);
+      else
+        launch_rwmh_accept(ctx->stream, ctx->d_zcur, ctx->d_zprop, ctx->d_lpcur, ctx->d_sse, ctx->d_nacc, M, C, k.c0, k.s2, k.seed,
+                           k.chain_id0, ctx->d_steps, dZ, dlp, k.itr, ctx->sigma_p > 0.0 ? ctx->d_wsq.get() : nullptr, prior_c0(ctx),
+                           ctx->sigma_p * ctx->sigma_p, accflag);
+    }
+    if (k.W_out) e = ring.push(t);
+  }
+  if (rc == SI_OK && e == hipSuccess && k.W_out)   // the samples no later push has drained
+    for (int64_t u = std::max<int64_t>(0, k.itr - (SI_WRING - 1)); u < k.itr && e == hipSuccess; ++u) e = ring.drain(u);
+  if (k.W_out) (void)hipStreamSynchronize(ctx->stream2);
+  if (rc != SI_OK || e != hipSuccess) {
+    (void)hipStreamSynchronize(ctx->stream);
+    if (rc != SI_OK) return rc;
+    return fail(ctx, SI_ERR_HIP, std::string(k.who) + ": " + hipGetErrorString(e));
+  }
+  return finish_chains(ctx, k.who, hipGetLastError(), k.itr, C, k.Z_out, k.lp_out, k.accept_rate_out, nullptr, 0, nullptr, nullptr);
+}
+
+// The entry of si_sample_rwmh / si_sample_rwmh_weights: checks, the chains' state and the output arrays, then the three forms in
+// this order -- the first that applies runs the call; finish_chains is their common end.
 static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, double sigma_z, uint64_t seed, int32_t chain_id0,
                                 int32_t nchains, double* Z_out, double* lp_out, double* accept_rate_out, double* W_out) {
   CHECK_CTX(ctx);
@@ -114,234 +383,20 @@ static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, doubl
     return fail(ctx, SI_ERR_INVALID, std::string(who) + ": itr, nchains, sigma_z must be positive");
   if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, std::string(who) + ": a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
   BIND(ctx);
-  const int32_t C = nchains, M = ctx->iM;
-  const int64_t N = ctx->iN, ldw = pad_ld(N);
+  const int32_t C = nchains;
   int32_t rc = ensure_chains(ctx, C);
   if (rc != SI_OK) return rc;
   if (W_out && (rc = ensure_wstream(ctx, C)) != SI_OK) return rc;
   // the device-side output arrays stay with the ctx (grown on demand, released with the inference set-up)
-  if (!ctx->d_outZ.reserve((size_t)M * itr * C) || !ctx->d_outlp.reserve((size_t)itr * C))
+  if (!ctx->d_outZ.reserve((size_t)ctx->iM * itr * C) || !ctx->d_outlp.reserve((size_t)itr * C))
     return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
-  double* const dZ = ctx->d_outZ;
-  double* const dlp = ctx->d_outlp;
   const double d = (double)ctx->out_dim * (double)ctx->B;
-  const double c0 = mvnormal_c0(d, ctx->sigma_m), s2 = ctx->sigma_m * ctx->sigma_m;
-  // ---- K6 as a device-resident loop (kernels_chain.hip): small Dense chains whose weights, data and activations fit one
-  // workgroup's LDS run ALL transitions in one launch, one workgroup per chain -- the launch-per-step loop below costs ~8
-  // dependent launches (25 us) per transition whatever the size.  Same bits (tests/test_gpu_chain.py).
-  // (with the output map requested -- what the drop-in sub_inference call does -- the weight samples of the finished chains
-  //  come from ONE K4 pass over all itr * C samples, the kernel si_reconstruct runs: same bits, no streaming needed at this size)
-  const size_t wall_elems = (size_t)ldw * (size_t)itr * (size_t)C;
-  if ((!W_out || wall_elems <= ((size_t)512 << 20) / sizeof(double)) && chain_loop_applies(ctx) && ctx->chain_mode == 1) {
-    ChainLoopArgs a{};
-    const int L = (int)ctx->layers.size();
-    for (int l = 0; l < L; ++l) a.lay[l] = ctx->layers[(size_t)l];
-    a.swa = ctx->i_swa; a.P = ctx->i_P; a.X = ctx->d_X; a.Y = ctx->d_Y;
-    a.Z_out = dZ; a.lp_out = dlp; a.nacc_out = ctx->d_nacc;
-    a.ldP = ctx->ldP; a.itr = itr; a.seed = seed; a.sigma_z = sigma_z; a.c0 = c0; a.sigma2 = s2;
-    a.N = (int)N; a.M = M; a.B = (int)ctx->B; a.L = L; a.chain_id0 = chain_id0;
-    a.slot_feats = dense_fused_slot_feats(ctx->layers[(size_t)L - 2].out);
-    a.fuse_slots = ctx->fuse_slots;
-    const size_t lds = chain_loop_plan(a, SI_CHAIN_LDS_LIMIT);
-    if (lds != 0) {
-      {
-        const double fl = 2.0 * (double)N * (double)ctx->B * (double)itr * C;
-        ProfScope ps(ctx, SI_K_RWMH, fl, 0.0);
-        launch_chain_loop(ctx->stream, a, C, lds);
-      }
-      return finish_chains(ctx, who, hipGetLastError(), itr, C, Z_out, lp_out, accept_rate_out, W_out, wall_elems, nullptr, nullptr);
-    }
-  }
-  // ---- K6 as a persistent loop over a GRID of workgroups (kernels_chain_grid.hip): a narrow chain too large for one
-  // workgroup (docs/src/nn_example.md's MLP) runs all transitions in one launch, G = ceil(B / tile) resident workgroups per
-  // chain, two bounded grid barriers per transition.  Same bits as the loop below (tests/test_gpu_chain_grid.py).
-  if ((!W_out || wall_elems <= ((size_t)512 << 20) / sizeof(double)) && ctx->fused_ok && ctx->chain_mode == 1 && !(ctx->sigma_p > 0.0) &&
-      C <= ctx->fw_slots && itr < ((int64_t)1 << 24)) {
-    ChainGridArgs a{};
-    const int L = (int)ctx->layers.size();
-    const int sf = ctx->fuse_tail ? dense_fused_slot_feats(ctx->layers[(size_t)L - 2].out) : 0;
-    int nb = 0;
-    size_t lds = 0;
-    for (int cand : {1, 2, 4}) {   // the smallest tile whose grid is resident: one workgroup per CU
-      const int64_t G = (ctx->B + 16 * cand - 1) / (16 * cand);
-      if (G * C > ctx->num_cu) continue;
-      const size_t lf = chain_fused_plan(a.p, ctx->layers.data(), L, ctx->B, cand, ctx->fuse_tail, sf, ctx->fuse_slots);
-      fused_fill_program(ctx, a.p);
-      a.M = M;
-      a.nblocks = ctx->sse_blocks;
-      a.G = (int)G;
-      lds = chain_grid_plan(a, lf);
-      if (lds != 0) {
-        nb = cand;
-        break;
-      }
-    }
-    // The loop specialised to this chain's shapes (chain_spec.inc through hiprtc; same bits): ONE barrier per transition, the
-    // weights handed over in fragment order.  Class: a narrow head, at most 1024 model outputs (four blocks of the SSE tree),
-    // every weight fragment in registers (spec_applies).
-    const SpecKernels* sk = nullptr;
-    SiSpecGridArgs sa{};
-    size_t lds_spec = 0;
-    if (nb != 0 && ctx->chain_spec && ctx->fuse_tail && (int64_t)ctx->out_dim * ctx->B <= 1024 && M <= 256) {
-      const int G = a.G;
-      const int rs = (int)((((N + G - 1) / G) + 15) & ~(int64_t)15);
-      sk = spec_kernels(ctx->layers.data(), L, nb, sf, M, rs <= 256 && M <= 32, &ctx->spec_message);
-      if (sk) {
-        auto even = [](int64_t v) { return (v + 1) & ~(int64_t)1; };
-        const int64_t d = (int64_t)ctx->out_dim * ctx->B;
-        int64_t off = sk->lds_doubles;
-        sa.y_in_lds = 1;
-        sa.o_y = (int)off;
-        off += even(d);
-        sa.o_blk = (int)off;
-        off += even(ctx->sse_blocks);
-        sa.o_z = (int)off;
-        off += even(5 * (int64_t)M);
-        sa.o_red = (int)off;
-        off += 24;
-        sa.o_flag = (int)off;
-        off += 2;
-        lds_spec = std::max((size_t)off * sizeof(double), (size_t)(81 * 1024));   // (more than half a CU's LDS: one workgroup per CU)
-        if (lds_spec > (size_t)160 * 1024 - 256) sk = nullptr;
-      }
-      if (sk && (ctx->spec_chains < C || ctx->spec_fo != sk->fo_total)) {
-        ctx->d_specw.reset();
-        ctx->d_specy.reset();
-        ctx->spec_chains = 0;
-        if (!ctx->d_specw.alloc((size_t)4 * (size_t)sk->fo_total * (size_t)C) ||
-            !ctx->d_specy.alloc((size_t)2 * (size_t)ctx->out_dim * (size_t)ctx->B * (size_t)C))
-          return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": allocation failed");
-        // (the padding elements of the fragment-ordered vectors are never written by K4: they must be finite)
-        if (hipMemsetAsync(ctx->d_specw, 0, (size_t)4 * (size_t)sk->fo_total * (size_t)C * sizeof(double), ctx->stream) != hipSuccess)
-          return fail(ctx, SI_ERR_HIP, std::string(who) + ": hipMemsetAsync failed");
-        ctx->spec_chains = C;
-        ctx->spec_fo = sk->fo_total;
-      }
-      if (sk && ctx->specperm_for != (const void*)sk) {
-        ctx->specperm_for = nullptr;
-        if (!ctx->d_specperm.alloc((size_t)N)) return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": allocation failed");
-        int* pp = ctx->d_specperm;
-        void* pargs[] = {&pp};
-        if (hipModuleLaunchKernel(sk->perm, (unsigned)((sk->max_wn + 255) / 256), 1, 1, 256, 1, 1, 0, ctx->stream, pargs, nullptr) != hipSuccess)
-          return fail(ctx, SI_ERR_HIP, std::string(who) + ": launch of the fragment-order permutation failed");
-        ctx->specperm_for = (const void*)sk;
-      }
-    }
-    const size_t sync_lines = sk ? (size_t)8 * (size_t)C + 1 : (size_t)C + 1;   // (the specialised loop shards each chain's counter over 8 lines)
-    if (nb != 0) {
-      if (!ctx->d_gridsync.reserve((size_t)32 * sync_lines)) return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": allocation failed");
-      a.swa = ctx->i_swa; a.P = ctx->i_P; a.X = ctx->d_X; a.Y = ctx->d_Y;
-      a.wbuf = ctx->d_w; a.w_stride = ldw;
-      a.ybuf = ctx->d_yhat; a.y_stride = (int64_t)ctx->out_dim * ctx->B;
-      a.cnt = ctx->d_gridsync; a.status = ctx->d_gridsync + (size_t)32 * (sync_lines - 1);
-      a.Z_out = dZ; a.lp_out = dlp; a.nacc_out = ctx->d_nacc;
-      a.ldP = ctx->ldP; a.itr = itr; a.seed = seed; a.sigma_z = sigma_z; a.c0 = c0; a.sigma2 = s2;
-      a.N = (int)N; a.chain_id0 = chain_id0;
-      hipError_t e = hipMemsetAsync(ctx->d_gridsync, 0, (size_t)32 * sync_lines * sizeof(unsigned), ctx->stream);
-      if (e == hipSuccess) {
-        const double fl = 2.0 * (double)N * (double)ctx->B * (double)itr * C;
-        ProfScope ps(ctx, SI_K_RWMH, fl, 0.0);
-        if (sk) {
-          sa.swa = a.swa; sa.P = a.P; sa.X = a.X; sa.Y = a.Y; sa.perm = ctx->d_specperm;
-          sa.wbuf = ctx->d_specw; sa.w_stride = sk->fo_total;
-          sa.ybuf = ctx->d_specy; sa.y_stride = a.y_stride;
-          sa.cnt = a.cnt; sa.status = a.status;
-          sa.Z_out = dZ; sa.lp_out = dlp; sa.nacc_out = (long long*)ctx->d_nacc.get();
-          sa.ldP = a.ldP; sa.itr = itr; sa.seed = seed; sa.sigma_z = sigma_z; sa.c0 = c0; sa.sigma2 = s2;
-          sa.N = (int)N; sa.M = M; sa.G = a.G; sa.B = (int)ctx->B; sa.chain_id0 = chain_id0; sa.nblocks = ctx->sse_blocks;
-          void* gargs[] = {&sa};
-          e = hipModuleLaunchKernel(sk->grid, (unsigned)(a.G * C), 1, 1, 256, 1, 1, (unsigned)lds_spec, ctx->stream, gargs, nullptr);
-          ctx->last_loop_spec = e == hipSuccess;
-        } else {
-          e = launch_chain_grid(ctx->stream, a, nb, C, lds);
-        }
-      }
-      unsigned status = 0;
-      if (e == hipSuccess) e = hipMemcpyAsync(&status, a.status, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
-      // the samples and lp go through pinned staging: a device-to-host copy straight into the caller's array pins its pages on the
-      // fly, and for an array nobody has touched yet (np.empty, Matrix{Float64}(undef, ...)) that costs ~9 us per page -- 7 ms for the
-      // 3.4 MB of a 20 000-transition chain, 0.35 us per transition of a 9.8 us loop
-      const size_t zbytes = Z_out ? (size_t)M * itr * C * sizeof(double) : 0, lbytes = lp_out ? (size_t)itr * C * sizeof(double) : 0;
-      const bool staged = zbytes + lbytes >= ((size_t)128 << 10) && zbytes + lbytes <= ((size_t)128 << 20) &&
-                          ctx->h_outpin.reserve(zbytes + lbytes);   // (the direct copy is always possible)
-      return finish_chains(ctx, who, e, itr, C, Z_out, lp_out, accept_rate_out, W_out, wall_elems, staged ? ctx->h_outpin.get() : nullptr, &status);
-    }
-  }
-  {
-    ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-    launch_rwmh_init(ctx->stream, ctx->d_zcur, ctx->d_lpcur, ctx->d_nacc, ctx->d_steps, M, C);
-  }
-  // the proposal weights of ALL chains are still in d_w at accept time only when one pass of launches carries them all
-  const bool select_path = W_out && C <= ctx->fw_slots;
-  // one transition for all chains; the transition index is a device-side counter, so the launches are identical.
-  // When one pass of launches carries all chains (and the prior term is off) the tail of a transition is ONE launch: the last
-  // stage of the SSE reduction, the accept step and the next transition's proposal (rwmh_tail_kernel) -- same functions, same
-  // order, same bits; otherwise sse_final / accept / propose stay separate kernels.
-  const bool fused_tail = C <= ctx->fw_slots && !(ctx->sigma_p > 0.0) && ctx->chain_loop_enabled;
-  int64_t tdone = 0;
-  auto transition = [&]() -> int32_t {
-    if (!fused_tail || tdone == 0) {
-      ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-      launch_rwmh_propose(ctx->stream, ctx->d_zcur, ctx->d_zprop, M, C, sigma_z, seed, chain_id0, ctx->d_steps);
-    }
-    ctx->defer_sse_final = fused_tail;
-    const int32_t r = eval_density_all(ctx, C);
-    ctx->defer_sse_final = false;
-    if (r != SI_OK) return r;
-    ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-    if (fused_tail)
-      launch_rwmh_tail(ctx->stream, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse, ctx->d_zcur, ctx->d_zprop, ctx->d_lpcur, ctx->d_nacc, M,
-                       C, c0, s2, sigma_z, seed, chain_id0, ctx->d_steps, dZ, dlp, itr, select_path ? ctx->d_accflag : nullptr,
-                       tdone + 1 < itr);
-    else
-      launch_rwmh_accept(ctx->stream, ctx->d_zcur, ctx->d_zprop, ctx->d_lpcur, ctx->d_sse, ctx->d_nacc, M, C, c0, s2, seed,
-                         chain_id0, ctx->d_steps, dZ, dlp, itr, ctx->sigma_p > 0.0 ? ctx->d_wsq : nullptr, prior_c0(ctx),
-                         ctx->sigma_p * ctx->sigma_p, select_path ? ctx->d_accflag : nullptr);
-    ++tdone;
-    return SI_OK;
-  };
-  hipError_t e = hipSuccess;
-  auto ring = [&](int64_t t) { return ctx->d_wring + (size_t)(t % SI_WRING) * (size_t)C * (size_t)ldw; };
-  auto drain = [&](int64_t u) {   // sample u of every chain: pinned slot -> the caller's (pageable) N x itr x C array
-    const int r = (int)(u % SI_WRING);
-    hipError_t w = hipEventSynchronize(ctx->ev_wcopy[r]);
-    for (int c = 0; c < C && w == hipSuccess; ++c)
-      host_copy(W_out + (size_t)N * ((size_t)u + (size_t)itr * c), ctx->h_wring[r] + (size_t)c * N, (size_t)N * sizeof(double));
-    return w;
-  };
-  // Replaying one captured transition as a hipGraph was measured and dropped: the README-toy transition takes 27.8 us
-  // graphed vs 25.7 us eager -- it is bound by the serial latency of its 8 dependent small kernels, not by host
-  // launches -- and at cfg2 a transition is 3.3 ms of kernel time.
-  for (int64_t t = 0; t < itr && rc == SI_OK && e == hipSuccess; ++t) {
-    rc = transition();
-    if (rc != SI_OK || !W_out) continue;
-    const int r = (int)(t % SI_WRING);
-    if (t >= SI_WRING) e = hipStreamWaitEvent(ctx->stream, ctx->ev_wcopy[r], 0);  // the DMA of sample t - R has read this slot
-    if (e != hipSuccess) break;
-    {
-      ProfScope ps(ctx, SI_K_RECON, 0.0, 16.0 * (double)N * C);
-      if (select_path)
-        launch_weights_select(ctx->stream, ctx->d_accflag, ctx->d_w, ldw, t > 0 ? ring(t - 1) : nullptr, ring(t), ldw, N, C, ctx->num_cu);
-      else  // more chains than one pass of launches carries: K4 on the current states (same kernel, same bits)
-        launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, ctx->d_zcur, C, ring(t), ldw, ctx->num_cu);
-    }
-    e = hipEventRecord(ctx->ev_wcomp[r], ctx->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream2, ctx->ev_wcomp[r], 0);
-    if (e == hipSuccess)
-      e = hipMemcpy2DAsync(ctx->h_wring[r], (size_t)N * sizeof(double), ring(t), (size_t)ldw * sizeof(double), (size_t)N * sizeof(double),
-                           (size_t)C, hipMemcpyDeviceToHost, ctx->stream2);
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev_wcopy[r], ctx->stream2);
-    if (e == hipSuccess && t >= SI_WRING - 1) e = drain(t - (SI_WRING - 1));   // frees the pinned slot sample t + 1 will use
-  }
-  if (rc == SI_OK && e == hipSuccess && W_out)
-    for (int64_t u = std::max<int64_t>(0, itr - (SI_WRING - 1)); u < itr && e == hipSuccess; ++u) e = drain(u);
-  if (W_out) (void)hipStreamSynchronize(ctx->stream2);
-  if (rc != SI_OK || e != hipSuccess) {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (rc != SI_OK) return rc;
-    return fail(ctx, SI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-  }
-  return finish_chains(ctx, who, hipGetLastError(), itr, C, Z_out, lp_out, accept_rate_out, nullptr, 0, nullptr, nullptr);
+  const size_t wall_elems = (size_t)pad_ld(ctx->iN) * (size_t)itr * (size_t)C;
+  const RwmhCall k{who, itr, sigma_z, seed, chain_id0, C, Z_out, lp_out, accept_rate_out, W_out, mvnormal_c0(d, ctx->sigma_m),
+                   ctx->sigma_m * ctx->sigma_m, wall_elems, !W_out || wall_elems <= ((size_t)512 << 20) / sizeof(double)};
+  if ((rc = rwmh_one_workgroup(ctx, k)) != SI_NOT_TAKEN) return rc;
+  if ((rc = rwmh_grid(ctx, k)) != SI_NOT_TAKEN) return rc;
+  return rwmh_per_step(ctx, k);
 }
 
 int32_t si_sample_rwmh(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, int32_t chain_id0, int32_t nchains,
@@ -414,7 +469,7 @@ int32_t si_rwmh_step_eval(si_ctx* ctx, double* sse_local_out) {
   launch_rwmh_propose(ctx->stream, ctx->d_zcur, ctx->d_zprop, ctx->iM, C, ctx->sw_sigma_z, ctx->sw_seed, ctx->sw_chain0,
                       ctx->d_steps);
   {
-    const int32_t rc = eval_density_all(ctx, C);
+    const int32_t rc = eval_density_all(ctx, setup_view(ctx), C);   // (the deferred SSE stage off: d_sse goes to the caller)
     if (rc != SI_OK) return rc;
   }
   if (sse_local_out) {  // NULL: the partial sums stay on the device (si_rwmh_sse_ptr) -- no copy, no synchronisation

@@ -188,7 +188,6 @@ struct CtxCore {
   uint64_t sw_seed = 0;
   int32_t sw_chain0 = 0, sw_C = 0;
   bool sw_evaluated = false;
-  bool defer_sse_final = false;   // eval_density leaves the SSE block partials in d_ssepart (sample_rwmh_impl's fused tail sums them)
   bool chain_loop_enabled = true;   // si_set_chain_loop: 0 forces the launch-per-step loop (the parity tests compare the two)
   // narrow Dense chains (kernels_chain_grid.hip): every layer of the density in ONE launch, and K6 as a persistent grid loop
   int chain_mode = 1;               // si_set_chain_loop: 0 per-layer launches, 1 automatic, 2 the fused forward without the persistent loops

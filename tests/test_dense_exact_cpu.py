@@ -78,13 +78,16 @@ DISPATCH_TEXT = {
         "for (int l = 0; l < (ctx->fuse_tail ? L - 2 : L); ++l) maxstored = std::max<int64_t>(maxstored, plan.L[(size_t)l].out_elems);",
         "ctx->act_elems = pad_ld(maxstored * B);",
         "static constexpr int SI_FUSED_MAX_WIDTH = 256;", "if (ctx->fused_ok && ctx->chain_mode != 0 && !yhat_out) {",
-        "cb.n = nc; cb.w = ldw; cb.hout = ctx->act_elems;",
+        "cb.n = nc; cb.w = ldw; cb.hout = v.act_elems;",
+        "ctx->d_part, ctx->d_yhat, ctx->act_elems, ctx->f32, defer_sse_final, true};",   # setup_view: the set-up's own stride and type
         """const double per = (ctx->f32 ? 4.0 : 8.0) * 2.0 * (double)ctx->act_elems +
            8.0 * ((pslots + 1.0) * (double)ctx->out_dim * (double)ctx->B + (ctx->f32 ? 1.5 : 1.0) * (double)pad_ld(ctx->iN) +
            (double)ctx->sse_blocks);
            const double fit = std::floor(SI_BATCH_BYTES / per);
            return (int)std::max(1.0, std::min({(double)C, fit, 1024.0}));""",
-        "ctx->f32 = false; const int64_t act_elems = pad_ld(ctx->max_stored * Bn);",   # si_predict: fp64, its own workspace
+        # si_predict: fp64, its own workspace, through a view of its own
+        "const int64_t act_elems = pad_ld(ctx->max_stored * Bn);",
+        "const DensityView v{tX, tXc, nullptr, tY, Bn, tA, nullptr, tS, sse_blocks, tP, tYh, act_elems, /*f32=*/false,",
     ),
     "capi.hip": (
         "hipError_t raw_dev_malloc(void** out, size_t bytes) { return hipMalloc(out, bytes); }",   # A1: every buffer its own allocation

@@ -313,13 +313,15 @@ def test_rwmh_stepwise_sse_exact_and_shards(si, gpu_ctx):
 
 
 # ----------------------------------------------------------------------------------------------- Gram
-# (N, K): gram_small NT 1..8 (K <= 128) and the gram_off panels (K > 128); ragged N
+# (N, K), ragged N, every push path and both storage types.  (These shapes reach 7 of the 26 LDS-DMA instantiations and about a
+#  dozen of the 32 panel ones; tests/test_gpu_gram_exact.py holds every reachable one, route by route: tests/gram_routes.py.)
 GRAM_CASES = [(1, 1), (31, 15), (33, 16), (4097, 17), (100003, 100), (4097, 128), (33, 129), (4097, 200), (31, 260)]
 
 
 def gram_problem(n, k):
-    """(snapshots, epoch counters, A, exact A'A) of one GRAM_CASES entry"""
-    snaps, ns, _, a = lat.snapshots(n, k, seed=n + k)
+    """(snapshots, epoch counters, A, exact A'A) of one GRAM_CASES entry.  The epoch counters start at 1: with n_0 = 0 the first
+    deviation column is zero, and so are row and column 0 of G (tests/test_gram_exact_cpu.py pins that no column is zero)"""
+    snaps, ns, _, a = lat.snapshots(n, k, seed=n + k, ns=[1 + j // 3 for j in range(k)])
     return snaps, ns, a, lat.gram_exact(a).astype(np.float64)
 
 

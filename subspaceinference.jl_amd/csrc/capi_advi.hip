@@ -15,7 +15,7 @@ int32_t si_fit_advi(si_ctx* ctx, int64_t max_iters, int32_t samples_per_step, do
                     double* theta_trace_out, double* points_out) {
   CHECK_CTX(ctx);
   const char* who = "si_fit_advi";
-  ctx->last_advi_fused = ctx->last_advi_passes = 0;   // (si_advi_kernel_info reports THIS call)
+  ctx->info_advi = CallInfo();   // (si_advi_kernel_info reports THIS call)
   const int64_t T = max_iters, D = ndraws;
   const int32_t S = samples_per_step, W = window, R = nruns;
   // (the comparisons are written so that a NaN refuses; S nblk < 2^24: the Philox block field of the step draws)
@@ -70,15 +70,14 @@ int32_t si_fit_advi(si_ctx* ctx, int64_t max_iters, int32_t samples_per_step, do
                                           {theta_trace_out, a.trace_out, trace_elems * f64},
                                           {points_out, a.pts_out, ptsout_elems * f64}});
   if (rc != SI_OK) return rc;
-  ctx->last_advi_fused = vg.fused ? 1 : 0;
-  ctx->last_advi_passes = vg.passes;
+  ctx->info_advi = call_info(vg);
   return SI_OK;
 }
 
 int32_t si_advi_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out) {
   CHECK_CTX(ctx);
-  if (fused_out) *fused_out = ctx->last_advi_fused;
-  if (passes_out) *passes_out = ctx->last_advi_passes;
+  if (fused_out) *fused_out = ctx->info_advi.fused;
+  if (passes_out) *passes_out = ctx->info_advi.passes;
   return SI_OK;
 }
 

@@ -92,11 +92,67 @@ struct StackedVgrad {
 struct Download { void* dst; const void* src; size_t bytes; };
 int32_t finish_downloads(si_ctx* ctx, const char* who, hipError_t e, int32_t rc, std::initializer_list<Download> downs);
 
-// capi_hmc.hip: what si_sample_hmc and si_sample_nuts share.  The chains' state for C chains (grown on demand); the kernels' shared
-// arguments over that state and the output arrays (reserved by the caller); the preamble -- hmc_init, then the step-size search
-// round by round with one 4-byte read-back each -- returning its rounds, with e / rc as StackedVgrad::eval treats them; and the
-// adaptation phase of every step t = 1, 2, ... in turn (the host's knowledge, handed to the kernels as flags).
-int32_t hmc_reserve_state(si_ctx* ctx, const char* who, int32_t C);
+// What such a call took, for the context's CallInfo of its entry point (each entry point clears its own first: a refused call reports zeros)
+inline CallInfo call_info(const StackedVgrad& vg, int search_rounds = 0, int64_t rounds = 0, int64_t leaves = 0) {
+  return CallInfo{vg.fused ? 1 : 0, vg.passes, search_rounds, rounds, leaves};
+}
+
+// Per-chain sampler state that grows on demand, for every group of buffers that has a capacity: nothing is queued on the buffers
+// while they are replaced, and a failed growth leaves the capacity at zero.  alloc() allocates the group for C chains.
+template <class Alloc>
+int32_t reserve_state(si_ctx* ctx, const char* who, int& cap, int32_t C, Alloc&& alloc) {
+  if (cap >= C) return SI_OK;
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  cap = 0;
+  if (!alloc()) return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": sampler state allocation failed");
+  cap = C;
+  return SI_OK;
+}
+// the context's ChainState for C chains: what si_sample_mala, si_sample_hmc and si_sample_nuts reserve first
+inline int32_t reserve_chain_state(si_ctx* ctx, const char* who, int32_t C) {
+  ChainState& s = ctx->chain_state;
+  const size_t mc = (size_t)ctx->iM * (size_t)C;
+  return reserve_state(ctx, who, s.cap, C, [&] {
+    return s.z.alloc(mc) && s.g.alloc(mc) && s.zp.alloc(mc) && s.gp.alloc(mc) && s.lp.alloc((size_t)C) && s.lpp.alloc((size_t)C);
+  });
+}
+// ... and the part of their kernels' arguments that lies over it and over the sample arrays (reserved by the caller)
+inline void chain_run_args(ChainRun& r, si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, int32_t chain_id0, bool want_G) {
+  ChainState& s = ctx->chain_state;
+  r.z = s.z, r.lp = s.lp, r.g = s.g, r.zp = s.zp, r.lpp = s.lpp, r.gp = s.gp;
+  r.Z_out = ctx->d_outZ, r.lp_out = ctx->d_outlp, r.G_out = want_G ? ctx->d_outG.get() : nullptr;
+  r.M = ctx->iM, r.chain_id0 = chain_id0, r.itr = itr, r.seed = seed, r.sigma_z = sigma_z;
+}
+
+// the value and gradient at the chains' proposals / pending points: (lpp, gp) at zp
+inline void eval_pending(si_ctx* ctx, StackedVgrad& vg, hipError_t& e, int32_t& rc) {
+  ChainState& s = ctx->chain_state;
+  vg.eval(s.zp, s.lpp, s.gp, e, rc);
+}
+
+// One synchronised round of a data-dependent loop (the step-size search, a NUTS leaf): one evaluation at the chains' pending
+// points, the open word cleared, launch(open word) -- the kernel counts the chains that go on into it -- a 4-byte read-back into
+// `open` and a synchronisation.  e / rc as StackedVgrad::eval treats them; returns whether the round was completed.
+template <class Launch>
+bool synced_round(si_ctx* ctx, StackedVgrad& vg, int32_t& open, hipError_t& e, int32_t& rc, Launch&& launch) {
+  if (e == hipSuccess && rc == SI_OK) eval_pending(ctx, vg, e, rc);
+  if (e != hipSuccess || rc != SI_OK) return false;
+  if ((e = hipMemsetAsync(ctx->d_hmc_open, 0, sizeof(int32_t), ctx->stream)) != hipSuccess) return false;
+  {
+    ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+    launch(ctx->d_hmc_open.get());
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&open, ctx->d_hmc_open, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  return e == hipSuccess;
+}
+
+// capi_hmc.hip: what si_sample_hmc and si_sample_nuts share.  The chains' state on top of ChainState (nuts: the tree's too); the
+// kernels' shared arguments over the state and the output arrays (reserved by the caller); the preamble -- hmc_init, then the step-size search round by round -- returning its rounds, with
+// e / rc as StackedVgrad::eval treats them; and the adaptation phase of every step t = 1, 2, ... in turn (the host's knowledge,
+// handed to the kernels as flags).
+int32_t hmc_reserve_state(si_ctx* ctx, const char* who, int32_t C, bool nuts);
 HmcRun hmc_run_args(si_ctx* ctx, int64_t itr, double sigma_z, double delta, uint64_t seed, int32_t chain_id0, bool want_G, bool want_Minv);
 int hmc_preamble(si_ctx* ctx, const char* who, const HmcRun& a, StackedVgrad& vg, int32_t C, hipError_t& e, int32_t& rc);
 struct HmcPhases {

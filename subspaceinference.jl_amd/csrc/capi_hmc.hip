@@ -46,24 +46,31 @@ int32_t hmc_windows(int64_t n_adapts, int64_t* window_start, int64_t* window_end
   return count;
 }
 
-int32_t hmc_reserve_state(si_ctx* ctx, const char* who, int32_t C) {
-  if (ctx->hmc_cap >= C) return SI_OK;
-  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->hmc_cap = 0;
+int32_t hmc_reserve_state(si_ctx* ctx, const char* who, int32_t C, bool nuts) {
   const size_t mc = (size_t)ctx->iM * (size_t)C;
-  if (!ctx->d_hmc_z.alloc(mc) || !ctx->d_hmc_g.alloc(mc) || !ctx->d_hmc_zp.alloc(mc) || !ctx->d_hmc_gp.alloc(mc) ||
-      !ctx->d_hmc_rh.alloc(mc) || !ctx->d_hmc_minv.alloc(mc) || !ctx->d_hmc_wmean.alloc(mc) || !ctx->d_hmc_wm2.alloc(mc) ||
-      !ctx->d_hmc_lp.alloc((size_t)C) || !ctx->d_hmc_lpp.alloc((size_t)C) || !ctx->d_hmc_chain.alloc((size_t)C) ||
-      !ctx->d_hmc_open.alloc(1))
-    return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": sampler state allocation failed");
-  ctx->hmc_cap = C;
-  return SI_OK;
+  int32_t rc = reserve_chain_state(ctx, who, C);
+  if (rc == SI_OK)
+    rc = reserve_state(ctx, who, ctx->hmc_cap, C, [&] {
+      return ctx->d_hmc_rh.alloc(mc) && ctx->d_hmc_minv.alloc(mc) && ctx->d_hmc_wmean.alloc(mc) && ctx->d_hmc_wm2.alloc(mc) &&
+             ctx->d_hmc_chain.alloc((size_t)C) && ctx->d_hmc_open.alloc(1);
+    });
+  if (rc == SI_OK && nuts)
+    rc = reserve_state(ctx, who, ctx->nuts_cap, C, [&] {
+      for (DevBuf<double>* b : {&ctx->d_nuts_zm, &ctx->d_nuts_rm, &ctx->d_nuts_gm, &ctx->d_nuts_zq, &ctx->d_nuts_rq, &ctx->d_nuts_gq,
+                                &ctx->d_nuts_rho, &ctx->d_nuts_zc, &ctx->d_nuts_gc})
+        if (!b->alloc(mc)) return false;
+      return ctx->d_nuts_stack.alloc(4 * mc * NUTS_MAX_DEPTH) && ctx->d_nuts_tree.alloc((size_t)C);
+    });
+  return rc;
 }
 
 HmcRun hmc_run_args(si_ctx* ctx, int64_t itr, double sigma_z, double delta, uint64_t seed, int32_t chain_id0, bool want_G, bool want_Minv) {
-  return HmcRun{ctx->d_hmc_z, ctx->d_hmc_lp, ctx->d_hmc_g, ctx->d_hmc_zp, ctx->d_hmc_rh, ctx->d_hmc_minv, ctx->d_hmc_wmean, ctx->d_hmc_wm2,
-                ctx->d_hmc_lpp, ctx->d_hmc_gp, ctx->d_hmc_chain, ctx->d_outZ, ctx->d_outlp, ctx->d_outalpha, ctx->d_outeps,
-                want_G ? ctx->d_outG.get() : nullptr, want_Minv ? ctx->d_outMinv.get() : nullptr, ctx->iM, chain_id0, itr, seed, sigma_z, delta};
+  HmcRun a;
+  chain_run_args(a, ctx, itr, sigma_z, seed, chain_id0, want_G);
+  a.rh = ctx->d_hmc_rh, a.minv = ctx->d_hmc_minv, a.wmean = ctx->d_hmc_wmean, a.wm2 = ctx->d_hmc_wm2, a.chain = ctx->d_hmc_chain;
+  a.alpha_out = ctx->d_outalpha, a.eps_out = ctx->d_outeps, a.Minv_out = want_Minv ? ctx->d_outMinv.get() : nullptr;
+  a.delta = delta;
+  return a;
 }
 
 int hmc_preamble(si_ctx* ctx, const char* who, const HmcRun& a, StackedVgrad& vg, int32_t C, hipError_t& e, int32_t& rc) {
@@ -76,20 +83,9 @@ int hmc_preamble(si_ctx* ctx, const char* who, const HmcRun& a, StackedVgrad& vg
   // crossings, the bisections)
   int rounds = 0;
   int32_t open = 1;
-  while (open > 0 && e == hipSuccess && rc == SI_OK && rounds < 2 * 100 + 3) {
-    vg.eval(ctx->d_hmc_zp, ctx->d_hmc_lpp, ctx->d_hmc_gp, e, rc);
-    if (e != hipSuccess || rc != SI_OK) break;
-    e = hipMemsetAsync(ctx->d_hmc_open, 0, sizeof(int32_t), ctx->stream);
-    if (e != hipSuccess) break;
-    {
-      ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-      launch_hmc_search(ctx->stream, a, C, ctx->d_hmc_open);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&open, ctx->d_hmc_open, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  while (open > 0 && rounds < 2 * 100 + 3 &&
+         synced_round(ctx, vg, open, e, rc, [&](int32_t* d_open) { launch_hmc_search(ctx->stream, a, C, d_open); }))
     ++rounds;
-  }
   if (e == hipSuccess && rc == SI_OK && open > 0) rc = fail(ctx, SI_ERR_STATE, std::string(who) + ": the step-size search did not finish within its own limits");
   return rounds;
 }
@@ -119,7 +115,7 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
                       double* Minv_out) {
   CHECK_CTX(ctx);
   const char* who = "si_sample_hmc";
-  ctx->last_hmc_fused = ctx->last_hmc_passes = ctx->last_hmc_rounds = 0;   // (si_hmc_kernel_info reports THIS call)
+  ctx->info_hmc = CallInfo();   // (si_hmc_kernel_info reports THIS call)
   // (every comparison is false for a NaN: refused)
   int32_t rc = grad_entry_check(ctx, who, itr > 0 && n_adapts >= 0 && n_adapts <= itr && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0 &&
                                               delta > 0.0 && delta < 1.0);
@@ -127,7 +123,7 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
   BIND(ctx);
   const int32_t C = nchains, M = ctx->iM;
   const int64_t cols = itr + 1;
-  if ((rc = hmc_reserve_state(ctx, who, C)) != SI_OK) return rc;
+  if ((rc = hmc_reserve_state(ctx, who, C, false)) != SI_OK) return rc;
   const size_t zelems = (size_t)M * (size_t)cols * (size_t)C, selems = (size_t)cols * (size_t)C;
   if (!ctx->d_outZ.reserve(zelems) || !ctx->d_outlp.reserve(selems) || !ctx->d_outalpha.reserve(selems) || !ctx->d_outeps.reserve(selems) ||
       (G_out && !ctx->d_outG.reserve(zelems)) || (Minv_out && !ctx->d_outMinv.reserve(zelems)))
@@ -144,7 +140,7 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
     e = hipGetLastError();
   }
   for (int64_t t = 1; t <= itr && e == hipSuccess && rc == SI_OK; ++t) {
-    vg.eval(ctx->d_hmc_zp, ctx->d_hmc_lpp, ctx->d_hmc_gp, e, rc);
+    eval_pending(ctx, vg, e, rc);
     if (e != hipSuccess || rc != SI_OK) break;
     bool adapting, in_window, window_close, last_adapt;
     phases.at(t, adapting, in_window, window_close, last_adapt);
@@ -156,17 +152,15 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
   rc = finish_downloads(ctx, who, e, rc, {{Z_out, ctx->d_outZ, zbytes}, {lp_out, ctx->d_outlp, sbytes}, {alpha_out, ctx->d_outalpha, sbytes},
                                           {eps_out, ctx->d_outeps, sbytes}, {G_out, a.G_out, zbytes}, {Minv_out, a.Minv_out, zbytes}});
   if (rc != SI_OK) return rc;
-  ctx->last_hmc_fused = vg.fused ? 1 : 0;
-  ctx->last_hmc_passes = vg.passes;
-  ctx->last_hmc_rounds = rounds;
+  ctx->info_hmc = call_info(vg, rounds);
   return SI_OK;
 }
 
 int32_t si_hmc_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out, int32_t* search_rounds_out) {
   CHECK_CTX(ctx);
-  if (fused_out) *fused_out = ctx->last_hmc_fused;
-  if (passes_out) *passes_out = ctx->last_hmc_passes;
-  if (search_rounds_out) *search_rounds_out = ctx->last_hmc_rounds;
+  if (fused_out) *fused_out = ctx->info_hmc.fused;
+  if (passes_out) *passes_out = ctx->info_hmc.passes;
+  if (search_rounds_out) *search_rounds_out = ctx->info_hmc.search_rounds;
   return SI_OK;
 }
 

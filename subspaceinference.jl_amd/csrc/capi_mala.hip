@@ -13,56 +13,50 @@ int32_t si_sample_mala(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, 
                        double* lp_out, double* accept_rate_out, double* G_out) {
   CHECK_CTX(ctx);
   const char* who = "si_sample_mala";
-  ctx->last_mala_fused = ctx->last_mala_passes = 0;   // (si_mala_kernel_info reports THIS call)
+  ctx->info_mala = CallInfo();   // (si_mala_kernel_info reports THIS call)
   int32_t rc = grad_entry_check(ctx, who, itr > 0 && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0);
   if (rc != SI_OK) return rc;
   BIND(ctx);
   const int32_t C = nchains, M = ctx->iM;
-  if (ctx->mala_cap < C) {
-    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->mala_cap = 0;
-    const size_t mc = (size_t)M * (size_t)C;
-    if (!ctx->d_mala_z.alloc(mc) || !ctx->d_mala_g.alloc(mc) || !ctx->d_mala_zp.alloc(mc) || !ctx->d_mala_gp.alloc(mc) ||
-        !ctx->d_mala_lp.alloc((size_t)C) || !ctx->d_mala_lpp.alloc((size_t)C) || !ctx->d_mala_nacc.alloc((size_t)C))
-      return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": sampler state allocation failed");
-    ctx->mala_cap = C;
-  }
+  if ((rc = reserve_chain_state(ctx, who, C)) != SI_OK) return rc;
+  if ((rc = reserve_state(ctx, who, ctx->mala_cap, C, [&] { return ctx->d_mala_nacc.alloc((size_t)C); })) != SI_OK) return rc;
   const size_t zelems = (size_t)M * (size_t)itr * (size_t)C;
   if (!ctx->d_outZ.reserve(zelems) || !ctx->d_outlp.reserve((size_t)itr * C) || (G_out && !ctx->d_outG.reserve(zelems)))
     return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
-  double* const dG = G_out ? ctx->d_outG.get() : nullptr;
+  MalaRun a;
+  chain_run_args(a, ctx, itr, sigma_z, seed, chain_id0, G_out != nullptr);
+  a.nacc = ctx->d_mala_nacc;
+  a.h = 0.5 * (sigma_z * sigma_z);
   StackedVgrad vg;
   if ((rc = vg.open(ctx, who, C)) != SI_OK) return rc;
   hipError_t e = hipSuccess;
   {
     ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-    launch_mala_propose(ctx->stream, ctx->d_mala_z, ctx->d_mala_g, ctx->d_mala_zp, M, C, sigma_z, seed, chain_id0, 0, true);
+    launch_mala_propose(ctx->stream, a, C, 0, true);
     e = hipGetLastError();
   }
   for (int64_t t = 0; t < itr && e == hipSuccess && rc == SI_OK; ++t) {
-    vg.eval(ctx->d_mala_zp, ctx->d_mala_lpp, ctx->d_mala_gp, e, rc);
+    eval_pending(ctx, vg, e, rc);
     if (e != hipSuccess || rc != SI_OK) break;
     ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-    launch_mala_accept(ctx->stream, ctx->d_mala_z, ctx->d_mala_lp, ctx->d_mala_g, ctx->d_mala_zp, ctx->d_mala_lpp, ctx->d_mala_gp,
-                       ctx->d_mala_nacc, M, C, sigma_z, seed, chain_id0, (uint64_t)t, ctx->d_outZ, ctx->d_outlp, dG, itr, t + 1 < itr);
+    launch_mala_accept(ctx->stream, a, C, (uint64_t)t, t + 1 < itr);
     e = hipGetLastError();
   }
   std::vector<int64_t> nacc((size_t)C);
   rc = finish_downloads(ctx, who, e, rc, {{Z_out, ctx->d_outZ, zelems * sizeof(double)},
                                           {lp_out, ctx->d_outlp, (size_t)itr * C * sizeof(double)},
-                                          {G_out, dG, zelems * sizeof(double)},
+                                          {G_out, a.G_out, zelems * sizeof(double)},
                                           {nacc.data(), ctx->d_mala_nacc, (size_t)C * sizeof(int64_t)}});
   if (rc != SI_OK) return rc;
   accept_rates(nacc, itr, accept_rate_out);
-  ctx->last_mala_fused = vg.fused ? 1 : 0;
-  ctx->last_mala_passes = vg.passes;
+  ctx->info_mala = call_info(vg);
   return SI_OK;
 }
 
 int32_t si_mala_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out) {
   CHECK_CTX(ctx);
-  if (fused_out) *fused_out = ctx->last_mala_fused;
-  if (passes_out) *passes_out = ctx->last_mala_passes;
+  if (fused_out) *fused_out = ctx->info_mala.fused;
+  if (passes_out) *passes_out = ctx->info_mala.passes;
   return SI_OK;
 }
 

@@ -18,8 +18,7 @@ int32_t si_sample_nuts(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_
                        double* leaf_out, int64_t leaf_cap) {
   CHECK_CTX(ctx);
   const char* who = "si_sample_nuts";
-  ctx->last_nuts_fused = ctx->last_nuts_passes = ctx->last_nuts_search = 0;   // (si_nuts_kernel_info reports THIS call)
-  ctx->last_nuts_rounds = ctx->last_nuts_leaves = 0;
+  ctx->info_nuts = CallInfo();   // (si_nuts_kernel_info reports THIS call)
   // (every comparison is false for a NaN: refused)
   int32_t rc = grad_entry_check(ctx, who, itr > 0 && n_adapts >= 0 && n_adapts <= itr && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0 &&
                                               delta > 0.0 && delta < 1.0 && max_depth >= 1 && max_depth <= NUTS_MAX_DEPTH && max_dh > 0.0 &&
@@ -28,18 +27,7 @@ int32_t si_sample_nuts(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_
   BIND(ctx);
   const int32_t C = nchains, M = ctx->iM;
   const int64_t cols = itr + 1;
-  if ((rc = hmc_reserve_state(ctx, who, C)) != SI_OK) return rc;
-  if (ctx->nuts_cap < C) {
-    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->nuts_cap = 0;
-    const size_t mc = (size_t)M * (size_t)C;
-    for (DevBuf<double>* b : {&ctx->d_nuts_zm, &ctx->d_nuts_rm, &ctx->d_nuts_gm, &ctx->d_nuts_zq, &ctx->d_nuts_rq, &ctx->d_nuts_gq,
-                              &ctx->d_nuts_rho, &ctx->d_nuts_zc, &ctx->d_nuts_gc})
-      if (!b->alloc(mc)) return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": sampler state allocation failed");
-    if (!ctx->d_nuts_stack.alloc(4 * mc * NUTS_MAX_DEPTH) || !ctx->d_nuts_tree.alloc((size_t)C))
-      return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": sampler state allocation failed");
-    ctx->nuts_cap = C;
-  }
+  if ((rc = hmc_reserve_state(ctx, who, C, true)) != SI_OK) return rc;
   const size_t zelems = (size_t)M * (size_t)cols * (size_t)C, selems = (size_t)cols * (size_t)C;
   const size_t lelems = leaf_out ? (3 * (size_t)M + 1) * (size_t)leaf_cap * (size_t)C : 0;
   if (!ctx->d_outZ.reserve(zelems) || !ctx->d_outlp.reserve(selems) || !ctx->d_outalpha.reserve(selems) || !ctx->d_outeps.reserve(selems) ||
@@ -66,19 +54,9 @@ int32_t si_sample_nuts(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_
     }
     int32_t open = 1;
     int64_t r = 0;
-    for (; open > 0 && e == hipSuccess && rc == SI_OK && r < round_cap; ++r) {
-      vg.eval(ctx->d_hmc_zp, ctx->d_hmc_lpp, ctx->d_hmc_gp, e, rc);
-      if (e != hipSuccess || rc != SI_OK) break;
-      e = hipMemsetAsync(ctx->d_hmc_open, 0, sizeof(int32_t), ctx->stream);
-      if (e != hipSuccess) break;
-      {
-        ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-        launch_nuts_leaf(ctx->stream, a, n, C, (uint64_t)t, ctx->d_hmc_open);
-        e = hipGetLastError();
-      }
-      if (e == hipSuccess) e = hipMemcpyAsync(&open, ctx->d_hmc_open, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    }
+    while (open > 0 && r < round_cap &&
+           synced_round(ctx, vg, open, e, rc, [&](int32_t* d_open) { launch_nuts_leaf(ctx->stream, a, n, C, (uint64_t)t, d_open); }))
+      ++r;
     rounds += r;
     if (e != hipSuccess || rc != SI_OK) break;
     if (open > 0) {
@@ -102,22 +80,19 @@ int32_t si_sample_nuts(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_
   int64_t leaves = 0;
   for (int32_t v : nleaf) leaves += v;
   if (nleaf_out) std::memcpy(nleaf_out, nleaf.data(), ibytes);
-  ctx->last_nuts_fused = vg.fused ? 1 : 0;
-  ctx->last_nuts_passes = vg.passes;
-  ctx->last_nuts_search = search_rounds;
-  ctx->last_nuts_rounds = rounds;
-  ctx->last_nuts_leaves = leaves;
+  ctx->info_nuts = call_info(vg, search_rounds, rounds, leaves);
   return SI_OK;
 }
 
 int32_t si_nuts_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out, int32_t* search_rounds_out, int64_t* rounds_out,
                             int64_t* leaves_out) {
   CHECK_CTX(ctx);
-  if (fused_out) *fused_out = ctx->last_nuts_fused;
-  if (passes_out) *passes_out = ctx->last_nuts_passes;
-  if (search_rounds_out) *search_rounds_out = ctx->last_nuts_search;
-  if (rounds_out) *rounds_out = ctx->last_nuts_rounds;
-  if (leaves_out) *leaves_out = ctx->last_nuts_leaves;
+  const CallInfo& i = ctx->info_nuts;
+  if (fused_out) *fused_out = i.fused;
+  if (passes_out) *passes_out = i.passes;
+  if (search_rounds_out) *search_rounds_out = i.search_rounds;
+  if (rounds_out) *rounds_out = i.rounds;
+  if (leaves_out) *leaves_out = i.leaves;
   return SI_OK;
 }
 

@@ -11,19 +11,17 @@
 //            ring slot t mod W of component p = d_p^2;  s_p = the W slots in slot order;  theta_p -= d_p (eta_opt / (tau + sqrt(s_p)))
 //   draws    z_i = mu_T + exp(omega_T) n_i, n_i = (purpose 4, step i)
 //
-// Two kernels, one workgroup of 256 threads per run.  The values and gradients at the points come from the caller's launches
-// between them (si_fit_advi, capi_advi.hip).  Thread i owns the components m = 2j, 2j + 1 of mu AND of omega for j = i, i + 256, ...
-// in every phase after theta_0: the sums over k and over the ring's slots are sequential inside one thread, and nothing but
-// sum_m omega_m crosses threads -- that sum has kernels_mala.hip's order (thread-strided, chain_wave_sum, (r0 + r1) + (r2 + r3)).
+// Two kernels, one workgroup of SAMPLER_NT threads per run.  The values and gradients at the points come from the caller's launches
+// between them (si_fit_advi, capi_advi.hip).  Thread i owns the components m of mu AND of omega that sampler_device.h's for_owned
+// gives it, in every phase after theta_0: the sums over k and over the ring's slots are sequential inside one thread, and nothing
+// but sum_m omega_m crosses threads -- that sum is sampler_device.h's block_sum.  Two loops keep their own block index and are
+// written out: the step draws (block k nblk + j) and theta_0 (M full blocks over 2M components).
 // eta_k stays in a device buffer between the two kernels: the update uses the bits the points were made from.  The file is
 // compiled without contraction of a * b + c: every product, sum and quotient is rounded by itself, as the host restatement's.
-#include "chain_common.h"
-#include "philox.h"
-#include "si_internal.h"
+#include "sampler_device.h"
 
 namespace si {
 
-static constexpr int ADVI_NT = 256;
 static constexpr double ADVI_LOG_2PI = 1.8378770664093453;   // (a literal: the host restatement must not depend on a libm's log)
 
 // the points of `step` from theta as it stands, for the components this thread owns: eta, z = mu + exp(omega) eta, the trace copy
@@ -33,7 +31,8 @@ __device__ __forceinline__ void advi_form_points(const AdviRun& a, int64_t r, ui
   double* eta = a.eta + (int64_t)M * S * r;
   double* z = a.z + (int64_t)M * S * r;
   double* pts = a.pts_out ? a.pts_out + (int64_t)M * S * ((int64_t)step + a.T * r) : nullptr;
-  for (int j = threadIdx.x; j < nblk; j += ADVI_NT) {
+  // (for_owned's ownership written out: draw k of the components 2j, 2j + 1 is block k nblk + j, and exp(omega) is formed once per j)
+  for (int j = threadIdx.x; j < nblk; j += SAMPLER_NT) {
     double mu[2] = {0.0, 0.0}, sg[2] = {0.0, 0.0};
     for (int c = 0; c < 2; ++c) {
       const int m = 2 * j + c;
@@ -60,16 +59,16 @@ __device__ __forceinline__ void advi_form_points(const AdviRun& a, int64_t r, ui
 
 // first: theta_0 = sigma_z n, the ring cleared, trace column 0, the points of step 0.  final: Z_out[:, i, r] for the i of this
 // workgroup's blockIdx.y.  (grid: R x 1 with first, R x min(D, 128) with final)
-__global__ __launch_bounds__(ADVI_NT) void advi_draw_kernel(AdviRun a, double sigma_z, int first, int final, double* __restrict__ Z_out,
+__global__ __launch_bounds__(SAMPLER_NT) void advi_draw_kernel(AdviRun a, double sigma_z, int first, int final, double* __restrict__ Z_out,
                                                             int64_t D) {
   const int64_t r = blockIdx.x;
   const int tid = threadIdx.x;
-  const int M = a.M, nblk = (M + 1) >> 1;
+  const int M = a.M;
   const uint32_t chain = (uint32_t)(a.chain_id0 + (int32_t)r);
   double* theta = a.theta + 2 * (int64_t)M * r;
   if (first) {
     double* trace = a.trace_out ? a.trace_out + 2 * (int64_t)M * (a.T + 1) * r : nullptr;
-    for (int j = tid; j < M; j += ADVI_NT) {   // (2M components: M blocks, none ragged)
+    for (int j = tid; j < M; j += SAMPLER_NT) {   // (not for_owned: 2M components in M full blocks, none ragged, block by block)
       double n[2];
       philox_normal2_purpose(a.seed, chain, 0, 2u, (uint32_t)j, n[0], n[1]);
       for (int c = 0; c < 2; ++c) {
@@ -79,34 +78,26 @@ __global__ __launch_bounds__(ADVI_NT) void advi_draw_kernel(AdviRun a, double si
       }
     }
     double* ring = a.ring + (int64_t)a.W * 2 * M * r;
-    for (int64_t i = tid; i < (int64_t)a.W * 2 * M; i += ADVI_NT) ring[i] = 0.0;
+    for (int64_t i = tid; i < (int64_t)a.W * 2 * M; i += SAMPLER_NT) ring[i] = 0.0;
     __syncthreads();   // (theta_0 was written block by block, the points read it component by component)
     advi_form_points(a, r, chain, 0);
   }
   if (final) {
     for (int64_t i = blockIdx.y; i < D; i += gridDim.y) {
       double* zo = Z_out + (int64_t)M * (i + D * r);
-      for (int j = tid; j < nblk; j += ADVI_NT) {
-        double n[2];
-        philox_normal2_purpose(a.seed, chain, (uint64_t)i, 4u, (uint32_t)j, n[0], n[1]);
-        for (int c = 0; c < 2; ++c) {
-          const int m = 2 * j + c;
-          if (m < M) zo[m] = theta[m] + exp(theta[M + m]) * n[c];
-        }
-      }
+      for_owned_normal(M, a.seed, chain, (uint64_t)i, 4u, [&](int m, double n) { zo[m] = theta[m] + exp(theta[M + m]) * n; });
     }
   }
 }
 
 // Step t of every run, given (lp_k, g_k) at its points: elbo_t, d, the ring write, s, theta_{t+1}, the trace column t + 1 and --
 // in the same launch -- the points of step t + 1 from the state just written.
-__global__ __launch_bounds__(ADVI_NT) void advi_update_kernel(AdviRun a, const double* __restrict__ lp, const double* __restrict__ g,
+__global__ __launch_bounds__(SAMPLER_NT) void advi_update_kernel(AdviRun a, const double* __restrict__ lp, const double* __restrict__ g,
                                                               double eta_opt, double tau, int64_t t, double* __restrict__ elbo_out,
                                                               int form_next) {
-  __shared__ double red[ADVI_NT / 64];
+  __shared__ double red[SAMPLER_WAVES];
   const int64_t r = blockIdx.x;
-  const int tid = threadIdx.x;
-  const int M = a.M, S = a.S, W = a.W, nblk = (M + 1) >> 1;
+  const int M = a.M, S = a.S, W = a.W;
   const uint32_t chain = (uint32_t)(a.chain_id0 + (int32_t)r);
   double* theta = a.theta + 2 * (int64_t)M * r;
   const double* eta = a.eta + (int64_t)M * S * r;
@@ -115,16 +106,10 @@ __global__ __launch_bounds__(ADVI_NT) void advi_update_kernel(AdviRun a, const d
   const double Sd = (double)S;
   if (elbo_out) {
     double so = 0.0;
-    for (int j = tid; j < nblk; j += ADVI_NT)
-      for (int c = 0; c < 2; ++c) {
-        const int m = 2 * j + c;
-        if (m < M) so += theta[M + m];
-      }
-    so = chain_wave_sum(so);
-    if ((tid & 63) == 0) red[tid >> 6] = so;
-    __syncthreads();
-    if (tid == 0) {
-      const double H = ((double)M * (ADVI_LOG_2PI + 1.0)) / 2.0 + ((red[0] + red[1]) + (red[2] + red[3]));
+    for_owned(M, [&](int m) { so += theta[M + m]; });
+    so = block_sum<true>(so, red);   // (elbo_out is a kernel argument: the whole workgroup reaches the barrier or none of it does)
+    if (threadIdx.x == 0) {
+      const double H = ((double)M * (ADVI_LOG_2PI + 1.0)) / 2.0 + so;
       double e = lp[0] / Sd + H;
       for (int k = 1; k < S; ++k) e += lp[k] / Sd;
       elbo_out[t + a.T * r] = e;
@@ -134,29 +119,25 @@ __global__ __launch_bounds__(ADVI_NT) void advi_update_kernel(AdviRun a, const d
   double* ring = a.ring + (int64_t)W * 2 * M * r;
   double* trace = a.trace_out ? a.trace_out + 2 * (int64_t)M * ((t + 1) + (a.T + 1) * r) : nullptr;
   const int slot = (int)(t % W);
-  for (int j = tid; j < nblk; j += ADVI_NT) {
-    for (int c = 0; c < 2; ++c) {
-      const int m = 2 * j + c;
-      if (m >= M) continue;
-      const double sg = exp(theta[M + m]);
-      double sm = 0.0, sw = 0.0;
-      for (int k = 0; k < S; ++k) {
-        const double gv = g[(int64_t)M * k + m];
-        sm += gv;
-        sw += (gv * eta[(int64_t)M * k + m]) * sg;
-      }
-      const double d[2] = {-(sm / Sd), -(sw / Sd) - 1.0};
-      for (int h = 0; h < 2; ++h) {
-        const int p = h * M + m;
-        ring[(int64_t)slot * 2 * M + p] = d[h] * d[h];
-        double s = 0.0;
-        for (int w = 0; w < W; ++w) s += ring[(int64_t)w * 2 * M + p];
-        const double v = theta[p] - d[h] * (eta_opt / (tau + sqrt(s)));
-        theta[p] = v;
-        if (trace) trace[p] = v;
-      }
+  for_owned(M, [&](int m) {
+    const double sg = exp(theta[M + m]);
+    double sm = 0.0, sw = 0.0;
+    for (int k = 0; k < S; ++k) {
+      const double gv = g[(int64_t)M * k + m];
+      sm += gv;
+      sw += (gv * eta[(int64_t)M * k + m]) * sg;
     }
-  }
+    const double d[2] = {-(sm / Sd), -(sw / Sd) - 1.0};
+    for (int h = 0; h < 2; ++h) {
+      const int p = h * M + m;
+      ring[(int64_t)slot * 2 * M + p] = d[h] * d[h];
+      double s = 0.0;
+      for (int w = 0; w < W; ++w) s += ring[(int64_t)w * 2 * M + p];
+      const double v = theta[p] - d[h] * (eta_opt / (tau + sqrt(s)));
+      theta[p] = v;
+      if (trace) trace[p] = v;
+    }
+  });
   // (the thread that wrote mu_m and omega_m is the one that reads them here: no barrier)
   if (form_next) advi_form_points(a, r, chain, (uint64_t)(t + 1));
 }
@@ -164,12 +145,12 @@ __global__ __launch_bounds__(ADVI_NT) void advi_update_kernel(AdviRun a, const d
 void launch_advi_draw(hipStream_t st, const AdviRun& a, int32_t R, double sigma_z, bool first, bool final, double* Z_out, int64_t D) {
   // (first writes theta: one workgroup per run; the draws only read it and are spread over grid.y)
   const unsigned gy = final && !first ? (unsigned)std::min<int64_t>(std::max<int64_t>(D, 1), 128) : 1u;
-  hipLaunchKernelGGL(advi_draw_kernel, dim3((unsigned)R, gy), dim3(ADVI_NT), 0, st, a, sigma_z, first ? 1 : 0, final ? 1 : 0, Z_out, D);
+  hipLaunchKernelGGL(advi_draw_kernel, dim3((unsigned)R, gy), dim3(SAMPLER_NT), 0, st, a, sigma_z, first ? 1 : 0, final ? 1 : 0, Z_out, D);
 }
 
 void launch_advi_update(hipStream_t st, const AdviRun& a, int32_t R, const double* lp, const double* g, double eta_opt, double tau,
                         int64_t t, double* elbo_out, bool form_next) {
-  hipLaunchKernelGGL(advi_update_kernel, dim3((unsigned)R), dim3(ADVI_NT), 0, st, a, lp, g, eta_opt, tau, t, elbo_out, form_next ? 1 : 0);
+  hipLaunchKernelGGL(advi_update_kernel, dim3((unsigned)R), dim3(SAMPLER_NT), 0, st, a, lp, g, eta_opt, tau, t, elbo_out, form_next ? 1 : 0);
 }
 
 }  // namespace si

@@ -24,15 +24,13 @@
 //            window the Welford update with the KEPT state; at a window's close Minv = n / (n + 5) var + 1e-3 5 / (n + 5) (n >= 2),
 //            the window emptied and the dual averaging restarted at the current eps; after step n_adapts eps = exp(log_eps_bar)
 //
-// The helpers that si_sample_nuts shares (the fixed-order sum, the half kick and drift, the adaptor's update) are hmc_device.h's.
-// Kernels: one workgroup of 256 threads per chain; the value and gradient at the trial points and proposals come from the caller's
-// launches between them (si_sample_hmc, capi_hmc.hip).  Component ownership and the order of every sum over m are kernels_mala.hip's:
-// thread i owns the components 2j, 2j + 1 of its Philox blocks j = i, i + 256, ... and adds them in that order, the wave sums are
-// chain_wave_sum's, the four wave sums are added as (r0 + r1) + (r2 + r3) -- a chain's bits depend on M alone, not on the number of
-// chains, its column, the pass or the run.  Which phase of the adaptation a step is in is the host's knowledge and arrives as kernel
-// arguments; there is no schedule on the device.  Compiled without contraction of a * b + c, like kernels_mala.hip.
-#include "hmc_device.h"
-#include "philox.h"
+// Kernels: one workgroup of SAMPLER_NT threads per chain; the value and gradient at the trial points and proposals come from the
+// caller's launches between them (si_sample_hmc, capi_hmc.hip).  Component ownership, the fixed order of every sum over m, the
+// keep-and-record step, the half kick and drift and the adaptor's update are sampler_device.h's, shared with the other samplers -- a
+// chain's bits depend on M alone, not on the number of chains, its column, the pass or the run.  Which phase of the adaptation a step
+// is in is the host's knowledge and arrives as kernel arguments; there is no schedule on the device.  Compiled without contraction
+// of a * b + c, like kernels_mala.hip.
+#include "sampler_device.h"
 
 namespace si {
 
@@ -43,53 +41,30 @@ enum { HMC_S_START = 0, HMC_S_DIRECTION = 1, HMC_S_CROSS = 2, HMC_S_BISECT = 3 }
 __device__ __forceinline__ void hmc_propose_chain(const double* __restrict__ z, const double* __restrict__ g, double* __restrict__ zp,
                                                   double* __restrict__ rh, const double* __restrict__ minv, HmcChain* ch, double eps,
                                                   int32_t M, uint64_t seed, uint32_t chain, uint64_t step, double* red) {
-  const int nblk = (M + 1) >> 1;
   double kk = 0.0;
-  for (int j = threadIdx.x; j < nblk; j += HMC_NT) {
-    double n[2];
-    philox_normal2_purpose(seed, chain, step, HMC_P_MOMENTUM, (uint32_t)j, n[0], n[1]);
-    for (int k = 0; k < 2; ++k) {
-      const int m = 2 * j + k;
-      if (m < M) {
-        const double mi = minv[m];
-        kk += hmc_kick_drift(m, n[k] / sqrt(mi), eps, mi, z, g, rh, zp);
-      }
-    }
-  }
-  const double ksum = hmc_block_sum(kk, red);
+  for_owned_normal(M, seed, chain, step, HMC_P_MOMENTUM, [&](int m, double n) {
+    const double mi = minv[m];
+    kk += hmc_kick_drift(m, n / sqrt(mi), eps, mi, z, g, rh, zp);
+  });
+  const double ksum = block_sum(kk, red);
   if (threadIdx.x == 0) ch->k0 = 0.5 * ksum;
 }
 
 // 1/2 sum (minv rp) rp with rp = rh + (e / 2) gp
 __device__ __forceinline__ double hmc_kinetic_after(const double* __restrict__ rh, const double* __restrict__ gp,
                                                     const double* __restrict__ minv, double e, int32_t M, double* red) {
-  const int nblk = (M + 1) >> 1;
   double kk = 0.0;
-  for (int j = threadIdx.x; j < nblk; j += HMC_NT) {
-    for (int k = 0; k < 2; ++k) {
-      const int m = 2 * j + k;
-      if (m < M) {
-        const double rp = rh[m] + (0.5 * e) * gp[m];
-        kk += (minv[m] * rp) * rp;
-      }
-    }
-  }
-  return 0.5 * hmc_block_sum(kk, red);
+  for_owned(M, [&](int m) {
+    const double rp = rh[m] + (0.5 * e) * gp[m];
+    kk += (minv[m] * rp) * rp;
+  });
+  return 0.5 * block_sum(kk, red);
 }
 
-__global__ __launch_bounds__(HMC_NT) void hmc_init_kernel(HmcRun a) {
+__global__ __launch_bounds__(SAMPLER_NT) void hmc_init_kernel(HmcRun a) {
   const int64_t c = blockIdx.x;
-  const uint32_t chain = (uint32_t)(a.chain_id0 + (int32_t)c);
   double* zp = a.zp + c * a.M;
-  const int nblk = (a.M + 1) >> 1;
-  for (int j = threadIdx.x; j < nblk; j += HMC_NT) {
-    double n[2];
-    philox_normal2(a.seed, chain, 0, (uint32_t)j, n[0], n[1]);
-    for (int k = 0; k < 2; ++k) {
-      const int m = 2 * j + k;
-      if (m < a.M) zp[m] = a.sigma_z * n[k];
-    }
-  }
+  for_owned_normal(a.M, a.seed, (uint32_t)(a.chain_id0 + (int32_t)c), 0, 0u, [&](int m, double n) { zp[m] = a.sigma_z * n; });
   if (threadIdx.x == 0) {
     HmcChain& ch = a.chain[c];
     ch.s_phase = HMC_S_START;
@@ -101,8 +76,8 @@ __global__ __launch_bounds__(HMC_NT) void hmc_init_kernel(HmcRun a) {
 
 // One round of the step-size search of every chain: the state machine consumes (lpp, gp) at the last trial point and forms the next
 // trial point in zp.  A finished chain returns at once and keeps its last point.
-__global__ __launch_bounds__(HMC_NT) void hmc_search_kernel(HmcRun a, int32_t* __restrict__ open) {
-  __shared__ double red[HMC_NT / 64];
+__global__ __launch_bounds__(SAMPLER_NT) void hmc_search_kernel(HmcRun a, int32_t* __restrict__ open) {
+  __shared__ double red[SAMPLER_WAVES];
   __shared__ double trial_s;
   __shared__ int done_s;
   const int64_t c = blockIdx.x;
@@ -113,33 +88,19 @@ __global__ __launch_bounds__(HMC_NT) void hmc_search_kernel(HmcRun a, int32_t* _
   if (ch->s_done) return;   // (uniform over the workgroup: written by thread 0 of an earlier launch)
   double *z = a.z + c * M, *g = a.g + c * M, *zp = a.zp + c * M, *rh = a.rh + c * M, *minv = a.minv + c * M;
   const double* gp = a.gp + c * M;
-  const int nblk = (M + 1) >> 1;
   const int phase = ch->s_phase;
   const double lpp = a.lpp[c];
   if (phase == HMC_S_START) {
     // (lpp, gp) are the value and gradient at z_0 = zp: the chain's state, column 0 of the outputs, H at (z_0, rho)
-    const int64_t obase = (int64_t)M * ((a.itr + 1) * c);
     double rr = 0.0;
-    for (int j = tid; j < nblk; j += HMC_NT) {
-      double n[2];
-      philox_normal2_purpose(a.seed, chain, 0, HMC_P_SEARCH, (uint32_t)j, n[0], n[1]);
-      for (int k = 0; k < 2; ++k) {
-        const int m = 2 * j + k;
-        if (m < M) {
-          const double zv = zp[m], gv = gp[m];
-          z[m] = zv;
-          g[m] = gv;
-          minv[m] = 1.0;
-          a.wmean[c * M + m] = 0.0;
-          a.wm2[c * M + m] = 0.0;
-          a.Z_out[obase + m] = zv;
-          if (a.G_out) a.G_out[obase + m] = gv;
-          if (a.Minv_out) a.Minv_out[obase + m] = 1.0;
-          rr += n[k] * n[k];
-        }
-      }
-    }
-    const double rsum = hmc_block_sum(rr, red);
+    for_owned_normal(M, a.seed, chain, 0, HMC_P_SEARCH, [&](int m, double n) {
+      minv[m] = 1.0;
+      a.wmean[c * M + m] = 0.0;
+      a.wm2[c * M + m] = 0.0;
+      rr += n * n;
+    });
+    keep_and_record(a, c, (a.itr + 1) * c, zp, gp);
+    const double rsum = block_sum(rr, red);
     if (tid == 0) {
       a.lp[c] = lpp;
       a.lp_out[(a.itr + 1) * c] = lpp;
@@ -231,22 +192,15 @@ __global__ __launch_bounds__(HMC_NT) void hmc_search_kernel(HmcRun a, int32_t* _
   __syncthreads();
   if (done_s) return;
   const double e = trial_s;
-  for (int j = tid; j < nblk; j += HMC_NT) {
-    double n[2];
-    philox_normal2_purpose(a.seed, chain, 0, HMC_P_SEARCH, (uint32_t)j, n[0], n[1]);
-    for (int k = 0; k < 2; ++k) {
-      const int m = 2 * j + k;
-      if (m < M) (void)hmc_kick_drift(m, n[k], e, 1.0, z, g, rh, zp);
-    }
-  }
+  for_owned_normal(M, a.seed, chain, 0, HMC_P_SEARCH, [&](int m, double n) { (void)hmc_kick_drift(m, n, e, 1.0, z, g, rh, zp); });
   if (tid == 0) {
     ch->s_trial = e;
     atomicAdd(open, 1);
   }
 }
 
-__global__ __launch_bounds__(HMC_NT) void hmc_propose_kernel(HmcRun a, uint64_t step) {
-  __shared__ double red[HMC_NT / 64];
+__global__ __launch_bounds__(SAMPLER_NT) void hmc_propose_kernel(HmcRun a, uint64_t step) {
+  __shared__ double red[SAMPLER_WAVES];
   const int64_t c = blockIdx.x;
   const int32_t M = a.M;
   HmcChain* ch = a.chain + c;
@@ -256,9 +210,9 @@ __global__ __launch_bounds__(HMC_NT) void hmc_propose_kernel(HmcRun a, uint64_t 
 
 // Transition `step` of every chain given (lpp, gp) at zp: K1, a, the decision, the next state, column `step` of the outputs, the
 // adaptor's update and -- in the same launch -- the proposal of transition step + 1 from the state and the (eps, Minv) just set.
-__global__ __launch_bounds__(HMC_NT) void hmc_accept_kernel(HmcRun a, uint64_t step, int adapting, int in_window, int window_close,
+__global__ __launch_bounds__(SAMPLER_NT) void hmc_accept_kernel(HmcRun a, uint64_t step, int adapting, int in_window, int window_close,
                                                             int last_adapt, int propose_next) {
-  __shared__ double red[HMC_NT / 64];
+  __shared__ double red[SAMPLER_WAVES];
   __shared__ int accept_s;
   __shared__ double eps_next_s, wn_s;
   const int64_t c = blockIdx.x;
@@ -267,9 +221,7 @@ __global__ __launch_bounds__(HMC_NT) void hmc_accept_kernel(HmcRun a, uint64_t s
   const uint32_t chain = (uint32_t)(a.chain_id0 + (int32_t)c);
   HmcChain* ch = a.chain + c;
   double *z = a.z + c * M, *g = a.g + c * M, *zp = a.zp + c * M, *rh = a.rh + c * M, *minv = a.minv + c * M;
-  double *wmean = a.wmean + c * M, *wm2 = a.wm2 + c * M;
   const double* gp = a.gp + c * M;
-  const int nblk = (M + 1) >> 1;
   const double eps = ch->eps;
   const int64_t col = (int64_t)step + (a.itr + 1) * c;
   const double k1 = hmc_kinetic_after(rh, gp, minv, eps, M, red);
@@ -294,43 +246,26 @@ __global__ __launch_bounds__(HMC_NT) void hmc_accept_kernel(HmcRun a, uint64_t s
   }
   __syncthreads();
   const bool accept = accept_s != 0;
-  const double wn = wn_s;   // the window's count INCLUDING this step
-  const int64_t obase = (int64_t)M * col;
-  // (thread i owns the components 2j, 2j + 1 of its j in every phase: nothing below reads what another thread writes)
-  for (int j = tid; j < nblk; j += HMC_NT) {
-    for (int k = 0; k < 2; ++k) {
-      const int m = 2 * j + k;
-      if (m < M) {
-        const double zv = accept ? zp[m] : z[m];
-        const double gv = accept ? gp[m] : g[m];
-        const double mi = minv[m];
-        z[m] = zv;
-        g[m] = gv;
-        a.Z_out[obase + m] = zv;
-        if (a.G_out) a.G_out[obase + m] = gv;
-        if (a.Minv_out) a.Minv_out[obase + m] = mi;
-        if (adapting && in_window) hmc_adapt_component(m, zv, wn, window_close, minv, wmean, wm2);
-      }
-    }
-  }
+  // (thread i owns the same components in every phase: nothing below reads what another thread writes)
+  keep_and_record(a, c, col, accept ? zp : z, accept ? gp : g, adapting && in_window, wn_s /* INCLUDING this step */, window_close);
   if (propose_next) hmc_propose_chain(z, g, zp, rh, minv, ch, eps_next_s, M, a.seed, chain, step + 1, red);
 }
 
 void launch_hmc_init(hipStream_t st, const HmcRun& a, int32_t C) {
-  hipLaunchKernelGGL(hmc_init_kernel, dim3((unsigned)C), dim3(HMC_NT), 0, st, a);
+  hipLaunchKernelGGL(hmc_init_kernel, dim3((unsigned)C), dim3(SAMPLER_NT), 0, st, a);
 }
 
 void launch_hmc_search(hipStream_t st, const HmcRun& a, int32_t C, int32_t* open) {
-  hipLaunchKernelGGL(hmc_search_kernel, dim3((unsigned)C), dim3(HMC_NT), 0, st, a, open);
+  hipLaunchKernelGGL(hmc_search_kernel, dim3((unsigned)C), dim3(SAMPLER_NT), 0, st, a, open);
 }
 
 void launch_hmc_propose(hipStream_t st, const HmcRun& a, int32_t C, uint64_t step) {
-  hipLaunchKernelGGL(hmc_propose_kernel, dim3((unsigned)C), dim3(HMC_NT), 0, st, a, step);
+  hipLaunchKernelGGL(hmc_propose_kernel, dim3((unsigned)C), dim3(SAMPLER_NT), 0, st, a, step);
 }
 
 void launch_hmc_accept(hipStream_t st, const HmcRun& a, int32_t C, uint64_t step, bool adapting, bool in_window, bool window_close,
                        bool last_adapt, bool propose_next) {
-  hipLaunchKernelGGL(hmc_accept_kernel, dim3((unsigned)C), dim3(HMC_NT), 0, st, a, step, adapting ? 1 : 0, in_window ? 1 : 0,
+  hipLaunchKernelGGL(hmc_accept_kernel, dim3((unsigned)C), dim3(SAMPLER_NT), 0, st, a, step, adapting ? 1 : 0, in_window ? 1 : 0,
                      window_close ? 1 : 0, last_adapt ? 1 : 0, propose_next ? 1 : 0);
 }
 

@@ -9,130 +9,73 @@
 //            accept: (z, lp, g) = (zp, lpp, gp);  sample t = (z, lp, g)
 //
 // Two kernels, one workgroup per chain.  The value and gradient at the proposals come from the caller's launches between them
-// (si_sample_mala, capi_mala.hip).  Every sum over m has a fixed order that depends on M alone: thread i adds its components
-// 2j, 2j + 1 for j = i, i + 256, ... in that order, the wave sums are chain_wave_sum's, the four wave sums are added as
-// (r0 + r1) + (r2 + r3) -- so a chain's bits do not depend on the number of chains, on its column or on the run.  The file is
-// compiled without contraction of a * b + c, like K1: every product and sum here is rounded by itself, as the host restatement's.
-#include "chain_common.h"
-#include "philox.h"
-#include "si_internal.h"
+// (si_sample_mala, capi_mala.hip).  Component ownership and the fixed order of every sum over m are sampler_device.h's -- so a
+// chain's bits do not depend on the number of chains, on its column or on the run.  The file is compiled without contraction of
+// a * b + c, like K1: every product and sum here is rounded by itself, as the host restatement's.
+#include "sampler_device.h"
 
 namespace si {
 
-static constexpr int MALA_NT = 256;
-
-// zprop[:, c] = z[:, c] + h g[:, c] + sigma_z n_step  (first: z = sigma_z n_0, nothing is read)
-__device__ __forceinline__ void mala_propose_chain(const double* __restrict__ z, const double* __restrict__ g, double* __restrict__ zprop,
-                                                   int32_t M, double sigma_z, double h, uint64_t seed, uint32_t chain, uint64_t step,
-                                                   bool first) {
-  const int nblk = (M + 1) >> 1;
-  for (int j = threadIdx.x; j < nblk; j += MALA_NT) {
-    double n[2];
-    philox_normal2(seed, chain, step, (uint32_t)j, n[0], n[1]);
-    for (int k = 0; k < 2; ++k) {
-      const int m = 2 * j + k;
-      if (m < M) zprop[m] = first ? sigma_z * n[k] : (z[m] + h * g[m]) + sigma_z * n[k];
-    }
-  }
+// zp = z + h g + sigma_z n_step for the chain of this workgroup  (first: z = sigma_z n_0, nothing is read)
+__device__ __forceinline__ void mala_propose_chain(const MalaRun& a, int64_t c, uint64_t step, bool first) {
+  const double *z = a.z + c * a.M, *g = a.g + c * a.M;
+  double* zp = a.zp + c * a.M;
+  for_owned_normal(a.M, a.seed, (uint32_t)(a.chain_id0 + (int32_t)c), step, 0u, [&](int m, double n) {
+    zp[m] = first ? a.sigma_z * n : (z[m] + a.h * g[m]) + a.sigma_z * n;
+  });
 }
 
-__global__ __launch_bounds__(MALA_NT) void mala_propose_kernel(const double* __restrict__ z, const double* __restrict__ g,
-                                                               double* __restrict__ zprop, int32_t M, double sigma_z, double h,
-                                                               uint64_t seed, int32_t chain_id0, uint64_t step, int first) {
-  const int64_t c = blockIdx.x;
-  mala_propose_chain(z + c * M, g + c * M, zprop + c * M, M, sigma_z, h, seed, (uint32_t)(chain_id0 + (int32_t)c), step, first != 0);
+__global__ __launch_bounds__(SAMPLER_NT) void mala_propose_kernel(MalaRun a, uint64_t step, int first) {
+  mala_propose_chain(a, blockIdx.x, step, first != 0);
 }
 
-// Transition `step` of every chain, given (lpp, gp) at zprop: logq, the decision, the next state, sample `step` of Z / lp / G,
+// Transition `step` of every chain, given (lpp, gp) at zp: logq, the decision, the next state, sample `step` of Z / lp / G,
 // the accept count, and -- in the same launch -- the proposal of transition step + 1 from the state just chosen.
-__global__ __launch_bounds__(MALA_NT) void mala_accept_kernel(double* __restrict__ z, double* __restrict__ lp, double* __restrict__ g,
-                                                              double* __restrict__ zprop, const double* __restrict__ lpp,
-                                                              const double* __restrict__ gp, int64_t* __restrict__ nacc, int32_t M,
-                                                              double sigma_z, double h, uint64_t seed, int32_t chain_id0, uint64_t step,
-                                                              double* __restrict__ Z_out, double* __restrict__ lp_out,
-                                                              double* __restrict__ G_out, int64_t itr, int propose_next) {
-  __shared__ double red[2][MALA_NT / 64];
-  __shared__ int accept_s;
+// The decision's scalars are computed by every thread from the same inputs (the sums are broadcast by block_sum); thread 0 writes
+// them.  lp[c] is read BEFORE the barriers of the sums: thread 0 writes it after them.
+__global__ __launch_bounds__(SAMPLER_NT) void mala_accept_kernel(MalaRun a, uint64_t step, int propose_next) {
+  __shared__ double red[2 * SAMPLER_WAVES];
   const int64_t c = blockIdx.x;
-  const int tid = threadIdx.x;
-  const uint32_t chain = (uint32_t)(chain_id0 + (int32_t)c);
-  z += c * M;
-  g += c * M;
-  zprop += c * M;
-  gp += c * M;
-  const int nblk = (M + 1) >> 1;
-  if (step > 0) {
-    double ff = 0.0, bb = 0.0;
-    for (int j = tid; j < nblk; j += MALA_NT) {
-      for (int k = 0; k < 2; ++k) {
-        const int m = 2 * j + k;
-        if (m < M) {
-          const double zv = z[m], zpv = zprop[m];
-          const double fwd = (zpv - zv) - h * g[m];
-          const double bwd = (zv - zpv) - h * gp[m];
-          ff += fwd * fwd;
-          bb += bwd * bwd;
-        }
-      }
-    }
-    ff = chain_wave_sum(ff);
-    bb = chain_wave_sum(bb);
-    if ((tid & 63) == 0) {
-      red[0][tid >> 6] = ff;
-      red[1][tid >> 6] = bb;
-    }
+  const int32_t M = a.M;
+  double *z = a.z + c * M, *g = a.g + c * M;
+  const double *zp = a.zp + c * M, *gp = a.gp + c * M;
+  const double lp_new = a.lpp[c];
+  bool accept = true;
+  if (step > 0) {   // (uniform over the workgroup)
+    const double lp_old = a.lp[c];
+    double s[2] = {0.0, 0.0};   // fwd.fwd, bwd.bwd
+    for_owned(M, [&](int m) {
+      const double zv = z[m], zpv = zp[m];
+      const double fwd = (zpv - zv) - a.h * g[m];
+      const double bwd = (zv - zpv) - a.h * gp[m];
+      s[0] += fwd * fwd;
+      s[1] += bwd * bwd;
+    });
+    block_sum(s, red);
+    const double logq = -(s[1] - s[0]) / (2.0 * (a.sigma_z * a.sigma_z));
+    const double e = philox_randexp(a.seed, (uint32_t)(a.chain_id0 + (int32_t)c), step);
+    accept = (-e < (lp_new - lp_old) + logq);   // NaN compares false => reject
   }
-  __syncthreads();
-  if (tid == 0) {
-    bool accept = true;
-    const double lp_new = lpp[c];
-    if (step > 0) {
-      const double fsum = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-      const double bsum = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-      const double logq = -(bsum - fsum) / (2.0 * (sigma_z * sigma_z));
-      const double e = philox_randexp(seed, chain, step);
-      accept = (-e < (lp_new - lp[c]) + logq);   // NaN compares false => reject
-    }
-    const double lp_keep = accept ? lp_new : lp[c];
-    lp[c] = lp_keep;
-    lp_out[(int64_t)step + itr * c] = lp_keep;
+  const int64_t col = (int64_t)step + a.itr * c;
+  if (threadIdx.x == 0) {
+    const double lp_keep = accept ? lp_new : a.lp[c];
+    a.lp[c] = lp_keep;
+    a.lp_out[col] = lp_keep;
     if (step == 0)
-      nacc[c] = 0;
+      a.nacc[c] = 0;
     else if (accept)
-      nacc[c] += 1;
-    accept_s = accept ? 1 : 0;
+      a.nacc[c] += 1;
   }
-  __syncthreads();
-  const bool accept = accept_s != 0;
-  const int64_t obase = (int64_t)M * ((int64_t)step + itr * c);
-  // (thread i owns the components 2j, 2j + 1 of its j in every phase: nothing below reads what another thread writes)
-  for (int j = tid; j < nblk; j += MALA_NT) {
-    for (int k = 0; k < 2; ++k) {
-      const int m = 2 * j + k;
-      if (m < M) {
-        const double zv = accept ? zprop[m] : z[m];
-        const double gv = accept ? gp[m] : g[m];
-        z[m] = zv;
-        g[m] = gv;
-        Z_out[obase + m] = zv;
-        if (G_out) G_out[obase + m] = gv;
-      }
-    }
-  }
-  if (propose_next) mala_propose_chain(z, g, zprop, M, sigma_z, h, seed, chain, step + 1, false);
+  keep_and_record(M, accept ? zp : z, accept ? gp : g, z, g, a.Z_out + M * col, a.G_out ? a.G_out + M * col : nullptr);
+  if (propose_next) mala_propose_chain(a, c, step + 1, false);
 }
 
-void launch_mala_propose(hipStream_t st, const double* z, const double* g, double* zprop, int32_t M, int32_t C, double sigma_z,
-                         uint64_t seed, int32_t chain_id0, uint64_t step, bool first) {
-  hipLaunchKernelGGL(mala_propose_kernel, dim3((unsigned)C), dim3(MALA_NT), 0, st, z, g, zprop, M, sigma_z, 0.5 * (sigma_z * sigma_z),
-                     seed, chain_id0, step, first ? 1 : 0);
+void launch_mala_propose(hipStream_t st, const MalaRun& a, int32_t C, uint64_t step, bool first) {
+  hipLaunchKernelGGL(mala_propose_kernel, dim3((unsigned)C), dim3(SAMPLER_NT), 0, st, a, step, first ? 1 : 0);
 }
 
-void launch_mala_accept(hipStream_t st, double* z, double* lp, double* g, double* zprop, const double* lpp, const double* gp,
-                        int64_t* nacc, int32_t M, int32_t C, double sigma_z, uint64_t seed, int32_t chain_id0, uint64_t step,
-                        double* Z_out, double* lp_out, double* G_out, int64_t itr, bool propose_next) {
-  hipLaunchKernelGGL(mala_accept_kernel, dim3((unsigned)C), dim3(MALA_NT), 0, st, z, lp, g, zprop, lpp, gp, nacc, M, sigma_z,
-                     0.5 * (sigma_z * sigma_z), seed, chain_id0, step, Z_out, lp_out, G_out, itr, propose_next ? 1 : 0);
+void launch_mala_accept(hipStream_t st, const MalaRun& a, int32_t C, uint64_t step, bool propose_next) {
+  hipLaunchKernelGGL(mala_accept_kernel, dim3((unsigned)C), dim3(SAMPLER_NT), 0, st, a, step, propose_next ? 1 : 0);
 }
 
 }  // namespace si

@@ -1,7 +1,7 @@
 // NUTS (reference src/space_inference.jl:139-160: AdvancedHMC 0.2.27 `NUTS{MultinomialTS, GeneralisedNoUTurn}(Leapfrog(eps))` under
 // `StanHMCAdaptor`) with the trajectory tree, the step size, the metric and the adaptor state on the device: samplers.nuts_iter --
 // the leaf-by-leaf restatement of samplers.nuts [upstream, unverifiable offline] -- on the Philox stream of philox.h.  Column 0, the
-// step-size search and the adaptor are si_sample_hmc's (kernels_hmc.hip, hmc_device.h), shared, not copied.
+// step-size search and the adaptor are si_sample_hmc's (kernels_hmc.hip, sampler_device.h), shared, not copied.
 //
 //   chain c draws from Philox chain chain_id0 + c:  purposes 0, 5, 6 as si_sample_hmc;  purpose 7, step t, block j = the doubling at
 //   depth j: direction +1 iff u53(x1, x0) < 0.5, progressive pick with u53(x3, x2);  purpose 8, step t, block 16 leaf + level = the
@@ -25,13 +25,12 @@
 // Where things live: the tree's ends, rho, the candidate and the stack's vectors (4 M doubles per entry) are in global memory, M x C
 // arrays that stay in L2 between the rounds -- at M = 513 one chain's stack alone is 164 KB, more than a workgroup's LDS, and every
 // round is a separate launch anyway, so nothing could stay in LDS or registers from one leaf to the next.  Thread i owns the
-// components 2j, 2j + 1 of j = i, i + 256, ... in every phase (kernels_hmc.hip's ownership), so no vector element is read by a
-// thread other than the one that wrote it: merges are component-parallel and need no barrier apart from hmc_block_sum's.  Every
-// scalar of the tree is computed redundantly by every thread from the same inputs (the sums are broadcast by hmc_block_sum) and kept
+// same components in every phase (sampler_device.h's ownership: for_owned), so no vector element is read by a thread other
+// than the one that wrote it: merges are component-parallel and need no barrier apart from block_sum's.  Every
+// scalar of the tree is computed redundantly by every thread from the same inputs (the sums are broadcast by block_sum) and kept
 // in registers through the launch; thread 0 writes them back.  Entries below the top were written by earlier launches.
 // Compiled without contraction of a * b + c, like kernels_hmc.hip.
-#include "hmc_device.h"
-#include "philox.h"
+#include "sampler_device.h"
 
 namespace si {
 
@@ -65,16 +64,11 @@ __device__ __forceinline__ void nuts_next_point(const NutsPtrs& p, int dir, doub
   const double* er = dir > 0 ? p.rq : p.rm;
   const double* eg = dir > 0 ? p.gq : p.gm;
   const double ve = (double)dir * eps;
-  const int nblk = (M + 1) >> 1;
-  for (int j = threadIdx.x; j < nblk; j += HMC_NT)
-    for (int k = 0; k < 2; ++k) {
-      const int m = 2 * j + k;
-      if (m < M) (void)hmc_kick_drift(m, er[m], ve, minv[m], ez, eg, rh, zp);
-    }
+  for_owned(M, [&](int m) { (void)hmc_kick_drift(m, er[m], ve, minv[m], ez, eg, rh, zp); });
 }
 
-__global__ __launch_bounds__(HMC_NT) void nuts_begin_kernel(HmcRun a, NutsRun n, uint64_t step, int first) {
-  __shared__ double red[HMC_NT / 64];
+__global__ __launch_bounds__(SAMPLER_NT) void nuts_begin_kernel(HmcRun a, NutsRun n, uint64_t step, int first) {
+  __shared__ double red[SAMPLER_WAVES];
   const int64_t c = blockIdx.x;
   const int32_t M = a.M;
   const uint32_t chain = (uint32_t)(a.chain_id0 + (int32_t)c);
@@ -82,23 +76,15 @@ __global__ __launch_bounds__(HMC_NT) void nuts_begin_kernel(HmcRun a, NutsRun n,
   NutsChain* tr = n.tree + c;
   const NutsPtrs p = nuts_ptrs(n, c, M);
   const double *z = a.z + c * M, *g = a.g + c * M, *minv = a.minv + c * M;
-  const int nblk = (M + 1) >> 1;
   double kk = 0.0;
-  for (int j = threadIdx.x; j < nblk; j += HMC_NT) {
-    double nn[2];
-    philox_normal2_purpose(a.seed, chain, step, HMC_P_MOMENTUM, (uint32_t)j, nn[0], nn[1]);
-    for (int k = 0; k < 2; ++k) {
-      const int m = 2 * j + k;
-      if (m < M) {
-        const double mi = minv[m], r = nn[k] / sqrt(mi), zv = z[m], gv = g[m];
-        kk += (mi * r) * r;
-        p.zm[m] = zv, p.zq[m] = zv, p.zc[m] = zv;
-        p.gm[m] = gv, p.gq[m] = gv, p.gc[m] = gv;
-        p.rm[m] = r, p.rq[m] = r, p.rho[m] = r;
-      }
-    }
-  }
-  const double ksum = hmc_block_sum(kk, red);
+  for_owned_normal(M, a.seed, chain, step, HMC_P_MOMENTUM, [&](int m, double nn) {
+    const double mi = minv[m], r = nn / sqrt(mi), zv = z[m], gv = g[m];
+    kk += (mi * r) * r;
+    p.zm[m] = zv, p.zq[m] = zv, p.zc[m] = zv;
+    p.gm[m] = gv, p.gq[m] = gv, p.gc[m] = gv;
+    p.rm[m] = r, p.rq[m] = r, p.rho[m] = r;
+  });
+  const double ksum = block_sum(kk, red);
   const int dir = nuts_direction(a.seed, chain, step, 0);
   if (threadIdx.x == 0) {
     const double lp = a.lp[c];
@@ -126,8 +112,8 @@ __global__ __launch_bounds__(HMC_NT) void nuts_begin_kernel(HmcRun a, NutsRun n,
   nuts_next_point(p, dir, ch->eps, minv, a.rh + c * M, a.zp + c * M, M);
 }
 
-__global__ __launch_bounds__(HMC_NT) void nuts_leaf_kernel(HmcRun a, NutsRun n, uint64_t step, int32_t* __restrict__ open) {
-  __shared__ double red[HMC_NT / 64];
+__global__ __launch_bounds__(SAMPLER_NT) void nuts_leaf_kernel(HmcRun a, NutsRun n, uint64_t step, int32_t* __restrict__ open) {
+  __shared__ double red[2 * SAMPLER_WAVES];
   const int64_t c = blockIdx.x;
   const int tid = threadIdx.x;
   const int32_t M = a.M;
@@ -137,7 +123,6 @@ __global__ __launch_bounds__(HMC_NT) void nuts_leaf_kernel(HmcRun a, NutsRun n, 
   const NutsPtrs p = nuts_ptrs(n, c, M);
   const double *minv = a.minv + c * M, *gp = a.gp + c * M;
   double *zp = a.zp + c * M, *rh = a.rh + c * M;
-  const int nblk = (M + 1) >> 1;
   const double eps = a.chain[c].eps;
   // the tree's scalars, in every thread's registers through the launch
   const double h0 = tr->h0;
@@ -154,19 +139,15 @@ __global__ __launch_bounds__(HMC_NT) void nuts_leaf_kernel(HmcRun a, NutsRun n, 
   const bool log_it = n.leaf_out && nlog < n.leaf_cap;
   double* lg = log_it ? n.leaf_out + (3 * (int64_t)M + 1) * (nlog + n.leaf_cap * c) : nullptr;
   double kk = 0.0;
-  for (int j = tid; j < nblk; j += HMC_NT)
-    for (int q = 0; q < 2; ++q) {
-      const int m = 2 * j + q;
-      if (m < M) {
-        const double zv = zp[m], gv = gp[m];
-        const double r1 = rh[m] + (0.5 * ve) * gv;
-        kk += (minv[m] * r1) * r1;
-        ez[m] = zv, er[m] = r1, eg[m] = gv;
-        top[m] = r1, top[M + m] = r1, top[2 * M + m] = zv, top[3 * M + m] = gv;
-        if (log_it) lg[m] = zv, lg[M + m] = r1, lg[2 * M + 1 + m] = gv;
-      }
-    }
-  const double k1 = 0.5 * hmc_block_sum(kk, red);
+  for_owned(M, [&](int m) {
+    const double zv = zp[m], gv = gp[m];
+    const double r1 = rh[m] + (0.5 * ve) * gv;
+    kk += (minv[m] * r1) * r1;
+    ez[m] = zv, er[m] = r1, eg[m] = gv;
+    top[m] = r1, top[M + m] = r1, top[2 * M + m] = zv, top[3 * M + m] = gv;
+    if (log_it) lg[m] = zv, lg[M + m] = r1, lg[2 * M + 1 + m] = gv;
+  });
+  const double k1 = 0.5 * block_sum(kk, red);
   if (log_it && tid == 0) lg[2 * M] = lp1;
   double h1 = lp1 - k1;
   if (!isfinite(h1)) h1 = -INFINITY;
@@ -193,26 +174,22 @@ __global__ __launch_bounds__(HMC_NT) void nuts_leaf_kernel(HmcRun a, NutsRun n, 
       const double lw = nuts_logaddexp(a_logw, t_logw);
       const Philox4 x = philox_draw(a.seed, chain, step, NUTS_P_MERGE, (uint32_t)(16 * nleaf + level));
       const bool pick = log(u53(x.v[1], x.v[0])) < t_logw - lw;
-      double dm = 0.0, dq = 0.0;
-      for (int j = tid; j < nblk; j += HMC_NT)
-        for (int q = 0; q < 2; ++q) {
-          const int m = 2 * j + q;
-          if (m < M) {
-            const double rho = sa[M + m] + sb[M + m];
-            sa[M + m] = rho;
-            if (pick) sa[2 * M + m] = sb[2 * M + m], sa[3 * M + m] = sb[3 * M + m];
-            const double rs = sa[m], re = er[m], mi = minv[m];
-            dm += rho * (mi * (dir > 0 ? rs : re));
-            dq += rho * (mi * (dir > 0 ? re : rs));
-          }
-        }
-      const double sm = hmc_block_sum(dm, red), sq = hmc_block_sum(dq, red);
+      double d[2] = {0.0, 0.0};   // rho . (Minv r-), rho . (Minv r+)
+      for_owned(M, [&](int m) {
+        const double rho = sa[M + m] + sb[M + m];
+        sa[M + m] = rho;
+        if (pick) sa[2 * M + m] = sb[2 * M + m], sa[3 * M + m] = sb[3 * M + m];
+        const double rs = sa[m], re = er[m], mi = minv[m];
+        d[0] += rho * (mi * (dir > 0 ? rs : re));
+        d[1] += rho * (mi * (dir > 0 ? re : rs));
+      });
+      block_sum(d, red);
       if (!pick) t_lp = a_lp, t_sel = a_sel;
       t_logw = lw;
       t_alpha = a_alpha + t_alpha;
       t_n = a_n + t_n;
       --sp;
-      if (sm <= 0.0 || sq <= 0.0) {
+      if (d[0] <= 0.0 || d[1] <= 0.0) {
         stop = true;
         break;
       }
@@ -233,23 +210,19 @@ __global__ __launch_bounds__(HMC_NT) void nuts_leaf_kernel(HmcRun a, NutsRun n, 
     n_alpha += t_n;
     const Philox4 x = philox_draw(a.seed, chain, step, NUTS_P_DOUBLING, (uint32_t)depth);
     const bool pick = log(u53(x.v[3], x.v[2])) < t_logw - logw;
-    double dm = 0.0, dq = 0.0;
-    for (int j = tid; j < nblk; j += HMC_NT)
-      for (int q = 0; q < 2; ++q) {
-        const int m = 2 * j + q;
-        if (m < M) {
-          if (pick) p.zc[m] = sub[2 * M + m], p.gc[m] = sub[3 * M + m];
-          const double rho = p.rho[m] + sub[M + m], mi = minv[m];
-          p.rho[m] = rho;
-          dm += rho * (mi * p.rm[m]);
-          dq += rho * (mi * p.rq[m]);
-        }
-      }
-    const double sm = hmc_block_sum(dm, red), sq = hmc_block_sum(dq, red);
+    double d[2] = {0.0, 0.0};   // rho . (Minv r-), rho . (Minv r+) of the whole tree
+    for_owned(M, [&](int m) {
+      if (pick) p.zc[m] = sub[2 * M + m], p.gc[m] = sub[3 * M + m];
+      const double rho = p.rho[m] + sub[M + m], mi = minv[m];
+      p.rho[m] = rho;
+      d[0] += rho * (mi * p.rm[m]);
+      d[1] += rho * (mi * p.rq[m]);
+    });
+    block_sum(d, red);
     if (pick) lpc = t_lp, selc = t_sel;
     logw = nuts_logaddexp(logw, t_logw);
     ++depth;
-    if (sm <= 0.0 || sq <= 0.0 || depth >= n.max_depth) {
+    if (d[0] <= 0.0 || d[1] <= 0.0 || depth >= n.max_depth) {
       still = 0;
     } else {
       dir = nuts_direction(a.seed, chain, step, depth);
@@ -272,7 +245,7 @@ __global__ __launch_bounds__(HMC_NT) void nuts_leaf_kernel(HmcRun a, NutsRun n, 
   }
 }
 
-__global__ __launch_bounds__(HMC_NT) void nuts_end_kernel(HmcRun a, NutsRun n, uint64_t step, int adapting, int in_window,
+__global__ __launch_bounds__(SAMPLER_NT) void nuts_end_kernel(HmcRun a, NutsRun n, uint64_t step, int adapting, int in_window,
                                                           int window_close, int last_adapt) {
   __shared__ double wn_s;
   const int64_t c = blockIdx.x;
@@ -281,8 +254,6 @@ __global__ __launch_bounds__(HMC_NT) void nuts_end_kernel(HmcRun a, NutsRun n, u
   HmcChain* ch = a.chain + c;
   const NutsChain* tr = n.tree + c;
   const NutsPtrs p = nuts_ptrs(n, c, M);
-  double *z = a.z + c * M, *g = a.g + c * M, *minv = a.minv + c * M, *wmean = a.wmean + c * M, *wm2 = a.wm2 + c * M;
-  const int nblk = (M + 1) >> 1;
   const int64_t col = (int64_t)step + (a.itr + 1) * c;
   if (tid == 0) {
     const double eps = ch->eps;
@@ -301,34 +272,20 @@ __global__ __launch_bounds__(HMC_NT) void nuts_end_kernel(HmcRun a, NutsRun n, u
     wn_s = (double)wn;
   }
   __syncthreads();
-  const double wn = wn_s;   // the window's count INCLUDING this step
-  const int64_t obase = (int64_t)M * col;
-  for (int j = tid; j < nblk; j += HMC_NT)
-    for (int k = 0; k < 2; ++k) {
-      const int m = 2 * j + k;
-      if (m < M) {
-        const double zv = p.zc[m], gv = p.gc[m], mi = minv[m];
-        z[m] = zv;
-        g[m] = gv;
-        a.Z_out[obase + m] = zv;
-        if (a.G_out) a.G_out[obase + m] = gv;
-        if (a.Minv_out) a.Minv_out[obase + m] = mi;
-        if (adapting && in_window) hmc_adapt_component(m, zv, wn, window_close, minv, wmean, wm2);
-      }
-    }
+  keep_and_record(a, c, col, p.zc, p.gc, adapting && in_window, wn_s /* the window's count INCLUDING this step */, window_close);
 }
 
 void launch_nuts_begin(hipStream_t st, const HmcRun& a, const NutsRun& n, int32_t C, uint64_t step, bool first) {
-  hipLaunchKernelGGL(nuts_begin_kernel, dim3((unsigned)C), dim3(HMC_NT), 0, st, a, n, step, first ? 1 : 0);
+  hipLaunchKernelGGL(nuts_begin_kernel, dim3((unsigned)C), dim3(SAMPLER_NT), 0, st, a, n, step, first ? 1 : 0);
 }
 
 void launch_nuts_leaf(hipStream_t st, const HmcRun& a, const NutsRun& n, int32_t C, uint64_t step, int32_t* open) {
-  hipLaunchKernelGGL(nuts_leaf_kernel, dim3((unsigned)C), dim3(HMC_NT), 0, st, a, n, step, open);
+  hipLaunchKernelGGL(nuts_leaf_kernel, dim3((unsigned)C), dim3(SAMPLER_NT), 0, st, a, n, step, open);
 }
 
 void launch_nuts_end(hipStream_t st, const HmcRun& a, const NutsRun& n, int32_t C, uint64_t step, bool adapting, bool in_window,
                      bool window_close, bool last_adapt) {
-  hipLaunchKernelGGL(nuts_end_kernel, dim3((unsigned)C), dim3(HMC_NT), 0, st, a, n, step, adapting ? 1 : 0, in_window ? 1 : 0,
+  hipLaunchKernelGGL(nuts_end_kernel, dim3((unsigned)C), dim3(SAMPLER_NT), 0, st, a, n, step, adapting ? 1 : 0, in_window ? 1 : 0,
                      window_close ? 1 : 0, last_adapt ? 1 : 0);
 }
 

@@ -244,6 +244,22 @@ struct NutsChain {
                                      // direction; leaves of the doubling; stack entries; leaves; the candidate's leaf; still building
 };
 
+// What every sampler over stacked points keeps per chain (si_sample_mala, si_sample_hmc, si_sample_nuts): the state, the proposal or
+// pending point, and the value and gradient at both.  Nothing in it outlives a call: the first kernels of every call write all of it.
+struct ChainState {
+  int cap = 0;                    // chains it holds (grown on demand: reserve_chain_state, capi_common.h)
+  DevBuf<double> z, g, zp, gp;    // M x C each
+  DevBuf<double> lp, lpp;         // C each
+};
+
+// What a call of a gradient-driven entry point took, for its si_*_kernel_info: the stacked evaluator's route and passes; the rounds
+// of the step-size search (HMC, NUTS); the rounds and leaves of all transitions (NUTS).  All zero before a first call and after a
+// refused one.
+struct CallInfo {
+  int32_t fused = 0, passes = 0, search_rounds = 0;
+  int64_t rounds = 0, leaves = 0;
+};
+
 // ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops
 struct InferState {
   bool i_ready = false;
@@ -313,24 +329,21 @@ struct InferState {
   int vg_cap = 0;
   DevBuf<double> d_vg_z, d_vg_w, d_vg_part, d_vg_ssepart, d_vg_gw, d_vg_lp, d_vg_gz;
   int last_grad_fused = 0;          // si_grad_kernel_info
-  // si_sample_mala (capi_mala.hip, kernels_mala.hip): the chains' state, the proposals with their values and gradients, and the
-  // device-side gradient samples; its own buffers, so that the per-point gradient path may use d_zprop between the two kernels
+  // si_sample_mala / si_sample_hmc / si_sample_nuts: the chains' state with the proposals' (pending points') values and gradients
+  // (ChainState: one for the three, every call rewrites all of it); its own buffers, so that the per-point gradient path may use
+  // d_zprop between two kernels.  On top of it MALA has the accept counts and the device-side gradient samples
+  ChainState chain_state;
   int mala_cap = 0;
-  DevBuf<double> d_mala_z, d_mala_g, d_mala_zp, d_mala_gp;   // M x C each
-  DevBuf<double> d_mala_lp, d_mala_lpp;                      // C each
   DevBuf<int64_t> d_mala_nacc;                               // C
   DevBuf<double> d_outG;                                     // M x itr x C, kept between calls like d_outZ
-  int last_mala_fused = 0, last_mala_passes = 0;             // si_mala_kernel_info
-  // si_sample_hmc (capi_hmc.hip, kernels_hmc.hip): the chains' state as MALA's, the half-kicked momentum of the proposal, the metric
+  CallInfo info_mala, info_hmc, info_nuts, info_advi;        // si_*_kernel_info: what the last call of each took
+  // si_sample_hmc (capi_hmc.hip, kernels_hmc.hip), on top of the chain state: the half-kicked momentum of the proposal, the metric
   // with its Welford window, the per-chain scalars (HmcChain) and the device-side alpha / eps / Minv samples
   int hmc_cap = 0;
-  DevBuf<double> d_hmc_z, d_hmc_g, d_hmc_zp, d_hmc_gp, d_hmc_rh;   // M x C each
-  DevBuf<double> d_hmc_minv, d_hmc_wmean, d_hmc_wm2;               // M x C each
-  DevBuf<double> d_hmc_lp, d_hmc_lpp;                              // C each
+  DevBuf<double> d_hmc_rh, d_hmc_minv, d_hmc_wmean, d_hmc_wm2;     // M x C each
   DevBuf<HmcChain> d_hmc_chain;                                    // C
-  DevBuf<int32_t> d_hmc_open;                                      // 1: chains whose step-size search is not finished
+  DevBuf<int32_t> d_hmc_open;                                      // 1: chains still searching / building (synced_round)
   DevBuf<double> d_outalpha, d_outeps, d_outMinv;                  // (itr+1) x C twice, M x (itr+1) x C; kept between calls like d_outZ
-  int last_hmc_fused = 0, last_hmc_passes = 0, last_hmc_rounds = 0;   // si_hmc_kernel_info
   // si_sample_nuts (capi_nuts.hip, kernels_nuts.hip), on top of si_sample_hmc's state: both ends of the tree (z, r, g), the sum of its
   // momenta, the candidate (z, g), the stack of sub-tree summaries (4 M doubles per entry, NUTS_MAX_DEPTH entries per chain), the
   // per-chain scalars, the device-side depth / leaf count / selected leaf samples and, when asked for, the leaf log
@@ -340,8 +353,6 @@ struct InferState {
   DevBuf<NutsChain> d_nuts_tree;                                   // C
   DevBuf<int32_t> d_outdepth, d_outnleaf, d_outsel;                // (itr+1) x C each, kept between calls like d_outZ
   DevBuf<double> d_outleaf;                                        // (3M+1) x leaf_cap x C, only when asked for
-  int last_nuts_fused = 0, last_nuts_passes = 0, last_nuts_search = 0;   // si_nuts_kernel_info
-  int64_t last_nuts_rounds = 0, last_nuts_leaves = 0;
   // si_fit_advi (capi_advi.hip, kernels_advi.hip): the state theta = [mu; omega] of R runs, the optimiser's ring of squared
   // gradients, the step's draws eta with the points made from them, the points' values and gradients, and the device-side traces
   // (grown on demand and kept between calls; every call ends synchronised, so none is in use when it is replaced)
@@ -350,7 +361,6 @@ struct InferState {
   DevBuf<double> d_advi_eta, d_advi_z, d_advi_g;             // M x S x R each
   DevBuf<double> d_advi_lp;                                  // S x R
   DevBuf<double> d_advi_trace, d_advi_pts;                   // 2M x (T+1) x R, M x S x T x R: only when asked for, kept between calls
-  int last_advi_fused = 0, last_advi_passes = 0;             // si_advi_kernel_info
 };
 
 struct Ctx : CtxCore, ConstructState, InferState {};
@@ -763,24 +773,31 @@ void launch_chain_vgrad_reduce(hipStream_t st, const double* part, int G, int64_
                                double c0, double sigma2, double* gw, double* lp_out, double* gz_out, int npoints);
 int dense_fused_slot_feats(int32_t out);   // features per head slot of the fused fp64 layer (kernels_gemm.hip: BM / WM)
 // K6
-// kernels_mala.hip: zprop = z + (sigma_z^2 / 2) g + sigma_z n_step for C chains (first: sigma_z n_0); transition `step` of C chains
-// given the proposals' lpp / gp, sample `step` written to Z_out / lp_out / G_out (G_out may be NULL), the next proposal formed
-void launch_mala_propose(hipStream_t st, const double* z, const double* g, double* zprop, int32_t M, int32_t C, double sigma_z,
-                         uint64_t seed, int32_t chain_id0, uint64_t step, bool first);
-void launch_mala_accept(hipStream_t st, double* z, double* lp, double* g, double* zprop, const double* lpp, const double* gp,
-                        int64_t* nacc, int32_t M, int32_t C, double sigma_z, uint64_t seed, int32_t chain_id0, uint64_t step,
-                        double* Z_out, double* lp_out, double* G_out, int64_t itr, bool propose_next);
-// kernels_hmc.hip (the transition, the adaptor update and the step-size search are defined in its header comment): C chains, one
-// workgroup each.  HmcRun: what the three kernels share.
-struct HmcRun {
-  double *z, *lp, *g, *zp, *rh, *minv, *wmean, *wm2;   // state: M x C (lp: C)
+// What the kernels of every sampler over stacked points share: C chains, one workgroup each.
+struct ChainRun {
+  double *z, *lp, *g, *zp;                             // state and proposal / pending point: M x C (lp: C)
   const double *lpp, *gp;                              // value and gradient at zp
-  HmcChain* chain;                                     // C
-  double *Z_out, *lp_out, *alpha_out, *eps_out, *G_out, *Minv_out;   // M x (itr+1) x C / (itr+1) x C; G_out, Minv_out may be NULL
+  double *Z_out, *lp_out, *G_out;                      // the samples, `itr` (MALA) or itr + 1 (HMC, NUTS) columns per chain; G_out may be NULL
   int32_t M, chain_id0;
   int64_t itr;
   uint64_t seed;
-  double sigma_z, delta;
+  double sigma_z;
+};
+// kernels_mala.hip: zp = z + h g + sigma_z n_step for C chains (first: sigma_z n_0); transition `step` of C chains given the
+// proposals' lpp / gp, sample `step` written to Z_out / lp_out / G_out, the next proposal formed
+struct MalaRun : ChainRun {
+  int64_t* nacc;                                       // C
+  double h;                                            // sigma_z^2 / 2, formed on the host, once
+};
+void launch_mala_propose(hipStream_t st, const MalaRun& a, int32_t C, uint64_t step, bool first);
+void launch_mala_accept(hipStream_t st, const MalaRun& a, int32_t C, uint64_t step, bool propose_next);
+// kernels_hmc.hip (the transition, the adaptor update and the step-size search are defined in its header comment).  HmcRun: what
+// its kernels and kernels_nuts.hip's share.
+struct HmcRun : ChainRun {
+  double *rh, *minv, *wmean, *wm2;                     // M x C
+  HmcChain* chain;                                     // C
+  double *alpha_out, *eps_out, *Minv_out;              // (itr+1) x C twice, M x (itr+1) x C or NULL
+  double delta;
 };
 void launch_hmc_init(hipStream_t st, const HmcRun& a, int32_t C);   // zp = sigma_z n_0, the search's state machine at its start
 // one round of the step-size search given (lpp, gp) at the last trial point; open: the chains still searching are counted into it

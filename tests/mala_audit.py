@@ -304,6 +304,9 @@ CASES = [
     Case("A-M2-itr1", MODEL_A, 2, 0.2, True, itr=1),
     # 64 chains of 7 transitions: both branches in the case as a whole, not in every chain
     Case("A-M33x64", MODEL_A, 33, 0.2, True, nchains=64, itr=8, seed=12, per_chain=False),
+    # 257 Philox blocks: the 256-thread sweep runs twice.  (sigma_z: 20 weights leave most of the 513 directions flat, so every chain
+    #  accepts all 7 steps up to 0.8 and chain 0 up to 1.3; from 1.4 to 3.0 every chain does both, and 2.0 lies in the middle)
+    Case("small-M513", SMALL, 513, 2.0, True, itr=8),
     # (14 observations pin the posterior loosely and large steps are accepted.  sigma_z = 1.0 is the largest of 0.5 / 0.8 / 1.0 / 1.2
     #  whose chains stay where the tanh units ahead of the MaxPool are not saturated: at 1.2 a chain reaches |z| = 15, pooling windows
     #  hold several values within sqrt(eps) of each other, the reference's `y ≈ x` rule no longer singles out the maximum and the

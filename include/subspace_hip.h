@@ -192,6 +192,37 @@ int32_t si_construct_get_result(si_ctx* ctx, double* W_swa_out /* N */, double* 
 /* read back deviation columns [k0, k0+nk) (N x nk col-major) -- parity tests of :51-52 */
 int32_t si_construct_get_A(si_ctx* ctx, int64_t k0, int64_t nk, double* A_out);
 
+/* ---- method = :diffusion: replaces src/subspace_construction.jl:202-206 (diffusion_subspace) ------------------------
+ * diff_M = fit(DiffMap, A', maxoutdim = M); P = transform(diff_M); return W_swa, P'   (ManifoldLearning 0.6.2).
+ * The definition below is  [upstream, from memory, unverifiable offline]  (diffmap.py restates it in NumPy); every point where
+ * memory may be wrong is an argument.  With X = A' (K x N):
+ *   rescale != 0: per snapshot k, Xr[k, i] = (X[k, i] - min_k) * (1 / (max_k - min_k)), NaN -> 0 (StatsBase UnitRangeTransform)
+ *   Kmat_ij = exp(kernel_sign * ||Xr_i - Xr_j||^2 / eps)   kernel_sign -1: upstream's docstring; +1: what 0.6.2's source is
+ *                                                          remembered to compute.  eps = 1 is upstream's default
+ *   p = rowsums(Kmat); Kmat_ij /= (p_i p_j)^alpha (alpha = 1: upstream's t = 1); q = sqrt(rowsums); Kn_ij = Kmat_ij / (q_i q_j)
+ *   U = eigenvectors of Kn by |lambda| descending (lambda_1 = 1, u_1 = q / ||q||);  P = U[:, 2:M+1] ./ U[:, 1]
+ * Column signs of P: the entry of largest magnitude of each column is positive (lowest index on a tie).
+ * Only the M + 1 leading vectors are computed: u_1 analytically, the rest by block subspace iteration on the device-resident
+ * N x N matrix (block min(N - 1, 2M + 16)), stopped when every leading residual ||Kn u - theta u|| <= tol (tol <= 0: 1e-12) or
+ * after max_iters (<= 0: 500) iterations.  Not converged is SI_ERR_INVALID with the residual and the count in the message: the
+ * spectrum is not separated well enough -- a stated limitation against the reference's full SVD.
+ * State rules: si_construct_finish's (pushes must have happened; outputs may be NULL).  Afterwards the ctx holds a finished
+ * construction: si_infer_setup(NULL, NULL), si_construct_result_ptr, si_construct_get_result (s = |lambda_2 .. lambda_{M+1}|)
+ * and si_bcast_subspace behave as after a PCA finish.  The deviation matrix and the PCA route's state are untouched: a
+ * si_construct_finish before and after gives the same bits.
+ * lambda_out: the M + 1 eigenvalues, |.| descending, lambda_out[0] = 1.
+ * SI_ERR_INVALID: M < 1; eps or alpha not finite; eps <= 0; kernel_sign not +1 / -1; N > 65536 (the N x N fp64 matrix is 34 GB
+ * there); a non-finite kernel entry (overflow with kernel_sign = +1).  SI_ERR_BOUNDS: M + 1 > N - 1.  SI_ERR_NOMEM as elsewhere.
+ * A ROW-SHARDED construction is not supported: the kernel matrix couples every pair of weights.                       */
+int32_t si_construct_finish_diffmap(si_ctx* ctx, int32_t M, double eps, double alpha, int32_t kernel_sign, int32_t rescale,
+                                    double tol, int32_t max_iters, double* W_swa_out /* N */, double* P_out /* N x M */,
+                                    double* lambda_out /* M + 1 */, int64_t* K_out);
+/* iterations and largest leading residual of the last si_construct_finish_diffmap (a refused call: zeros) */
+int32_t si_diffmap_info(si_ctx* ctx, int32_t* iters_out, double* residual_out);
+/* audit read-back of the last call that got as far as the iteration (converged or not): Kn (N x N col-major) and u_1 (N);
+ * either may be NULL */
+int32_t si_diffmap_get_kernel(si_ctx* ctx, double* Kn_out, double* u1_out);
+
 /* ---- density + sampling: replaces src/space_inference.jl:88-95,111-116,125 ------------------- */
 /* :88 split_data (full X, Y), :90-95 density closure.  W_swa / P may both be NULL: the result of the
  * ctx's finished construction is used in place (no host round trip).  X is in_dim x B, Y is out_dim x B,

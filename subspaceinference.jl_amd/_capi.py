@@ -79,6 +79,10 @@ SIGNATURES = {
     "si_construct_refine": (c_int32, [c_void_p]),
     "si_construct_finish": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
     "si_construct_get_A": (c_int32, [c_void_p, c_int64, c_int64, c_void_p]),
+    "si_construct_finish_diffmap": (c_int32, [c_void_p, c_int32, c_double, c_double, c_int32, c_int32, c_double, c_int32, c_void_p,
+                                              c_void_p, c_void_p, POINTER(c_int64)]),
+    "si_diffmap_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_double)]),
+    "si_diffmap_get_kernel": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "si_construct_get_result": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int32)]),
     "si_infer_setup": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_int32, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_int32, c_int32, c_int64, c_double, c_int32]),
@@ -467,6 +471,31 @@ class Context:
         s = np.empty(int(m), dtype=np.float64)
         self._check(self.lib.si_construct_finish(self.h, int(m), _ptr(w_swa), _ptr(p), _ptr(s), byref(k)))
         return w_swa, p, s, k.value
+
+    def construct_finish_diffmap(self, m, eps=1.0, alpha=1.0, kernel_sign=-1, rescale=True, tol=0.0, max_iters=0, want_swa=True,
+                                 want_p=True):
+        """method = :diffusion (reference src/subspace_construction.jl:202-206; the definition is diffmap.py's): (W_swa, P, lam, K)
+        with lam the M + 1 leading eigenvalues by |.| descending, lam[0] = 1.  tol <= 0: 1e-12; max_iters <= 0: 500."""
+        k = c_int64()
+        w_swa = np.empty(self._n, dtype=np.float64) if want_swa else None
+        p = np.empty((self._n, max(int(m), 0)), dtype=np.float64, order="F") if want_p else None
+        lam = np.empty(max(int(m), 0) + 1, dtype=np.float64)
+        self._check(self.lib.si_construct_finish_diffmap(self.h, int(m), float(eps), float(alpha), int(kernel_sign), 1 if rescale else 0,
+                                                         float(tol), int(max_iters), _ptr(w_swa), _ptr(p), _ptr(lam), byref(k)))
+        return w_swa, p, lam, k.value
+
+    def diffmap_info(self):
+        """(iterations, largest leading residual) of the last construct_finish_diffmap"""
+        it, res = c_int32(), c_double()
+        self._check(self.lib.si_diffmap_info(self.h, byref(it), byref(res)))
+        return it.value, res.value
+
+    def diffmap_get_kernel(self, want_kn=True):
+        """audit read-back of the last construct_finish_diffmap: (Kn (N x N) or None, u_1)"""
+        kn = np.empty((self._n, self._n), dtype=np.float64, order="F") if want_kn else None
+        u1 = np.empty(self._n, dtype=np.float64)
+        self._check(self.lib.si_diffmap_get_kernel(self.h, _ptr(kn), _ptr(u1)))
+        return kn, u1
 
     def construct_get_A(self, k0, nk):
         a = np.empty((self._n, int(nk)), dtype=np.float64, order="F")

@@ -1,6 +1,7 @@
 """Host-side mirror of the reference's exported API for the hot path (src/SubspaceInference.jl:27-34):
 
     subspace_construction(model, cost, data, opt; T=10, c=1, M=3, print_freq=1)        -> (W_swa, P)
+    diffusion_subspace(model, cost, data, opt; T=10, c=1, M=3, print_freq=1)           -> (W_swa, P)
     subspace_inference(model, cost, data, opt; σ_z, σ_m, σ_p, itr, T, c, M, ...)        -> (chn, lp, W_swa)
     sub_inference(in_model, data, W_swa, P; σ_z, σ_m, σ_p, itr, M, alg, backend)        -> (chn, lp)
     inference(...)  README-only alias of sub_inference (README.md:153-154); alg=:mh == :rwmh
@@ -61,6 +62,38 @@ def subspace_construction(model, cost, data, opt, T=10, c=1, M=3, print_freq=1, 
     ctx carries: the documented cfg3 flow (construct on rank 0, then si_bcast_subspace) must not find rank 0 alone inside a
     gradient all-reduce.
     """
+    return _swa_construction(model, cost, data, opt, T, c, print_freq,
+                             lambda cx: cx.construct_finish(M, want_swa=True, want_p=not keep_on_device)[:2],
+                             device=device, ctx=ctx, max_cols=max_cols, verbose=verbose, keep_on_device=keep_on_device,
+                             device_training=device_training, init=init, data_parallel=data_parallel, a_storage=a_storage,
+                             compute_dtype=compute_dtype)
+
+
+def diffusion_subspace(model, cost, data, opt, T=10, c=1, M=3, print_freq=1, *, eps=1.0, alpha=1.0, kernel_sign=-1, rescale=True,
+                       tol=0.0, max_iters=0, device=0, ctx=None, verbose=True, keep_on_device=False, device_training="auto",
+                       init="zeros", a_storage="f64", compute_dtype="auto"):
+    """src/subspace_construction.jl:167-207: the SWA loop of `subspace_construction` (:181-200, the same lines), then
+    `fit(DiffMap, A', maxoutdim = M); P = transform(diff_M)` (:202-206) instead of the SVD -> (W_swa, P), P being N x M.
+
+    The diffusion map runs on the device (si_construct_finish_diffmap).  Its definition is `diffmap.diffmap_dense`, a restatement of
+    ManifoldLearning 0.6.2  [upstream, from memory, unverifiable offline]: `eps` (kernel width, upstream's default 1), `alpha`
+    (upstream's t = 1), `kernel_sign` (-1: the Gaussian kernel of upstream's docstring; +1: what its source is remembered to
+    compute) and `rescale` (the per-snapshot unit-range transform) are the points a maintainer with Julia may have to change.
+    `tol` / `max_iters` steer the block subspace iteration (0: 1e-12 / 500); a spectrum it cannot separate raises.
+    The other keywords are `subspace_construction`'s (a ring of `max_cols` columns and a row-sharded / data-parallel
+    construction are not offered on this route)."""
+    return _swa_construction(model, cost, data, opt, T, c, print_freq,
+                             lambda cx: cx.construct_finish_diffmap(M, eps, alpha, kernel_sign, rescale, tol, max_iters, want_swa=True,
+                                                                    want_p=not keep_on_device)[:2],
+                             device=device, ctx=ctx, max_cols=0, verbose=verbose, keep_on_device=keep_on_device,
+                             device_training=device_training, init=init, data_parallel=False, a_storage=a_storage,
+                             compute_dtype=compute_dtype)
+
+
+def _swa_construction(model, cost, data, opt, T, c, print_freq, finish, *, device, ctx, max_cols, verbose, keep_on_device,
+                      device_training, init, data_parallel, a_storage, compute_dtype):
+    """What `subspace_construction` and `diffusion_subspace` share (reference :28-59 and :169-200, the same lines twice): training
+    with the SWA update and the deviation columns on the device; `finish(ctx)` -> (W_swa, P) is what differs."""
     ps = flux.params(model)
     n_par = int(sum(p.size for p in ps))
     nb = len(data)
@@ -129,8 +162,7 @@ def subspace_construction(model, cost, data, opt, T=10, c=1, M=3, print_freq=1, 
         if use_dev:
             flux.load_flat(model, ctx.train_get_weights())
             flux.store_device_state(opt, model, *ctx.train_get_opt_state())  # opt continues where the device left it
-        w_swa, p, _, _ = ctx.construct_finish(M, want_swa=True, want_p=not keep_on_device)
-        return w_swa, p
+        return finish(ctx)
     finally:
         if own and not keep_on_device:
             ctx.close()
@@ -277,17 +309,16 @@ def subspace_inference(model, cost, data, opt, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr
     """src/space_inference.jl:33-54: construction, then sampling; returns (chn, lp, W_swa).
     W_swa and P stay on the device between the two stages (no host round trip)."""
     m = _alg_name(method)
-    if m == "diffusion":
-        raise SubspaceError("method :diffusion is outside the accelerated path (SURVEY section 2)")
-    if m != "subspace":
+    if m not in ("subspace", "diffusion"):
         raise SubspaceError("Error: No method found")  # reference :42
+    construct = subspace_construction if m == "subspace" else diffusion_subspace  # reference :37-40
     a = _alg_name(alg)
     if a in ("turing_mh", "turing_nuts"):
         raise SubspaceError("Turing samplers are outside the accelerated path (SURVEY section 2)")
     ctx, own = _get_ctx(ctx, device)
     try:
-        w_swa, _ = subspace_construction(model, cost, data, opt, T=T, c=c, M=M, print_freq=print_freq, ctx=ctx,
-                                         verbose=verbose, keep_on_device=True)
+        w_swa, _ = construct(model, cost, data, opt, T=T, c=c, M=M, print_freq=print_freq, ctx=ctx, verbose=verbose,
+                             keep_on_device=True)
         chn, lp = sub_inference(model, data, None, None, σ_z=σ_z, σ_m=σ_m, σ_p=σ_p, itr=itr, M=M, alg=alg,
                                 backend=backend, sigma_z=sigma_z, sigma_m=sigma_m, ctx=ctx, seed=seed,
                                 return_z=return_z, compute_dtype=compute_dtype, device_loop=device_loop,

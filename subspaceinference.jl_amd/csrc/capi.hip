@@ -390,6 +390,7 @@ int32_t si_construct_begin(si_ctx* ctx, int64_t N, int64_t K_capacity, int32_t m
     ctx->c_finished = ctx->gram_valid = false;
     ctx->K = 0;
     ctx->npush = 0;
+    ctx->dm = DiffmapState();   // the diffusion route's buffers belong to one construction
   } else {
     free_construct(ctx);
     ctx->N = N;
@@ -743,7 +744,9 @@ int32_t si_construct_refine(si_ctx* ctx) {
   return SI_OK;
 }
 
-static int32_t alloc_P(si_ctx* ctx, int32_t M) {
+}   // extern "C"
+// (shared with si_construct_finish_diffmap, capi_diffmap.hip)
+int32_t si::construct_alloc_P(si::Ctx* ctx, int32_t M) {
   if (ctx->d_P != nullptr && ctx->M_built == M) return SI_OK;
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // P is re-allocated: an inference bound to the old P of this construction must not outlive it
@@ -755,6 +758,8 @@ static int32_t alloc_P(si_ctx* ctx, int32_t M) {
   SI_HIP(ctx, hipMemsetAsync(ctx->d_P, 0, (size_t)ctx->ldA * M * sizeof(double), ctx->stream));
   return SI_OK;
 }
+extern "C" {
+static int32_t alloc_P(si_ctx* ctx, int32_t M) { return construct_alloc_P(ctx, M); }
 
 // K > N: A' on the device (transpose), G = A A' with the Gram kernel, top-M eigenpairs of the N x N matrix on the host,
 // the right singular vectors A'U only to read the deterministic column signs from, P = U * Diagonal(s) uploaded.

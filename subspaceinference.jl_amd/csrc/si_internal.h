@@ -201,6 +201,21 @@ struct CtxCore {
   ~CtxCore() { delete train; }
 };
 
+// What si_construct_finish_diffmap keeps (capi_diffmap.hip, kernels_diffmap.hip): its own buffers, none shared with the PCA route.
+// Part of the construction state: dropped by free_construct and by every si_construct_begin.
+struct DiffmapState {
+  int64_t N = 0;               // rows of the last finished call (0: none; si_diffmap_get_kernel reads Kn and u_1 of it)
+  int32_t iters = 0;           // si_diffmap_info
+  double residual = 0.0;
+  DevBuf<double> Xr, s, mm;    // rescaled X (Kp x Npad), squared column norms (Npad), per-snapshot min / max (2 K)
+  DevBuf<double> Kn;           // ldn x N, padding rows zero: Kmat, normalised in place
+  DevBuf<double> part, p, q, u1;   // row-sum partials (blocks x ldn); p, q, u_1 (ldn each)
+  DevBuf<int> flag;            // a non-finite kernel entry was seen
+  DevBuf<double> Z[2];         // the stacked block [V W] (ldn x 2b) and where the next block / the Ritz vectors go
+  DevBuf<double> R, Vt, coef;  // residual vectors (ldn x M), V' for the product (pad_ld(b) x N), coefficient uploads
+  DevBuf<double> G, Gpart, res;   // the stacked Gram matrix (2b x 2b), K2's partial slabs, residual norms (M)
+};
+
 // ---- construction state (reference src/subspace_construction.jl:31-33,45-52,61-65): what free_construct drops
 struct ConstructState {
   bool c_active = false, c_finished = false, gram_valid = false;
@@ -221,6 +236,7 @@ struct ConstructState {
   int refine_stage = 0;           // 0: d_G = A'A;  1: d_B valid and d_G = B'B (possibly all-reduced by the caller)
   DevBuf<double> d_At;            // K > N route: A' (pad_ld(K) x N), kept between finishes of one shape
   DevBuf<double> d_B;             // ldA x K
+  DiffmapState dm;                // method = :diffusion
 };
 
 // per-chain scalars of si_sample_hmc (kernels_hmc.hip): the adaptor's dual averaging and Welford count, the kinetic energy of the
@@ -858,6 +874,23 @@ void launch_weights_select(hipStream_t st, const int32_t* flag, const double* wp
 void launch_prior_grad(hipStream_t st, double* g, const double* w, int64_t n, double inv_s2, int num_cu);
 void launch_widen_f32(hipStream_t st, const float* src, double* dst, int64_t n, int num_cu);
 void launch_transpose(hipStream_t st, const void* A, int32_t a_dtype, int64_t lda, int64_t N, int64_t K, double* At, int64_t ldt);
+// kernels_diffmap.hip (the diffusion map of si_construct_finish_diffmap; the steps are defined in its header comment)
+int dm_blocks(int64_t N);   // 64-row blocks of the pairwise matrix = rows of the row-sum partials
+// mm (2 K, only with rescale), Xr (Kp x dm_blocks(N) * 64, zeroed by the caller) and s from the deviation matrix A
+void launch_dm_rescale(hipStream_t st, const void* A, int32_t a_dtype, int64_t ldA, int64_t N, int K, int Kp, int rescale, double* mm,
+                       double* Xr, double* s);
+// Kmat (ldn x N, exactly symmetric) with part[b][i] = its row sums over column block b; *flag raised on a non-finite entry
+void launch_dm_pairwise(hipStream_t st, const double* Xr, int Kp, const double* s, int64_t N, int kernel_sign, double eps, double* Kmat,
+                        int64_t ldn, double* part, int* flag);
+void launch_dm_sum_parts(hipStream_t st, const double* part, int64_t ldn, int64_t N, bool root, double* out);
+// Kmat_ij /= (v_i v_j)^alpha with the new row-sum partials (with_sums), or Kmat_ij /= v_i v_j
+void launch_dm_scale_rows(hipStream_t st, double* Kmat, int64_t ldn, int64_t N, const double* v, double alpha, bool with_sums, double* part);
+void launch_dm_unit(hipStream_t st, const double* q, int64_t N, double* u1);
+void launch_dm_deflate(hipStream_t st, double* V, int64_t ldv, int64_t N, int ncol, const double* u1);
+void launch_dm_colnorm(hipStream_t st, const double* R, int64_t ldr, int64_t N, int ncol, double* out);
+void launch_dm_finish(hipStream_t st, const double* U, int64_t ldu, int64_t N, int M, const double* u1, double* P, int64_t ldp);
+// capi.hip: d_P for M columns (an inference bound to a P that is replaced is dropped)
+int32_t construct_alloc_P(Ctx* c, int32_t M);
 
 // host copy pool (host_copy.cpp): parallel memcpy between pageable caller arrays and pinned staging
 void host_copy(void* dst, const void* src, size_t bytes);

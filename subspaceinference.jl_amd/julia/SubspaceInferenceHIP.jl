@@ -38,6 +38,7 @@ using Flux, Zygote, Random, Distributed
 using Distributions: MvNormal
 using AdvancedMH, AdvancedHMC
 export subspace_construction, subspace_inference, sub_inference, inference, predict
+export diffusion_subspace
 export init_gpus, sub_inference_chains, sharded_construct_finish!, sample_data_sharded, bcast_subspace!
 
 const LIB = get(ENV, "SUBSPACE_HIP_LIB", joinpath(@__DIR__, "..", "libsubspace_hip.so"))
@@ -243,6 +244,58 @@ end
 function subspace_construction(model, cost, data, opt; T = 10, c = 1, M = 3, print_freq = 1, device = 0,
                                ctx = Ctx(device), max_cols = 0, keep_on_device = false, device_training = false,
                                init = :zeros, data_parallel = false, a_storage = :f64, compute_dtype = :auto)
+    N = swa_columns!(ctx, model, cost, data, opt; T = T, c = c, print_freq = print_freq, max_cols = max_cols,
+                     device_training = device_training, init = init, data_parallel = data_parallel, a_storage = a_storage,
+                     compute_dtype = compute_dtype)
+    W_swa = Vector{Float64}(undef, N)
+    P = keep_on_device ? nothing : Matrix{Float64}(undef, N, M)
+    s = Vector{Float64}(undef, M); K = Ref{Int64}(0)
+    GC.@preserve W_swa P s check(ctx, ccall((:si_construct_finish, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}),
+        ctx.h, M, W_swa, P === nothing ? C_NULL : pointer(P), s, K))
+    return W_swa, P
+end
+
+# src/subspace_construction.jl:167-207: the same SWA loop, then `fit(DiffMap, A', maxoutdim = M); P = transform(diff_M)` on the
+# device (si_construct_finish_diffmap) instead of ManifoldLearning on the host.  The definition is restated in diffmap.py
+# [upstream, from memory, unverifiable offline]; ϵ (kernel width), α (upstream's t), kernel_sign (-1: the Gaussian kernel of
+# upstream's docstring, +1: what its source is remembered to compute) and rescale are the points to change once it is compared
+# with the package itself (tests/golden/make_golden_diffmap.jl).  Returns (W_swa, P) with P of size N x M, as the reference's P'.
+function diffusion_subspace(model, cost, data, opt; T = 10, c = 1, M = 3, print_freq = 1, device = 0,
+                            ctx = Ctx(device), keep_on_device = false, device_training = false, init = :zeros,
+                            a_storage = :f64, compute_dtype = :auto, ϵ = 1.0, α = 1.0, kernel_sign = -1, rescale = true,
+                            tol = 0.0, max_iters = 0)
+    N = swa_columns!(ctx, model, cost, data, opt; T = T, c = c, print_freq = print_freq, max_cols = 0,
+                     device_training = device_training, init = init, data_parallel = false, a_storage = a_storage,
+                     compute_dtype = compute_dtype)
+    W_swa = Vector{Float64}(undef, N)
+    P = keep_on_device ? nothing : Matrix{Float64}(undef, N, M)
+    λ = Vector{Float64}(undef, M + 1); K = Ref{Int64}(0)
+    GC.@preserve W_swa P λ check(ctx, ccall((:si_construct_finish_diffmap, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Float64, Float64, Int32, Int32, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}),
+        ctx.h, M, ϵ, α, kernel_sign, rescale ? 1 : 0, tol, max_iters, W_swa, P === nothing ? C_NULL : pointer(P), λ, K))
+    return W_swa, P
+end
+
+# (iterations, largest leading residual) of the last diffusion_subspace on ctx
+function diffmap_info(ctx::Ctx)
+    it = Ref{Int32}(0); res = Ref{Float64}(0.0)
+    check(ctx, ccall((:si_diffmap_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Float64}), ctx.h, it, res))
+    return Int(it[]), res[]
+end
+
+# audit read-back of the last diffusion_subspace on ctx: the normalised kernel matrix Kn (N x N) and its Perron vector u_1
+function diffmap_kernel(ctx::Ctx, N)
+    Kn = Matrix{Float64}(undef, N, N); u1 = Vector{Float64}(undef, N)
+    GC.@preserve Kn u1 check(ctx, ccall((:si_diffmap_get_kernel, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
+                                        ctx.h, pointer(Kn), pointer(u1)))
+    return Kn, u1
+end
+
+# What subspace_construction and diffusion_subspace share (the reference has these lines twice, :28-59 and :169-200): training with
+# the SWA update and the deviation columns on the device.  Returns N.
+function swa_columns!(ctx::Ctx, model, cost, data, opt; T, c, print_freq, max_cols, device_training, init, data_parallel,
+                      a_storage, compute_dtype)
     training_loss = 0.0
     ps = Flux.params(model)
     N = sum(length, ps)
@@ -280,13 +333,7 @@ function subspace_construction(model, cost, data, opt; T = 10, c = 1, M = 3, pri
             end
         end
     end
-    W_swa = Vector{Float64}(undef, N)
-    P = keep_on_device ? nothing : Matrix{Float64}(undef, N, M)
-    s = Vector{Float64}(undef, M); K = Ref{Int64}(0)
-    GC.@preserve W_swa P s check(ctx, ccall((:si_construct_finish, LIB), Int32,
-        (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}),
-        ctx.h, M, W_swa, P === nothing ? C_NULL : pointer(P), s, K))
-    return W_swa, P
+    return N
 end
 
 # ---- the two device callbacks every sampler of sub_inference is driven by ------------------------------------------
@@ -729,13 +776,15 @@ end
 function subspace_inference(model, cost, data, opt; σ_z = 1.0, σ_m = 1.0, σ_p = 1.0, itr = 1000, T = 25, c = 1, M = 20,
                             print_freq = 1, alg = :rwmh, backend = :forwarddiff, method = :subspace, device = 0,
                             device_training = false, ngpu = 1, nchains = ngpu, device_loop = false)
-    method == :subspace || throw("Error: No method found")
+    (method == :subspace || method == :diffusion) || throw("Error: No method found")   # src/space_inference.jl:37-42
+    method == :diffusion && ngpu > 1 && throw("method = :diffusion runs on one GPU (the kernel matrix couples every pair of weights)")
+    construct = method == :subspace ? subspace_construction : diffusion_subspace
     ngpu > 1 && return subspace_inference_multi(model, cost, data, opt; ngpu = ngpu, nchains = nchains, σ_z = σ_z, σ_m = σ_m,
                                                 σ_p = σ_p, itr = itr, T = T, c = c, M = M, print_freq = print_freq, alg = alg,
                                                 backend = backend, device_training = device_training)
     ctx = Ctx(device)
-    W_swa, _ = subspace_construction(model, cost, data, opt; T = T, c = c, M = M, print_freq = print_freq, ctx = ctx,
-                                     keep_on_device = true, device_training = device_training)
+    W_swa, _ = construct(model, cost, data, opt; T = T, c = c, M = M, print_freq = print_freq, ctx = ctx,
+                         keep_on_device = true, device_training = device_training)
     chn, lp = sub_inference(model, data, nothing, nothing; σ_z = σ_z, σ_m = σ_m, σ_p = σ_p, itr = itr, M = M,
                             alg = alg, backend = backend, ctx = ctx, device_loop = device_loop)   # W_swa / P taken in place on the device
     return chn, lp, W_swa

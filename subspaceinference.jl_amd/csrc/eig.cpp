@@ -178,7 +178,9 @@ int ql_implicit(int n, double* a, double* d, double* e) {
   for (int l = 0; l < n; ++l) {
     tst1 = std::max(tst1, std::fabs(d[l]) + std::fabs(e[l]));
     int m = l;
-    while (m < n) {
+    // (m stops at n - 1 by its bound and not by the sentinel e[n - 1] = 0: a NaN met on the way turns the sentinel into NaN,
+    // and m = n had the sweep below read and write d[n], e[n] and column n of a.  Finite input: the same m as before.)
+    while (m < n - 1) {
       if (std::fabs(e[m]) <= eps * tst1) break;
       ++m;
     }
@@ -488,12 +490,15 @@ int sym_eig(int n, double* a, double* w) {
   if (n <= 0) return 0;
   std::vector<double> e(n);
   if (n == 1) {
+    if (!std::isfinite(a[0])) return 1;
     w[0] = a[0];
     a[0] = 1.0;
     return 0;
   }
   tridiagonalize(n, a, w, e.data());
   if (ql_implicit(n, a, w, e.data()) != 0) return 1;
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(w[i])) return 1;   // a non-finite matrix (or one that overflows on the way) has no eigenpairs to return
   // selection sort of eigenpairs, ascending
   for (int i = 0; i < n - 1; ++i) {
     int k = i;

@@ -35,8 +35,32 @@ static int check(int n, int m, int kind, unsigned seed) {
   return 0;
 }
 
+// A matrix with a non-finite entry (the diffusion finish hands over V'W of a kernel matrix that came out 0 / 0) must be
+// refused, inside the buffers: NaN off-diagonals defeat the sentinel e[n - 1] = 0 of the QL sweep.
+static int check_nonfinite(int n, int where, double v) {
+  std::vector<double> g((size_t)n * n, 0.0);
+  for (int i = 0; i < n; ++i) g[i + (size_t)n * i] = 1.0 + i;
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j)
+      if (where == 0 || (where == 1 && i == j) || (where == 2 && i + j == n - 1) || (where == 3 && i == n - 1 && j == n - 1))
+        g[i + (size_t)n * j] = v;
+  std::vector<double> full(g), w(n), wt(n), V((size_t)n * n);
+  if (sym_eig(n, full.data(), w.data()) == 0) return 3;
+  if (sym_eig_top(n, g.data(), std::max(n / 3, 1), wt.data(), V.data()) == 0) return 4;
+  return 0;
+}
+
 int main() {
   int bad = 0;
+  for (int n : {1, 2, 3, 4, 9, 36})
+    for (int where = 0; where < 4; ++where)
+      for (double v : {std::nan(""), HUGE_VAL, -HUGE_VAL}) {
+        const int rc = check_nonfinite(n, where, v);
+        if (rc != 0) {
+          std::printf("FAILED non-finite n=%d where=%d v=%g rc=%d\n", n, where, v, rc);
+          ++bad;
+        }
+      }
   const int ns[] = {1, 2, 3, 8, 9, 31, 64, 100};
   for (int n : ns)
     for (int kind = 0; kind < 4; ++kind)

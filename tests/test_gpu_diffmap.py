@@ -42,6 +42,17 @@ OPERATOR_CASES = [
     (333, 12, 1, 1.0, 1.0, True, True, False),            # fp32 storage of A
     (682, 30, 1, 10.0, 0.5, True, False, True),           # a constant snapshot: 0 * Inf -> 0
     (2051, 37, -1, 1.0, 1.0, True, False, False),         # 33 row blocks: 561 workgroups, 33 row-sum partials per row
+    # ---- the operator's edges on real-valued inputs: N at a 64-row tile edge (ldn == Npad == N, a full last tile) and one
+    # past it, one 16-row wave patch, the smallest N; K a multiple of 4 (Kp == K); K > N; alpha = 0 and 0.5 at a tile edge
+    (64, 4, -1, 1.0, 1.0, True, False, False),
+    (64, 8, -1, 1.0, 1.0, True, True, False),             # fp32 storage at a tile edge
+    (65, 8, 1, 0.5, 1.0, False, False, False),
+    (128, 8, -1, 1.0, 0.0, True, False, False),           # alpha = 0: pow(w, 0) = 1
+    (128, 4, 1, 0.5, 0.5, True, False, False),
+    (16, 4, -1, 1.0, 1.0, False, False, False),
+    (3, 4, 1, 0.5, 1.0, True, False, False),              # the smallest legal N (M = 1)
+    (3, 8, -1, 1.0, 0.5, True, False, False),             # K > N
+    (20, 30, 1, 10.0, 1.0, True, False, False),           # K > N
 ]
 
 
@@ -55,7 +66,8 @@ def test_operator(si, gpu_ctx, dmp, n, k, sign, eps, alpha, rescale, f32, const)
         assert np.array_equal(ad, ad.astype(np.float32))
     if const:
         assert np.all(ad[:, 0] == 0.375)
-    _, p1, lam1, kk = gpu_ctx.construct_finish_diffmap(2, eps, alpha, sign, rescale)
+    m = min(2, n - 2)   # (N = 3 admits M = 1 only)
+    _, p1, lam1, kk = gpu_ctx.construct_finish_diffmap(m, eps, alpha, sign, rescale)
     assert kk == k
     kn, u1 = gpu_ctx.diffmap_get_kernel()
     kn_ref, q = dmp.diffmap_kernel(ad, eps, alpha, sign, rescale)
@@ -66,7 +78,7 @@ def test_operator(si, gpu_ctx, dmp, n, k, sign, eps, alpha, rescale, f32, const)
     assert np.array_equal(kn, kn.T)
     assert np.max(np.abs(u1 - q / np.linalg.norm(q)) / u1) <= r
     # the bits do not depend on the run
-    _, p2, lam2, _ = gpu_ctx.construct_finish_diffmap(2, eps, alpha, sign, rescale)
+    _, p2, lam2, _ = gpu_ctx.construct_finish_diffmap(m, eps, alpha, sign, rescale)
     kn2, u12 = gpu_ctx.diffmap_get_kernel()
     assert np.array_equal(kn, kn2) and np.array_equal(u1, u12) and np.array_equal(p1, p2) and np.array_equal(lam1, lam2)
 

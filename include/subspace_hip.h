@@ -262,6 +262,31 @@ int32_t si_infer_setup_dev(si_ctx* ctx, const si_layer* layers, int32_t L, int64
  * reference's behaviour and the default after every si_infer_setup).  Applies to si_logdensity, its gradient and the
  * RWMH samplers.                                                                                                   */
 int32_t si_infer_set_prior(si_ctx* ctx, double sigma_p);
+/* The autoencoder route (src/space_inference.jl:238-318, auto_inference): the density at W_swa + decoder(z) instead of
+ * W_swa + P z.  The decoder is a Dense-only chain M -> h_1 -> ... -> h_{D-1} -> N given as a layer table whose w_off / b_off
+ * index the flat parameter vector wdec_host (Nd elements of wdec_dtype, Flux.destructure order: [vec(W_l); b_l] per layer).  Call
+ * after si_infer_setup / si_infer_setup_dev, like si_infer_set_prior; the next set-up drops it.  From then on every entry point
+ * that uses the density -- si_logdensity, si_forward, si_predict, si_reconstruct (the output map W_swa + decoder(z)),
+ * si_sample_rwmh, si_sample_rwmh_weights, the si_rwmh_* session, si_logdensity_grad, si_logdensity_grad_batch, si_sample_mala /
+ * _hmc / _nuts, si_fit_advi -- uses it, and the stored P is ignored.  dec_layers = NULL with D = 0 clears the decoder: the P route
+ * returns bit for bit.  Definition: subspaceinference.jl_amd/autoencoder.py (a_0 = z; u = W a + b with the sum over the input
+ * index ascending from 0.0 and the bias added last; a = act(u); every sum fp64).  The parameters stay on the device in the
+ * element type they came in (widening on load is exact; a Float32 decoder halves the bytes of the last layer's stream).
+ * Routes that form W_swa + P z or P' g inside a kernel of their own are NOT taken while a decoder is set: the device-resident
+ * and persistent RWMH loops, the run-time specialised loop and the fused gradient of si_logdensity_grad_batch; the
+ * launch-per-step loop and the per-point gradient path run instead, and si_chain_kernel_info's loop flag, si_grad_kernel_info
+ * and the fused flag of si_mala / hmc / nuts / advi_kernel_info report 0.
+ * SI_ERR_INVALID: a layer that is not SI_LAYER_DENSE; D outside 1 .. 8; the first `in` != M or the last `out` != N of the
+ * set-up; widths that do not chain; a hidden width or M above 1024; an offset range outside [0, Nd); an activation id out of
+ * range; a set-up with compute_dtype = SI_F32 (the fp32 weight vector is not fed on this route).  SI_ERR_STATE: before a
+ * set-up, or while a step-wise RWMH session is open.
+ * si_construct_*, si_bcast_subspace and the communicator entry points neither know nor carry a decoder: every rank sets its own. */
+int32_t si_infer_set_decoder(si_ctx* ctx, const si_layer* dec_layers, int32_t D, int64_t Nd, const void* wdec_host,
+                             int32_t wdec_dtype /* SI_F32 | SI_F64 */);
+/* D (0: no decoder set), the last layer's input width and the parameters' element type (outputs may be NULL) */
+int32_t si_infer_decoder_info(si_ctx* ctx, int32_t* D_out, int32_t* H_out, int32_t* storage_dtype_out);
+/* Y_out[:, c] = decoder(Z[:, c]) alone (N x C, column-major), without W_swa; needs a decoder */
+int32_t si_decode(si_ctx* ctx, const double* Z /* M x C */, int64_t C, double* Y_out /* N x C */);
 /* :90-95  lp[c] = logpdf(MvNormal(vec(f_{W_swa+P z_c}(X)), sigma_m), vec(Y)),  Z is M x C          */
 int32_t si_logdensity(si_ctx* ctx, const double* Z, int32_t C, double* lp_out /* C */);
 /* lp and its gradient with respect to z: grad_out[m] = d lp / d z_m = (P' * d lp / d w)[m].

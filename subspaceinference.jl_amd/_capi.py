@@ -89,6 +89,9 @@ SIGNATURES = {
     "si_infer_setup_dev": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_int32, c_void_p, c_void_p, c_int64,
                                      c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_double, c_int32]),
     "si_infer_set_prior": (c_int32, [c_void_p, c_double]),
+    "si_infer_set_decoder": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_void_p, c_int32]),
+    "si_infer_decoder_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "si_decode": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
     "si_logdensity": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p]),
     "si_logdensity_grad": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "si_logdensity_grad_batch": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
@@ -612,6 +615,37 @@ class Context:
     def set_prior(self, sigma_p):
         """non-default include_prior (Q4): sigma_p > 0 adds logpdf(MvNormal(zeros(N), sigma_p), W_swa + P z); 0 = off"""
         self._check(self.lib.si_infer_set_prior(self.h, float(sigma_p)))
+
+    def set_decoder(self, table, wdec):
+        """si_infer_set_decoder, after infer_setup: the density at W_swa + decoder(z) (autoencoder.py is the definition).  `table` is
+        the decoder's Dense layer table (flux.layer_table), `wdec` its flat Float32 or Float64 parameter vector; it stays on the
+        device in that element type.  table=None clears the decoder: the P route returns bit for bit."""
+        if table is None:
+            self._check(self.lib.si_infer_set_decoder(self.h, None, 0, 0, None, SI_F64))
+            return
+        wdec = np.ascontiguousarray(wdec)
+        if wdec.dtype not in (np.float32, np.float64) or wdec.ndim != 1:
+            raise SubspaceError("decoder parameters must be a flat Float32 or Float64 vector, got %s %s" % (wdec.dtype, wdec.shape))
+        arr = _layer_array(table)
+        self._check(self.lib.si_infer_set_decoder(self.h, arr, len(table), wdec.size, _ptr(wdec),
+                                                  SI_F32 if wdec.dtype == np.float32 else SI_F64))
+
+    def decoder_info(self):
+        """(D, H, storage dtype) of the decoder set: layers (0: none), the last layer's input width, SI_F32 / SI_F64"""
+        d, h, t = c_int32(0), c_int32(0), c_int32(0)
+        self._check(self.lib.si_infer_decoder_info(self.h, byref(d), byref(h), byref(t)))
+        return int(d.value), int(h.value), int(t.value)
+
+    def decode(self, z):
+        """decoder(z) alone for every column of the M x C matrix z: the N x C matrix (si_decode)"""
+        z = _f64(z)
+        if z.ndim == 1:
+            z = z.reshape(-1, 1, order="F")
+        if z.ndim != 2 or z.shape[0] != self._m:
+            raise SubspaceError("DimensionMismatch: z has %d rows, M = %d" % (z.shape[0], self._m))
+        y = np.empty((self._ni, z.shape[1]), dtype=np.float64, order="F")
+        self._check(self.lib.si_decode(self.h, _ptr(z), z.shape[1], _ptr(y)))
+        return y
 
     def logdensity(self, z):
         z = _f64(z)

@@ -5,6 +5,9 @@
     subspace_inference(model, cost, data, opt; σ_z, σ_m, σ_p, itr, T, c, M, ...)        -> (chn, lp, W_swa)
     sub_inference(in_model, data, W_swa, P; σ_z, σ_m, σ_p, itr, M, alg, backend)        -> (chn, lp)
     inference(...)  README-only alias of sub_inference (README.md:153-154); alg=:mh == :rwmh
+    auto_encoder_subspace(model, cost, data, opt, encoder, decoder; T=10, c=1, M=3, print_freq=1)   -> (W_swa, decoder)
+    auto_inference(m, data, decoder, W_swa; σ_z, σ_m, σ_p, itr, M, alg=:hmc, backend)               -> (chn, lp)
+    autoencoder_inference(model, cost, data, opt, encoder, decoder; σ_z, ..., alg=:hmc, backend)    -> (chn, lp)
 
 Same names, argument meaning, defaults and error behaviour (`throw(String)` -> SubspaceError) as the
 reference.  Everything numerical goes through the C ABI (include/subspace_hip.h) to the HIP kernels; the
@@ -206,6 +209,17 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
     Philox streams (seed, chain_id + c), n_adapts = round(itr / 2), max_depth = 10, max_dh = 1000; the initial state is dropped.
     It allows nchains > 1, with :hmc's shapes.  The default :nuts stays `samplers.nuts` on PCG64, bit for bit.
     """
+    return _inference(in_model, data, W_swa, P, None, σ_z, σ_m, σ_p, itr, M, alg, sigma_z=sigma_z, sigma_m=sigma_m, sigma_p=sigma_p,
+                      device=device, ctx=ctx, seed=seed, chain_id=chain_id, return_z=return_z, nchains=nchains,
+                      include_prior=include_prior, compute_dtype=compute_dtype, device_loop=device_loop,
+                      device_sampler=device_sampler, device_nuts=device_nuts)
+
+
+def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg, *, sigma_z, sigma_m, sigma_p, device, ctx, seed, chain_id,
+               return_z, nchains, include_prior, compute_dtype, device_loop, device_sampler, device_nuts):
+    """What `sub_inference` and `auto_inference` share (reference :82-164 and :238-318, the same sampler calls twice): `decoder` is
+    None (the density at W_swa + P*z) or the decoder's (layer table, flat parameters), set on the context right after the
+    inference set-up (the density, its gradient and the output map at W_swa + decoder(z))."""
     σ_z = σ_z if sigma_z is None else sigma_z
     σ_m = σ_m if sigma_m is None else sigma_m
     σ_p = σ_p if sigma_p is None else sigma_p
@@ -233,6 +247,8 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
                 # reference: MvNormal(zeros(M), σ_z) proposal against an N x size(P,2) matrix -> DimensionMismatch in P*z
                 raise SubspaceError("DimensionMismatch: P has %d columns but M = %d" % (P.shape[1], M))
             ctx.infer_setup(table, n_par, M, W_swa, P, x, y, σ_m, compute_dtype=cdt)
+        if decoder is not None:
+            ctx.set_decoder(*decoder)
         # include_prior=True adds the term the reference leaves dead after its `return` (quirk Q4); default: as the reference
         ctx.set_prior(σ_p if include_prior else 0.0)
         if device_sampler and a != "hmc":
@@ -324,6 +340,117 @@ def subspace_inference(model, cost, data, opt, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr
                                 return_z=return_z, compute_dtype=compute_dtype, device_loop=device_loop,
                                 device_sampler=device_sampler, device_nuts=device_nuts)
         return chn, lp, w_swa
+    finally:
+        if own:
+            ctx.close()
+
+
+def _decoder_spec(decoder):
+    """(layer table, flat parameters in Flux.destructure order and the decoder's own element type) of a Dense-only decoder chain"""
+    if not isinstance(decoder, flux.Chain) or not decoder.layers or not all(isinstance(l, flux.Dense) for l in decoder.layers):
+        raise SubspaceError("Error: the decoder must be a Chain of Dense layers")
+    table, _ = flux.layer_table(decoder)
+    return table, flux.extract_params(flux.params(decoder))
+
+
+def auto_encoder_subspace(model, cost, data, opt, encoder, decoder, T=10, c=1, M=3, print_freq=1, *, include_penalty=False,
+                          seed=0, device=0, ctx=None, verbose=True, device_training="auto", init="zeros", a_storage="f64",
+                          compute_dtype="auto"):
+    """src/subspace_construction.jl:93-143: the SWA loop of `subspace_construction` (:104-123, the same lines), then
+    `Chain(encoder, decoder)` trained to reproduce the deviation columns -> (W_swa, decoder); the decoder's arrays are trained in
+    place and the same object comes back, as in the reference.
+
+    The loop runs on the device like the other two constructions; the deviation matrix A (N x K) and the mean are then read
+    back (the mean through a one-column `construct_finish`, whose projection is discarded) and the autoencoder is trained on the
+    host with `flux.gradient` / `flux.update`: cost `mse(sae(X), X)`, a fresh `ADAM()`, `DataLoader(A, batchsize = 5, shuffle =
+    true)`, ONE pass (:127-140).  [upstream, unverifiable offline]: that `Flux.train!` makes a single pass over its data and
+    that `ADAM()` is ADAM(0.001, (0.9, 0.999)) are restated from Flux 0.11.2 from memory.  Training it through si_train_* is a
+    follow-up.  `M` is accepted and unused, as in the reference (the decoder's first layer carries it).
+
+    include_penalty: the reference writes `+ sum(sqnorm, autops)` on a line of its own AFTER the loss (:130-131), so Julia parses
+    it as a separate statement and the penalty is dead -- like the prior term (quirk Q4).  False (default):
+    as the reference's code behaves; True adds the term it meant.  `seed` seeds the shuffle of the autoencoder's loader."""
+    if not isinstance(encoder, flux.Chain) or not all(isinstance(l, flux.Dense) for l in encoder.layers):
+        raise SubspaceError("Error: the encoder must be a Chain of Dense layers")
+    dec_table, _ = _decoder_spec(decoder)
+    n_par = int(sum(p.size for p in flux.params(model)))
+    if encoder.layers[0].W.shape[1] != n_par or int(dec_table[-1][1]) != n_par:
+        raise SubspaceError("DimensionMismatch: the encoder takes %d inputs and the decoder returns %d values, but the model has %d "
+                            "parameters" % (encoder.layers[0].W.shape[1], int(dec_table[-1][1]), n_par))
+    if encoder.layers[-1].W.shape[0] != int(dec_table[0][0]):
+        raise SubspaceError("DimensionMismatch: the encoder returns %d values but the decoder takes %d"
+                            % (encoder.layers[-1].W.shape[0], int(dec_table[0][0])))
+
+    def finish(cx):
+        nb = len(data)
+        k = sum(1 for i in range(1, T + 1) if i % c == 0) * nb
+        a = cx.construct_get_A(0, k)
+        return cx.construct_finish(1, want_swa=True, want_p=False)[0], a
+
+    w_swa, re_weight = _swa_construction(model, cost, data, opt, T, c, print_freq, finish, device=device, ctx=ctx, max_cols=0,
+                                         verbose=verbose, keep_on_device=False, device_training=device_training, init=init,
+                                         data_parallel=False, a_storage=a_storage, compute_dtype=compute_dtype)
+    sae = flux.Chain(*encoder.layers, *decoder.layers)          # :127 Chain(encoder, decoder): the same arrays
+    autops = flux.params(sae)
+    aopt = flux.ADAM()                                         # :134
+    wdata = flux.DataLoader(re_weight, batchsize=5, shuffle=True, rng=np.random.default_rng(seed))   # :139
+    for (xb,) in wdata:                                        # :140 Flux.train!: one pass
+        loss, gs = flux.gradient(flux.mse, sae, xb, xb)
+        if include_penalty:
+            gs = [g + 2.0 * p.astype(np.float64) for g, p in zip(gs, autops)]
+        flux.update(aopt, autops, gs)
+        if verbose:                                            # :137 cb() = @show autoloss(re_weight)
+            full = flux.mse(sae, re_weight, re_weight)
+            if include_penalty:
+                full += float(sum(np.sum(p.astype(np.float64) ** 2) for p in autops))
+            print("autoloss(re_weight) = ", full)
+    return w_swa, decoder
+
+
+def auto_inference(m, data, decoder, W_swa, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=100, M=3, alg="hmc", backend="forwarddiff", *,
+                   sigma_z=None, sigma_m=None, sigma_p=None, device=0, ctx=None, seed=0, chain_id=0, return_z=False, nchains=1,
+                   include_prior=False, compute_dtype="f64", device_loop=False, device_sampler=False, device_nuts=False):
+    """src/space_inference.jl:238-318 for a Chain model: `sub_inference` with the density at `W_swa + decoder(z)` (:247) and the
+    output map `W_swa + decoder(z)` (:278,291,314) -> (chn, lp).  The default algorithm is :hmc, as in the reference.
+
+    `decoder` is a Chain of Dense layers M -> ... -> N (Float32 or Float64 parameters: they stay on the device in their own
+    element type, all sums are Float64).  The decoder's forward and the pull-back of the gradient through it run on the device
+    (si_infer_set_decoder; autoencoder.py is the definition); every algorithm and keyword of `sub_inference` is accepted, with
+    the same meaning, except compute_dtype="f32", which the decoder route refuses.  While a decoder is set the device-resident
+    RWMH loops and the fused stacked gradient are not taken (they form W_swa + P*z themselves): the launch-per-step loop and the
+    per-point gradient path run instead.  The inference set-up is given a zero N x M matrix for P -- 8 N M idle bytes on the
+    device, the price of sharing the set-up with `sub_inference`."""
+    if not isinstance(m, flux.Chain):
+        raise SubspaceError("Error: density function is not avaliable for this model")  # [sic] as sub_inference (:103)
+    spec = _decoder_spec(decoder)
+    n_par = int(sum(p.size for p in flux.params(m)))
+    if int(spec[0][0][0]) != M:
+        raise SubspaceError("DimensionMismatch: the decoder takes %d inputs but M = %d" % (int(spec[0][0][0]), M))
+    if int(spec[0][-1][1]) != n_par:
+        raise SubspaceError("DimensionMismatch: the decoder returns %d values but the model has %d parameters"
+                            % (int(spec[0][-1][1]), n_par))
+    W_swa = np.asarray(W_swa, dtype=np.float64)
+    if W_swa.shape != (n_par,):
+        raise SubspaceError("DimensionMismatch: W_swa has shape %s but the model has %d parameters" % (W_swa.shape, n_par))
+    return _inference(m, data, W_swa, np.zeros((n_par, M), order="F"), spec, σ_z, σ_m, σ_p, itr, M, alg, sigma_z=sigma_z,
+                      sigma_m=sigma_m, sigma_p=sigma_p, device=device, ctx=ctx, seed=seed, chain_id=chain_id, return_z=return_z,
+                      nchains=nchains, include_prior=include_prior, compute_dtype=compute_dtype, device_loop=device_loop,
+                      device_sampler=device_sampler, device_nuts=device_nuts)
+
+
+def autoencoder_inference(model, cost, data, opt, encoder, decoder, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=1000, T=25, c=1, M=20,
+                          print_freq=1, alg="hmc", backend="forwarddiff", *, sigma_z=None, sigma_m=None, sigma_p=None, device=0,
+                          ctx=None, seed=0, verbose=True, return_z=False, include_penalty=False, include_prior=False,
+                          device_loop=False, device_sampler=False, device_nuts=False):
+    """src/space_inference.jl:198-210: `auto_encoder_subspace`, then `auto_inference`, on one context -> (chn, lp)."""
+    ctx, own = _get_ctx(ctx, device)
+    try:
+        w_swa, decoder = auto_encoder_subspace(model, cost, data, opt, encoder, decoder, T=T, c=c, M=M, print_freq=print_freq,
+                                               include_penalty=include_penalty, seed=seed, ctx=ctx, verbose=verbose)
+        return auto_inference(model, data, decoder, w_swa, σ_z=σ_z, σ_m=σ_m, σ_p=σ_p, itr=itr, M=M, alg=alg, backend=backend,
+                              sigma_z=sigma_z, sigma_m=sigma_m, sigma_p=sigma_p, ctx=ctx, seed=seed, return_z=return_z,
+                              include_prior=include_prior, device_loop=device_loop, device_sampler=device_sampler,
+                              device_nuts=device_nuts)
     finally:
         if own:
             ctx.close()

@@ -61,6 +61,13 @@ si::DensityView setup_view(const si_ctx* ctx, bool defer_sse_final = false);
 // d_zprop[:, c0 .. c0+nc) -> d_sse, nc <= the view's chain slots; eval_density_all: all C chains, fw_slots at a time
 int32_t eval_density(si_ctx* ctx, const si::DensityView& v, int c0, int nc, const double** yhat_out);
 int32_t eval_density_all(si_ctx* ctx, const si::DensityView& v, int C);
+// "form the weights of these points": w[:, c] = W_swa + P z_c (K4), or W_swa + decoder(z_c) while a decoder is set
+// (si_infer_set_decoder), for the n points z_dev[M x n] (device).  The one place the C ABI forms weights outside a sampler
+// kernel of its own.  w32: also rounded once to fp32 (P route only).  keep_y (decoder route, n = 1): decoder(z) stays in dec.y
+// for pull_back_to_z.  Queued on the stream; an error only when the decoder's workspace cannot grow.
+int32_t form_weights(si_ctx* ctx, const double* z_dev, int32_t n, double* w, int64_t ldw, float* w32 = nullptr, bool keep_y = false);
+// "pull d_gw back to z": gz = P' gw, or J_decoder(z)' gw at the point form_weights(.., keep_y = true) saw last
+void pull_back_to_z(si_ctx* ctx, const double* gw, double* gz);
 double mvnormal_c0(double d, double sigma);
 double prior_c0(const si_ctx* ctx);
 void fused_fill_program(const si_ctx* ctx, si::ChainFusedPlan& fp);

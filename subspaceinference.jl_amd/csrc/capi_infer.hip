@@ -284,6 +284,55 @@ DensityView setup_view(const si_ctx* ctx, bool defer_sse_final) {
           ctx->d_part, ctx->d_yhat, ctx->act_elems, ctx->f32, defer_sse_final, true};
 }
 
+// ---- the seam between z and the weights: W_swa + P z (K4, P' g) or, while a decoder is set, W_swa + decoder(z) ------------------
+// The decoder's launches carry at most SI_DEC_CHUNK points; `hid` (every head layer's output per point) grows to the chunk.
+static constexpr int32_t SI_DEC_CHUNK = 16384;
+static int32_t decoder_reserve_hid(si_ctx* ctx, int32_t n) {
+  DecoderState& d = ctx->dec;
+  if (d.SH == 0 || d.hid_cap >= n) return SI_OK;
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (launches queued on the old buffer)
+  d.hid_cap = 0;
+  if (!d.hid.alloc((size_t)d.SH * (size_t)n)) return fail(ctx, SI_ERR_NOMEM, "decoder: allocation of the hidden activations failed");
+  d.hid_cap = n;
+  return SI_OK;
+}
+// decoder(z) of n <= SI_DEC_CHUNK points: w = swa + y and / or y alone (either may be null)
+static int32_t decoder_forward(si_ctx* ctx, const double* z_dev, int32_t n, double* w, int64_t ldw, double* y, int64_t ldy) {
+  DecoderState& d = ctx->dec;
+  const int32_t rc = decoder_reserve_hid(ctx, n);
+  if (rc != SI_OK) return rc;
+  launch_decoder_head_fwd(ctx->stream, d.head, d.params, d.dtype, z_dev, ctx->iM, d.hid, d.SH, n);
+  const double* a = d.D > 1 ? d.hid + d.head.hid_off[d.D - 2] : z_dev;   // the last layer's input: a_{D-1}, or z itself
+  launch_decoder_last_fwd(ctx->stream, ctx->i_swa, d.lastW, pad_ld(ctx->iN), d.lastb, d.dtype, ctx->iN, d.H, d.last_act, a,
+                          d.D > 1 ? d.SH : ctx->iM, n, w, ldw, y, ldy, ctx->num_cu);
+  return SI_OK;
+}
+
+int32_t form_weights(si_ctx* ctx, const double* z_dev, int32_t n, double* w, int64_t ldw, float* w32, bool keep_y) {
+  if (!ctx->dec.on) {
+    launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, ctx->iN, ctx->iM, z_dev, n, w, ldw, ctx->num_cu, w32, ldw);
+    return SI_OK;
+  }
+  // (w32 is never asked for here: si_infer_set_decoder refuses a set-up with compute_dtype = SI_F32)
+  for (int32_t p0 = 0; p0 < n; p0 += SI_DEC_CHUNK) {
+    const int32_t np = std::min(SI_DEC_CHUNK, n - p0);
+    const int32_t rc = decoder_forward(ctx, z_dev + (size_t)ctx->iM * p0, np, w + (size_t)ldw * p0, ldw,
+                                       keep_y ? ctx->dec.y.get() : nullptr, pad_ld(ctx->iN));
+    if (rc != SI_OK) return rc;
+  }
+  return SI_OK;
+}
+
+void pull_back_to_z(si_ctx* ctx, const double* gw, double* gz) {
+  DecoderState& d = ctx->dec;
+  if (!d.on) {
+    launch_ptg(ctx->stream, ctx->i_P, ctx->ldP, ctx->iN, ctx->iM, gw, ctx->d_ptgpart, gz);
+    return;
+  }
+  launch_decoder_last_rev(ctx->stream, d.lastW, pad_ld(ctx->iN), d.dtype, ctx->iN, d.H, d.last_act, gw, d.y, d.part, d.ga);
+  launch_decoder_head_rev(ctx->stream, d.head, d.params, d.dtype, d.ga, d.H, d.hid, d.SH, gz, ctx->iM, 1);
+}
+
 // ---- the three routes of a density evaluation: K4 has left the weights of chain slots [c0, c0 + nc) in d_w (and d_w32) ------------
 // Conv / MaxPool / flatten / Dense layers one after the other (capi_net.hip), ping-pong activations, one chain per pass.
 // T = float is compute_dtype = SI_F32 on a Conv chain: the same pass on fp32 operands, the squared errors in fp64 with the
@@ -405,8 +454,8 @@ int32_t eval_density(si_ctx* ctx, const DensityView& v, int c0, int nc, const do
   const double dn = (double)nc;
   {
     ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * dn, (double)N * (M + 1 + dn) * 8.0);
-    launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, ctx->d_zprop + (size_t)c0 * M, nc, ctx->d_w, ldw,
-                       ctx->num_cu, v.f32 ? ctx->d_w32.get() : nullptr, ldw);
+    const int32_t rc = form_weights(ctx, ctx->d_zprop + (size_t)c0 * M, nc, ctx->d_w, ldw, v.f32 ? ctx->d_w32.get() : nullptr);
+    if (rc != SI_OK) return rc;
   }
   if (ctx->sigma_p > 0.0)  // ||new_W||^2 per chain for the optional prior term (same fixed-order reduction as the SSE)
     launch_sse(ctx->stream, ctx->d_w, nullptr, N, ctx->d_wsqpart, ctx->wsq_blocks, ctx->d_wsq + c0, nc, ldw);
@@ -452,6 +501,100 @@ int32_t si_infer_set_prior(si_ctx* ctx, double sigma_p) {
   if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_infer_set_prior: a step-wise RWMH session is open");
   if (!(sigma_p >= 0.0)) return fail(ctx, SI_ERR_INVALID, "si_infer_set_prior: sigma_p must be >= 0 (0 = off, the reference's behaviour)");
   ctx->sigma_p = sigma_p;
+  return SI_OK;
+}
+
+// the decoder's last layer as the streaming kernels read it: W (N x H) with its columns ldD apart, b, both with zero padding rows
+extern "C++" template <typename T>
+static bool decoder_upload(si_ctx* ctx, DecoderState& d, const si_layer& last, const void* wdec, int64_t Nd, int64_t N, int64_t ldD) {
+  const T* src = static_cast<const T*>(wdec);
+  std::vector<T> Wp((size_t)ldD * (size_t)last.in, T(0)), bp((size_t)ldD, T(0));
+  for (int32_t h = 0; h < last.in; ++h)
+    std::memcpy(Wp.data() + (size_t)ldD * h, src + last.w_off + (int64_t)N * h, (size_t)N * sizeof(T));
+  std::memcpy(bp.data(), src + last.b_off, (size_t)N * sizeof(T));
+  return d.params.alloc((size_t)Nd * sizeof(T)) && d.lastW.alloc(Wp.size() * sizeof(T)) && d.lastb.alloc(bp.size() * sizeof(T)) &&
+         hipMemcpy(d.params, src, (size_t)Nd * sizeof(T), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d.lastW, Wp.data(), Wp.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d.lastb, bp.data(), bp.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+}
+
+int32_t si_infer_set_decoder(si_ctx* ctx, const si_layer* dec_layers, int32_t D, int64_t Nd, const void* wdec_host, int32_t wdec_dtype) {
+  CHECK_CTX(ctx);
+  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_infer_set_decoder: call si_infer_setup first");
+  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_infer_set_decoder: a step-wise RWMH session is open");
+  BIND(ctx);
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (!dec_layers && D == 0) {   // clear: the P route returns
+    ctx->dec = DecoderState();
+    return SI_OK;
+  }
+  auto bad = [&](const char* what) { return fail(ctx, SI_ERR_INVALID, std::string("si_infer_set_decoder: ") + what); };
+  if (!dec_layers || D < 1 || D > SI_DEC_MAX_LAYERS || Nd <= 0 || !wdec_host) return bad("bad argument (1 <= D <= 8 layers, Nd > 0, parameters given)");
+  if (wdec_dtype != SI_F32 && wdec_dtype != SI_F64) return bad("wdec_dtype must be SI_F32 or SI_F64");
+  if (ctx->f32) return bad("the set-up's compute_dtype is SI_F32: the fp32 weight vector is not fed on the decoder route (set up with SI_F64)");
+  const int64_t N = ctx->iN;
+  if (ctx->iM > 1024) return bad("M exceeds 1024");
+  for (int32_t l = 0; l < D; ++l) {
+    const si_layer& ly = dec_layers[l];
+    if (ly.kind != SI_LAYER_DENSE) return bad("every decoder layer must be SI_LAYER_DENSE");
+    if (ly.in < 1 || ly.out < 1) return bad("layer widths must be positive");
+    if (ly.act < 0 || ly.act >= SI_ACT_COUNT) return bad("unknown activation");
+    if (l == 0 && ly.in != ctx->iM) return bad("the first layer's `in` differs from the set-up's M");
+    if (l > 0 && ly.in != dec_layers[l - 1].out) return bad("consecutive layer widths do not chain");
+    if (l == D - 1 && ly.out != N) return bad("the last layer's `out` differs from the set-up's N");
+    if (l < D - 1 && ly.out > 1024) return bad("a hidden width exceeds 1024");
+    const int64_t wn = (int64_t)ly.in * ly.out;
+    if (ly.w_off < 0 || ly.w_off > Nd - wn || ly.b_off < 0 || ly.b_off > Nd - ly.out) return bad("a layer's offset range falls outside [0, Nd)");
+  }
+  DecoderState d;
+  d.D = D, d.dtype = wdec_dtype, d.H = dec_layers[D - 1].in, d.last_act = dec_layers[D - 1].act;
+  d.head.n = D - 1;
+  for (int32_t l = 0; l < D - 1; ++l) {
+    const si_layer& ly = dec_layers[l];
+    d.head.in[l] = ly.in, d.head.out[l] = ly.out, d.head.act[l] = ly.act, d.head.hid_off[l] = d.SH;
+    d.head.w_off[l] = ly.w_off, d.head.b_off[l] = ly.b_off;
+    d.SH += ly.out;
+  }
+  const int64_t ldD = pad_ld(N);
+  const bool up = wdec_dtype == SI_F32 ? decoder_upload<float>(ctx, d, dec_layers[D - 1], wdec_host, Nd, N, ldD)
+                                       : decoder_upload<double>(ctx, d, dec_layers[D - 1], wdec_host, Nd, N, ldD);
+  if (!up || !d.y.alloc((size_t)ldD) || !d.part.alloc((size_t)decoder_rev_blocks() * (size_t)d.H) || !d.ga.alloc((size_t)d.H))
+    return fail(ctx, SI_ERR_NOMEM, "si_infer_set_decoder: device allocation / upload failed");   // (the decoder set before stays)
+  d.on = true;
+  ctx->dec = std::move(d);
+  return SI_OK;
+}
+
+int32_t si_infer_decoder_info(si_ctx* ctx, int32_t* D_out, int32_t* H_out, int32_t* storage_dtype_out) {
+  CHECK_CTX(ctx);
+  if (D_out) *D_out = ctx->dec.on ? ctx->dec.D : 0;
+  if (H_out) *H_out = ctx->dec.on ? ctx->dec.H : 0;
+  if (storage_dtype_out) *storage_dtype_out = ctx->dec.on ? ctx->dec.dtype : SI_F64;
+  return SI_OK;
+}
+
+int32_t si_decode(si_ctx* ctx, const double* Z, int64_t C, double* Y_out) {
+  CHECK_CTX(ctx);
+  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_decode: call si_infer_setup first");
+  if (!ctx->dec.on) return fail(ctx, SI_ERR_STATE, "si_decode: no decoder is set (si_infer_set_decoder)");
+  if (!Z || C <= 0 || !Y_out) return fail(ctx, SI_ERR_INVALID, "si_decode: bad argument");
+  BIND(ctx);
+  const int64_t N = ctx->iN, ldy = pad_ld(N);
+  const int32_t M = ctx->iM;
+  // a test and audit read-back, not a hot path: groups of at most 64 points (~32 MB of output), one synchronisation per group
+  const int64_t group = std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)32 << 20) / (N * 8)));
+  DevBuf<double> dZ, dY;
+  if (!dZ.alloc((size_t)M * (size_t)group) || !dY.alloc((size_t)ldy * (size_t)group)) return fail(ctx, SI_ERR_NOMEM, "si_decode: device allocation failed");
+  for (int64_t c0 = 0; c0 < C; c0 += group) {
+    const int32_t nc = (int32_t)std::min(group, C - c0);
+    SI_HIP(ctx, hipMemcpyAsync(dZ, Z + c0 * M, (size_t)M * nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const int32_t rc = decoder_forward(ctx, dZ, nc, nullptr, 0, dY, ldy);
+    if (rc != SI_OK) return rc;
+    SI_HIP(ctx, hipGetLastError());
+    SI_HIP(ctx, hipMemcpy2DAsync(Y_out + c0 * N, (size_t)N * sizeof(double), dY, (size_t)ldy * sizeof(double), (size_t)N * sizeof(double),
+                                 (size_t)nc, hipMemcpyDeviceToHost, ctx->stream));
+    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
   return SI_OK;
 }
 
@@ -553,8 +696,8 @@ static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_ou
   SI_HIP(ctx, hipMemcpyAsync(ctx->d_zprop, z, (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   {
     ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M, (double)N * (M + 2) * 8.0);
-    launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, ctx->d_zprop, 1, ctx->d_w, pad_ld(N), ctx->num_cu,
-                       ctx->f32 ? ctx->d_w32 : nullptr, pad_ld(N));
+    if ((rc = form_weights(ctx, ctx->d_zprop, 1, ctx->d_w, pad_ld(N), ctx->f32 ? ctx->d_w32.get() : nullptr, /*keep_y=*/true)) != SI_OK)
+      return rc;
   }
   const bool prior = ctx->sigma_p > 0.0;
   if (prior) launch_sse(ctx->stream, ctx->d_w, nullptr, N, ctx->d_wsqpart, ctx->wsq_blocks, ctx->d_wsq, 1, pad_ld(N));
@@ -582,7 +725,7 @@ static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_ou
     if ((rc = dense_value_and_grad_f64(ctx, ctx->stream, vg)) != SI_OK) return rc;
   }
   if (prior) launch_prior_grad(ctx->stream, ctx->d_gw, ctx->d_w, N, 1.0 / (ctx->sigma_p * ctx->sigma_p), ctx->num_cu);
-  launch_ptg(ctx->stream, ctx->i_P, ctx->ldP, N, M, ctx->d_gw, ctx->d_ptgpart, ctx->d_gz);
+  pull_back_to_z(ctx, ctx->d_gw, ctx->d_gz);
   SI_HIP(ctx, hipGetLastError());
   double sse = 0.0, wsq = 0.0;
   SI_HIP(ctx, hipMemcpyAsync(&sse, ctx->d_sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -648,7 +791,7 @@ static int vgrad_class(si_ctx* ctx) {
 // the points one pass of launches may carry.
 static int vgrad_route(si_ctx* ctx, int64_t* G_out, int64_t* fit_out) {
   const int64_t B = ctx->B, ldw = pad_ld(ctx->iN);
-  const int nb = vgrad_class(ctx);
+  const int nb = ctx->dec.on ? 0 : vgrad_class(ctx);   // (chain_vgrad_reduce_kernel forms P' g itself: not taken with a decoder)
   const int64_t G = nb > 0 ? (B + 16 * nb - 1) / (16 * nb) : 0;
   // points per pass of launches: the workspace (weights, G partials of grad_w, grad_w per point) is capped like the forward
   // workspace of the stacked density (SI_BATCH_BYTES), and a launch carries at most 65535 points in grid.y
@@ -688,7 +831,7 @@ static void vgrad_pass(si_ctx* ctx, int nb, int64_t G, const double* z_dev, int 
   const double c0 = mvnormal_c0((double)ctx->out_dim * (double)B, ctx->sigma_m);
   {
     ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * n, (double)N * (M + 1 + n) * 8.0);
-    launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, z_dev, n, ctx->d_vg_w, ldw, ctx->num_cu);
+    (void)form_weights(ctx, z_dev, n, ctx->d_vg_w, ldw);   // (the P route: vgrad_route keeps this pass away from a decoder, whose reverse it does not carry)
   }
   {
     ProfScope ps(ctx, SI_K_BACKWARD, 6.0 * (double)N * (double)B * n, 0.0);

@@ -58,7 +58,7 @@ static int32_t ensure_wstream(si_ctx* ctx, int32_t C) {
 // launches per transition spread over the chip (2 N B <= 3 MFLOP: the README toy is 0.14)
 static constexpr size_t SI_CHAIN_LDS_LIMIT = 160 * 1024 - 256;
 static bool chain_loop_applies(const si_ctx* ctx) {
-  if (ctx->f32 || ctx->plan.has_conv || !ctx->fuse_tail || ctx->sigma_p > 0.0) return false;
+  if (ctx->f32 || ctx->plan.has_conv || !ctx->fuse_tail || ctx->sigma_p > 0.0 || ctx->dec.on) return false;   // (dec: the loop forms W_swa + P z itself)
   if (ctx->layers.size() > (size_t)SI_CHAIN_MAX_LAYERS || ctx->iN > (1 << 20) || ctx->B > (1 << 20)) return false;
   if (ctx->iM > 1024) return false;   // (rwmh_chain_kernel keeps z one element per thread of its 1024-thread workgroup)
   for (const auto& ly : ctx->layers)
@@ -86,8 +86,8 @@ static int32_t finish_chains(si_ctx* ctx, const char* who, hipError_t e, int64_t
     if (!dW.alloc(wall_elems)) e = hipErrorOutOfMemory;   // (ldw * itr * C: the caller has held it to its 512 MB gate)
     if (e == hipSuccess) {
       ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * (double)itr * C, (double)N * (M + 1 + (double)itr * C) * 8.0);
-      launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, ctx->d_outZ, (int32_t)(itr * C), dW, ldw, ctx->num_cu);
-      e = hipGetLastError();
+      const int32_t rcw = form_weights(ctx, ctx->d_outZ, (int32_t)(itr * C), dW, ldw);
+      e = rcw == SI_OK ? hipGetLastError() : hipErrorOutOfMemory;
     }
     if (e == hipSuccess)
       e = hipMemcpy2DAsync(W_out, (size_t)N * sizeof(double), dW, (size_t)ldw * sizeof(double), (size_t)N * sizeof(double),
@@ -217,7 +217,8 @@ static const SpecKernels* prepare_spec_loop(si_ctx* ctx, const RwmhCall& k, int 
 // chain, two bounded grid barriers per transition.  Same bits as the launch-per-step loop (tests/test_gpu_chain_grid.py).
 static int32_t rwmh_grid(si_ctx* ctx, const RwmhCall& k) {
   const int32_t C = k.C, M = ctx->iM;
-  if (!k.map_fits || !ctx->fused_ok || ctx->chain_mode != 1 || ctx->sigma_p > 0.0 || C > ctx->fw_slots || k.itr >= ((int64_t)1 << 24))
+  if (!k.map_fits || !ctx->fused_ok || ctx->chain_mode != 1 || ctx->sigma_p > 0.0 || C > ctx->fw_slots || k.itr >= ((int64_t)1 << 24) ||
+      ctx->dec.on)   // (both grid loops, the run-time specialised one included, form W_swa + P z in their own K4)
     return SI_NOT_TAKEN;
   ChainGridArgs a{};
   const int L = (int)ctx->layers.size();
@@ -308,7 +309,7 @@ struct WeightRing {
       if (select_path)
         launch_weights_select(ctx->stream, ctx->d_accflag, ctx->d_w, ldw, t > 0 ? slot(t - 1) : nullptr, slot(t), ldw, N, C, ctx->num_cu);
       else  // more chains than one pass of launches carries: K4 on the current states (same kernel, same bits)
-        launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, ctx->iM, ctx->d_zcur, C, slot(t), ldw, ctx->num_cu);
+        if (form_weights(ctx, ctx->d_zcur, C, slot(t), ldw) != SI_OK) return hipErrorOutOfMemory;
     }
     e = hipEventRecord(ctx->ev_wcomp[r], ctx->stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream2, ctx->ev_wcomp[r], 0);
@@ -593,8 +594,9 @@ int32_t si_reconstruct(si_ctx* ctx, const double* Z, int64_t C, double* W_out) {
     if (e != hipSuccess) break;
     {
       ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * nc, (double)N * (M + 1 + nc) * 8.0);
-      launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, N, M, dZ[b], (int32_t)nc, dW[b], ldw, ctx->num_cu);
+      if (form_weights(ctx, dZ[b], (int32_t)nc, dW[b], ldw) != SI_OK) e = hipErrorOutOfMemory;
     }
+    if (e != hipSuccess) break;
     e = hipEventRecord(ev_comp[b], ctx->stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream2, ev_comp[b], 0);
     if (e == hipSuccess)

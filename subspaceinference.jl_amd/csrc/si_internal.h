@@ -276,9 +276,33 @@ struct CallInfo {
   int64_t rounds = 0, leaves = 0;
 };
 
+// The autoencoder route (si_infer_set_decoder; reference src/space_inference.jl:247,278: W_swa + decoder(z)): a Dense-only
+// decoder M -> h_1 -> ... -> h_{D-1} -> N with its parameters on the device in the element type they came in.  The layers
+// 1 .. D-1 (the "head") read `params` at the caller's offsets; the last layer's W (N x H) is kept a second time with its
+// columns pad_ld(N) apart and zero padding rows, so that the streaming kernels read aligned row pairs whatever N is.
+constexpr int SI_DEC_MAX_LAYERS = 8;
+struct DecoderHead {             // the head's layer table as the two one-workgroup-per-point kernels take it (by value)
+  int32_t n = 0;                 // D - 1
+  int32_t in[SI_DEC_MAX_LAYERS] = {0}, out[SI_DEC_MAX_LAYERS] = {0}, act[SI_DEC_MAX_LAYERS] = {0}, hid_off[SI_DEC_MAX_LAYERS] = {0};
+  int64_t w_off[SI_DEC_MAX_LAYERS] = {0}, b_off[SI_DEC_MAX_LAYERS] = {0};
+};
+struct DecoderState {
+  bool on = false;
+  int32_t D = 0, H = 0, dtype = SI_F64, last_act = 0;   // H: the last layer's `in` (M when D = 1)
+  int32_t SH = 0;                // sum of the hidden widths: rows of `hid`
+  DecoderHead head;
+  DevBuf<char> params;           // the flat parameter vector (Nd elements of `dtype`)
+  DevBuf<char> lastW, lastb;     // pad_ld(N) x H and pad_ld(N) elements of `dtype`
+  DevBuf<double> hid;            // SH x hid_cap: every head layer's output per point (the reverse sweep's act')
+  int64_t hid_cap = 0;
+  DevBuf<double> y;              // pad_ld(N): decoder(z) at the gradient's point
+  DevBuf<double> part, ga;       // the last layer's reverse: block partials (blocks x H), d lp / d a_{D-1} (H)
+};
+
 // ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops
 struct InferState {
   bool i_ready = false;
+  DecoderState dec;               // set: every density entry point forms W_swa + decoder(z); the stored P is ignored
   const double* i_swa = nullptr;  // device; borrowed (the construction's, the caller's) or d_iswa
   const double* i_P = nullptr;    // device, ldP x M; likewise
   DevBuf<double> d_iswa;          // owned copies when set from host
@@ -448,6 +472,22 @@ bool launch_project_stream_f32(hipStream_t st, const float* A, int64_t ldA, int6
 void launch_reconstruct(hipStream_t st, const double* swa, const double* P, int64_t ldP, int64_t N,
                         int32_t M, const double* Z, int32_t C, double* w, int64_t ldw, int num_cu,
                         float* w32 = nullptr /* SI_F32: the same sums rounded once to fp32 */, int64_t ldw32 = 0);
+// The decoder's kernels (kernels_decoder.hip); `dtype` is the parameters' element type (SI_F32 / SI_F64), every sum fp64.
+// head forward: a_l = act(W_l a_{l-1} + b_l), l = 1 .. D-1, one workgroup per point; hid[:, p] keeps every a_l
+void launch_decoder_head_fwd(hipStream_t st, const DecoderHead& hd, const void* params, int32_t dtype, const double* Z, int32_t M,
+                             double* hid, int32_t SH, int32_t npoints);
+// last layer forward, K4's access pattern: y = act(W_D a + b_D), w = swa + y for point c at w + c * ldw (w may be null) and y
+// at y + c * ldy (y may be null); a of point c at A + c * lda
+void launch_decoder_last_fwd(hipStream_t st, const double* swa, const void* Wd, int64_t ldD, const void* bd, int32_t dtype, int64_t N,
+                             int32_t H, int32_t act, const double* A, int64_t lda, int32_t C, double* w, int64_t ldw, double* y,
+                             int64_t ldy, int num_cu);
+// last layer reverse: ga[h] = sum_r W_D[r, h] * g[r] * act'(y[r]) (launch_ptg's scheme; part: decoder_rev_blocks() x H)
+int decoder_rev_blocks();
+void launch_decoder_last_rev(hipStream_t st, const void* Wd, int64_t ldD, int32_t dtype, int64_t N, int32_t H, int32_t act,
+                             const double* g, const double* y, double* part, double* ga);
+// head reverse: ga -> gz through the transposed head layers, act' from hid; one workgroup per point
+void launch_decoder_head_rev(hipStream_t st, const DecoderHead& hd, const void* params, int32_t dtype, const double* ga, int32_t H,
+                             const double* hid, int32_t SH, double* gz, int32_t M, int32_t npoints);
 // Chain batching of the forward pass: `n` chain slots run in ONE launch (grid.y = slot).  Strides, in elements, from
 // one slot to the next: `w` of the reconstructed weight vectors (W, bias, Wlast all live in it), `hin` / `hout` of
 // the layer's input / output activations (hin = 0 for the first layer: X is shared), `part` of the fused-tail partials.

@@ -493,6 +493,33 @@ function reconstruct(ctx::Ctx, Z::Matrix{Float64}, N)
     return [Wm[:, t] for t in 1:size(Z, 2)]
 end
 
+# ---- the autoencoder route (src/space_inference.jl:238-318): the density at W_swa + decoder(z) -------------------------------
+# set_decoder!(ctx, decoder) after the inference set-up: a Dense-only Chain, its parameters in Flux.destructure order and in their
+# own element type (Float32, Flux's default, or Float64); from then on logdensity, logdensity_grad, the samplers and reconstruct
+# use it and the stored P is ignored.  set_decoder!(ctx, nothing) clears it.
+function set_decoder!(ctx::Ctx, decoder)
+    if decoder === nothing
+        check(ctx, ccall((:si_infer_set_decoder, LIB), Int32, (Ptr{Cvoid}, Ptr{SiLayer}, Int32, Int64, Ptr{Cvoid}, Int32),
+            ctx.h, C_NULL, 0, 0, C_NULL, SI_F64))
+        return
+    end
+    tbl, Nd = layer_table(decoder)
+    wdec = collect(extract_params(Flux.params(decoder)))
+    eltype(wdec) in (Float32, Float64) || throw("Error: decoder parameters must be Float32 or Float64")
+    GC.@preserve tbl wdec check(ctx, ccall((:si_infer_set_decoder, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{SiLayer}, Int32, Int64, Ptr{Cvoid}, Int32), ctx.h, tbl, length(tbl), Nd, wdec, si_dtype(eltype(wdec))))
+end
+function decoder_info(ctx::Ctx)
+    D, H, dt = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    check(ctx, ccall((:si_infer_decoder_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}), ctx.h, D, H, dt))
+    return Int(D[]), Int(H[]), Int(dt[])
+end
+function decode(ctx::Ctx, Z::Matrix{Float64}, N)                     # decoder(z) alone, column by column
+    Y = Matrix{Float64}(undef, N, size(Z, 2))
+    GC.@preserve Z Y check(ctx, ccall((:si_decode, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}), ctx.h, Z, size(Z, 2), Y))
+    return Y
+end
+
 # include_prior = true adds the term the reference writes after its `return` (dead code, :95); default: as the reference
 # compute_dtype = :f32 (non-default; SURVEY section 0 Q6): the density of a Dense or Conv chain on the fp32 matrix instructions -- X rounded
 # once, W_swa + P*z formed in Float64 and rounded once per transition, Float32 activations, head + sum of squared errors in Float64

@@ -51,6 +51,11 @@ class SiStats(Structure):
                 ("flops", c_double * K_COUNT), ("bytes", c_double * K_COUNT)]
 
 
+class SiNodeOpts(Structure):
+    _fields_ = [("t0", c_double), ("reltol", c_double), ("abstol", c_double), ("dt", c_double),
+                ("adaptive", c_int32), ("max_steps", c_int32), ("pre_power", c_int32)]
+
+
 # every symbol include/subspace_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "si_version": (c_int32, []),
@@ -92,6 +97,11 @@ SIGNATURES = {
     "si_infer_set_decoder": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_void_p, c_int32]),
     "si_infer_decoder_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "si_decode": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "si_infer_setup_node": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int32, c_int32, c_int64, c_void_p, c_void_p]),
+    "si_node_solve": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "si_node_tableau": (c_int32, [c_void_p]),
+    "si_node_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), POINTER(c_int32)]),
     "si_logdensity": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p]),
     "si_logdensity_grad": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "si_logdensity_grad_batch": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
@@ -646,6 +656,51 @@ class Context:
         y = np.empty((self._ni, z.shape[1]), dtype=np.float64, order="F")
         self._check(self.lib.si_decode(self.h, _ptr(z), z.shape[1], _ptr(y)))
         return y
+
+    def infer_setup_node(self, table, n, m, w_swa, p, u0, y, ts, t0=0.0, reltol=1e-3, abstol=1e-6, dt=0.0, adaptive=True,
+                         max_steps=100000, pre_power=1):
+        """si_infer_setup_node, in place of infer_setup, for a NeuralODE (node.py is the definition): `table` is the Dense layer table
+        of the right-hand side d -> ... -> d, u0 the initial states (d x f), y the observed trajectories (d*S x f, row i*S + s: state i
+        at ts[s]), ts the S save times.  w_swa / p None => the finished construction."""
+        arr = _layer_array(table)
+        u0, y, ts = _f64(u0), _f64(y), np.ascontiguousarray(ts, dtype=np.float64).reshape(-1)
+        if u0.ndim != 2 or y.ndim != 2 or u0.shape[1] != y.shape[1] or y.shape[0] != u0.shape[0] * ts.size:
+            raise SubspaceError("DimensionMismatch: U0 is %s, Y is %s, %d save times: Y must be (d*S, f)" % (u0.shape, y.shape, ts.size))
+        if w_swa is not None:
+            w_swa = _f64(w_swa)
+            p = _f64(p)
+            if w_swa.shape != (n,) or p.shape != (n, m):
+                raise SubspaceError("DimensionMismatch: W_swa %s, P %s, expected (%d,), (%d, %d)" % (w_swa.shape, p.shape, n, n, m))
+        opts = SiNodeOpts(float(t0), float(reltol), float(abstol), float(dt), 1 if adaptive else 0, int(max_steps), int(pre_power))
+        self._check(self.lib.si_infer_setup_node(self.h, arr, len(table), int(n), int(m), _ptr(w_swa), _ptr(p), _ptr(u0), _ptr(y),
+                                                 u0.shape[0], ts.size, u0.shape[1], _ptr(ts), byref(opts)))
+        self._m, self._in, self._out, self._b, self._ni = int(m), u0.shape[0], y.shape[0], u0.shape[1], int(n)
+
+    def node_info(self):
+        """(active, d, S, f, G): whether a NeuralODE set-up is active, its sizes and the lanes that share one trajectory"""
+        on, d, s, g, f = c_int32(0), c_int32(0), c_int32(0), c_int32(0), c_int64(0)
+        self._check(self.lib.si_node_info(self.h, byref(on), byref(d), byref(s), byref(f), byref(g)))
+        return bool(on.value), int(d.value), int(s.value), int(f.value), int(g.value)
+
+    def node_solve(self, z, want_u=True):
+        """the trajectories at every column of z (M x C): (U (d*S, f, C) or None, sse (f, C), naccept, nreject, status (f, C) int32)"""
+        z = _f64(z)
+        if z.ndim == 1:
+            z = z.reshape(-1, 1, order="F")
+        if z.ndim != 2 or z.shape[0] != self._m:
+            raise SubspaceError("DimensionMismatch: z has %d rows, M = %d" % (z.shape[0], self._m))
+        c = z.shape[1]
+        u = np.empty((self._out, self._b, c), dtype=np.float64, order="F") if want_u else None
+        sse = np.empty((self._b, c), dtype=np.float64, order="F")
+        na, nr, st = (np.empty((self._b, c), dtype=np.int32, order="F") for _ in range(3))
+        self._check(self.lib.si_node_solve(self.h, _ptr(z), c, _ptr(u), _ptr(sse), _ptr(na), _ptr(nr), _ptr(st)))
+        return u, sse, na, nr, st
+
+    def node_tableau(self):
+        """c, a, b~ and the interpolant's constants as the kernel holds them (node.TABLEAU's order)"""
+        out = np.empty(57, dtype=np.float64)
+        self._check(self.lib.si_node_tableau(_ptr(out)))
+        return out
 
     def logdensity(self, z):
         z = _f64(z)

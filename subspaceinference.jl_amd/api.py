@@ -93,10 +93,17 @@ def diffusion_subspace(model, cost, data, opt, T=10, c=1, M=3, print_freq=1, *, 
                              compute_dtype=compute_dtype)
 
 
+def _refuse_node_training(model):
+    if isinstance(model, flux.NeuralODE):
+        raise SubspaceError("training a NeuralODE through the solver is out of scope: pass W_swa, P to sub_inference, or push "
+                            "weight snapshots through the construction API (Context.construct_begin / construct_push / construct_finish)")
+
+
 def _swa_construction(model, cost, data, opt, T, c, print_freq, finish, *, device, ctx, max_cols, verbose, keep_on_device,
                       device_training, init, data_parallel, a_storage, compute_dtype):
     """What `subspace_construction` and `diffusion_subspace` share (reference :28-59 and :169-200, the same lines twice): training
     with the SWA update and the deviation columns on the device; `finish(ctx)` -> (W_swa, P) is what differs."""
+    _refuse_node_training(model)
     ps = flux.params(model)
     n_par = int(sum(p.size for p in ps))
     nb = len(data)
@@ -177,6 +184,11 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
                   device_loop=False, device_sampler=False, device_nuts=False):
     """src/space_inference.jl:82-164 for a Chain model and alg = :rwmh.
 
+    A `flux.NeuralODE` model (reference :96-101; docs/src/node_example.md) is accepted for alg = :rwmh / :mh: `data` holds the initial
+    states (d x f) and the observed trajectories (d*S x f), the density -sum_p ||sol_p - Y_p||^2 - ||W||^2 integrates every trajectory
+    with Tsit5 on the device (si_infer_setup_node; node.py is the definition), and `nchains`, `return_z` and the output map work as
+    for a Chain.  The gradient samplers raise: the gradient through the solver is not built.
+
     `density(z)` (:90-95: W_swa + P*z -> model_re -> forward over the FULL data -> Gaussian log-likelihood,
     prior term dead) and the RWMH loop (:111-116) run on the device; the output map (:125) materialises
     `W_swa + P*z` for every sample like the reference unless `return_z=True` (then chn is the M x itr matrix
@@ -229,28 +241,44 @@ def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg,
         raise SubspaceError("alg = :advi is available with device_loop=True and nchains = 1 only (si_fit_advi; DESIGN section 13)")
     if a not in _RWMH_ALGS and a not in ("mala", "hmc", "nuts", "advi"):
         raise SubspaceError("%s is not available" % a)  # reference :162
-    if not isinstance(in_model, flux.Chain):
+    is_node = isinstance(in_model, flux.NeuralODE)   # reference :96-101: the density integrates the model instead of evaluating it
+    if not is_node and not isinstance(in_model, flux.Chain):
         raise SubspaceError("Error: density function is not avaliable for this model")  # [sic] reference :103
     x, y, in_size = flux.data_matrices(data)  # split_data, src/libs.jl:75-77 (full data, not the batches)
-    table, n_par = flux.layer_table(in_model, in_size)
+    if is_node:
+        if a not in _RWMH_ALGS:
+            raise SubspaceError("alg = :%s needs the gradient of the density, and the gradient through the ODE solver is not built: "
+                                "a NeuralODE model is sampled with alg = :rwmh / :mh" % a)
+        if include_prior or compute_dtype != "f64":
+            raise SubspaceError("a NeuralODE's density carries -||W||^2 itself and is evaluated in Float64: include_prior and "
+                                "compute_dtype = \"f32\" are not available")
+        table, n_par = flux.layer_table(in_model.chain)
+    else:
+        table, n_par = flux.layer_table(in_model, in_size)
     if compute_dtype not in ("f64", "f32"):
         raise SubspaceError("compute_dtype must be \"f64\" (the reference's arithmetic) or \"f32\"")
     cdt = _capi.SI_F32 if compute_dtype == "f32" else _capi.SI_F64
     ctx, own = _get_ctx(ctx, device)
+    def setup(w_swa, p):
+        if is_node:   # σ_m and σ_p are accepted and unused, as in the reference (:96-101)
+            ctx.infer_setup_node(table, n_par, M, w_swa, p, x, y, in_model.saveat, **in_model.options())
+        else:
+            ctx.infer_setup(table, n_par, M, w_swa, p, x, y, σ_m, compute_dtype=cdt)
     try:
         if W_swa is None:
-            ctx.infer_setup(table, n_par, M, None, None, x, y, σ_m, compute_dtype=cdt)
+            setup(None, None)
         else:
             W_swa = np.asarray(W_swa, dtype=np.float64)
             P = np.asarray(P, dtype=np.float64)
             if P.shape[1] != M:
                 # reference: MvNormal(zeros(M), σ_z) proposal against an N x size(P,2) matrix -> DimensionMismatch in P*z
                 raise SubspaceError("DimensionMismatch: P has %d columns but M = %d" % (P.shape[1], M))
-            ctx.infer_setup(table, n_par, M, W_swa, P, x, y, σ_m, compute_dtype=cdt)
+            setup(W_swa, P)
         if decoder is not None:
             ctx.set_decoder(*decoder)
         # include_prior=True adds the term the reference leaves dead after its `return` (quirk Q4); default: as the reference
-        ctx.set_prior(σ_p if include_prior else 0.0)
+        if not is_node:
+            ctx.set_prior(σ_p if include_prior else 0.0)
         if device_sampler and a != "hmc":
             raise SubspaceError("device_sampler=True is available for alg = :hmc only" + (
                 " (alg = :%s runs on the device with device_loop=True)" % a if a in ("mala", "advi") else ""))
@@ -324,6 +352,7 @@ def subspace_inference(model, cost, data, opt, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr
                        compute_dtype="f64", device_loop=False, device_sampler=False, device_nuts=False):
     """src/space_inference.jl:33-54: construction, then sampling; returns (chn, lp, W_swa).
     W_swa and P stay on the device between the two stages (no host round trip)."""
+    _refuse_node_training(model)
     m = _alg_name(method)
     if m not in ("subspace", "diffusion"):
         raise SubspaceError("Error: No method found")  # reference :42
@@ -370,6 +399,7 @@ def auto_encoder_subspace(model, cost, data, opt, encoder, decoder, T=10, c=1, M
     include_penalty: the reference writes `+ sum(sqnorm, autops)` on a line of its own AFTER the loss (:130-131), so Julia parses
     it as a separate statement and the penalty is dead -- like the prior term (quirk Q4).  False (default):
     as the reference's code behaves; True adds the term it meant.  `seed` seeds the shuffle of the autoencoder's loader."""
+    _refuse_node_training(model)
     if not isinstance(encoder, flux.Chain) or not all(isinstance(l, flux.Dense) for l in encoder.layers):
         raise SubspaceError("Error: the encoder must be a Chain of Dense layers")
     dec_table, _ = _decoder_spec(decoder)
@@ -420,7 +450,7 @@ def auto_inference(m, data, decoder, W_swa, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
     RWMH loops and the fused stacked gradient are not taken (they form W_swa + P*z themselves): the launch-per-step loop and the
     per-point gradient path run instead.  The inference set-up is given a zero N x M matrix for P -- 8 N M idle bytes on the
     device, the price of sharing the set-up with `sub_inference`."""
-    if not isinstance(m, flux.Chain):
+    if not isinstance(m, (flux.Chain, flux.NeuralODE)):
         raise SubspaceError("Error: density function is not avaliable for this model")  # [sic] as sub_inference (:103)
     spec = _decoder_spec(decoder)
     n_par = int(sum(p.size for p in flux.params(m)))
@@ -443,6 +473,7 @@ def autoencoder_inference(model, cost, data, opt, encoder, decoder, σ_z=1.0, σ
                           ctx=None, seed=0, verbose=True, return_z=False, include_penalty=False, include_prior=False,
                           device_loop=False, device_sampler=False, device_nuts=False):
     """src/space_inference.jl:198-210: `auto_encoder_subspace`, then `auto_inference`, on one context -> (chn, lp)."""
+    _refuse_node_training(model)
     ctx, own = _get_ctx(ctx, device)
     try:
         w_swa, decoder = auto_encoder_subspace(model, cost, data, opt, encoder, decoder, T=T, c=c, M=M, print_freq=print_freq,

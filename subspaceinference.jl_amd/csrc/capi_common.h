@@ -70,6 +70,16 @@ int32_t form_weights(si_ctx* ctx, const double* z_dev, int32_t n, double* w, int
 void pull_back_to_z(si_ctx* ctx, const double* gw, double* gz);
 double mvnormal_c0(double d, double sigma);
 double prior_c0(const si_ctx* ctx);
+// the constants of lp = c0 - (sse / s2) / 2 [+ prior_c0 - (wsq / sp2) / 2] for the chain or NeuralODE set up
+double lik_c0(const si_ctx* ctx, double d);
+double lik_s2(const si_ctx* ctx);
+double prior_sp2(const si_ctx* ctx);
+// capi_node.hip: the NeuralODE route behind eval_density and si_predict (node.on), and the part of its set-up that
+// infer_setup_common carries (capi_infer.hip)
+int32_t node_density(si_ctx* ctx, const si::DensityView& v, int c0, int nc, const double** yhat_out);
+int32_t node_predict(si_ctx* ctx, const double* Z, int32_t C, const double* U0new, int64_t Bn, double* U_out);
+int32_t infer_setup_node_base(si_ctx* ctx, const si_layer* layers, int32_t L, int64_t N, int32_t M, const double* W_swa, const double* P,
+                              const double* U0, const double* Y, int32_t d, int32_t S, int64_t f);
 void fused_fill_program(const si_ctx* ctx, si::ChainFusedPlan& fp);
 int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok);   // the gradient entry points' state rules and error texts
 }

@@ -67,14 +67,15 @@ static bool alloc_forward(si_ctx* ctx, int slots) {
   for (DevBuf<float>* b : {&ctx->d_w32, &ctx->d_act32[0], &ctx->d_act32[1]}) b->reset();
   ctx->fw_slots = 0;
   const size_t S = (size_t)slots, dB = (size_t)ctx->out_dim * (size_t)ctx->B;
+  const bool node = ctx->node.d > 0;   // a NeuralODE set-up: its layers run inside the integration kernel, which keeps its own per-trajectory sums
   // SI_F32: fp32 weights + fp32 ping-pong activations INSTEAD of the fp64 activations (the fp64 weights stay: K4 writes
   // both, the output map / prior / gradient read them); the head partials serve both paths (the larger slot count)
   const size_t pslots = (size_t)std::max(ctx->fuse_slots, ctx->fuse_slots32);
   if (!ctx->d_w.alloc(S * (size_t)pad_ld(ctx->iN)) ||
-      (!ctx->f32 && (!ctx->d_act[0].alloc(S * (size_t)ctx->act_elems) || !ctx->d_act[1].alloc(S * (size_t)ctx->act_elems))) ||
+      (!ctx->f32 && !node && (!ctx->d_act[0].alloc(S * (size_t)ctx->act_elems) || !ctx->d_act[1].alloc(S * (size_t)ctx->act_elems))) ||
       (ctx->f32 && (!ctx->d_w32.alloc(S * (size_t)pad_ld(ctx->iN)) || !ctx->d_act32[0].alloc(S * (size_t)ctx->act_elems) ||
                     !ctx->d_act32[1].alloc(S * (size_t)ctx->act_elems))) ||
-      !ctx->d_ssepart.alloc(S * (size_t)ctx->sse_blocks) ||
+      (!node && !ctx->d_ssepart.alloc(S * (size_t)ctx->sse_blocks)) ||
       (ctx->fuse_tail && !ctx->d_part.alloc(S * pslots * dB)) ||
       ((ctx->fuse_tail || ctx->f32 || ctx->fused_ok) && !ctx->d_yhat.alloc(S * dB)))
     return false;
@@ -90,20 +91,22 @@ enum SetupSrc { SRC_HOST = 0, SRC_DEV_COPY = 1, SRC_DEV_BORROW = 2 };
 
 static int32_t infer_setup_common(si_ctx* ctx, const si_layer* layers, int32_t L, int64_t N, int32_t M, const double* W_swa,
                                   const double* P, int64_t ldP_in, const double* X, const double* Y, int32_t in_dim,
-                                  int32_t out_dim, int64_t B, double sigma_m, int32_t compute_dtype, SetupSrc src) {
+                                  int32_t out_dim, int64_t B, double sigma_m, int32_t compute_dtype, SetupSrc src, int32_t node_d = 0) {
   CHECK_CTX(ctx);
+  const std::string who = node_d > 0 ? "si_infer_setup_node" : "si_infer_setup";   // (the entry point the caller used, for the messages)
   if (!layers || L <= 0 || N <= 0 || M <= 0 || !X || !Y || in_dim <= 0 || out_dim <= 0 || B <= 0)
-    return fail(ctx, SI_ERR_INVALID, "si_infer_setup: bad argument");
-  if (!(sigma_m > 0.0)) return fail(ctx, SI_ERR_INVALID, "si_infer_setup: sigma_m must be positive");
+    return fail(ctx, SI_ERR_INVALID, who + ": bad argument");
+  if (!(sigma_m > 0.0)) return fail(ctx, SI_ERR_INVALID, who + ": sigma_m must be positive");
   if (compute_dtype != SI_F64 && compute_dtype != SI_F32)
-    return fail(ctx, SI_ERR_INVALID, "si_infer_setup: compute_dtype must be SI_F64 (the reference's arithmetic) or SI_F32");
+    return fail(ctx, SI_ERR_INVALID, who + ": compute_dtype must be SI_F64 (the reference's arithmetic) or SI_F32");
   if ((W_swa == nullptr) != (P == nullptr))
-    return fail(ctx, SI_ERR_INVALID, "si_infer_setup: W_swa and P must both be given or both be NULL");
+    return fail(ctx, SI_ERR_INVALID, who + ": W_swa and P must both be given or both be NULL");
   // the Chain: Dense / Conv / MaxPool / flatten layers (anything else: the reference's "model_re function is not
   // available for this model", libs.jl:59)
   NetPlan plan;
   {
-    const int32_t prc = net_plan(ctx, "si_infer_setup", layers, L, N, in_dim, out_dim, plan);
+    // (node_d: a NeuralODE's right-hand side d -> ... -> d; its out_dim is the d*S rows of the observed trajectories)
+    const int32_t prc = net_plan(ctx, who.c_str(), layers, L, N, in_dim, node_d > 0 ? node_d : out_dim, plan);
     if (prc != SI_OK) return prc;
   }
   int main_layer = 0;
@@ -121,9 +124,9 @@ static int32_t infer_setup_common(si_ctx* ctx, const si_layer* layers, int32_t L
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   free_infer(ctx);
   if (!W_swa) {
-    if (!ctx->c_finished) return fail(ctx, SI_ERR_STATE, "si_infer_setup: no finished construction to take W_swa / P from");
+    if (!ctx->c_finished) return fail(ctx, SI_ERR_STATE, who + ": no finished construction to take W_swa / P from");
     if (ctx->N != N || ctx->M_built != M)
-      return fail(ctx, SI_ERR_INVALID, "si_infer_setup: N / M differ from the finished construction");
+      return fail(ctx, SI_ERR_INVALID, who + ": N / M differ from the finished construction");
     ctx->i_swa = ctx->d_swa;
     ctx->i_P = ctx->d_P;
     ctx->ldP = ctx->ldA;
@@ -138,7 +141,7 @@ static int32_t infer_setup_common(si_ctx* ctx, const si_layer* layers, int32_t L
       ctx->ldP = pad_ld(N);
       if (!ctx->d_iswa.alloc((size_t)ctx->ldP) || !ctx->d_iP.alloc((size_t)ctx->ldP * M)) {
         free_infer(ctx);
-        return fail(ctx, SI_ERR_NOMEM, "si_infer_setup: allocation of W_swa / P failed");
+        return fail(ctx, SI_ERR_NOMEM, who + ": allocation of W_swa / P failed");
       }
       SI_HIP(ctx, hipMemsetAsync(ctx->d_iswa, 0, (size_t)ctx->ldP * sizeof(double), ctx->stream));
       SI_HIP(ctx, hipMemsetAsync(ctx->d_iP, 0, (size_t)ctx->ldP * M * sizeof(double), ctx->stream));
@@ -149,6 +152,7 @@ static int32_t infer_setup_common(si_ctx* ctx, const si_layer* layers, int32_t L
       ctx->i_P = ctx->d_iP;
     }
   }
+  ctx->node.d = node_d;   // (> 0 from here on: alloc_forward leaves the Chain kernels' activation and SSE-partial buffers out)
   ctx->layers.assign(layers, layers + L);
   ctx->iN = N;
   ctx->iM = M;
@@ -161,6 +165,7 @@ static int32_t infer_setup_common(si_ctx* ctx, const si_layer* layers, int32_t L
   ctx->plan = plan;
   ctx->fuse_tail = !plan.has_conv && (L >= 2) && layers[L - 1].out <= SI_FUSE_MAX_OUT &&
                    layers[L - 1].act < SI_ACT_LEAKYRELU && layers[L - 2].act < SI_ACT_LEAKYRELU;   // (kernels_gemm.h)
+  if (node_d > 0) ctx->fuse_tail = false;   // (a NeuralODE's layers are evaluated inside the integration kernel alone)
   ctx->fuse_slots = ctx->fuse_tail ? dense_fused_slots(layers[L - 2].out) : 0;
   ctx->f32 = compute_dtype == SI_F32;
   // (the fp32 weight vector is 256-byte aligned and its slots are pad_ld(N) apart: a layer's W is 16-byte aligned iff w_off % 4 == 0)
@@ -170,13 +175,13 @@ static int32_t infer_setup_common(si_ctx* ctx, const si_layer* layers, int32_t L
   ctx->max_stored = maxstored;
   ctx->act_elems = pad_ld(maxstored * B);
   ctx->sse_blocks = sse_num_blocks((int64_t)out_dim * B, ctx->num_cu);
-  ctx->fused_ok = fused_chain_class(ctx);
+  ctx->fused_ok = node_d == 0 && fused_chain_class(ctx);   // (the chain kernels evaluate a Chain: never for a NeuralODE's right-hand side)
   if (ctx->fused_ok) {   // the chain's tile program (64 bytes per 16-feature tile), uploaded once
     std::vector<CgTileD> prog;
     chain_fused_program(ctx->layers.data(), L, ctx->fuse_tail, prog, ctx->cg_start, ctx->cg_count, ctx->cg_chunks);
     if (!ctx->d_cgprog.alloc(prog.size())) {
       free_infer(ctx);
-      return fail(ctx, SI_ERR_NOMEM, "si_infer_setup: device allocation failed");
+      return fail(ctx, SI_ERR_NOMEM, who + ": device allocation failed");
     }
     SI_HIP(ctx, hipMemcpy(ctx->d_cgprog, prog.data(), prog.size() * sizeof(CgTileD), hipMemcpyHostToDevice));
   }
@@ -187,7 +192,7 @@ static int32_t infer_setup_common(si_ctx* ctx, const si_layer* layers, int32_t L
       (plan.has_conv && !ctx->d_wpack.alloc(plan.wpack_elems)) ||
       (plan.input_spatial && !ctx->d_Xc.alloc((size_t)plan.in_elems * B))) {
     free_infer(ctx);
-    return fail(ctx, SI_ERR_NOMEM, "si_infer_setup: device allocation failed");
+    return fail(ctx, SI_ERR_NOMEM, who + ": device allocation failed");
   }
   {
     const hipMemcpyKind kind = src == SRC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
@@ -209,6 +214,13 @@ int32_t si_infer_setup(si_ctx* ctx, const si_layer* layers, int32_t L, int64_t N
                        const double* P, const double* X, const double* Y, int32_t in_dim, int32_t out_dim,
                        int64_t B, double sigma_m, int32_t compute_dtype) {
   return infer_setup_common(ctx, layers, L, N, M, W_swa, P, N, X, Y, in_dim, out_dim, B, sigma_m, compute_dtype, SRC_HOST);
+}
+
+// si_infer_setup_node's share of the set-up (capi_node.hip): W_swa / P, the layer table, X = the initial states, Y = the observed
+// trajectories, the forward workspace -- everything but the Chain kernels' plans
+int32_t infer_setup_node_base(si_ctx* ctx, const si_layer* layers, int32_t L, int64_t N, int32_t M, const double* W_swa, const double* P,
+                              const double* U0, const double* Y, int32_t d, int32_t S, int64_t f) {
+  return infer_setup_common(ctx, layers, L, N, M, W_swa, P, N, U0, Y, d, d * S, f, 1.0, SI_F64, SRC_HOST, d);
 }
 
 int32_t si_infer_setup_dev(si_ctx* ctx, const si_layer* layers, int32_t L, int64_t N, int32_t M, const double* W_swa_dev,
@@ -449,6 +461,7 @@ static int32_t density_layers(si_ctx* ctx, const DensityView& v, int c0, int nc,
 // tail, at + j * act_elems otherwise)
 int32_t eval_density(si_ctx* ctx, const DensityView& v, int c0, int nc, const double** yhat_out) {
   ctx->last_density_spec = 0;   // (si_chain_kernel_info reports the last evaluation)
+  if (ctx->node.on) return node_density(ctx, v, c0, nc, yhat_out);   // form_weights, ||W||^2, the integrations (capi_node.hip)
   const int64_t N = ctx->iN, ldw = pad_ld(N);
   const int32_t M = ctx->iM;
   const double dn = (double)nc;
@@ -485,19 +498,26 @@ double mvnormal_c0(double d, double sigma) {
 }
 
 // log N(w; 0, sigma_p^2 I) = c0p - ||w||^2 / (2 sigma_p^2): the term the reference writes AFTER its `return` (Q4)
-double prior_c0(const si_ctx* ctx) { return ctx->sigma_p > 0.0 ? mvnormal_c0((double)ctx->iN, ctx->sigma_p) : 0.0; }
+double prior_c0(const si_ctx* ctx) { return ctx->sigma_p > 0.0 && !ctx->node.on ? mvnormal_c0((double)ctx->iN, ctx->sigma_p) : 0.0; }
+// The constants of lp = c0 - (sse / s2) / 2 [+ prior_c0 - (wsq / sp2) / 2].  A NeuralODE set-up (reference
+// src/space_inference.jl:96-101: lp = -sse - ||W||^2, sigma_m and sigma_p unused) is c0 = 0, s2 = 1/2, the prior term on (the set-up
+// holds sigma_p at 1), prior_c0 = 0, sp2 = 1/2: every division is exact, so the RWMH kernels carry it with these constants alone.
+double lik_c0(const si_ctx* ctx, double d) { return ctx->node.on ? 0.0 : mvnormal_c0(d, ctx->sigma_m); }
+double lik_s2(const si_ctx* ctx) { return ctx->node.on ? 0.5 : ctx->sigma_m * ctx->sigma_m; }
+double prior_sp2(const si_ctx* ctx) { return ctx->node.on ? 0.5 : ctx->sigma_p * ctx->sigma_p; }
 
 // the value of the log-density from the device's sums, as the host forms it: lp = c0 - (sse / s2) / 2 [+ prior_c0 - (wsq / sp2) / 2]
 static double lp_from_sums(const si_ctx* ctx, double sse, double wsq) {
-  const double c0 = mvnormal_c0((double)ctx->out_dim * (double)ctx->B, ctx->sigma_m), s2 = ctx->sigma_m * ctx->sigma_m;
+  const double c0 = lik_c0(ctx, (double)ctx->out_dim * (double)ctx->B), s2 = lik_s2(ctx);
   double lp = c0 - (sse / s2) / 2.0;
-  if (ctx->sigma_p > 0.0) lp += prior_c0(ctx) - (wsq / (ctx->sigma_p * ctx->sigma_p)) / 2.0;
+  if (ctx->sigma_p > 0.0) lp += prior_c0(ctx) - (wsq / prior_sp2(ctx)) / 2.0;
   return lp;
 }
 
 int32_t si_infer_set_prior(si_ctx* ctx, double sigma_p) {
   CHECK_CTX(ctx);
   if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_infer_set_prior: call si_infer_setup first");
+  if (ctx->node.on) return fail(ctx, SI_ERR_INVALID, "si_infer_set_prior: not available for NeuralODE models (their density carries -||W||^2 itself)");
   if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_infer_set_prior: a step-wise RWMH session is open");
   if (!(sigma_p >= 0.0)) return fail(ctx, SI_ERR_INVALID, "si_infer_set_prior: sigma_p must be >= 0 (0 = off, the reference's behaviour)");
   ctx->sigma_p = sigma_p;
@@ -739,6 +759,7 @@ static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_ou
 // the state rules and error texts shared by the two gradient entry points
 int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok) {
   if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_infer_setup first");
+  if (ctx->node.on) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": not available for NeuralODE models (the gradient through the solver is not built)");
   if (!args_ok) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": bad argument");
   if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, std::string(who) + ": a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
   return SI_OK;
@@ -965,6 +986,7 @@ int32_t si_predict(si_ctx* ctx, const double* Z, int32_t C, const double* Xnew, 
   BIND(ctx);
   int32_t rc = ensure_chains(ctx, C);
   if (rc != SI_OK) return rc;
+  if (ctx->node.on) return node_predict(ctx, Z, C, Xnew, Bn, Yhat_out);   // new initial states d x Bn (capi_node.hip)
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // run the ordinary forward path on temporary data buffers sized for Bn, through a view of its own: the context is only read;
   // like the density, up to `wb` samples share one pass of launches (grid.y), within the same workspace cap

@@ -1,0 +1,208 @@
+// C ABI, NeuralODE models (reference src/space_inference.jl:96-101; model_re at src/libs.jl:36-54): si_infer_setup_node,
+// si_node_solve, si_node_tableau, si_node_info, and the two routes eval_density and si_predict hand over while a node set-up is
+// active.  Host-side orchestration only: the integrations run in kernels_node.hip, W_swa + P z (or the decoder) in form_weights,
+// ||W||^2 in launch_sse as the prior term does.  No CPU fallback anywhere in this file.
+#include "capi_common.h"
+#include "node_tableau.h"
+
+using namespace si;
+
+namespace {
+
+// the kernel's arguments for `nc` chain slots whose weights lie in w: the set-up's constants plus this pass's data and outputs
+NodeArgs node_args(const si_ctx* ctx, const double* w, const double* U0, const double* Y, int64_t f, double* sse_p, double* U_out,
+                   int32_t* nacc, int32_t* nrej, int32_t* status) {
+  NodeArgs a = ctx->node.args;
+  a.w = w, a.ldw = pad_ld(ctx->iN);
+  a.U0 = U0, a.Y = Y, a.f = f;
+  a.ts = ctx->node.ts;
+  a.sse_p = sse_p, a.U_out = U_out, a.nacc = nacc, a.nrej = nrej, a.status = status;
+  return a;
+}
+
+// the per-trajectory sums (and, on request, the saved states) of one pass of launches; nothing is queued on a buffer that goes
+int32_t node_reserve(si_ctx* ctx, size_t ssep, size_t uout) {
+  NodeState& n = ctx->node;
+  if (n.ssep.size() >= ssep && (uout == 0 || n.uout.size() >= uout)) return SI_OK;
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (!n.ssep.reserve(ssep) || (uout != 0 && !n.uout.reserve(uout))) return fail(ctx, SI_ERR_NOMEM, "NeuralODE density: workspace allocation failed");
+  return SI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t node_density(si_ctx* ctx, const DensityView& v, int c0, int nc, const double** yhat_out) {
+  const int64_t N = ctx->iN, ldw = pad_ld(N), f = v.B;
+  const int32_t M = ctx->iM;
+  const size_t traj = (size_t)ctx->node.d * (size_t)ctx->node.S * (size_t)f;
+  int32_t rc = node_reserve(ctx, (size_t)f * (size_t)nc, yhat_out ? traj * (size_t)nc : 0);
+  if (rc != SI_OK) return rc;
+  {
+    ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * nc, (double)N * (M + 1 + nc) * 8.0);
+    if ((rc = form_weights(ctx, ctx->d_zprop + (size_t)c0 * M, nc, ctx->d_w, ldw)) != SI_OK) return rc;
+  }
+  launch_sse(ctx->stream, ctx->d_w, nullptr, N, ctx->d_wsqpart, ctx->wsq_blocks, ctx->d_wsq + c0, nc, ldw);   // ||W||^2 per chain
+  {
+    ProfScope ps(ctx, SI_K_DENSE, 0.0, 0.0);
+    const NodeArgs a = node_args(ctx, ctx->d_w, v.X, v.Y, f, ctx->node.ssep, yhat_out ? ctx->node.uout.get() : nullptr, nullptr, nullptr, nullptr);
+    SI_HIP(ctx, launch_node_solve(ctx->stream, a, nc));
+    launch_node_sum(ctx->stream, ctx->node.ssep, f, ctx->d_sse + c0, nc);
+  }
+  SI_HIP(ctx, hipGetLastError());
+  if (yhat_out) *yhat_out = ctx->node.uout;
+  return SI_OK;
+}
+
+int32_t si_infer_setup_node(si_ctx* ctx, const si_layer* layers, int32_t L, int64_t N, int32_t M, const double* W_swa, const double* P,
+                            const double* U0, const double* Y, int32_t d, int32_t S, int64_t f, const double* ts, const void* opts_in) {
+  CHECK_CTX(ctx);
+  const si_node_opts* opts = static_cast<const si_node_opts*>(opts_in);
+  auto bad = [&](const char* what) { return fail(ctx, SI_ERR_INVALID, std::string("si_infer_setup_node: ") + what); };
+  if (!layers || !U0 || !Y || !ts || !opts || M <= 0 || f <= 0) return bad("bad argument");
+  if (L < 1 || L > SI_NODE_MAX_LAYERS) return bad("a NeuralODE right-hand side has 1 to 8 Dense layers");
+  if (d < 1 || d > SI_NODE_MAX_D) return bad("the state dimension d must be 1 to 8");
+  if (N < 1 || N > SI_NODE_MAX_N) return bad("N must be 1 to 8192");
+  if (S < 1 || S > SI_NODE_MAX_S) return bad("the number of save times S must be 1 to 4096");
+  // (the per-chain sum walks its f per-trajectory values in the reference's order, one thread per chain: 2^20 is a millisecond of it)
+  if (f > ((int64_t)1 << 20)) return bad("f must be at most 2^20 trajectories");
+  NodeArgs a;
+  int32_t prev = d, widest = 1;
+  for (int32_t l = 0; l < L; ++l) {
+    const si_layer& ly = layers[l];
+    if (ly.kind != SI_LAYER_DENSE) return bad("every layer of the right-hand side must be SI_LAYER_DENSE");
+    if (ly.act < 0 || ly.act >= SI_ACT_COUNT) return bad("unknown activation");
+    if (ly.in != prev) return bad("consecutive layer widths do not chain from d");
+    if (ly.out < 1 || ly.out > SI_NODE_MAX_WIDTH) return bad("layer widths must be 1 to 256");
+    const int64_t wn = (int64_t)ly.in * ly.out;
+    if (ly.w_off < 0 || ly.w_off > N - wn || ly.b_off < 0 || ly.b_off > N - ly.out) return bad("a layer's offset range falls outside [0, N)");
+    a.lay.in[l] = ly.in, a.lay.out[l] = ly.out, a.lay.act[l] = ly.act, a.lay.w_off[l] = (int32_t)ly.w_off, a.lay.b_off[l] = (int32_t)ly.b_off;
+    prev = ly.out;
+    widest = std::max(widest, ly.out);
+  }
+  if (prev != d) return bad("the right-hand side must map d to d");
+  a.lay.n = L;
+  if (!std::isfinite(opts->t0)) return bad("t0 must be finite");
+  for (int32_t s = 0; s < S; ++s)
+    if (!std::isfinite(ts[s]) || (s == 0 ? ts[0] < opts->t0 : !(ts[s] > ts[s - 1])))
+      return bad("the save times must be finite, strictly ascending and not before t0");
+  if (opts->pre_power != 1 && opts->pre_power != 3) return bad("pre_power must be 1 or 3");
+  if (opts->max_steps < 0 || opts->max_steps > SI_NODE_MAX_STEPS) return bad("max_steps must be 1 to 1000000 (0: 100000)");
+  if (opts->adaptive != 0 && opts->adaptive != 1) return bad("adaptive must be 0 or 1");
+  if (opts->adaptive) {
+    if (!(std::isfinite(opts->reltol) && opts->reltol > 0.0 && std::isfinite(opts->abstol) && opts->abstol > 0.0))
+      return bad("reltol and abstol must be finite and positive in adaptive mode");
+    if (!(std::isfinite(opts->dt) && opts->dt >= 0.0)) return bad("dt must be finite and >= 0 (0: the starting-step rule)");
+  } else if (!(std::isfinite(opts->dt) && opts->dt > 0.0)) {
+    return bad("dt must be finite and positive in fixed-step mode");
+  }
+  // G lanes per trajectory: the smallest power of two >= the widest layer, capped at 64 (a group never crosses a wave)
+  a.G = 1, a.lgG = 0;
+  while (a.G < widest && a.G < 64) a.G *= 2, a.lgG += 1;
+  a.maxw = widest, a.d = d, a.S = S, a.N = (int32_t)N;
+  a.t0 = opts->t0, a.reltol = opts->reltol, a.abstol = opts->abstol, a.dt = opts->dt;
+  a.adaptive = opts->adaptive, a.max_steps = opts->max_steps == 0 ? 100000 : opts->max_steps, a.pre_power = opts->pre_power;
+  int32_t rc = infer_setup_node_base(ctx, layers, L, N, M, W_swa, P, U0, Y, d, S, f);
+  if (rc != SI_OK) return rc;
+  NodeState& n = ctx->node;
+  if (!n.ts.alloc((size_t)S) || hipMemcpy(n.ts, ts, (size_t)S * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+    free_infer(ctx);
+    return fail(ctx, SI_ERR_NOMEM, "si_infer_setup_node: device allocation / upload failed");
+  }
+  n.args = a, n.d = d, n.S = S;
+  ctx->sigma_p = 1.0;   // "the prior term on": its constants are lik_c0 / lik_s2 / prior_c0 / prior_sp2 (capi_infer.hip)
+  n.on = true;
+  return SI_OK;
+}
+
+int32_t si_node_solve(si_ctx* ctx, const double* Z, int32_t C, double* U_out, double* sse_out, int32_t* naccept_out,
+                      int32_t* nreject_out, int32_t* status_out) {
+  CHECK_CTX(ctx);
+  if (!ctx->i_ready || !ctx->node.on) return fail(ctx, SI_ERR_STATE, "si_node_solve: call si_infer_setup_node first");
+  if (!Z || C <= 0) return fail(ctx, SI_ERR_INVALID, "si_node_solve: bad argument");
+  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_node_solve: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
+  BIND(ctx);
+  int32_t rc = ensure_chains(ctx, C);
+  if (rc != SI_OK) return rc;
+  const int64_t N = ctx->iN, ldw = pad_ld(N), f = ctx->B;
+  const int32_t M = ctx->iM;
+  const size_t traj = (size_t)ctx->node.d * (size_t)ctx->node.S * (size_t)f;
+  // an audit read-back, not a hot path: fw_slots chains per pass (at most 256 MB of saved states), one synchronisation per pass
+  int wb = std::max(1, std::min<int>(ctx->fw_slots, C));
+  if (U_out) wb = (int)std::max<size_t>(1, std::min<size_t>((size_t)wb, ((size_t)32 << 20) / traj));
+  DevBuf<double> dU, dS;
+  DevBuf<int32_t> dI;
+  if ((U_out && !dU.alloc(traj * (size_t)wb)) || !dS.alloc((size_t)f * wb) || !dI.alloc((size_t)3 * (size_t)f * wb))
+    return fail(ctx, SI_ERR_NOMEM, "si_node_solve: device allocation failed");
+  SI_HIP(ctx, hipMemcpyAsync(ctx->d_zprop, Z, (size_t)M * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const size_t fw = (size_t)f * (size_t)wb;
+  for (int c0 = 0; c0 < C; c0 += wb) {
+    const int nc = std::min(wb, C - c0);
+    const size_t fn = (size_t)f * (size_t)nc;
+    if ((rc = form_weights(ctx, ctx->d_zprop + (size_t)c0 * M, nc, ctx->d_w, ldw)) != SI_OK) return rc;
+    const NodeArgs a = node_args(ctx, ctx->d_w, ctx->d_X, ctx->d_Y, f, dS, U_out ? dU.get() : nullptr, dI, dI + fw, dI + 2 * fw);
+    SI_HIP(ctx, launch_node_solve(ctx->stream, a, nc));
+    if (U_out) SI_HIP(ctx, hipMemcpyAsync(U_out + traj * (size_t)c0, dU, traj * (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (sse_out) SI_HIP(ctx, hipMemcpyAsync(sse_out + (size_t)f * c0, dS, fn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (naccept_out) SI_HIP(ctx, hipMemcpyAsync(naccept_out + (size_t)f * c0, dI, fn * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (nreject_out) SI_HIP(ctx, hipMemcpyAsync(nreject_out + (size_t)f * c0, dI + fw, fn * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (status_out) SI_HIP(ctx, hipMemcpyAsync(status_out + (size_t)f * c0, dI + 2 * fw, fn * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return SI_OK;
+}
+
+// si_predict in a node set-up: the saved states from new initial conditions U0new (d x Bn) at Z[:, c], d*S x Bn x C
+int32_t node_predict(si_ctx* ctx, const double* Z, int32_t C, const double* U0new, int64_t Bn, double* U_out) {
+  const int64_t N = ctx->iN, ldw = pad_ld(N);
+  const int32_t M = ctx->iM, d = ctx->node.d;
+  const size_t traj = (size_t)d * (size_t)ctx->node.S * (size_t)Bn;
+  const int wb = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min<int>(ctx->fw_slots, C), ((size_t)32 << 20) / traj));
+  DevBuf<double> dX, dU, dS;
+  if (!dX.alloc((size_t)d * (size_t)Bn) || !dU.alloc(traj * (size_t)wb) || !dS.alloc((size_t)Bn * wb))
+    return fail(ctx, SI_ERR_NOMEM, "si_predict: device allocation failed");
+  SI_HIP(ctx, hipMemcpyAsync(dX, U0new, (size_t)d * (size_t)Bn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(ctx->d_zprop, Z, (size_t)M * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  for (int c0 = 0; c0 < C; c0 += wb) {
+    const int nc = std::min(wb, C - c0);
+    const int32_t rc = form_weights(ctx, ctx->d_zprop + (size_t)c0 * M, nc, ctx->d_w, ldw);
+    if (rc != SI_OK) return rc;
+    const NodeArgs a = node_args(ctx, ctx->d_w, dX, nullptr, Bn, dS, dU, nullptr, nullptr, nullptr);
+    SI_HIP(ctx, launch_node_solve(ctx->stream, a, nc));
+    SI_HIP(ctx, hipMemcpyAsync(U_out + traj * (size_t)c0, dU, traj * (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return SI_OK;
+}
+
+int32_t si_node_tableau(double* out) {
+  if (!out) return SI_ERR_INVALID;
+  int n = 0;
+  for (double v : NODE_C) out[n++] = v;
+  for (int i = 1; i < 7; ++i)
+    for (int j = 0; j < i; ++j) out[n++] = NODE_A[i][j];
+  for (double v : NODE_BT) out[n++] = v;
+  for (double v : NODE_B1) out[n++] = v;
+  for (double v : NODE_B2) out[n++] = v;
+  for (double v : NODE_B3) out[n++] = v;
+  for (double v : NODE_B4) out[n++] = v;
+  for (double v : NODE_B5) out[n++] = v;
+  for (double v : NODE_B6) out[n++] = v;
+  for (double v : NODE_B7) out[n++] = v;
+  static_assert(7 + 21 + 7 + 4 + 6 * 3 == NODE_TABLEAU_LEN, "si_node_tableau's length");
+  return SI_OK;
+}
+
+int32_t si_node_info(si_ctx* ctx, int32_t* active_out, int32_t* d_out, int32_t* S_out, int64_t* f_out, int32_t* G_out) {
+  CHECK_CTX(ctx);
+  const bool on = ctx->i_ready && ctx->node.on;
+  if (active_out) *active_out = on ? 1 : 0;
+  if (d_out) *d_out = on ? ctx->node.d : 0;
+  if (S_out) *S_out = on ? ctx->node.S : 0;
+  if (f_out) *f_out = on ? ctx->B : 0;
+  if (G_out) *G_out = on ? ctx->node.args.G : 0;
+  return SI_OK;
+}
+
+}  // extern "C"

@@ -358,7 +358,7 @@ static int32_t rwmh_per_step(si_ctx* ctx, const RwmhCall& k) {
       else
         launch_rwmh_accept(ctx->stream, ctx->d_zcur, ctx->d_zprop, ctx->d_lpcur, ctx->d_sse, ctx->d_nacc, M, C, k.c0, k.s2, k.seed,
                            k.chain_id0, ctx->d_steps, dZ, dlp, k.itr, ctx->sigma_p > 0.0 ? ctx->d_wsq.get() : nullptr, prior_c0(ctx),
-                           ctx->sigma_p * ctx->sigma_p, accflag);
+                           prior_sp2(ctx), accflag);
     }
     if (k.W_out) e = ring.push(t);
   }
@@ -393,8 +393,8 @@ static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, doubl
     return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
   const double d = (double)ctx->out_dim * (double)ctx->B;
   const size_t wall_elems = (size_t)pad_ld(ctx->iN) * (size_t)itr * (size_t)C;
-  const RwmhCall k{who, itr, sigma_z, seed, chain_id0, C, Z_out, lp_out, accept_rate_out, W_out, mvnormal_c0(d, ctx->sigma_m),
-                   ctx->sigma_m * ctx->sigma_m, wall_elems, !W_out || wall_elems <= ((size_t)512 << 20) / sizeof(double)};
+  const RwmhCall k{who, itr, sigma_z, seed, chain_id0, C, Z_out, lp_out, accept_rate_out, W_out, lik_c0(ctx, d),
+                   lik_s2(ctx), wall_elems, !W_out || wall_elems <= ((size_t)512 << 20) / sizeof(double)};
   if ((rc = rwmh_one_workgroup(ctx, k)) != SI_NOT_TAKEN) return rc;
   if ((rc = rwmh_grid(ctx, k)) != SI_NOT_TAKEN) return rc;
   return rwmh_per_step(ctx, k);
@@ -441,6 +441,7 @@ int32_t si_rwmh_begin(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, i
   if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_rwmh_begin: call si_infer_setup first");
   if (itr <= 0 || nchains <= 0 || chain_id0 < 0 || !(sigma_z > 0.0) || d_total < 0)
     return fail(ctx, SI_ERR_INVALID, "si_rwmh_begin: itr, nchains, sigma_z must be positive");
+  if (ctx->node.on && d_total > 0) return fail(ctx, SI_ERR_INVALID, "si_rwmh_begin: a data-sharded density (d_total > 0) is not available for NeuralODE models");
   BIND(ctx);
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   int32_t rc = ensure_chains(ctx, nchains);
@@ -490,10 +491,10 @@ int32_t si_rwmh_step_accept(si_ctx* ctx, const double* sse_total) {
     SI_HIP(ctx, hipMemcpyAsync(ctx->d_sse, sse_total, (size_t)C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // sse_total is caller-owned
   }
-  const double c0 = mvnormal_c0(ctx->sw_d, ctx->sigma_m), s2 = ctx->sigma_m * ctx->sigma_m;
+  const double c0 = lik_c0(ctx, ctx->sw_d), s2 = lik_s2(ctx);
   launch_rwmh_accept(ctx->stream, ctx->d_zcur, ctx->d_zprop, ctx->d_lpcur, ctx->d_sse, ctx->d_nacc, ctx->iM, C, c0, s2,
                      ctx->sw_seed, ctx->sw_chain0, ctx->d_steps, ctx->sw_Z, ctx->sw_lp, ctx->sw_itr,
-                     ctx->sigma_p > 0.0 ? ctx->d_wsq : nullptr, prior_c0(ctx), ctx->sigma_p * ctx->sigma_p);
+                     ctx->sigma_p > 0.0 ? ctx->d_wsq : nullptr, prior_c0(ctx), prior_sp2(ctx));
   SI_HIP(ctx, hipGetLastError());
   ctx->sw_next += 1;
   ctx->sw_evaluated = false;

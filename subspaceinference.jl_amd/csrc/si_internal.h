@@ -299,9 +299,46 @@ struct DecoderState {
   DevBuf<double> part, ga;       // the last layer's reverse: block partials (blocks x H), d lp / d a_{D-1} (H)
 };
 
+// The NeuralODE route (si_infer_setup_node; reference src/space_inference.jl:96-101): the set-up's layers are the right-hand
+// side d -> ... -> d, d_X holds the initial states (d x f), d_Y the observed trajectories (d*S x f).  The kernel's arguments
+// (kernels_node.hip), by value:
+constexpr int SI_NODE_MAX_LAYERS = 8, SI_NODE_MAX_D = 8, SI_NODE_MAX_WIDTH = 256, SI_NODE_MAX_S = 4096, SI_NODE_MAX_STEPS = 1000000;
+constexpr int64_t SI_NODE_MAX_N = 8192;
+struct NodeLayers {
+  int32_t n = 0;
+  int32_t in[SI_NODE_MAX_LAYERS] = {0}, out[SI_NODE_MAX_LAYERS] = {0}, act[SI_NODE_MAX_LAYERS] = {0};
+  int32_t w_off[SI_NODE_MAX_LAYERS] = {0}, b_off[SI_NODE_MAX_LAYERS] = {0};
+};
+struct NodeArgs {
+  NodeLayers lay;
+  const double* w = nullptr;       // chain slot c: w + c * ldw
+  int64_t ldw = 0;
+  const double* U0 = nullptr;      // d x f
+  const double* Y = nullptr;       // d*S x f, or null (no squared errors: sse_p = 0 for a finished trajectory)
+  const double* ts = nullptr;      // S
+  double* sse_p = nullptr;         // f x nchains
+  double* U_out = nullptr;         // d*S x f x nchains in Y's layout, or null
+  int32_t *nacc = nullptr, *nrej = nullptr, *status = nullptr;   // f x nchains each, or null
+  int64_t f = 0;
+  int32_t d = 0, S = 0, N = 0, G = 1, lgG = 0, maxw = 1;
+  double t0 = 0.0, reltol = 0.0, abstol = 0.0, dt = 0.0;
+  int32_t adaptive = 1, max_steps = 0, pre_power = 1;
+};
+struct NodeState {
+  bool on = false;
+  NodeArgs args;                   // everything but the per-call pointers (w, U0, Y, the outputs, f)
+  int32_t d = 0, S = 0;
+  DevBuf<double> ts;               // S
+  DevBuf<double> ssep;             // f x slots: the per-trajectory sums of one pass of launches
+  DevBuf<double> uout;             // d*S x f x slots: the saved states, only on request (si_forward)
+};
+hipError_t launch_node_solve(hipStream_t st, const NodeArgs& a, int nchains);
+void launch_node_sum(hipStream_t st, const double* sse_p, int64_t f, double* sse, int nchains);
+
 // ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops
 struct InferState {
   bool i_ready = false;
+  NodeState node;                 // on: the set-up is a NeuralODE's; the density integrates instead of evaluating a Chain
   DecoderState dec;               // set: every density entry point forms W_swa + decoder(z); the stored P is ignored
   const double* i_swa = nullptr;  // device; borrowed (the construction's, the caller's) or d_iswa
   const double* i_P = nullptr;    // device, ldP x M; likewise

@@ -162,8 +162,58 @@ class Chain:
         return x
 
 
+class Cube:
+    """the tutorial's `x -> x.^3` in front of a NeuralODE's right-hand side (docs/src/node_example.md): Julia's literal x^3, (x*x)*x"""
+
+    def __call__(self, x):
+        return (x * x) * x
+
+
+cube = Cube()
+
+
+class NeuralODE:
+    """DiffEqFlux's `NeuralODE(dudt, tspan, Tsit5(), saveat = ..., reltol = ..., abstol = ...)` as the reference's `model_re`
+    takes it (src/libs.jl:36-54): `dudt` is a Chain of Dense layers d -> ... -> d whose first element may be `cube`; `saveat` is
+    the vector of save times (or a step: tspan[0], tspan[0] + saveat, ... up to tspan[1]).  Tsit5 is the only solver.  The
+    definition of its solve is node.py; `adaptive=False` takes fixed steps of `dt`.  Calling it solves on the host (node.solve):
+    (d, f) initial states -> (d*S, f), row i*S + s being state i at save time s."""
+
+    def __init__(self, dudt, tspan, saveat, reltol=1e-3, abstol=1e-6, adaptive=True, dt=0.0, max_steps=100000):
+        if not isinstance(dudt, Chain) or not dudt.layers:
+            raise SubspaceError("Error: the right-hand side of a NeuralODE must be a Chain")
+        layers = list(dudt.layers)
+        self.pre_power = 1
+        if isinstance(layers[0], Cube):
+            self.pre_power, layers = 3, layers[1:]
+        if not layers or not all(isinstance(l, Dense) for l in layers):
+            raise SubspaceError("Error: the right-hand side of a NeuralODE must be Dense layers, optionally behind flux.cube "
+                                "(FastChain and other layers are out of scope)")
+        self.dudt = dudt
+        self.chain = Chain(*layers)            # the Dense layers alone: the same arrays, Flux.destructure order
+        self.tspan = (float(tspan[0]), float(tspan[1]))
+        if np.isscalar(saveat):
+            n = int(np.floor((self.tspan[1] - self.tspan[0]) / float(saveat) + 1e-12))
+            saveat = self.tspan[0] + float(saveat) * np.arange(n + 1)
+        self.saveat = np.ascontiguousarray(saveat, dtype=np.float64).reshape(-1)
+        self.reltol, self.abstol, self.adaptive, self.dt, self.max_steps = float(reltol), float(abstol), bool(adaptive), float(dt), int(max_steps)
+
+    def options(self):
+        """the keyword arguments of Context.infer_setup_node / the fields of node.Opts"""
+        return dict(t0=self.tspan[0], reltol=self.reltol, abstol=self.abstol, dt=self.dt, adaptive=1 if self.adaptive else 0,
+                    max_steps=self.max_steps, pre_power=self.pre_power)
+
+    def __call__(self, u0):
+        from . import node
+        table, _ = layer_table(self.chain)
+        w = extract_params(params(self.chain)).astype(np.float64)
+        return node.solve(table, w, np.asarray(u0, dtype=np.float64), self.saveat, node.Opts(**self.options())).U
+
+
 def params(model):
     """Flux.params(model): ordered list of the trainable arrays (W then b per Dense layer)."""
+    if isinstance(model, NeuralODE):
+        return params(model.chain)
     if not isinstance(model, Chain):
         raise SubspaceError("Error: model_re function is not available for this model")
     out = []

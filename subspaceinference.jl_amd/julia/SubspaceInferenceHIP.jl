@@ -520,6 +520,53 @@ function decode(ctx::Ctx, Z::Matrix{Float64}, N)                     # decoder(z
     return Y
 end
 
+# ---- NeuralODE models (src/space_inference.jl:96-101; model_re at src/libs.jl:36-54) --------------------------------------------
+# infer_setup_node!(ctx, dudt, W_swa, P, U0, Y, ts; ...) in place of the Chain set-up: dudt is the Dense chain d -> ... -> d of the
+# right-hand side (pre_power = 3: the tutorial's `x -> x.^3` in front of it), U0 is d x f, Y is d*S x f (reshape(out[:, p], :, d)'
+# per column), ts the S save times.  From then on logdensity, the RWMH samplers and reconstruct integrate on the device; the
+# gradient-driven samplers are refused.  node_solve returns the saved states and the solver's counts at the columns of Z.
+struct SiNodeOpts
+    t0::Float64
+    reltol::Float64
+    abstol::Float64
+    dt::Float64
+    adaptive::Int32
+    max_steps::Int32
+    pre_power::Int32
+end
+function infer_setup_node!(ctx::Ctx, dudt, W_swa::Vector{Float64}, P::Matrix{Float64}, U0::Matrix{Float64}, Y::Matrix{Float64},
+                           ts::Vector{Float64}; t0 = 0.0, reltol = 1e-3, abstol = 1e-6, dt = 0.0, adaptive = true,
+                           max_steps = 100000, pre_power = 1)
+    tbl, N = layer_table(dudt)
+    d, f, S = size(U0, 1), size(U0, 2), length(ts)
+    size(Y) == (d * S, f) || throw(DimensionMismatch("Y must be d*S x f"))
+    opts = Ref(SiNodeOpts(t0, reltol, abstol, dt, adaptive ? 1 : 0, max_steps, pre_power))
+    GC.@preserve tbl W_swa P U0 Y ts opts check(ctx, ccall((:si_infer_setup_node, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{SiLayer}, Int32, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Int64,
+         Ptr{Float64}, Ptr{Cvoid}), ctx.h, tbl, length(tbl), N, size(P, 2), W_swa, P, U0, Y, d, S, f, ts, opts))
+end
+function node_info(ctx::Ctx)
+    on, d, S, f, G = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0), Ref{Int64}(0), Ref{Int32}(0)
+    check(ctx, ccall((:si_node_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int64}, Ref{Int32}),
+        ctx.h, on, d, S, f, G))
+    return on[] != 0, Int(d[]), Int(S[]), Int(f[]), Int(G[])
+end
+function node_solve(ctx::Ctx, Z::Matrix{Float64})
+    _, d, S, f, _ = node_info(ctx)
+    C = size(Z, 2)
+    U = Array{Float64}(undef, d * S, f, C)
+    sse = Matrix{Float64}(undef, f, C)
+    na, nr, st = Matrix{Int32}(undef, f, C), Matrix{Int32}(undef, f, C), Matrix{Int32}(undef, f, C)
+    GC.@preserve Z U sse na nr st check(ctx, ccall((:si_node_solve, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}), ctx.h, Z, C, U, sse, na, nr, st))
+    return U, sse, na, nr, st
+end
+function node_tableau()
+    out = Vector{Float64}(undef, 57)
+    ccall((:si_node_tableau, LIB), Int32, (Ptr{Float64},), out) == 0 || throw("si_node_tableau failed")
+    return out
+end
+
 # include_prior = true adds the term the reference writes after its `return` (dead code, :95); default: as the reference
 # compute_dtype = :f32 (non-default; SURVEY section 0 Q6): the density of a Dense or Conv chain on the fp32 matrix instructions -- X rounded
 # once, W_swa + P*z formed in Float64 and rounded once per transition, Float32 activations, head + sum of squared errors in Float64

@@ -311,8 +311,9 @@ typedef struct {
  * that bindings pass a reference to their own mirror of the struct).
  * While it is active si_logdensity, si_forward (the saved states, d*S x f), si_predict (new initial states d x Bn), si_reconstruct,
  * si_sample_rwmh, si_sample_rwmh_weights, the si_rwmh_* session and si_infer_set_decoder work as for a Chain;
- * si_logdensity_grad*, si_sample_mala / _hmc / _nuts, si_fit_advi, si_infer_set_prior and the sharded sampler return SI_ERR_INVALID
- * ("not available for NeuralODE models").  The next si_infer_setup* leaves the mode. */
+ * si_infer_set_prior and the sharded sampler return SI_ERR_INVALID ("not available for NeuralODE models"), and so do
+ * si_logdensity_grad*, si_sample_mala / _hmc / _nuts and si_fit_advi until si_node_set_grad(ctx, 1).  The next si_infer_setup*
+ * leaves the mode and drops that switch. */
 int32_t si_infer_setup_node(si_ctx* ctx, const si_layer* layers, int32_t L, int64_t N, int32_t M, const double* W_swa,
                             const double* P, const double* U0 /* d x f */, const double* Y /* d*S x f */, int32_t d, int32_t S,
                             int64_t f, const double* ts /* S */, const void* opts /* const si_node_opts* */);
@@ -325,6 +326,20 @@ int32_t si_node_solve(si_ctx* ctx, const double* Z, int32_t C, double* U_out, do
 int32_t si_node_tableau(double* out);
 /* whether a NeuralODE set-up is active, d, S, f and the lanes G that share one trajectory (outputs may be NULL) */
 int32_t si_node_info(si_ctx* ctx, int32_t* active_out, int32_t* d_out, int32_t* S_out, int64_t* f_out, int32_t* G_out);
+/* The gradient through the solver, off after every si_infer_setup_node.  on = 1 lets si_logdensity_grad, si_logdensity_grad_batch,
+ * si_sample_mala / _hmc / _nuts and si_fit_advi through on this set-up; what they differentiate is the DISCRETE ADJOINT of the
+ * integration si_node_solve performs with its accepted step sequence frozen (node.py: logdensity_grad): hs_n and every
+ * interpolation theta are constants, rejected steps, the starting step and the controller do not enter.  (Not what ForwardDiff
+ * gives through OrdinaryDiffEq, where the partials enter the error norm: the two agree to the order of the tolerances.)  A failed
+ * trajectory gives lp = -Inf and NaN in every component.  SI_ERR_INVALID naming the reason when a layer is wider than 64, or when
+ * the step record of one chain (f * max_steps * (d + 2) doubles) with its gradient slices (f * N) exceeds the 2 GiB workspace
+ * budget -- lower max_steps.  on = 0 turns it off and frees the workspace. */
+int32_t si_node_set_grad(si_ctx* ctx, int32_t on);
+/* whether the switch is on, and the chains one pass of launches carries under the budget (outputs may be NULL) */
+int32_t si_node_grad_info(si_ctx* ctx, int32_t* on_out, int32_t* chains_per_pass_out);
+/* The audit read-back of that gradient at Z[:, c]: lp (C), d lp / dW with the prior term (N x C) and its pull-back to z (M x C).
+ * Every output may be NULL. */
+int32_t si_node_grad(si_ctx* ctx, const double* Z /* M x C */, int32_t C, double* lp_out, double* gw_out, double* gz_out);
 /* :90-95  lp[c] = logpdf(MvNormal(vec(f_{W_swa+P z_c}(X)), sigma_m), vec(Y)),  Z is M x C          */
 int32_t si_logdensity(si_ctx* ctx, const double* Z, int32_t C, double* lp_out /* C */);
 /* lp and its gradient with respect to z: grad_out[m] = d lp / d z_m = (P' * d lp / d w)[m].

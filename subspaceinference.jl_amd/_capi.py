@@ -102,6 +102,9 @@ SIGNATURES = {
     "si_node_solve": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "si_node_tableau": (c_int32, [c_void_p]),
     "si_node_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), POINTER(c_int32)]),
+    "si_node_set_grad": (c_int32, [c_void_p, c_int32]),
+    "si_node_grad_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
+    "si_node_grad": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "si_logdensity": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p]),
     "si_logdensity_grad": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "si_logdensity_grad_batch": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
@@ -695,6 +698,31 @@ class Context:
         na, nr, st = (np.empty((self._b, c), dtype=np.int32, order="F") for _ in range(3))
         self._check(self.lib.si_node_solve(self.h, _ptr(z), c, _ptr(u), _ptr(sse), _ptr(na), _ptr(nr), _ptr(st)))
         return u, sse, na, nr, st
+
+    def node_set_grad(self, on=True):
+        """si_node_set_grad: the gradient through the solver (the discrete adjoint over the frozen accepted steps, node.logdensity_grad)
+        for the NeuralODE set up; off after every infer_setup_node"""
+        self._check(self.lib.si_node_set_grad(self.h, 1 if on else 0))
+
+    def node_grad_info(self):
+        """(on, chains per pass of launches under the workspace budget)"""
+        on, cpp = c_int32(0), c_int32(0)
+        self._check(self.lib.si_node_grad_info(self.h, byref(on), byref(cpp)))
+        return bool(on.value), int(cpp.value)
+
+    def node_grad(self, z):
+        """si_node_grad at every column of z (M x C): (lp (C), d lp / dW with the prior term (N, C), its pull-back to z (M, C))"""
+        z = _f64(z)
+        if z.ndim == 1:
+            z = z.reshape(-1, 1, order="F")
+        if z.ndim != 2 or z.shape[0] != self._m:
+            raise SubspaceError("DimensionMismatch: z has %d rows, M = %d" % (z.shape[0], self._m))
+        c = z.shape[1]
+        lp = np.empty(c, dtype=np.float64)
+        gw = np.empty((self._ni, c), dtype=np.float64, order="F")
+        gz = np.empty((self._m, c), dtype=np.float64, order="F")
+        self._check(self.lib.si_node_grad(self.h, _ptr(z), c, _ptr(lp), _ptr(gw), _ptr(gz)))
+        return lp, gw, gz
 
     def node_tableau(self):
         """c, a, b~ and the interpolant's constants as the kernel holds them (node.TABLEAU's order)"""

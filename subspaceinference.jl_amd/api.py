@@ -187,7 +187,9 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
     A `flux.NeuralODE` model (reference :96-101; docs/src/node_example.md) is accepted for alg = :rwmh / :mh: `data` holds the initial
     states (d x f) and the observed trajectories (d*S x f), the density -sum_p ||sol_p - Y_p||^2 - ||W||^2 integrates every trajectory
     with Tsit5 on the device (si_infer_setup_node; node.py is the definition), and `nchains`, `return_z` and the output map work as
-    for a Chain.  The gradient samplers raise: the gradient through the solver is not built.
+    for a Chain.  The gradient samplers (:mala / :hmc / :nuts / :advi, host loop or device) need the model's
+    `sensealg="discrete_adjoint"` (si_node_set_grad: the discrete adjoint of the integration with its accepted steps frozen, DESIGN
+    section 19); without it they raise: the gradient through the solver is not built.
 
     `density(z)` (:90-95: W_swa + P*z -> model_re -> forward over the FULL data -> Gaussian log-likelihood,
     prior term dead) and the RWMH loop (:111-116) run on the device; the output map (:125) materialises
@@ -246,9 +248,10 @@ def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg,
         raise SubspaceError("Error: density function is not avaliable for this model")  # [sic] reference :103
     x, y, in_size = flux.data_matrices(data)  # split_data, src/libs.jl:75-77 (full data, not the batches)
     if is_node:
-        if a not in _RWMH_ALGS:
-            raise SubspaceError("alg = :%s needs the gradient of the density, and the gradient through the ODE solver is not built: "
-                                "a NeuralODE model is sampled with alg = :rwmh / :mh" % a)
+        if a not in _RWMH_ALGS and in_model.sensealg is None:
+            raise SubspaceError("alg = :%s needs the gradient of the density, and the gradient through the ODE solver is not built "
+                                "for this model: a NeuralODE model is sampled with alg = :rwmh / :mh, or constructed with "
+                                "sensealg=\"discrete_adjoint\"" % a)
         if include_prior or compute_dtype != "f64":
             raise SubspaceError("a NeuralODE's density carries -||W||^2 itself and is evaluated in Float64: include_prior and "
                                 "compute_dtype = \"f32\" are not available")
@@ -262,6 +265,8 @@ def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg,
     def setup(w_swa, p):
         if is_node:   # σ_m and σ_p are accepted and unused, as in the reference (:96-101)
             ctx.infer_setup_node(table, n_par, M, w_swa, p, x, y, in_model.saveat, **in_model.options())
+            if in_model.sensealg == "discrete_adjoint" and a not in _RWMH_ALGS:
+                ctx.node_set_grad(True)
         else:
             ctx.infer_setup(table, n_par, M, w_swa, p, x, y, σ_m, compute_dtype=cdt)
     try:

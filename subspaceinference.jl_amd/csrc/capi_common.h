@@ -50,6 +50,9 @@ struct DensityView {
   bool defer_sse_final;           // the SSE block partials stay in ssepart (the RWMH tail kernel sums them)
   bool is_setup_data;             // X, Y, B are the set-up's: what the narrow chain's plan and tile program were built for
 };
+// the cap on a stacked workspace: how many chains one pass of launches carries follows from it (batch_width, vgrad_route, the
+// NeuralODE gradient's record)
+constexpr double SI_BATCH_BYTES = 2.0 * 1024.0 * 1024.0 * 1024.0;
 constexpr int32_t SI_NOT_TAKEN = INT32_MIN;   // a density route's or a sampler form's answer "does not apply": the next one is tried
 
 }  // namespace si
@@ -80,6 +83,13 @@ int32_t node_density(si_ctx* ctx, const si::DensityView& v, int c0, int nc, cons
 int32_t node_predict(si_ctx* ctx, const double* Z, int32_t C, const double* U0new, int64_t Bn, double* U_out);
 int32_t infer_setup_node_base(si_ctx* ctx, const si_layer* layers, int32_t L, int64_t N, int32_t M, const double* W_swa, const double* P,
                               const double* U0, const double* Y, int32_t d, int32_t S, int64_t f);
+// ... and its value-and-gradient route (si_node_set_grad): the workspace for min(C, what the budget allows) chains per pass; one
+// pass of launches for n <= node.g_cap points on the device (queued: nothing is copied, nothing synchronises; P route only); one
+// point from the host (either seam; synchronises); C points from the host, pass by pass (P route)
+int32_t node_grad_ensure(si_ctx* ctx, const char* who, int32_t C);
+int32_t node_value_and_grad(si_ctx* ctx, const double* z_dev, int32_t n, double* lp_dev, double* gz_dev);
+int32_t node_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* grad_out);
+int32_t node_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double* lp_out, double* grad_out);
 void fused_fill_program(const si_ctx* ctx, si::ChainFusedPlan& fp);
 int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok);   // the gradient entry points' state rules and error texts
 }
@@ -90,6 +100,7 @@ namespace si {
 // si_sample_hmc, si_fit_advi); defined in capi_infer.hip, where the two routes are described.
 struct StackedVgrad {
   bool fused = false;   // the route of this call
+  bool node = false;    // ... or the third: a NeuralODE set-up on the P route, node_value_and_grad pass by pass (capi_node.hip)
   int passes = 0;       // per evaluation: passes of launches (fused) / single-point evaluations (other)
   // once per call, after the caller's own allocations: the route, then the fused workspace or the other route's host images
   int32_t open(si_ctx* ctx, const char* who, int32_t C);

@@ -256,7 +256,6 @@ int32_t si_construct_result_ptr(si_ctx* ctx, double** W_swa_dev_out, double** P_
 // (a 20-wide Dense layer on 1000 observations is 8 workgroups), so independent chains are stacked in grid.y; the
 // workspace for that is capped so that a model whose single chain already fills the chip (cfg2: 1.5 GB of activations
 // per chain) keeps one slot.
-static constexpr double SI_BATCH_BYTES = 2.0 * 1024.0 * 1024.0 * 1024.0;
 static int batch_width(const si_ctx* ctx, int C) {
   if (ctx->plan.has_conv) return 1;  // chains with Conv layers fill the chip one chain at a time
   const double pslots = (double)std::max(ctx->fuse_slots, ctx->fuse_slots32);
@@ -708,6 +707,7 @@ static int32_t ensure_grad(si_ctx* ctx) {
 static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* grad_out) {
   int32_t rc = ensure_chains(ctx, 1);
   if (rc != SI_OK) return rc;
+  if (ctx->node.on) return node_grad_point(ctx, z, lp_out, grad_out);   // the discrete adjoint through the solver (capi_node.hip)
   if ((rc = ensure_grad(ctx)) != SI_OK) return rc;
   const int64_t N = ctx->iN, B = ctx->B;
   const int32_t M = ctx->iM;
@@ -759,7 +759,9 @@ static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_ou
 // the state rules and error texts shared by the two gradient entry points
 int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok) {
   if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_infer_setup first");
-  if (ctx->node.on) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": not available for NeuralODE models (the gradient through the solver is not built)");
+  if (ctx->node.on && !ctx->node.grad)   // (the switch: si_node_set_grad)
+    return fail(ctx, SI_ERR_INVALID, std::string(who) + ": not available for NeuralODE models (the gradient through the solver is not built "
+                                                        "for this set-up: si_node_set_grad(ctx, 1) turns the discrete adjoint on)");
   if (!args_ok) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": bad argument");
   if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, std::string(who) + ": a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
   return SI_OK;
@@ -878,6 +880,13 @@ namespace si {
 //           has the device samplers' definitions.
 int32_t StackedVgrad::open(si_ctx* c, const char* who, int32_t npoints) {
   ctx = c, C = npoints;
+  node = ctx->node.on && !ctx->dec.on;   // (with a decoder a node set-up goes column by column, as Chains do)
+  if (node) {
+    const int32_t rc = node_grad_ensure(ctx, who, C);
+    if (rc != SI_OK) return rc;
+    passes = (C + ctx->node.g_cap - 1) / ctx->node.g_cap;
+    return SI_OK;
+  }
   int64_t fit = 0;
   nb = vgrad_route(ctx, &G, &fit);
   fused = fit >= 1;
@@ -895,6 +904,12 @@ int32_t StackedVgrad::open(si_ctx* c, const char* who, int32_t npoints) {
 
 void StackedVgrad::eval(const double* z_dev, double* lp_dev, double* g_dev, hipError_t& e, int32_t& rc) {
   const size_t M = (size_t)ctx->iM;
+  if (node) {
+    for (int32_t p0 = 0; p0 < C && rc == SI_OK; p0 += ctx->node.g_cap)
+      rc = node_value_and_grad(ctx, z_dev + M * p0, std::min<int32_t>(ctx->node.g_cap, C - p0), lp_dev + p0, g_dev + M * p0);
+    e = hipGetLastError();
+    return;
+  }
   if (fused) {
     for (int32_t p0 = 0; p0 < C; p0 += ctx->vg_cap)
       vgrad_pass(ctx, nb, G, z_dev + M * p0, std::min<int32_t>(ctx->vg_cap, C - p0), lp_dev + p0, g_dev + M * p0);
@@ -932,6 +947,7 @@ int32_t si_logdensity_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double
   BIND(ctx);
   ctx->last_grad_fused = 0;
   const int32_t M = ctx->iM;
+  if (ctx->node.on && !ctx->dec.on) return node_grad_batch(ctx, Z, C, lp_out, grad_out);   // all points of a pass in one launch each
   int64_t G = 0, fit = 0;
   const int nb = vgrad_route(ctx, &G, &fit);
   if (fit < 1) {

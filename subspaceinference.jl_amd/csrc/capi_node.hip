@@ -176,6 +176,166 @@ int32_t node_predict(si_ctx* ctx, const double* Z, int32_t C, const double* U0ne
   return SI_OK;
 }
 
+// ---- the gradient through the solver (si_node_set_grad; node.py: logdensity_grad is the definition) ----------------------------
+// the bytes one chain of a pass needs: its record (f * max_steps * (d + 2) doubles) and its per-trajectory gradient slices (f * N)
+static double node_grad_chain_bytes(const si_ctx* ctx) {
+  const NodeArgs& a = ctx->node.args;
+  return 8.0 * (double)ctx->B * ((double)a.max_steps * (double)(a.d + 2) + (double)ctx->iN);
+}
+
+static void node_grad_drop(NodeState& n) {
+  for (DevBuf<double>* b : {&n.g_z, &n.g_w, &n.g_ssep, &n.g_sse, &n.g_wsq, &n.g_wsqpart, &n.g_rec, &n.g_slices, &n.g_gw, &n.g_lp, &n.g_gz}) b->reset();
+  n.g_cnt.reset();
+  n.g_cap = 0;
+}
+
+int32_t si_node_set_grad(si_ctx* ctx, int32_t on) {
+  CHECK_CTX(ctx);
+  if (!ctx->i_ready || !ctx->node.on) return fail(ctx, SI_ERR_STATE, "si_node_set_grad: call si_infer_setup_node first");
+  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_node_set_grad: a step-wise RWMH session is open");
+  if (on != 0 && on != 1) return fail(ctx, SI_ERR_INVALID, "si_node_set_grad: on must be 0 or 1");
+  BIND(ctx);
+  NodeState& n = ctx->node;
+  if (!on) {
+    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    node_grad_drop(n);
+    n.grad = false, n.g_fit = 0;
+    return SI_OK;
+  }
+  if (n.args.maxw > 64)
+    return fail(ctx, SI_ERR_INVALID, "si_node_set_grad: a layer is wider than 64 (the reverse kernel gives every lane of a trajectory's group one unit per layer)");
+  const double fit = std::floor(SI_BATCH_BYTES / node_grad_chain_bytes(ctx));
+  if (fit < 1.0)
+    return fail(ctx, SI_ERR_INVALID, "si_node_set_grad: the record of one chain (f * max_steps * (d + 2) doubles) and its gradient slices (f * N) "
+                                     "do not fit the 2 GiB workspace budget: lower max_steps");
+  n.g_fit = (int)std::min(fit, 65535.0);   // (a launch carries its chains in grid.y)
+  n.grad = true;
+  return SI_OK;
+}
+
+int32_t si_node_grad_info(si_ctx* ctx, int32_t* on_out, int32_t* chains_per_pass_out) {
+  CHECK_CTX(ctx);
+  const bool on = ctx->i_ready && ctx->node.on && ctx->node.grad;
+  if (on_out) *on_out = on ? 1 : 0;
+  if (chains_per_pass_out) *chains_per_pass_out = on ? ctx->node.g_fit : 0;
+  return SI_OK;
+}
+
+int32_t node_grad_ensure(si_ctx* ctx, const char* who, int32_t C) {
+  NodeState& n = ctx->node;
+  const int cap = std::min<int>(n.g_fit, std::max(1, C));
+  if (n.g_cap >= cap) return SI_OK;
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  node_grad_drop(n);
+  const size_t S = (size_t)cap, f = (size_t)ctx->B, N = (size_t)ctx->iN, ldw = (size_t)pad_ld(ctx->iN), M = (size_t)ctx->iM;
+  const bool ok = n.g_z.alloc(S * M) && n.g_w.alloc(S * ldw) && n.g_ssep.alloc(S * f) && n.g_sse.alloc(S) && n.g_wsq.alloc(S) &&
+                  n.g_wsqpart.alloc(S * (size_t)ctx->wsq_blocks) && n.g_rec.alloc(S * f * (size_t)n.args.max_steps * (size_t)(n.d + 2)) &&
+                  n.g_slices.alloc(S * f * N) && n.g_gw.alloc(S * ldw) && n.g_lp.alloc(S) && n.g_gz.alloc(S * M) && n.g_cnt.alloc(3 * S * f) &&
+                  ctx->d_ptgpart.reserve((size_t)ptg_blocks() * M);
+  if (!ok) {
+    node_grad_drop(n);
+    return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": workspace allocation failed (the NeuralODE gradient's record: lower max_steps)");
+  }
+  // (the padding rows of g_w / g_gw are written by no kernel and launch_prior_grad runs over whole columns: defined once, here)
+  SI_HIP(ctx, hipMemset(n.g_w, 0, S * ldw * sizeof(double)));
+  SI_HIP(ctx, hipMemset(n.g_gw, 0, S * ldw * sizeof(double)));
+  n.g_cap = cap;
+  return SI_OK;
+}
+
+// the weights are in g_w: ||W||^2, the forward with record, the reverse kernel, the sums (gw without the prior term, lp)
+static int32_t node_grad_launches(si_ctx* ctx, int32_t nc, double* lp_dev) {
+  NodeState& n = ctx->node;
+  const int64_t N = ctx->iN, ldw = pad_ld(N), f = ctx->B;
+  const size_t fc = (size_t)f * (size_t)n.g_cap;
+  launch_sse(ctx->stream, n.g_w, nullptr, N, n.g_wsqpart, ctx->wsq_blocks, n.g_wsq, nc, ldw);
+  SI_HIP(ctx, hipMemsetAsync(n.g_slices, 0, (size_t)nc * (size_t)f * (size_t)N * sizeof(double), ctx->stream));   // "from 0.0"
+  NodeArgs a = node_args(ctx, n.g_w, ctx->d_X, ctx->d_Y, f, n.g_ssep, nullptr, n.g_cnt, n.g_cnt + fc, n.g_cnt + 2 * fc);
+  a.rec = n.g_rec, a.gsl = n.g_slices;
+  {
+    ProfScope ps(ctx, SI_K_DENSE, 0.0, 0.0);
+    SI_HIP(ctx, launch_node_solve(ctx->stream, a, nc));
+    launch_node_sum(ctx->stream, n.g_ssep, f, n.g_sse, nc);
+  }
+  {
+    ProfScope ps(ctx, SI_K_BACKWARD, 0.0, 0.0);
+    SI_HIP(ctx, launch_node_grad(ctx->stream, a, nc));
+    launch_node_grad_sum(ctx->stream, n.g_slices, f, N, n.g_gw, ldw, n.g_sse, n.g_wsq, lp_dev, nc);
+  }
+  launch_prior_grad(ctx->stream, n.g_gw, n.g_w, (int64_t)nc * ldw, 1.0 / prior_sp2(ctx), ctx->num_cu);   // - 2 W, every chain at once
+  SI_HIP(ctx, hipGetLastError());
+  return SI_OK;
+}
+
+int32_t node_value_and_grad(si_ctx* ctx, const double* z_dev, int32_t nc, double* lp_dev, double* gz_dev) {
+  NodeState& n = ctx->node;
+  const int64_t ldw = pad_ld(ctx->iN);
+  int32_t rc;
+  {
+    ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)ctx->iN * ctx->iM * nc, (double)ctx->iN * (ctx->iM + 1 + nc) * 8.0);
+    if ((rc = form_weights(ctx, z_dev, nc, n.g_w, ldw, nullptr, /*keep_y=*/ctx->dec.on)) != SI_OK) return rc;
+  }
+  if ((rc = node_grad_launches(ctx, nc, lp_dev)) != SI_OK) return rc;
+  for (int32_t c = 0; c < nc; ++c) pull_back_to_z(ctx, n.g_gw + (size_t)ldw * c, gz_dev + (size_t)ctx->iM * c);   // queued per point
+  SI_HIP(ctx, hipGetLastError());
+  return SI_OK;
+}
+
+int32_t node_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* grad_out) {
+  NodeState& n = ctx->node;
+  const size_t M = (size_t)ctx->iM;
+  int32_t rc = node_grad_ensure(ctx, "si_logdensity_grad", 1);
+  if (rc != SI_OK) return rc;
+  SI_HIP(ctx, hipMemcpyAsync(n.g_z, z, M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = node_value_and_grad(ctx, n.g_z, 1, n.g_lp, n.g_gz)) != SI_OK) return rc;
+  SI_HIP(ctx, hipMemcpyAsync(lp_out, n.g_lp, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(grad_out, n.g_gz, M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SI_OK;
+}
+
+int32_t node_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double* lp_out, double* grad_out) {
+  NodeState& n = ctx->node;
+  const size_t M = (size_t)ctx->iM;
+  int32_t rc = node_grad_ensure(ctx, "si_logdensity_grad_batch", C);
+  if (rc != SI_OK) return rc;
+  for (int32_t c0 = 0; c0 < C; c0 += n.g_cap) {
+    const int32_t nc = std::min<int32_t>(n.g_cap, C - c0);
+    SI_HIP(ctx, hipMemcpyAsync(n.g_z, Z + M * c0, M * nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = node_value_and_grad(ctx, n.g_z, nc, n.g_lp, n.g_gz)) != SI_OK) return rc;
+    SI_HIP(ctx, hipMemcpyAsync(lp_out + c0, n.g_lp, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SI_HIP(ctx, hipMemcpyAsync(grad_out + M * c0, n.g_gz, M * nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SI_OK;
+}
+
+// the audit read-back: lp (C), d lp / dW (N x C, the prior term included) and its pull-back (M x C) at Z[:, c]; either seam
+int32_t si_node_grad(si_ctx* ctx, const double* Z, int32_t C, double* lp_out, double* gw_out, double* gz_out) {
+  CHECK_CTX(ctx);
+  if (!ctx->i_ready || !ctx->node.on) return fail(ctx, SI_ERR_STATE, "si_node_grad: call si_infer_setup_node first");
+  int32_t rc = grad_entry_check(ctx, "si_node_grad", Z && C >= 1);
+  if (rc != SI_OK) return rc;
+  BIND(ctx);
+  NodeState& n = ctx->node;
+  const size_t M = (size_t)ctx->iM, N = (size_t)ctx->iN, ldw = (size_t)pad_ld(ctx->iN);
+  const int32_t want = ctx->dec.on ? 1 : C;   // (the decoder's reverse holds one point: column by column)
+  if ((rc = node_grad_ensure(ctx, "si_node_grad", want)) != SI_OK) return rc;
+  const int32_t step = ctx->dec.on ? 1 : n.g_cap;
+  for (int32_t c0 = 0; c0 < C; c0 += step) {
+    const int32_t nc = std::min<int32_t>(step, C - c0);
+    SI_HIP(ctx, hipMemcpyAsync(n.g_z, Z + M * c0, M * nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = node_value_and_grad(ctx, n.g_z, nc, n.g_lp, n.g_gz)) != SI_OK) return rc;
+    if (lp_out) SI_HIP(ctx, hipMemcpyAsync(lp_out + c0, n.g_lp, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (gw_out)
+      SI_HIP(ctx, hipMemcpy2DAsync(gw_out + N * c0, N * sizeof(double), n.g_gw, ldw * sizeof(double), N * sizeof(double), (size_t)nc,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+    if (gz_out) SI_HIP(ctx, hipMemcpyAsync(gz_out + M * c0, n.g_gz, M * nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return SI_OK;
+}
+
 int32_t si_node_tableau(double* out) {
   if (!out) return SI_ERR_INVALID;
   int n = 0;

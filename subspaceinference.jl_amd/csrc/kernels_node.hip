@@ -72,7 +72,10 @@ __device__ __forceinline__ double node_comb(const double (&c)[NK], const double 
   return s;
 }
 
-template <int D>
+// RECORD: the same body once more, writing (t_n, hs_n, u_n) of every accepted step for the reverse kernel below (a.rec, sized by
+// max_steps: accepted + rejected steps stay below it, so the record cannot overflow).  Nothing else differs: sums, counts and
+// statuses are the unrecorded kernel's bits.
+template <int D, bool RECORD>
 __global__ __launch_bounds__(256) void node_solve_kernel(NodeArgs a) {
   extern __shared__ double node_lds[];
   const int G = a.G;
@@ -227,6 +230,14 @@ __global__ __launch_bounds__(256) void node_solve_kernel(NodeArgs a) {
       h = hnew;
       continue;
     }
+    if constexpr (RECORD) {
+      if (lead) {
+        double* r = a.rec + (tr * a.max_steps + nacc) * (int64_t)(D + 2);
+        r[0] = t, r[1] = hs;
+#pragma unroll
+        for (int i = 0; i < D; ++i) r[2 + i] = u[i];
+      }
+    }
     nacc += 1;
     const double tn = last ? tend : t + hs;
     while (s < S) {   // (saveat without tstops: the step never stops at a save time)
@@ -286,15 +297,277 @@ __global__ __launch_bounds__(64) void node_sum_kernel(const double* __restrict__
   sse[c] = acc;
 }
 
+// ---- the gradient through the solver (si_node_set_grad; node.py: grad_slices is the definition) ---------------------------------
+// The discrete adjoint over the recorded accepted steps, hs_n and every theta frozen.  The forward kernel's layout: G lanes per
+// trajectory, 256 / G trajectories per workgroup, the chain's weights in LDS; every layer is at most 64 wide (si_node_set_grad), so
+// lane j owns unit j -- row j of W and b_j -- of every layer.  Per step, descending, the seven stages are recomputed from the
+// recorded u_n with node_rhs itself (k_1 = f(u_n) has the bits of the forward's FSAL value); then per stage in reverse node_vjp
+// recomputes that stage's layer outputs, one value per lane and layer kept in the group's LDS slice, and back-propagates: the
+// transposed product is lane i's own ascending sum over the exchanged delta, and lane j adds delta_j * a_in[i] into the
+// trajectory's own N-slice in global memory with plain loads and stores (one lane per element and stage; the stream zeroed it).
+// No atomics; the lanes of a group take identical branches (t, hs, the RK state and the adjoints are replicated in each);
+// wavefront fences only after the one weight-load barrier; the step loop is bounded by the recorded count, the save loop by S.
+// A trajectory's bits depend on its inputs alone: not on G, f, C, its column, its chain slot or the run.
+
+// node_comb over stage values kept in LDS (kl[j * D + i] = k_{j+1}[i]): the same terms in the same order
+template <int D, int NK>
+__device__ __forceinline__ double node_comb_lds(const double (&c)[NK], const double* kl, int n, int i) {
+  double s = c[0] * kl[i];
+#pragma unroll
+  for (int j = 1; j < NK; ++j)
+    if (j < n) s = s + c[j] * kl[j * D + i];
+  return s;
+}
+
+// g = J_u' kb of f at x; J_W' kb goes into the slice gs.  ac: the group's n x maxw layer outputs, dx: its two delta buffers.
+template <int D>
+__device__ __forceinline__ void node_vjp(const NodeArgs& a, const double* __restrict__ wl, double* ac, double* dx, int lane,
+                                         const double (&x)[D], const double (&kb)[D], double (&g)[D], double* __restrict__ gs) {
+  double a0[D];
+#pragma unroll
+  for (int i = 0; i < D; ++i) a0[i] = a.pre_power == 3 ? (x[i] * x[i]) * x[i] : x[i];
+  const int mw = a.maxw;
+  for (int l = 0; l < a.lay.n; ++l) {   // the forward's own sums, every layer's outputs kept
+    const int in = a.lay.in[l], on = a.lay.out[l];
+    const double* W = wl + a.lay.w_off[l];
+    const double* src = l > 0 ? ac + (l - 1) * mw : ac;   // (layer 0 reads a0)
+    if (lane < on) {
+      double acc = 0.0;
+      if (l == 0) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) acc = acc + W[lane + on * i] * a0[i];
+      } else {
+        for (int i = 0; i < in; ++i) acc = acc + W[lane + on * i] * src[i];
+      }
+      acc = acc + wl[a.lay.b_off[l] + lane];
+      ac[l * mw + lane] = node_act(acc, a.lay.act[l]);
+    }
+    node_group_sync();
+  }
+  double* dout = dx;
+  double* din = dx + mw;
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < D; ++i) din[i] = kb[i];
+  }
+  node_group_sync();
+  for (int l = a.lay.n - 1; l >= 0; --l) {
+    const int in = a.lay.in[l], on = a.lay.out[l];
+    const double* W = wl + a.lay.w_off[l];
+    const double* src = l > 0 ? ac + (l - 1) * mw : ac;
+    if (lane < on) {
+      const double delta = din[lane] * dact_full(ac[l * mw + lane], a.lay.act[l]);
+      dout[lane] = delta;
+      double* gb = gs + a.lay.b_off[l] + lane;
+      *gb = *gb + delta;
+      double* gw = gs + a.lay.w_off[l] + lane;
+      if (l == 0) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) gw[on * i] = gw[on * i] + delta * a0[i];
+      } else {
+        for (int i = 0; i < in; ++i) gw[on * i] = gw[on * i] + delta * src[i];
+      }
+    }
+    node_group_sync();
+    if (lane < in) {
+      double acc = 0.0;
+      for (int j = 0; j < on; ++j) acc = acc + W[j + on * lane] * dout[j];
+      din[lane] = acc;
+    }
+    node_group_sync();
+  }
+#pragma unroll
+  for (int i = 0; i < D; ++i) g[i] = a.pre_power == 3 ? (3.0 * (x[i] * x[i])) * din[i] : din[i];
+  node_group_sync();
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void node_grad_kernel(NodeArgs a) {
+  extern __shared__ double node_lds[];
+  const int G = a.G;
+  const int grp = (int)threadIdx.x >> a.lgG, lane = (int)threadIdx.x & (G - 1);
+  double* wl = node_lds;
+  double* ex = node_lds + ((a.N + 1) & ~1) + (size_t)grp * (size_t)(4 + a.lay.n) * (size_t)a.maxw;   // node_rhs's two buffers,
+  double* dx = ex + 2 * a.maxw;                                                                       // two delta buffers,
+  double* ac = dx + 2 * a.maxw;                                                                       // the layer outputs
+  // the step's seven stage values, per group (registers hold the adjoints: 7 d of those, u, u_{n+1}, lambda and u-bar)
+  double* kl = node_lds + ((a.N + 1) & ~1) + (size_t)(256 >> a.lgG) * (size_t)(4 + a.lay.n) * (size_t)a.maxw + (size_t)grp * (7 * D);
+  {
+    const double* wg = a.w + (int64_t)blockIdx.y * a.ldw;
+    for (int i = threadIdx.x; i < a.N; i += 256) wl[i] = wg[i];
+  }
+  __syncthreads();   // the only workgroup barrier: before any group can leave
+  const int64_t p = (int64_t)blockIdx.x * (256 >> a.lgG) + grp;
+  if (p >= a.f) return;
+  const int S = a.S;
+  const int64_t tr = (int64_t)blockIdx.y * a.f + p;
+  const double* Yp = a.Y + p * (int64_t)(D * S);
+  double* gs = a.gsl + tr * (int64_t)a.N;
+  if (a.status[tr] != 0) {   // a failed trajectory: NaN in every component
+    for (int i = lane; i < a.N; i += G) gs[i] = __longlong_as_double(0x7ff8000000000000LL);
+    return;
+  }
+  int nst = a.nacc[tr];
+  nst = nst < a.max_steps ? nst : a.max_steps;   // (the record's size, whatever the count says)
+  const double* rc = a.rec + tr * (int64_t)a.max_steps * (int64_t)(D + 2);
+  const double tend = a.ts[S - 1];
+
+  double u[D], un[D], lam[D], ub[D], kb[7][D], g[D], arg[D];
+#pragma unroll
+  for (int i = 0; i < D; ++i) lam[i] = 0.0;
+  auto stage = [&](int st, const double (&x)[D]) {   // k_{st+1} = f(x), left in the group's LDS slice
+    node_rhs<D>(a, wl, ex, lane, x, g);
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < D; ++i) kl[st * D + i] = g[i];
+    }
+    node_group_sync();
+  };
+  int s = S - 1;
+  for (int n = nst - 1; n >= 0; --n) {
+    const double* r = rc + (int64_t)n * (D + 2);
+    const double t = r[0], hs = r[1];
+    const double tn = n + 1 < nst ? r[D + 2] : tend;
+#pragma unroll
+    for (int i = 0; i < D; ++i) u[i] = r[2 + i];
+    stage(0, u);
+#pragma unroll
+    for (int st = 1; st < 6; ++st) {
+#pragma unroll
+      for (int i = 0; i < D; ++i) arg[i] = u[i] + hs * node_comb_lds<D, 6>(NODE_A[st], kl, st, i);
+      stage(st, arg);
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i) un[i] = u[i] + hs * node_comb_lds<D, 6>(NODE_A[6], kl, 6, i);
+    stage(6, un);
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      ub[i] = 0.0;
+#pragma unroll
+      for (int j = 0; j < 7; ++j) kb[j][i] = 0.0;
+    }
+    while (s >= 0) {   // 1. the saves of the step, descending (a save at t0 belongs to no step)
+      const double tss = a.ts[s];
+      if (!(tss > t)) break;
+      if (tss == tn) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) lam[i] = lam[i] + -2.0 * (un[i] - Yp[(int64_t)i * S + s]);
+      } else {
+        const double th = (tss - t) / hs, th2 = th * th;
+        const double bw[7] = {NODE_B1[0] * th * (th - NODE_B1[1]) * (th2 - NODE_B1[2] * th + NODE_B1[3]),
+                              NODE_B2[0] * th2 * (th2 - NODE_B2[1] * th + NODE_B2[2]),
+                              NODE_B3[0] * th2 * (th2 - NODE_B3[1] * th + NODE_B3[2]),
+                              NODE_B4[0] * (th - NODE_B4[1]) * (th - NODE_B4[2]) * th2,
+                              NODE_B5[0] * (th - NODE_B5[1]) * (th - NODE_B5[2]) * th2,
+                              NODE_B6[0] * (th - NODE_B6[1]) * (th - NODE_B6[2]) * th2,
+                              NODE_B7[0] * (th - NODE_B7[1]) * (th - NODE_B7[2]) * th2};
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+          const double us = u[i] + hs * node_comb_lds<D, 7>(bw, kl, 7, i);
+          const double res = -2.0 * (us - Yp[(int64_t)i * S + s]);
+          ub[i] = ub[i] + res;
+#pragma unroll
+          for (int j = 0; j < 7; ++j) kb[j][i] = kb[j][i] + (hs * bw[j]) * res;
+        }
+      }
+      s -= 1;
+    }
+    node_vjp<D>(a, wl, ac, dx, lane, un, kb[6], g, gs);   // 2. k_7 = f(u_{n+1})
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      lam[i] = lam[i] + g[i];
+      ub[i] = ub[i] + lam[i];   // 3. u_{n+1} = u_n + hs sum_j a_7j k_j
+#pragma unroll
+      for (int j = 0; j < 6; ++j) kb[j][i] = kb[j][i] + (hs * NODE_A[6][j]) * lam[i];
+    }
+#pragma unroll
+    for (int st = 5; st >= 1; --st) {   // 4. the stages 6 .. 2
+#pragma unroll
+      for (int i = 0; i < D; ++i) arg[i] = u[i] + hs * node_comb_lds<D, 6>(NODE_A[st], kl, st, i);
+      node_vjp<D>(a, wl, ac, dx, lane, arg, kb[st], g, gs);
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        ub[i] = ub[i] + g[i];
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+          if (j < st) kb[j][i] = kb[j][i] + (hs * NODE_A[st][j]) * g[i];
+      }
+    }
+    node_vjp<D>(a, wl, ac, dx, lane, u, kb[0], g, gs);   // 5. k_1 = f(u_n)
+#pragma unroll
+    for (int i = 0; i < D; ++i) lam[i] = ub[i] + g[i];   // 6.
+  }
+}
+
+// gw[:, c] = sum_p slice_p in ascending p from 0.0, one thread per element; thread 0 of the chain's first block forms lp[c] from
+// the chain's sums exactly as the host does (lp_from_sums with the NeuralODE constants)
+__global__ __launch_bounds__(256) void node_grad_sum_kernel(const double* __restrict__ gsl, int64_t f, int64_t N, double* __restrict__ gw,
+                                                             int64_t ldg, const double* __restrict__ sse, const double* __restrict__ wsq,
+                                                             double* __restrict__ lp) {
+  const int c = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) {
+    double v = 0.0 - (sse[c] / 0.5) / 2.0;
+    v += 0.0 - (wsq[c] / 0.5) / 2.0;
+    lp[c] = v;
+  }
+  if (i >= N) return;
+  const double* v = gsl + (int64_t)c * f * N + i;
+  double acc = 0.0;
+  for (int64_t p = 0; p < f; ++p) acc = acc + v[p * N];
+  gw[(int64_t)c * ldg + i] = acc;
+}
+
+size_t node_grad_lds_bytes(const NodeArgs& a) {
+  return ((size_t)((a.N + 1) & ~1) + (size_t)(256 >> a.lgG) * ((size_t)(4 + a.lay.n) * (size_t)a.maxw + (size_t)7 * a.d)) * sizeof(double);
+}
+
+template <int D>
+static hipError_t node_grad_launch_d(hipStream_t st, const NodeArgs& a, dim3 grid, size_t lds) {
+  static LdsOptIn opt;
+  if (lds > (size_t)48 * 1024) opt.ensure(reinterpret_cast<const void*>(&node_grad_kernel<D>), lds);
+  hipLaunchKernelGGL(node_grad_kernel<D>, grid, dim3(256), lds, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_node_grad(hipStream_t st, const NodeArgs& a, int nchains) {
+  if (!a.rec || !a.gsl || !a.nacc || !a.status || !a.Y || a.maxw > 64) return hipErrorInvalidValue;
+  const int gpb = 256 >> a.lgG;
+  const dim3 grid((unsigned)((a.f + gpb - 1) / gpb), (unsigned)nchains);
+  const size_t lds = node_grad_lds_bytes(a);
+  switch (a.d) {
+    case 1: return node_grad_launch_d<1>(st, a, grid, lds);
+    case 2: return node_grad_launch_d<2>(st, a, grid, lds);
+    case 3: return node_grad_launch_d<3>(st, a, grid, lds);
+    case 4: return node_grad_launch_d<4>(st, a, grid, lds);
+    case 5: return node_grad_launch_d<5>(st, a, grid, lds);
+    case 6: return node_grad_launch_d<6>(st, a, grid, lds);
+    case 7: return node_grad_launch_d<7>(st, a, grid, lds);
+    case 8: return node_grad_launch_d<8>(st, a, grid, lds);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+void launch_node_grad_sum(hipStream_t st, const double* gsl, int64_t f, int64_t N, double* gw, int64_t ldg, const double* sse,
+                          const double* wsq, double* lp, int nchains) {
+  hipLaunchKernelGGL(node_grad_sum_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)nchains), dim3(256), 0, st, gsl, f, N, gw, ldg,
+                     sse, wsq, lp);
+}
+
 size_t node_lds_bytes(const NodeArgs& a) {
   return ((size_t)((a.N + 1) & ~1) + (size_t)(256 >> a.lgG) * 2 * (size_t)a.maxw) * sizeof(double);
 }
 
 template <int D>
 static hipError_t node_launch_d(hipStream_t st, const NodeArgs& a, dim3 grid, size_t lds) {
-  static LdsOptIn opt;
-  if (lds > (size_t)48 * 1024) opt.ensure(reinterpret_cast<const void*>(&node_solve_kernel<D>), lds);
-  hipLaunchKernelGGL(node_solve_kernel<D>, grid, dim3(256), lds, st, a);
+  static LdsOptIn opt, opt_rec;
+  if (a.rec) {
+    if (lds > (size_t)48 * 1024) opt_rec.ensure(reinterpret_cast<const void*>(&node_solve_kernel<D, true>), lds);
+    hipLaunchKernelGGL((node_solve_kernel<D, true>), grid, dim3(256), lds, st, a);
+  } else {
+    if (lds > (size_t)48 * 1024) opt.ensure(reinterpret_cast<const void*>(&node_solve_kernel<D, false>), lds);
+    hipLaunchKernelGGL((node_solve_kernel<D, false>), grid, dim3(256), lds, st, a);
+  }
   return hipGetLastError();
 }
 

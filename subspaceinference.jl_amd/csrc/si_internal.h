@@ -323,6 +323,11 @@ struct NodeArgs {
   int32_t d = 0, S = 0, N = 0, G = 1, lgG = 0, maxw = 1;
   double t0 = 0.0, reltol = 0.0, abstol = 0.0, dt = 0.0;
   int32_t adaptive = 1, max_steps = 0, pre_power = 1;
+  // the gradient through the solver (si_node_set_grad): the forward with record writes (t_n, hs_n, u_n) of accepted step n of
+  // trajectory tr at rec + (tr * max_steps + n) * (d + 2); the reverse kernel reads them, with nacc / status, and adds into the
+  // trajectory's own slice gsl + tr * N
+  double* rec = nullptr;
+  double* gsl = nullptr;
 };
 struct NodeState {
   bool on = false;
@@ -331,9 +336,18 @@ struct NodeState {
   DevBuf<double> ts;               // S
   DevBuf<double> ssep;             // f x slots: the per-trajectory sums of one pass of launches
   DevBuf<double> uout;             // d*S x f x slots: the saved states, only on request (si_forward)
+  // si_node_set_grad(1): the value-and-gradient route's workspace for g_cap chains per pass of launches (capi_node.hip)
+  bool grad = false;
+  int g_fit = 0, g_cap = 0;        // chains per pass the budget allows / the workspace holds
+  DevBuf<double> g_z, g_w, g_ssep, g_sse, g_wsq, g_wsqpart, g_rec, g_slices, g_gw, g_lp, g_gz;
+  DevBuf<int32_t> g_cnt;           // nacc, nrej, status: f x g_cap each
 };
-hipError_t launch_node_solve(hipStream_t st, const NodeArgs& a, int nchains);
+hipError_t launch_node_solve(hipStream_t st, const NodeArgs& a, int nchains);   // (a.rec set: the forward with record)
 void launch_node_sum(hipStream_t st, const double* sse_p, int64_t f, double* sse, int nchains);
+hipError_t launch_node_grad(hipStream_t st, const NodeArgs& a, int nchains);    // the reverse kernel: a.rec, a.nacc, a.status -> a.gsl
+// gw[:, c] = the chain's f slices added in ascending p from 0.0; lp[c] from the chain's sums as the host forms it
+void launch_node_grad_sum(hipStream_t st, const double* gsl, int64_t f, int64_t N, double* gw, int64_t ldg, const double* sse,
+                          const double* wsq, double* lp, int nchains);
 
 // ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops
 struct InferState {

@@ -177,9 +177,19 @@ class NeuralODE:
     takes it (src/libs.jl:36-54): `dudt` is a Chain of Dense layers d -> ... -> d whose first element may be `cube`; `saveat` is
     the vector of save times (or a step: tspan[0], tspan[0] + saveat, ... up to tspan[1]).  Tsit5 is the only solver.  The
     definition of its solve is node.py; `adaptive=False` takes fixed steps of `dt`.  Calling it solves on the host (node.solve):
-    (d, f) initial states -> (d*S, f), row i*S + s being state i at save time s."""
+    (d, f) initial states -> (d*S, f), row i*S + s being state i at save time s.
 
-    def __init__(self, dudt, tspan, saveat, reltol=1e-3, abstol=1e-6, adaptive=True, dt=0.0, max_steps=100000):
+    `sensealg` chooses the gradient through the solver that alg = :mala / :hmc / :nuts / :advi need: None (default) has none and
+    those samplers raise; "discrete_adjoint" differentiates the integration with its accepted step sequence frozen
+    (node.logdensity_grad is the definition; si_node_set_grad on the device).  That is not DiffEqFlux's default of ForwardDiff
+    through the adaptive solver, where the partials also move the steps; the two agree to the order of the tolerances."""
+
+    SENSEALGS = (None, "discrete_adjoint")
+
+    def __init__(self, dudt, tspan, saveat, reltol=1e-3, abstol=1e-6, adaptive=True, dt=0.0, max_steps=100000, sensealg=None):
+        if sensealg not in self.SENSEALGS:
+            raise SubspaceError("sensealg must be None or \"discrete_adjoint\" (got %r)" % (sensealg,))
+        self.sensealg = sensealg
         if not isinstance(dudt, Chain) or not dudt.layers:
             raise SubspaceError("Error: the right-hand side of a NeuralODE must be a Chain")
         layers = list(dudt.layers)

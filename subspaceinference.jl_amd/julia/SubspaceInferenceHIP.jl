@@ -561,6 +561,22 @@ function node_solve(ctx::Ctx, Z::Matrix{Float64})
         (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}), ctx.h, Z, C, U, sse, na, nr, st))
     return U, sse, na, nr, st
 end
+# The gradient through the solver (off after every infer_setup_node!): node_set_grad!(ctx) lets logdensity_grad and the
+# gradient-driven device samplers through.  What they differentiate is the discrete adjoint of the integration with its accepted
+# steps frozen -- not ForwardDiff through the adaptive solver, which also moves the steps.  node_grad is the audit read-back.
+node_set_grad!(ctx::Ctx, on::Bool = true) = check(ctx, ccall((:si_node_set_grad, LIB), Int32, (Ptr{Cvoid}, Int32), ctx.h, on ? 1 : 0))
+function node_grad_info(ctx::Ctx)
+    on, cpp = Ref{Int32}(0), Ref{Int32}(0)
+    check(ctx, ccall((:si_node_grad_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}), ctx.h, on, cpp))
+    return on[] != 0, Int(cpp[])
+end
+function node_grad(ctx::Ctx, Z::Matrix{Float64}, N::Integer)
+    M, C = size(Z)
+    lp, gw, gz = Vector{Float64}(undef, C), Matrix{Float64}(undef, N, C), Matrix{Float64}(undef, M, C)
+    GC.@preserve Z lp gw gz check(ctx, ccall((:si_node_grad, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ctx.h, Z, C, lp, gw, gz))
+    return lp, gw, gz
+end
 function node_tableau()
     out = Vector{Float64}(undef, 57)
     ccall((:si_node_tableau, LIB), Int32, (Ptr{Float64},), out) == 0 || throw("si_node_tableau failed")

@@ -205,9 +205,22 @@ class Solution:
     nreject: np.ndarray    # f
     status: np.ndarray     # f: 0 done, 1 max_steps reached, 2 non-finite state or error / t + h == t
     min_margin: float      # the smallest |err - 1| over all accept / reject decisions (inf in fixed-step mode)
+    record: list = None    # solve(record=True): per trajectory its accepted steps (t_n, hs_n, h_n, u_n), see Steps
 
 
-def solve(table, w, u0, ts, opts, y=None, nudge=None):
+@dataclass
+class Steps:
+    """the accepted steps of one trajectory, the shortened last step included: step n starts at t[n] in u[:, n] and is hs[n] long.
+    It ends at t[n + 1], the last one at tend.  h[n] is the controller's step before it was shortened to hs[n] (the device does
+    not record it: only a mutant of tests/node_grad_cases.py reads it)."""
+    t: np.ndarray
+    hs: np.ndarray
+    h: np.ndarray
+    u: np.ndarray          # d x n
+    status: int = 0        # the trajectory's status: the gradient is defined for 0 alone
+
+
+def solve(table, w, u0, ts, opts, y=None, nudge=None, record=False):
     """all columns of u0 (d x f) through the right-hand side with the flat weights w"""
     nudge = nudge if nudge is not None else _same
     w = np.asarray(w, dtype=np.float64).reshape(-1)
@@ -228,6 +241,7 @@ def solve(table, w, u0, ts, opts, y=None, nudge=None):
     snext = np.zeros(f, np.int64)
     min_margin = np.inf
     rows = np.arange(d) * S
+    rec = [([], [], [], []) for _ in range(f)] if record else None
 
     def fn(u):
         return rhs(table, w, u, opts.pre_power, nudge)
@@ -306,6 +320,9 @@ def solve(table, w, u0, ts, opts, y=None, nudge=None):
                     h[p] = hnew[j]
                     continue
                 nacc[p] += 1
+                if rec is not None:
+                    for lst, v in zip(rec[p], (tt[j], hs[j], hh[j], uu[:, j].copy())):
+                        lst.append(v)
                 while snext[p] < S and ts[snext[p]] <= tn[j]:
                     s = snext[p]
                     if ts[s] == tn[j]:
@@ -321,7 +338,10 @@ def solve(table, w, u0, ts, opts, y=None, nudge=None):
     sse[status != 0] = np.inf
     if y is None:
         sse[status == 0] = 0.0
-    return Solution(U, sse, nacc, nrej, status, min_margin)
+    if rec is not None:
+        rec = [Steps(np.array(r[0]), np.array(r[1]), np.array(r[2]), np.array(r[3]).reshape(-1, d).T, int(status[p]))
+               for p, r in enumerate(rec)]
+    return Solution(U, sse, nacc, nrej, status, min_margin, rec)
 
 
 def sum_squares(w):
@@ -360,3 +380,230 @@ def logdensity(table, w, u0, y, ts, opts, nudge=None):
     """lp = -sum_p ||sol_p - Y_p||^2 - ||w||^2 (src/space_inference.jl:96-101; sigma_m and sigma_p are unused there too)"""
     sol = solve(table, w, u0, ts, opts, y=y, nudge=nudge)
     return (0.0 - (sse_total(sol.sse) / 0.5) / 2.0) + (0.0 - (sum_squares(w) / 0.5) / 2.0)
+
+
+# ---- the gradient through the solver: the discrete adjoint of the integration above with its accepted steps frozen -----------------
+# For a trajectory that ended with status 0 take its accepted steps (t_n, hs_n, u_n), the shortened last step included.  d lp / d W
+# is the exact derivative of W -> -sum_s ||us_s - y_s||^2 built from those steps with hs_n and every theta_s = (ts_s - t_n) / hs_n
+# held constant: rejected steps, the starting-step evaluations and the controller do not enter.  This is NOT what ForwardDiff gives
+# through OrdinaryDiffEq in the reference, where the partials enter the error norm and move the steps [upstream, from memory,
+# unverifiable offline]; the two agree to the order of the tolerance.  As everywhere in this file every product and sum is rounded on
+# its own and the written order is the definition (csrc/kernels_node.hip: node_grad_kernel repeats it).
+GRAD_MAX_WIDTH = 64        # si_node_set_grad: every lane of a group owns one unit per layer
+MUTANTS = ("interp-k7-dropped", "k1-dropped", "h-for-hs", "theta-of-wrong-step", "cube-derivative-missing", "end-save-twice")
+
+
+def dact(h, kind, nudge=_same):
+    """act'(x) through the output h = act(x), as the Chain reverse sweep defines it (csrc/kernels_gemm.h: dact_full)"""
+    if kind == flux.identity:
+        return np.ones_like(h)
+    if kind == flux.relu:
+        return np.where(h > 0.0, 1.0, 0.0)
+    if kind == flux.tanh:
+        return 1.0 - h * h
+    if kind == flux.sigmoid:
+        return h * (1.0 - h)
+    if kind == flux.leakyrelu:
+        return np.where(h > 0.0, 1.0, 0.01)
+    if kind == flux.elu:
+        return np.where(h >= 0.0, 1.0, h + 1.0)
+    if kind == flux.softplus:
+        return 1.0 - nudge(np.exp(-h))
+    if kind == flux.selu:
+        return np.where(h > 0.0, flux._SELU_L, h + flux._SELU_L * flux._SELU_A)
+    raise SubspaceError("Error: activation %r is not available" % (kind,))
+
+
+def _step_end(st, n, tend):
+    return st.t[n + 1] if n + 1 < st.t.size else tend
+
+
+def _stages(fn, u, hs):
+    """the seven stage values of the step from u (d x 1) and its end state, as `solve` forms them; k_1 = f(u) is the FSAL value"""
+    ks = [fn(u)]
+    for i in range(1, 6):
+        ks.append(fn(u + hs * _comb(A[i], ks)))
+    un = u + hs * _comb(A[6], ks)
+    ks.append(fn(un))
+    return ks, un
+
+
+def replay(table, w, u0, ts, opts, record, y=None, nudge=None):
+    """the arithmetic of `solve` on the given steps: U and sse of `solve(..., record=True)` again, bit for bit.  Only t_n and hs_n are read:
+    the state is carried from u0, so that this is the function of W whose derivative grad_w is (its u_n are the recorded ones
+    at the recorded W).  A trajectory whose record is that of a failed integration keeps the saves of its steps and sse = +Inf."""
+    nudge = nudge if nudge is not None else _same
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    u0 = np.asarray(u0, dtype=np.float64)
+    u0 = u0.reshape(u0.shape[0], -1)
+    ts = np.asarray(ts, dtype=np.float64).reshape(-1)
+    d, f = u0.shape
+    S = ts.size
+    check(table, w.size, d, ts, opts)
+    if y is not None:
+        y = np.asarray(y, dtype=np.float64).reshape(d * S, f)
+    tend = ts[-1]
+    U = np.full((d * S, f), np.nan)
+    sse = np.zeros(f)
+    rows = np.arange(d) * S
+
+    def fn(u):
+        return rhs(table, w, u, opts.pre_power, nudge)
+
+    def save(p, s, us):
+        U[rows + s, p] = us
+        if y is not None:
+            for i in range(d):
+                r = us[i] - y[i * S + s, p]
+                sse[p] = sse[p] + r * r
+
+    with np.errstate(all="ignore"):
+        for p in range(f):
+            st = record[p]
+            s = 0
+            if ts[0] == opts.t0:
+                save(p, 0, u0[:, p])
+                s = 1
+            u = u0[:, p:p + 1]
+            for n in range(st.t.size):
+                t, hs = st.t[n], st.hs[n]
+                ks, un = _stages(fn, u, hs)
+                tn = _step_end(st, n, tend)
+                while s < S and ts[s] <= tn:
+                    if ts[s] == tn:
+                        us = un[:, 0]
+                    else:
+                        bw = interp_weights((ts[s] - t) / hs)
+                        us = (u + hs * _comb(bw, ks))[:, 0]
+                    save(p, s, us)
+                    s += 1
+                u = un
+            if st.status != 0:
+                sse[p] = np.inf
+    if y is None:
+        sse[np.isfinite(sse)] = 0.0
+    return U, sse
+
+
+def _vjp(table, w, x, kbar, pre_power, gw, nudge, no_cube=False):
+    """J_u' kbar of f at x (both d x 1); J_W' kbar is added into gw, one contribution per weight element"""
+    a = (x * x) * x if pre_power == 3 else x
+    rows = [tuple(int(v) for v in row[:5]) for row in table]
+    outs = [a]
+    for fin, fout, kind, w_off, b_off in rows:
+        W = w[w_off:w_off + fin * fout].reshape((fout, fin), order="F")
+        acc = np.zeros((fout, 1))
+        for i in range(fin):
+            acc = acc + W[:, i:i + 1] * a[i:i + 1]
+        acc = acc + w[b_off:b_off + fout][:, None]
+        a = act(acc, kind, nudge)
+        outs.append(a)
+    g = kbar
+    for l in range(len(rows) - 1, -1, -1):
+        fin, fout, kind, w_off, b_off = rows[l]
+        W = w[w_off:w_off + fin * fout].reshape((fout, fin), order="F")
+        delta = g * dact(outs[l + 1], kind, nudge)
+        gw[b_off:b_off + fout] = gw[b_off:b_off + fout] + delta[:, 0]
+        for i in range(fin):
+            gw[w_off + fout * i:w_off + fout * (i + 1)] = gw[w_off + fout * i:w_off + fout * (i + 1)] + delta[:, 0] * outs[l][i, 0]
+        g = np.zeros((fin, 1))
+        for j in range(fout):                                  # the transposed product: the output index ascending, from 0.0
+            g = g + W[j:j + 1, :].T * delta[j:j + 1]
+    if pre_power == 3 and not no_cube:
+        g = (3.0 * (x * x)) * g
+    return g
+
+
+def grad_slices(table, w, u0, ts, opts, y, record, nudge=None, mutant=None):
+    """N x f: column p is d(-sse_p) / dW of trajectory p over its recorded steps, contributions added from 0.0 in sweep order (steps
+    descending; within a step k_7, then the stages 6 .. 1).  A trajectory whose record carries status != 0 (a failed
+    integration) gives NaN.  `mutant` (one of MUTANTS) breaks one rule, for the tests' catalogue."""
+    nudge = nudge if nudge is not None else _same
+    if mutant is not None and mutant not in MUTANTS:
+        raise SubspaceError("unknown mutant %r" % (mutant,))
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    u0 = np.asarray(u0, dtype=np.float64)
+    u0 = u0.reshape(u0.shape[0], -1)
+    ts = np.asarray(ts, dtype=np.float64).reshape(-1)
+    d, f = u0.shape
+    S = ts.size
+    check(table, w.size, d, ts, opts)
+    y = np.asarray(y, dtype=np.float64).reshape(d * S, f)
+    tend = ts[-1]
+    out = np.zeros((w.size, f))
+
+    def fn(u):
+        return rhs(table, w, u, opts.pre_power, nudge)
+
+    def vjp(x, kbar, gw):
+        return _vjp(table, w, x, kbar, opts.pre_power, gw, nudge, no_cube=mutant == "cube-derivative-missing")
+
+    with np.errstate(all="ignore"):
+        for p in range(f):
+            st = record[p]
+            nsteps = st.t.size
+            if st.status != 0:
+                out[:, p] = np.nan
+                continue
+            gw = out[:, p]
+            lam = np.zeros((d, 1))
+            s = S - 1
+            for n in range(nsteps - 1, -1, -1):
+                t, hs, u = st.t[n], st.hs[n], st.u[:, n:n + 1]
+                if mutant == "h-for-hs":
+                    hs = st.h[n]
+                ks, un = _stages(fn, u, hs)
+                tn = _step_end(st, n, tend)
+                ub = np.zeros((d, 1))
+                kb = [np.zeros((d, 1)) for _ in range(7)]
+                while s >= 0 and ts[s] > t:                    # 1. the saves of the step, descending
+                    ys = y[np.arange(d) * S + s, p][:, None]
+                    if ts[s] == tn:
+                        r = -2.0 * (un - ys)
+                        lam = lam + r
+                        if mutant == "end-save-twice":
+                            lam = lam + r
+                    else:
+                        bw = interp_weights((ts[s] - t) / hs)
+                        us = u + hs * _comb(bw, ks)
+                        if mutant == "theta-of-wrong-step":    # (measured from the start of step n + 1)
+                            bw = interp_weights((ts[s] - tn) / hs)
+                        r = -2.0 * (us - ys)
+                        ub = ub + r
+                        for j in range(6 if mutant == "interp-k7-dropped" else 7):
+                            kb[j] = kb[j] + (hs * bw[j]) * r
+                    s -= 1
+                lam = lam + vjp(un, kb[6], gw)                 # 2. k_7 = f(u_{n+1})
+                ub = ub + lam                                  # 3. u_{n+1} = u_n + hs sum_j a_7j k_j
+                for j in range(6):
+                    kb[j] = kb[j] + (hs * A[6][j]) * lam
+                for i in range(5, 0, -1):                      # 4. the stages 6 .. 2
+                    g = vjp(u + hs * _comb(A[i], ks), kb[i], gw)
+                    ub = ub + g
+                    for j in range(i):
+                        kb[j] = kb[j] + (hs * A[i][j]) * g
+                if mutant != "k1-dropped":                     # 5. k_1 = f(u_n)
+                    ub = ub + vjp(u, kb[0], gw)
+                lam = ub                                       # 6.
+    return out
+
+
+def grad_w(table, w, u0, ts, opts, y, record, nudge=None, mutant=None):
+    """d(-sum_p sse_p) / dW: the trajectories' slices added in ascending p, from 0.0"""
+    sl = grad_slices(table, w, u0, ts, opts, y, record, nudge=nudge, mutant=mutant)
+    acc = np.zeros(sl.shape[0])
+    with np.errstate(all="ignore"):
+        for p in range(sl.shape[1]):
+            acc = acc + sl[:, p]
+    return acc
+
+
+def logdensity_grad(table, w, u0, y, ts, opts, nudge=None):
+    """(lp, d lp / dW): `logdensity`'s value; grad_w over the steps of that very integration, then -2 W (the prior term's gradient,
+    g - w * 2 as launch_prior_grad forms it).  A failed trajectory: lp = -Inf and NaN in every component."""
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    sol = solve(table, w, u0, ts, opts, y=y, nudge=nudge, record=True)
+    lp = (0.0 - (sse_total(sol.sse) / 0.5) / 2.0) + (0.0 - (sum_squares(w) / 0.5) / 2.0)
+    if np.any(sol.status != 0):
+        return lp, np.full(w.size, np.nan)
+    return lp, grad_w(table, w, u0, ts, opts, y, sol.record, nudge=nudge) - w * 2.0

@@ -287,6 +287,10 @@ int32_t si_infer_set_decoder(si_ctx* ctx, const si_layer* dec_layers, int32_t D,
 int32_t si_infer_decoder_info(si_ctx* ctx, int32_t* D_out, int32_t* H_out, int32_t* storage_dtype_out);
 /* Y_out[:, c] = decoder(Z[:, c]) alone (N x C, column-major), without W_swa; needs a decoder */
 int32_t si_decode(si_ctx* ctx, const double* Z /* M x C */, int64_t C, double* Y_out /* N x C */);
+/* gz_out = J_decoder(z)' gy at one point: the decoder's reverse kernels alone, launch for launch those si_logdensity_grad runs
+ * around the model's sweep (the audit read-back of tests/test_gpu_decoder_reverse.py).  SI_ERR_STATE: before a set-up, with no
+ * decoder set, or while a step-wise RWMH session is open (the buffers are shared). */
+int32_t si_decode_vjp(si_ctx* ctx, const double* z /* M */, const double* gy /* N */, double* gz_out /* M */);
 
 /* ---- NeuralODE models (reference src/space_inference.jl:96-101, model_re at src/libs.jl:36-54; docs/src/node_example.md) ----------
  * The model is du/dt = dudt(u; w): a Dense chain d -> ... -> d (optionally behind the elementwise cube u -> (u*u)*u, the tutorial's

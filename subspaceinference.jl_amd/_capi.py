@@ -97,6 +97,7 @@ SIGNATURES = {
     "si_infer_set_decoder": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_void_p, c_int32]),
     "si_infer_decoder_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "si_decode": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "si_decode_vjp": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "si_infer_setup_node": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_int32, c_int32, c_int64, c_void_p, c_void_p]),
     "si_node_solve": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -659,6 +660,16 @@ class Context:
         y = np.empty((self._ni, z.shape[1]), dtype=np.float64, order="F")
         self._check(self.lib.si_decode(self.h, _ptr(z), z.shape[1], _ptr(y)))
         return y
+
+    def decode_vjp(self, z, gy):
+        """J_decoder(z)' gy at the point z (M) for the cotangent gy (N): the M-vector (si_decode_vjp).  It runs the decoder's
+        forward with its outputs kept and then the reverse kernels, launch for launch as logdensity_grad does."""
+        z, gy = _f64(z).reshape(-1), _f64(gy).reshape(-1)
+        if z.size != self._m or gy.size != self._ni:
+            raise SubspaceError("DimensionMismatch: z has %d entries (M = %d), gy has %d (N = %d)" % (z.size, self._m, gy.size, self._ni))
+        gz = np.empty(self._m, dtype=np.float64)
+        self._check(self.lib.si_decode_vjp(self.h, _ptr(z), _ptr(gy), _ptr(gz)))
+        return gz
 
     def infer_setup_node(self, table, n, m, w_swa, p, u0, y, ts, t0=0.0, reltol=1e-3, abstol=1e-6, dt=0.0, adaptive=True,
                          max_steps=100000, pre_power=1):

@@ -617,6 +617,30 @@ int32_t si_decode(si_ctx* ctx, const double* Z, int64_t C, double* Y_out) {
   return SI_OK;
 }
 
+// gz = J_decoder(z)' gy at one point, through the seam alone: form_weights(.., keep_y = true) and pull_back_to_z are, launch for
+// launch, what si_logdensity_grad runs around its model sweep; d_zprop, d_w, d_gw and d_gz are the buffers it uses.
+int32_t si_decode_vjp(si_ctx* ctx, const double* z, const double* gy, double* gz_out) {
+  CHECK_CTX(ctx);
+  if (!z || !gy || !gz_out) return fail(ctx, SI_ERR_INVALID, "si_decode_vjp: bad argument");
+  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_decode_vjp: call si_infer_setup first");
+  if (!ctx->dec.on) return fail(ctx, SI_ERR_STATE, "si_decode_vjp: no decoder is set (si_infer_set_decoder)");
+  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_decode_vjp: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
+  BIND(ctx);
+  int32_t rc = ensure_chains(ctx, 1);
+  if (rc != SI_OK) return rc;
+  const int64_t N = ctx->iN;
+  const int32_t M = ctx->iM;
+  if (!ctx->d_gw.reserve((size_t)pad_ld(N)) || !ctx->d_gz.reserve((size_t)M)) return fail(ctx, SI_ERR_NOMEM, "si_decode_vjp: device allocation failed");
+  SI_HIP(ctx, hipMemcpyAsync(ctx->d_zprop, z, (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(ctx->d_gw, gy, (size_t)N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = form_weights(ctx, ctx->d_zprop, 1, ctx->d_w, pad_ld(N), nullptr, /*keep_y=*/true)) != SI_OK) return rc;
+  pull_back_to_z(ctx, ctx->d_gw, ctx->d_gz);
+  SI_HIP(ctx, hipGetLastError());
+  SI_HIP(ctx, hipMemcpyAsync(gz_out, ctx->d_gz, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SI_OK;
+}
+
 int32_t si_logdensity(si_ctx* ctx, const double* Z, int32_t C, double* lp_out) {
   CHECK_CTX(ctx);
   if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_logdensity: call si_infer_setup first");

@@ -519,6 +519,11 @@ function decode(ctx::Ctx, Z::Matrix{Float64}, N)                     # decoder(z
     GC.@preserve Z Y check(ctx, ccall((:si_decode, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}), ctx.h, Z, size(Z, 2), Y))
     return Y
 end
+function decode_vjp(ctx::Ctx, z::Vector{Float64}, gy::Vector{Float64})   # J_decoder(z)' gy: the decoder's reverse kernels alone
+    gz = Vector{Float64}(undef, length(z))
+    GC.@preserve z gy gz check(ctx, ccall((:si_decode_vjp, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ctx.h, z, gy, gz))
+    return gz
+end
 
 # ---- NeuralODE models (src/space_inference.jl:96-101; model_re at src/libs.jl:36-54) --------------------------------------------
 # infer_setup_node!(ctx, dudt, W_swa, P, U0, Y, ts; ...) in place of the Chain set-up: dudt is the Dense chain d -> ... -> d of the

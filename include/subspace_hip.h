@@ -606,6 +606,38 @@ int32_t si_train_grad_ptr(si_ctx* ctx, double** grad_dev_out, int64_t* n_out);
 int32_t si_train_grad_get(si_ctx* ctx, double* g_out /* N */);
 int32_t si_train_grad_set(si_ctx* ctx, const double* g_in /* N */);
 int32_t si_train_apply(si_ctx* ctx);
+/* ---- the training step of a NeuralODE (docs/src/node_example.md:272-285) -------------------------------------------------------
+ * In place of si_train_setup for a NeuralODE right-hand side (si_infer_setup_node's layers, data layout, `ts` and si_node_opts):
+ * a step minimises, over the batch's trajectories,
+ *     loss = sum_{p in batch} ||sol_p(W) - Y_p||^2 + ||W||^2 / penalty_div            (penalty_div = 0: no penalty)
+ * -- for a batch of one column the tutorial's L1(m, x, y) = sum(abs2, m(vec(x)) .- reshape(y[:,1], :,2)') + sum(sqnorm, ps)/100;
+ * several columns sum over them (an extension).  The gradient is the DISCRETE ADJOINT of si_node_set_grad (accepted steps frozen;
+ * node.py: train_value_and_grad is the definition) plus (W * 2) / penalty_div -- not Zygote's through DiffEqFlux's NeuralODE, a
+ * continuous adjoint by default [upstream, from memory, unverifiable offline]: the two agree to the order of the tolerances, not
+ * to rounding.  ||W||^2 is summed over the flat vector, not array by array as `sum(sqnorm, params)`: only the printed loss
+ * depends on that order.  Weights and optimiser state are Float32, the arithmetic Float64, as for Chains.
+ * After it si_train_step, si_train_grad + si_train_apply (nb_total == nb; sse_local_out receives the loss), si_train_grad_get
+ * (also after a si_train_step: the step's gradient stays in the buffer) / _set / _ptr, si_train_push, si_train_get_weights, si_train_get_opt_state and si_train_compute_dtype (SI_F64) work with the
+ * meanings above; loss_out is the loss of the batch before the update.  si_train_step_dp and si_train_allreduce_grad return
+ * SI_ERR_INVALID ("not available for NeuralODE training").
+ * Refused (SI_ERR_INVALID naming the limit): what si_infer_setup_node refuses, a layer wider than 64, and a step record plus
+ * gradient slices -- batch_max * (max_steps * (d + 2) + N) doubles -- over the 2 GiB workspace budget ("lower max_steps or the
+ * batch size").
+ * A FAILED TRAJECTORY (status 1: max_steps reached, 2: a non-finite state) must not reach the weights: that step leaves w, m, v
+ * as they were and records its number (1-based, counted from the set-up), the trajectory's position in its batch and the status
+ * in a sticky device word; every later step of the set-up is a no-op too.  The next synchronising call (a step with loss_out,
+ * si_train_grad, si_train_get_weights, si_train_get_opt_state, si_construct_finish*, si_synchronize) returns SI_ERR_INVALID
+ * naming step, trajectory and status -- once; si_train_node_info keeps reporting it (failed_step_out -1: none).  si_train_push is
+ * unchanged: it may push the unchanged weights after a failure, the synchronising call that follows raises.  Once the failure has been returned, further steps return SI_ERR_INVALID ("set up again")
+ * and the host's beta powers are those of the last step that was taken.
+ * Profiling classes of a step: SI_K_SSE the batch gather, ||W||^2 and the zeroing of the slices; SI_K_DENSE the forward with
+ * record; SI_K_BACKWARD the reverse kernel; SI_K_RECON the tail kernel (gradient, loss, update, the Float64 copy of w).      */
+int32_t si_train_setup_node(si_ctx* ctx, const si_layer* layers, int32_t L, int64_t N, const float* w0 /* N */,
+                            const double* U0 /* d x f */, const double* Y /* d*S x f */, int32_t d, int32_t S, int64_t f,
+                            const double* ts /* S */, const void* opts /* const si_node_opts* */, int64_t batch_max,
+                            int32_t opt_kind, double eta, double p1, double p2, double penalty_div /* 0: no penalty */);
+int32_t si_train_node_info(si_ctx* ctx, int32_t* active_out, int32_t* G_out, int64_t* failed_step_out /* -1: none */,
+                           int64_t* failed_traj_out, int32_t* failed_status_out);
 
 /* ---- R1: multi-GPU behind the C ABI ------------------------------------------------------------
  * One process per GPU, one si_ctx per process, one RCCL communicator per ctx (RCCL over xGMI; bound with dlopen at the

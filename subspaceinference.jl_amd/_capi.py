@@ -151,6 +151,9 @@ SIGNATURES = {
     "si_train_grad_get": (c_int32, [c_void_p, c_void_p]),
     "si_train_grad_set": (c_int32, [c_void_p, c_void_p]),
     "si_train_apply": (c_int32, [c_void_p]),
+    "si_train_setup_node": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64,
+                                      c_void_p, c_void_p, c_int64, c_int32, c_double, c_double, c_double, c_double]),
+    "si_train_node_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), POINTER(c_int64), POINTER(c_int32)]),
     "si_comm_unique_id": (c_int32, [c_void_p]),
     "si_comm_init_rank": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),
     "si_comm_destroy": (c_int32, [c_void_p]),
@@ -537,6 +540,30 @@ class Context:
                                                SI_DTYPE_OF_DATA if compute_dtype is None else int(compute_dtype)))
         self._tn = int(n)
         self._tout = int(y.shape[0])
+
+    def train_setup_node(self, table, n, w0, u0, y, ts, batch_max, opt_kind, eta, p1=0.0, p2=0.0, penalty_div=100.0, t0=0.0,
+                         reltol=1e-3, abstol=1e-6, dt=0.0, adaptive=True, max_steps=100000, pre_power=1):
+        """si_train_setup_node, in place of train_setup, for a NeuralODE (node.train_value_and_grad is the definition of a step):
+        `table`, u0 (d x f), y (d*S x f), ts and the options as infer_setup_node takes them; penalty_div None or 0: no penalty."""
+        arr = _layer_array(table)
+        u0, y, ts = _f64(u0), _f64(y), np.ascontiguousarray(ts, dtype=np.float64).reshape(-1)
+        w0 = np.ascontiguousarray(w0, dtype=np.float32)
+        if w0.size != n or u0.ndim != 2 or y.ndim != 2 or u0.shape[1] != y.shape[1] or y.shape[0] != u0.shape[0] * ts.size:
+            raise SubspaceError("DimensionMismatch: w0 %s, U0 is %s, Y is %s, %d save times: Y must be (d*S, f)"
+                                % (w0.shape, u0.shape, y.shape, ts.size))
+        opts = SiNodeOpts(float(t0), float(reltol), float(abstol), float(dt), 1 if adaptive else 0, int(max_steps), int(pre_power))
+        self._check(self.lib.si_train_setup_node(self.h, arr, len(table), int(n), _ptr(w0), _ptr(u0), _ptr(y), u0.shape[0], ts.size,
+                                                 u0.shape[1], _ptr(ts), byref(opts), int(batch_max), int(opt_kind), float(eta), float(p1),
+                                                 float(p2), 0.0 if penalty_div is None else float(penalty_div)))
+        self._tn = int(n)
+        self._tout = int(y.shape[0])
+
+    def train_node_info(self):
+        """(active, G, failed step or -1, the failed trajectory's position in its batch or -1, its status): si_train_node_info"""
+        on, g, st = c_int32(0), c_int32(0), c_int32(0)
+        step, traj = c_int64(-1), c_int64(-1)
+        self._check(self.lib.si_train_node_info(self.h, byref(on), byref(g), byref(step), byref(traj), byref(st)))
+        return bool(on.value), int(g.value), int(step.value), int(traj.value), int(st.value)
 
     def train_compute_dtype(self):
         out = np.zeros(1, dtype=np.int32)

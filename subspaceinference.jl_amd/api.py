@@ -1,6 +1,6 @@
 """Host-side mirror of the reference's exported API for the hot path (src/SubspaceInference.jl:27-34):
 
-    subspace_construction(model, cost, data, opt; T=10, c=1, M=3, print_freq=1)        -> (W_swa, P)
+    subspace_construction(model, cost, data, opt; T=10, c=1, M=3, print_freq=1)        -> (W_swa, P)      (Chain + flux.mse, or NeuralODE + flux.node_sse)
     diffusion_subspace(model, cost, data, opt; T=10, c=1, M=3, print_freq=1)           -> (W_swa, P)
     subspace_inference(model, cost, data, opt; σ_z, σ_m, σ_p, itr, T, c, M, ...)        -> (chn, lp, W_swa)
     sub_inference(in_model, data, W_swa, P; σ_z, σ_m, σ_p, itr, M, alg, backend)        -> (chn, lp)
@@ -46,6 +46,15 @@ def subspace_construction(model, cost, data, opt, T=10, c=1, M=3, print_freq=1, 
     optimiser) and the weights are pushed in place (si_train_push) -- no weight vector crosses PCIe.  The model's
     arrays receive the trained weights at the end, like Flux's in-place `update!`.
 
+    A `flux.NeuralODE` model (docs/src/node_example.md:272-285) trains with the cost `flux.node_sse` (the tutorial's L1: the sum of
+    squared errors of the batch's trajectories plus ||W||^2 / 100) and `sensealg="discrete_adjoint"`: `data` holds the initial states
+    (d x f) and the observed trajectories (d*S x f); the device step is si_train_setup_node (the forward with record, the reverse
+    kernel and node_train_tail_kernel; node.train_value_and_grad is the definition), the host step (device_training=False, Float64
+    parameters or a used optimiser) is that definition through flux.gradient / flux.update.  The gradient is the frozen-step discrete
+    adjoint, not Zygote's through DiffEqFlux: the two agree to the order of the tolerances.  compute_dtype is "auto" or "f64" and
+    data_parallel is not offered; a trajectory that fails (max_steps, a non-finite state) leaves the weights as they were and the
+    call raises naming step, trajectory and status.  Any other cost on a NeuralODE raises, as before.
+
     init ("zeros" | "pretrained"): "zeros" is what the reference's CODE does (W_swa = zeros, :31 -- quirk Q1, the default);
     "pretrained" starts the running mean at the model's weights, as the reference's docs describe (nn_example.md:44).
 
@@ -84,7 +93,7 @@ def diffusion_subspace(model, cost, data, opt, T=10, c=1, M=3, print_freq=1, *, 
     compute) and `rescale` (the per-snapshot unit-range transform) are the points a maintainer with Julia may have to change.
     `tol` / `max_iters` steer the block subspace iteration (0: 1e-12 / 500); a spectrum it cannot separate raises.
     The other keywords are `subspace_construction`'s (a ring of `max_cols` columns and a row-sharded / data-parallel
-    construction are not offered on this route)."""
+    construction are not offered on this route).  A NeuralODE with `flux.node_sse` trains as in `subspace_construction`."""
     return _swa_construction(model, cost, data, opt, T, c, print_freq,
                              lambda cx: cx.construct_finish_diffmap(M, eps, alpha, kernel_sign, rescale, tol, max_iters, want_swa=True,
                                                                     want_p=not keep_on_device)[:2],
@@ -93,17 +102,26 @@ def diffusion_subspace(model, cost, data, opt, T=10, c=1, M=3, print_freq=1, *, 
                              compute_dtype=compute_dtype)
 
 
-def _refuse_node_training(model):
+def _refuse_node_training(model, cost):
+    """A NeuralODE trains with `flux.node_sse` (a flux.NodeSSE) and `sensealg="discrete_adjoint"` alone; raised before any context
+    is created."""
     if isinstance(model, flux.NeuralODE):
-        raise SubspaceError("training a NeuralODE through the solver is out of scope: pass W_swa, P to sub_inference, or push "
-                            "weight snapshots through the construction API (Context.construct_begin / construct_push / construct_finish)")
+        if not isinstance(cost, flux.NodeSSE):
+            raise SubspaceError("training a NeuralODE through the solver is out of scope: pass W_swa, P to sub_inference, or push "
+                                "weight snapshots through the construction API (Context.construct_begin / construct_push / construct_finish)")
+        if model.sensealg != "discrete_adjoint":
+            raise SubspaceError("training a NeuralODE with flux.node_sse needs the gradient through the solver: construct the model "
+                                "with sensealg=\"discrete_adjoint\"")
+    elif isinstance(cost, flux.NodeSSE):
+        raise SubspaceError("flux.node_sse is the cost of a flux.NeuralODE model (a Chain trains with flux.mse)")
 
 
 def _swa_construction(model, cost, data, opt, T, c, print_freq, finish, *, device, ctx, max_cols, verbose, keep_on_device,
                       device_training, init, data_parallel, a_storage, compute_dtype):
     """What `subspace_construction` and `diffusion_subspace` share (reference :28-59 and :169-200, the same lines twice): training
     with the SWA update and the deviation columns on the device; `finish(ctx)` -> (W_swa, P) is what differs."""
-    _refuse_node_training(model)
+    _refuse_node_training(model, cost)
+    is_node = isinstance(model, flux.NeuralODE)
     ps = flux.params(model)
     n_par = int(sum(p.size for p in ps))
     nb = len(data)
@@ -111,7 +129,9 @@ def _swa_construction(model, cost, data, opt, T, c, print_freq, finish, *, devic
     if n_push == 0:
         # reference: reshape of an empty A, then psvd / U[:,1:M] fails
         raise SubspaceError("BoundsError: no snapshot was collected (mod(i,c) never 0 for i in 1:T)")
-    dev_opt = flux.device_optimiser(opt) if isinstance(cost, flux.MSE) and hasattr(data, "index_batches") else None
+    # the device step exists for a Chain with flux.mse and for a NeuralODE with flux.node_sse (si_train_setup / si_train_setup_node)
+    dev_cost = isinstance(cost, flux.NodeSSE) if is_node else isinstance(cost, flux.MSE)
+    dev_opt = flux.device_optimiser(opt) if dev_cost and hasattr(data, "index_batches") else None
     # si_train_* keeps Float32 weights and optimiser state (Flux's default): a Float64 model stays on the host step,
     # otherwise "auto" and device_training=False would return different (W_swa, P) for the same inputs
     all_f32 = all(p.dtype == np.float32 for p in ps)
@@ -119,6 +139,11 @@ def _swa_construction(model, cost, data, opt, T, c, print_freq, finish, *, devic
         raise SubspaceError("device_training needs cost = flux.mse, a fresh Descent / Momentum / ADAM optimiser and "
                             "Float32 parameters (the device step keeps Float32 weights and optimiser state)")
     use_dev = dev_opt is not None and all_f32 and device_training in ("auto", True)
+    if is_node:
+        if compute_dtype not in ("auto", "f64"):
+            raise SubspaceError("a NeuralODE trains in Float64: compute_dtype must be \"auto\" or \"f64\"")
+        if data_parallel:
+            raise SubspaceError("data_parallel=True is not available for NeuralODE training")
     ctx, own = _get_ctx(ctx, device)
     try:
         ctx.construct_begin(n_par, n_push, max_cols)
@@ -139,12 +164,17 @@ def _swa_construction(model, cost, data, opt, T, c, print_freq, finish, *, devic
         dp_rank, dp_world = dist.world(ctx) if use_dp else (0, 1)
         if use_dev:
             xm, ym, in_size = flux.data_matrices(data)
-            table, _ = flux.layer_table(model, in_size)
             bmax = min(data.batchsize, data.nobs)
             if compute_dtype not in ("auto", "f32", "f64"):
                 raise SubspaceError("compute_dtype must be \"auto\" (the data's element type, as in the reference), \"f32\" or \"f64\"")
-            ctx.train_setup(table, n_par, flux.extract_params(ps), xm, ym, bmax, *dev_opt,
-                            compute_dtype={"auto": None, "f32": _capi.SI_F32, "f64": _capi.SI_F64}[compute_dtype])
+            if is_node:
+                table, _ = flux.layer_table(model.chain)
+                ctx.train_setup_node(table, n_par, flux.extract_params(ps), xm, ym, model.saveat, bmax, *dev_opt, cost.penalty_div,
+                                     **model.options())
+            else:
+                table, _ = flux.layer_table(model, in_size)
+                ctx.train_setup(table, n_par, flux.extract_params(ps), xm, ym, bmax, *dev_opt,
+                                compute_dtype={"auto": None, "f32": _capi.SI_F32, "f64": _capi.SI_F64}[compute_dtype])
         for i in range(1, T + 1):
             if use_dev:
                 last = (i % print_freq == 0) or (i == T)
@@ -356,8 +386,9 @@ def subspace_inference(model, cost, data, opt, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr
                        sigma_m=None, sigma_p=None, device=0, ctx=None, seed=0, verbose=True, return_z=False,
                        compute_dtype="f64", device_loop=False, device_sampler=False, device_nuts=False):
     """src/space_inference.jl:33-54: construction, then sampling; returns (chn, lp, W_swa).
-    W_swa and P stay on the device between the two stages (no host round trip)."""
-    _refuse_node_training(model)
+    W_swa and P stay on the device between the two stages (no host round trip).  With a `flux.NeuralODE(...,
+    sensealg="discrete_adjoint")` and `flux.node_sse` this is the NeuralODE tutorial's call (docs/src/node_example.md:285)."""
+    _refuse_node_training(model, cost)
     m = _alg_name(method)
     if m not in ("subspace", "diffusion"):
         raise SubspaceError("Error: No method found")  # reference :42
@@ -403,8 +434,9 @@ def auto_encoder_subspace(model, cost, data, opt, encoder, decoder, T=10, c=1, M
 
     include_penalty: the reference writes `+ sum(sqnorm, autops)` on a line of its own AFTER the loss (:130-131), so Julia parses
     it as a separate statement and the penalty is dead -- like the prior term (quirk Q4).  False (default):
-    as the reference's code behaves; True adds the term it meant.  `seed` seeds the shuffle of the autoencoder's loader."""
-    _refuse_node_training(model)
+    as the reference's code behaves; True adds the term it meant.  `seed` seeds the shuffle of the autoencoder's loader.
+    A NeuralODE with `flux.node_sse` trains as in `subspace_construction`."""
+    _refuse_node_training(model, cost)
     if not isinstance(encoder, flux.Chain) or not all(isinstance(l, flux.Dense) for l in encoder.layers):
         raise SubspaceError("Error: the encoder must be a Chain of Dense layers")
     dec_table, _ = _decoder_spec(decoder)
@@ -477,8 +509,9 @@ def autoencoder_inference(model, cost, data, opt, encoder, decoder, σ_z=1.0, σ
                           print_freq=1, alg="hmc", backend="forwarddiff", *, sigma_z=None, sigma_m=None, sigma_p=None, device=0,
                           ctx=None, seed=0, verbose=True, return_z=False, include_penalty=False, include_prior=False,
                           device_loop=False, device_sampler=False, device_nuts=False):
-    """src/space_inference.jl:198-210: `auto_encoder_subspace`, then `auto_inference`, on one context -> (chn, lp)."""
-    _refuse_node_training(model)
+    """src/space_inference.jl:198-210: `auto_encoder_subspace`, then `auto_inference`, on one context -> (chn, lp).  A NeuralODE
+    with `flux.node_sse` trains as in `subspace_construction`."""
+    _refuse_node_training(model, cost)
     ctx, own = _get_ctx(ctx, device)
     try:
         w_swa, decoder = auto_encoder_subspace(model, cost, data, opt, encoder, decoder, T=T, c=c, M=M, print_freq=print_freq,

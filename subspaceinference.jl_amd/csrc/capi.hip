@@ -304,7 +304,7 @@ int32_t si_synchronize(si_ctx* ctx) {
   CHECK_CTX(ctx);
   BIND(ctx);
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SI_OK;
+  return train_node_report(ctx, "si_synchronize");
 }
 
 int32_t si_set_profiling_classes(si_ctx* ctx, uint32_t class_mask) {
@@ -838,6 +838,7 @@ int32_t si_construct_finish(si_ctx* ctx, int32_t M, double* W_swa_out, double* P
   if (!ctx->c_active || ctx->K <= 0) return fail(ctx, SI_ERR_STATE, "si_construct_finish: nothing pushed");
   if (M <= 0) return fail(ctx, SI_ERR_INVALID, "si_construct_finish: M must be positive");
   BIND(ctx);
+  if (const int32_t rcn = train_node_report(ctx, "si_construct_finish")) return rcn;   // (queued NeuralODE training steps: a failed one)
   const int64_t K = ctx->K, N = ctx->N;
   if (K_out) *K_out = K;
   // U[:,1:M] throws BoundsError in the reference when psvd returns fewer than M columns (:65)

@@ -90,6 +90,9 @@ int32_t node_grad_ensure(si_ctx* ctx, const char* who, int32_t C);
 int32_t node_value_and_grad(si_ctx* ctx, const double* z_dev, int32_t n, double* lp_dev, double* gz_dev);
 int32_t node_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* grad_out);
 int32_t node_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double* lp_out, double* grad_out);
+// capi_train.hip: after NeuralODE training steps (si_train_setup_node) a synchronising call ends with this -- it synchronises the
+// stream, reads the failure record back and returns SI_ERR_INVALID naming step, trajectory and status, once; SI_OK otherwise
+int32_t train_node_report(si_ctx* ctx, const char* who);
 void fused_fill_program(const si_ctx* ctx, si::ChainFusedPlan& fp);
 int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok);   // the gradient entry points' state rules and error texts
 }

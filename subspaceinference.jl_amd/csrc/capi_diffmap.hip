@@ -230,9 +230,10 @@ int32_t si_construct_finish_diffmap(si_ctx* ctx, int32_t M, double eps, double a
   if (!(tol > 0.0)) tol = 1e-12;
   if (max_iters <= 0) max_iters = 500;
   BIND(ctx);
+  if (const int32_t rcn = train_node_report(ctx, "si_construct_finish_diffmap")) return rcn;   // (queued NeuralODE training steps: a failed one)
   hipStream_t st = ctx->stream;
   int32_t rc;
-  dm.N = 0;   // the read-back is valid again once this call has built its kernel matrix
+  dm.N = 0;  // the read-back is valid again once this call has built its kernel matrix
   const int b = (int)std::min<int64_t>(N - 1, 2 * (int64_t)M + 16), n2 = 2 * b;
   const int Kp = (int)((K + 3) / 4 * 4), nb = dm_blocks(N);
   const int64_t Npad = (int64_t)nb * 64, ldt = pad_ld(b);

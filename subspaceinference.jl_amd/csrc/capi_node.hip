@@ -7,6 +7,50 @@
 
 using namespace si;
 
+namespace si {
+
+const char* node_plan(const si_layer* layers, int32_t L, int64_t N, int32_t d, int32_t S, const double* ts, const si_node_opts* opts,
+                      NodeArgs& a) {
+  int32_t prev = d, widest = 1;
+  for (int32_t l = 0; l < L; ++l) {
+    const si_layer& ly = layers[l];
+    if (ly.kind != SI_LAYER_DENSE) return "every layer of the right-hand side must be SI_LAYER_DENSE";
+    if (ly.act < 0 || ly.act >= SI_ACT_COUNT) return "unknown activation";
+    if (ly.in != prev) return "consecutive layer widths do not chain from d";
+    if (ly.out < 1 || ly.out > SI_NODE_MAX_WIDTH) return "layer widths must be 1 to 256";
+    const int64_t wn = (int64_t)ly.in * ly.out;
+    if (ly.w_off < 0 || ly.w_off > N - wn || ly.b_off < 0 || ly.b_off > N - ly.out) return "a layer's offset range falls outside [0, N)";
+    a.lay.in[l] = ly.in, a.lay.out[l] = ly.out, a.lay.act[l] = ly.act, a.lay.w_off[l] = (int32_t)ly.w_off, a.lay.b_off[l] = (int32_t)ly.b_off;
+    prev = ly.out;
+    widest = std::max(widest, ly.out);
+  }
+  if (prev != d) return "the right-hand side must map d to d";
+  a.lay.n = L;
+  if (!std::isfinite(opts->t0)) return "t0 must be finite";
+  for (int32_t s = 0; s < S; ++s)
+    if (!std::isfinite(ts[s]) || (s == 0 ? ts[0] < opts->t0 : !(ts[s] > ts[s - 1])))
+      return "the save times must be finite, strictly ascending and not before t0";
+  if (opts->pre_power != 1 && opts->pre_power != 3) return "pre_power must be 1 or 3";
+  if (opts->max_steps < 0 || opts->max_steps > SI_NODE_MAX_STEPS) return "max_steps must be 1 to 1000000 (0: 100000)";
+  if (opts->adaptive != 0 && opts->adaptive != 1) return "adaptive must be 0 or 1";
+  if (opts->adaptive) {
+    if (!(std::isfinite(opts->reltol) && opts->reltol > 0.0 && std::isfinite(opts->abstol) && opts->abstol > 0.0))
+      return "reltol and abstol must be finite and positive in adaptive mode";
+    if (!(std::isfinite(opts->dt) && opts->dt >= 0.0)) return "dt must be finite and >= 0 (0: the starting-step rule)";
+  } else if (!(std::isfinite(opts->dt) && opts->dt > 0.0)) {
+    return "dt must be finite and positive in fixed-step mode";
+  }
+  // G lanes per trajectory: the smallest power of two >= the widest layer, capped at 64 (a group never crosses a wave)
+  a.G = 1, a.lgG = 0;
+  while (a.G < widest && a.G < 64) a.G *= 2, a.lgG += 1;
+  a.maxw = widest, a.d = d, a.S = S, a.N = (int32_t)N;
+  a.t0 = opts->t0, a.reltol = opts->reltol, a.abstol = opts->abstol, a.dt = opts->dt;
+  a.adaptive = opts->adaptive, a.max_steps = opts->max_steps == 0 ? 100000 : opts->max_steps, a.pre_power = opts->pre_power;
+  return nullptr;
+}
+
+}  // namespace si
+
 namespace {
 
 // the kernel's arguments for `nc` chain slots whose weights lie in w: the set-up's constants plus this pass's data and outputs
@@ -68,41 +112,7 @@ int32_t si_infer_setup_node(si_ctx* ctx, const si_layer* layers, int32_t L, int6
   // (the per-chain sum walks its f per-trajectory values in the reference's order, one thread per chain: 2^20 is a millisecond of it)
   if (f > ((int64_t)1 << 20)) return bad("f must be at most 2^20 trajectories");
   NodeArgs a;
-  int32_t prev = d, widest = 1;
-  for (int32_t l = 0; l < L; ++l) {
-    const si_layer& ly = layers[l];
-    if (ly.kind != SI_LAYER_DENSE) return bad("every layer of the right-hand side must be SI_LAYER_DENSE");
-    if (ly.act < 0 || ly.act >= SI_ACT_COUNT) return bad("unknown activation");
-    if (ly.in != prev) return bad("consecutive layer widths do not chain from d");
-    if (ly.out < 1 || ly.out > SI_NODE_MAX_WIDTH) return bad("layer widths must be 1 to 256");
-    const int64_t wn = (int64_t)ly.in * ly.out;
-    if (ly.w_off < 0 || ly.w_off > N - wn || ly.b_off < 0 || ly.b_off > N - ly.out) return bad("a layer's offset range falls outside [0, N)");
-    a.lay.in[l] = ly.in, a.lay.out[l] = ly.out, a.lay.act[l] = ly.act, a.lay.w_off[l] = (int32_t)ly.w_off, a.lay.b_off[l] = (int32_t)ly.b_off;
-    prev = ly.out;
-    widest = std::max(widest, ly.out);
-  }
-  if (prev != d) return bad("the right-hand side must map d to d");
-  a.lay.n = L;
-  if (!std::isfinite(opts->t0)) return bad("t0 must be finite");
-  for (int32_t s = 0; s < S; ++s)
-    if (!std::isfinite(ts[s]) || (s == 0 ? ts[0] < opts->t0 : !(ts[s] > ts[s - 1])))
-      return bad("the save times must be finite, strictly ascending and not before t0");
-  if (opts->pre_power != 1 && opts->pre_power != 3) return bad("pre_power must be 1 or 3");
-  if (opts->max_steps < 0 || opts->max_steps > SI_NODE_MAX_STEPS) return bad("max_steps must be 1 to 1000000 (0: 100000)");
-  if (opts->adaptive != 0 && opts->adaptive != 1) return bad("adaptive must be 0 or 1");
-  if (opts->adaptive) {
-    if (!(std::isfinite(opts->reltol) && opts->reltol > 0.0 && std::isfinite(opts->abstol) && opts->abstol > 0.0))
-      return bad("reltol and abstol must be finite and positive in adaptive mode");
-    if (!(std::isfinite(opts->dt) && opts->dt >= 0.0)) return bad("dt must be finite and >= 0 (0: the starting-step rule)");
-  } else if (!(std::isfinite(opts->dt) && opts->dt > 0.0)) {
-    return bad("dt must be finite and positive in fixed-step mode");
-  }
-  // G lanes per trajectory: the smallest power of two >= the widest layer, capped at 64 (a group never crosses a wave)
-  a.G = 1, a.lgG = 0;
-  while (a.G < widest && a.G < 64) a.G *= 2, a.lgG += 1;
-  a.maxw = widest, a.d = d, a.S = S, a.N = (int32_t)N;
-  a.t0 = opts->t0, a.reltol = opts->reltol, a.abstol = opts->abstol, a.dt = opts->dt;
-  a.adaptive = opts->adaptive, a.max_steps = opts->max_steps == 0 ? 100000 : opts->max_steps, a.pre_power = opts->pre_power;
+  if (const char* what = node_plan(layers, L, N, d, S, ts, opts, a)) return bad(what);
   int32_t rc = infer_setup_node_base(ctx, layers, L, N, M, W_swa, P, U0, Y, d, S, f);
   if (rc != SI_OK) return rc;
   NodeState& n = ctx->node;

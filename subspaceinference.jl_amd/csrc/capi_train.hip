@@ -11,7 +11,7 @@
 #include <cstring>
 #include <string>
 
-#include "si_internal.h"
+#include "capi_common.h"
 
 namespace si {
 
@@ -83,6 +83,8 @@ static int grid_for(int64_t n, int num_cu) {
   if (b > (int64_t)num_cu * 8) b = (int64_t)num_cu * 8;
   return (int)(b < 1 ? 1 : b);
 }
+
+TrainState::~TrainState() { delete node; }
 
 void free_train(Ctx* c) {
   delete c->train;
@@ -319,6 +321,186 @@ int32_t si_train_compute_dtype(si_ctx* ctx, int32_t* out) {
   return SI_OK;
 }
 
+// idx is caller-owned: copied into a pinned buffer, shipped asynchronously; the buffer is free again once its event has
+// passed (two steps later at the earliest) -- no synchronisation of the stream, the call returns while the GPU works
+static int32_t stage_indices(si_ctx* ctx, TrainState* t, const int64_t* idx, int64_t nb) {
+  const int b = t->idx_slot;
+  t->idx_slot ^= 1;
+  if (t->idx_busy[b]) SI_HIP(ctx, hipEventSynchronize(t->idx_ev[b]));
+  std::memcpy(t->idx_pin[b], idx, (size_t)nb * sizeof(int64_t));
+  SI_HIP(ctx, hipMemcpyAsync(t->idx, t->idx_pin[b], (size_t)nb * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  SI_HIP(ctx, hipEventRecord(t->idx_ev[b], ctx->stream));
+  t->idx_busy[b] = true;
+  return SI_OK;
+}
+
+// ---- NeuralODE training (node.py: train_value_and_grad is the definition; flux.NodeSSE the cost) ----------------------------------
+// loss = sum_{p in batch} ||sol_p(W) - Y_p||^2 + ||W||^2 / penalty_div; its gradient is the frozen-step discrete adjoint of
+// si_node_set_grad (kernels_node.hip: the forward with record, then the reverse kernel, one chain, f = nb) plus the penalty's.
+// The solver workspace is the training state's own (NodeTrain); only the launchers are the inference route's.
+int32_t si_train_setup_node(si_ctx* ctx, const si_layer* layers, int32_t L, int64_t N, const float* w0, const double* U0, const double* Y,
+                            int32_t d, int32_t S, int64_t f, const double* ts, const void* opts_in, int64_t batch_max, int32_t opt_kind,
+                            double eta, double p1, double p2, double penalty_div) {
+  if (!ctx) return SI_ERR_INVALID;
+  const si_node_opts* opts = static_cast<const si_node_opts*>(opts_in);
+  auto bad = [&](const char* what) { return fail(ctx, SI_ERR_INVALID, std::string("si_train_setup_node: ") + what); };
+  if (!layers || !w0 || !U0 || !Y || !ts || !opts || f <= 0 || batch_max <= 0 || batch_max > f || opt_kind < 0 || opt_kind > 2 ||
+      !(penalty_div >= 0.0) || !std::isfinite(penalty_div))
+    return bad("bad argument");
+  if (L < 1 || L > SI_NODE_MAX_LAYERS) return bad("a NeuralODE right-hand side has 1 to 8 Dense layers");
+  if (d < 1 || d > SI_NODE_MAX_D) return bad("the state dimension d must be 1 to 8");
+  if (N < 1 || N > SI_NODE_MAX_N) return bad("N must be 1 to 8192");
+  if (S < 1 || S > SI_NODE_MAX_S) return bad("the number of save times S must be 1 to 4096");
+  if (f > ((int64_t)1 << 20)) return bad("f must be at most 2^20 trajectories");
+  NodeArgs a;
+  if (const char* what = node_plan(layers, L, N, d, S, ts, opts, a)) return bad(what);
+  if (a.maxw > 64) return bad("a layer is wider than 64 (the reverse kernel gives every lane of a trajectory's group one unit per layer)");
+  // the step record (batch_max * max_steps * (d + 2) doubles) and the gradient slices (batch_max * N) within the workspace budget
+  if (8.0 * (double)batch_max * ((double)a.max_steps * (double)(d + 2) + (double)N) > SI_BATCH_BYTES)
+    return bad("the step record (batch_max * max_steps * (d + 2) doubles) and the gradient slices (batch_max * N) do not fit the "
+               "2 GiB workspace budget: lower max_steps or the batch size");
+  SI_HIP(ctx, hipSetDevice(ctx->device));
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  free_train(ctx);
+  TrainState* t = new TrainState();
+  ctx->train = t;
+  NodeTrain* nt = t->node = new NodeTrain();
+  t->layers.assign(layers, layers + L);
+  t->N = N; t->Btot = f; t->Bmax = batch_max; t->in_dim = d; t->out_dim = d * S;
+  t->opt = opt_kind; t->eta = eta; t->p1 = p1; t->p2 = p2; t->bp1 = p1; t->bp2 = p2;  // ADAM: beta powers start at beta
+  nt->args = a;
+  nt->penalty_div = penalty_div;
+  nt->wsq_blocks = sse_num_blocks(N, ctx->num_cu);
+  const size_t bm = (size_t)batch_max;
+  const bool ok = t->X.alloc((size_t)d * (size_t)f) && t->Xb.alloc((size_t)d * bm) && t->Y.alloc((size_t)t->out_dim * (size_t)f) &&
+                  t->Yb.alloc((size_t)t->out_dim * bm) && t->idx.alloc(bm) && t->idx_pin[0].alloc(bm) && t->idx_pin[1].alloc(bm) &&
+                  t->idx_ev[0].create() && t->idx_ev[1].create() && t->w32.alloc((size_t)N) && t->m32.alloc((size_t)N) &&
+                  t->v32.alloc((size_t)N) && t->w64.alloc((size_t)pad_ld(N)) && t->gw.alloc((size_t)pad_ld(N)) && t->sse.alloc(1) &&
+                  nt->ts.alloc((size_t)S) && nt->ssep.alloc(bm) && nt->rec.alloc(bm * (size_t)a.max_steps * (size_t)(d + 2)) &&
+                  nt->slices.alloc(bm * (size_t)N) && nt->cnt.alloc(3 * bm) && nt->wsq.alloc(1) &&
+                  nt->wsqpart.alloc((size_t)nt->wsq_blocks) && nt->fail.alloc(3);
+  if (!ok) {
+    free_train(ctx);
+    return fail(ctx, SI_ERR_NOMEM, "si_train_setup_node: device allocation failed (the step record: lower max_steps or the batch size)");
+  }
+  hipStream_t st = ctx->stream;
+  hipError_t e = hipMemcpyAsync(t->X, U0, (size_t)d * (size_t)f * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(t->Y, Y, (size_t)t->out_dim * (size_t)f * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(nt->ts, ts, (size_t)S * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(t->w32, w0, (size_t)N * sizeof(float), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(t->m32, 0, (size_t)N * sizeof(float), st);
+  if (e == hipSuccess) e = hipMemsetAsync(t->v32, 0, (size_t)N * sizeof(float), st);
+  if (e == hipSuccess) e = hipMemsetAsync(t->w64, 0, (size_t)pad_ld(N) * sizeof(double), st);
+  if (e == hipSuccess) e = hipMemsetAsync(t->gw, 0, (size_t)pad_ld(N) * sizeof(double), st);
+  if (e == hipSuccess) e = hipMemsetAsync(t->sse, 0, sizeof(double), st);
+  if (e == hipSuccess) e = hipMemsetAsync(nt->fail, 0, 3 * sizeof(int64_t), st);
+  if (e == hipSuccess) {
+    launch_widen_f32_to_f64(st, t->w32, N, t->w64, ctx->num_cu);   // the first step's solve reads the Float64 copy
+    e = hipGetLastError();
+  }
+  const hipError_t e2 = hipStreamSynchronize(st);
+  if (e != hipSuccess || e2 != hipSuccess) {
+    free_train(ctx);
+    return fail(ctx, SI_ERR_HIP, std::string("si_train_setup_node: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+  }
+  return SI_OK;
+}
+
+int32_t si_train_node_info(si_ctx* ctx, int32_t* active_out, int32_t* G_out, int64_t* failed_step_out, int64_t* failed_traj_out,
+                           int32_t* failed_status_out) {
+  if (!ctx) return SI_ERR_INVALID;
+  const NodeTrain* nt = ctx->train ? ctx->train->node : nullptr;
+  int64_t rec[3] = {0, 0, 0};
+  if (nt) {
+    SI_HIP(ctx, hipSetDevice(ctx->device));
+    SI_HIP(ctx, hipMemcpyAsync(rec, nt->fail, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
+    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  if (active_out) *active_out = nt ? 1 : 0;
+  if (G_out) *G_out = nt ? nt->args.G : 0;
+  if (failed_step_out) *failed_step_out = rec[0] != 0 ? rec[0] : -1;
+  if (failed_traj_out) *failed_traj_out = rec[0] != 0 ? rec[1] : -1;
+  if (failed_status_out) *failed_status_out = rec[0] != 0 ? (int32_t)rec[2] : 0;
+  return SI_OK;
+}
+
+// the batch's columns, ||W||^2, the forward with record, the reverse kernel and the tail, all queued on the context's stream
+static int32_t node_train_launches(si_ctx* ctx, const char* who, const int64_t* idx, int64_t nb, bool apply) {
+  TrainState* t = ctx->train;
+  NodeTrain* nt = t->node;
+  // (a failure the caller has been told about: the set-up takes no further steps, the device's would be no-ops)
+  if (nt->reported) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": an earlier NeuralODE training step failed (si_train_node_info): set up again");
+  if (!idx || nb <= 0 || nb > t->Bmax) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": bad batch");
+  bool in_order = true;
+  for (int64_t j = 0; j < nb; ++j) {
+    if (idx[j] < 0 || idx[j] >= t->Btot)
+      return fail(ctx, SI_ERR_INVALID, std::string(who) + ": BoundsError: batch index out of range");
+    in_order = in_order && idx[j] == j;
+  }
+  SI_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int64_t N = t->N, Bmax = t->Bmax;
+  const double *U0b = t->X, *Yb = t->Y;
+  {
+    ProfScope ps(ctx, SI_K_SSE, 0.0, 0.0);
+    if (!in_order) {
+      const int32_t rcs = stage_indices(ctx, t, idx, nb);
+      if (rcs != SI_OK) return rcs;
+      hipLaunchKernelGGL(gather_cols_kernel, dim3(grid_for((int64_t)t->in_dim * nb, ctx->num_cu)), dim3(256), 0, st, t->X, t->in_dim,
+                         t->idx, nb, t->Xb);
+      hipLaunchKernelGGL(gather_cols_kernel, dim3(grid_for((int64_t)t->out_dim * nb, ctx->num_cu)), dim3(256), 0, st, t->Y, t->out_dim,
+                         t->idx, nb, t->Yb);
+      U0b = t->Xb;
+      Yb = t->Yb;
+    }
+    launch_sse(st, t->w64, nullptr, N, nt->wsqpart, nt->wsq_blocks, nt->wsq, 1, pad_ld(N));   // ||W||^2, as the density forms it
+    SI_HIP(ctx, hipMemsetAsync(nt->slices, 0, (size_t)nb * (size_t)N * sizeof(double), st));     // "from 0.0"
+  }
+  NodeArgs a = nt->args;
+  a.w = t->w64, a.ldw = pad_ld(N);
+  a.U0 = U0b, a.Y = Yb, a.f = nb, a.ts = nt->ts;
+  a.sse_p = nt->ssep, a.U_out = nullptr;
+  a.nacc = nt->cnt, a.nrej = nt->cnt + Bmax, a.status = nt->cnt + 2 * Bmax;
+  a.rec = nt->rec, a.gsl = nt->slices;
+  {
+    ProfScope ps(ctx, SI_K_DENSE, 0.0, 0.0);
+    SI_HIP(ctx, launch_node_solve(st, a, 1));
+  }
+  {
+    ProfScope ps(ctx, SI_K_BACKWARD, 0.0, 0.0);
+    SI_HIP(ctx, launch_node_grad(st, a, 1));
+  }
+  {
+    ProfScope ps(ctx, SI_K_RECON, 0.0, 0.0);   // (the tail: gw, the loss, the update and the refreshed Float64 weights)
+    const NodeTailArgs ta{nt->slices, nt->ssep, nt->wsq, a.status, nb, N, nt->steps + 1, nt->penalty_div, t->w32, t->m32, t->v32,
+                          t->w64, t->gw, t->sse, nt->fail, t->opt, t->eta, t->p1, t->p2, t->bp1, t->bp2};
+    launch_node_train_tail(st, ta, apply);
+  }
+  SI_HIP(ctx, hipGetLastError());
+  return SI_OK;
+}
+
+// after a synchronisation of the stream: a failure record the caller has not been told about yet -> SI_ERR_INVALID, once
+int32_t train_node_report(si_ctx* ctx, const char* who) {
+  NodeTrain* nt = ctx->train ? ctx->train->node : nullptr;
+  if (!nt || nt->reported || nt->checked == nt->steps) return SI_OK;
+  int64_t rec[3] = {0, 0, 0};
+  SI_HIP(ctx, hipSetDevice(ctx->device));
+  SI_HIP(ctx, hipMemcpyAsync(rec, nt->fail, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  nt->checked = nt->steps;
+  if (rec[0] == 0) return SI_OK;
+  nt->reported = true;
+  TrainState* t = ctx->train;
+  t->grad_ready = false;
+  t->bp1 = t->p1, t->bp2 = t->p2;   // the beta powers as the last step that was taken left them
+  for (int64_t k = 1; k < rec[0] && t->opt == 2; ++k) t->bp1 *= t->p1, t->bp2 *= t->p2;
+  return fail(ctx, SI_ERR_INVALID, std::string(who) + ": NeuralODE training step " + std::to_string(rec[0]) + ": trajectory " +
+                                       std::to_string(rec[1]) + " of its batch ended with status " + std::to_string(rec[2]) +
+                                       " (1: max_steps reached, 2: a non-finite state); that step and every later one left the "
+                                       "weights and the optimiser state as they were");
+}
+
 // forward + reverse sweep of the mse cost on the observations idx[0..nb): the gradient w.r.t. the flat weights, scaled
 // as if the batch were part of d_total = out_dim * (observations of the WHOLE batch), is left in t->gw; t->sse holds the
 // local sum of squared errors
@@ -339,15 +521,8 @@ static int32_t train_gradient(si_ctx* ctx, const char* who, const int64_t* idx, 
   const double *Xb = t->X, *Yb = t->Y;
   const float* Xb32 = t->X32;
   if (!in_order) {
-    // idx is caller-owned: copied into a pinned buffer, shipped asynchronously; the buffer is free again once its event has
-    // passed (two steps later at the earliest) -- no synchronisation of the stream, the call returns while the GPU works
-    const int b = t->idx_slot;
-    t->idx_slot ^= 1;
-    if (t->idx_busy[b]) SI_HIP(ctx, hipEventSynchronize(t->idx_ev[b]));
-    std::memcpy(t->idx_pin[b], idx, (size_t)nb * sizeof(int64_t));
-    SI_HIP(ctx, hipMemcpyAsync(t->idx, t->idx_pin[b], (size_t)nb * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    SI_HIP(ctx, hipEventRecord(t->idx_ev[b], st));
-    t->idx_busy[b] = true;
+    const int32_t rcs = stage_indices(ctx, t, idx, nb);
+    if (rcs != SI_OK) return rcs;
     if (t->f32) {
       hipLaunchKernelGGL(gather_cols_f32_kernel, dim3(grid_for((int64_t)t->in_dim * nb, ctx->num_cu)), dim3(256), 0, st, t->X32,
                          t->in_dim, t->idx, nb, t->Xb32);
@@ -416,9 +591,31 @@ static int32_t train_apply(si_ctx* ctx) {
   return SI_OK;
 }
 
+// si_train_step on a NeuralODE set-up: one pass of launches ending in the tail kernel with the update; nothing synchronises
+// unless the loss is asked for
+static int32_t node_train_step(si_ctx* ctx, const int64_t* idx, int64_t nb, double* loss_out) {
+  TrainState* t = ctx->train;
+  NodeTrain* nt = t->node;
+  int32_t rc = node_train_launches(ctx, "si_train_step", idx, nb, /*apply=*/true);
+  if (rc != SI_OK) return rc;
+  nt->steps += 1;
+  if (t->opt == 2) {   // (a failed step does not advance them: train_node_report rewinds)
+    t->bp1 *= t->p1;
+    t->bp2 *= t->p2;
+  }
+  t->grad_ready = false;
+  if (loss_out) {
+    SI_HIP(ctx, hipMemcpyAsync(loss_out, t->sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = train_node_report(ctx, "si_train_step")) != SI_OK) return rc;
+  }
+  return SI_OK;
+}
+
 int32_t si_train_step(si_ctx* ctx, const int64_t* idx, int64_t nb, double* loss_out) {
   if (!ctx) return SI_ERR_INVALID;
   TrainState* t = ctx->train;
+  if (t && t->node) return node_train_step(ctx, idx, nb, loss_out);
   const double d = t ? (double)t->out_dim * (double)nb : 1.0;
   int32_t rc = train_gradient(ctx, "si_train_step", idx, nb, d);
   if (rc != SI_OK) return rc;
@@ -441,6 +638,19 @@ int32_t si_train_grad(si_ctx* ctx, const int64_t* idx, int64_t nb, int64_t nb_to
   if (!ctx) return SI_ERR_INVALID;
   if (nb_total < nb) return fail(ctx, SI_ERR_INVALID, "si_train_grad: nb_total < nb");
   TrainState* t = ctx->train;
+  if (t && t->node) {
+    // a NeuralODE step is not data-parallel: the gradient of this batch alone (the tail kernel without the update);
+    // sse_local_out receives the loss of the batch, penalty included
+    if (nb_total != nb) return fail(ctx, SI_ERR_INVALID, "si_train_grad: a share of a batch is not available for NeuralODE training (nb_total must equal nb)");
+    int32_t rcn = node_train_launches(ctx, "si_train_grad", idx, nb, /*apply=*/false);
+    if (rcn != SI_OK) return rcn;
+    t->node->steps += 1;
+    if (sse_local_out) SI_HIP(ctx, hipMemcpyAsync(sse_local_out, t->sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rcn = train_node_report(ctx, "si_train_grad")) != SI_OK) return rcn;
+    t->grad_ready = true;
+    return SI_OK;
+  }
   const double d_total = t ? (double)t->out_dim * (double)nb_total : 1.0;
   if (t && nb == 0 && nb_total > 0) {  // a rank without a share of a small batch contributes a zero gradient
     SI_HIP(ctx, hipSetDevice(ctx->device));
@@ -468,7 +678,9 @@ int32_t si_train_grad_ptr(si_ctx* ctx, double** grad_dev_out, int64_t* n_out) {
 
 int32_t si_train_grad_get(si_ctx* ctx, double* g_out) {
   if (!ctx) return SI_ERR_INVALID;
-  if (!ctx->train || !ctx->train->grad_ready || !g_out) return fail(ctx, SI_ERR_STATE, "si_train_grad_get: no gradient pending / NULL output");
+  // (a NeuralODE step's tail kernel leaves its gradient in gw: it can be read after si_train_step too, for the audit)
+  const bool node_gw = ctx->train && ctx->train->node && ctx->train->node->steps > 0 && !ctx->train->node->reported;
+  if (!ctx->train || !(ctx->train->grad_ready || node_gw) || !g_out) return fail(ctx, SI_ERR_STATE, "si_train_grad_get: no gradient pending / NULL output");
   SI_HIP(ctx, hipSetDevice(ctx->device));
   SI_HIP(ctx, hipMemcpyAsync(g_out, ctx->train->gw, (size_t)ctx->train->N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -488,7 +700,10 @@ int32_t si_train_apply(si_ctx* ctx) {
   if (!ctx) return SI_ERR_INVALID;
   if (!ctx->train || !ctx->train->grad_ready) return fail(ctx, SI_ERR_STATE, "si_train_apply: no gradient pending (call si_train_grad)");
   SI_HIP(ctx, hipSetDevice(ctx->device));
-  return train_apply(ctx);
+  const int32_t rc = train_apply(ctx);
+  if (rc == SI_OK && ctx->train->node)   // the next step's solve reads the Float64 copy (si_train_step refreshes it in its tail kernel)
+    launch_widen_f32_to_f64(ctx->stream, ctx->train->w32, ctx->train->N, ctx->train->w64, ctx->num_cu);
+  return rc;
 }
 
 int32_t si_train_push(si_ctx* ctx, double n) {
@@ -504,7 +719,7 @@ int32_t si_train_get_weights(si_ctx* ctx, float* w_out) {
   SI_HIP(ctx, hipSetDevice(ctx->device));
   SI_HIP(ctx, hipMemcpyAsync(w_out, ctx->train->w32, (size_t)ctx->train->N * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SI_OK;
+  return train_node_report(ctx, "si_train_get_weights");
 }
 
 int32_t si_train_get_opt_state(si_ctx* ctx, float* m_out, float* v_out, double* beta_pows_out) {
@@ -515,6 +730,8 @@ int32_t si_train_get_opt_state(si_ctx* ctx, float* m_out, float* v_out, double* 
   if (m_out && t->m32) SI_HIP(ctx, hipMemcpyAsync(m_out, t->m32, (size_t)t->N * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   if (v_out && t->v32) SI_HIP(ctx, hipMemcpyAsync(v_out, t->v32, (size_t)t->N * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const int32_t rcn = train_node_report(ctx, "si_train_get_opt_state");
+  if (rcn != SI_OK) return rcn;
   if (beta_pows_out) {
     beta_pows_out[0] = t->bp1;
     beta_pows_out[1] = t->bp2;

@@ -81,8 +81,12 @@ struct SweepF32Ws {
   DevBuf<double> rspart64, tailpart64, yhat64;
 };
 
+struct NodeTrain;   // si_train_setup_node: a NeuralODE's training step (below, after NodeArgs)
+
 // on-device training (capi_train.hip)
 struct TrainState {
+  ~TrainState();            // (capi_train.hip: releases `node`)
+  NodeTrain* node = nullptr;   // set: the model is a NeuralODE; X = U0 (d x f), Y = the trajectories (d*S x f), in_dim = d, out_dim = d*S
   std::vector<si_layer> layers;
   int64_t N = 0, Btot = 0, Bmax = 0;
   int32_t in_dim = 0, out_dim = 0;
@@ -348,6 +352,42 @@ hipError_t launch_node_grad(hipStream_t st, const NodeArgs& a, int nchains);    
 // gw[:, c] = the chain's f slices added in ascending p from 0.0; lp[c] from the chain's sums as the host forms it
 void launch_node_grad_sum(hipStream_t st, const double* gsl, int64_t f, int64_t N, double* gw, int64_t ldg, const double* sse,
                           const double* wsq, double* lp, int nchains);
+// the validation si_infer_setup_node and si_train_setup_node share: the layers, the save times and the options -> the constant
+// part of the kernel's arguments; nullptr, or the limit that refuses the set-up
+const char* node_plan(const si_layer* layers, int32_t L, int64_t N, int32_t d, int32_t S, const double* ts, const si_node_opts* opts,
+                      NodeArgs& a);
+
+// si_train_setup_node (capi_train.hip; node.py: train_value_and_grad is the definition): the training step's own solver workspace
+// for batch_max trajectories of ONE weight vector -- the inference state's (NodeState) is not shared, the launchers are
+struct NodeTrain {
+  NodeArgs args;                   // the constants (node_plan); per step: w = TrainState::w64, U0 / Y = the batch's columns, f = nb
+  DevBuf<double> ts;               // S
+  DevBuf<double> ssep;             // batch_max
+  DevBuf<double> rec;              // batch_max x max_steps x (d + 2): the step record
+  DevBuf<double> slices;           // batch_max x N: the per-trajectory gradient slices
+  DevBuf<int32_t> cnt;             // nacc, nrej, status: batch_max each
+  DevBuf<double> wsq, wsqpart;     // ||W||^2 and its block partials
+  int wsq_blocks = 0;
+  DevBuf<int64_t> fail;            // the sticky failure record: [0] the 1-based step that failed first (0: none), [1] trajectory, [2] status
+  double penalty_div = 0.0;        // 0: no penalty
+  int64_t steps = 0;               // steps queued so far (a step's number is steps + 1)
+  int64_t checked = 0;             // the failure record has been read back after this many steps ...
+  bool reported = false;           // ... and a failure found in it has been returned to the caller (once)
+};
+// node_train_tail_kernel (kernels_node_train.hip): the batch's slices -> gw (with the penalty), the loss word, and with `apply`
+// the optimiser update and the refreshed Float64 copy of the weights; a failed trajectory or a set failure record stores nothing
+// but the record
+struct NodeTailArgs {
+  const double* slices; const double* ssep; const double* wsq; const int32_t* status;
+  int64_t nb, N, step;
+  double penalty_div;
+  float *w32, *m32, *v32;
+  double *w64, *gw, *loss;
+  int64_t* fail;
+  int kind;
+  double eta, p1, p2, bp1, bp2;
+};
+void launch_node_train_tail(hipStream_t st, const NodeTailArgs& a, bool apply);
 
 // ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops
 struct InferState {

@@ -359,6 +359,47 @@ class MSE:
 mse = MSE()
 
 
+class NodeSSE:
+    """The NeuralODE tutorial's cost (docs/src/node_example.md:272)
+        L1(m, x, y) = sum(abs2, m(vec(x)) .- reshape(y[:,1], :,2)') + sum(sqnorm, Flux.params(m))/100
+    as `loss(model, x, y) = sum_{p in batch} ||sol_p(W) - Y_p||^2 + ||W||^2 / penalty_div` (penalty_div None drops the term), x the
+    batch's initial states (d x nb), y its observed trajectories (d*S x nb, row i*S + s).  For a batch of one column this is L1.  A
+    batch of several columns sums over them: an EXTENSION -- the tutorial's `vec(x)` / `y[:,1]` only mean something at batchsize =
+    1, the DataLoader's default.  node.train_value_and_grad is the definition; its gradient is the frozen-step discrete adjoint,
+    not Zygote's through DiffEqFlux (see there).  si_train_setup_node runs the same step on the device."""
+
+    def __init__(self, penalty_div=100.0):
+        if penalty_div is not None and not (np.isfinite(penalty_div) and penalty_div > 0.0):
+            raise SubspaceError("penalty_div must be positive and finite, or None (no penalty)")
+        self.penalty_div = None if penalty_div is None else float(penalty_div)
+
+    def _args(self, model, x, y):
+        from . import node
+        if not isinstance(model, NeuralODE):
+            raise SubspaceError("flux.node_sse is the cost of a flux.NeuralODE model (a Chain trains with flux.mse)")
+        x = np.asarray(x, dtype=np.float64)
+        x = x.reshape(x.shape[0], -1)
+        y = np.asarray(y, dtype=np.float64).reshape(x.shape[0] * model.saveat.size, x.shape[1])
+        table, _ = layer_table(model.chain)
+        return node, table, extract_params(params(model)).astype(np.float64), x, y, node.Opts(**model.options())
+
+    def __call__(self, model, x, y):
+        return self.value_and_grad(model, x, y)[0]
+
+    def value_and_grad(self, model, x, y):
+        """(loss, per-array Float64 gradients in `params` order): a Float64 gradient, so `update` takes a Float64 step and rounds once"""
+        node, table, w, x, y, opts = self._args(model, x, y)
+        loss, g = node.train_value_and_grad(table, w, x, y, model.saveat, opts, self.penalty_div)
+        grads, off = [], 0
+        for p in params(model):
+            grads.append(g[off:off + p.size].reshape(p.shape, order="F"))
+            off += p.size
+        return float(loss), grads
+
+
+node_sse = NodeSSE()
+
+
 def gradient(cost, model, *batch):
     if hasattr(cost, "value_and_grad"):
         return cost.value_and_grad(model, *batch)

@@ -582,6 +582,31 @@ function node_grad(ctx::Ctx, Z::Matrix{Float64}, N::Integer)
         (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ctx.h, Z, C, lp, gw, gz))
     return lp, gw, gz
 end
+# The training step of a NeuralODE (docs/src/node_example.md:272-285): train_setup_node! in place of the Chain's training set-up;
+# train_step!, train_push and the weight / optimiser read-backs then work as for a Chain.  A step minimises
+# sum_p ||sol_p(W) - Y_p||^2 + ||W||^2 / penalty_div over its batch (penalty_div = 0: no penalty; one column and 100: the tutorial's
+# L1) with the discrete adjoint's gradient -- not Zygote's through DiffEqFlux, which agrees with it to the order of the tolerances.
+# A trajectory that fails leaves the weights as they were; the next synchronising call throws, train_node_info keeps reporting it.
+function train_setup_node!(ctx::Ctx, dudt, w0::Vector{Float32}, U0::Matrix{Float64}, Y::Matrix{Float64}, ts::Vector{Float64},
+                           batch_max::Integer, opt; penalty_div = 100.0, t0 = 0.0, reltol = 1e-3, abstol = 1e-6, dt = 0.0,
+                           adaptive = true, max_steps = 100000, pre_power = 1)
+    tbl, N = layer_table(dudt)
+    d, f, S = size(U0, 1), size(U0, 2), length(ts)
+    size(Y) == (d * S, f) || throw(DimensionMismatch("Y must be d*S x f"))
+    kind, η, p1, p2 = device_optimiser(opt)
+    opts = Ref(SiNodeOpts(t0, reltol, abstol, dt, adaptive ? 1 : 0, max_steps, pre_power))
+    GC.@preserve tbl w0 U0 Y ts opts check(ctx, ccall((:si_train_setup_node, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{SiLayer}, Int32, Int64, Ptr{Float32}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Int64, Ptr{Float64}, Ptr{Cvoid},
+         Int64, Int32, Float64, Float64, Float64, Float64),
+        ctx.h, tbl, length(tbl), N, w0, U0, Y, d, S, f, ts, opts, batch_max, kind, η, p1, p2, Float64(penalty_div)))
+end
+function train_node_info(ctx::Ctx)
+    on, G, st = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    step, traj = Ref{Int64}(-1), Ref{Int64}(-1)
+    check(ctx, ccall((:si_train_node_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int64}, Ref{Int64}, Ref{Int32}),
+        ctx.h, on, G, step, traj, st))
+    return on[] != 0, Int(G[]), Int(step[]), Int(traj[]), Int(st[])
+end
 function node_tableau()
     out = Vector{Float64}(undef, 57)
     ccall((:si_node_tableau, LIB), Int32, (Ptr{Float64},), out) == 0 || throw("si_node_tableau failed")

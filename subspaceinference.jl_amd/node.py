@@ -607,3 +607,30 @@ def logdensity_grad(table, w, u0, y, ts, opts, nudge=None):
     if np.any(sol.status != 0):
         return lp, np.full(w.size, np.nan)
     return lp, grad_w(table, w, u0, ts, opts, y, sol.record, nudge=nudge) - w * 2.0
+
+
+# ---- the training step of a NeuralODE (si_train_setup_node; flux.NodeSSE is the cost) ------------------------------------------------
+# loss(W) = sum_{p in batch} ||sol_p(W) - Y_p||^2 + ||W||^2 / penalty_div: at one column and penalty_div = 100 the tutorial's
+#     L1(m, x, y) = sum(abs2, m(vec(x)) .- reshape(y[:,1], :,2)') + sum(sqnorm, Flux.params(m))/100      (docs/src/node_example.md:272)
+# The gradient is the frozen-step discrete adjoint above (grad_slices) -- NOT what Zygote gives through DiffEqFlux's NeuralODE, which
+# differentiates with a continuous adjoint by default [upstream, from memory, unverifiable offline]: the two agree to the order of the
+# tolerances, not to rounding.  `sum(sqnorm, params)` adds array by array in the reference; here ||W||^2 is sum_squares over the flat
+# vector.  Only the printed loss depends on that order (the penalty's gradient is elementwise), and it is not reproduced.
+def train_value_and_grad(table, w, u0_b, y_b, ts, opts, penalty_div, nudge=None):
+    """(loss, g) of the batch columns u0_b (d x nb), y_b (d*S x nb) at the flat weights w; penalty_div None drops the penalty.
+    Per weight element acc = the batch's slices added from 0.0 in batch order; g = (w * 2.0) / penalty_div - acc, or 0.0 - acc.
+    A trajectory that ends with status != 0 raises (si_train_step: the step leaves the weights as they were)."""
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    sol = solve(table, w, u0_b, ts, opts, y=y_b, nudge=nudge, record=True)
+    for p, st in enumerate(sol.status):
+        if st != 0:
+            raise SubspaceError("NeuralODE training: trajectory %d of the batch ended with status %d (1: max_steps reached, 2: a "
+                                "non-finite state)" % (p, int(st)))
+    sl = grad_slices(table, w, u0_b, ts, opts, y_b, sol.record, nudge=nudge)
+    acc = np.zeros(w.size)
+    for p in range(sl.shape[1]):
+        acc = acc + sl[:, p]
+    loss = sse_total(sol.sse)
+    if penalty_div is None:
+        return loss, 0.0 - acc
+    return loss + sum_squares(w) / penalty_div, (w * 2.0) / penalty_div - acc

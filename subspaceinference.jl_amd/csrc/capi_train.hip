@@ -5,18 +5,23 @@
 // Float32 parameters and Float32 optimiser state, Float64 arithmetic because the data are Float64).  The weights never
 // leave the GPU: si_train_push feeds K1 from the device-resident Float32 vector.  The gradient is one of the value-and-gradient
 // passes shared with si_logdensity_grad: dense_value_and_grad_f64 (capi.hip), dense_value_and_grad_f32 (below), net_value_and_grad
-// (capi_net.hip), each with the mse scale -2 / d.
+// (capi_net.hip), each with the mse scale -2 / d; or a NeuralODE's (si_train_setup_node, below).
+// One step is: the batch (train_batch), the gradient by the set-up's route (TrainState::route: train_gradient, node_gradient), the
+// update (optimiser_update.h: optimiser_kernel here, fused into the tail kernel on the NeuralODE route).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <optional>
 #include <string>
 
 #include "capi_common.h"
+#include "optimiser_update.h"
 
 namespace si {
 
-__global__ __launch_bounds__(256) void gather_cols_kernel(const double* __restrict__ src, int rows, const int64_t* __restrict__ idx,
-                                                          int64_t nb, double* __restrict__ dst) {
+template <class T>
+__global__ __launch_bounds__(256) void gather_cols_kernel(const T* __restrict__ src, int rows, const int64_t* __restrict__ idx, int64_t nb,
+                                                          T* __restrict__ dst) {
   const int64_t total = (int64_t)rows * nb;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
@@ -26,56 +31,20 @@ __global__ __launch_bounds__(256) void gather_cols_kernel(const double* __restri
   }
 }
 
-__global__ __launch_bounds__(256) void widen_kernel(const float* __restrict__ w32, int64_t n, double* __restrict__ w64) {
+// Float32 -> Float64 (exact) or Float64 -> Float32 (rounds once, as `Float32.(x)` would)
+template <class S, class D>
+__global__ __launch_bounds__(256) void convert_kernel(const S* __restrict__ src, int64_t n, D* __restrict__ dst) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) w64[i] = (double)w32[i];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = (D)src[i];
 }
 
-__global__ __launch_bounds__(256) void gather_cols_f32_kernel(const float* __restrict__ src, int rows, const int64_t* __restrict__ idx,
-                                                              int64_t nb, float* __restrict__ dst) {
-  const int64_t total = (int64_t)rows * nb;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-    const int64_t j = e / rows;
-    const int r = (int)(e - j * rows);
-    dst[e] = src[r + (int64_t)rows * idx[j]];
-  }
-}
-__global__ __launch_bounds__(256) void narrow_kernel(const double* __restrict__ src, int64_t n, float* __restrict__ dst) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = (float)src[i];
-}
-
-// Flux 0.11.2 apply! + update!:  x .-= apply!(opt, x, g), state zero(x) (Float32), arithmetic in Float64
-// g32: the gradient arrays are Float32 (compute_dtype = SI_F32: g holds Float32 values) -- then `apply!` writes its step back
-// into the Float32 array `delta` (rounded) and `x .-= delta` is a Float32 subtraction; with a Float64 gradient the step stays
-// Float64 and x - step is rounded once on the store into x
+// the update rule (optimiser_update.h) on every element of the flat weight vector
 __global__ __launch_bounds__(256) void optimiser_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
                                                         const double* __restrict__ g, int64_t n, int kind, double eta,
                                                         double p1, double p2, double bp1, double bp2, int g32) {
-#pragma clang fp contract(off)
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const double gi = g[i];
-    double step;
-    if (kind == 0) {  // Descent: delta .*= eta
-      step = gi * eta;
-    } else if (kind == 1) {  // Momentum: v = rho*v - eta*delta; delta = -v
-      const float vn = (float)(p1 * (double)m[i] - eta * gi);
-      m[i] = vn;
-      step = -(double)vn;
-    } else {  // ADAM
-      const float mt = (float)(p1 * (double)m[i] + (1.0 - p1) * gi);
-      const float vt = (float)(p2 * (double)v[i] + (1.0 - p2) * (gi * gi));
-      m[i] = mt;
-      v[i] = vt;
-      step = (double)mt / (1.0 - bp1) / (sqrt((double)vt / (1.0 - bp2)) + 1e-8) * eta;
-    }
-    if (g32)
-      w[i] = w[i] - (float)step;
-    else
-      w[i] = (float)((double)w[i] - step);
-  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    optimiser_update(w, m, v, i, g[i], kind, eta, p1, p2, bp1, bp2, g32 != 0);
 }
 
 static int grid_for(int64_t n, int num_cu) {
@@ -84,12 +53,21 @@ static int grid_for(int64_t n, int num_cu) {
   return (int)(b < 1 ? 1 : b);
 }
 
-TrainState::~TrainState() { delete node; }
+template <class T>
+static void launch_gather_cols(hipStream_t st, const T* src, int rows, const int64_t* idx, int64_t nb, T* dst, int num_cu) {
+  hipLaunchKernelGGL(gather_cols_kernel<T>, dim3(grid_for((int64_t)rows * nb, num_cu)), dim3(256), 0, st, src, rows, idx, nb, dst);
+}
+template <class S, class D>
+static void launch_convert(hipStream_t st, const S* src, int64_t n, D* dst, int num_cu) {
+  hipLaunchKernelGGL((convert_kernel<S, D>), dim3(grid_for(n, num_cu)), dim3(256), 0, st, src, n, dst);
+}
+void launch_widen_f32_to_f64(hipStream_t st, const float* src, int64_t n, double* dst, int num_cu) { launch_convert(st, src, n, dst, num_cu); }
 
 void free_train(Ctx* c) {
   delete c->train;
   c->train = nullptr;
 }
+CtxCore::~CtxCore() { delete train; }
 
 // ---- value and gradient in fp32 (dense_forward<float> + the fp32 reverse sweep), shared by the training step and si_logdensity_grad
 bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const si_layer* layers, int L, bool fuse_tail, int64_t N, int32_t in_dim, int32_t out_dim,
@@ -168,15 +146,49 @@ int32_t dense_value_and_grad_f32(Ctx* ctx, hipStream_t st, const DenseSweepF32& 
   return SI_OK;
 }
 
-void launch_widen_f32_to_f64(hipStream_t st, const float* src, int64_t n, double* dst, int num_cu) {
-  hipLaunchKernelGGL(widen_kernel, dim3(grid_for(n, num_cu)), dim3(256), 0, st, src, n, dst);
-}
-
 }  // namespace si
 
 using namespace si;
 
 extern "C" {
+
+static int32_t train_setup_failed(si_ctx* ctx, int32_t code, const std::string& msg) {
+  free_train(ctx);
+  return fail(ctx, code, msg);
+}
+
+// What every set-up does first: the stream drains, the old state goes, the new one gets its route, its sizes, the optimiser's
+// parameters and the buffers every route has.  ok: those allocations succeeded (the caller adds its own and reports them together)
+static int32_t train_setup_begin(si_ctx* ctx, TrainRoute route, const si_layer* layers, int32_t L, int64_t N, int32_t in_dim, int32_t out_dim,
+                                 int64_t B_total, int64_t batch_max, int32_t opt_kind, double eta, double p1, double p2, bool& ok) {
+  SI_HIP(ctx, hipSetDevice(ctx->device));
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  free_train(ctx);
+  TrainState* t = ctx->train = new TrainState();
+  TrainOpt& o = t->opt;
+  TrainBatch& b = t->batch;
+  t->route = route;
+  t->layers.assign(layers, layers + L);
+  t->N = N; t->Btot = B_total; t->Bmax = batch_max; t->in_dim = in_dim; t->out_dim = out_dim;
+  o.kind = opt_kind; o.eta = eta; o.p1 = p1; o.p2 = p2; o.bp1 = p1; o.bp2 = p2;  // ADAM: beta powers start at beta
+  const size_t bm = (size_t)batch_max, nx = (size_t)in_dim * (size_t)B_total;
+  ok = (route == TrainRoute::DenseF32 ? t->f32.X.alloc(nx) && t->f32.Xb.alloc((size_t)in_dim * bm) : t->X.alloc(nx) && t->Xb.alloc((size_t)in_dim * bm)) &&
+       t->Y.alloc((size_t)out_dim * (size_t)B_total) && t->Yb.alloc((size_t)out_dim * bm) && b.idx.alloc(bm) && b.pin[0].alloc(bm) &&
+       b.pin[1].alloc(bm) && b.ev[0].create() && b.ev[1].create() && o.w32.alloc((size_t)N) && o.m32.alloc((size_t)N) &&
+       o.v32.alloc((size_t)N) && o.w64.alloc((size_t)pad_ld(N)) && o.gw.alloc((size_t)pad_ld(N)) && t->sse.alloc(1);
+  return SI_OK;
+}
+
+// ... and last, behind the route's own uploads: the weights, zero moments, a zero Float64 copy (queued)
+static hipError_t train_setup_upload(si_ctx* ctx, const float* w0) {
+  TrainOpt& o = ctx->train->opt;
+  const size_t n = (size_t)ctx->train->N;
+  hipError_t e = hipMemcpyAsync(o.w32, w0, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(o.m32, 0, n * sizeof(float), ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(o.v32, 0, n * sizeof(float), ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(o.w64, 0, (size_t)pad_ld(ctx->train->N) * sizeof(double), ctx->stream);
+  return e;
+}
 
 static int32_t train_setup_impl(si_ctx* ctx, const si_layer* layers, int32_t L, int64_t N, const float* w0, const void* Xv,
                                 const void* Yv, int32_t data_dtype, int32_t in_dim, int32_t out_dim, int64_t B_total, int64_t batch_max,
@@ -208,96 +220,59 @@ static int32_t train_setup_impl(si_ctx* ctx, const si_layer* layers, int32_t L, 
   if (fuse_tail) maxpart = std::max(maxpart, tail_bwd_part_elems(layers[L - 1].out, layers[L - 1].in));
   if (f32 && plan.has_conv)
     return fail(ctx, SI_ERR_INVALID, "si_train_setup_ex: compute_dtype = SI_F32 is implemented for Dense chains; Conv / MaxPool / flatten chains train in SI_F64");
-  SI_HIP(ctx, hipSetDevice(ctx->device));
-  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  free_train(ctx);
-  TrainState* t = new TrainState();
-  ctx->train = t;
-  t->layers.assign(layers, layers + L);
-  t->N = N; t->Btot = B_total; t->Bmax = batch_max; t->in_dim = in_dim; t->out_dim = out_dim;
-  t->opt = opt_kind; t->eta = eta; t->p1 = p1; t->p2 = p2; t->bp1 = p1; t->bp2 = p2;  // ADAM: beta powers start at beta
+  const TrainRoute route = plan.has_conv ? TrainRoute::Conv : f32 ? TrainRoute::DenseF32 : TrainRoute::DenseF64;
+  bool ok = false;
+  const int32_t rcb = train_setup_begin(ctx, route, layers, L, N, in_dim, out_dim, B_total, batch_max, opt_kind, eta, p1, p2, ok);
+  if (rcb != SI_OK) return rcb;
+  TrainState* t = ctx->train;
+  TrainDenseWs& dn = t->dense;
+  TrainConvWs& cv = t->conv;
   t->sse_blocks = sse_num_blocks((int64_t)out_dim * batch_max, ctx->num_cu);
-  t->fuse_tail = fuse_tail;
-  t->fuse_slots = fuse_tail ? dense_fused_slots(layers[L - 2].out) : 0;
-  t->f32 = f32;
+  dn.fuse_tail = fuse_tail;
+  dn.fuse_slots = fuse_tail ? dense_fused_slots(layers[L - 2].out) : 0;
   if (f32 && fuse_tail)   // (w32 is 256-byte aligned: a layer's W is 16-byte aligned iff w_off % 4 == 0)
-    t->fuse_slots = std::max(t->fuse_slots, dense_f32_fused_slots(layers[L - 2].out, layers[L - 2].in, layers[L - 2].w_off % 4 == 0));
-  t->hs = std::vector<DevBuf<double>>((size_t)L);
-  t->plan = plan;
+    dn.fuse_slots = std::max(dn.fuse_slots, dense_f32_fused_slots(layers[L - 2].out, layers[L - 2].in, layers[L - 2].w_off % 4 == 0));
+  dn.hs = std::vector<DevBuf<double>>((size_t)L);
+  cv.plan = plan;
+  cv.pidx = std::vector<DevBuf<uint8_t>>((size_t)L);
+  cv.scratch.pidx = cv.pidx.data();
   size_t nb = 1, nr = 1, nw = 1, nd = 1;
   if (plan.has_conv) net_scratch_sizes(plan, batch_max, ctx->num_cu, &nb, &nr, &nw, &nd);
-  bool ok = (!plan.has_conv || (t->wpack.alloc(plan.wpack_elems) && t->scratch.bwpart.alloc(nb) && t->scratch.rspart.alloc(nr) &&
-                                t->scratch.wt.alloc(nw) && t->scratch.dbtmp.alloc(nd))) &&
-            (!plan.input_spatial || t->Xc.alloc((size_t)plan.in_elems * batch_max)) &&
-            (f32 || (t->X.alloc((size_t)in_dim * B_total) && t->Xb.alloc((size_t)in_dim * batch_max))) &&
-            t->Y.alloc((size_t)out_dim * B_total) && t->Yb.alloc((size_t)out_dim * batch_max) &&
-            t->idx.alloc((size_t)batch_max) &&
-            t->idx_pin[0].alloc((size_t)batch_max) && t->idx_pin[1].alloc((size_t)batch_max) &&
-            t->idx_ev[0].create() && t->idx_ev[1].create() &&
-            t->w32.alloc((size_t)N) && t->m32.alloc((size_t)N) &&
-            t->v32.alloc((size_t)N) && t->w64.alloc((size_t)pad_ld(N)) && t->gw.alloc((size_t)pad_ld(N)) &&
-            (f32 || (t->delta[0].alloc((size_t)maxw * batch_max) && t->delta[1].alloc((size_t)maxw * batch_max) &&
-                     t->bwpart.alloc(maxpart) && t->rspart.alloc((size_t)rowsum_chunks() * maxw))) &&
-            t->ssepart.alloc((size_t)t->sse_blocks) && t->sse.alloc(1) &&
-            (!fuse_tail || t->part.alloc((size_t)t->fuse_slots * out_dim * batch_max));
-  t->pidx = std::vector<DevBuf<uint8_t>>((size_t)L);
-  if (f32 && ok)
-    ok = t->X32.alloc((size_t)in_dim * B_total) && t->Xb32.alloc((size_t)in_dim * batch_max) &&
-         sweep_f32_alloc(ctx, t->ws32, layers, L, fuse_tail, N, in_dim, out_dim, batch_max);
+  ok = ok && t->ssepart.alloc((size_t)t->sse_blocks) && (!fuse_tail || dn.part.alloc((size_t)dn.fuse_slots * out_dim * batch_max)) &&
+       (!plan.has_conv || (cv.wpack.alloc(plan.wpack_elems) && cv.scratch.bwpart.alloc(nb) && cv.scratch.rspart.alloc(nr) &&
+                           cv.scratch.wt.alloc(nw) && cv.scratch.dbtmp.alloc(nd))) &&
+       (!plan.input_spatial || cv.Xc.alloc((size_t)plan.in_elems * batch_max)) &&
+       (f32 ? sweep_f32_alloc(ctx, t->f32.ws, layers, L, fuse_tail, N, in_dim, out_dim, batch_max)
+            : dn.delta[0].alloc((size_t)maxw * batch_max) && dn.delta[1].alloc((size_t)maxw * batch_max) && dn.bwpart.alloc(maxpart) &&
+                  dn.rspart.alloc((size_t)rowsum_chunks() * maxw));
   for (int l = 0; l < L && ok && !f32; ++l) {
     if (plan.has_conv && net_grad_fused(plan, (size_t)l))   // Conv + MaxPool as one kernel: a byte index instead of the activation
-      ok = t->pidx[(size_t)l].alloc(net_pidx_bytes(plan, (size_t)l, batch_max));
+      ok = cv.pidx[(size_t)l].alloc(net_pidx_bytes(plan, (size_t)l, batch_max));
     else
-      ok = t->hs[(size_t)l].alloc((size_t)plan.L[(size_t)l].out_elems * batch_max);
+      ok = dn.hs[(size_t)l].alloc((size_t)plan.L[(size_t)l].out_elems * batch_max);
   }
-  t->scratch.pidx = t->pidx.data();
-  if (!ok) {
-    free_train(ctx);
-    return fail(ctx, SI_ERR_NOMEM, "si_train_setup: device allocation failed");
+  if (!ok) return train_setup_failed(ctx, SI_ERR_NOMEM, "si_train_setup: device allocation failed");
+  // the data in the element type the step computes in (X) / sums the loss in (Y: fp64 always); one conversion at set-up where
+  // the caller's type differs (Float32 -> Float64 is exact; Float64 -> Float32 rounds once, as `Float32.(X)` would)
+  const size_t nx = (size_t)in_dim * B_total, ny = (size_t)out_dim * B_total;
+  const size_t esz = data_dtype == SI_F32 ? 4 : 8;
+  DevBuf<char> stage;
+  const bool x_conv = (data_dtype == SI_F32) != f32, y_conv = data_dtype == SI_F32;
+  if ((x_conv || y_conv) && !stage.alloc(std::max(nx, ny) * esz))
+    return train_setup_failed(ctx, SI_ERR_NOMEM, "si_train_setup: device allocation failed");
+  hipStream_t st = ctx->stream;
+  hipError_t e = hipMemcpyAsync(x_conv ? (void*)stage.get() : f32 ? (void*)t->f32.X.get() : (void*)t->X.get(), Xv, nx * esz, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && x_conv) {
+    if (f32) launch_convert(st, reinterpret_cast<const double*>(stage.get()), (int64_t)nx, t->f32.X.get(), ctx->num_cu);
+    else launch_widen_f32_to_f64(st, reinterpret_cast<const float*>(stage.get()), (int64_t)nx, t->X, ctx->num_cu);
   }
-  {
-    // the data in the element type the step computes in (X) / sums the loss in (Y: fp64 always); one conversion at set-up where
-    // the caller's type differs (Float32 -> Float64 is exact; Float64 -> Float32 rounds once, as `Float32.(X)` would)
-    const size_t nx = (size_t)in_dim * B_total, ny = (size_t)out_dim * B_total;
-    const size_t esz = data_dtype == SI_F32 ? 4 : 8;
-    DevBuf<char> stage;
-    const bool x_conv = (data_dtype == SI_F32) != f32, y_conv = data_dtype == SI_F32;
-    if ((x_conv || y_conv) && !stage.alloc(std::max(nx, ny) * esz)) {
-      free_train(ctx);
-      return fail(ctx, SI_ERR_NOMEM, "si_train_setup: device allocation failed");
-    }
-    hipError_t e = hipSuccess;
-    const int gx = grid_for((int64_t)nx, ctx->num_cu), gy = grid_for((int64_t)ny, ctx->num_cu);
-    if (!x_conv) {
-      e = hipMemcpyAsync(f32 ? (void*)t->X32.get() : (void*)t->X.get(), Xv, nx * esz, hipMemcpyHostToDevice, ctx->stream);
-    } else {
-      e = hipMemcpyAsync(stage, Xv, nx * esz, hipMemcpyHostToDevice, ctx->stream);
-      if (e == hipSuccess) {
-        if (f32) hipLaunchKernelGGL(narrow_kernel, dim3(gx), dim3(256), 0, ctx->stream, reinterpret_cast<const double*>(stage.get()), (int64_t)nx, t->X32);
-        else hipLaunchKernelGGL(widen_kernel, dim3(gx), dim3(256), 0, ctx->stream, reinterpret_cast<const float*>(stage.get()), (int64_t)nx, t->X);
-      }
-    }
-    if (e == hipSuccess) {
-      if (!y_conv) {
-        e = hipMemcpyAsync(t->Y, Yv, ny * 8, hipMemcpyHostToDevice, ctx->stream);
-      } else {
-        e = hipStreamSynchronize(ctx->stream);   // (the staging buffer is reused)
-        if (e == hipSuccess) e = hipMemcpyAsync(stage, Yv, ny * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) hipLaunchKernelGGL(widen_kernel, dim3(gy), dim3(256), 0, ctx->stream, reinterpret_cast<const float*>(stage.get()), (int64_t)ny, t->Y);
-      }
-    }
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    stage.reset();
-    if (e != hipSuccess || e2 != hipSuccess) {
-      free_train(ctx);
-      return fail(ctx, SI_ERR_HIP, std::string("si_train_setup: ") + hipGetErrorString(e != hipSuccess ? e : e2));
-    }
-  }
-  SI_HIP(ctx, hipMemcpyAsync(t->w32, w0, (size_t)N * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  SI_HIP(ctx, hipMemsetAsync(t->m32, 0, (size_t)N * sizeof(float), ctx->stream));
-  SI_HIP(ctx, hipMemsetAsync(t->v32, 0, (size_t)N * sizeof(float), ctx->stream));
-  SI_HIP(ctx, hipMemsetAsync(t->w64, 0, (size_t)pad_ld(N) * sizeof(double), ctx->stream));
-  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (e == hipSuccess && y_conv) e = hipStreamSynchronize(st);   // (the staging buffer is reused)
+  if (e == hipSuccess) e = hipMemcpyAsync(y_conv ? (void*)stage.get() : (void*)t->Y.get(), Yv, ny * esz, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && y_conv) launch_widen_f32_to_f64(st, reinterpret_cast<const float*>(stage.get()), (int64_t)ny, t->Y, ctx->num_cu);
+  if (e == hipSuccess) e = train_setup_upload(ctx, w0);
+  const hipError_t e2 = hipStreamSynchronize(st);
+  if (e != hipSuccess || e2 != hipSuccess)
+    return train_setup_failed(ctx, SI_ERR_HIP, std::string("si_train_setup: ") + hipGetErrorString(e != hipSuccess ? e : e2));
   return SI_OK;
 }
 
@@ -317,20 +292,7 @@ int32_t si_train_setup_ex(si_ctx* ctx, const si_layer* layers, int32_t L, int64_
 int32_t si_train_compute_dtype(si_ctx* ctx, int32_t* out) {
   if (!ctx) return SI_ERR_INVALID;
   if (!ctx->train || !out) return fail(ctx, SI_ERR_STATE, "si_train_compute_dtype: no training state / NULL output");
-  *out = ctx->train->f32 ? SI_F32 : SI_F64;
-  return SI_OK;
-}
-
-// idx is caller-owned: copied into a pinned buffer, shipped asynchronously; the buffer is free again once its event has
-// passed (two steps later at the earliest) -- no synchronisation of the stream, the call returns while the GPU works
-static int32_t stage_indices(si_ctx* ctx, TrainState* t, const int64_t* idx, int64_t nb) {
-  const int b = t->idx_slot;
-  t->idx_slot ^= 1;
-  if (t->idx_busy[b]) SI_HIP(ctx, hipEventSynchronize(t->idx_ev[b]));
-  std::memcpy(t->idx_pin[b], idx, (size_t)nb * sizeof(int64_t));
-  SI_HIP(ctx, hipMemcpyAsync(t->idx, t->idx_pin[b], (size_t)nb * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-  SI_HIP(ctx, hipEventRecord(t->idx_ev[b], ctx->stream));
-  t->idx_busy[b] = true;
+  *out = ctx->train->route == TrainRoute::DenseF32 ? SI_F32 : SI_F64;
   return SI_OK;
 }
 
@@ -359,106 +321,149 @@ int32_t si_train_setup_node(si_ctx* ctx, const si_layer* layers, int32_t L, int6
   if (8.0 * (double)batch_max * ((double)a.max_steps * (double)(d + 2) + (double)N) > SI_BATCH_BYTES)
     return bad("the step record (batch_max * max_steps * (d + 2) doubles) and the gradient slices (batch_max * N) do not fit the "
                "2 GiB workspace budget: lower max_steps or the batch size");
-  SI_HIP(ctx, hipSetDevice(ctx->device));
-  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  free_train(ctx);
-  TrainState* t = new TrainState();
-  ctx->train = t;
-  NodeTrain* nt = t->node = new NodeTrain();
-  t->layers.assign(layers, layers + L);
-  t->N = N; t->Btot = f; t->Bmax = batch_max; t->in_dim = d; t->out_dim = d * S;
-  t->opt = opt_kind; t->eta = eta; t->p1 = p1; t->p2 = p2; t->bp1 = p1; t->bp2 = p2;  // ADAM: beta powers start at beta
+  bool ok = false;
+  const int32_t rcb = train_setup_begin(ctx, TrainRoute::Node, layers, L, N, d, d * S, f, batch_max, opt_kind, eta, p1, p2, ok);
+  if (rcb != SI_OK) return rcb;
+  TrainState* t = ctx->train;
+  NodeTrain* nt = &t->node;
   nt->args = a;
   nt->penalty_div = penalty_div;
   nt->wsq_blocks = sse_num_blocks(N, ctx->num_cu);
   const size_t bm = (size_t)batch_max;
-  const bool ok = t->X.alloc((size_t)d * (size_t)f) && t->Xb.alloc((size_t)d * bm) && t->Y.alloc((size_t)t->out_dim * (size_t)f) &&
-                  t->Yb.alloc((size_t)t->out_dim * bm) && t->idx.alloc(bm) && t->idx_pin[0].alloc(bm) && t->idx_pin[1].alloc(bm) &&
-                  t->idx_ev[0].create() && t->idx_ev[1].create() && t->w32.alloc((size_t)N) && t->m32.alloc((size_t)N) &&
-                  t->v32.alloc((size_t)N) && t->w64.alloc((size_t)pad_ld(N)) && t->gw.alloc((size_t)pad_ld(N)) && t->sse.alloc(1) &&
-                  nt->ts.alloc((size_t)S) && nt->ssep.alloc(bm) && nt->rec.alloc(bm * (size_t)a.max_steps * (size_t)(d + 2)) &&
-                  nt->slices.alloc(bm * (size_t)N) && nt->cnt.alloc(3 * bm) && nt->wsq.alloc(1) &&
-                  nt->wsqpart.alloc((size_t)nt->wsq_blocks) && nt->fail.alloc(3);
-  if (!ok) {
-    free_train(ctx);
-    return fail(ctx, SI_ERR_NOMEM, "si_train_setup_node: device allocation failed (the step record: lower max_steps or the batch size)");
-  }
+  ok = ok && nt->ts.alloc((size_t)S) && nt->ssep.alloc(bm) && nt->rec.alloc(bm * (size_t)a.max_steps * (size_t)(d + 2)) &&
+       nt->slices.alloc(bm * (size_t)N) && nt->cnt.alloc(3 * bm) && nt->wsq.alloc(1) && nt->wsqpart.alloc((size_t)nt->wsq_blocks) &&
+       nt->fail.alloc(3);
+  if (!ok)
+    return train_setup_failed(ctx, SI_ERR_NOMEM, "si_train_setup_node: device allocation failed (the step record: lower max_steps or the batch size)");
   hipStream_t st = ctx->stream;
   hipError_t e = hipMemcpyAsync(t->X, U0, (size_t)d * (size_t)f * sizeof(double), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(t->Y, Y, (size_t)t->out_dim * (size_t)f * sizeof(double), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(nt->ts, ts, (size_t)S * sizeof(double), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(t->w32, w0, (size_t)N * sizeof(float), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(t->m32, 0, (size_t)N * sizeof(float), st);
-  if (e == hipSuccess) e = hipMemsetAsync(t->v32, 0, (size_t)N * sizeof(float), st);
-  if (e == hipSuccess) e = hipMemsetAsync(t->w64, 0, (size_t)pad_ld(N) * sizeof(double), st);
-  if (e == hipSuccess) e = hipMemsetAsync(t->gw, 0, (size_t)pad_ld(N) * sizeof(double), st);
+  if (e == hipSuccess) e = train_setup_upload(ctx, w0);
+  if (e == hipSuccess) e = hipMemsetAsync(t->opt.gw, 0, (size_t)pad_ld(N) * sizeof(double), st);
   if (e == hipSuccess) e = hipMemsetAsync(t->sse, 0, sizeof(double), st);
   if (e == hipSuccess) e = hipMemsetAsync(nt->fail, 0, 3 * sizeof(int64_t), st);
   if (e == hipSuccess) {
-    launch_widen_f32_to_f64(st, t->w32, N, t->w64, ctx->num_cu);   // the first step's solve reads the Float64 copy
+    launch_widen_f32_to_f64(st, t->opt.w32, N, t->opt.w64, ctx->num_cu);   // the first step's solve reads the Float64 copy
     e = hipGetLastError();
   }
   const hipError_t e2 = hipStreamSynchronize(st);
-  if (e != hipSuccess || e2 != hipSuccess) {
-    free_train(ctx);
-    return fail(ctx, SI_ERR_HIP, std::string("si_train_setup_node: ") + hipGetErrorString(e != hipSuccess ? e : e2));
-  }
+  if (e != hipSuccess || e2 != hipSuccess)
+    return train_setup_failed(ctx, SI_ERR_HIP, std::string("si_train_setup_node: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+  return SI_OK;
+}
+
+static bool is_node(const si_ctx* ctx) { return ctx->train && ctx->train->route == TrainRoute::Node; }
+
+// the NeuralODE route's failure record, read back (synchronises): [0] the 1-based step that failed first (0: none), [1] trajectory, [2] status
+static int32_t node_fail_record(si_ctx* ctx, int64_t rec[3]) {
+  SI_HIP(ctx, hipSetDevice(ctx->device));
+  SI_HIP(ctx, hipMemcpyAsync(rec, ctx->train->node.fail, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SI_OK;
 }
 
 int32_t si_train_node_info(si_ctx* ctx, int32_t* active_out, int32_t* G_out, int64_t* failed_step_out, int64_t* failed_traj_out,
                            int32_t* failed_status_out) {
   if (!ctx) return SI_ERR_INVALID;
-  const NodeTrain* nt = ctx->train ? ctx->train->node : nullptr;
+  const bool node = is_node(ctx);
   int64_t rec[3] = {0, 0, 0};
-  if (nt) {
-    SI_HIP(ctx, hipSetDevice(ctx->device));
-    SI_HIP(ctx, hipMemcpyAsync(rec, nt->fail, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
-    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  if (active_out) *active_out = nt ? 1 : 0;
-  if (G_out) *G_out = nt ? nt->args.G : 0;
+  if (node)
+    if (const int32_t rc = node_fail_record(ctx, rec)) return rc;
+  if (active_out) *active_out = node ? 1 : 0;
+  if (G_out) *G_out = node ? ctx->train->node.args.G : 0;
   if (failed_step_out) *failed_step_out = rec[0] != 0 ? rec[0] : -1;
   if (failed_traj_out) *failed_traj_out = rec[0] != 0 ? rec[1] : -1;
   if (failed_status_out) *failed_status_out = rec[0] != 0 ? (int32_t)rec[2] : 0;
   return SI_OK;
 }
 
-// the batch's columns, ||W||^2, the forward with record, the reverse kernel and the tail, all queued on the context's stream
-static int32_t node_train_launches(si_ctx* ctx, const char* who, const int64_t* idx, int64_t nb, bool apply) {
+// ADAM's beta powers after one more update: the running product, one multiplication per update
+static void advance_beta_powers(TrainOpt& o) {
+  if (o.kind == 2) o.bp1 *= o.p1, o.bp2 *= o.p2;
+}
+
+// after a synchronisation of the stream: a failure record the caller has not been told about yet -> SI_ERR_INVALID, once
+int32_t train_node_report(si_ctx* ctx, const char* who) {
+  if (!is_node(ctx)) return SI_OK;
+  NodeTrain* nt = &ctx->train->node;
+  if (nt->reported || nt->checked == nt->steps) return SI_OK;
+  int64_t rec[3] = {0, 0, 0};
+  if (const int32_t rc = node_fail_record(ctx, rec)) return rc;
+  nt->checked = nt->steps;
+  if (rec[0] == 0) return SI_OK;
+  nt->reported = true;
+  TrainOpt& o = ctx->train->opt;
+  o.grad_ready = false;
+  o.bp1 = o.p1, o.bp2 = o.p2;   // the beta powers as the last step that was taken left them
+  for (int64_t k = 1; k < rec[0] && o.kind == 2; ++k) advance_beta_powers(o);
+  return fail(ctx, SI_ERR_INVALID, std::string(who) + ": NeuralODE training step " + std::to_string(rec[0]) + ": trajectory " +
+                                       std::to_string(rec[1]) + " of its batch ended with status " + std::to_string(rec[2]) +
+                                       " (1: max_steps reached, 2: a non-finite state); that step and every later one left the "
+                                       "weights and the optimiser state as they were");
+}
+
+// ---- the batch stage of every route: the observations idx[0..nb) of the set-up's data, in the route's element types
+struct TrainBatchView {
+  const double* X;
+  const float* X32;
+  const double* Y;
+};
+// idx is caller-owned: copied into a pinned buffer, shipped asynchronously; the buffer is free again once its event has
+// passed (two steps later at the earliest) -- no synchronisation of the stream, the call returns while the GPU works.
+// prof: a scope of class SI_K_SSE opened in front of the first launch and left open for the caller's launches behind it
+static int32_t train_batch(si_ctx* ctx, const char* who, const int64_t* idx, int64_t nb, TrainBatchView& v,
+                           std::optional<ProfScope>* prof = nullptr) {
   TrainState* t = ctx->train;
-  NodeTrain* nt = t->node;
-  // (a failure the caller has been told about: the set-up takes no further steps, the device's would be no-ops)
-  if (nt->reported) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": an earlier NeuralODE training step failed (si_train_node_info): set up again");
+  TrainBatch& b = t->batch;
   if (!idx || nb <= 0 || nb > t->Bmax) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": bad batch");
-  bool in_order = true;
+  bool in_order = true;   // idx = 0, 1, ..., nb-1 (a full batch of an unshuffled DataLoader): the data are used in place
   for (int64_t j = 0; j < nb; ++j) {
     if (idx[j] < 0 || idx[j] >= t->Btot)
       return fail(ctx, SI_ERR_INVALID, std::string(who) + ": BoundsError: batch index out of range");
     in_order = in_order && idx[j] == j;
   }
   SI_HIP(ctx, hipSetDevice(ctx->device));
+  if (prof) prof->emplace(ctx, SI_K_SSE, 0.0, 0.0);
+  v = TrainBatchView{t->X, t->f32.X, t->Y};
+  if (in_order) return SI_OK;
+  const int s = b.slot;
+  b.slot ^= 1;
+  if (b.busy[s]) SI_HIP(ctx, hipEventSynchronize(b.ev[s]));
+  std::memcpy(b.pin[s], idx, (size_t)nb * sizeof(int64_t));
+  SI_HIP(ctx, hipMemcpyAsync(b.idx, b.pin[s], (size_t)nb * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  SI_HIP(ctx, hipEventRecord(b.ev[s], ctx->stream));
+  b.busy[s] = true;
+  if (t->route == TrainRoute::DenseF32)
+    launch_gather_cols(ctx->stream, t->f32.X.get(), t->in_dim, b.idx.get(), nb, t->f32.Xb.get(), ctx->num_cu);
+  else
+    launch_gather_cols(ctx->stream, t->X.get(), t->in_dim, b.idx.get(), nb, t->Xb.get(), ctx->num_cu);
+  launch_gather_cols(ctx->stream, t->Y.get(), t->out_dim, b.idx.get(), nb, t->Yb.get(), ctx->num_cu);
+  v = TrainBatchView{t->Xb, t->f32.Xb, t->Yb};
+  return SI_OK;
+}
+
+// the NeuralODE route: the batch's columns, ||W||^2, the forward with record, the reverse kernel and the tail -- with `apply` the
+// update is fused into it (si_train_step) -- all queued on the context's stream
+static int32_t node_gradient(si_ctx* ctx, const char* who, const int64_t* idx, int64_t nb, bool apply) {
+  TrainState* t = ctx->train;
+  TrainOpt& o = t->opt;
+  NodeTrain* nt = &t->node;
+  // (a failure the caller has been told about: the set-up takes no further steps, the device's would be no-ops)
+  if (nt->reported) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": an earlier NeuralODE training step failed (si_train_node_info): set up again");
   hipStream_t st = ctx->stream;
   const int64_t N = t->N, Bmax = t->Bmax;
-  const double *U0b = t->X, *Yb = t->Y;
+  TrainBatchView v;
   {
-    ProfScope ps(ctx, SI_K_SSE, 0.0, 0.0);
-    if (!in_order) {
-      const int32_t rcs = stage_indices(ctx, t, idx, nb);
-      if (rcs != SI_OK) return rcs;
-      hipLaunchKernelGGL(gather_cols_kernel, dim3(grid_for((int64_t)t->in_dim * nb, ctx->num_cu)), dim3(256), 0, st, t->X, t->in_dim,
-                         t->idx, nb, t->Xb);
-      hipLaunchKernelGGL(gather_cols_kernel, dim3(grid_for((int64_t)t->out_dim * nb, ctx->num_cu)), dim3(256), 0, st, t->Y, t->out_dim,
-                         t->idx, nb, t->Yb);
-      U0b = t->Xb;
-      Yb = t->Yb;
-    }
-    launch_sse(st, t->w64, nullptr, N, nt->wsqpart, nt->wsq_blocks, nt->wsq, 1, pad_ld(N));   // ||W||^2, as the density forms it
+    std::optional<ProfScope> ps;
+    const int32_t rcb = train_batch(ctx, who, idx, nb, v, &ps);
+    if (rcb != SI_OK) return rcb;
+    launch_sse(st, o.w64, nullptr, N, nt->wsqpart, nt->wsq_blocks, nt->wsq, 1, pad_ld(N));   // ||W||^2, as the density forms it
     SI_HIP(ctx, hipMemsetAsync(nt->slices, 0, (size_t)nb * (size_t)N * sizeof(double), st));     // "from 0.0"
   }
   NodeArgs a = nt->args;
-  a.w = t->w64, a.ldw = pad_ld(N);
-  a.U0 = U0b, a.Y = Yb, a.f = nb, a.ts = nt->ts;
+  a.w = o.w64, a.ldw = pad_ld(N);
+  a.U0 = v.X, a.Y = v.Y, a.f = nb, a.ts = nt->ts;
   a.sse_p = nt->ssep, a.U_out = nullptr;
   a.nacc = nt->cnt, a.nrej = nt->cnt + Bmax, a.status = nt->cnt + 2 * Bmax;
   a.rec = nt->rec, a.gsl = nt->slices;
@@ -472,160 +477,94 @@ static int32_t node_train_launches(si_ctx* ctx, const char* who, const int64_t* 
   }
   {
     ProfScope ps(ctx, SI_K_RECON, 0.0, 0.0);   // (the tail: gw, the loss, the update and the refreshed Float64 weights)
-    const NodeTailArgs ta{nt->slices, nt->ssep, nt->wsq, a.status, nb, N, nt->steps + 1, nt->penalty_div, t->w32, t->m32, t->v32,
-                          t->w64, t->gw, t->sse, nt->fail, t->opt, t->eta, t->p1, t->p2, t->bp1, t->bp2};
+    const NodeTailArgs ta{nt->slices, nt->ssep, nt->wsq, a.status, nb, N, nt->steps + 1, nt->penalty_div, o.w32, o.m32, o.v32,
+                          o.w64, o.gw, t->sse, nt->fail, o.kind, o.eta, o.p1, o.p2, o.bp1, o.bp2};
     launch_node_train_tail(st, ta, apply);
   }
   SI_HIP(ctx, hipGetLastError());
+  nt->steps += 1;
   return SI_OK;
 }
 
-// after a synchronisation of the stream: a failure record the caller has not been told about yet -> SI_ERR_INVALID, once
-int32_t train_node_report(si_ctx* ctx, const char* who) {
-  NodeTrain* nt = ctx->train ? ctx->train->node : nullptr;
-  if (!nt || nt->reported || nt->checked == nt->steps) return SI_OK;
-  int64_t rec[3] = {0, 0, 0};
-  SI_HIP(ctx, hipSetDevice(ctx->device));
-  SI_HIP(ctx, hipMemcpyAsync(rec, nt->fail, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
-  SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  nt->checked = nt->steps;
-  if (rec[0] == 0) return SI_OK;
-  nt->reported = true;
-  TrainState* t = ctx->train;
-  t->grad_ready = false;
-  t->bp1 = t->p1, t->bp2 = t->p2;   // the beta powers as the last step that was taken left them
-  for (int64_t k = 1; k < rec[0] && t->opt == 2; ++k) t->bp1 *= t->p1, t->bp2 *= t->p2;
-  return fail(ctx, SI_ERR_INVALID, std::string(who) + ": NeuralODE training step " + std::to_string(rec[0]) + ": trajectory " +
-                                       std::to_string(rec[1]) + " of its batch ended with status " + std::to_string(rec[2]) +
-                                       " (1: max_steps reached, 2: a non-finite state); that step and every later one left the "
-                                       "weights and the optimiser state as they were");
-}
-
-// forward + reverse sweep of the mse cost on the observations idx[0..nb): the gradient w.r.t. the flat weights, scaled
-// as if the batch were part of d_total = out_dim * (observations of the WHOLE batch), is left in t->gw; t->sse holds the
-// local sum of squared errors
-static int32_t train_gradient(si_ctx* ctx, const char* who, const int64_t* idx, int64_t nb, double d_total) {
+// The gradient of the route's cost on the observations idx[0..nb), left in opt.gw, the sum of squared errors (Node: the loss) in
+// t->sse.  The mse routes scale it as if the batch were part of d_total = out_dim * (observations of the WHOLE batch)
+static int32_t train_gradient(si_ctx* ctx, const char* who, const int64_t* idx, int64_t nb, double d_total, bool node_apply) {
   TrainState* t = ctx->train;
   if (!t) return fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_train_setup first");
-  if (!idx || nb <= 0 || nb > t->Bmax) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": bad batch");
-  bool in_order = true;   // idx = 0, 1, ..., nb-1 (a full batch of an unshuffled DataLoader): the data are used in place
-  for (int64_t j = 0; j < nb; ++j) {
-    if (idx[j] < 0 || idx[j] >= t->Btot)
-      return fail(ctx, SI_ERR_INVALID, std::string(who) + ": BoundsError: batch index out of range");
-    in_order = in_order && idx[j] == j;
-  }
-  SI_HIP(ctx, hipSetDevice(ctx->device));
+  if (t->route == TrainRoute::Node) return node_gradient(ctx, who, idx, nb, node_apply);
+  TrainOpt& o = t->opt;
+  TrainDenseWs& dn = t->dense;
+  TrainBatchView v;
+  const int32_t rcb = train_batch(ctx, who, idx, nb, v);
+  if (rcb != SI_OK) return rcb;
   hipStream_t st = ctx->stream;
   const int64_t N = t->N;
   const size_t nl = t->layers.size();
-  const double *Xb = t->X, *Yb = t->Y;
-  const float* Xb32 = t->X32;
-  if (!in_order) {
-    const int32_t rcs = stage_indices(ctx, t, idx, nb);
-    if (rcs != SI_OK) return rcs;
-    if (t->f32) {
-      hipLaunchKernelGGL(gather_cols_f32_kernel, dim3(grid_for((int64_t)t->in_dim * nb, ctx->num_cu)), dim3(256), 0, st, t->X32,
-                         t->in_dim, t->idx, nb, t->Xb32);
-      Xb32 = t->Xb32;
-    } else {
-      hipLaunchKernelGGL(gather_cols_kernel, dim3(grid_for((int64_t)t->in_dim * nb, ctx->num_cu)), dim3(256), 0, st, t->X,
-                         t->in_dim, t->idx, nb, t->Xb);
-    }
-    hipLaunchKernelGGL(gather_cols_kernel, dim3(grid_for((int64_t)t->out_dim * nb, ctx->num_cu)), dim3(256), 0, st, t->Y,
-                       t->out_dim, t->idx, nb, t->Yb);
-    Xb = t->Xb;
-    Yb = t->Yb;
-  }
-  hipLaunchKernelGGL(widen_kernel, dim3(grid_for(N, ctx->num_cu)), dim3(256), 0, st, t->w32, N, t->w64);
+  launch_widen_f32_to_f64(st, o.w32, N, o.w64, ctx->num_cu);
   const int sse_blocks = sse_num_blocks((int64_t)t->out_dim * nb, ctx->num_cu);
   const double scale = -2.0 / d_total;   // d mse / d yhat = 2 (yhat - y) / d
-  if (t->f32) {
+  int32_t rc = SI_OK;
+  if (t->route == TrainRoute::DenseF32) {
     // ---- the step in the caller's precision: a Float32 model on Float32 data is a Float32 Zygote pass in the reference
     // (src/subspace_construction.jl:39-43).  fp32 operands and activations on v_mfma_f32_32x32x2_f32; fp64 for the head's
     // partial sums, the loss and every sum over the batch (rounded once into the Float32 gradient).
-    DenseSweepF32 sw{t->layers.data(), nl, t->fuse_tail, t->w32, t->w64, Xb32, Yb, &t->ws32, t->part, t->ssepart, t->sse, sse_blocks, nb, N,
+    DenseSweepF32 sw{t->layers.data(), nl, dn.fuse_tail, o.w32, o.w64, v.X32, v.Y, &t->f32.ws, dn.part, t->ssepart, t->sse, sse_blocks, nb, N,
                      scale};
-    const int32_t rcs = dense_value_and_grad_f32(ctx, st, sw);
-    if (rcs != SI_OK) return rcs;
+    if ((rc = dense_value_and_grad_f32(ctx, st, sw)) != SI_OK) return rc;
     // the gradient as the optimiser and the data-parallel all-reduce see it: fp64 words holding the Float32 values
-    hipLaunchKernelGGL(widen_kernel, dim3(grid_for(N, ctx->num_cu)), dim3(256), 0, st, t->ws32.gw32, N, t->gw);
-    SI_HIP(ctx, hipGetLastError());
-    t->grad_ready = true;
-    return SI_OK;
-  }
-  if (t->plan.has_conv) {
+    launch_widen_f32_to_f64(st, t->f32.ws.gw32, N, o.gw, ctx->num_cu);
+  } else if (t->route == TrainRoute::Conv) {
     // chains with Conv / MaxPool / flatten layers: the generic forward / reverse sweep of capi_net.hip
-    const NetPlan& p = t->plan;
-    const double* xin = Xb;
-    if (p.input_spatial) {
-      net_input(ctx, p, Xb, t->Xc, nb);
-      xin = t->Xc;
-    }
-    const NetValueGrad vg{&p, t->w64, xin, Yb, nb, t->hs.data(), t->wpack, t->ssepart, sse_blocks, t->sse, {t->delta[0], t->delta[1]}, t->gw,
-                          &t->scratch, N, scale, 0.0};
-    const int32_t rc = net_value_and_grad(ctx, vg);
-    if (rc != SI_OK) return rc;
+    const NetPlan& p = t->conv.plan;
+    if (p.input_spatial) net_input(ctx, p, v.X, t->conv.Xc, nb);
+    const NetValueGrad vg{&p, o.w64, p.input_spatial ? t->conv.Xc.get() : v.X, v.Y, nb, dn.hs.data(), t->conv.wpack, t->ssepart, sse_blocks, t->sse,
+                          {dn.delta[0], dn.delta[1]}, o.gw, &t->conv.scratch, N, scale, 0.0};
+    if ((rc = net_value_and_grad(ctx, vg)) != SI_OK) return rc;
   } else {
-    const DenseValueGrad vg{{t->layers.data(), nl, t->fuse_tail, t->w64, Xb, t->hs.data(), {t->delta[0], t->delta[1]}, t->gw, t->rspart,
-                             t->bwpart, nb},
-                            Yb, t->fuse_slots, t->part, t->ssepart, t->sse, sse_blocks, N, scale, false};
-    const int32_t rc = dense_value_and_grad_f64(ctx, st, vg);
-    if (rc != SI_OK) return rc;
+    const DenseValueGrad vg{{t->layers.data(), nl, dn.fuse_tail, o.w64, v.X, dn.hs.data(), {dn.delta[0], dn.delta[1]}, o.gw, dn.rspart,
+                             dn.bwpart, nb},
+                            v.Y, dn.fuse_slots, dn.part, t->ssepart, t->sse, sse_blocks, N, scale, false};
+    if ((rc = dense_value_and_grad_f64(ctx, st, vg)) != SI_OK) return rc;
   }
   SI_HIP(ctx, hipGetLastError());
-  t->grad_ready = true;
+  o.grad_ready = true;
   return SI_OK;
 }
 
-// Flux.update!(opt, ps, gs) from the gradient in t->gw
+// Flux.update!(opt, ps, gs) from the gradient in opt.gw
 static int32_t train_apply(si_ctx* ctx) {
   TrainState* t = ctx->train;
-  hipLaunchKernelGGL(optimiser_kernel, dim3(grid_for(t->N, ctx->num_cu)), dim3(256), 0, ctx->stream, t->w32, t->m32, t->v32,
-                     t->gw, t->N, t->opt, t->eta, t->p1, t->p2, t->bp1, t->bp2, t->f32 ? 1 : 0);
+  TrainOpt& o = t->opt;
+  hipLaunchKernelGGL(optimiser_kernel, dim3(grid_for(t->N, ctx->num_cu)), dim3(256), 0, ctx->stream, o.w32, o.m32, o.v32, o.gw, t->N,
+                     o.kind, o.eta, o.p1, o.p2, o.bp1, o.bp2, t->route == TrainRoute::DenseF32 ? 1 : 0);
   SI_HIP(ctx, hipGetLastError());
-  if (t->opt == 2) {
-    t->bp1 *= t->p1;
-    t->bp2 *= t->p2;
-  }
-  t->grad_ready = false;
+  advance_beta_powers(o);
+  o.grad_ready = false;
   return SI_OK;
 }
 
-// si_train_step on a NeuralODE set-up: one pass of launches ending in the tail kernel with the update; nothing synchronises
-// unless the loss is asked for
-static int32_t node_train_step(si_ctx* ctx, const int64_t* idx, int64_t nb, double* loss_out) {
-  TrainState* t = ctx->train;
-  NodeTrain* nt = t->node;
-  int32_t rc = node_train_launches(ctx, "si_train_step", idx, nb, /*apply=*/true);
-  if (rc != SI_OK) return rc;
-  nt->steps += 1;
-  if (t->opt == 2) {   // (a failed step does not advance them: train_node_report rewinds)
-    t->bp1 *= t->p1;
-    t->bp2 *= t->p2;
-  }
-  t->grad_ready = false;
-  if (loss_out) {
-    SI_HIP(ctx, hipMemcpyAsync(loss_out, t->sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rc = train_node_report(ctx, "si_train_step")) != SI_OK) return rc;
-  }
-  return SI_OK;
-}
-
+// batch, gradient by route, update.  A NeuralODE's update is fused into its tail kernel: one pass of launches, and nothing
+// synchronises unless the loss is asked for
 int32_t si_train_step(si_ctx* ctx, const int64_t* idx, int64_t nb, double* loss_out) {
   if (!ctx) return SI_ERR_INVALID;
   TrainState* t = ctx->train;
-  if (t && t->node) return node_train_step(ctx, idx, nb, loss_out);
+  const bool node = is_node(ctx);
   const double d = t ? (double)t->out_dim * (double)nb : 1.0;
-  int32_t rc = train_gradient(ctx, "si_train_step", idx, nb, d);
+  int32_t rc = train_gradient(ctx, "si_train_step", idx, nb, d, /*node_apply=*/true);
   if (rc != SI_OK) return rc;
-  ProfScope ps(ctx, SI_K_BACKWARD, 0.0, 0.0);
-  if ((rc = train_apply(ctx)) != SI_OK) return rc;
+  if (node) {   // (a failed step does not advance the beta powers: train_node_report rewinds)
+    advance_beta_powers(t->opt);
+    t->opt.grad_ready = false;
+  } else {
+    ProfScope ps(ctx, SI_K_BACKWARD, 0.0, 0.0);
+    if ((rc = train_apply(ctx)) != SI_OK) return rc;
+  }
   if (loss_out) {
     double sse = 0.0;
     SI_HIP(ctx, hipMemcpyAsync(&sse, t->sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *loss_out = sse / d;  // mse of the batch BEFORE the update, as Zygote's forward value
+    *loss_out = node ? sse : sse / d;  // mse of the batch BEFORE the update, as Zygote's forward value (Node: the loss, penalty included)
+    return train_node_report(ctx, "si_train_step");
   }
   return SI_OK;
 }
@@ -638,40 +577,33 @@ int32_t si_train_grad(si_ctx* ctx, const int64_t* idx, int64_t nb, int64_t nb_to
   if (!ctx) return SI_ERR_INVALID;
   if (nb_total < nb) return fail(ctx, SI_ERR_INVALID, "si_train_grad: nb_total < nb");
   TrainState* t = ctx->train;
-  if (t && t->node) {
-    // a NeuralODE step is not data-parallel: the gradient of this batch alone (the tail kernel without the update);
-    // sse_local_out receives the loss of the batch, penalty included
-    if (nb_total != nb) return fail(ctx, SI_ERR_INVALID, "si_train_grad: a share of a batch is not available for NeuralODE training (nb_total must equal nb)");
-    int32_t rcn = node_train_launches(ctx, "si_train_grad", idx, nb, /*apply=*/false);
-    if (rcn != SI_OK) return rcn;
-    t->node->steps += 1;
-    if (sse_local_out) SI_HIP(ctx, hipMemcpyAsync(sse_local_out, t->sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rcn = train_node_report(ctx, "si_train_grad")) != SI_OK) return rcn;
-    t->grad_ready = true;
-    return SI_OK;
-  }
+  const bool node = is_node(ctx);
+  // a NeuralODE step is not data-parallel: the gradient of this batch alone (the tail kernel without the update);
+  // sse_local_out receives the loss of the batch, penalty included
+  if (node && nb_total != nb) return fail(ctx, SI_ERR_INVALID, "si_train_grad: a share of a batch is not available for NeuralODE training (nb_total must equal nb)");
   const double d_total = t ? (double)t->out_dim * (double)nb_total : 1.0;
   if (t && nb == 0 && nb_total > 0) {  // a rank without a share of a small batch contributes a zero gradient
     SI_HIP(ctx, hipSetDevice(ctx->device));
-    SI_HIP(ctx, hipMemsetAsync(t->gw, 0, (size_t)pad_ld(t->N) * sizeof(double), ctx->stream));
+    SI_HIP(ctx, hipMemsetAsync(t->opt.gw, 0, (size_t)pad_ld(t->N) * sizeof(double), ctx->stream));
     SI_HIP(ctx, hipMemsetAsync(t->sse, 0, sizeof(double), ctx->stream));
-    t->grad_ready = true;
+    t->opt.grad_ready = true;
     if (sse_local_out) *sse_local_out = 0.0;
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SI_OK;
   }
-  const int32_t rc = train_gradient(ctx, "si_train_grad", idx, nb, d_total);
+  int32_t rc = train_gradient(ctx, "si_train_grad", idx, nb, d_total, /*node_apply=*/false);
   if (rc != SI_OK) return rc;
   if (sse_local_out) SI_HIP(ctx, hipMemcpyAsync(sse_local_out, t->sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the gradient is complete when the caller starts its collective
+  if ((rc = train_node_report(ctx, "si_train_grad")) != SI_OK) return rc;
+  t->opt.grad_ready = true;
   return SI_OK;
 }
 
 int32_t si_train_grad_ptr(si_ctx* ctx, double** grad_dev_out, int64_t* n_out) {
   if (!ctx) return SI_ERR_INVALID;
   if (!ctx->train || !grad_dev_out || !n_out) return fail(ctx, SI_ERR_STATE, "si_train_grad_ptr: no training state / NULL output");
-  *grad_dev_out = ctx->train->gw;
+  *grad_dev_out = ctx->train->opt.gw;
   *n_out = ctx->train->N;
   return SI_OK;
 }
@@ -679,30 +611,30 @@ int32_t si_train_grad_ptr(si_ctx* ctx, double** grad_dev_out, int64_t* n_out) {
 int32_t si_train_grad_get(si_ctx* ctx, double* g_out) {
   if (!ctx) return SI_ERR_INVALID;
   // (a NeuralODE step's tail kernel leaves its gradient in gw: it can be read after si_train_step too, for the audit)
-  const bool node_gw = ctx->train && ctx->train->node && ctx->train->node->steps > 0 && !ctx->train->node->reported;
-  if (!ctx->train || !(ctx->train->grad_ready || node_gw) || !g_out) return fail(ctx, SI_ERR_STATE, "si_train_grad_get: no gradient pending / NULL output");
+  const bool node_gw = is_node(ctx) && ctx->train->node.steps > 0 && !ctx->train->node.reported;
+  if (!ctx->train || !(ctx->train->opt.grad_ready || node_gw) || !g_out) return fail(ctx, SI_ERR_STATE, "si_train_grad_get: no gradient pending / NULL output");
   SI_HIP(ctx, hipSetDevice(ctx->device));
-  SI_HIP(ctx, hipMemcpyAsync(g_out, ctx->train->gw, (size_t)ctx->train->N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(g_out, ctx->train->opt.gw, (size_t)ctx->train->N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SI_OK;
 }
 
 int32_t si_train_grad_set(si_ctx* ctx, const double* g_in) {
   if (!ctx) return SI_ERR_INVALID;
-  if (!ctx->train || !ctx->train->grad_ready || !g_in) return fail(ctx, SI_ERR_STATE, "si_train_grad_set: no gradient pending / NULL input");
+  if (!ctx->train || !ctx->train->opt.grad_ready || !g_in) return fail(ctx, SI_ERR_STATE, "si_train_grad_set: no gradient pending / NULL input");
   SI_HIP(ctx, hipSetDevice(ctx->device));
-  SI_HIP(ctx, hipMemcpyAsync(ctx->train->gw, g_in, (size_t)ctx->train->N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(ctx->train->opt.gw, g_in, (size_t)ctx->train->N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SI_OK;
 }
 
 int32_t si_train_apply(si_ctx* ctx) {
   if (!ctx) return SI_ERR_INVALID;
-  if (!ctx->train || !ctx->train->grad_ready) return fail(ctx, SI_ERR_STATE, "si_train_apply: no gradient pending (call si_train_grad)");
+  if (!ctx->train || !ctx->train->opt.grad_ready) return fail(ctx, SI_ERR_STATE, "si_train_apply: no gradient pending (call si_train_grad)");
   SI_HIP(ctx, hipSetDevice(ctx->device));
   const int32_t rc = train_apply(ctx);
-  if (rc == SI_OK && ctx->train->node)   // the next step's solve reads the Float64 copy (si_train_step refreshes it in its tail kernel)
-    launch_widen_f32_to_f64(ctx->stream, ctx->train->w32, ctx->train->N, ctx->train->w64, ctx->num_cu);
+  if (rc == SI_OK && is_node(ctx))   // the next step's solve reads the Float64 copy (si_train_step refreshes it in its tail kernel)
+    launch_widen_f32_to_f64(ctx->stream, ctx->train->opt.w32, ctx->train->N, ctx->train->opt.w64, ctx->num_cu);
   return rc;
 }
 
@@ -710,14 +642,14 @@ int32_t si_train_push(si_ctx* ctx, double n) {
   if (!ctx) return SI_ERR_INVALID;
   if (!ctx->train) return fail(ctx, SI_ERR_STATE, "si_train_push: call si_train_setup first");
   if (ctx->train->N != ctx->N) return fail(ctx, SI_ERR_INVALID, "si_train_push: construction and training sizes differ");
-  return si_construct_push_dev(ctx, ctx->train->w32, SI_F32, n);
+  return si_construct_push_dev(ctx, ctx->train->opt.w32, SI_F32, n);
 }
 
 int32_t si_train_get_weights(si_ctx* ctx, float* w_out) {
   if (!ctx) return SI_ERR_INVALID;
   if (!ctx->train || !w_out) return fail(ctx, SI_ERR_STATE, "si_train_get_weights: no training state / NULL output");
   SI_HIP(ctx, hipSetDevice(ctx->device));
-  SI_HIP(ctx, hipMemcpyAsync(w_out, ctx->train->w32, (size_t)ctx->train->N * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(w_out, ctx->train->opt.w32, (size_t)ctx->train->N * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return train_node_report(ctx, "si_train_get_weights");
 }
@@ -726,15 +658,16 @@ int32_t si_train_get_opt_state(si_ctx* ctx, float* m_out, float* v_out, double* 
   if (!ctx) return SI_ERR_INVALID;
   if (!ctx->train) return fail(ctx, SI_ERR_STATE, "si_train_get_opt_state: no training state");
   SI_HIP(ctx, hipSetDevice(ctx->device));
-  TrainState* t = ctx->train;
-  if (m_out && t->m32) SI_HIP(ctx, hipMemcpyAsync(m_out, t->m32, (size_t)t->N * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  if (v_out && t->v32) SI_HIP(ctx, hipMemcpyAsync(v_out, t->v32, (size_t)t->N * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  TrainOpt& o = ctx->train->opt;
+  const size_t nbytes = (size_t)ctx->train->N * sizeof(float);
+  if (m_out && o.m32) SI_HIP(ctx, hipMemcpyAsync(m_out, o.m32, nbytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (v_out && o.v32) SI_HIP(ctx, hipMemcpyAsync(v_out, o.v32, nbytes, hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const int32_t rcn = train_node_report(ctx, "si_train_get_opt_state");
   if (rcn != SI_OK) return rcn;
   if (beta_pows_out) {
-    beta_pows_out[0] = t->bp1;
-    beta_pows_out[1] = t->bp2;
+    beta_pows_out[0] = o.bp1;
+    beta_pows_out[1] = o.bp2;
   }
   return SI_OK;
 }

@@ -295,14 +295,14 @@ int32_t si_rwmh_allreduce_sse(si_ctx* ctx) {
 // local sum of squared errors, one grouped launch
 int32_t si_train_allreduce_grad(si_ctx* ctx, double* sse_total_out) {
   if (!ctx) return SI_ERR_INVALID;
-  if (ctx->train && ctx->train->node) return fail(ctx, SI_ERR_INVALID, "si_train_allreduce_grad: not available for NeuralODE training");
+  if (ctx->train && ctx->train->route == TrainRoute::Node) return fail(ctx, SI_ERR_INVALID, "si_train_allreduce_grad: not available for NeuralODE training");
   int32_t rc = need_comm(ctx, "si_train_allreduce_grad");
   if (rc != SI_OK) return rc;
   TrainState* t = ctx->train;
-  if (!t || !t->grad_ready) return fail(ctx, SI_ERR_STATE, "si_train_allreduce_grad: no gradient pending (call si_train_grad)");
+  if (!t || !t->opt.grad_ready) return fail(ctx, SI_ERR_STATE, "si_train_allreduce_grad: no gradient pending (call si_train_grad)");
   SI_HIP(ctx, hipSetDevice(ctx->device));
   SI_NCCL(ctx, rccl().GroupStart());
-  const ncclResult_t r1 = rccl().AllReduce(t->gw, t->gw, (size_t)t->N, ncclFloat64, ncclSum, comm_of(ctx), ctx->stream);
+  const ncclResult_t r1 = rccl().AllReduce(t->opt.gw, t->opt.gw, (size_t)t->N, ncclFloat64, ncclSum, comm_of(ctx), ctx->stream);
   const ncclResult_t r2 = rccl().AllReduce(t->sse, t->sse, 1, ncclFloat64, ncclSum, comm_of(ctx), ctx->stream);
   SI_NCCL(ctx, rccl().GroupEnd());
   SI_NCCL(ctx, r1);
@@ -316,7 +316,7 @@ int32_t si_train_allreduce_grad(si_ctx* ctx, double* sse_total_out) {
 
 int32_t si_train_step_dp(si_ctx* ctx, const int64_t* idx, int64_t nb, int64_t nb_total, double* loss_out) {
   if (!ctx) return SI_ERR_INVALID;
-  if (ctx->train && ctx->train->node) return fail(ctx, SI_ERR_INVALID, "si_train_step_dp: not available for NeuralODE training");
+  if (ctx->train && ctx->train->route == TrainRoute::Node) return fail(ctx, SI_ERR_INVALID, "si_train_step_dp: not available for NeuralODE training");
   int32_t rc = need_comm(ctx, "si_train_step_dp");
   if (rc != SI_OK) return rc;
   // (a rank whose forward / reverse sweep failed must not leave the others inside the gradient all-reduce)

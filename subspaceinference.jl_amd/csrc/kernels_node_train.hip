@@ -1,13 +1,15 @@
 // The tail of a NeuralODE training step (si_train_setup_node; node.py: train_value_and_grad is the definition): what follows the
 // forward with record and the reverse kernel of kernels_node.hip.  One launch instead of four (the sum of the batch's gradient
-// slices, the penalty, optimiser_kernel and widen_kernel of capi_train.hip).  gfx950, fp64, compiled without contraction of a*b+c:
-// every product and sum is rounded on its own, in the written order.
+// slices, the penalty, the update and the Float32 -> Float64 copy of capi_train.hip); the update is optimiser_update
+// (optimiser_update.h), the function optimiser_kernel calls.  gfx950, fp64, compiled without contraction of a*b+c: every product
+// and sum is rounded on its own, in the written order.
 //
 // One thread per weight element, 256-thread blocks, ceil(N / 256) blocks.  No atomics, no spinning, no workgroup barrier, plain
 // loads and stores; every loop is bounded by nb.  Every thread first reads the nb status words of the batch and the sticky failure
 // word, so the branch that follows is uniform across the grid: on a failure NOTHING is stored -- not gw, not the loss, not w, m,
 // v or the Float64 copy -- except the failure record, which thread 0 of block 0 writes once (the first failing step wins: a set
 // record is never overwritten).  (A thread that reads the record while thread 0 writes it leaves either way.)
+#include "optimiser_update.h"
 #include "si_internal.h"
 
 namespace si {
@@ -37,24 +39,8 @@ __global__ __launch_bounds__(256) void node_train_tail_kernel(NodeTailArgs a) {
   for (int64_t p = 0; p < a.nb; ++p) acc = acc + a.slices[p * a.N + i];
   const double gi = a.penalty_div != 0.0 ? (a.w64[i] * 2.0) / a.penalty_div - acc : 0.0 - acc;
   a.gw[i] = gi;
-  if constexpr (APPLY) {   // optimiser_kernel's arithmetic with a Float64 gradient (g32 = 0), operator by operator
-    double step;
-    if (a.kind == 0) {
-      step = gi * a.eta;
-    } else if (a.kind == 1) {
-      const float vn = (float)(a.p1 * (double)a.m32[i] - a.eta * gi);
-      a.m32[i] = vn;
-      step = -(double)vn;
-    } else {
-      const float mt = (float)(a.p1 * (double)a.m32[i] + (1.0 - a.p1) * gi);
-      const float vt = (float)(a.p2 * (double)a.v32[i] + (1.0 - a.p2) * (gi * gi));
-      a.m32[i] = mt;
-      a.v32[i] = vt;
-      step = (double)mt / (1.0 - a.bp1) / (sqrt((double)vt / (1.0 - a.bp2)) + 1e-8) * a.eta;
-    }
-    const float wn = (float)((double)a.w32[i] - step);
-    a.w32[i] = wn;
-    a.w64[i] = (double)wn;   // the next step's solve reads this copy
+  if constexpr (APPLY) {   // the update with a Float64 gradient, and the copy the next step's solve reads
+    a.w64[i] = (double)optimiser_update(a.w32, a.m32, a.v32, i, gi, a.kind, a.eta, a.p1, a.p2, a.bp1, a.bp2, /*g32=*/false);
   }
 }
 

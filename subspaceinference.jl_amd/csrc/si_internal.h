@@ -70,7 +70,7 @@ struct NetPlan {
 struct NetScratch {             // reverse-sweep workspaces (sized by net_scratch_sizes)
   DevBuf<double> bwpart, rspart, wt, dbtmp;
   // gradient mode: pidx[l] = byte index tensor of conv layer l whose MaxPool ran fused with it (net_grad_fused), else empty
-  // (a view of the owning vector beside it: TrainState::pidx / InferState::d_pidx)
+  // (a view of the owning vector beside it: TrainConvWs::pidx / InferState::d_pidx)
   const DevBuf<uint8_t>* pidx = nullptr;
 };
 // workspace of one fp32 sweep at up to Bmax observations (sweep_f32_alloc; see dense_value_and_grad_f32 below)
@@ -81,46 +81,7 @@ struct SweepF32Ws {
   DevBuf<double> rspart64, tailpart64, yhat64;
 };
 
-struct NodeTrain;   // si_train_setup_node: a NeuralODE's training step (below, after NodeArgs)
-
-// on-device training (capi_train.hip)
-struct TrainState {
-  ~TrainState();            // (capi_train.hip: releases `node`)
-  NodeTrain* node = nullptr;   // set: the model is a NeuralODE; X = U0 (d x f), Y = the trajectories (d*S x f), in_dim = d, out_dim = d*S
-  std::vector<si_layer> layers;
-  int64_t N = 0, Btot = 0, Bmax = 0;
-  int32_t in_dim = 0, out_dim = 0;
-  DevBuf<double> X, Y, Xb, Yb;
-  DevBuf<int64_t> idx;
-  // batch indices travel through two pinned buffers (copy in, async H2D, event): a step never synchronises the stream, so the
-  // caller's work between two steps (its next batch, the K1 push) overlaps the GPU's
-  PinBuf<int64_t> idx_pin[2];
-  Event idx_ev[2];
-  bool idx_busy[2] = {false, false};
-  int idx_slot = 0;
-  DevBuf<float> w32, m32, v32;
-  DevBuf<double> w64, gw;
-  std::vector<DevBuf<double>> hs;
-  DevBuf<double> delta[2];
-  DevBuf<double> bwpart, rspart, ssepart, sse;
-  int sse_blocks = 0;
-  int opt = 0;
-  double eta = 0.0, p1 = 0.0, p2 = 0.0, bp1 = 0.0, bp2 = 0.0;
-  bool grad_ready = false;  // gw holds a gradient that has not been applied yet
-  bool fuse_tail = false;   // narrow head: folded into the epilogue of the layer in front of it (forward and reverse)
-  int fuse_slots = 0;
-  DevBuf<double> part;      // [fuse_slots][out_last][Bmax] partial head products
-  // compute_dtype = SI_F32 (Dense chains; reference src/subspace_construction.jl:39-43 with a Float32 model AND Float32 data):
-  // fp32 data, activations, deltas and gradient; fp64 only for the loss, the head's partial sums and the sums over the batch
-  bool f32 = false;
-  DevBuf<float> X32, Xb32;
-  SweepF32Ws ws32;          // kept outputs, deltas, gradient, scratch of the fp32 sweep (empty unless f32)
-  // chains with Conv / MaxPool / flatten layers (generic path, capi_net.hip)
-  NetPlan plan;
-  DevBuf<double> Xc, wpack;
-  NetScratch scratch;
-  std::vector<DevBuf<uint8_t>> pidx;   // per layer: window-index bytes of a Conv layer fused with its MaxPool (net_grad_fused)
-};
+struct TrainState;   // on-device training (below, after NodeTrain)
 
 // ---- the context.  Its members are split by WHO RELEASES THEM: assigning a fresh ConstructState / InferState is
 // free_construct / free_infer, everything in CtxCore lives until si_destroy deletes the context.
@@ -202,7 +163,7 @@ struct CtxCore {
   CtxCore() = default;
   CtxCore(const CtxCore&) = delete;
   CtxCore& operator=(const CtxCore&) = delete;
-  ~CtxCore() { delete train; }
+  ~CtxCore();   // (capi_train.hip, where TrainState is complete: releases `train`)
 };
 
 // What si_construct_finish_diffmap keeps (capi_diffmap.hip, kernels_diffmap.hip): its own buffers, none shared with the PCA route.
@@ -360,7 +321,7 @@ const char* node_plan(const si_layer* layers, int32_t L, int64_t N, int32_t d, i
 // si_train_setup_node (capi_train.hip; node.py: train_value_and_grad is the definition): the training step's own solver workspace
 // for batch_max trajectories of ONE weight vector -- the inference state's (NodeState) is not shared, the launchers are
 struct NodeTrain {
-  NodeArgs args;                   // the constants (node_plan); per step: w = TrainState::w64, U0 / Y = the batch's columns, f = nb
+  NodeArgs args;                   // the constants (node_plan); per step: w = TrainOpt::w64, U0 / Y = the batch's columns, f = nb
   DevBuf<double> ts;               // S
   DevBuf<double> ssep;             // batch_max
   DevBuf<double> rec;              // batch_max x max_steps x (d + 2): the step record
@@ -388,6 +349,61 @@ struct NodeTailArgs {
   double eta, p1, p2, bp1, bp2;
 };
 void launch_node_train_tail(hipStream_t st, const NodeTailArgs& a, bool apply);
+
+// ---- on-device training (capi_train.hip).  One step -- batch, gradient, update -- with four gradient routes, chosen at set-up
+enum class TrainRoute { DenseF64, DenseF32, Conv, Node };
+// batch indices travel through two pinned buffers (copy in, async H2D, event): a step never synchronises the stream, so the
+// caller's work between two steps (its next batch, the K1 push) overlaps the GPU's
+struct TrainBatch {
+  DevBuf<int64_t> idx;
+  PinBuf<int64_t> pin[2];
+  Event ev[2];
+  bool busy[2] = {false, false};
+  int slot = 0;
+};
+// Flux 0.11.2's Float32 parameters and optimiser state (optimiser_update.h), the Float64 copy the sweeps read, the gradient
+struct TrainOpt {
+  DevBuf<float> w32, m32, v32;
+  DevBuf<double> w64, gw;
+  int kind = 0;             // 0 Descent, 1 Momentum, 2 ADAM
+  double eta = 0.0, p1 = 0.0, p2 = 0.0, bp1 = 0.0, bp2 = 0.0;
+  bool grad_ready = false;  // gw holds a gradient that has not been applied yet
+};
+struct TrainDenseWs {       // Dense chains in fp64 (dense_value_and_grad_f64); hs and delta also carry a Conv chain's sweep
+  std::vector<DevBuf<double>> hs;
+  DevBuf<double> delta[2];
+  DevBuf<double> bwpart, rspart;
+  bool fuse_tail = false;   // (both Dense routes) narrow head: folded into the epilogue of the layer in front of it
+  int fuse_slots = 0;
+  DevBuf<double> part;      // [fuse_slots][out_last][Bmax] partial head products
+};
+// compute_dtype = SI_F32 (Dense chains; reference src/subspace_construction.jl:39-43 with a Float32 model AND Float32 data):
+// fp32 data, activations, deltas and gradient; fp64 only for the loss, the head's partial sums and the sums over the batch
+struct TrainF32Ws {
+  DevBuf<float> X, Xb;
+  SweepF32Ws ws;            // kept outputs, deltas, gradient, scratch of the fp32 sweep
+};
+struct TrainConvWs {        // chains with Conv / MaxPool / flatten layers (net_value_and_grad, capi_net.hip)
+  NetPlan plan;
+  DevBuf<double> Xc, wpack;
+  NetScratch scratch;
+  std::vector<DevBuf<uint8_t>> pidx;   // per layer: window-index bytes of a Conv layer fused with its MaxPool (net_grad_fused)
+};
+struct TrainState {
+  TrainRoute route = TrainRoute::DenseF64;
+  std::vector<si_layer> layers;
+  int64_t N = 0, Btot = 0, Bmax = 0;
+  int32_t in_dim = 0, out_dim = 0;   // (Node: X = U0 (d x f), Y = the trajectories (d*S x f), in_dim = d, out_dim = d*S)
+  DevBuf<double> X, Y, Xb, Yb;       // the data and the gathered batch (DenseF32: X is f32.X)
+  DevBuf<double> ssepart, sse;       // the loss word and its block partials
+  int sse_blocks = 0;
+  TrainBatch batch;
+  TrainOpt opt;
+  TrainDenseWs dense;                // what a route does not use stays empty
+  TrainF32Ws f32;
+  TrainConvWs conv;
+  NodeTrain node;
+};
 
 // ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops
 struct InferState {

@@ -32,7 +32,7 @@ Pointer alignment, from how the buffers are laid out (every rule below enters a 
   A5  the split-K range ks of a weight gradient is a multiple of 16 by construction, so `ksplit % 2 == 0` always holds.
 So on this library's own buffers every alignment test reduces to parities of out, in, w_off, b_off and B.
 
-Not in the table: the kernels in front of the chain (reconstruct_kernel, widen_kernel, gather_cols_kernel), the chain-grid
+Not in the table: the kernels in front of the chain (reconstruct_kernel, convert_kernel<float, double>, gather_cols_kernel<double | float>), the chain-grid
 kernels that take the log-density of a narrow chain (every hidden width <= 256; kernels_chain_grid.hip, held by
 tests/test_gpu_lattice.py and tests/test_gpu_chain_grid.py -- for such a chain the log-density mode is left out of the route
 set, see maybe_narrow_class), and the later activations (leakyrelu, elu, softplus, selu: not exact)."""

@@ -194,7 +194,7 @@ DISPATCH_TEXT = {
            else
            launch_mul_dact_rowsum_f32(st, ws.delta32[cur ^ 1], ws.hs32[li - 1], ly.in, nb, lq.act, ws.delta32[cur ^ 1], ws.rspart64,
            ws.gw32 + lq.b_off);""",
-        "const double *Xb = t->X, *Yb = t->Y;",   # A4: an in-order batch uses X in place
+        "v = TrainBatchView{t->X, t->f32.X, t->Y}; if (in_order) return SI_OK;",   # A4: an in-order batch uses X in place (train_batch)
         "const bool fuse_tail = !plan.has_conv && (L >= 2) && layers[L - 1].out <= SI_FUSE_MAX_OUT &&",
     ),
 }

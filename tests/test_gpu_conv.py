@@ -131,6 +131,16 @@ def test_conv_training_gradient_and_step(gpu_ctx, case):
     assert np.allclose(w1, (w64 - 0.05 * g_ref).astype(np.float32), rtol=1e-6, atol=1e-7)
 
 
+def test_a_batch_in_place_is_the_batch_through_the_index_path(gpu_ctx):
+    """the Conv route behind the shared batch stage (tests/batch_stage.py): the smallest five-observation chain of
+    tests/conv_routes.py (Conv, two MaxPools, flatten, Dense on 6 x 4 x 3 images; N = 1442), 3 of its 5 observations"""
+    from tests import batch_stage
+    from tests import conv_routes as cr
+    table, n, w, x, y = cr.train_problem("first_9_3")
+    assert x.shape[1] == 5
+    batch_stage.assert_in_place_is_the_index_path(gpu_ctx, table, n, w.astype(np.float32), x, y, 3)
+
+
 def test_conv_layer_tables_are_validated(si, gpu_ctx):
     whc, spec, b = CASES[0]
     table, n, w_swa, p, x, y = _problem(whc, spec, b, 2, seed=5)

@@ -1042,6 +1042,17 @@ def test_training_step_on_a_smaller_last_batch_of_an_epoch(si, gpu_ctx):
         assert np.allclose(gpu_ctx.train_grad_get(), gref, rtol=1e-8, atol=1e-10 * np.abs(gref).max()), nb
 
 
+def test_a_batch_in_place_is_the_batch_through_the_index_path(si, gpu_ctx):
+    """the Dense fp64 route behind the shared batch stage (tests/batch_stage.py): 4 -> 6 -> 2, 5 of 9 observations (an odd count:
+    the gather's grid ends on a ragged block)"""
+    from tests import batch_stage
+    rng = np.random.default_rng(11)
+    table, n = so.layer_table([4, 6, 2], [so.ACT_TANH, so.ACT_IDENTITY])
+    x, y = np.asfortranarray(rng.standard_normal((4, 9))), np.asfortranarray(rng.standard_normal((2, 9)))
+    batch_stage.assert_in_place_is_the_index_path(gpu_ctx, table, n, (0.3 * rng.standard_normal(n)).astype(np.float32), x, y, 5)
+    assert gpu_ctx.train_compute_dtype() == si._capi.SI_F64
+
+
 def test_random_shape_sweep_training_gradient(si, gpu_ctx):
     """si_train_grad (forward + reverse sweep of the mse cost, with the fused narrow-head path for heads of width <= 4 and
     the generic one above) against the host stand-in of Zygote's gradient on random Dense chains and batches."""

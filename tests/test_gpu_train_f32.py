@@ -117,6 +117,18 @@ def test_f32_gradient_on_other_shapes(si, gpu_ctx, dims, acts, b, bmax):
         assert np.abs(g_dev - g32).max() <= 6e-6 * scale + 1.2e-7 * np.abs(w0).max()
 
 
+def test_a_batch_in_place_is_the_batch_through_the_index_path(si, gpu_ctx):
+    """the Dense fp32 route behind the shared batch stage (tests/batch_stage.py): gather_cols_kernel on Float32 columns; 4 -> 6 -> 2,
+    5 of 9 observations (an odd count: the gather's grid ends on a ragged block)"""
+    from tests import batch_stage
+    rng = np.random.default_rng(12)
+    table, n = so.layer_table([4, 6, 2], [so.ACT_TANH, so.ACT_IDENTITY])
+    x = np.asfortranarray(rng.standard_normal((4, 9)).astype(np.float32))
+    y = np.asfortranarray(rng.standard_normal((2, 9)).astype(np.float32))
+    batch_stage.assert_in_place_is_the_index_path(gpu_ctx, table, n, (0.3 * rng.standard_normal(n)).astype(np.float32), x, y, 5)
+    assert gpu_ctx.train_compute_dtype() == si._capi.SI_F32
+
+
 def test_f32_refused_for_conv_chains_in_training(si, gpu_ctx):
     from subspaceinference_jl_amd import _capi
     table, n = so.conv_table([("conv", (3, 3), 4, so.ACT_RELU, (1, 1), (1, 1)), ("flatten",), ("dense", 2, so.ACT_IDENTITY)], (6, 6, 1))

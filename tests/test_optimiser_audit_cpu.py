@@ -5,10 +5,13 @@
     forms, six consecutive steps from the fresh state and six more from the state they leave, and the special values;
   * every catalogued near-miss rule differs from the true rule in at least one bit of (w, m, v, beta powers) on that input set --
     a condition on the inputs: the audit can only catch on the device what its inputs can tell apart on the host;
-  * the beta powers are the running product, at a t where beta ** (t + 1) is another number.
+  * the beta powers are the running product, at a t where beta ** (t + 1) is another number;
+  * the device states the rule once (csrc/optimiser_update.h), and both kernels that apply it call that function.
 """
 import functools
 import math
+import os
+import re
 
 import numpy as np
 import pytest
@@ -173,6 +176,25 @@ def test_beta_powers_are_the_running_product():
     oa.same_powers(bp_scalar, want, "scalar restatement")
     oa.same_powers(bp_oracle, want, "apply_update")
     assert want[0] != hp[1] ** (t + 1) or want[1] != hp[2] ** (t + 1), "t = %d does not tell pow from the running product" % t
+
+
+def test_the_update_rule_is_written_once():
+    """csrc/optimiser_update.h holds the Descent / Momentum / ADAM arithmetic, with its own contraction pragma; optimiser_kernel and
+    the NeuralODE step's tail kernel call it, and no other file of csrc/ states the ADAM or the Momentum step"""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "subspaceinference.jl_amd", "csrc")
+    text = {f: re.sub(r"\s+", " ", open(os.path.join(csrc, f)).read()) for f in sorted(os.listdir(csrc))
+            if os.path.isfile(os.path.join(csrc, f))}
+    for expr in ("/ (1.0 - bp1) / (sqrt(", "(float)(p1 * (double)m[i] - eta * gi)"):
+        assert {f: t.count(expr) for f, t in text.items() if expr in t} == {"optimiser_update.h": 1}, expr
+    rule = text["optimiser_update.h"]
+    body = rule[rule.index("float optimiser_update("):]
+    assert body[body.index("{"):].startswith("{ #pragma clang fp contract(off) ")
+    for f, kernel, call in (("capi_train.hip", "void optimiser_kernel(", "optimiser_update(w, m, v, i, g[i], "),
+                            ("kernels_node_train.hip", "void node_train_tail_kernel(", "a.w64[i] = (double)optimiser_update(a.w32, ")):
+        raw = open(os.path.join(csrc, f)).read()
+        assert '#include "optimiser_update.h"' in raw
+        body = raw[raw.index(kernel):]
+        assert call in body[:body.index("\n}\n")], f        # (up to the closing brace of the kernel)
 
 
 def test_same_bits_names_the_first_difference():

@@ -700,6 +700,40 @@ int32_t si_sample_rwmh_sharded(si_ctx* ctx, int64_t itr, double sigma_z, uint64_
 int32_t si_train_allreduce_grad(si_ctx* ctx, double* sse_total_out);
 int32_t si_train_step_dp(si_ctx* ctx, const int64_t* idx, int64_t nb, int64_t nb_total, double* loss_out);
 
+/* ---- the autoencoder of auto_encoder_subspace trained on the device (reference src/subspace_construction.jl:125-140) ----------
+ * Chain(encoder, decoder) = N -> e_1 -> ... -> H -> N, Dense only, trained to reproduce the columns of the N x K deviation
+ * matrix: loss = sum r^2 / (N nb) over a batch of nb columns, r = sae(x) - x; with `penalty` the loss gains sum w^2 and the
+ * gradient 2 w.  subspaceinference.jl_amd/autoencoder.py: train_step is the definition (all arithmetic fp64; parameters and
+ * optimiser state in w_dtype, rounded once on the store).  `layers` are the L = E + D layers with their offsets in the packed
+ * flux.params order ([vec(W_l); b_l] per layer); w0 holds n_params elements of w_dtype.  X = NULL reads the OPEN construction's
+ * deviation matrix in place (fp64 or fp32 storage; N must be the construction's, K is its column count); otherwise X is the
+ * N x K fp64 host matrix, copied once.  The two big layers run as N-parallel streaming kernels with the optimiser update fused
+ * (their gradients are never written); the three N-long sums have one blocked order that depends on N alone.
+ * The state is its own object on the context: independent of si_train_* and of an inference set-up; si_construct_begin,
+ * si_ae_train_free and si_destroy free it.
+ * Refused with SI_ERR_INVALID, naming the limit: a layer that is not SI_LAYER_DENSE; the first `in` or the last `out` != N; E + D
+ * outside 2 .. 16 (the library sees the sum only: that E and D lie in 1 .. 8 EACH is NOT enforced here -- E = 1, D = 15 is
+ * accepted -- but by the caller that knows the split, as api.py does); a hidden width > 256; batch_max outside 1 .. 8; widths that do not chain, an
+ * unknown activation, offsets that are not the packed order, n_params that differs from their sum; w_dtype or opt_kind unknown;
+ * X = NULL on a construction with max_cols > 0 or another N.  SI_ERR_STATE: X = NULL without an open construction that holds
+ * columns.  A step refuses nb > batch_max, nb < 1 and an index outside 0 .. K-1.
+ * si_ae_train_step: one step on the nb columns idx (the host DataLoader's shuffle, passed step by step); loss_out receives the
+ * loss of the batch BEFORE the update, or NULL: the step is queued and nothing synchronises, as si_train_step.
+ * si_ae_train_loss: the loss over all K columns, forward only, batch_max columns at a time (the reference's callback).
+ * si_ae_train_get_params / _get_opt_state: flat, in w_dtype (m_out, v_out may be NULL; beta_pows_out[2] as si_train_get_opt_state).
+ * si_ae_train_info: whether a set-up is active, its N, K, n_params, and whether the last layer's update runs inside the pass over
+ * W_D (1: it does).  Profiling classes of a step: SI_K_DENSE the first layer's forward and the head; SI_K_DENSE_MAIN the pass over
+ * W_D; SI_K_BACKWARD the head's reverse and the updates of the small arrays and of W_1; SI_K_SSE the passes of si_ae_train_loss. */
+int32_t si_ae_train_setup(si_ctx* ctx, const si_layer* layers, int32_t L /* E + D */, int64_t n_params, const void* w0,
+                          int32_t w_dtype /* SI_F32 | SI_F64 */, const double* X /* N x K fp64 host, or NULL */, int64_t N, int64_t K,
+                          int32_t batch_max, int32_t opt_kind, double eta, double p1, double p2, int32_t penalty);
+int32_t si_ae_train_step(si_ctx* ctx, const int64_t* idx /* nb column indices, 0-based */, int64_t nb, double* loss_out /* may be NULL */);
+int32_t si_ae_train_loss(si_ctx* ctx, double* loss_out);
+int32_t si_ae_train_get_params(si_ctx* ctx, void* w_out /* n_params of w_dtype */);
+int32_t si_ae_train_get_opt_state(si_ctx* ctx, void* m_out, void* v_out, double* beta_pows_out /* 2 */);
+int32_t si_ae_train_info(si_ctx* ctx, int32_t* active_out, int64_t* N_out, int64_t* K_out, int64_t* n_params_out, int32_t* fused_out);
+int32_t si_ae_train_free(si_ctx* ctx);
+
 /* ---- host utility (no GPU needed): the K x K symmetric eigensolver used inside si_construct_finish.
  * a: n x n symmetric column-major, overwritten by the eigenvectors (columns); w: eigenvalues ascending. */
 int si_host_sym_eig(int n, double* a, double* w);

@@ -154,6 +154,14 @@ SIGNATURES = {
     "si_train_setup_node": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64,
                                       c_void_p, c_void_p, c_int64, c_int32, c_double, c_double, c_double, c_double]),
     "si_train_node_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), POINTER(c_int64), POINTER(c_int32)]),
+    "si_ae_train_setup": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int32,
+                                    c_int32, c_double, c_double, c_double, c_int32]),
+    "si_ae_train_step": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "si_ae_train_loss": (c_int32, [c_void_p, c_void_p]),
+    "si_ae_train_get_params": (c_int32, [c_void_p, c_void_p]),
+    "si_ae_train_get_opt_state": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "si_ae_train_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int32)]),
+    "si_ae_train_free": (c_int32, [c_void_p]),
     "si_comm_unique_id": (c_int32, [c_void_p]),
     "si_comm_init_rank": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),
     "si_comm_destroy": (c_int32, [c_void_p]),
@@ -622,6 +630,61 @@ class Context:
         bp = np.empty(2, dtype=np.float64)
         self._check(self.lib.si_train_get_opt_state(self.h, _ptr(m), _ptr(v), _ptr(bp)))
         return m, v, (float(bp[0]), float(bp[1]))
+
+    # -- the autoencoder of auto_encoder_subspace trained on the device (autoencoder.py: train_step is the definition)
+    def ae_train_setup(self, table, w0, x, n, batch_max, opt_kind, eta, p1=0.0, p2=0.0, penalty=False):
+        """si_ae_train_setup.  `table` is the Dense layer table of Chain(encoder, decoder), `w0` its flat Float32 or Float64
+        parameters (they and the optimiser state stay on the device in that type).  x None: the open construction's deviation
+        matrix, read in place; else the N x K matrix, uploaded once."""
+        w0 = np.ascontiguousarray(w0)
+        if w0.dtype not in (np.float32, np.float64) or w0.ndim != 1:
+            raise SubspaceError("autoencoder parameters must be a flat Float32 or Float64 vector, got %s %s" % (w0.dtype, w0.shape))
+        k = 0
+        if x is not None:
+            x = _f64(x)
+            if x.ndim != 2 or x.shape[0] != n:
+                raise SubspaceError("DimensionMismatch: X is %s, expected %d rows" % (x.shape, n))
+            k = x.shape[1]
+        arr = _layer_array(table)
+        self._check(self.lib.si_ae_train_setup(self.h, arr, len(table), w0.size, _ptr(w0), SI_F32 if w0.dtype == np.float32 else SI_F64,
+                                               _ptr(x), int(n), int(k), int(batch_max), int(opt_kind), float(eta), float(p1), float(p2),
+                                               1 if penalty else 0))
+        self._ae_n, self._ae_dtype = w0.size, w0.dtype
+
+    def ae_train_step(self, idx, want_loss=True):
+        """one step on the columns idx; the loss of the batch before the update, or None (queued: no host synchronisation)"""
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        loss = c_double(0.0)
+        self._check(self.lib.si_ae_train_step(self.h, _ptr(idx), idx.size, byref(loss) if want_loss else None))
+        return float(loss.value) if want_loss else None
+
+    def ae_train_loss(self):
+        """the loss over all K columns (the reference's callback `autoloss(re_weight)`)"""
+        loss = c_double(0.0)
+        self._check(self.lib.si_ae_train_loss(self.h, byref(loss)))
+        return float(loss.value)
+
+    def ae_train_get_params(self):
+        w = np.empty(self._ae_n, dtype=self._ae_dtype)
+        self._check(self.lib.si_ae_train_get_params(self.h, _ptr(w)))
+        return w
+
+    def ae_train_get_opt_state(self):
+        """(m, v, (beta1^t, beta2^t)) in the parameters' element type"""
+        m, v = np.empty(self._ae_n, dtype=self._ae_dtype), np.empty(self._ae_n, dtype=self._ae_dtype)
+        bp = np.empty(2, dtype=np.float64)
+        self._check(self.lib.si_ae_train_get_opt_state(self.h, _ptr(m), _ptr(v), _ptr(bp)))
+        return m, v, (float(bp[0]), float(bp[1]))
+
+    def ae_train_info(self):
+        """(active, N, K, n_params, whether the last layer's update is fused into the pass over W_D)"""
+        a, f = c_int32(0), c_int32(0)
+        n, k, p = c_int64(0), c_int64(0), c_int64(0)
+        self._check(self.lib.si_ae_train_info(self.h, byref(a), byref(n), byref(k), byref(p), byref(f)))
+        return bool(a.value), int(n.value), int(k.value), int(p.value), bool(f.value)
+
+    def ae_train_free(self):
+        self._check(self.lib.si_ae_train_free(self.h))
 
     # -- density + sampling
     def infer_setup(self, table, n, m, w_swa, p, x, y, sigma_m, compute_dtype=SI_F64):

@@ -420,17 +420,23 @@ def _decoder_spec(decoder):
 
 def auto_encoder_subspace(model, cost, data, opt, encoder, decoder, T=10, c=1, M=3, print_freq=1, *, include_penalty=False,
                           seed=0, device=0, ctx=None, verbose=True, device_training="auto", init="zeros", a_storage="f64",
-                          compute_dtype="auto"):
+                          compute_dtype="auto", device_autoencoder=False):
     """src/subspace_construction.jl:93-143: the SWA loop of `subspace_construction` (:104-123, the same lines), then
     `Chain(encoder, decoder)` trained to reproduce the deviation columns -> (W_swa, decoder); the decoder's arrays are trained in
     place and the same object comes back, as in the reference.
 
     The loop runs on the device like the other two constructions; the deviation matrix A (N x K) and the mean are then read
     back (the mean through a one-column `construct_finish`, whose projection is discarded) and the autoencoder is trained on the
-    host with `flux.gradient` / `flux.update`: cost `mse(sae(X), X)`, a fresh `ADAM()`, `DataLoader(A, batchsize = 5, shuffle =
+    host (the default; `device_autoencoder` below) with `flux.gradient` / `flux.update`: cost `mse(sae(X), X)`, a fresh `ADAM()`, `DataLoader(A, batchsize = 5, shuffle =
     true)`, ONE pass (:127-140).  [upstream, unverifiable offline]: that `Flux.train!` makes a single pass over its data and
-    that `ADAM()` is ADAM(0.001, (0.9, 0.999)) are restated from Flux 0.11.2 from memory.  Training it through si_train_* is a
-    follow-up.  `M` is accepted and unused, as in the reference (the decoder's first layer carries it).
+    that `ADAM()` is ADAM(0.001, (0.9, 0.999)) are restated from Flux 0.11.2 from memory.  `M` is accepted and unused, as in the reference (the decoder's first layer carries it).
+
+    device_autoencoder: False (default) is that host loop.  True trains the autoencoder on the device (si_ae_train_*;
+    autoencoder.py: train_step is the definition): A is read in place, never read back; the shuffle stays the host DataLoader's
+    permutation, passed step by step; the encoder's and decoder's arrays are written back at the end; a set-up the library refuses
+    raises SubspaceError with its message.  "auto": the device when it accepts the set-up, else the host loop.  The device's
+    gradient carries the unscaled cotangent and takes its three N-long sums in a blocked order, so the two routes agree to
+    rounding, not to the bit.
 
     include_penalty: the reference writes `+ sum(sqnorm, autops)` on a line of its own AFTER the loss (:130-131), so Julia parses
     it as a separate statement and the penalty is dead -- like the prior term (quirk Q4).  False (default):
@@ -448,17 +454,48 @@ def auto_encoder_subspace(model, cost, data, opt, encoder, decoder, T=10, c=1, M
         raise SubspaceError("DimensionMismatch: the encoder returns %d values but the decoder takes %d"
                             % (encoder.layers[-1].W.shape[0], int(dec_table[0][0])))
 
+    if device_autoencoder not in (False, True, "auto"):
+        raise SubspaceError("device_autoencoder must be False, True or \"auto\"")
+    sae = flux.Chain(*encoder.layers, *decoder.layers)          # :127 Chain(encoder, decoder): the same arrays
+    autops = flux.params(sae)
+
+    def train_on_device(cx, k):
+        """the loop of :134-140 through si_ae_train_*; False when "auto" met a refusal"""
+        table, _ = flux.layer_table(sae)
+        w0 = flux.extract_params(autops)
+        aopt = flux.ADAM()
+        try:
+            if not 1 <= len(encoder.layers) <= 8 or not 1 <= len(decoder.layers) <= 8:
+                raise SubspaceError("si_ae_train_setup: E or D outside 1 .. 8")
+            cx.ae_train_setup(table, w0, None, n_par, 5, 2, aopt.eta, aopt.beta[0], aopt.beta[1], penalty=include_penalty)
+        except SubspaceError:
+            if device_autoencoder == "auto":
+                return False
+            raise
+        try:
+            loader = flux.DataLoader(np.zeros((1, k)), batchsize=5, shuffle=True, rng=np.random.default_rng(seed))   # :139
+            for ids in loader.index_batches():                     # :140 Flux.train!: one pass
+                cx.ae_train_step(ids, want_loss=False)
+                if verbose:                                        # :137 cb() = @show autoloss(re_weight)
+                    print("autoloss(re_weight) = ", cx.ae_train_loss())
+            flux.load_flat(sae, cx.ae_train_get_params())
+        finally:
+            cx.ae_train_free()
+        return True
+
     def finish(cx):
         nb = len(data)
         k = sum(1 for i in range(1, T + 1) if i % c == 0) * nb
+        if device_autoencoder is not False and train_on_device(cx, k):
+            return cx.construct_finish(1, want_swa=True, want_p=False)[0], None
         a = cx.construct_get_A(0, k)
         return cx.construct_finish(1, want_swa=True, want_p=False)[0], a
 
     w_swa, re_weight = _swa_construction(model, cost, data, opt, T, c, print_freq, finish, device=device, ctx=ctx, max_cols=0,
                                          verbose=verbose, keep_on_device=False, device_training=device_training, init=init,
                                          data_parallel=False, a_storage=a_storage, compute_dtype=compute_dtype)
-    sae = flux.Chain(*encoder.layers, *decoder.layers)          # :127 Chain(encoder, decoder): the same arrays
-    autops = flux.params(sae)
+    if re_weight is None:                                      # trained on the device
+        return w_swa, decoder
     aopt = flux.ADAM()                                         # :134
     wdata = flux.DataLoader(re_weight, batchsize=5, shuffle=True, rng=np.random.default_rng(seed))   # :139
     for (xb,) in wdata:                                        # :140 Flux.train!: one pass
@@ -508,14 +545,15 @@ def auto_inference(m, data, decoder, W_swa, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
 def autoencoder_inference(model, cost, data, opt, encoder, decoder, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=1000, T=25, c=1, M=20,
                           print_freq=1, alg="hmc", backend="forwarddiff", *, sigma_z=None, sigma_m=None, sigma_p=None, device=0,
                           ctx=None, seed=0, verbose=True, return_z=False, include_penalty=False, include_prior=False,
-                          device_loop=False, device_sampler=False, device_nuts=False):
+                          device_loop=False, device_sampler=False, device_nuts=False, device_autoencoder=False):
     """src/space_inference.jl:198-210: `auto_encoder_subspace`, then `auto_inference`, on one context -> (chn, lp).  A NeuralODE
-    with `flux.node_sse` trains as in `subspace_construction`."""
+    with `flux.node_sse` trains as in `subspace_construction`.  device_autoencoder: as in `auto_encoder_subspace`."""
     _refuse_node_training(model, cost)
     ctx, own = _get_ctx(ctx, device)
     try:
         w_swa, decoder = auto_encoder_subspace(model, cost, data, opt, encoder, decoder, T=T, c=c, M=M, print_freq=print_freq,
-                                               include_penalty=include_penalty, seed=seed, ctx=ctx, verbose=verbose)
+                                               include_penalty=include_penalty, seed=seed, ctx=ctx, verbose=verbose,
+                                               device_autoencoder=device_autoencoder)
         return auto_inference(model, data, decoder, w_swa, σ_z=σ_z, σ_m=σ_m, σ_p=σ_p, itr=itr, M=M, alg=alg, backend=backend,
                               sigma_z=sigma_z, sigma_m=sigma_m, sigma_p=sigma_p, ctx=ctx, seed=seed, return_z=return_z,
                               include_prior=include_prior, device_loop=device_loop, device_sampler=device_sampler,

@@ -121,3 +121,183 @@ def decode_vjp(table, wdec, z, gy):
         for j in range(W.shape[0]):
             g = g + W[j, :] * delta[j]
     return g
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Training Chain(encoder, decoder) on the deviation columns (reference src/subspace_construction.jl:125-140): the definition of
+# si_ae_train_step / si_ae_train_loss (csrc/kernels_ae_train.hip).  `table` is the Dense-only layer table of the whole
+# autoencoder N -> e_1 -> ... -> M -> ... -> H -> N, `w` its flat parameters in flux.params order, `xb` the N x nb batch.
+#
+# Three sums run over the N rows: the first layer's forward, the last layer's pull-back W_D' delta, and sum r^2 (with
+# `penalty`, the rows' shares of sum w^2 as well).  `order` names how they are taken: "ascending" (the default: the written
+# order of this file), "pairwise", or "blocked" -- the device's order, which depends on N alone: row n belongs to row block
+# n // AE_ROWS, row block rb to workgroup rb % G with G = min(row blocks, AE_GRID); per row block a shuffle-down tree over each
+# wave's 64 rows and (w0 + w1) + (w2 + w3) over the four waves; a workgroup adds its row blocks in ascending order from 0.0,
+# and the G workgroup sums are added in ascending order from 0.0.  Every other sum is ascending from 0.0.
+AE_ROWS, AE_GRID = 256, 1024   # the kernels' constants of the same names (tests/test_ae_train_cpu.py compares them)
+
+
+def _nsum(t, order="ascending"):
+    """sum over axis 0 of t (N x ...) in the named order"""
+    t = np.asarray(t, dtype=np.float64)
+    n = t.shape[0]
+    if order == "ascending":
+        return np.cumsum(t, axis=0)[-1]          # (cumsum adds one element after the other)
+    if order == "pairwise":
+        while t.shape[0] > 1:
+            if t.shape[0] & 1:
+                t = np.concatenate([t, np.zeros((1,) + t.shape[1:])], axis=0)
+            t = t[0::2] + t[1::2]
+        return t[0]
+    if order != "blocked":
+        raise SubspaceError("unknown summation order %r" % (order,))
+    nblk = -(-n // AE_ROWS)
+    g = min(nblk, AE_GRID)
+    passes = -(-nblk // g)
+    pad = passes * g * AE_ROWS - n
+    if pad:
+        t = np.concatenate([t, np.zeros((pad,) + t.shape[1:])], axis=0)
+    t = t.reshape((passes, g, AE_ROWS // 64, 64) + t.shape[1:])
+    off = 32
+    while off > 0:
+        t = t[:, :, :, :off] + t[:, :, :, off:2 * off]
+        off >>= 1
+    t = t[:, :, :, 0]
+    t = (t[:, :, 0] + t[:, :, 1]) + (t[:, :, 2] + t[:, :, 3])
+    acc = np.zeros(t.shape[1:])
+    for p in range(passes):
+        acc = acc + t[p]
+    return np.cumsum(np.concatenate([np.zeros((1,) + acc.shape[1:]), acc], axis=0), axis=0)[-1]
+
+
+def check_train_table(table, w, n=None):
+    """the refusals of si_ae_train_setup that need no device; returns N"""
+    check_table(table, w)
+    big = int(table[0][0])
+    if int(table[-1][1]) != big or (n is not None and big != n):
+        raise SubspaceError("DimensionMismatch: the autoencoder must take and return N values")
+    if len(table) < 2:
+        raise SubspaceError("an autoencoder needs an encoder and a decoder layer")
+    if any(int(r[1]) > 256 for r in table[:-1]):
+        raise SubspaceError("a hidden width above 256")
+    return big
+
+
+def _train_forward(table, w, xb, order):
+    xb = np.asarray(xb, dtype=np.float64)
+    xb = xb.reshape(xb.shape[0], -1)
+    lay = list(_layers(table, w))
+    outs = [xb]
+    W, b, act = lay[0]
+    u = _nsum(W.T[:, :, None] * xb[:, None, :], order) + b[:, None]      # terms[n, j, b] = W_1[j, n] x[n, b]
+    outs.append(flux._act_fwd(u, act))
+    for W, b, act in lay[1:]:
+        a = outs[-1]
+        u = np.zeros((W.shape[0], a.shape[1]))
+        for i in range(W.shape[1]):
+            u = u + W[:, i:i + 1] * a[i:i + 1]
+        outs.append(flux._act_fwd(u + b[:, None], act))
+    return lay, outs
+
+
+def _penalty(table, w, order):
+    """sum w^2 as the device takes it: (first layer's rows + the small arrays in flat order) + last layer's rows"""
+    lay = list(_layers(table, w))
+    w64 = np.asarray(w).astype(np.float64)
+    W1, WD, bD = lay[0][0], lay[-1][0], lay[-1][1]
+    q1 = np.zeros(W1.shape[1])
+    for j in range(W1.shape[0]):
+        q1 = q1 + W1[j, :] * W1[j, :]
+    qd = np.zeros(WD.shape[0])
+    for h in range(WD.shape[1]):
+        qd = qd + WD[:, h] * WD[:, h]
+    qd = qd + bD * bD
+    lo, hi = int(table[0][4]), int(table[-1][3])          # b_1 and every middle array: one contiguous flat range
+    mid = 0.0
+    for x in w64[lo:hi]:
+        mid = mid + x * x
+    return (float(_nsum(q1, order)) + mid) + float(_nsum(qd, order))
+
+
+def train_loss(table, w, x, penalty=False, order="ascending"):
+    """autoloss(re_weight) (reference :129,137): (sum r^2 over ALL columns) / (N K), one division; + sum w^2 with `penalty`.
+    sum r^2 of a row is taken over the columns ascending, the rows as `order` says (the device: chunk after chunk of batch_max
+    columns, the chunks' sums added in ascending order -- on the integer lattice the same number)"""
+    lay, outs = _train_forward(table, w, x, order)
+    r = outs[-1] - outs[0]
+    q = np.zeros(r.shape[0])
+    for b in range(r.shape[1]):
+        q = q + r[:, b] * r[:, b]
+    loss = float(_nsum(q, order)) / float(r.shape[0] * r.shape[1])
+    return loss + _penalty(table, w, order) if penalty else loss
+
+
+def train_value_and_grad(table, w, xb, penalty=False, order="ascending"):
+    """(loss, g): loss = (sum r^2) / (N nb), r = sae(xb) - xb, and its gradient w.r.t. the flat parameters, Float64.
+
+    The reverse sweep carries the UNSCALED cotangent: dt_L = r .* act'(a_L); per layer, from the last, G_l = dt_l a_{l-1}',
+    gb_l = sum_batch dt_l (both over the batch index ascending from 0.0), dt_{l-1} = (W_l' dt_l) .* act'(a_{l-1}) (the sum over
+    the output index ascending from 0.0; the last layer's over its N rows as `order` says).  The factor s = 2.0 / (N nb) enters
+    once per gradient element, g = s * G; with `penalty`, g += 2 w and the loss gains sum w^2.  flux.MSE.value_and_grad scales
+    the cotangent first: the two differ by rounding only."""
+    w = np.asarray(w)
+    lay, outs = _train_forward(table, w, xb, order)
+    big, nb = outs[0].shape
+    r = outs[-1] - outs[0]
+    q = np.zeros(big)
+    for b in range(nb):
+        q = q + r[:, b] * r[:, b]
+    loss = float(_nsum(q, order)) / float(big * nb)
+    s = 2.0 / float(big * nb)
+    g = np.zeros(w.size)
+    dt = r * dact_from_output(outs[-1], lay[-1][2])
+    for l in range(len(lay) - 1, -1, -1):
+        W, _, _ = lay[l]
+        _, fout, _, w_off, b_off = (int(v) for v in table[l][:5])
+        a = outs[l]
+        G = np.zeros(W.shape)
+        gb = np.zeros(fout)
+        for b in range(nb):
+            G = G + dt[:, b:b + 1] * a[:, b][None, :]
+            gb = gb + dt[:, b]
+        g[w_off:w_off + W.size] = (s * G).reshape(-1, order="F")
+        g[b_off:b_off + fout] = s * gb
+        if l > 0:
+            if l == len(lay) - 1:
+                back = _nsum(W[:, :, None] * dt[:, None, :], order)       # terms[n, h, b] = W_D[n, h] dt[n, b]
+            else:
+                back = np.zeros((W.shape[1], nb))
+                for j in range(W.shape[0]):
+                    back = back + W[j, :][:, None] * dt[j:j + 1, :]
+            dt = back * dact_from_output(a, lay[l - 1][2])
+    if penalty:
+        g = g + 2.0 * w.astype(np.float64)
+        loss = loss + _penalty(table, w, order)
+    return loss, g
+
+
+def optimiser_update(w, m, v, g, opt, beta_pows):
+    """csrc/optimiser_update.h on whole arrays for a Float64 gradient: Float64 arithmetic, the state and the parameters rounded
+    once on the store into their own element type.  opt = (kind, eta, p1, p2); returns (w, m, v) -- new arrays"""
+    kind, eta, p1, p2 = opt
+    T = w.dtype.type
+    w64, m64, v64 = w.astype(np.float64), m.astype(np.float64), v.astype(np.float64)
+    if kind == 0:
+        step = g * eta
+    elif kind == 1:
+        m = (p1 * m64 - eta * g).astype(T)
+        step = -m.astype(np.float64)
+    else:
+        m = (p1 * m64 + (1.0 - p1) * g).astype(T)
+        v = (p2 * v64 + (1.0 - p2) * (g * g)).astype(T)
+        step = m.astype(np.float64) / (1.0 - beta_pows[0]) / (np.sqrt(v.astype(np.float64) / (1.0 - beta_pows[1])) + 1e-8) * eta
+    return (w64 - step).astype(T), m.copy(), v.copy()
+
+
+def train_step(table, w, m, v, beta_pows, xb, opt, penalty=False, order="ascending"):
+    """one step: the gradient at w, then the update -> (loss, w, m, v, beta_pows), the loss that of the batch BEFORE the update.
+    w, m, v share an element type (Float32 or Float64: Flux keeps zero(x) as state); the beta powers advance once per ADAM step"""
+    loss, g = train_value_and_grad(table, w, xb, penalty, order)
+    w2, m2, v2 = optimiser_update(np.asarray(w), np.asarray(m), np.asarray(v), g, opt, beta_pows)
+    bp = [beta_pows[0] * opt[2], beta_pows[1] * opt[3]] if opt[0] == 2 else list(beta_pows)
+    return loss, w2, m2, v2, bp

@@ -81,6 +81,7 @@ static void resolve_events(Ctx* c) {
 
 
 static void free_construct(Ctx* c) {
+  c->ae.reset();   // (si_ae_train_* may read the deviation matrix in place)
   // an inference set up on the construction's own W_swa / P dies with it
   if (c->i_ready && c->i_swa == c->d_swa && c->d_swa != nullptr) free_infer(c);
   static_cast<ConstructState&>(*c) = ConstructState();
@@ -384,6 +385,7 @@ int32_t si_construct_begin(si_ctx* ctx, int64_t N, int64_t K_capacity, int32_t m
   BIND(ctx);
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const int64_t kcap = max_cols > 0 ? std::min<int64_t>(max_cols, K_capacity) : K_capacity;
+  ctx->ae.reset();   // an autoencoder training state may have borrowed the old deviation matrix
   if (ctx->d_swa != nullptr && ctx->N == N) {
     // same problem size as the previous construction: keep the buffers (ensure_A re-uses A when it is large enough)
     if (ctx->i_ready && ctx->i_swa == ctx->d_swa) free_infer(ctx);  // an inference bound to the old W_swa / P

@@ -35,4 +35,29 @@ __device__ __forceinline__ float optimiser_update(float* w, float* m, float* v, 
   return wn;
 }
 
+// the same rule on Float64 parameters (si_ae_train_setup with SI_F64): Flux keeps zero(x) as state, so m and v are Float64 and
+// nothing is rounded to Float32 -- every expression as above
+__device__ __forceinline__ double optimiser_update(double* w, double* m, double* v, int64_t i, double gi, int kind, double eta, double p1,
+                                                   double p2, double bp1, double bp2, bool /*g32: a Float64 array has no Float32 gradient*/) {
+#pragma clang fp contract(off)
+  double step;
+  if (kind == 0) {
+    step = gi * eta;
+  } else if (kind == 1) {
+    const double vn = p1 * m[i] - eta * gi;
+    m[i] = vn;
+    step = -vn;
+  } else {
+    const double mt = p1 * m[i] + (1.0 - p1) * gi;
+    const double vt = p2 * v[i] + (1.0 - p2) * (gi * gi);
+    m[i] = mt;
+    v[i] = vt;
+    const double c1 = 1.0 - bp1, c2 = 1.0 - bp2;   // (the bias corrections' denominators, as above)
+    step = mt / c1 / (sqrt(vt / c2) + 1e-8) * eta;
+  }
+  const double wn = w[i] - step;
+  w[i] = wn;
+  return wn;
+}
+
 }  // namespace si

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -81,6 +82,50 @@ struct SweepF32Ws {
   DevBuf<double> rspart64, tailpart64, yhat64;
 };
 
+// ---- training of the autoencoder on the device (si_ae_train_*; capi_ae_train.hip, kernels_ae_train.hip; autoencoder.py:
+// train_step is the definition).  Chain(encoder, decoder) = N -> e_1 -> ... -> H -> N, Dense only, parameters and ADAM moments in
+// the caller's element type in the packed flux.params order; the data are the N x K deviation columns, read IN PLACE from the open
+// construction's d_A (borrowed: si_construct_begin drops this state) or from an uploaded copy.
+constexpr int SI_AE_MAX_LAYERS = 16, SI_AE_MAX_WIDTH = 256, SI_AE_MAX_BATCH = 8;
+struct AeLayers {
+  int32_t n = 0;
+  int32_t in[SI_AE_MAX_LAYERS] = {0}, out[SI_AE_MAX_LAYERS] = {0}, act[SI_AE_MAX_LAYERS] = {0};
+  int32_t a_off[SI_AE_MAX_LAYERS] = {0};   // layer l < n-1: where its output (out x batch_max, column pitch out) sits in acts / deltas
+  int64_t w_off[SI_AE_MAX_LAYERS] = {0}, b_off[SI_AE_MAX_LAYERS] = {0};
+};
+struct AeArgs {                  // every kernel of the step takes this by value
+  AeLayers lay;
+  int64_t col[SI_AE_MAX_BATCH] = {0};   // the batch's columns of A
+  int32_t nb = 0;
+  void *w = nullptr, *m = nullptr, *v = nullptr;
+  const void* A = nullptr;       // TA elements, column pitch ldA
+  int64_t ldA = 0, N = 0, nblk = 0;     // nblk: row blocks of AE_ROWS rows
+  int32_t G = 0;                 // workgroups of the two row kernels: min(nblk, AE_GRID)
+  double *part1 = nullptr, *part2 = nullptr;   // G x (e_1 nb + 1), G x (H nb + 2) workgroup sums
+  double *acts = nullptr, *deltas = nullptr;   // a_l and the unscaled cotangents dt_l of layers 0 .. n-2
+  double* loss = nullptr;        // [0] the loss, [1] sum r^2 carried from chunk to chunk by si_ae_train_loss
+  int32_t kind = 0, penalty = 0;
+  double eta = 0.0, p1 = 0.0, p2 = 0.0, bp1 = 0.0, bp2 = 0.0, s = 0.0;   // s = 2.0 / (N nb)
+};
+struct AeTrainState {
+  AeArgs args;                   // the constants; per step: col, nb, bp1, bp2, s
+  int64_t K = 0, n_params = 0;
+  int32_t dtype = SI_F64, a_dtype = SI_F64, batch_max = 0;
+  bool borrowed = false;         // A is the construction's d_A
+  DevBuf<char> w, m, v;          // n_params elements of dtype each
+  DevBuf<double> X;              // the uploaded copy (pad_ld(N) x K) when X was given
+  DevBuf<double> part1, part2, acts, deltas, loss;
+};
+int ae_rows();                   // AE_ROWS, AE_GRID of kernels_ae_train.hip
+int ae_grid_cap();
+// one step's launches on st (dtype / a_dtype: element types of the parameters and of A).  forward: first layer, head.  last:
+// the pass over W_D -- with update, the pull-back partials and the fused update of W_D, b_D; without, sum r^2 only.  reverse:
+// head reverse, the loss word, the update of the small arrays and of W_1.  loss_chunk: si_ae_train_loss's accumulation.
+void launch_ae_forward(hipStream_t st, const AeArgs& a, int32_t dtype, int32_t a_dtype);
+void launch_ae_last(hipStream_t st, const AeArgs& a, int32_t dtype, int32_t a_dtype, bool update);
+void launch_ae_reverse(hipStream_t st, const AeArgs& a, int32_t dtype, int32_t a_dtype, int num_cu);
+void launch_ae_loss_chunk(hipStream_t st, const AeArgs& a, int32_t dtype, bool last, double denom);
+
 struct TrainState;   // on-device training (below, after NodeTrain)
 
 // ---- the context.  Its members are split by WHO RELEASES THEM: assigning a fresh ConstructState / InferState is
@@ -88,6 +133,7 @@ struct TrainState;   // on-device training (below, after NodeTrain)
 struct CtxCore {
   int device = -1;
   TrainState* train = nullptr;
+  std::unique_ptr<AeTrainState> ae;   // si_ae_train_*: its own object, independent of `train` and of an inference set-up
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   std::string err;

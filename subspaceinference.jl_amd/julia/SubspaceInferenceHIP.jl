@@ -525,6 +525,50 @@ function decode_vjp(ctx::Ctx, z::Vector{Float64}, gy::Vector{Float64})   # J_dec
     return gz
 end
 
+# ---- the autoencoder trained on the device (src/subspace_construction.jl:125-140): si_ae_train_* ---------------------------------
+# ae_train_setup!(ctx, sae, X, N, opt_kind, eta, p1, p2; batch_max = 5, penalty = false): sae = Chain(encoder, decoder), Dense only,
+# N its input and output width; X = nothing reads the open construction's deviation matrix in place.  The parameters stay on the device in their own element type.
+function ae_train_setup!(ctx::Ctx, sae, X, N, opt_kind, eta, p1, p2; batch_max = 5, penalty = false)
+    tbl, Np = layer_table(sae)
+    w0 = collect(extract_params(Flux.params(sae)))
+    eltype(w0) in (Float32, Float64) || throw("Error: autoencoder parameters must be Float32 or Float64")
+    Xp = X === nothing ? Ptr{Float64}(C_NULL) : pointer(X)
+    K = X === nothing ? 0 : size(X, 2)
+    GC.@preserve tbl w0 X check(ctx, ccall((:si_ae_train_setup, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{SiLayer}, Int32, Int64, Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int32, Int32, Float64, Float64, Float64, Int32),
+        ctx.h, tbl, length(tbl), Np, w0, si_dtype(eltype(w0)), Xp, N, K, batch_max, opt_kind, eta, p1, p2, penalty ? 1 : 0))
+    return eltype(w0), Np
+end
+function ae_train_step!(ctx::Ctx, idx::Vector{Int64}; want_loss = true)     # idx 0-based
+    loss = Ref{Float64}(0.0)
+    GC.@preserve idx check(ctx, ccall((:si_ae_train_step, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Float64}),
+        ctx.h, idx, length(idx), want_loss ? Base.unsafe_convert(Ptr{Float64}, loss) : Ptr{Float64}(C_NULL)))
+    return want_loss ? loss[] : nothing
+end
+function ae_train_loss(ctx::Ctx)
+    loss = Ref{Float64}(0.0)
+    check(ctx, ccall((:si_ae_train_loss, LIB), Int32, (Ptr{Cvoid}, Ref{Float64}), ctx.h, loss))
+    return loss[]
+end
+function ae_train_get_params(ctx::Ctx, T, Np)
+    w = Vector{T}(undef, Np)
+    GC.@preserve w check(ctx, ccall((:si_ae_train_get_params, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), ctx.h, w))
+    return w
+end
+function ae_train_get_opt_state(ctx::Ctx, T, Np)
+    m = Vector{T}(undef, Np); v = Vector{T}(undef, Np); βp = Vector{Float64}(undef, 2)
+    GC.@preserve m v βp check(ctx, ccall((:si_ae_train_get_opt_state, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}),
+        ctx.h, m, v, βp))
+    return m, v, βp
+end
+function ae_train_info(ctx::Ctx)
+    a, f = Ref{Int32}(0), Ref{Int32}(0)
+    n, k, p = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ctx, ccall((:si_ae_train_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int32}), ctx.h, a, n, k, p, f))
+    return a[] != 0, n[], k[], p[], f[] != 0
+end
+ae_train_free!(ctx::Ctx) = check(ctx, ccall((:si_ae_train_free, LIB), Int32, (Ptr{Cvoid},), ctx.h))
+
 # ---- NeuralODE models (src/space_inference.jl:96-101; model_re at src/libs.jl:36-54) --------------------------------------------
 # infer_setup_node!(ctx, dudt, W_swa, P, U0, Y, ts; ...) in place of the Chain set-up: dudt is the Dense chain d -> ... -> d of the
 # right-hand side (pre_power = 3: the tutorial's `x -> x.^3` in front of it), U0 is d x f, Y is d*S x f (reshape(out[:, p], :, d)'

@@ -606,6 +606,33 @@ int32_t si_train_grad_ptr(si_ctx* ctx, double** grad_dev_out, int64_t* n_out);
 int32_t si_train_grad_get(si_ctx* ctx, double* g_out /* N */);
 int32_t si_train_grad_set(si_ctx* ctx, const double* g_in /* N */);
 int32_t si_train_apply(si_ctx* ctx);
+/* ---- the cost of the training step ------------------------------------------------------------------------------------------
+ * The reference's loop takes any `cost`; the device step knows five of Flux 0.11.2's, each with its default agg = mean
+ * [upstream Flux 0.11.2 src/losses/functions.jl and NNlib's logsoftmax / logsigmoid, restated from memory, unverifiable
+ * offline; costs.py of the Python package is the definition the kernels are held to].  yhat = the chain's output (out x nb),
+ * Y the targets, r = yhat - Y, d = out * nb:
+ *   SI_COST_MSE       sum r^2 / d                                                             (the default; untouched)
+ *   SI_COST_MAE       sum |r| / d;                         d/dyhat = sign(r) / d, sign(0) = 0
+ *   SI_COST_HUBER     sum h(r) / d, h = r^2 / 2 for |r| < delta (strict), delta (|r| - delta / 2) otherwise; param = delta
+ *   SI_COST_LOGITCE   logitcrossentropy(yhat, Y; dims = 1) = (1 / nb) sum_b -sum_i Y_ib (yhat_ib - lse_b), lse_b the
+ *                     log-sum-exp of column b taken about its maximum; d/dyhat = (S_b softmax(yhat)_ib - Y_ib) / nb with
+ *                     S_b = sum_i Y_ib kept (Zygote differentiates the formula as written)
+ *   SI_COST_LOGITBCE  sum((1 - Y) yhat + softplus(-yhat)) / d, softplus(-x) = max(-x, 0) + log1p(exp(-|x|));
+ *                     d/dyhat = (sigmoid(yhat) - Y) / d, the sigmoid evaluated without overflow for either sign
+ * `param` is Huber's delta (finite, > 0) and ignored by the others.  The last layer's activation applies as for mse.  The
+ * arithmetic of the cost is fp64 on every route; the SI_F32 route rounds Delta once into its Float32 reverse sweep.
+ * si_train_set_cost is called after si_train_setup / _ex, like si_infer_set_prior after its set-up; every set-up starts
+ * with SI_COST_MSE again.  SI_ERR_STATE without a training state; SI_ERR_INVALID (naming the reason) for an unknown id, a
+ * delta that is not finite and positive, a NeuralODE set-up ("not available for NeuralODE training") and a call while a
+ * gradient is pending (between si_train_grad and si_train_apply).
+ * What the other calls return then: loss_out of si_train_step / si_train_step_dp and the total of si_train_allreduce_grad
+ * divided by the cost's denominator (d, or nb for SI_COST_LOGITCE) are the cost; sse_local_out of si_train_grad is the LOCAL
+ * NUMERATOR -- sum r^2 (mse), sum |r| (mae), sum h(r) (Huber), -sum_b sum_i Y_ib (yhat_ib - lse_b) (logitce),
+ * sum((1 - Y) yhat + softplus(-yhat)) (logitbce) -- over this rank's observations; the gradient is scaled by 1 / (out *
+ * nb_total), or 1 / nb_total for SI_COST_LOGITCE.  The sums are formed in a fixed order: the same inputs give the same bits. */
+enum { SI_COST_MSE = 0, SI_COST_MAE, SI_COST_HUBER, SI_COST_LOGITCE, SI_COST_LOGITBCE };
+int32_t si_train_set_cost(si_ctx* ctx, int32_t cost, double param);
+int32_t si_train_cost_info(si_ctx* ctx, int32_t* cost_out, double* param_out);
 /* ---- the training step of a NeuralODE (docs/src/node_example.md:272-285) -------------------------------------------------------
  * In place of si_train_setup for a NeuralODE right-hand side (si_infer_setup_node's layers, data layout, `ts` and si_node_opts):
  * a step minimises, over the batch's trajectories,

@@ -142,6 +142,8 @@ SIGNATURES = {
     "si_train_setup_ex": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                     c_int32, c_int64, c_int64, c_int32, c_double, c_double, c_double, c_int32]),
     "si_train_compute_dtype": (c_int32, [c_void_p, c_void_p]),
+    "si_train_set_cost": (c_int32, [c_void_p, c_int32, c_double]),
+    "si_train_cost_info": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "si_train_step": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
     "si_train_push": (c_int32, [c_void_p, c_double]),
     "si_train_get_weights": (c_int32, [c_void_p, c_void_p]),
@@ -578,6 +580,17 @@ class Context:
         self._check(self.lib.si_train_compute_dtype(self.h, _ptr(out)))
         return int(out[0])
 
+    def train_set_cost(self, cost, param=0.0):
+        """si_train_set_cost: the cost of the steps that follow (costs.py: MSE .. LOGITBCE; param = Huber's delta).  It follows
+        train_setup, which starts with mse again."""
+        self._check(self.lib.si_train_set_cost(self.h, int(cost), float(param)))
+
+    def train_cost_info(self):
+        """(cost id, param) of the training state: si_train_cost_info"""
+        cost, param = c_int32(0), c_double(0.0)
+        self._check(self.lib.si_train_cost_info(self.h, byref(cost), byref(param)))
+        return int(cost.value), float(param.value)
+
     def train_step(self, idx, want_loss=True):
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         loss = np.empty(1, dtype=np.float64) if want_loss else None
@@ -586,7 +599,8 @@ class Context:
 
     # data-parallel form: grad -> (caller's all-reduce) -> apply
     def train_grad(self, idx, nb_total):
-        """Gradient of mse over the WHOLE batch (nb_total observations) restricted to this rank's idx; returns local SSE."""
+        """Gradient of the cost (mse by default) over the WHOLE batch (nb_total observations) restricted to this rank's idx;
+        returns the local numerator of the cost (mse: the local SSE)."""
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         sse = np.empty(1, dtype=np.float64)
         self._check(self.lib.si_train_grad(self.h, _ptr(idx), idx.size, int(nb_total), _ptr(sse)))

@@ -41,7 +41,8 @@ def subspace_construction(model, cost, data, opt, T=10, c=1, M=3, print_freq=1, 
     forms the deviation column and appends it (:45-52, kernel K1).  After the loop the device forms A'A
     (K2), the host solves the K x K eigenproblem (H1) and the device projects P = A*V_M (K3) == :61-65.
 
-    device_training ("auto" | True | False): when the cost is `flux.mse` and the optimiser is a fresh Descent /
+    device_training ("auto" | True | False): when the cost is `flux.mse` (or another cost flux.device_cost knows: flux.mae,
+    flux.huber_loss, flux.logitcrossentropy, flux.logitbinarycrossentropy) and the optimiser is a fresh Descent /
     Momentum / ADAM, the training step itself (:39-43) also runs on the GPU (si_train_step: forward, reverse sweep,
     optimiser) and the weights are pushed in place (si_train_push) -- no weight vector crosses PCIe.  The model's
     arrays receive the trained weights at the end, like Flux's in-place `update!`.
@@ -129,8 +130,9 @@ def _swa_construction(model, cost, data, opt, T, c, print_freq, finish, *, devic
     if n_push == 0:
         # reference: reshape of an empty A, then psvd / U[:,1:M] fails
         raise SubspaceError("BoundsError: no snapshot was collected (mod(i,c) never 0 for i in 1:T)")
-    # the device step exists for a Chain with flux.mse and for a NeuralODE with flux.node_sse (si_train_setup / si_train_setup_node)
-    dev_cost = isinstance(cost, flux.NodeSSE) if is_node else isinstance(cost, flux.MSE)
+    # the device step exists for a Chain with one of flux's costs (flux.device_cost: mse, mae, huber_loss, logitcrossentropy,
+    # logitbinarycrossentropy) and for a NeuralODE with flux.node_sse (si_train_setup + si_train_set_cost / si_train_setup_node)
+    dev_cost = isinstance(cost, flux.NodeSSE) if is_node else flux.device_cost(cost) is not None
     dev_opt = flux.device_optimiser(opt) if dev_cost and hasattr(data, "index_batches") else None
     # si_train_* keeps Float32 weights and optimiser state (Flux's default): a Float64 model stays on the host step,
     # otherwise "auto" and device_training=False would return different (W_swa, P) for the same inputs
@@ -175,6 +177,8 @@ def _swa_construction(model, cost, data, opt, T, c, print_freq, finish, *, devic
                 table, _ = flux.layer_table(model, in_size)
                 ctx.train_setup(table, n_par, flux.extract_params(ps), xm, ym, bmax, *dev_opt,
                                 compute_dtype={"auto": None, "f32": _capi.SI_F32, "f64": _capi.SI_F64}[compute_dtype])
+                if not isinstance(cost, flux.MSE):   # (every set-up starts with mse)
+                    ctx.train_set_cost(*flux.device_cost(cost))
         for i in range(1, T + 1):
             if use_dev:
                 last = (i % print_freq == 0) or (i == T)
@@ -183,7 +187,7 @@ def _swa_construction(model, cost, data, opt, T, c, print_freq, finish, *, devic
                     if use_dp and (dp_world > 1 or dist._has_comm(ctx)):
                         # data-parallel step: this rank's share of the batch, one gradient all-reduce (dist.py)
                         c0, c1 = dist.col_shard(len(ids), dp_rank, dp_world)
-                        loss = dist.train_step_data_parallel(ctx, np.asarray(ids)[c0:c1], len(ids))
+                        loss = dist.train_step_data_parallel(ctx, np.asarray(ids)[c0:c1], len(ids), flux.device_cost(cost)[0])
                     else:
                         loss = ctx.train_step(ids, want_loss=last and j == len(batches) - 1)
                     if loss is not None:

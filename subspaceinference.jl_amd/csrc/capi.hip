@@ -227,7 +227,10 @@ int32_t dense_value_and_grad_f64(Ctx* ctx, hipStream_t st, const DenseValueGrad&
   for (size_t l = 0; l < nl; ++l) bflops += 4.0 * (double)sw.layers[l].in * sw.layers[l].out * (double)sw.B;
   ProfScope ps(ctx, SI_K_BACKWARD, bflops, 0.0);
   SI_HIP(ctx, hipMemsetAsync(sw.gw, 0, (size_t)pad_ld(s.N) * sizeof(double), st));
-  launch_delta_out(st, s.Y, sw.hs[nl - 1], (int64_t)sw.layers[nl - 1].out * sw.B, s.scale, sw.layers[nl - 1].act, sw.delta[0]);
+  if (s.cost)   // (the head's outputs are in hs[nl - 1], fused or not)
+    launch_cost_tail<double>(st, *s.cost, s.Y, sw.hs[nl - 1], nullptr, sw.layers[nl - 1].out, sw.B, sw.layers[nl - 1].act, sw.delta[0], s.sse);
+  else
+    launch_delta_out(st, s.Y, sw.hs[nl - 1], (int64_t)sw.layers[nl - 1].out * sw.B, s.scale, sw.layers[nl - 1].act, sw.delta[0]);
   return dense_reverse_sweep(ctx, st, sw);
 }
 

@@ -317,7 +317,10 @@ int32_t net_value_and_grad(Ctx* c, const NetValueGrad& s) {
   launch_sse(st, yhat, s.Y, d, s.ssepart, s.sse_blocks, s.sse);
   ProfScope ps(c, SI_K_BACKWARD, s.bwd_flops, 0.0);
   SI_HIP(c, hipMemsetAsync(s.gw, 0, (size_t)pad_ld(s.N) * sizeof(double), st));
-  launch_delta_out(st, s.Y, yhat, d, s.scale, SI_ACT_IDENTITY, s.delta[0]);
+  if (s.cost)
+    launch_cost_tail<double>(st, *s.cost, s.Y, yhat, nullptr, p.L.back().out_feat, s.B, SI_ACT_IDENTITY, s.delta[0], s.sse);
+  else
+    launch_delta_out(st, s.Y, yhat, d, s.scale, SI_ACT_IDENTITY, s.delta[0]);
   return net_backward(c, p, s.w, s.xin, s.B, s.hs, s.delta[0], s.delta[1], s.gw, *s.scratch);
 }
 

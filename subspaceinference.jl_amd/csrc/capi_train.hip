@@ -5,7 +5,8 @@
 // Float32 parameters and Float32 optimiser state, Float64 arithmetic because the data are Float64).  The weights never
 // leave the GPU: si_train_push feeds K1 from the device-resident Float32 vector.  The gradient is one of the value-and-gradient
 // passes shared with si_logdensity_grad: dense_value_and_grad_f64 (capi.hip), dense_value_and_grad_f32 (below), net_value_and_grad
-// (capi_net.hip), each with the mse scale -2 / d; or a NeuralODE's (si_train_setup_node, below).
+// (capi_net.hip), each with the mse scale -2 / d -- or, after si_train_set_cost, with the tail of another cost (kernels_cost.hip) in
+// place of its launch_delta_out; or a NeuralODE's (si_train_setup_node, below).
 // One step is: the batch (train_batch), the gradient by the set-up's route (TrainState::route: train_gradient, node_gradient), the
 // update (optimiser_update.h: optimiser_kernel here, fused into the tail kernel on the NeuralODE route).
 #include <algorithm>
@@ -69,6 +70,12 @@ void free_train(Ctx* c) {
 }
 CtxCore::~CtxCore() { delete train; }
 
+// what the cost's numerator is divided by for a batch of nb observations: out_dim * nb, SI_COST_LOGITCE: nb (agg = mean over the
+// columns of a dims = 1 sum)
+double train_denominator(const TrainState* t, int64_t nb) {
+  return t->cost == SI_COST_LOGITCE ? (double)nb : (double)t->out_dim * (double)nb;
+}
+
 // ---- value and gradient in fp32 (dense_forward<float> + the fp32 reverse sweep), shared by the training step and si_logdensity_grad
 bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const si_layer* layers, int L, bool fuse_tail, int64_t N, int32_t in_dim, int32_t out_dim,
                      int64_t Bmax) {
@@ -109,7 +116,11 @@ int32_t dense_value_and_grad_f32(Ctx* ctx, hipStream_t st, const DenseSweepF32& 
   ProfScope ps(ctx, SI_K_BACKWARD, bflops, 0.0);
   SI_HIP(ctx, hipMemsetAsync(ws.gw32, 0, (size_t)pad_ld(s.N) * sizeof(float), st));
   int cur = 0;
-  launch_delta_out_f32(st, s.Y, s.fuse_tail ? ws.yhat64 : nullptr, s.fuse_tail ? nullptr : h, d, s.scale, ll.act, ws.delta32[cur]);
+  if (s.cost)
+    launch_cost_tail<float>(st, *s.cost, s.Y, s.fuse_tail ? ws.yhat64.get() : nullptr, s.fuse_tail ? nullptr : h, ll.out, nb, ll.act,
+                            ws.delta32[cur].get(), s.sse);
+  else
+    launch_delta_out_f32(st, s.Y, s.fuse_tail ? ws.yhat64 : nullptr, s.fuse_tail ? nullptr : h, d, s.scale, ll.act, ws.delta32[cur]);
   size_t top = nl;
   bool have_db = false;   // db of layer top-1 already produced (by the pass that formed its Delta)
   if (s.fuse_tail) {
@@ -287,6 +298,33 @@ int32_t si_train_setup_ex(si_ctx* ctx, const si_layer* layers, int32_t L, int64_
                           double eta, double p1, double p2, int32_t compute_dtype) {
   return train_setup_impl(ctx, layers, L, N, w0, X, Y, data_dtype, in_dim, out_dim, B_total, batch_max, opt_kind, eta, p1, p2,
                           compute_dtype);
+}
+
+// The cost of the steps that follow (kernels_cost.hip).  Like si_infer_set_prior it follows its set-up, which starts with mse
+int32_t si_train_set_cost(si_ctx* ctx, int32_t cost, double param) {
+  if (!ctx) return SI_ERR_INVALID;
+  TrainState* t = ctx->train;
+  if (!t) return fail(ctx, SI_ERR_STATE, "si_train_set_cost: call si_train_setup first");
+  if (t->route == TrainRoute::Node) return fail(ctx, SI_ERR_INVALID, "si_train_set_cost: not available for NeuralODE training");
+  if (cost < SI_COST_MSE || cost > SI_COST_LOGITBCE)
+    return fail(ctx, SI_ERR_INVALID, "si_train_set_cost: unknown cost " + std::to_string(cost) + " (0 mse, 1 mae, 2 huber_loss, 3 logitcrossentropy, 4 logitbinarycrossentropy)");
+  if (cost == SI_COST_HUBER && !(std::isfinite(param) && param > 0.0))
+    return fail(ctx, SI_ERR_INVALID, "si_train_set_cost: huber_loss needs a finite delta > 0");
+  if (t->opt.grad_ready) return fail(ctx, SI_ERR_INVALID, "si_train_set_cost: a gradient is pending (si_train_apply first)");
+  SI_HIP(ctx, hipSetDevice(ctx->device));
+  if (cost != SI_COST_MSE && !t->costpart && !t->costpart.alloc((size_t)SI_COST_MAX_BLOCKS))
+    return fail(ctx, SI_ERR_NOMEM, "si_train_set_cost: device allocation failed");
+  t->cost = cost;
+  t->cost_param = cost == SI_COST_HUBER ? param : 0.0;
+  return SI_OK;
+}
+
+int32_t si_train_cost_info(si_ctx* ctx, int32_t* cost_out, double* param_out) {
+  if (!ctx) return SI_ERR_INVALID;
+  if (!ctx->train) return fail(ctx, SI_ERR_STATE, "si_train_cost_info: no training state");
+  if (cost_out) *cost_out = ctx->train->cost;
+  if (param_out) *param_out = ctx->train->cost_param;
+  return SI_OK;
 }
 
 int32_t si_train_compute_dtype(si_ctx* ctx, int32_t* out) {
@@ -486,8 +524,9 @@ static int32_t node_gradient(si_ctx* ctx, const char* who, const int64_t* idx, i
   return SI_OK;
 }
 
-// The gradient of the route's cost on the observations idx[0..nb), left in opt.gw, the sum of squared errors (Node: the loss) in
-// t->sse.  The mse routes scale it as if the batch were part of d_total = out_dim * (observations of the WHOLE batch)
+// The gradient of the route's cost on the observations idx[0..nb), left in opt.gw, the cost's numerator -- mse: the sum of squared
+// errors (Node: the loss) -- in t->sse.  The Chain routes scale it as if the batch were part of d_total = train_denominator of the
+// WHOLE batch.  A cost other than mse runs its tail (kernels_cost.hip) in place of the route's launch_delta_out*
 static int32_t train_gradient(si_ctx* ctx, const char* who, const int64_t* idx, int64_t nb, double d_total, bool node_apply) {
   TrainState* t = ctx->train;
   if (!t) return fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_train_setup first");
@@ -503,13 +542,15 @@ static int32_t train_gradient(si_ctx* ctx, const char* who, const int64_t* idx, 
   launch_widen_f32_to_f64(st, o.w32, N, o.w64, ctx->num_cu);
   const int sse_blocks = sse_num_blocks((int64_t)t->out_dim * nb, ctx->num_cu);
   const double scale = -2.0 / d_total;   // d mse / d yhat = 2 (yhat - y) / d
+  const CostTail tail{t->cost, t->cost_param, 1.0 / d_total, t->costpart};
+  const CostTail* cost = t->cost != SI_COST_MSE ? &tail : nullptr;
   int32_t rc = SI_OK;
   if (t->route == TrainRoute::DenseF32) {
     // ---- the step in the caller's precision: a Float32 model on Float32 data is a Float32 Zygote pass in the reference
     // (src/subspace_construction.jl:39-43).  fp32 operands and activations on v_mfma_f32_32x32x2_f32; fp64 for the head's
     // partial sums, the loss and every sum over the batch (rounded once into the Float32 gradient).
     DenseSweepF32 sw{t->layers.data(), nl, dn.fuse_tail, o.w32, o.w64, v.X32, v.Y, &t->f32.ws, dn.part, t->ssepart, t->sse, sse_blocks, nb, N,
-                     scale};
+                     scale, cost};
     if ((rc = dense_value_and_grad_f32(ctx, st, sw)) != SI_OK) return rc;
     // the gradient as the optimiser and the data-parallel all-reduce see it: fp64 words holding the Float32 values
     launch_widen_f32_to_f64(st, t->f32.ws.gw32, N, o.gw, ctx->num_cu);
@@ -518,12 +559,12 @@ static int32_t train_gradient(si_ctx* ctx, const char* who, const int64_t* idx, 
     const NetPlan& p = t->conv.plan;
     if (p.input_spatial) net_input(ctx, p, v.X, t->conv.Xc, nb);
     const NetValueGrad vg{&p, o.w64, p.input_spatial ? t->conv.Xc.get() : v.X, v.Y, nb, dn.hs.data(), t->conv.wpack, t->ssepart, sse_blocks, t->sse,
-                          {dn.delta[0], dn.delta[1]}, o.gw, &t->conv.scratch, N, scale, 0.0};
+                          {dn.delta[0], dn.delta[1]}, o.gw, &t->conv.scratch, N, scale, 0.0, cost};
     if ((rc = net_value_and_grad(ctx, vg)) != SI_OK) return rc;
   } else {
     const DenseValueGrad vg{{t->layers.data(), nl, dn.fuse_tail, o.w64, v.X, dn.hs.data(), {dn.delta[0], dn.delta[1]}, o.gw, dn.rspart,
                              dn.bwpart, nb},
-                            v.Y, dn.fuse_slots, dn.part, t->ssepart, t->sse, sse_blocks, N, scale, false};
+                            v.Y, dn.fuse_slots, dn.part, t->ssepart, t->sse, sse_blocks, N, scale, false, cost};
     if ((rc = dense_value_and_grad_f64(ctx, st, vg)) != SI_OK) return rc;
   }
   SI_HIP(ctx, hipGetLastError());
@@ -549,7 +590,7 @@ int32_t si_train_step(si_ctx* ctx, const int64_t* idx, int64_t nb, double* loss_
   if (!ctx) return SI_ERR_INVALID;
   TrainState* t = ctx->train;
   const bool node = is_node(ctx);
-  const double d = t ? (double)t->out_dim * (double)nb : 1.0;
+  const double d = t ? train_denominator(t, nb) : 1.0;
   int32_t rc = train_gradient(ctx, "si_train_step", idx, nb, d, /*node_apply=*/true);
   if (rc != SI_OK) return rc;
   if (node) {   // (a failed step does not advance the beta powers: train_node_report rewinds)
@@ -563,7 +604,7 @@ int32_t si_train_step(si_ctx* ctx, const int64_t* idx, int64_t nb, double* loss_
     double sse = 0.0;
     SI_HIP(ctx, hipMemcpyAsync(&sse, t->sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *loss_out = node ? sse : sse / d;  // mse of the batch BEFORE the update, as Zygote's forward value (Node: the loss, penalty included)
+    *loss_out = node ? sse : sse / d;  // the cost (mse by default) of the batch BEFORE the update, as Zygote's forward value (Node: the loss, penalty included)
     return train_node_report(ctx, "si_train_step");
   }
   return SI_OK;
@@ -581,7 +622,7 @@ int32_t si_train_grad(si_ctx* ctx, const int64_t* idx, int64_t nb, int64_t nb_to
   // a NeuralODE step is not data-parallel: the gradient of this batch alone (the tail kernel without the update);
   // sse_local_out receives the loss of the batch, penalty included
   if (node && nb_total != nb) return fail(ctx, SI_ERR_INVALID, "si_train_grad: a share of a batch is not available for NeuralODE training (nb_total must equal nb)");
-  const double d_total = t ? (double)t->out_dim * (double)nb_total : 1.0;
+  const double d_total = t ? train_denominator(t, nb_total) : 1.0;
   if (t && nb == 0 && nb_total > 0) {  // a rank without a share of a small batch contributes a zero gradient
     SI_HIP(ctx, hipSetDevice(ctx->device));
     SI_HIP(ctx, hipMemsetAsync(t->opt.gw, 0, (size_t)pad_ld(t->N) * sizeof(double), ctx->stream));

@@ -324,7 +324,7 @@ int32_t si_train_step_dp(si_ctx* ctx, const int64_t* idx, int64_t nb, int64_t nb
   double sse = 0.0;
   if ((rc = si_train_allreduce_grad(ctx, loss_out ? &sse : nullptr)) != SI_OK) return rc;
   if ((rc = si_train_apply(ctx)) != SI_OK) return rc;
-  if (loss_out) *loss_out = sse / ((double)ctx->train->out_dim * (double)nb_total);
+  if (loss_out) *loss_out = sse / train_denominator(ctx->train, nb_total);
   return SI_OK;
 }
 

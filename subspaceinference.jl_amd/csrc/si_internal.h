@@ -397,6 +397,14 @@ struct NodeTailArgs {
 void launch_node_train_tail(hipStream_t st, const NodeTailArgs& a, bool apply);
 
 // ---- on-device training (capi_train.hip).  One step -- batch, gradient, update -- with four gradient routes, chosen at set-up
+// A cost other than mse at the seam of the three training routes (kernels_cost.hip; si_train_set_cost): it produces the loss's
+// numerator (into the route's loss word, behind the forward pass's SSE) and Delta_L in place of launch_delta_out*
+struct CostTail {
+  int kind;           // SI_COST_MAE .. SI_COST_LOGITBCE
+  double param;       // Huber's delta
+  double inv_denom;   // 1 / (out * nb_total), SI_COST_LOGITCE: 1 / nb_total
+  double* part;       // workgroup partials of the numerator (SI_COST_MAX_BLOCKS doubles)
+};
 enum class TrainRoute { DenseF64, DenseF32, Conv, Node };
 // batch indices travel through two pinned buffers (copy in, async H2D, event): a step never synchronises the stream, so the
 // caller's work between two steps (its next batch, the K1 push) overlaps the GPU's
@@ -443,6 +451,9 @@ struct TrainState {
   DevBuf<double> X, Y, Xb, Yb;       // the data and the gathered batch (DenseF32: X is f32.X)
   DevBuf<double> ssepart, sse;       // the loss word and its block partials
   int sse_blocks = 0;
+  int cost = 0;                      // SI_COST_* (si_train_set_cost; every set-up starts with mse)
+  double cost_param = 0.0;
+  DevBuf<double> costpart;           // workgroup partials of a cost other than mse
   TrainBatch batch;
   TrainOpt opt;
   TrainDenseWs dense;                // what a route does not use stays empty
@@ -450,6 +461,7 @@ struct TrainState {
   TrainConvWs conv;
   NodeTrain node;
 };
+double train_denominator(const TrainState* t, int64_t nb);   // (capi_train.hip) what the cost's numerator of nb observations is divided by
 
 // ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops
 struct InferState {
@@ -761,6 +773,7 @@ struct DenseValueGrad {
   int64_t N;
   double scale;         // of Delta_L: -2 / d for the mse loss, 1 / sigma^2 for the log-density
   bool traffic;         // as DenseForward::traffic
+  const CostTail* cost = nullptr;   // training with another cost: its tail in place of launch_delta_out (scale unused)
 };
 int32_t dense_value_and_grad_f64(Ctx* ctx, hipStream_t st, const DenseValueGrad& s);
 // The same in fp32 (capi_train.hip; kernels_gemm_f32.hip + kernels_bwd_f32.hip): dense_forward<float> with every output kept, the
@@ -782,6 +795,7 @@ struct DenseSweepF32 {
   int sse_blocks;
   int64_t B, N;
   double scale;         // of Delta_L: -2 / d for the mse loss, 1 / sigma^2 for the log-density
+  const CostTail* cost = nullptr;   // as DenseValueGrad::cost
 };
 int32_t dense_value_and_grad_f32(Ctx* ctx, hipStream_t st, const DenseSweepF32& s);
 void launch_widen_f32_to_f64(hipStream_t st, const float* src, int64_t n, double* dst, int num_cu);
@@ -792,6 +806,12 @@ void launch_backward_weight(hipStream_t st, const double* Delta, const double* H
                             int32_t in, int64_t B, int num_cu, double* dW, double* db = nullptr);
 void launch_split_reduce(hipStream_t st, const double* part, int nsplit, int64_t elems, double* dst);
 void launch_delta_out(hipStream_t st, const double* Y, const double* Yhat, int64_t d, double scale, int act, double* delta);
+// the tail of a cost other than mse (kernels_cost.hip): *loss = the cost's numerator over the out x B outputs, summed in a fixed
+// order through c.part; delta = dL/dyhat .* act'(yhat).  yhat in fp64 (Yhat64) or fp32 (Yhat32), Delta in TD
+constexpr int SI_COST_MAX_BLOCKS = 256;   // doubles in CostTail::part
+template <class TD>
+void launch_cost_tail(hipStream_t st, const CostTail& c, const double* Y, const double* Yhat64, const float* Yhat32, int32_t out, int64_t B,
+                      int act, TD* delta, double* loss);
 void launch_rowsum(hipStream_t st, const double* D, int32_t out, int64_t B, double* part, double* db);
 // reverse sweep through a narrow last layer (out_last <= SI_FUSE_MAX_OUT) in one pass over its input H (F x B):
 // DeltaPrev = (W' Delta) .* act_prev'(H), dW = Delta H', dbprev = rowsum(DeltaPrev); part: tail_bwd_part_elems doubles
@@ -905,6 +925,7 @@ struct NetValueGrad {
   int64_t N;
   double scale;         // -2 / d for the mse loss, 1 / sigma^2 for the log-density
   double bwd_flops;     // what the caller reports for its SI_K_BACKWARD scope
+  const CostTail* cost = nullptr;   // as DenseValueGrad::cost
 };
 int32_t net_value_and_grad(Ctx* c, const NetValueGrad& s);
 // K6, device-resident loop (kernels_chain.hip): all `itr` transitions of `nchains` small Dense chains in ONE launch, one

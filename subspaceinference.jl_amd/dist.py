@@ -21,7 +21,7 @@ import time
 
 import numpy as np
 
-from . import _capi
+from . import _capi, costs
 
 
 def init(backend=None, device=None, force=False):
@@ -296,12 +296,13 @@ def sample_data_sharded(ctx, itr, sigma_z, seed, d_total, chain_id0=0, nchains=1
     return ctx.rwmh_end()
 
 
-def train_step_data_parallel(ctx, idx_local, nb_total):
+def train_step_data_parallel(ctx, idx_local, nb_total, cost_kind=costs.MSE):
     """One data-parallel `gradient(ps) do cost(model, d...) end; Flux.update!(opt, ps, gs)` (src/subspace_construction.jl:
     39-43, SURVEY 8e last paragraph): `idx_local` are this rank's observations of the batch of `nb_total`; every rank
     holds the same weights and optimiser state before and after.  The only exchange is ONE all-reduce(sum) of the
     N-double gradient plus the 8-byte SSE (si_train_step_dp; host staging under the gloo test double).  Returns the mse
-    of the whole batch before the update."""
+    of the whole batch before the update -- with `cost_kind` the cost the context was given by train_set_cost, that cost: the
+    summed numerator over costs.denominator."""
     if _has_comm(ctx):
         return ctx.train_step_dp(idx_local, nb_total)
     sse = ctx.train_grad(idx_local, nb_total)
@@ -309,7 +310,7 @@ def train_step_data_parallel(ctx, idx_local, nb_total):
         ctx.train_grad_set(allreduce_sum(ctx.train_grad_get()))
         sse = float(allreduce_sum(np.array([sse]))[0])
     ctx.train_apply()
-    return sse / (ctx.train_out_dim() * nb_total)
+    return sse / costs.denominator(cost_kind, ctx.train_out_dim(), nb_total)   # (mse: out_dim * nb_total)
 
 
 def sample_chains(ctx, nchains_total, itr, sigma_z, seed):

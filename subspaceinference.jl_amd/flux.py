@@ -14,9 +14,11 @@ Semantics restated from Flux 0.11.2 (Manifest.toml:491; not vendored):
   Descent(eta=0.1); Momentum(eta=0.01, rho=0.9); ADAM(eta=0.001, beta=(0.9, 0.999)), eps = 1e-8
   update!(opt, x, g): x .-= apply!(opt, x, g)
   Flux.Losses.mse(yhat, y) = mean((yhat .- y).^2)
+  Flux.Losses.mae / huber_loss / logitcrossentropy / logitbinarycrossentropy: costs.py (the definition the device step is held to)
 """
 import numpy as np
 
+from . import costs as _costs
 from ._capi import (ACT_ELU, ACT_IDENTITY, ACT_LEAKYRELU, ACT_RELU, ACT_SELU, ACT_SIGMOID, ACT_SOFTPLUS, ACT_TANH,
                     SubspaceError)
 
@@ -357,6 +359,74 @@ class MSE:
 
 
 mse = MSE()
+
+
+class _Cost:
+    """`L(m, x, y) = Flux.Losses.<cost>(m(x), y)` for the costs of costs.py, with the reverse sweep of MSE.value_and_grad seeded
+    with costs.dvalue (what Zygote supplies).  The device training step knows them all (device_cost)."""
+
+    kind, param = None, 0.0
+
+    def __call__(self, model, x, y):
+        return float(_costs.value(self.kind, model(x), y, self.param))
+
+    def value_and_grad(self, model, x, y):
+        if has_conv(model):
+            raise SubspaceError("there is no AD on the Python host for Conv / MaxPool layers (Zygote's job in the "
+                                "reference): the training step of such a Chain runs on the device (device_training)")
+        acts, pres = [x], []
+        for l in model.layers:
+            pre = l.W @ acts[-1] + l.b[:, None]
+            pres.append(pre)
+            acts.append(_act_fwd(pre, l.act))
+        loss = float(_costs.value(self.kind, acts[-1], y, self.param))
+        delta = _costs.dvalue(self.kind, acts[-1], y, self.param)
+        grads = []
+        for i in range(len(model.layers) - 1, -1, -1):
+            l = model.layers[i]
+            delta = delta * _act_bwd(pres[i], acts[i + 1], l.act)
+            grads = [delta @ acts[i].T, delta.sum(axis=1)] + grads
+            delta = l.W.T @ delta
+        return loss, grads
+
+
+class MAE(_Cost):
+    """Flux.Losses.mae(yhat, y) = mean(abs.(yhat .- y))"""
+    kind = _costs.MAE
+
+
+class Huber(_Cost):
+    """Flux.Losses.huber_loss(yhat, y; delta = 1)"""
+    kind = _costs.HUBER
+
+    def __init__(self, delta=1.0):
+        if not (np.isfinite(delta) and delta > 0.0):
+            raise SubspaceError("huber_loss: delta must be positive and finite")
+        self.param = float(delta)
+
+
+class LogitCrossEntropy(_Cost):
+    """Flux.Losses.logitcrossentropy(yhat, y; dims = 1) = mean(.-sum(y .* logsoftmax(yhat; dims = 1); dims = 1))"""
+    kind = _costs.LOGITCE
+
+
+class LogitBinaryCrossEntropy(_Cost):
+    """Flux.Losses.logitbinarycrossentropy(yhat, y) = mean(@. (1 - y) * yhat - logσ(yhat))"""
+    kind = _costs.LOGITBCE
+
+
+mae, huber_loss = MAE(), Huber()
+logitcrossentropy, logitbinarycrossentropy = LogitCrossEntropy(), LogitBinaryCrossEntropy()
+
+
+def device_cost(cost):
+    """(id, param) for si_train_set_cost when `cost` is one of this module's Chain costs -- the caller's assertion of which Flux
+    loss its closure is -- or None: any other cost trains on the host through its own value_and_grad."""
+    if isinstance(cost, MSE):
+        return _costs.MSE, 0.0
+    if isinstance(cost, _Cost):
+        return cost.kind, float(cost.param)
+    return None
 
 
 class NodeSSE:

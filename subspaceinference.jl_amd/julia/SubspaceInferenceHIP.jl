@@ -18,8 +18,9 @@
 #   * src/subspace_construction.jl:45-52,61-65 (SWA update, deviation, append, psvd, P)        -> GPU, always
 #   * src/subspace_construction.jl:39-43 (gradient + Flux.update!)                               -> Julia (Zygote + Flux)
 #       by default: an arbitrary `cost` closure and optimiser cannot cross a C ABI;
-#       with device_training = true (the caller asserts cost(m, x, y) == Flux.Losses.mse(m(x), y) and opt is a fresh
-#       Descent / Momentum / ADAM)                                                                -> GPU (si_train_*)
+#       with device_training = true (the caller asserts cost(m, x, y) == Flux.Losses.mse(m(x), y) -- or, with device_cost, mae,
+#       huber_loss, logitcrossentropy or logitbinarycrossentropy of m(x) and y -- and opt is a fresh Descent / Momentum / ADAM)
+#                                                                       -> GPU (si_train_*)
 #   * src/space_inference.jl:90-95 `density(z)` and :107 `ℓπ_grad(θ)`                          -> GPU (si_logdensity,
 #       si_logdensity_grad: ONE reverse sweep instead of M-wide ForwardDiff duals; `backend` is accepted and unused)
 #   * :rwmh / :mh sampler loop (:111-116)                                                        -> GPU (si_sample_rwmh)
@@ -186,7 +187,25 @@ end
 # rank followed by bcast_subspace! (the cfg3 flow) must not wait alone inside a gradient all-reduce.
 # compute_dtype: SI_DTYPE_OF_DATA (default: Float32 data => the Float32 pass, Float64 data => the Float64 pass, as in the
 # reference), or si_dtype(Float32) / si_dtype(Float64) to override
-function train_on_device!(ctx::Ctx, model, data, opt, T, c, print_freq; data_parallel = false, compute_dtype = SI_DTYPE_OF_DATA)
+# device_cost: which Flux loss the caller's `cost` closure is (its assertion, as for mse): :mse (default), :mae, :huber_loss or
+# (:huber_loss, δ), :logitcrossentropy (dims = 1), :logitbinarycrossentropy, each with agg = mean (si_train_set_cost)
+const SI_COSTS = Dict(:mse => Int32(0), :mae => Int32(1), :huber_loss => Int32(2), :logitcrossentropy => Int32(3),
+                      :logitbinarycrossentropy => Int32(4))
+function device_cost_id(device_cost)
+    name, param = device_cost isa Tuple ? device_cost : (device_cost, device_cost == :huber_loss ? 1.0 : 0.0)
+    haskey(SI_COSTS, name) || throw("Error: device_cost must be one of :mse, :mae, :huber_loss, :logitcrossentropy, :logitbinarycrossentropy")
+    return SI_COSTS[name], Float64(param)
+end
+
+# (id, param) of the cost the training state computes (si_train_cost_info)
+function train_cost_info(ctx::Ctx)
+    id = Ref{Int32}(0); param = Ref{Float64}(0.0)
+    check(ctx, ccall((:si_train_cost_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Float64}), ctx.h, id, param))
+    return id[], param[]
+end
+
+function train_on_device!(ctx::Ctx, model, data, opt, T, c, print_freq; data_parallel = false, compute_dtype = SI_DTYPE_OF_DATA,
+                          device_cost = :mse)
     X, Y, insize = train_matrices(data)
     tbl, N = layer_table(model, insize)
     kind, η, p1, p2 = device_optimiser(opt)
@@ -197,6 +216,8 @@ function train_on_device!(ctx::Ctx, model, data, opt, T, c, print_freq; data_par
          Int32, Float64, Float64, Float64, Int32),
         ctx.h, tbl, length(tbl), N, w0, X, Y, si_dtype(eltype(X)), size(X, 1), size(Y, 1), size(X, 2),
         min(data.batchsize, data.nobs), kind, η, p1, p2, Int32(compute_dtype)))
+    cid, cparam = device_cost_id(device_cost)   # (every set-up starts with mse)
+    cid != 0 && check(ctx, ccall((:si_train_set_cost, LIB), Int32, (Ptr{Cvoid}, Int32, Float64), ctx.h, cid, cparam))
     loss = Ref{Float64}(0.0)
     world, rank = comm_info(ctx)
     for i in 1:T
@@ -243,10 +264,10 @@ end
 # init = :zeros is what the reference's code does (W_swa = zeros, :31); :pretrained is what its docs describe (nn_example.md:44)
 function subspace_construction(model, cost, data, opt; T = 10, c = 1, M = 3, print_freq = 1, device = 0,
                                ctx = Ctx(device), max_cols = 0, keep_on_device = false, device_training = false,
-                               init = :zeros, data_parallel = false, a_storage = :f64, compute_dtype = :auto)
+                               init = :zeros, data_parallel = false, a_storage = :f64, compute_dtype = :auto, device_cost = :mse)
     N = swa_columns!(ctx, model, cost, data, opt; T = T, c = c, print_freq = print_freq, max_cols = max_cols,
                      device_training = device_training, init = init, data_parallel = data_parallel, a_storage = a_storage,
-                     compute_dtype = compute_dtype)
+                     compute_dtype = compute_dtype, device_cost = device_cost)
     W_swa = Vector{Float64}(undef, N)
     P = keep_on_device ? nothing : Matrix{Float64}(undef, N, M)
     s = Vector{Float64}(undef, M); K = Ref{Int64}(0)
@@ -263,11 +284,11 @@ end
 # with the package itself (tests/golden/make_golden_diffmap.jl).  Returns (W_swa, P) with P of size N x M, as the reference's P'.
 function diffusion_subspace(model, cost, data, opt; T = 10, c = 1, M = 3, print_freq = 1, device = 0,
                             ctx = Ctx(device), keep_on_device = false, device_training = false, init = :zeros,
-                            a_storage = :f64, compute_dtype = :auto, ϵ = 1.0, α = 1.0, kernel_sign = -1, rescale = true,
+                            a_storage = :f64, compute_dtype = :auto, device_cost = :mse, ϵ = 1.0, α = 1.0, kernel_sign = -1, rescale = true,
                             tol = 0.0, max_iters = 0)
     N = swa_columns!(ctx, model, cost, data, opt; T = T, c = c, print_freq = print_freq, max_cols = 0,
                      device_training = device_training, init = init, data_parallel = false, a_storage = a_storage,
-                     compute_dtype = compute_dtype)
+                     compute_dtype = compute_dtype, device_cost = device_cost)
     W_swa = Vector{Float64}(undef, N)
     P = keep_on_device ? nothing : Matrix{Float64}(undef, N, M)
     λ = Vector{Float64}(undef, M + 1); K = Ref{Int64}(0)
@@ -295,7 +316,7 @@ end
 # What subspace_construction and diffusion_subspace share (the reference has these lines twice, :28-59 and :169-200): training with
 # the SWA update and the deviation columns on the device.  Returns N.
 function swa_columns!(ctx::Ctx, model, cost, data, opt; T, c, print_freq, max_cols, device_training, init, data_parallel,
-                      a_storage, compute_dtype)
+                      a_storage, compute_dtype, device_cost = :mse)
     training_loss = 0.0
     ps = Flux.params(model)
     N = sum(length, ps)
@@ -312,7 +333,8 @@ function swa_columns!(ctx::Ctx, model, cost, data, opt; T, c, print_freq, max_co
         # compute_dtype = :auto: the device step computes in the DATA's element type, as the reference's Zygote pass does
         # (Float32 model + Float32 data: Float32 throughout; Float64 data: Float64); :f32 / :f64 override
         cd = compute_dtype == :auto ? SI_DTYPE_OF_DATA : compute_dtype == :f32 ? SI_F32 : SI_F64
-        train_on_device!(ctx, model, data, opt, T, c, print_freq; data_parallel = data_parallel, compute_dtype = cd)
+        train_on_device!(ctx, model, data, opt, T, c, print_freq; data_parallel = data_parallel, compute_dtype = cd,
+                         device_cost = device_cost)
     else
         for i in 1:T
             for d in data

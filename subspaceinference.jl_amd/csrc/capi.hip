@@ -83,7 +83,7 @@ static void resolve_events(Ctx* c) {
 static void free_construct(Ctx* c) {
   c->ae.reset();   // (si_ae_train_* may read the deviation matrix in place)
   // an inference set up on the construction's own W_swa / P dies with it
-  if (c->i_ready && c->i_swa == c->d_swa && c->d_swa != nullptr) free_infer(c);
+  if (c->setup.ready && c->setup.swa == c->d_swa && c->d_swa != nullptr) free_infer(c);
   static_cast<ConstructState&>(*c) = ConstructState();
 }
 
@@ -232,6 +232,89 @@ int32_t dense_value_and_grad_f64(Ctx* ctx, hipStream_t st, const DenseValueGrad&
   else
     launch_delta_out(st, s.Y, sw.hs[nl - 1], (int64_t)sw.layers[nl - 1].out * sw.B, s.scale, sw.layers[nl - 1].act, sw.delta[0]);
   return dense_reverse_sweep(ctx, st, sw);
+}
+
+// ---- the reverse-sweep workspace of a chain, sized here and nowhere else, and the dispatch over its three routes ---------------
+static bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const si_layer* layers, int L, bool fuse_tail, int64_t N, int32_t in_dim,
+                            int32_t out_dim, int64_t Bmax) {
+  size_t maxpart32 = 1, maxwt = 1, maxin = (size_t)in_dim, maxw = 1;
+  for (int l = 0; l < L; ++l) {
+    maxpart32 = std::max(maxpart32, backward_weight_f32_part_elems(layers[l].out, layers[l].in, Bmax, ctx->num_cu));
+    maxwt = std::max(maxwt, (size_t)layers[l].out * (size_t)layers[l].in);
+    maxin = std::max(maxin, (size_t)layers[l].in);
+    maxw = std::max(maxw, (size_t)layers[l].out);
+  }
+  const size_t wide = std::max(maxin, maxw);
+  ws.hs32 = std::vector<DevBuf<float>>((size_t)L);
+  bool ok = ws.delta32[0].alloc(maxw * (size_t)Bmax) && ws.delta32[1].alloc(maxw * (size_t)Bmax) && ws.gw32.alloc((size_t)pad_ld(N)) &&
+            ws.wt32.alloc(maxwt) && ws.zero32.alloc(wide) && ws.part32.alloc(maxpart32) &&
+            ws.rspart64.alloc(rowsum_f32_part_elems((int)wide)) && ws.yhat64.alloc((size_t)out_dim * (size_t)Bmax) &&
+            (!fuse_tail || ws.tailpart64.alloc(tail_bwd_f32_part_elems(layers[L - 1].out, layers[L - 1].in)));
+  for (int l = 0; l < L && ok; ++l)   // (a fused head's own output lives in yhat64)
+    if (!(fuse_tail && l == L - 1)) ok = ws.hs32[(size_t)l].alloc((size_t)layers[l].out * (size_t)Bmax);
+  return ok && hipMemsetAsync(ws.zero32, 0, wide * sizeof(float), ctx->stream) == hipSuccess;
+}
+
+bool sweep_ws_alloc(Ctx* ctx, SweepWs& ws, const si_layer* layers, int L, const NetPlan& plan, bool fuse_tail, int64_t N, int32_t in_dim,
+                    int32_t out_dim, int64_t Bmax, bool f32) {
+  ws = SweepWs();
+  ws.route = plan.has_conv ? TrainRoute::Conv : f32 ? TrainRoute::DenseF32 : TrainRoute::DenseF64;
+  const size_t bm = (size_t)Bmax;
+  bool ok = true;
+  if (ws.route == TrainRoute::DenseF32) {
+    ok = sweep_f32_alloc(ctx, ws.f32, layers, L, fuse_tail, N, in_dim, out_dim, Bmax);
+  } else {
+    size_t maxw = (size_t)plan.max_elems;   // rows of the two Delta buffers: the largest activation (Conv), the widest layer (Dense)
+    if (ws.route == TrainRoute::Conv) {
+      size_t nb, nr, nw, nd;
+      net_scratch_sizes(plan, Bmax, ctx->num_cu, &nb, &nr, &nw, &nd);
+      ws.pidx = std::vector<DevBuf<uint8_t>>((size_t)L);
+      ws.net.pidx = ws.pidx.data();
+      ok = ws.net.bwpart.alloc(nb) && ws.net.rspart.alloc(nr) && ws.net.wt.alloc(nw) && ws.net.dbtmp.alloc(nd);
+    } else {
+      size_t maxpart = 1;
+      maxw = 1;
+      for (int l = 0; l < L; ++l) {
+        maxw = std::max(maxw, (size_t)layers[l].out);
+        maxpart = std::max(maxpart, backward_weight_part_elems(layers[l].out, layers[l].in, Bmax, ctx->num_cu));
+      }
+      if (fuse_tail) maxpart = std::max(maxpart, tail_bwd_part_elems(layers[L - 1].out, layers[L - 1].in));
+      ok = ws.bwpart.alloc(maxpart) && ws.rspart.alloc((size_t)rowsum_chunks() * maxw);
+    }
+    ok = ok && ws.delta[0].alloc(maxw * bm) && ws.delta[1].alloc(maxw * bm);
+    ws.hs = std::vector<DevBuf<double>>((size_t)L);
+    for (size_t l = 0; l < (size_t)L && ok; ++l) {
+      if (plan.has_conv && net_grad_fused(plan, l))   // Conv + MaxPool as one kernel: a byte index instead of the un-pooled activation
+        ok = ws.pidx[l].alloc(net_pidx_bytes(plan, l, Bmax));
+      else
+        ok = ws.hs[l].alloc((size_t)plan.L[l].out_elems * bm);
+    }
+  }
+  if (!ok) ws = SweepWs();
+  ws.ready = ok;
+  return ok;
+}
+
+int32_t chain_value_and_grad(Ctx* ctx, hipStream_t st, SweepWs& ws, const ChainValueGrad& in) {
+  if (ws.route == TrainRoute::DenseF32) {
+    // fp32 operands and activations on v_mfma_f32_32x32x2_f32; fp64 for the head's partial sums, the SSE and every sum over the
+    // batch (rounded once into the fp32 gradient).  Behind it the gradient as every reader sees it: fp64 words holding fp32 values
+    const DenseSweepF32 sw{in.layers, in.nl, in.fuse_tail, in.w32, in.w64, in.X32, in.Y, &ws.f32, in.part, in.ssepart, in.sse, in.sse_blocks,
+                           in.B, in.N, in.scale, in.cost};
+    const int32_t rc = dense_value_and_grad_f32(ctx, st, sw);
+    if (rc != SI_OK) return rc;
+    launch_widen_f32_to_f64(st, ws.f32.gw32, in.N, in.gw, ctx->num_cu);
+    return SI_OK;
+  }
+  if (ws.route == TrainRoute::Conv) {   // Conv / MaxPool / flatten layers: the generic forward / reverse sweep of capi_net.hip
+    const NetValueGrad vg{in.plan, in.w64, in.plan->input_spatial ? in.Xc : in.X, in.Y, in.B, ws.hs.data(), in.wpack, in.ssepart, in.sse_blocks,
+                          in.sse, {ws.delta[0], ws.delta[1]}, in.gw, &ws.net, in.N, in.scale, in.bwd_flops, in.cost};
+    return net_value_and_grad(ctx, vg);
+  }
+  const DenseValueGrad vg{{in.layers, in.nl, in.fuse_tail, in.w64, in.X, ws.hs.data(), {ws.delta[0], ws.delta[1]}, in.gw, ws.rspart, ws.bwpart,
+                           in.B},
+                          in.Y, in.fuse_slots, in.part, in.ssepart, in.sse, in.sse_blocks, in.N, in.scale, in.traffic, in.cost};
+  return dense_value_and_grad_f64(ctx, st, vg);
 }
 
 }  // namespace si
@@ -391,7 +474,7 @@ int32_t si_construct_begin(si_ctx* ctx, int64_t N, int64_t K_capacity, int32_t m
   ctx->ae.reset();   // an autoencoder training state may have borrowed the old deviation matrix
   if (ctx->d_swa != nullptr && ctx->N == N) {
     // same problem size as the previous construction: keep the buffers (ensure_A re-uses A when it is large enough)
-    if (ctx->i_ready && ctx->i_swa == ctx->d_swa) free_infer(ctx);  // an inference bound to the old W_swa / P
+    if (ctx->setup.ready && ctx->setup.swa == ctx->d_swa) free_infer(ctx);  // an inference bound to the old W_swa / P
     ctx->c_finished = ctx->gram_valid = false;
     ctx->K = 0;
     ctx->npush = 0;
@@ -755,7 +838,7 @@ int32_t si::construct_alloc_P(si::Ctx* ctx, int32_t M) {
   if (ctx->d_P != nullptr && ctx->M_built == M) return SI_OK;
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // P is re-allocated: an inference bound to the old P of this construction must not outlive it
-  if (ctx->i_ready && ctx->i_P == ctx->d_P && ctx->d_P != nullptr) free_infer(ctx);
+  if (ctx->setup.ready && ctx->setup.P == ctx->d_P && ctx->d_P != nullptr) free_infer(ctx);
   ctx->M_built = 0;
   if (!ctx->d_P.alloc((size_t)ctx->ldA * M))
     return fail(ctx, SI_ERR_NOMEM, "si_construct_finish: allocation of P failed");

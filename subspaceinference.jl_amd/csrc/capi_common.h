@@ -33,7 +33,7 @@ inline void accept_rates(const std::vector<int64_t>& nacc, int64_t itr, double* 
 namespace si {
 
 // What a density evaluation reads that depends on WHICH data set and WHICH workspace the call is for.  What belongs to the chain
-// set up stays on the context: layers and plan, fuse_tail, the slot counts, d_w / d_w32 / d_wpack*, d_zprop, d_sse, d_wsq, the
+// set up stays on the context: layers and plan, fuse_tail, the slot counts, fw.w / fw.w32 / fw.wpack*, chains.zprop, chains.sse, chains.wsq, the
 // tile program.  setup_view is the view of the set-up's own data; si_predict builds one over its temporaries.
 struct DensityView {
   const double *X, *Xc;           // Xc: X re-laid channel-fastest (spatial input), else null
@@ -50,6 +50,42 @@ struct DensityView {
   bool defer_sse_final;           // the SSE block partials stay in ssepart (the RWMH tail kernel sums them)
   bool is_setup_data;             // X, Y, B are the set-up's: what the narrow chain's plan and tile program were built for
 };
+// the rule, for si_infer_setup and si_train_setup alike: a narrow last layer (regression heads: out = 1) of a Dense chain is
+// folded into the epilogue of the layer before it (kernels_gemm.h carries the four MFMA-epilogue activations)
+inline bool head_fused(const NetPlan& plan, const si_layer* layers, int L) {
+  return !plan.has_conv && (L >= 2) && layers[L - 1].out <= SI_FUSE_MAX_OUT &&
+         layers[L - 1].act < SI_ACT_LEAKYRELU && layers[L - 2].act < SI_ACT_LEAKYRELU;
+}
+// ---- the three value-and-gradient passes (dense_value_and_grad_f64 / _f32, net_value_and_grad) behind one workspace and one
+// dispatch (capi.hip), for si_logdensity_grad and the training step.  sweep_ws_alloc is the ONE place that decides how large a
+// reverse-sweep buffer is: the route follows from plan.has_conv and f32 (never both); on any failure ws is left empty.
+bool sweep_ws_alloc(Ctx* ctx, SweepWs& ws, const si_layer* layers, int L, const NetPlan& plan, bool fuse_tail, int64_t N, int32_t in_dim,
+                    int32_t out_dim, int64_t Bmax, bool f32);
+// What differs between the callers of the pass.  chain_value_and_grad runs the route of `ws` on `st` (the context's stream) over
+// B <= Bmax observations and, on the fp32 route, widens gw32 into gw behind it: gw holds the gradient, *sse the sum of squared
+// errors (another cost: its numerator).
+struct ChainValueGrad {
+  const si_layer* layers;
+  size_t nl;
+  const NetPlan* plan;
+  bool fuse_tail;
+  const double* w64;      // flat weights, and rounded to fp32 (DenseF32)
+  const float* w32;
+  const double *X, *Xc;   // input of layer 0; Xc: re-laid channel-fastest (a Conv chain on spatial input: net_input)
+  const float* X32;       // (DenseF32)
+  const double* Y;
+  int64_t B, N;
+  double* part;           // the forward pass's head partials and feature slots (the fp32 pass counts its own slots)
+  int fuse_slots;
+  double *ssepart, *sse;
+  int sse_blocks;
+  double *gw, *wpack;     // wpack: packed conv weights (Conv)
+  double scale;           // of Delta_L: -2 / d for the mse loss, 1 / sigma^2 for the log-density
+  const CostTail* cost;   // training with another cost, else nullptr
+  bool traffic;           // profile: DenseForward::traffic (DenseF64)
+  double bwd_flops;       // profile: NetValueGrad::bwd_flops (Conv)
+};
+int32_t chain_value_and_grad(Ctx* ctx, hipStream_t st, SweepWs& ws, const ChainValueGrad& in);
 // the cap on a stacked workspace: how many chains one pass of launches carries follows from it (batch_width, vgrad_route, the
 // NeuralODE gradient's record)
 constexpr double SI_BATCH_BYTES = 2.0 * 1024.0 * 1024.0 * 1024.0;
@@ -61,7 +97,7 @@ extern "C" {   // (defined inside the extern "C" blocks of their translation uni
 // capi_infer.hip
 int32_t ensure_chains(si_ctx* ctx, int32_t C);   // forward workspace + sampler state for C chains
 si::DensityView setup_view(const si_ctx* ctx, bool defer_sse_final = false);
-// d_zprop[:, c0 .. c0+nc) -> d_sse, nc <= the view's chain slots; eval_density_all: all C chains, fw_slots at a time
+// chains.zprop[:, c0 .. c0+nc) -> chains.sse, nc <= the view's chain slots; eval_density_all: all C chains, fw.slots at a time
 int32_t eval_density(si_ctx* ctx, const si::DensityView& v, int c0, int nc, const double** yhat_out);
 int32_t eval_density_all(si_ctx* ctx, const si::DensityView& v, int C);
 // "form the weights of these points": w[:, c] = W_swa + P z_c (K4), or W_swa + decoder(z_c) while a decoder is set
@@ -69,7 +105,7 @@ int32_t eval_density_all(si_ctx* ctx, const si::DensityView& v, int C);
 // kernel of its own.  w32: also rounded once to fp32 (P route only).  keep_y (decoder route, n = 1): decoder(z) stays in dec.y
 // for pull_back_to_z.  Queued on the stream; an error only when the decoder's workspace cannot grow.
 int32_t form_weights(si_ctx* ctx, const double* z_dev, int32_t n, double* w, int64_t ldw, float* w32 = nullptr, bool keep_y = false);
-// "pull d_gw back to z": gz = P' gw, or J_decoder(z)' gw at the point form_weights(.., keep_y = true) saw last
+// "pull grad.gw back to z": gz = P' gw, or J_decoder(z)' gw at the point form_weights(.., keep_y = true) saw last
 void pull_back_to_z(si_ctx* ctx, const double* gw, double* gz);
 double mvnormal_c0(double d, double sigma);
 double prior_c0(const si_ctx* ctx);
@@ -151,7 +187,7 @@ inline int32_t reserve_chain_state(si_ctx* ctx, const char* who, int32_t C) {
 inline void chain_run_args(ChainRun& r, si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, int32_t chain_id0, bool want_G) {
   ChainState& s = ctx->chain_state;
   r.z = s.z, r.lp = s.lp, r.g = s.g, r.zp = s.zp, r.lpp = s.lpp, r.gp = s.gp;
-  r.Z_out = ctx->d_outZ, r.lp_out = ctx->d_outlp, r.G_out = want_G ? ctx->d_outG.get() : nullptr;
+  r.Z_out = ctx->chains.outZ, r.lp_out = ctx->chains.outlp, r.G_out = want_G ? ctx->mala.outG.get() : nullptr;
   r.M = ctx->iM, r.chain_id0 = chain_id0, r.itr = itr, r.seed = seed, r.sigma_z = sigma_z;
 }
 
@@ -168,13 +204,13 @@ template <class Launch>
 bool synced_round(si_ctx* ctx, StackedVgrad& vg, int32_t& open, hipError_t& e, int32_t& rc, Launch&& launch) {
   if (e == hipSuccess && rc == SI_OK) eval_pending(ctx, vg, e, rc);
   if (e != hipSuccess || rc != SI_OK) return false;
-  if ((e = hipMemsetAsync(ctx->d_hmc_open, 0, sizeof(int32_t), ctx->stream)) != hipSuccess) return false;
+  if ((e = hipMemsetAsync(ctx->hmc.open, 0, sizeof(int32_t), ctx->stream)) != hipSuccess) return false;
   {
     ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-    launch(ctx->d_hmc_open.get());
+    launch(ctx->hmc.open.get());
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(&open, ctx->d_hmc_open, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&open, ctx->hmc.open, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   return e == hipSuccess;
 }

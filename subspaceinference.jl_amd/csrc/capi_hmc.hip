@@ -50,16 +50,16 @@ int32_t hmc_reserve_state(si_ctx* ctx, const char* who, int32_t C, bool nuts) {
   const size_t mc = (size_t)ctx->iM * (size_t)C;
   int32_t rc = reserve_chain_state(ctx, who, C);
   if (rc == SI_OK)
-    rc = reserve_state(ctx, who, ctx->hmc_cap, C, [&] {
-      return ctx->d_hmc_rh.alloc(mc) && ctx->d_hmc_minv.alloc(mc) && ctx->d_hmc_wmean.alloc(mc) && ctx->d_hmc_wm2.alloc(mc) &&
-             ctx->d_hmc_chain.alloc((size_t)C) && ctx->d_hmc_open.alloc(1);
+    rc = reserve_state(ctx, who, ctx->hmc.cap, C, [&] {
+      return ctx->hmc.rh.alloc(mc) && ctx->hmc.minv.alloc(mc) && ctx->hmc.wmean.alloc(mc) && ctx->hmc.wm2.alloc(mc) &&
+             ctx->hmc.chain.alloc((size_t)C) && ctx->hmc.open.alloc(1);
     });
   if (rc == SI_OK && nuts)
-    rc = reserve_state(ctx, who, ctx->nuts_cap, C, [&] {
-      for (DevBuf<double>* b : {&ctx->d_nuts_zm, &ctx->d_nuts_rm, &ctx->d_nuts_gm, &ctx->d_nuts_zq, &ctx->d_nuts_rq, &ctx->d_nuts_gq,
-                                &ctx->d_nuts_rho, &ctx->d_nuts_zc, &ctx->d_nuts_gc})
+    rc = reserve_state(ctx, who, ctx->nuts.cap, C, [&] {
+      for (DevBuf<double>* b : {&ctx->nuts.zm, &ctx->nuts.rm, &ctx->nuts.gm, &ctx->nuts.zq, &ctx->nuts.rq, &ctx->nuts.gq,
+                                &ctx->nuts.rho, &ctx->nuts.zc, &ctx->nuts.gc})
         if (!b->alloc(mc)) return false;
-      return ctx->d_nuts_stack.alloc(4 * mc * NUTS_MAX_DEPTH) && ctx->d_nuts_tree.alloc((size_t)C);
+      return ctx->nuts.stack.alloc(4 * mc * NUTS_MAX_DEPTH) && ctx->nuts.tree.alloc((size_t)C);
     });
   return rc;
 }
@@ -67,8 +67,8 @@ int32_t hmc_reserve_state(si_ctx* ctx, const char* who, int32_t C, bool nuts) {
 HmcRun hmc_run_args(si_ctx* ctx, int64_t itr, double sigma_z, double delta, uint64_t seed, int32_t chain_id0, bool want_G, bool want_Minv) {
   HmcRun a;
   chain_run_args(a, ctx, itr, sigma_z, seed, chain_id0, want_G);
-  a.rh = ctx->d_hmc_rh, a.minv = ctx->d_hmc_minv, a.wmean = ctx->d_hmc_wmean, a.wm2 = ctx->d_hmc_wm2, a.chain = ctx->d_hmc_chain;
-  a.alpha_out = ctx->d_outalpha, a.eps_out = ctx->d_outeps, a.Minv_out = want_Minv ? ctx->d_outMinv.get() : nullptr;
+  a.rh = ctx->hmc.rh, a.minv = ctx->hmc.minv, a.wmean = ctx->hmc.wmean, a.wm2 = ctx->hmc.wm2, a.chain = ctx->hmc.chain;
+  a.alpha_out = ctx->hmc.outalpha, a.eps_out = ctx->hmc.outeps, a.Minv_out = want_Minv ? ctx->hmc.outMinv.get() : nullptr;
   a.delta = delta;
   return a;
 }
@@ -115,7 +115,7 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
                       double* Minv_out) {
   CHECK_CTX(ctx);
   const char* who = "si_sample_hmc";
-  ctx->info_hmc = CallInfo();   // (si_hmc_kernel_info reports THIS call)
+  ctx->hmc.info = CallInfo();   // (si_hmc_kernel_info reports THIS call)
   // (every comparison is false for a NaN: refused)
   int32_t rc = grad_entry_check(ctx, who, itr > 0 && n_adapts >= 0 && n_adapts <= itr && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0 &&
                                               delta > 0.0 && delta < 1.0);
@@ -125,8 +125,8 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
   const int64_t cols = itr + 1;
   if ((rc = hmc_reserve_state(ctx, who, C, false)) != SI_OK) return rc;
   const size_t zelems = (size_t)M * (size_t)cols * (size_t)C, selems = (size_t)cols * (size_t)C;
-  if (!ctx->d_outZ.reserve(zelems) || !ctx->d_outlp.reserve(selems) || !ctx->d_outalpha.reserve(selems) || !ctx->d_outeps.reserve(selems) ||
-      (G_out && !ctx->d_outG.reserve(zelems)) || (Minv_out && !ctx->d_outMinv.reserve(zelems)))
+  if (!ctx->chains.outZ.reserve(zelems) || !ctx->chains.outlp.reserve(selems) || !ctx->hmc.outalpha.reserve(selems) || !ctx->hmc.outeps.reserve(selems) ||
+      (G_out && !ctx->mala.outG.reserve(zelems)) || (Minv_out && !ctx->hmc.outMinv.reserve(zelems)))
     return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
   HmcPhases phases(n_adapts);
   const HmcRun a = hmc_run_args(ctx, itr, sigma_z, delta, seed, chain_id0, G_out != nullptr, Minv_out != nullptr);
@@ -149,18 +149,18 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
     e = hipGetLastError();
   }
   const size_t zbytes = zelems * sizeof(double), sbytes = selems * sizeof(double);
-  rc = finish_downloads(ctx, who, e, rc, {{Z_out, ctx->d_outZ, zbytes}, {lp_out, ctx->d_outlp, sbytes}, {alpha_out, ctx->d_outalpha, sbytes},
-                                          {eps_out, ctx->d_outeps, sbytes}, {G_out, a.G_out, zbytes}, {Minv_out, a.Minv_out, zbytes}});
+  rc = finish_downloads(ctx, who, e, rc, {{Z_out, ctx->chains.outZ, zbytes}, {lp_out, ctx->chains.outlp, sbytes}, {alpha_out, ctx->hmc.outalpha, sbytes},
+                                          {eps_out, ctx->hmc.outeps, sbytes}, {G_out, a.G_out, zbytes}, {Minv_out, a.Minv_out, zbytes}});
   if (rc != SI_OK) return rc;
-  ctx->info_hmc = call_info(vg, rounds);
+  ctx->hmc.info = call_info(vg, rounds);
   return SI_OK;
 }
 
 int32_t si_hmc_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out, int32_t* search_rounds_out) {
   CHECK_CTX(ctx);
-  if (fused_out) *fused_out = ctx->info_hmc.fused;
-  if (passes_out) *passes_out = ctx->info_hmc.passes;
-  if (search_rounds_out) *search_rounds_out = ctx->info_hmc.search_rounds;
+  if (fused_out) *fused_out = ctx->hmc.info.fused;
+  if (passes_out) *passes_out = ctx->hmc.info.passes;
+  if (search_rounds_out) *search_rounds_out = ctx->hmc.info.search_rounds;
   return SI_OK;
 }
 

@@ -3,8 +3,9 @@
 // every arithmetic step runs in the kernels of kernels_*.hip.  No CPU fallback anywhere in this file.  eval_density is K4, the
 // optional prior sum and ONE of three routes (density_net, density_fused, density_layers); the data and workspace it runs on
 // come in a DensityView (capi_common.h), so no caller steers it through the context -- si_predict hands it its own.  The per-layer passes over a
-// chain are shared with the training step: dense_forward / dense_value_and_grad_f64 (capi.hip), dense_value_and_grad_f32
-// (capi_train.hip), net_forward / net_value_and_grad (capi_net.hip).
+// chain are shared with the training step: dense_forward and net_forward for the density; for the gradient the whole pass --
+// workspace (SweepWs, sized by sweep_ws_alloc), route and dispatch (chain_value_and_grad, capi.hip) -- and the narrow-head rule
+// (head_fused).  si_logdensity_grad keeps form_weights, the prior's two launches, pull_back_to_z and the read-back.
 #include "capi_common.h"
 #include "chain_spec_rtc.h"
 
@@ -22,23 +23,23 @@ extern "C" {
 // reproduces).  docs/src/nn_example.md:112-118 is the model this is for.
 static constexpr int SI_FUSED_MAX_WIDTH = 256;
 static bool fused_chain_class(const si_ctx* ctx) {
-  if (ctx->f32 || ctx->plan.has_conv) return false;
+  if (ctx->setup.f32 || ctx->setup.plan.has_conv) return false;
   const int L = (int)ctx->layers.size();
   if (L < 1 || L > SI_CHAIN_MAX_LAYERS) return false;
   for (int l = 0; l + 1 < L; ++l)
     if (ctx->layers[(size_t)l].out > SI_FUSED_MAX_WIDTH) return false;
-  if (!ctx->fuse_tail && ctx->layers[(size_t)L - 1].out > SI_FUSED_MAX_WIDTH) return false;
+  if (!ctx->setup.fuse_tail && ctx->layers[(size_t)L - 1].out > SI_FUSED_MAX_WIDTH) return false;
   if ((int64_t)ctx->out_dim * ctx->B > (int64_t)256 * ctx->sse_blocks) return false;
   ChainFusedPlan fp;
-  return chain_fused_plan(fp, ctx->layers.data(), L, ctx->B, 1, ctx->fuse_tail,
-                          ctx->fuse_tail ? dense_fused_slot_feats(ctx->layers[(size_t)L - 2].out) : 0, ctx->fuse_slots) != 0;
+  return chain_fused_plan(fp, ctx->layers.data(), L, ctx->B, 1, ctx->setup.fuse_tail,
+                          ctx->setup.fuse_tail ? dense_fused_slot_feats(ctx->layers[(size_t)L - 2].out) : 0, ctx->fuse_slots) != 0;
 }
 // batch tile of the stacked launch (16 NB observations per workgroup; the 16-feature tiles of a layer dealt over its four
 // waves).  Measured on docs/src/nn_example.md's model at 512 chains (profiles/r05_chain_grid_knockouts.log): 32 observations
 // per workgroup 730 us, 16 per workgroup 780 us, one WAVE per 16-observation tile without any barrier (launch_chain_fused's
 // wave_tiles form, kept for the harness) 1430 us -- a single wave's stream of small dependent steps leaves the SIMD idle.
 void fused_fill_program(const si_ctx* ctx, ChainFusedPlan& fp) {
-  fp.prog = ctx->d_cgprog;
+  fp.prog = ctx->loop.cgprog;
   for (int i = 0; i < 5; ++i) {
     fp.prog_start[i] = ctx->cg_start[i];
     fp.prog_count[i] = ctx->cg_count[i];
@@ -48,10 +49,10 @@ void fused_fill_program(const si_ctx* ctx, ChainFusedPlan& fp) {
 static size_t fused_plan_for(const si_ctx* ctx, int nchains, ChainFusedPlan& fp, int* nb_out, bool* wave_tiles) {
   fused_fill_program(ctx, fp);
   const int L = (int)ctx->layers.size();
-  const int sf = ctx->fuse_tail ? dense_fused_slot_feats(ctx->layers[(size_t)L - 2].out) : 0;
+  const int sf = ctx->setup.fuse_tail ? dense_fused_slot_feats(ctx->layers[(size_t)L - 2].out) : 0;
   *wave_tiles = false;
   for (int nb : {2, 1}) {
-    const size_t lds = chain_fused_plan(fp, ctx->layers.data(), L, ctx->B, nb, ctx->fuse_tail, sf, ctx->fuse_slots);
+    const size_t lds = chain_fused_plan(fp, ctx->layers.data(), L, ctx->B, nb, ctx->setup.fuse_tail, sf, ctx->fuse_slots);
     const int64_t wgs = (ctx->B + 16 * nb - 1) / (16 * nb) * nchains;
     if (lds != 0 && (nb == 1 || (lds <= (size_t)80 * 1024 && wgs >= (int64_t)2 * ctx->num_cu))) {
       *nb_out = nb;
@@ -63,25 +64,25 @@ static size_t fused_plan_for(const si_ctx* ctx, int nchains, ChainFusedPlan& fp,
 
 // forward workspace for `slots` chains evaluated in one launch (grid.y = chain slot)
 static bool alloc_forward(si_ctx* ctx, int slots) {
-  for (DevBuf<double>* b : {&ctx->d_w, &ctx->d_act[0], &ctx->d_act[1], &ctx->d_ssepart, &ctx->d_part, &ctx->d_yhat}) b->reset();
-  for (DevBuf<float>* b : {&ctx->d_w32, &ctx->d_act32[0], &ctx->d_act32[1]}) b->reset();
-  ctx->fw_slots = 0;
+  for (DevBuf<double>* b : {&ctx->fw.w, &ctx->fw.act[0], &ctx->fw.act[1], &ctx->fw.ssepart, &ctx->fw.part, &ctx->fw.yhat}) b->reset();
+  for (DevBuf<float>* b : {&ctx->fw.w32, &ctx->fw.act32[0], &ctx->fw.act32[1]}) b->reset();
+  ctx->fw.slots = 0;
   const size_t S = (size_t)slots, dB = (size_t)ctx->out_dim * (size_t)ctx->B;
   const bool node = ctx->node.d > 0;   // a NeuralODE set-up: its layers run inside the integration kernel, which keeps its own per-trajectory sums
   // SI_F32: fp32 weights + fp32 ping-pong activations INSTEAD of the fp64 activations (the fp64 weights stay: K4 writes
   // both, the output map / prior / gradient read them); the head partials serve both paths (the larger slot count)
-  const size_t pslots = (size_t)std::max(ctx->fuse_slots, ctx->fuse_slots32);
-  if (!ctx->d_w.alloc(S * (size_t)pad_ld(ctx->iN)) ||
-      (!ctx->f32 && !node && (!ctx->d_act[0].alloc(S * (size_t)ctx->act_elems) || !ctx->d_act[1].alloc(S * (size_t)ctx->act_elems))) ||
-      (ctx->f32 && (!ctx->d_w32.alloc(S * (size_t)pad_ld(ctx->iN)) || !ctx->d_act32[0].alloc(S * (size_t)ctx->act_elems) ||
-                    !ctx->d_act32[1].alloc(S * (size_t)ctx->act_elems))) ||
-      (!node && !ctx->d_ssepart.alloc(S * (size_t)ctx->sse_blocks)) ||
-      (ctx->fuse_tail && !ctx->d_part.alloc(S * pslots * dB)) ||
-      ((ctx->fuse_tail || ctx->f32 || ctx->fused_ok) && !ctx->d_yhat.alloc(S * dB)))
+  const size_t pslots = (size_t)std::max(ctx->fuse_slots, ctx->setup.fuse_slots32);
+  if (!ctx->fw.w.alloc(S * (size_t)pad_ld(ctx->iN)) ||
+      (!ctx->setup.f32 && !node && (!ctx->fw.act[0].alloc(S * (size_t)ctx->act_elems) || !ctx->fw.act[1].alloc(S * (size_t)ctx->act_elems))) ||
+      (ctx->setup.f32 && (!ctx->fw.w32.alloc(S * (size_t)pad_ld(ctx->iN)) || !ctx->fw.act32[0].alloc(S * (size_t)ctx->act_elems) ||
+                    !ctx->fw.act32[1].alloc(S * (size_t)ctx->act_elems))) ||
+      (!node && !ctx->fw.ssepart.alloc(S * (size_t)ctx->sse_blocks)) ||
+      (ctx->setup.fuse_tail && !ctx->fw.part.alloc(S * pslots * dB)) ||
+      ((ctx->setup.fuse_tail || ctx->setup.f32 || ctx->setup.fused_ok) && !ctx->fw.yhat.alloc(S * dB)))
     return false;
   ctx->wsq_blocks = sse_num_blocks(ctx->iN, ctx->num_cu);
-  if (!ctx->d_wsqpart.alloc(S * (size_t)ctx->wsq_blocks)) return false;
-  ctx->fw_slots = slots;
+  if (!ctx->fw.wsqpart.alloc(S * (size_t)ctx->wsq_blocks)) return false;
+  ctx->fw.slots = slots;
   return true;
 }
 
@@ -127,29 +128,29 @@ static int32_t infer_setup_common(si_ctx* ctx, const si_layer* layers, int32_t L
     if (!ctx->c_finished) return fail(ctx, SI_ERR_STATE, who + ": no finished construction to take W_swa / P from");
     if (ctx->N != N || ctx->M_built != M)
       return fail(ctx, SI_ERR_INVALID, who + ": N / M differ from the finished construction");
-    ctx->i_swa = ctx->d_swa;
-    ctx->i_P = ctx->d_P;
+    ctx->setup.swa = ctx->d_swa;
+    ctx->setup.P = ctx->d_P;
     ctx->ldP = ctx->ldA;
   } else {
     if (src == SRC_DEV_BORROW) {
       // used in place: the caller keeps both buffers alive (and unchanged) until the next set-up / si_destroy
       ctx->ldP = ldP_in;
-      ctx->i_swa = W_swa;
-      ctx->i_P = P;
+      ctx->setup.swa = W_swa;
+      ctx->setup.P = P;
     } else {
       const hipMemcpyKind kind = src == SRC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
       ctx->ldP = pad_ld(N);
-      if (!ctx->d_iswa.alloc((size_t)ctx->ldP) || !ctx->d_iP.alloc((size_t)ctx->ldP * M)) {
+      if (!ctx->setup.swa_own.alloc((size_t)ctx->ldP) || !ctx->setup.P_own.alloc((size_t)ctx->ldP * M)) {
         free_infer(ctx);
         return fail(ctx, SI_ERR_NOMEM, who + ": allocation of W_swa / P failed");
       }
-      SI_HIP(ctx, hipMemsetAsync(ctx->d_iswa, 0, (size_t)ctx->ldP * sizeof(double), ctx->stream));
-      SI_HIP(ctx, hipMemsetAsync(ctx->d_iP, 0, (size_t)ctx->ldP * M * sizeof(double), ctx->stream));
-      SI_HIP(ctx, hipMemcpyAsync(ctx->d_iswa, W_swa, (size_t)N * sizeof(double), kind, ctx->stream));
-      SI_HIP(ctx, hipMemcpy2DAsync(ctx->d_iP, (size_t)ctx->ldP * sizeof(double), P, (size_t)ldP_in * sizeof(double),
+      SI_HIP(ctx, hipMemsetAsync(ctx->setup.swa_own, 0, (size_t)ctx->ldP * sizeof(double), ctx->stream));
+      SI_HIP(ctx, hipMemsetAsync(ctx->setup.P_own, 0, (size_t)ctx->ldP * M * sizeof(double), ctx->stream));
+      SI_HIP(ctx, hipMemcpyAsync(ctx->setup.swa_own, W_swa, (size_t)N * sizeof(double), kind, ctx->stream));
+      SI_HIP(ctx, hipMemcpy2DAsync(ctx->setup.P_own, (size_t)ctx->ldP * sizeof(double), P, (size_t)ldP_in * sizeof(double),
                                    (size_t)N * sizeof(double), (size_t)M, kind, ctx->stream));
-      ctx->i_swa = ctx->d_iswa;
-      ctx->i_P = ctx->d_iP;
+      ctx->setup.swa = ctx->setup.swa_own;
+      ctx->setup.P = ctx->setup.P_own;
     }
   }
   ctx->node.d = node_d;   // (> 0 from here on: alloc_forward leaves the Chain kernels' activation and SSE-partial buffers out)
@@ -162,51 +163,49 @@ static int32_t infer_setup_common(si_ctx* ctx, const si_layer* layers, int32_t L
   ctx->sigma_m = sigma_m;
   ctx->main_layer = main_layer;
   // fused tail: a narrow last layer (regression heads: out = 1) is folded into the epilogue of the layer before it
-  ctx->plan = plan;
-  ctx->fuse_tail = !plan.has_conv && (L >= 2) && layers[L - 1].out <= SI_FUSE_MAX_OUT &&
-                   layers[L - 1].act < SI_ACT_LEAKYRELU && layers[L - 2].act < SI_ACT_LEAKYRELU;   // (kernels_gemm.h)
-  if (node_d > 0) ctx->fuse_tail = false;   // (a NeuralODE's layers are evaluated inside the integration kernel alone)
-  ctx->fuse_slots = ctx->fuse_tail ? dense_fused_slots(layers[L - 2].out) : 0;
-  ctx->f32 = compute_dtype == SI_F32;
+  ctx->setup.plan = plan;
+  ctx->setup.fuse_tail = node_d == 0 && head_fused(plan, layers, L);   // (a NeuralODE's layers are evaluated inside the integration kernel alone)
+  ctx->fuse_slots = ctx->setup.fuse_tail ? dense_fused_slots(layers[L - 2].out) : 0;
+  ctx->setup.f32 = compute_dtype == SI_F32;
   // (the fp32 weight vector is 256-byte aligned and its slots are pad_ld(N) apart: a layer's W is 16-byte aligned iff w_off % 4 == 0)
-  ctx->fuse_slots32 = (ctx->f32 && ctx->fuse_tail) ? dense_f32_fused_slots(layers[L - 2].out, layers[L - 2].in, layers[L - 2].w_off % 4 == 0) : 0;
+  ctx->setup.fuse_slots32 = (ctx->setup.f32 && ctx->setup.fuse_tail) ? dense_f32_fused_slots(layers[L - 2].out, layers[L - 2].in, layers[L - 2].w_off % 4 == 0) : 0;
   int64_t maxstored = 1;
-  for (int l = 0; l < (ctx->fuse_tail ? L - 2 : L); ++l) maxstored = std::max<int64_t>(maxstored, plan.L[(size_t)l].out_elems);
+  for (int l = 0; l < (ctx->setup.fuse_tail ? L - 2 : L); ++l) maxstored = std::max<int64_t>(maxstored, plan.L[(size_t)l].out_elems);
   ctx->max_stored = maxstored;
   ctx->act_elems = pad_ld(maxstored * B);
   ctx->sse_blocks = sse_num_blocks((int64_t)out_dim * B, ctx->num_cu);
-  ctx->fused_ok = node_d == 0 && fused_chain_class(ctx);   // (the chain kernels evaluate a Chain: never for a NeuralODE's right-hand side)
-  if (ctx->fused_ok) {   // the chain's tile program (64 bytes per 16-feature tile), uploaded once
+  ctx->setup.fused_ok = node_d == 0 && fused_chain_class(ctx);   // (the chain kernels evaluate a Chain: never for a NeuralODE's right-hand side)
+  if (ctx->setup.fused_ok) {   // the chain's tile program (64 bytes per 16-feature tile), uploaded once
     std::vector<CgTileD> prog;
-    chain_fused_program(ctx->layers.data(), L, ctx->fuse_tail, prog, ctx->cg_start, ctx->cg_count, ctx->cg_chunks);
-    if (!ctx->d_cgprog.alloc(prog.size())) {
+    chain_fused_program(ctx->layers.data(), L, ctx->setup.fuse_tail, prog, ctx->cg_start, ctx->cg_count, ctx->cg_chunks);
+    if (!ctx->loop.cgprog.alloc(prog.size())) {
       free_infer(ctx);
       return fail(ctx, SI_ERR_NOMEM, who + ": device allocation failed");
     }
-    SI_HIP(ctx, hipMemcpy(ctx->d_cgprog, prog.data(), prog.size() * sizeof(CgTileD), hipMemcpyHostToDevice));
+    SI_HIP(ctx, hipMemcpy(ctx->loop.cgprog, prog.data(), prog.size() * sizeof(CgTileD), hipMemcpyHostToDevice));
   }
-  if (!ctx->d_X.alloc((size_t)in_dim * B) || !ctx->d_Y.alloc((size_t)out_dim * B) ||
-      (ctx->f32 && !ctx->d_X32.alloc((size_t)pad_ld(std::max<int64_t>((int64_t)in_dim * B, plan.input_spatial ? plan.in_elems * B : 0)))) ||
-      (ctx->f32 && plan.has_conv && !ctx->d_wpack32.alloc(plan.wpack_elems)) ||
+  if (!ctx->setup.X.alloc((size_t)in_dim * B) || !ctx->setup.Y.alloc((size_t)out_dim * B) ||
+      (ctx->setup.f32 && !ctx->setup.X32.alloc((size_t)pad_ld(std::max<int64_t>((int64_t)in_dim * B, plan.input_spatial ? plan.in_elems * B : 0)))) ||
+      (ctx->setup.f32 && plan.has_conv && !ctx->fw.wpack32.alloc(plan.wpack_elems)) ||
       !alloc_forward(ctx, 1) ||
-      (plan.has_conv && !ctx->d_wpack.alloc(plan.wpack_elems)) ||
-      (plan.input_spatial && !ctx->d_Xc.alloc((size_t)plan.in_elems * B))) {
+      (plan.has_conv && !ctx->fw.wpack.alloc(plan.wpack_elems)) ||
+      (plan.input_spatial && !ctx->setup.Xc.alloc((size_t)plan.in_elems * B))) {
     free_infer(ctx);
     return fail(ctx, SI_ERR_NOMEM, who + ": device allocation failed");
   }
   {
     const hipMemcpyKind kind = src == SRC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    SI_HIP(ctx, hipMemcpyAsync(ctx->d_X, X, (size_t)in_dim * B * sizeof(double), kind, ctx->stream));
-    SI_HIP(ctx, hipMemcpyAsync(ctx->d_Y, Y, (size_t)out_dim * B * sizeof(double), kind, ctx->stream));
+    SI_HIP(ctx, hipMemcpyAsync(ctx->setup.X, X, (size_t)in_dim * B * sizeof(double), kind, ctx->stream));
+    SI_HIP(ctx, hipMemcpyAsync(ctx->setup.Y, Y, (size_t)out_dim * B * sizeof(double), kind, ctx->stream));
   }
-  if (plan.input_spatial) net_input(ctx, plan, ctx->d_X, ctx->d_Xc, B);  // (W, H, C, N) -> channel-fastest, once
-  if (ctx->f32 && plan.input_spatial)   // X rounded to fp32 once, in the layout the conv kernels read (pad channels: zero)
-    launch_narrow_f32(ctx->stream, ctx->d_Xc, ctx->d_X32, plan.in_elems * B);
-  else if (ctx->f32)
-    launch_narrow_f32(ctx->stream, ctx->d_X, ctx->d_X32, (int64_t)in_dim * B);   // X rounded to fp32 once
+  if (plan.input_spatial) net_input(ctx, plan, ctx->setup.X, ctx->setup.Xc, B);  // (W, H, C, N) -> channel-fastest, once
+  if (ctx->setup.f32 && plan.input_spatial)   // X rounded to fp32 once, in the layout the conv kernels read (pad channels: zero)
+    launch_narrow_f32(ctx->stream, ctx->setup.Xc, ctx->setup.X32, plan.in_elems * B);
+  else if (ctx->setup.f32)
+    launch_narrow_f32(ctx->stream, ctx->setup.X, ctx->setup.X32, (int64_t)in_dim * B);   // X rounded to fp32 once
   SI_HIP(ctx, hipGetLastError());
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->i_ready = true;
+  ctx->setup.ready = true;
   return SI_OK;
 }
 
@@ -257,10 +256,10 @@ int32_t si_construct_result_ptr(si_ctx* ctx, double** W_swa_dev_out, double** P_
 // workspace for that is capped so that a model whose single chain already fills the chip (cfg2: 1.5 GB of activations
 // per chain) keeps one slot.
 static int batch_width(const si_ctx* ctx, int C) {
-  if (ctx->plan.has_conv) return 1;  // chains with Conv layers fill the chip one chain at a time
-  const double pslots = (double)std::max(ctx->fuse_slots, ctx->fuse_slots32);
-  const double per = (ctx->f32 ? 4.0 : 8.0) * 2.0 * (double)ctx->act_elems +
-                     8.0 * ((pslots + 1.0) * (double)ctx->out_dim * (double)ctx->B + (ctx->f32 ? 1.5 : 1.0) * (double)pad_ld(ctx->iN) +
+  if (ctx->setup.plan.has_conv) return 1;  // chains with Conv layers fill the chip one chain at a time
+  const double pslots = (double)std::max(ctx->fuse_slots, ctx->setup.fuse_slots32);
+  const double per = (ctx->setup.f32 ? 4.0 : 8.0) * 2.0 * (double)ctx->act_elems +
+                     8.0 * ((pslots + 1.0) * (double)ctx->out_dim * (double)ctx->B + (ctx->setup.f32 ? 1.5 : 1.0) * (double)pad_ld(ctx->iN) +
                             (double)ctx->sse_blocks);
   const double fit = std::floor(SI_BATCH_BYTES / per);
   return (int)std::max(1.0, std::min({(double)C, fit, 1024.0}));
@@ -268,31 +267,31 @@ static int batch_width(const si_ctx* ctx, int C) {
 
 int32_t ensure_chains(si_ctx* ctx, int32_t C) {
   const int want = batch_width(ctx, C);
-  if (ctx->fw_slots < want) {
+  if (ctx->fw.slots < want) {
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (!alloc_forward(ctx, want)) {
       if (!alloc_forward(ctx, 1)) {
-        ctx->i_ready = false;
+        ctx->setup.ready = false;
         return fail(ctx, SI_ERR_NOMEM, "forward workspace allocation failed");
       }
     }
   }
-  if (ctx->chains_cap >= C) return SI_OK;
+  if (ctx->chains.cap >= C) return SI_OK;
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (DevBuf<double>* b : {&ctx->d_zcur, &ctx->d_zprop, &ctx->d_lpcur, &ctx->d_sse, &ctx->d_wsq}) b->reset();
-  ctx->d_nacc.reset();
-  ctx->d_steps.reset();
-  ctx->chains_cap = 0;
-  if (!ctx->d_wsq.alloc((size_t)C) || !ctx->d_zcur.alloc((size_t)ctx->iM * C) || !ctx->d_zprop.alloc((size_t)ctx->iM * C) ||
-      !ctx->d_lpcur.alloc((size_t)C) || !ctx->d_sse.alloc((size_t)C) || !ctx->d_nacc.alloc((size_t)C) || !ctx->d_steps.alloc((size_t)C))
+  for (DevBuf<double>* b : {&ctx->chains.zcur, &ctx->chains.zprop, &ctx->chains.lpcur, &ctx->chains.sse, &ctx->chains.wsq}) b->reset();
+  ctx->chains.nacc.reset();
+  ctx->chains.steps.reset();
+  ctx->chains.cap = 0;
+  if (!ctx->chains.wsq.alloc((size_t)C) || !ctx->chains.zcur.alloc((size_t)ctx->iM * C) || !ctx->chains.zprop.alloc((size_t)ctx->iM * C) ||
+      !ctx->chains.lpcur.alloc((size_t)C) || !ctx->chains.sse.alloc((size_t)C) || !ctx->chains.nacc.alloc((size_t)C) || !ctx->chains.steps.alloc((size_t)C))
     return fail(ctx, SI_ERR_NOMEM, "sampler state allocation failed");
-  ctx->chains_cap = C;
+  ctx->chains.cap = C;
   return SI_OK;
 }
 
 DensityView setup_view(const si_ctx* ctx, bool defer_sse_final) {
-  return {ctx->d_X, ctx->d_Xc, ctx->d_X32, ctx->d_Y, ctx->B, ctx->d_act, ctx->d_act32, ctx->d_ssepart, ctx->sse_blocks,
-          ctx->d_part, ctx->d_yhat, ctx->act_elems, ctx->f32, defer_sse_final, true};
+  return {ctx->setup.X, ctx->setup.Xc, ctx->setup.X32, ctx->setup.Y, ctx->B, ctx->fw.act, ctx->fw.act32, ctx->fw.ssepart, ctx->sse_blocks,
+          ctx->fw.part, ctx->fw.yhat, ctx->act_elems, ctx->setup.f32, defer_sse_final, true};
 }
 
 // ---- the seam between z and the weights: W_swa + P z (K4, P' g) or, while a decoder is set, W_swa + decoder(z) ------------------
@@ -314,14 +313,14 @@ static int32_t decoder_forward(si_ctx* ctx, const double* z_dev, int32_t n, doub
   if (rc != SI_OK) return rc;
   launch_decoder_head_fwd(ctx->stream, d.head, d.params, d.dtype, z_dev, ctx->iM, d.hid, d.SH, n);
   const double* a = d.D > 1 ? d.hid + d.head.hid_off[d.D - 2] : z_dev;   // the last layer's input: a_{D-1}, or z itself
-  launch_decoder_last_fwd(ctx->stream, ctx->i_swa, d.lastW, pad_ld(ctx->iN), d.lastb, d.dtype, ctx->iN, d.H, d.last_act, a,
+  launch_decoder_last_fwd(ctx->stream, ctx->setup.swa, d.lastW, pad_ld(ctx->iN), d.lastb, d.dtype, ctx->iN, d.H, d.last_act, a,
                           d.D > 1 ? d.SH : ctx->iM, n, w, ldw, y, ldy, ctx->num_cu);
   return SI_OK;
 }
 
 int32_t form_weights(si_ctx* ctx, const double* z_dev, int32_t n, double* w, int64_t ldw, float* w32, bool keep_y) {
   if (!ctx->dec.on) {
-    launch_reconstruct(ctx->stream, ctx->i_swa, ctx->i_P, ctx->ldP, ctx->iN, ctx->iM, z_dev, n, w, ldw, ctx->num_cu, w32, ldw);
+    launch_reconstruct(ctx->stream, ctx->setup.swa, ctx->setup.P, ctx->ldP, ctx->iN, ctx->iM, z_dev, n, w, ldw, ctx->num_cu, w32, ldw);
     return SI_OK;
   }
   // (w32 is never asked for here: si_infer_set_decoder refuses a set-up with compute_dtype = SI_F32)
@@ -337,23 +336,23 @@ int32_t form_weights(si_ctx* ctx, const double* z_dev, int32_t n, double* w, int
 void pull_back_to_z(si_ctx* ctx, const double* gw, double* gz) {
   DecoderState& d = ctx->dec;
   if (!d.on) {
-    launch_ptg(ctx->stream, ctx->i_P, ctx->ldP, ctx->iN, ctx->iM, gw, ctx->d_ptgpart, gz);
+    launch_ptg(ctx->stream, ctx->setup.P, ctx->ldP, ctx->iN, ctx->iM, gw, ctx->grad.ptgpart, gz);
     return;
   }
   launch_decoder_last_rev(ctx->stream, d.lastW, pad_ld(ctx->iN), d.dtype, ctx->iN, d.H, d.last_act, gw, d.y, d.part, d.ga);
   launch_decoder_head_rev(ctx->stream, d.head, d.params, d.dtype, d.ga, d.H, d.hid, d.SH, gz, ctx->iM, 1);
 }
 
-// ---- the three routes of a density evaluation: K4 has left the weights of chain slots [c0, c0 + nc) in d_w (and d_w32) ------------
+// ---- the three routes of a density evaluation: K4 has left the weights of chain slots [c0, c0 + nc) in fw.w (and fw.w32) ------------
 // Conv / MaxPool / flatten / Dense layers one after the other (capi_net.hip), ping-pong activations, one chain per pass.
 // T = float is compute_dtype = SI_F32 on a Conv chain: the same pass on fp32 operands, the squared errors in fp64 with the
 // fp64 outputs written beside them on request.  (the template has C++ linkage inside this extern "C" block)
 static void net_sse(si_ctx* ctx, const DensityView& v, const double* last, int64_t d, int c0, const double** yhat_out) {
-  launch_sse(ctx->stream, last, v.Y, d, v.ssepart, v.sse_blocks, ctx->d_sse + c0, 1, v.act_elems, !v.defer_sse_final);
+  launch_sse(ctx->stream, last, v.Y, d, v.ssepart, v.sse_blocks, ctx->chains.sse + c0, 1, v.act_elems, !v.defer_sse_final);
   if (yhat_out) *yhat_out = last;
 }
 static void net_sse(si_ctx* ctx, const DensityView& v, const float* last, int64_t d, int c0, const double** yhat_out) {
-  launch_sse_f32(ctx->stream, last, v.Y, d, v.ssepart, v.sse_blocks, ctx->d_sse + c0, 1, v.act_elems, yhat_out ? v.yhat : nullptr, d,
+  launch_sse_f32(ctx->stream, last, v.Y, d, v.ssepart, v.sse_blocks, ctx->chains.sse + c0, 1, v.act_elems, yhat_out ? v.yhat : nullptr, d,
                  !v.defer_sse_final);
   if (yhat_out) *yhat_out = v.yhat;
 }
@@ -361,7 +360,7 @@ extern "C++" template <typename T>
 static int32_t density_net(si_ctx* ctx, const DensityView& v, const T* w, const T* x, const DevBuf<T>* act, T* wpack, int c0,
                            const double** yhat_out) {
   T* last = nullptr;
-  const int32_t rc = net_forward<T>(ctx, ctx->plan, w, x, v.B, act, wpack, /*pingpong=*/true, &last);
+  const int32_t rc = net_forward<T>(ctx, ctx->setup.plan, w, x, v.B, act, wpack, /*pingpong=*/true, &last);
   if (rc != SI_OK) return rc;
   const int64_t d = (int64_t)ctx->out_dim * v.B;
   {
@@ -391,12 +390,12 @@ static int32_t density_fused(si_ctx* ctx, const DensityView& v, int c0, int nc) 
     ProfScope ps(ctx, SI_K_DENSE, fl, by);
     ProfScope pm(ctx, SI_K_DENSE_MAIN, fl, by);
     const SpecKernels* sk = nullptr;
-    if (ctx->chain_spec && ctx->fuse_tail)   // the same kernel compiled for this chain's shapes (chain_spec_rtc.cpp; same bits)
+    if (ctx->chain_spec && ctx->setup.fuse_tail)   // the same kernel compiled for this chain's shapes (chain_spec_rtc.cpp; same bits)
       sk = spec_kernels(ctx->layers.data(), (int)ctx->layers.size(), nb, dense_fused_slot_feats(ctx->layers[ctx->layers.size() - 2].out), 0, false,
                         &ctx->spec_message);
-    ctx->last_density_spec = sk != nullptr;
+    ctx->loop.last_density_spec = sk != nullptr;
     if (sk) {
-      const double* wp = ctx->d_w;
+      const double* wp = ctx->fw.w;
       const double* xp = v.X;
       double* yp = v.yhat;
       long long ws = ldw, ys = d;
@@ -413,24 +412,24 @@ static int32_t density_fused(si_ctx* ctx, const DensityView& v, int c0, int nc) 
                                           (unsigned)((size_t)sk->lds_doubles * sizeof(double)), ctx->stream, args, nullptr));
       }
     } else {
-      launch_chain_fused(ctx->stream, fp, nb, wave_tiles, lds, ctx->d_w, ldw, v.X, v.yhat, d, nc);
+      launch_chain_fused(ctx->stream, fp, nb, wave_tiles, lds, ctx->fw.w, ldw, v.X, v.yhat, d, nc);
     }
   }
   {
     ProfScope ps(ctx, SI_K_SSE, 3.0 * (double)d * dn, 16.0 * (double)d * dn);
-    launch_sse(ctx->stream, v.yhat, v.Y, d, v.ssepart, v.sse_blocks, ctx->d_sse + c0, nc, d, !v.defer_sse_final);
+    launch_sse(ctx->stream, v.yhat, v.Y, d, v.ssepart, v.sse_blocks, ctx->chains.sse + c0, nc, d, !v.defer_sse_final);
   }
   SI_HIP(ctx, hipGetLastError());
   return SI_OK;
 }
 
 // The per-layer launches (dense_forward), nc chain slots per launch, outputs ping-pong.  compute_dtype = SI_F32 runs them on the
-// fp32 matrix instruction (kernels_gemm_f32.hip): K4 has left W_swa + P z in d_w (fp64) AND rounded once in d_w32; X32 /
+// fp32 matrix instruction (kernels_gemm_f32.hip): K4 has left W_swa + P z in fw.w (fp64) AND rounded once in fw.w32; X32 /
 // activations are fp32; the narrow head's partial sums, the last bias + activation (tail_sse_kernel) and the sum of squared
 // errors are fp64 -- the precision option of SURVEY section 0 Q6 on the same reference lines, src/space_inference.jl:92-94
 static int32_t density_layers(si_ctx* ctx, const DensityView& v, int c0, int nc, const double** yhat_out) {
   const int64_t B = v.B, ldw = pad_ld(ctx->iN);
-  const int slots = v.f32 ? ctx->fuse_slots32 : ctx->fuse_slots;
+  const int slots = v.f32 ? ctx->setup.fuse_slots32 : ctx->fuse_slots;
   ChainBatch cb;
   cb.n = nc;
   cb.w = ldw;
@@ -439,51 +438,51 @@ static int32_t density_layers(si_ctx* ctx, const DensityView& v, int c0, int nc,
   const double* yh = v.yhat;
   double* yhat = yhat_out ? v.yhat : nullptr;
   if (v.f32) {
-    const DenseForward<float> fw{ctx->layers.data(), ctx->layers.size(), ctx->fuse_tail, ctx->d_w32, ctx->d_w, v.X32, v.Y, B, nullptr,
+    const DenseForward<float> fw{ctx->layers.data(), ctx->layers.size(), ctx->setup.fuse_tail, ctx->fw.w32, ctx->fw.w, v.X32, v.Y, B, nullptr,
                                  {v.act32[0], v.act32[1]}, cb, slots, v.part, yhat, v.ssepart, v.sse_blocks,
-                                 ctx->d_sse + c0, v.defer_sse_final, ctx->main_layer, true};
+                                 ctx->chains.sse + c0, v.defer_sse_final, ctx->main_layer, true};
     dense_forward(ctx, ctx->stream, fw);
   } else {
-    const DenseForward<double> fw{ctx->layers.data(), ctx->layers.size(), ctx->fuse_tail, ctx->d_w, ctx->d_w, v.X, v.Y, B, nullptr,
+    const DenseForward<double> fw{ctx->layers.data(), ctx->layers.size(), ctx->setup.fuse_tail, ctx->fw.w, ctx->fw.w, v.X, v.Y, B, nullptr,
                                   {v.act[0], v.act[1]}, cb, slots, v.part, yhat, v.ssepart, v.sse_blocks,
-                                  ctx->d_sse + c0, v.defer_sse_final, ctx->main_layer, true};
+                                  ctx->chains.sse + c0, v.defer_sse_final, ctx->main_layer, true};
     const double* h = dense_forward(ctx, ctx->stream, fw);
-    if (!ctx->fuse_tail) yh = h;   // without the fused tail the outputs stay in the last activation buffer
+    if (!ctx->setup.fuse_tail) yh = h;   // without the fused tail the outputs stay in the last activation buffer
   }
   SI_HIP(ctx, hipGetLastError());
   if (yhat_out) *yhat_out = yh;
   return SI_OK;
 }
 
-// density evaluations for chain slots [c0, c0 + nc), nc <= fw_slots, in ONE pass of launches:
-// d_zprop[:, c] -> d_sse[c]; optionally leaves the model outputs at *yhat_out (slot j at + j * out_dim*B after the fused
+// density evaluations for chain slots [c0, c0 + nc), nc <= fw.slots, in ONE pass of launches:
+// chains.zprop[:, c] -> chains.sse[c]; optionally leaves the model outputs at *yhat_out (slot j at + j * out_dim*B after the fused
 // tail, at + j * act_elems otherwise)
 int32_t eval_density(si_ctx* ctx, const DensityView& v, int c0, int nc, const double** yhat_out) {
-  ctx->last_density_spec = 0;   // (si_chain_kernel_info reports the last evaluation)
+  ctx->loop.last_density_spec = 0;   // (si_chain_kernel_info reports the last evaluation)
   if (ctx->node.on) return node_density(ctx, v, c0, nc, yhat_out);   // form_weights, ||W||^2, the integrations (capi_node.hip)
   const int64_t N = ctx->iN, ldw = pad_ld(N);
   const int32_t M = ctx->iM;
   const double dn = (double)nc;
   {
     ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * dn, (double)N * (M + 1 + dn) * 8.0);
-    const int32_t rc = form_weights(ctx, ctx->d_zprop + (size_t)c0 * M, nc, ctx->d_w, ldw, v.f32 ? ctx->d_w32.get() : nullptr);
+    const int32_t rc = form_weights(ctx, ctx->chains.zprop + (size_t)c0 * M, nc, ctx->fw.w, ldw, v.f32 ? ctx->fw.w32.get() : nullptr);
     if (rc != SI_OK) return rc;
   }
-  if (ctx->sigma_p > 0.0)  // ||new_W||^2 per chain for the optional prior term (same fixed-order reduction as the SSE)
-    launch_sse(ctx->stream, ctx->d_w, nullptr, N, ctx->d_wsqpart, ctx->wsq_blocks, ctx->d_wsq + c0, nc, ldw);
-  if (ctx->plan.has_conv)
-    return v.f32 ? density_net<float>(ctx, v, ctx->d_w32, v.X32, v.act32, ctx->d_wpack32, c0, yhat_out)
-                 : density_net<double>(ctx, v, ctx->d_w, ctx->plan.input_spatial ? v.Xc : v.X, v.act, ctx->d_wpack, c0, yhat_out);
-  if (ctx->fused_ok && ctx->chain_mode != 0 && !yhat_out) {   // (never with compute_dtype = SI_F32: fused_chain_class)
+  if (ctx->setup.sigma_p > 0.0)  // ||new_W||^2 per chain for the optional prior term (same fixed-order reduction as the SSE)
+    launch_sse(ctx->stream, ctx->fw.w, nullptr, N, ctx->fw.wsqpart, ctx->wsq_blocks, ctx->chains.wsq + c0, nc, ldw);
+  if (ctx->setup.plan.has_conv)
+    return v.f32 ? density_net<float>(ctx, v, ctx->fw.w32, v.X32, v.act32, ctx->fw.wpack32, c0, yhat_out)
+                 : density_net<double>(ctx, v, ctx->fw.w, ctx->setup.plan.input_spatial ? v.Xc : v.X, v.act, ctx->fw.wpack, c0, yhat_out);
+  if (ctx->setup.fused_ok && ctx->chain_mode != 0 && !yhat_out) {   // (never with compute_dtype = SI_F32: fused_chain_class)
     const int32_t rc = density_fused(ctx, v, c0, nc);
     if (rc != SI_NOT_TAKEN) return rc;
   }
   return density_layers(ctx, v, c0, nc, yhat_out);
 }
 
-// all C chain slots, fw_slots at a time
+// all C chain slots, fw.slots at a time
 int32_t eval_density_all(si_ctx* ctx, const DensityView& v, int C) {
-  const int w = std::max(1, ctx->fw_slots);
+  const int w = std::max(1, ctx->fw.slots);
   for (int c0 = 0; c0 < C; c0 += w) {
     const int32_t rc = eval_density(ctx, v, c0, std::min(w, C - c0), nullptr);
     if (rc != SI_OK) return rc;
@@ -497,29 +496,29 @@ double mvnormal_c0(double d, double sigma) {
 }
 
 // log N(w; 0, sigma_p^2 I) = c0p - ||w||^2 / (2 sigma_p^2): the term the reference writes AFTER its `return` (Q4)
-double prior_c0(const si_ctx* ctx) { return ctx->sigma_p > 0.0 && !ctx->node.on ? mvnormal_c0((double)ctx->iN, ctx->sigma_p) : 0.0; }
+double prior_c0(const si_ctx* ctx) { return ctx->setup.sigma_p > 0.0 && !ctx->node.on ? mvnormal_c0((double)ctx->iN, ctx->setup.sigma_p) : 0.0; }
 // The constants of lp = c0 - (sse / s2) / 2 [+ prior_c0 - (wsq / sp2) / 2].  A NeuralODE set-up (reference
 // src/space_inference.jl:96-101: lp = -sse - ||W||^2, sigma_m and sigma_p unused) is c0 = 0, s2 = 1/2, the prior term on (the set-up
 // holds sigma_p at 1), prior_c0 = 0, sp2 = 1/2: every division is exact, so the RWMH kernels carry it with these constants alone.
 double lik_c0(const si_ctx* ctx, double d) { return ctx->node.on ? 0.0 : mvnormal_c0(d, ctx->sigma_m); }
 double lik_s2(const si_ctx* ctx) { return ctx->node.on ? 0.5 : ctx->sigma_m * ctx->sigma_m; }
-double prior_sp2(const si_ctx* ctx) { return ctx->node.on ? 0.5 : ctx->sigma_p * ctx->sigma_p; }
+double prior_sp2(const si_ctx* ctx) { return ctx->node.on ? 0.5 : ctx->setup.sigma_p * ctx->setup.sigma_p; }
 
 // the value of the log-density from the device's sums, as the host forms it: lp = c0 - (sse / s2) / 2 [+ prior_c0 - (wsq / sp2) / 2]
 static double lp_from_sums(const si_ctx* ctx, double sse, double wsq) {
   const double c0 = lik_c0(ctx, (double)ctx->out_dim * (double)ctx->B), s2 = lik_s2(ctx);
   double lp = c0 - (sse / s2) / 2.0;
-  if (ctx->sigma_p > 0.0) lp += prior_c0(ctx) - (wsq / prior_sp2(ctx)) / 2.0;
+  if (ctx->setup.sigma_p > 0.0) lp += prior_c0(ctx) - (wsq / prior_sp2(ctx)) / 2.0;
   return lp;
 }
 
 int32_t si_infer_set_prior(si_ctx* ctx, double sigma_p) {
   CHECK_CTX(ctx);
-  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_infer_set_prior: call si_infer_setup first");
+  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, "si_infer_set_prior: call si_infer_setup first");
   if (ctx->node.on) return fail(ctx, SI_ERR_INVALID, "si_infer_set_prior: not available for NeuralODE models (their density carries -||W||^2 itself)");
-  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_infer_set_prior: a step-wise RWMH session is open");
+  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_infer_set_prior: a step-wise RWMH session is open");
   if (!(sigma_p >= 0.0)) return fail(ctx, SI_ERR_INVALID, "si_infer_set_prior: sigma_p must be >= 0 (0 = off, the reference's behaviour)");
-  ctx->sigma_p = sigma_p;
+  ctx->setup.sigma_p = sigma_p;
   return SI_OK;
 }
 
@@ -539,8 +538,8 @@ static bool decoder_upload(si_ctx* ctx, DecoderState& d, const si_layer& last, c
 
 int32_t si_infer_set_decoder(si_ctx* ctx, const si_layer* dec_layers, int32_t D, int64_t Nd, const void* wdec_host, int32_t wdec_dtype) {
   CHECK_CTX(ctx);
-  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_infer_set_decoder: call si_infer_setup first");
-  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_infer_set_decoder: a step-wise RWMH session is open");
+  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, "si_infer_set_decoder: call si_infer_setup first");
+  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_infer_set_decoder: a step-wise RWMH session is open");
   BIND(ctx);
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (!dec_layers && D == 0) {   // clear: the P route returns
@@ -550,7 +549,7 @@ int32_t si_infer_set_decoder(si_ctx* ctx, const si_layer* dec_layers, int32_t D,
   auto bad = [&](const char* what) { return fail(ctx, SI_ERR_INVALID, std::string("si_infer_set_decoder: ") + what); };
   if (!dec_layers || D < 1 || D > SI_DEC_MAX_LAYERS || Nd <= 0 || !wdec_host) return bad("bad argument (1 <= D <= 8 layers, Nd > 0, parameters given)");
   if (wdec_dtype != SI_F32 && wdec_dtype != SI_F64) return bad("wdec_dtype must be SI_F32 or SI_F64");
-  if (ctx->f32) return bad("the set-up's compute_dtype is SI_F32: the fp32 weight vector is not fed on the decoder route (set up with SI_F64)");
+  if (ctx->setup.f32) return bad("the set-up's compute_dtype is SI_F32: the fp32 weight vector is not fed on the decoder route (set up with SI_F64)");
   const int64_t N = ctx->iN;
   if (ctx->iM > 1024) return bad("M exceeds 1024");
   for (int32_t l = 0; l < D; ++l) {
@@ -594,7 +593,7 @@ int32_t si_infer_decoder_info(si_ctx* ctx, int32_t* D_out, int32_t* H_out, int32
 
 int32_t si_decode(si_ctx* ctx, const double* Z, int64_t C, double* Y_out) {
   CHECK_CTX(ctx);
-  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_decode: call si_infer_setup first");
+  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, "si_decode: call si_infer_setup first");
   if (!ctx->dec.on) return fail(ctx, SI_ERR_STATE, "si_decode: no decoder is set (si_infer_set_decoder)");
   if (!Z || C <= 0 || !Y_out) return fail(ctx, SI_ERR_INVALID, "si_decode: bad argument");
   BIND(ctx);
@@ -618,43 +617,43 @@ int32_t si_decode(si_ctx* ctx, const double* Z, int64_t C, double* Y_out) {
 }
 
 // gz = J_decoder(z)' gy at one point, through the seam alone: form_weights(.., keep_y = true) and pull_back_to_z are, launch for
-// launch, what si_logdensity_grad runs around its model sweep; d_zprop, d_w, d_gw and d_gz are the buffers it uses.
+// launch, what si_logdensity_grad runs around its model sweep; chains.zprop, fw.w, grad.gw and grad.gz are the buffers it uses.
 int32_t si_decode_vjp(si_ctx* ctx, const double* z, const double* gy, double* gz_out) {
   CHECK_CTX(ctx);
   if (!z || !gy || !gz_out) return fail(ctx, SI_ERR_INVALID, "si_decode_vjp: bad argument");
-  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_decode_vjp: call si_infer_setup first");
+  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, "si_decode_vjp: call si_infer_setup first");
   if (!ctx->dec.on) return fail(ctx, SI_ERR_STATE, "si_decode_vjp: no decoder is set (si_infer_set_decoder)");
-  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_decode_vjp: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
+  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_decode_vjp: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
   BIND(ctx);
   int32_t rc = ensure_chains(ctx, 1);
   if (rc != SI_OK) return rc;
   const int64_t N = ctx->iN;
   const int32_t M = ctx->iM;
-  if (!ctx->d_gw.reserve((size_t)pad_ld(N)) || !ctx->d_gz.reserve((size_t)M)) return fail(ctx, SI_ERR_NOMEM, "si_decode_vjp: device allocation failed");
-  SI_HIP(ctx, hipMemcpyAsync(ctx->d_zprop, z, (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  SI_HIP(ctx, hipMemcpyAsync(ctx->d_gw, gy, (size_t)N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = form_weights(ctx, ctx->d_zprop, 1, ctx->d_w, pad_ld(N), nullptr, /*keep_y=*/true)) != SI_OK) return rc;
-  pull_back_to_z(ctx, ctx->d_gw, ctx->d_gz);
+  if (!ctx->grad.gw.reserve((size_t)pad_ld(N)) || !ctx->grad.gz.reserve((size_t)M)) return fail(ctx, SI_ERR_NOMEM, "si_decode_vjp: device allocation failed");
+  SI_HIP(ctx, hipMemcpyAsync(ctx->chains.zprop, z, (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(ctx->grad.gw, gy, (size_t)N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = form_weights(ctx, ctx->chains.zprop, 1, ctx->fw.w, pad_ld(N), nullptr, /*keep_y=*/true)) != SI_OK) return rc;
+  pull_back_to_z(ctx, ctx->grad.gw, ctx->grad.gz);
   SI_HIP(ctx, hipGetLastError());
-  SI_HIP(ctx, hipMemcpyAsync(gz_out, ctx->d_gz, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(gz_out, ctx->grad.gz, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SI_OK;
 }
 
 int32_t si_logdensity(si_ctx* ctx, const double* Z, int32_t C, double* lp_out) {
   CHECK_CTX(ctx);
-  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_logdensity: call si_infer_setup first");
+  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, "si_logdensity: call si_infer_setup first");
   if (!Z || C <= 0 || !lp_out) return fail(ctx, SI_ERR_INVALID, "si_logdensity: bad argument");
-  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_logdensity: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
+  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_logdensity: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
   BIND(ctx);
   int32_t rc = ensure_chains(ctx, C);
   if (rc != SI_OK) return rc;
-  SI_HIP(ctx, hipMemcpyAsync(ctx->d_zprop, Z, (size_t)ctx->iM * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(ctx->chains.zprop, Z, (size_t)ctx->iM * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   if ((rc = eval_density_all(ctx, setup_view(ctx), C)) != SI_OK) return rc;
   std::vector<double> sse((size_t)C), wsq((size_t)C, 0.0);
-  SI_HIP(ctx, hipMemcpyAsync(sse.data(), ctx->d_sse, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (ctx->sigma_p > 0.0)
-    SI_HIP(ctx, hipMemcpyAsync(wsq.data(), ctx->d_wsq, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(sse.data(), ctx->chains.sse, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (ctx->setup.sigma_p > 0.0)
+    SI_HIP(ctx, hipMemcpyAsync(wsq.data(), ctx->chains.wsq, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (int c = 0; c < C; ++c) lp_out[c] = lp_from_sums(ctx, sse[(size_t)c], wsq[(size_t)c]);
   return SI_OK;
@@ -662,66 +661,19 @@ int32_t si_logdensity(si_ctx* ctx, const double* Z, int32_t C, double* lp_out) {
 
 // a gradient workspace that could not be allocated in full is dropped whole
 static int32_t drop_grad(si_ctx* ctx) {
-  ctx->d_hs.clear();
-  ctx->d_pidx.clear();
-  ctx->g_scratch = NetScratch();
-  ctx->g_ws32 = SweepF32Ws();
-  for (DevBuf<double>* b : {&ctx->d_delta[0], &ctx->d_delta[1], &ctx->d_gw, &ctx->d_bwpart, &ctx->d_rspart, &ctx->d_ptgpart, &ctx->d_gz}) b->reset();
+  ctx->grad = InferGrad();
   return fail(ctx, SI_ERR_NOMEM, "si_logdensity_grad: workspace allocation failed");
 }
 
 static int32_t ensure_grad(si_ctx* ctx) {
-  if (ctx->g_ready) return SI_OK;
-  const int64_t B = ctx->B;
-  if (ctx->plan.has_conv && ctx->f32)
+  InferGrad& g = ctx->grad;
+  if (g.ws.ready) return SI_OK;
+  if (ctx->setup.plan.has_conv && ctx->setup.f32)
     return fail(ctx, SI_ERR_INVALID, "si_logdensity_grad: compute_dtype = SI_F32 has a reverse sweep for Dense chains only; set a Conv chain up with SI_F64 for gradients");
-  if (ctx->plan.has_conv) {
-    const NetPlan& p = ctx->plan;
-    size_t nb, nr, nw, nd;
-    net_scratch_sizes(p, B, ctx->num_cu, &nb, &nr, &nw, &nd);
-    ctx->d_hs = std::vector<DevBuf<double>>(p.L.size());
-    ctx->d_pidx = std::vector<DevBuf<uint8_t>>(p.L.size());
-    bool ok = true;
-    for (size_t l = 0; l < p.L.size() && ok; ++l) {
-      if (net_grad_fused(p, l))   // Conv + MaxPool as one kernel: a byte index instead of the un-pooled activation
-        ok = ctx->d_pidx[l].alloc(net_pidx_bytes(p, l, B));
-      else
-        ok = ctx->d_hs[l].alloc((size_t)p.L[l].out_elems * B);
-    }
-    ctx->g_scratch.pidx = ctx->d_pidx.data();
-    ok = ok && ctx->d_delta[0].alloc((size_t)p.max_elems * B) && ctx->d_delta[1].alloc((size_t)p.max_elems * B) &&
-         ctx->d_gw.alloc((size_t)pad_ld(ctx->iN)) && ctx->g_scratch.bwpart.alloc(nb) && ctx->g_scratch.rspart.alloc(nr) &&
-         ctx->g_scratch.wt.alloc(nw) && ctx->g_scratch.dbtmp.alloc(nd) && ctx->d_ptgpart.alloc((size_t)ptg_blocks() * ctx->iM) &&
-         ctx->d_gz.alloc((size_t)ctx->iM);
-    if (!ok) return drop_grad(ctx);
-    ctx->g_ready = true;
-    return SI_OK;
-  }
-  if (ctx->f32) {   // compute_dtype = SI_F32: the fp32 forward + reverse sweep (kernels_bwd_f32.hip), P' g in fp64
-    const bool ok32 = sweep_f32_alloc(ctx, ctx->g_ws32, ctx->layers.data(), (int)ctx->layers.size(), ctx->fuse_tail, ctx->iN, ctx->in_dim,
-                                      ctx->out_dim, B) &&
-                      ctx->d_gw.alloc((size_t)pad_ld(ctx->iN)) && ctx->d_ptgpart.alloc((size_t)ptg_blocks() * ctx->iM) &&
-                      ctx->d_gz.alloc((size_t)ctx->iM);
-    if (!ok32) return drop_grad(ctx);
-    ctx->g_ready = true;
-    return SI_OK;
-  }
-  int64_t maxw = 1;
-  size_t maxpart = 1;
-  ctx->d_hs = std::vector<DevBuf<double>>(ctx->layers.size());
-  bool ok = true;
-  for (size_t l = 0; l < ctx->layers.size() && ok; ++l) {
-    const si_layer& ly = ctx->layers[l];
-    maxw = std::max<int64_t>(maxw, ly.out);
-    maxpart = std::max(maxpart, backward_weight_part_elems(ly.out, ly.in, B, ctx->num_cu));
-    ok = ctx->d_hs[l].alloc((size_t)ly.out * B);
-  }
-  if (ctx->fuse_tail) maxpart = std::max(maxpart, tail_bwd_part_elems(ctx->layers.back().out, ctx->layers.back().in));
-  ok = ok && ctx->d_delta[0].alloc((size_t)maxw * B) && ctx->d_delta[1].alloc((size_t)maxw * B) &&
-       ctx->d_gw.alloc((size_t)pad_ld(ctx->iN)) && ctx->d_bwpart.alloc(maxpart) && ctx->d_rspart.alloc((size_t)rowsum_chunks() * maxw) &&
-       ctx->d_ptgpart.alloc((size_t)ptg_blocks() * ctx->iM) && ctx->d_gz.alloc((size_t)ctx->iM);
-  if (!ok) return drop_grad(ctx);
-  ctx->g_ready = true;
+  if (!sweep_ws_alloc(ctx, g.ws, ctx->layers.data(), (int)ctx->layers.size(), ctx->setup.plan, ctx->setup.fuse_tail, ctx->iN, ctx->in_dim, ctx->out_dim,
+                      ctx->B, ctx->setup.f32) ||
+      !g.gw.alloc((size_t)pad_ld(ctx->iN)) || !g.ptgpart.alloc((size_t)ptg_blocks() * ctx->iM) || !g.gz.alloc((size_t)ctx->iM))
+    return drop_grad(ctx);
   return SI_OK;
 }
 
@@ -735,46 +687,32 @@ static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_ou
   if ((rc = ensure_grad(ctx)) != SI_OK) return rc;
   const int64_t N = ctx->iN, B = ctx->B;
   const int32_t M = ctx->iM;
-  const size_t nl = ctx->layers.size();
   const double s2 = ctx->sigma_m * ctx->sigma_m;
-  SI_HIP(ctx, hipMemcpyAsync(ctx->d_zprop, z, (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(ctx->chains.zprop, z, (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   {
     ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M, (double)N * (M + 2) * 8.0);
-    if ((rc = form_weights(ctx, ctx->d_zprop, 1, ctx->d_w, pad_ld(N), ctx->f32 ? ctx->d_w32.get() : nullptr, /*keep_y=*/true)) != SI_OK)
+    if ((rc = form_weights(ctx, ctx->chains.zprop, 1, ctx->fw.w, pad_ld(N), ctx->setup.f32 ? ctx->fw.w32.get() : nullptr, /*keep_y=*/true)) != SI_OK)
       return rc;
   }
-  const bool prior = ctx->sigma_p > 0.0;
-  if (prior) launch_sse(ctx->stream, ctx->d_w, nullptr, N, ctx->d_wsqpart, ctx->wsq_blocks, ctx->d_wsq, 1, pad_ld(N));
-  // every route leaves d (-SSE / (2 sigma^2)) / dw in d_gw and the SSE in d_sse: Delta_L = d lp / d yhat = (y - yhat) / sigma^2
-  if (ctx->f32) {
-    // compute_dtype = SI_F32: value and gradient on the fp32 density's own arithmetic (fp32 operands and activations, fp64 head
-    // partials / SSE / batch sums; W_swa + P z rounded once), the pull-back P' g and the optional prior term in fp64
-    DenseSweepF32 sw{ctx->layers.data(), nl, ctx->fuse_tail, ctx->d_w32, ctx->d_w, ctx->d_X32, ctx->d_Y, &ctx->g_ws32, ctx->d_part,
-                     ctx->d_ssepart, ctx->d_sse, ctx->sse_blocks, B, N, 1.0 / s2};
-    if ((rc = dense_value_and_grad_f32(ctx, ctx->stream, sw)) != SI_OK) return rc;
-    launch_widen_f32_to_f64(ctx->stream, ctx->g_ws32.gw32, N, ctx->d_gw, ctx->num_cu);
-  } else if (ctx->plan.has_conv) {
-    const NetPlan& p = ctx->plan;
-    double bflops = 0.0;
-    for (const auto& q : p.L)
-      bflops += q.kind == SI_LAYER_DENSE ? 4.0 * (double)q.in_feat * q.out_feat * (double)B
-                : q.kind == SI_LAYER_CONV ? 4.0 * (double)q.KW * q.KH * q.C * q.Co * (double)q.Wo * q.Ho * (double)B : 0.0;
-    const NetValueGrad vg{&p, ctx->d_w, p.input_spatial ? ctx->d_Xc : ctx->d_X, ctx->d_Y, B, ctx->d_hs.data(), ctx->d_wpack, ctx->d_ssepart,
-                          ctx->sse_blocks, ctx->d_sse, {ctx->d_delta[0], ctx->d_delta[1]}, ctx->d_gw, &ctx->g_scratch, N, 1.0 / s2, bflops};
-    if ((rc = net_value_and_grad(ctx, vg)) != SI_OK) return rc;
-  } else {
-    const DenseValueGrad vg{{ctx->layers.data(), nl, ctx->fuse_tail, ctx->d_w, ctx->d_X, ctx->d_hs.data(), {ctx->d_delta[0], ctx->d_delta[1]},
-                             ctx->d_gw, ctx->d_rspart, ctx->d_bwpart, B},
-                            ctx->d_Y, ctx->fuse_slots, ctx->d_part, ctx->d_ssepart, ctx->d_sse, ctx->sse_blocks, N, 1.0 / s2, true};
-    if ((rc = dense_value_and_grad_f64(ctx, ctx->stream, vg)) != SI_OK) return rc;
-  }
-  if (prior) launch_prior_grad(ctx->stream, ctx->d_gw, ctx->d_w, N, 1.0 / (ctx->sigma_p * ctx->sigma_p), ctx->num_cu);
-  pull_back_to_z(ctx, ctx->d_gw, ctx->d_gz);
+  const bool prior = ctx->setup.sigma_p > 0.0;
+  if (prior) launch_sse(ctx->stream, ctx->fw.w, nullptr, N, ctx->fw.wsqpart, ctx->wsq_blocks, ctx->chains.wsq, 1, pad_ld(N));
+  // d (-SSE / (2 sigma^2)) / dw into grad.gw and the SSE into chains.sse by the chain's route: Delta_L = d lp / d yhat = (y - yhat) / sigma^2.
+  // compute_dtype = SI_F32: on the fp32 density's own arithmetic (W_swa + P z rounded once); P' g and the prior term stay fp64
+  double bflops = 0.0;   // (what a Conv chain reports for its SI_K_BACKWARD scope)
+  for (const auto& q : ctx->setup.plan.L)
+    bflops += q.kind == SI_LAYER_DENSE ? 4.0 * (double)q.in_feat * q.out_feat * (double)B
+              : q.kind == SI_LAYER_CONV ? 4.0 * (double)q.KW * q.KH * q.C * q.Co * (double)q.Wo * q.Ho * (double)B : 0.0;
+  const ChainValueGrad in{ctx->layers.data(), ctx->layers.size(), &ctx->setup.plan, ctx->setup.fuse_tail, ctx->fw.w, ctx->fw.w32, ctx->setup.X, ctx->setup.Xc, ctx->setup.X32,
+                          ctx->setup.Y, B, N, ctx->fw.part, ctx->fuse_slots, ctx->fw.ssepart, ctx->chains.sse, ctx->sse_blocks, ctx->grad.gw, ctx->fw.wpack,
+                          1.0 / s2, nullptr, true, bflops};
+  if ((rc = chain_value_and_grad(ctx, ctx->stream, ctx->grad.ws, in)) != SI_OK) return rc;
+  if (prior) launch_prior_grad(ctx->stream, ctx->grad.gw, ctx->fw.w, N, 1.0 / (ctx->setup.sigma_p * ctx->setup.sigma_p), ctx->num_cu);
+  pull_back_to_z(ctx, ctx->grad.gw, ctx->grad.gz);
   SI_HIP(ctx, hipGetLastError());
   double sse = 0.0, wsq = 0.0;
-  SI_HIP(ctx, hipMemcpyAsync(&sse, ctx->d_sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  SI_HIP(ctx, hipMemcpyAsync(grad_out, ctx->d_gz, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (prior) SI_HIP(ctx, hipMemcpyAsync(&wsq, ctx->d_wsq, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(&sse, ctx->chains.sse, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(grad_out, ctx->grad.gz, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (prior) SI_HIP(ctx, hipMemcpyAsync(&wsq, ctx->chains.wsq, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   *lp_out = lp_from_sums(ctx, sse, wsq);
   return SI_OK;
@@ -782,12 +720,12 @@ static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_ou
 
 // the state rules and error texts shared by the two gradient entry points
 int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok) {
-  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_infer_setup first");
+  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_infer_setup first");
   if (ctx->node.on && !ctx->node.grad)   // (the switch: si_node_set_grad)
     return fail(ctx, SI_ERR_INVALID, std::string(who) + ": not available for NeuralODE models (the gradient through the solver is not built "
                                                         "for this set-up: si_node_set_grad(ctx, 1) turns the discrete adjoint on)");
   if (!args_ok) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": bad argument");
-  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, std::string(who) + ": a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
+  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, std::string(who) + ": a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
   return SI_OK;
 }
 
@@ -806,9 +744,9 @@ int32_t si_logdensity_grad(si_ctx* ctx, const double* z, double* lp_out, double*
 // of its partial).  32 observations per workgroup where that plan leaves room for two workgroups per CU (half the partials).
 // The choice depends on the chain and B only -- never on C -- so a point's bits do not depend on the call it arrives in.
 static int vgrad_class(si_ctx* ctx) {
-  if (ctx->vg_class >= 0) return ctx->vg_class;
-  ctx->vg_class = 0;
-  if (ctx->f32 || ctx->plan.has_conv) return 0;
+  if (ctx->vg.cls >= 0) return ctx->vg.cls;
+  ctx->vg.cls = 0;
+  if (ctx->setup.f32 || ctx->setup.plan.has_conv) return 0;
   const int L = (int)ctx->layers.size();
   ChainVgradPlan vp;
   if (chain_vgrad_plan(vp, ctx->layers.data(), L, ctx->B, 1) == 0) return 0;
@@ -829,8 +767,8 @@ static int vgrad_class(si_ctx* ctx) {
   }
   if (total != ctx->iN) return 0;
   const size_t lds2 = chain_vgrad_plan(vp, ctx->layers.data(), L, ctx->B, 2);
-  ctx->vg_class = (lds2 != 0 && lds2 <= (size_t)64 * 1024) ? 2 : 1;
-  return ctx->vg_class;
+  ctx->vg.cls = (lds2 != 0 && lds2 <= (size_t)64 * 1024) ? 2 : 1;
+  return ctx->vg.cls;
 }
 
 // The fused route's pieces, for si_logdensity_grad_batch (points from the host, staged per pass) and StackedVgrad (points on the
@@ -850,24 +788,24 @@ static int vgrad_route(si_ctx* ctx, int64_t* G_out, int64_t* fit_out) {
 
 // its workspace for `cap` points per pass
 static int32_t vgrad_ensure(si_ctx* ctx, const char* who, int cap, int64_t G) {
-  if (ctx->vg_cap >= cap) return SI_OK;
+  if (ctx->vg.cap >= cap) return SI_OK;
   const int64_t ldw = pad_ld(ctx->iN);
   const int32_t M = ctx->iM;
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const size_t S = (size_t)cap;
-  ctx->vg_cap = 0;
-  if (!ctx->d_vg_z.alloc(S * M) || !ctx->d_vg_w.alloc(S * (size_t)ldw) || !ctx->d_vg_part.alloc(S * (size_t)G * (size_t)ldw) ||
-      !ctx->d_vg_ssepart.alloc(S * (size_t)G) || !ctx->d_vg_gw.alloc(S * (size_t)ldw) || !ctx->d_vg_lp.alloc(S) ||
-      !ctx->d_vg_gz.alloc(S * M)) {
-    for (DevBuf<double>* b : {&ctx->d_vg_z, &ctx->d_vg_w, &ctx->d_vg_part, &ctx->d_vg_ssepart, &ctx->d_vg_gw, &ctx->d_vg_lp, &ctx->d_vg_gz})
+  ctx->vg.cap = 0;
+  if (!ctx->vg.z.alloc(S * M) || !ctx->vg.w.alloc(S * (size_t)ldw) || !ctx->vg.part.alloc(S * (size_t)G * (size_t)ldw) ||
+      !ctx->vg.ssepart.alloc(S * (size_t)G) || !ctx->vg.gw.alloc(S * (size_t)ldw) || !ctx->vg.lp.alloc(S) ||
+      !ctx->vg.gz.alloc(S * M)) {
+    for (DevBuf<double>* b : {&ctx->vg.z, &ctx->vg.w, &ctx->vg.part, &ctx->vg.ssepart, &ctx->vg.gw, &ctx->vg.lp, &ctx->vg.gz})
       b->reset();
     return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": workspace allocation failed");
   }
-  ctx->vg_cap = cap;
+  ctx->vg.cap = cap;
   return SI_OK;
 }
 
-// one pass of launches: value and gradient at the n <= vg_cap points z_dev[:, 0 .. n) (device) into lp_dev[n] / gz_dev[M x n]
+// one pass of launches: value and gradient at the n <= vg.cap points z_dev[:, 0 .. n) (device) into lp_dev[n] / gz_dev[M x n]
 // (device).  Queued on the stream; nothing is copied, nothing synchronises.
 static void vgrad_pass(si_ctx* ctx, int nb, int64_t G, const double* z_dev, int n, double* lp_dev, double* gz_dev) {
   const int64_t N = ctx->iN, B = ctx->B, ldw = pad_ld(N);
@@ -878,13 +816,13 @@ static void vgrad_pass(si_ctx* ctx, int nb, int64_t G, const double* z_dev, int 
   const double c0 = mvnormal_c0((double)ctx->out_dim * (double)B, ctx->sigma_m);
   {
     ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * n, (double)N * (M + 1 + n) * 8.0);
-    (void)form_weights(ctx, z_dev, n, ctx->d_vg_w, ldw);   // (the P route: vgrad_route keeps this pass away from a decoder, whose reverse it does not carry)
+    (void)form_weights(ctx, z_dev, n, ctx->vg.w, ldw);   // (the P route: vgrad_route keeps this pass away from a decoder, whose reverse it does not carry)
   }
   {
     ProfScope ps(ctx, SI_K_BACKWARD, 6.0 * (double)N * (double)B * n, 0.0);
-    launch_chain_vgrad(ctx->stream, vp, nb, lds, ctx->d_vg_w, ldw, ctx->d_X, ctx->d_Y, 1.0 / s2, ctx->d_vg_part, ldw, ctx->d_vg_ssepart, n);
-    launch_chain_vgrad_reduce(ctx->stream, ctx->d_vg_part, (int)G, N, ldw, ctx->d_vg_ssepart, ctx->d_vg_w, ldw, ctx->i_P, ctx->ldP, M,
-                              ctx->sigma_p, prior_c0(ctx), c0, s2, ctx->d_vg_gw, lp_dev, gz_dev, n);
+    launch_chain_vgrad(ctx->stream, vp, nb, lds, ctx->vg.w, ldw, ctx->setup.X, ctx->setup.Y, 1.0 / s2, ctx->vg.part, ldw, ctx->vg.ssepart, n);
+    launch_chain_vgrad_reduce(ctx->stream, ctx->vg.part, (int)G, N, ldw, ctx->vg.ssepart, ctx->vg.w, ldw, ctx->setup.P, ctx->ldP, M,
+                              ctx->setup.sigma_p, prior_c0(ctx), c0, s2, ctx->vg.gw, lp_dev, gz_dev, n);
   }
 }
 
@@ -895,7 +833,7 @@ namespace si {
 // ---- value and gradient at C stacked points that already live on the device (si_sample_mala, si_sample_hmc, si_fit_advi) ---------
 // Two routes, chosen by the chain set up, never by the caller:
 //   fused   chains of the class above: per evaluation launch_reconstruct, launch_chain_vgrad and launch_chain_vgrad_reduce are
-//           queued once per pass of vg_cap points, outputs left on the device.  Nothing is copied and nothing synchronises, so a
+//           queued once per pass of vg.cap points, outputs left on the device.  Nothing is copied and nothing synchronises, so a
 //           caller that queues its own kernel between evaluations keeps its state on the device until its tail.  A launch-queued
 //           loop: no persistent kernel, no grid barrier, nothing that can spin.
 //   other   every other chain (Conv / MaxPool / flatten, SI_F32, the four later activations, wide layers): the points come down
@@ -922,7 +860,7 @@ int32_t StackedVgrad::open(si_ctx* c, const char* who, int32_t npoints) {
     hlp.resize((size_t)C);
     hg.resize((size_t)ctx->iM * C);
   }
-  passes = fused ? (C + ctx->vg_cap - 1) / ctx->vg_cap : C;
+  passes = fused ? (C + ctx->vg.cap - 1) / ctx->vg.cap : C;
   return SI_OK;
 }
 
@@ -935,8 +873,8 @@ void StackedVgrad::eval(const double* z_dev, double* lp_dev, double* g_dev, hipE
     return;
   }
   if (fused) {
-    for (int32_t p0 = 0; p0 < C; p0 += ctx->vg_cap)
-      vgrad_pass(ctx, nb, G, z_dev + M * p0, std::min<int32_t>(ctx->vg_cap, C - p0), lp_dev + p0, g_dev + M * p0);
+    for (int32_t p0 = 0; p0 < C; p0 += ctx->vg.cap)
+      vgrad_pass(ctx, nb, G, z_dev + M * p0, std::min<int32_t>(ctx->vg.cap, C - p0), lp_dev + p0, g_dev + M * p0);
     e = hipGetLastError();
     return;
   }
@@ -969,7 +907,7 @@ int32_t si_logdensity_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double
   int32_t rc = grad_entry_check(ctx, "si_logdensity_grad_batch", Z && C >= 1 && lp_out && grad_out);
   if (rc != SI_OK) return rc;
   BIND(ctx);
-  ctx->last_grad_fused = 0;
+  ctx->vg.last_fused = 0;
   const int32_t M = ctx->iM;
   if (ctx->node.on && !ctx->dec.on) return node_grad_batch(ctx, Z, C, lp_out, grad_out);   // all points of a pass in one launch each
   int64_t G = 0, fit = 0;
@@ -982,35 +920,35 @@ int32_t si_logdensity_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double
     return SI_OK;
   }
   if ((rc = vgrad_ensure(ctx, "si_logdensity_grad_batch", (int)std::min<int64_t>(fit, C), G)) != SI_OK) return rc;
-  for (int32_t p0 = 0; p0 < C; p0 += ctx->vg_cap) {
-    const int n = std::min<int32_t>(ctx->vg_cap, C - p0);
-    SI_HIP(ctx, hipMemcpyAsync(ctx->d_vg_z, Z + (size_t)M * p0, (size_t)M * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    vgrad_pass(ctx, nb, G, ctx->d_vg_z, n, ctx->d_vg_lp, ctx->d_vg_gz);
+  for (int32_t p0 = 0; p0 < C; p0 += ctx->vg.cap) {
+    const int n = std::min<int32_t>(ctx->vg.cap, C - p0);
+    SI_HIP(ctx, hipMemcpyAsync(ctx->vg.z, Z + (size_t)M * p0, (size_t)M * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    vgrad_pass(ctx, nb, G, ctx->vg.z, n, ctx->vg.lp, ctx->vg.gz);
     SI_HIP(ctx, hipGetLastError());
-    SI_HIP(ctx, hipMemcpyAsync(lp_out + p0, ctx->d_vg_lp, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SI_HIP(ctx, hipMemcpyAsync(grad_out + (size_t)M * p0, ctx->d_vg_gz, (size_t)M * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SI_HIP(ctx, hipMemcpyAsync(lp_out + p0, ctx->vg.lp, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SI_HIP(ctx, hipMemcpyAsync(grad_out + (size_t)M * p0, ctx->vg.gz, (size_t)M * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   }
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->last_grad_fused = 1;
+  ctx->vg.last_fused = 1;
   return SI_OK;
 }
 
 int32_t si_grad_kernel_info(si_ctx* ctx, int32_t* fused_out) {
   CHECK_CTX(ctx);
   if (!fused_out) return fail(ctx, SI_ERR_INVALID, "si_grad_kernel_info: bad argument");
-  *fused_out = ctx->last_grad_fused;
+  *fused_out = ctx->vg.last_fused;
   return SI_OK;
 }
 
 int32_t si_forward(si_ctx* ctx, const double* z, double* Yhat_out) {
   CHECK_CTX(ctx);
-  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_forward: call si_infer_setup first");
+  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, "si_forward: call si_infer_setup first");
   if (!z || !Yhat_out) return fail(ctx, SI_ERR_INVALID, "si_forward: bad argument");
-  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_forward: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
+  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_forward: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
   BIND(ctx);
   int32_t rc = ensure_chains(ctx, 1);
   if (rc != SI_OK) return rc;
-  SI_HIP(ctx, hipMemcpyAsync(ctx->d_zprop, z, (size_t)ctx->iM * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(ctx->chains.zprop, z, (size_t)ctx->iM * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   const double* yh = nullptr;
   if ((rc = eval_density(ctx, setup_view(ctx), 0, 1, &yh)) != SI_OK) return rc;
   SI_HIP(ctx, hipMemcpyAsync(Yhat_out, yh, (size_t)ctx->out_dim * ctx->B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -1020,9 +958,9 @@ int32_t si_forward(si_ctx* ctx, const double* z, double* Yhat_out) {
 
 int32_t si_predict(si_ctx* ctx, const double* Z, int32_t C, const double* Xnew, int64_t Bn, double* Yhat_out) {
   CHECK_CTX(ctx);
-  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_predict: call si_infer_setup first");
+  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, "si_predict: call si_infer_setup first");
   if (!Z || C <= 0 || !Xnew || Bn <= 0 || !Yhat_out) return fail(ctx, SI_ERR_INVALID, "si_predict: bad argument");
-  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_predict: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
+  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_predict: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
   BIND(ctx);
   int32_t rc = ensure_chains(ctx, C);
   if (rc != SI_OK) return rc;
@@ -1036,12 +974,12 @@ int32_t si_predict(si_ctx* ctx, const double* Z, int32_t C, const double* Xnew, 
   const int sse_blocks = sse_num_blocks((int64_t)ctx->out_dim * Bn, ctx->num_cu);
   const size_t dB = (size_t)ctx->out_dim * (size_t)Bn;
   const double per = 8.0 * (2.0 * (double)act_elems + ((double)ctx->fuse_slots + 1.0) * (double)dB + (double)sse_blocks);
-  const size_t wb = (size_t)std::max(1.0, std::min({(double)C, (double)ctx->fw_slots, std::floor(SI_BATCH_BYTES / per)}));
+  const size_t wb = (size_t)std::max(1.0, std::min({(double)C, (double)ctx->fw.slots, std::floor(SI_BATCH_BYTES / per)}));
   DevBuf<double> tX, tY, tA[2], tS, tP, tYh, tXc;
   bool ok = tX.alloc((size_t)ctx->in_dim * Bn) && tY.alloc(dB) &&
-            (!ctx->plan.input_spatial || tXc.alloc((size_t)ctx->plan.in_elems * Bn)) &&
+            (!ctx->setup.plan.input_spatial || tXc.alloc((size_t)ctx->setup.plan.in_elems * Bn)) &&
             tA[0].alloc(wb * (size_t)act_elems) && tA[1].alloc(wb * (size_t)act_elems) && tS.alloc(wb * (size_t)sse_blocks) &&
-            (!ctx->fuse_tail || (tP.alloc(wb * (size_t)ctx->fuse_slots * dB) && tYh.alloc(wb * dB)));
+            (!ctx->setup.fuse_tail || (tP.alloc(wb * (size_t)ctx->fuse_slots * dB) && tYh.alloc(wb * dB)));
   hipError_t e = hipSuccess;
   if (ok) {
     const DensityView v{tX, tXc, nullptr, tY, Bn, tA, nullptr, tS, sse_blocks, tP, tYh, act_elems, /*f32=*/false,
@@ -1049,15 +987,15 @@ int32_t si_predict(si_ctx* ctx, const double* Z, int32_t C, const double* Xnew, 
     e = hipMemcpyAsync(tX, Xnew, (size_t)ctx->in_dim * Bn * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(tY, 0, dB * sizeof(double), ctx->stream);
     if (e == hipSuccess)
-      e = hipMemcpyAsync(ctx->d_zprop, Z, (size_t)ctx->iM * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (ctx->plan.input_spatial) net_input(ctx, ctx->plan, tX, tXc, Bn);
+      e = hipMemcpyAsync(ctx->chains.zprop, Z, (size_t)ctx->iM * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (ctx->setup.plan.input_spatial) net_input(ctx, ctx->setup.plan, tX, tXc, Bn);
     for (int c0 = 0; c0 < C && e == hipSuccess && rc == SI_OK; c0 += (int)wb) {
       const int nc = std::min<int>((int)wb, C - c0);
       const double* yh = nullptr;
       rc = eval_density(ctx, v, c0, nc, &yh);
       if (rc == SI_OK) {
         // sample j of the batch: yh + j * (out_dim*Bn) after the fused tail, yh + j * act_elems otherwise
-        const size_t src_pitch = (ctx->fuse_tail ? dB : (size_t)act_elems) * sizeof(double);
+        const size_t src_pitch = (ctx->setup.fuse_tail ? dB : (size_t)act_elems) * sizeof(double);
         e = hipMemcpy2DAsync(Yhat_out + (size_t)c0 * dB, dB * sizeof(double), yh, src_pitch, dB * sizeof(double), (size_t)nc,
                              hipMemcpyDeviceToHost, ctx->stream);
       }

@@ -13,19 +13,19 @@ int32_t si_sample_mala(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, 
                        double* lp_out, double* accept_rate_out, double* G_out) {
   CHECK_CTX(ctx);
   const char* who = "si_sample_mala";
-  ctx->info_mala = CallInfo();   // (si_mala_kernel_info reports THIS call)
+  ctx->mala.info = CallInfo();   // (si_mala_kernel_info reports THIS call)
   int32_t rc = grad_entry_check(ctx, who, itr > 0 && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0);
   if (rc != SI_OK) return rc;
   BIND(ctx);
   const int32_t C = nchains, M = ctx->iM;
   if ((rc = reserve_chain_state(ctx, who, C)) != SI_OK) return rc;
-  if ((rc = reserve_state(ctx, who, ctx->mala_cap, C, [&] { return ctx->d_mala_nacc.alloc((size_t)C); })) != SI_OK) return rc;
+  if ((rc = reserve_state(ctx, who, ctx->mala.cap, C, [&] { return ctx->mala.nacc.alloc((size_t)C); })) != SI_OK) return rc;
   const size_t zelems = (size_t)M * (size_t)itr * (size_t)C;
-  if (!ctx->d_outZ.reserve(zelems) || !ctx->d_outlp.reserve((size_t)itr * C) || (G_out && !ctx->d_outG.reserve(zelems)))
+  if (!ctx->chains.outZ.reserve(zelems) || !ctx->chains.outlp.reserve((size_t)itr * C) || (G_out && !ctx->mala.outG.reserve(zelems)))
     return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
   MalaRun a;
   chain_run_args(a, ctx, itr, sigma_z, seed, chain_id0, G_out != nullptr);
-  a.nacc = ctx->d_mala_nacc;
+  a.nacc = ctx->mala.nacc;
   a.h = 0.5 * (sigma_z * sigma_z);
   StackedVgrad vg;
   if ((rc = vg.open(ctx, who, C)) != SI_OK) return rc;
@@ -43,20 +43,20 @@ int32_t si_sample_mala(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, 
     e = hipGetLastError();
   }
   std::vector<int64_t> nacc((size_t)C);
-  rc = finish_downloads(ctx, who, e, rc, {{Z_out, ctx->d_outZ, zelems * sizeof(double)},
-                                          {lp_out, ctx->d_outlp, (size_t)itr * C * sizeof(double)},
+  rc = finish_downloads(ctx, who, e, rc, {{Z_out, ctx->chains.outZ, zelems * sizeof(double)},
+                                          {lp_out, ctx->chains.outlp, (size_t)itr * C * sizeof(double)},
                                           {G_out, a.G_out, zelems * sizeof(double)},
-                                          {nacc.data(), ctx->d_mala_nacc, (size_t)C * sizeof(int64_t)}});
+                                          {nacc.data(), ctx->mala.nacc, (size_t)C * sizeof(int64_t)}});
   if (rc != SI_OK) return rc;
   accept_rates(nacc, itr, accept_rate_out);
-  ctx->info_mala = call_info(vg);
+  ctx->mala.info = call_info(vg);
   return SI_OK;
 }
 
 int32_t si_mala_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out) {
   CHECK_CTX(ctx);
-  if (fused_out) *fused_out = ctx->info_mala.fused;
-  if (passes_out) *passes_out = ctx->info_mala.passes;
+  if (fused_out) *fused_out = ctx->mala.info.fused;
+  if (passes_out) *passes_out = ctx->mala.info.passes;
   return SI_OK;
 }
 

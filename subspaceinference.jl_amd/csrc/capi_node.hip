@@ -85,14 +85,14 @@ int32_t node_density(si_ctx* ctx, const DensityView& v, int c0, int nc, const do
   if (rc != SI_OK) return rc;
   {
     ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * nc, (double)N * (M + 1 + nc) * 8.0);
-    if ((rc = form_weights(ctx, ctx->d_zprop + (size_t)c0 * M, nc, ctx->d_w, ldw)) != SI_OK) return rc;
+    if ((rc = form_weights(ctx, ctx->chains.zprop + (size_t)c0 * M, nc, ctx->fw.w, ldw)) != SI_OK) return rc;
   }
-  launch_sse(ctx->stream, ctx->d_w, nullptr, N, ctx->d_wsqpart, ctx->wsq_blocks, ctx->d_wsq + c0, nc, ldw);   // ||W||^2 per chain
+  launch_sse(ctx->stream, ctx->fw.w, nullptr, N, ctx->fw.wsqpart, ctx->wsq_blocks, ctx->chains.wsq + c0, nc, ldw);   // ||W||^2 per chain
   {
     ProfScope ps(ctx, SI_K_DENSE, 0.0, 0.0);
-    const NodeArgs a = node_args(ctx, ctx->d_w, v.X, v.Y, f, ctx->node.ssep, yhat_out ? ctx->node.uout.get() : nullptr, nullptr, nullptr, nullptr);
+    const NodeArgs a = node_args(ctx, ctx->fw.w, v.X, v.Y, f, ctx->node.ssep, yhat_out ? ctx->node.uout.get() : nullptr, nullptr, nullptr, nullptr);
     SI_HIP(ctx, launch_node_solve(ctx->stream, a, nc));
-    launch_node_sum(ctx->stream, ctx->node.ssep, f, ctx->d_sse + c0, nc);
+    launch_node_sum(ctx->stream, ctx->node.ssep, f, ctx->chains.sse + c0, nc);
   }
   SI_HIP(ctx, hipGetLastError());
   if (yhat_out) *yhat_out = ctx->node.uout;
@@ -121,7 +121,7 @@ int32_t si_infer_setup_node(si_ctx* ctx, const si_layer* layers, int32_t L, int6
     return fail(ctx, SI_ERR_NOMEM, "si_infer_setup_node: device allocation / upload failed");
   }
   n.args = a, n.d = d, n.S = S;
-  ctx->sigma_p = 1.0;   // "the prior term on": its constants are lik_c0 / lik_s2 / prior_c0 / prior_sp2 (capi_infer.hip)
+  ctx->setup.sigma_p = 1.0;   // "the prior term on": its constants are lik_c0 / lik_s2 / prior_c0 / prior_sp2 (capi_infer.hip)
   n.on = true;
   return SI_OK;
 }
@@ -129,29 +129,29 @@ int32_t si_infer_setup_node(si_ctx* ctx, const si_layer* layers, int32_t L, int6
 int32_t si_node_solve(si_ctx* ctx, const double* Z, int32_t C, double* U_out, double* sse_out, int32_t* naccept_out,
                       int32_t* nreject_out, int32_t* status_out) {
   CHECK_CTX(ctx);
-  if (!ctx->i_ready || !ctx->node.on) return fail(ctx, SI_ERR_STATE, "si_node_solve: call si_infer_setup_node first");
+  if (!ctx->setup.ready || !ctx->node.on) return fail(ctx, SI_ERR_STATE, "si_node_solve: call si_infer_setup_node first");
   if (!Z || C <= 0) return fail(ctx, SI_ERR_INVALID, "si_node_solve: bad argument");
-  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_node_solve: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
+  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_node_solve: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
   BIND(ctx);
   int32_t rc = ensure_chains(ctx, C);
   if (rc != SI_OK) return rc;
   const int64_t N = ctx->iN, ldw = pad_ld(N), f = ctx->B;
   const int32_t M = ctx->iM;
   const size_t traj = (size_t)ctx->node.d * (size_t)ctx->node.S * (size_t)f;
-  // an audit read-back, not a hot path: fw_slots chains per pass (at most 256 MB of saved states), one synchronisation per pass
-  int wb = std::max(1, std::min<int>(ctx->fw_slots, C));
+  // an audit read-back, not a hot path: fw.slots chains per pass (at most 256 MB of saved states), one synchronisation per pass
+  int wb = std::max(1, std::min<int>(ctx->fw.slots, C));
   if (U_out) wb = (int)std::max<size_t>(1, std::min<size_t>((size_t)wb, ((size_t)32 << 20) / traj));
   DevBuf<double> dU, dS;
   DevBuf<int32_t> dI;
   if ((U_out && !dU.alloc(traj * (size_t)wb)) || !dS.alloc((size_t)f * wb) || !dI.alloc((size_t)3 * (size_t)f * wb))
     return fail(ctx, SI_ERR_NOMEM, "si_node_solve: device allocation failed");
-  SI_HIP(ctx, hipMemcpyAsync(ctx->d_zprop, Z, (size_t)M * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(ctx->chains.zprop, Z, (size_t)M * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   const size_t fw = (size_t)f * (size_t)wb;
   for (int c0 = 0; c0 < C; c0 += wb) {
     const int nc = std::min(wb, C - c0);
     const size_t fn = (size_t)f * (size_t)nc;
-    if ((rc = form_weights(ctx, ctx->d_zprop + (size_t)c0 * M, nc, ctx->d_w, ldw)) != SI_OK) return rc;
-    const NodeArgs a = node_args(ctx, ctx->d_w, ctx->d_X, ctx->d_Y, f, dS, U_out ? dU.get() : nullptr, dI, dI + fw, dI + 2 * fw);
+    if ((rc = form_weights(ctx, ctx->chains.zprop + (size_t)c0 * M, nc, ctx->fw.w, ldw)) != SI_OK) return rc;
+    const NodeArgs a = node_args(ctx, ctx->fw.w, ctx->setup.X, ctx->setup.Y, f, dS, U_out ? dU.get() : nullptr, dI, dI + fw, dI + 2 * fw);
     SI_HIP(ctx, launch_node_solve(ctx->stream, a, nc));
     if (U_out) SI_HIP(ctx, hipMemcpyAsync(U_out + traj * (size_t)c0, dU, traj * (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (sse_out) SI_HIP(ctx, hipMemcpyAsync(sse_out + (size_t)f * c0, dS, fn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -168,17 +168,17 @@ int32_t node_predict(si_ctx* ctx, const double* Z, int32_t C, const double* U0ne
   const int64_t N = ctx->iN, ldw = pad_ld(N);
   const int32_t M = ctx->iM, d = ctx->node.d;
   const size_t traj = (size_t)d * (size_t)ctx->node.S * (size_t)Bn;
-  const int wb = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min<int>(ctx->fw_slots, C), ((size_t)32 << 20) / traj));
+  const int wb = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min<int>(ctx->fw.slots, C), ((size_t)32 << 20) / traj));
   DevBuf<double> dX, dU, dS;
   if (!dX.alloc((size_t)d * (size_t)Bn) || !dU.alloc(traj * (size_t)wb) || !dS.alloc((size_t)Bn * wb))
     return fail(ctx, SI_ERR_NOMEM, "si_predict: device allocation failed");
   SI_HIP(ctx, hipMemcpyAsync(dX, U0new, (size_t)d * (size_t)Bn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  SI_HIP(ctx, hipMemcpyAsync(ctx->d_zprop, Z, (size_t)M * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(ctx->chains.zprop, Z, (size_t)M * C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   for (int c0 = 0; c0 < C; c0 += wb) {
     const int nc = std::min(wb, C - c0);
-    const int32_t rc = form_weights(ctx, ctx->d_zprop + (size_t)c0 * M, nc, ctx->d_w, ldw);
+    const int32_t rc = form_weights(ctx, ctx->chains.zprop + (size_t)c0 * M, nc, ctx->fw.w, ldw);
     if (rc != SI_OK) return rc;
-    const NodeArgs a = node_args(ctx, ctx->d_w, dX, nullptr, Bn, dS, dU, nullptr, nullptr, nullptr);
+    const NodeArgs a = node_args(ctx, ctx->fw.w, dX, nullptr, Bn, dS, dU, nullptr, nullptr, nullptr);
     SI_HIP(ctx, launch_node_solve(ctx->stream, a, nc));
     SI_HIP(ctx, hipMemcpyAsync(U_out + traj * (size_t)c0, dU, traj * (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -201,8 +201,8 @@ static void node_grad_drop(NodeState& n) {
 
 int32_t si_node_set_grad(si_ctx* ctx, int32_t on) {
   CHECK_CTX(ctx);
-  if (!ctx->i_ready || !ctx->node.on) return fail(ctx, SI_ERR_STATE, "si_node_set_grad: call si_infer_setup_node first");
-  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_node_set_grad: a step-wise RWMH session is open");
+  if (!ctx->setup.ready || !ctx->node.on) return fail(ctx, SI_ERR_STATE, "si_node_set_grad: call si_infer_setup_node first");
+  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_node_set_grad: a step-wise RWMH session is open");
   if (on != 0 && on != 1) return fail(ctx, SI_ERR_INVALID, "si_node_set_grad: on must be 0 or 1");
   BIND(ctx);
   NodeState& n = ctx->node;
@@ -225,7 +225,7 @@ int32_t si_node_set_grad(si_ctx* ctx, int32_t on) {
 
 int32_t si_node_grad_info(si_ctx* ctx, int32_t* on_out, int32_t* chains_per_pass_out) {
   CHECK_CTX(ctx);
-  const bool on = ctx->i_ready && ctx->node.on && ctx->node.grad;
+  const bool on = ctx->setup.ready && ctx->node.on && ctx->node.grad;
   if (on_out) *on_out = on ? 1 : 0;
   if (chains_per_pass_out) *chains_per_pass_out = on ? ctx->node.g_fit : 0;
   return SI_OK;
@@ -241,7 +241,7 @@ int32_t node_grad_ensure(si_ctx* ctx, const char* who, int32_t C) {
   const bool ok = n.g_z.alloc(S * M) && n.g_w.alloc(S * ldw) && n.g_ssep.alloc(S * f) && n.g_sse.alloc(S) && n.g_wsq.alloc(S) &&
                   n.g_wsqpart.alloc(S * (size_t)ctx->wsq_blocks) && n.g_rec.alloc(S * f * (size_t)n.args.max_steps * (size_t)(n.d + 2)) &&
                   n.g_slices.alloc(S * f * N) && n.g_gw.alloc(S * ldw) && n.g_lp.alloc(S) && n.g_gz.alloc(S * M) && n.g_cnt.alloc(3 * S * f) &&
-                  ctx->d_ptgpart.reserve((size_t)ptg_blocks() * M);
+                  ctx->grad.ptgpart.reserve((size_t)ptg_blocks() * M);
   if (!ok) {
     node_grad_drop(n);
     return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": workspace allocation failed (the NeuralODE gradient's record: lower max_steps)");
@@ -260,7 +260,7 @@ static int32_t node_grad_launches(si_ctx* ctx, int32_t nc, double* lp_dev) {
   const size_t fc = (size_t)f * (size_t)n.g_cap;
   launch_sse(ctx->stream, n.g_w, nullptr, N, n.g_wsqpart, ctx->wsq_blocks, n.g_wsq, nc, ldw);
   SI_HIP(ctx, hipMemsetAsync(n.g_slices, 0, (size_t)nc * (size_t)f * (size_t)N * sizeof(double), ctx->stream));   // "from 0.0"
-  NodeArgs a = node_args(ctx, n.g_w, ctx->d_X, ctx->d_Y, f, n.g_ssep, nullptr, n.g_cnt, n.g_cnt + fc, n.g_cnt + 2 * fc);
+  NodeArgs a = node_args(ctx, n.g_w, ctx->setup.X, ctx->setup.Y, f, n.g_ssep, nullptr, n.g_cnt, n.g_cnt + fc, n.g_cnt + 2 * fc);
   a.rec = n.g_rec, a.gsl = n.g_slices;
   {
     ProfScope ps(ctx, SI_K_DENSE, 0.0, 0.0);
@@ -323,7 +323,7 @@ int32_t node_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double* lp_out,
 // the audit read-back: lp (C), d lp / dW (N x C, the prior term included) and its pull-back (M x C) at Z[:, c]; either seam
 int32_t si_node_grad(si_ctx* ctx, const double* Z, int32_t C, double* lp_out, double* gw_out, double* gz_out) {
   CHECK_CTX(ctx);
-  if (!ctx->i_ready || !ctx->node.on) return fail(ctx, SI_ERR_STATE, "si_node_grad: call si_infer_setup_node first");
+  if (!ctx->setup.ready || !ctx->node.on) return fail(ctx, SI_ERR_STATE, "si_node_grad: call si_infer_setup_node first");
   int32_t rc = grad_entry_check(ctx, "si_node_grad", Z && C >= 1);
   if (rc != SI_OK) return rc;
   BIND(ctx);
@@ -366,7 +366,7 @@ int32_t si_node_tableau(double* out) {
 
 int32_t si_node_info(si_ctx* ctx, int32_t* active_out, int32_t* d_out, int32_t* S_out, int64_t* f_out, int32_t* G_out) {
   CHECK_CTX(ctx);
-  const bool on = ctx->i_ready && ctx->node.on;
+  const bool on = ctx->setup.ready && ctx->node.on;
   if (active_out) *active_out = on ? 1 : 0;
   if (d_out) *d_out = on ? ctx->node.d : 0;
   if (S_out) *S_out = on ? ctx->node.S : 0;

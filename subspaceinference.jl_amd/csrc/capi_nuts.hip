@@ -18,7 +18,7 @@ int32_t si_sample_nuts(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_
                        double* leaf_out, int64_t leaf_cap) {
   CHECK_CTX(ctx);
   const char* who = "si_sample_nuts";
-  ctx->info_nuts = CallInfo();   // (si_nuts_kernel_info reports THIS call)
+  ctx->nuts.info = CallInfo();   // (si_nuts_kernel_info reports THIS call)
   // (every comparison is false for a NaN: refused)
   int32_t rc = grad_entry_check(ctx, who, itr > 0 && n_adapts >= 0 && n_adapts <= itr && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0 &&
                                               delta > 0.0 && delta < 1.0 && max_depth >= 1 && max_depth <= NUTS_MAX_DEPTH && max_dh > 0.0 &&
@@ -30,19 +30,19 @@ int32_t si_sample_nuts(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_
   if ((rc = hmc_reserve_state(ctx, who, C, true)) != SI_OK) return rc;
   const size_t zelems = (size_t)M * (size_t)cols * (size_t)C, selems = (size_t)cols * (size_t)C;
   const size_t lelems = leaf_out ? (3 * (size_t)M + 1) * (size_t)leaf_cap * (size_t)C : 0;
-  if (!ctx->d_outZ.reserve(zelems) || !ctx->d_outlp.reserve(selems) || !ctx->d_outalpha.reserve(selems) || !ctx->d_outeps.reserve(selems) ||
-      !ctx->d_outdepth.reserve(selems) || !ctx->d_outnleaf.reserve(selems) || !ctx->d_outsel.reserve(selems) ||
-      (G_out && !ctx->d_outG.reserve(zelems)) || (Minv_out && !ctx->d_outMinv.reserve(zelems)) || (leaf_out && !ctx->d_outleaf.reserve(lelems)))
+  if (!ctx->chains.outZ.reserve(zelems) || !ctx->chains.outlp.reserve(selems) || !ctx->hmc.outalpha.reserve(selems) || !ctx->hmc.outeps.reserve(selems) ||
+      !ctx->nuts.outdepth.reserve(selems) || !ctx->nuts.outnleaf.reserve(selems) || !ctx->nuts.outsel.reserve(selems) ||
+      (G_out && !ctx->mala.outG.reserve(zelems)) || (Minv_out && !ctx->hmc.outMinv.reserve(zelems)) || (leaf_out && !ctx->nuts.outleaf.reserve(lelems)))
     return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
   HmcPhases phases(n_adapts);
   const HmcRun a = hmc_run_args(ctx, itr, sigma_z, delta, seed, chain_id0, G_out != nullptr, Minv_out != nullptr);
-  const NutsRun n{ctx->d_nuts_zm, ctx->d_nuts_rm, ctx->d_nuts_gm, ctx->d_nuts_zq, ctx->d_nuts_rq, ctx->d_nuts_gq, ctx->d_nuts_rho,
-                  ctx->d_nuts_zc, ctx->d_nuts_gc, ctx->d_nuts_stack, ctx->d_nuts_tree, ctx->d_outdepth, ctx->d_outnleaf, ctx->d_outsel,
-                  leaf_out ? ctx->d_outleaf.get() : nullptr, leaf_cap, max_depth, max_dh};
+  const NutsRun n{ctx->nuts.zm, ctx->nuts.rm, ctx->nuts.gm, ctx->nuts.zq, ctx->nuts.rq, ctx->nuts.gq, ctx->nuts.rho,
+                  ctx->nuts.zc, ctx->nuts.gc, ctx->nuts.stack, ctx->nuts.tree, ctx->nuts.outdepth, ctx->nuts.outnleaf, ctx->nuts.outsel,
+                  leaf_out ? ctx->nuts.outleaf.get() : nullptr, leaf_cap, max_depth, max_dh};
   StackedVgrad vg;
   if ((rc = vg.open(ctx, who, C)) != SI_OK) return rc;
   // (log slots that no leaf reaches read as NaN: all bits set)
-  hipError_t e = leaf_out ? hipMemsetAsync(ctx->d_outleaf, 0xFF, lelems * sizeof(double), ctx->stream) : hipSuccess;
+  hipError_t e = leaf_out ? hipMemsetAsync(ctx->nuts.outleaf, 0xFF, lelems * sizeof(double), ctx->stream) : hipSuccess;
   const int search_rounds = e == hipSuccess ? hmc_preamble(ctx, who, a, vg, C, e, rc) : 0;
   const int64_t round_cap = ((int64_t)1 << max_depth) - 1;
   int64_t rounds = 0;
@@ -71,23 +71,23 @@ int32_t si_sample_nuts(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_
   }
   const size_t zbytes = zelems * sizeof(double), sbytes = selems * sizeof(double), ibytes = selems * sizeof(int32_t);
   std::vector<int32_t> nleaf(selems);   // (always fetched: si_nuts_kernel_info's leaves)
-  rc = finish_downloads(ctx, who, e, rc, {{Z_out, ctx->d_outZ, zbytes}, {lp_out, ctx->d_outlp, sbytes}, {alpha_out, ctx->d_outalpha, sbytes},
-                                          {eps_out, ctx->d_outeps, sbytes}, {depth_out, ctx->d_outdepth, ibytes},
-                                          {nleaf.data(), ctx->d_outnleaf, ibytes}, {sel_out, ctx->d_outsel, ibytes},
+  rc = finish_downloads(ctx, who, e, rc, {{Z_out, ctx->chains.outZ, zbytes}, {lp_out, ctx->chains.outlp, sbytes}, {alpha_out, ctx->hmc.outalpha, sbytes},
+                                          {eps_out, ctx->hmc.outeps, sbytes}, {depth_out, ctx->nuts.outdepth, ibytes},
+                                          {nleaf.data(), ctx->nuts.outnleaf, ibytes}, {sel_out, ctx->nuts.outsel, ibytes},
                                           {G_out, a.G_out, zbytes}, {Minv_out, a.Minv_out, zbytes},
                                           {leaf_out, n.leaf_out, lelems * sizeof(double)}});
   if (rc != SI_OK) return rc;
   int64_t leaves = 0;
   for (int32_t v : nleaf) leaves += v;
   if (nleaf_out) std::memcpy(nleaf_out, nleaf.data(), ibytes);
-  ctx->info_nuts = call_info(vg, search_rounds, rounds, leaves);
+  ctx->nuts.info = call_info(vg, search_rounds, rounds, leaves);
   return SI_OK;
 }
 
 int32_t si_nuts_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out, int32_t* search_rounds_out, int64_t* rounds_out,
                             int64_t* leaves_out) {
   CHECK_CTX(ctx);
-  const CallInfo& i = ctx->info_nuts;
+  const CallInfo& i = ctx->nuts.info;
   if (fused_out) *fused_out = i.fused;
   if (passes_out) *passes_out = i.passes;
   if (search_rounds_out) *search_rounds_out = i.search_rounds;

@@ -16,7 +16,7 @@ using namespace si;
 extern "C" {
 
 // ---- streamed output map (a13, src/space_inference.jl:125: `map(z -> W_swa + P*z.params, chm)`) ------------------------
-// K4 has already produced W_swa + P z' for every proposal (d_w); the weight vector of sample t is that vector when the
+// K4 has already produced W_swa + P z' for every proposal (fw.w); the weight vector of sample t is that vector when the
 // proposal was accepted and the previous sample's otherwise.  A select kernel keeps the CURRENT weights of every chain in
 // a small device ring (8 bytes read + 8 written per weight, ~4 us at cfg2 -- instead of a second K4 pass over P), a DMA
 // on the second stream moves ring slot t into pinned memory while transition t+1 computes, and the host copy pool
@@ -58,7 +58,7 @@ static int32_t ensure_wstream(si_ctx* ctx, int32_t C) {
 // launches per transition spread over the chip (2 N B <= 3 MFLOP: the README toy is 0.14)
 static constexpr size_t SI_CHAIN_LDS_LIMIT = 160 * 1024 - 256;
 static bool chain_loop_applies(const si_ctx* ctx) {
-  if (ctx->f32 || ctx->plan.has_conv || !ctx->fuse_tail || ctx->sigma_p > 0.0 || ctx->dec.on) return false;   // (dec: the loop forms W_swa + P z itself)
+  if (ctx->setup.f32 || ctx->setup.plan.has_conv || !ctx->setup.fuse_tail || ctx->setup.sigma_p > 0.0 || ctx->dec.on) return false;   // (dec: the loop forms W_swa + P z itself)
   if (ctx->layers.size() > (size_t)SI_CHAIN_MAX_LAYERS || ctx->iN > (1 << 20) || ctx->B > (1 << 20)) return false;
   if (ctx->iM > 1024) return false;   // (rwmh_chain_kernel keeps z one element per thread of its 1024-thread workgroup)
   for (const auto& ly : ctx->layers)
@@ -66,8 +66,8 @@ static bool chain_loop_applies(const si_ctx* ctx) {
   return 2.0 * (double)ctx->iN * (double)ctx->B <= 3.0e6;
 }
 
-// The common end of the three sampler forms.  `e` is the state of what the form has queued so far.  Z / lp (from d_outZ /
-// d_outlp) and the accept counts come down -- Z and lp through the pinned `stage` where the form hands one in; with W_out the
+// The common end of the three sampler forms.  `e` is the state of what the form has queued so far.  Z / lp (from chains.outZ /
+// chains.outlp) and the accept counts come down -- Z and lp through the pinned `stage` where the form hands one in; with W_out the
 // weight samples of the finished chains come from ONE K4 pass over all itr * C samples into a temporary (the kernel
 // si_reconstruct runs: same bits) and a 2-D copy; one synchronisation; the first error is reported; a raised barrier word
 // of the grid loop (grid_status) is one; the accept rates are filled in.
@@ -77,16 +77,16 @@ static int32_t finish_chains(si_ctx* ctx, const char* who, hipError_t e, int64_t
   const int64_t N = ctx->iN, ldw = pad_ld(N);
   const size_t zbytes = Z_out ? (size_t)M * itr * C * sizeof(double) : 0, lbytes = lp_out ? (size_t)itr * C * sizeof(double) : 0;
   std::vector<int64_t> nacc((size_t)C);
-  if (e == hipSuccess && Z_out) e = hipMemcpyAsync(stage ? (void*)stage : (void*)Z_out, ctx->d_outZ, zbytes, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && Z_out) e = hipMemcpyAsync(stage ? (void*)stage : (void*)Z_out, ctx->chains.outZ, zbytes, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && lp_out)
-    e = hipMemcpyAsync(stage ? (void*)(stage + zbytes) : (void*)lp_out, ctx->d_outlp, lbytes, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(nacc.data(), ctx->d_nacc, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
+    e = hipMemcpyAsync(stage ? (void*)(stage + zbytes) : (void*)lp_out, ctx->chains.outlp, lbytes, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(nacc.data(), ctx->chains.nacc, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
   DevBuf<double> dW;
   if (e == hipSuccess && W_out) {   // src/space_inference.jl:125 for every sample of every chain
     if (!dW.alloc(wall_elems)) e = hipErrorOutOfMemory;   // (ldw * itr * C: the caller has held it to its 512 MB gate)
     if (e == hipSuccess) {
       ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * (double)itr * C, (double)N * (M + 1 + (double)itr * C) * 8.0);
-      const int32_t rcw = form_weights(ctx, ctx->d_outZ, (int32_t)(itr * C), dW, ldw);
+      const int32_t rcw = form_weights(ctx, ctx->chains.outZ, (int32_t)(itr * C), dW, ldw);
       e = rcw == SI_OK ? hipGetLastError() : hipErrorOutOfMemory;
     }
     if (e == hipSuccess)
@@ -109,7 +109,7 @@ static int32_t finish_chains(si_ctx* ctx, const char* who, hipError_t e, int64_t
 }
 
 // One si_sample_rwmh* call, as sample_rwmh_impl hands it to the sampler forms: the arguments, and what the entry has checked,
-// reserved (ensure_chains / ensure_wstream, d_outZ / d_outlp) and worked out once.
+// reserved (ensure_chains / ensure_wstream, chains.outZ / chains.outlp) and worked out once.
 struct RwmhCall {
   const char* who;
   int64_t itr;
@@ -125,8 +125,8 @@ struct RwmhCall {
 // the fields that the argument structs of the three device-resident kernels share (a template: C++ linkage inside this block)
 extern "C++" template <typename Args>
 static void fill_common_args(Args& a, const si_ctx* ctx, const RwmhCall& k) {
-  a.swa = ctx->i_swa; a.P = ctx->i_P; a.X = ctx->d_X; a.Y = ctx->d_Y;
-  a.Z_out = ctx->d_outZ; a.lp_out = ctx->d_outlp; a.nacc_out = reinterpret_cast<decltype(a.nacc_out)>(ctx->d_nacc.get());
+  a.swa = ctx->setup.swa; a.P = ctx->setup.P; a.X = ctx->setup.X; a.Y = ctx->setup.Y;
+  a.Z_out = ctx->chains.outZ; a.lp_out = ctx->chains.outlp; a.nacc_out = reinterpret_cast<decltype(a.nacc_out)>(ctx->chains.nacc.get());
   a.ldP = ctx->ldP; a.itr = k.itr; a.seed = k.seed; a.sigma_z = k.sigma_z; a.c0 = k.c0; a.sigma2 = k.s2;
   a.N = (int)ctx->iN; a.chain_id0 = k.chain_id0;
 }
@@ -158,7 +158,7 @@ static int32_t rwmh_one_workgroup(si_ctx* ctx, const RwmhCall& k) {
 // The grid loop specialised to this chain's shapes (chain_spec.inc through hiprtc; same bits): ONE barrier per transition, the
 // weights handed over in fragment order.  Class: a narrow head, at most 1024 model outputs (four blocks of the SSE tree),
 // every weight fragment in registers (spec_applies).  Lays out its LDS behind the images of the forward (sa, *lds_spec), keeps
-// d_specw / d_specy for C chains and the fragment-order permutation of these kernels.  Returns the kernels, or null with *rc
+// loop.specw / loop.specy for C chains and the fragment-order permutation of these kernels.  Returns the kernels, or null with *rc
 // SI_OK (not of the class: the generic loop runs) or the call's error.
 static const SpecKernels* prepare_spec_loop(si_ctx* ctx, const RwmhCall& k, int G, int nb, int sf, SiSpecGridArgs& sa, size_t* lds_spec,
                                             int32_t* rc) {
@@ -169,7 +169,7 @@ static const SpecKernels* prepare_spec_loop(si_ctx* ctx, const RwmhCall& k, int 
     *rc = fail(ctx, code, std::string(k.who) + what);
     return (const SpecKernels*)nullptr;
   };
-  if (!ctx->chain_spec || !ctx->fuse_tail || d > 1024 || M > 256) return nullptr;
+  if (!ctx->chain_spec || !ctx->setup.fuse_tail || d > 1024 || M > 256) return nullptr;
   const int rs = (int)((((N + G - 1) / G) + 15) & ~(int64_t)15);
   const SpecKernels* sk = spec_kernels(ctx->layers.data(), (int)ctx->layers.size(), nb, sf, M, rs <= 256 && M <= 32, &ctx->spec_message);
   if (!sk) return nullptr;
@@ -188,26 +188,26 @@ static const SpecKernels* prepare_spec_loop(si_ctx* ctx, const RwmhCall& k, int 
   off += 2;
   *lds_spec = std::max((size_t)off * sizeof(double), (size_t)(81 * 1024));   // (more than half a CU's LDS: one workgroup per CU)
   if (*lds_spec > (size_t)160 * 1024 - 256) return nullptr;
-  if (ctx->spec_chains < C || ctx->spec_fo != sk->fo_total) {
-    ctx->d_specw.reset();
-    ctx->d_specy.reset();
-    ctx->spec_chains = 0;
-    if (!ctx->d_specw.alloc((size_t)4 * (size_t)sk->fo_total * (size_t)C) || !ctx->d_specy.alloc((size_t)2 * (size_t)d * (size_t)C))
+  if (ctx->loop.spec_chains < C || ctx->loop.spec_fo != sk->fo_total) {
+    ctx->loop.specw.reset();
+    ctx->loop.specy.reset();
+    ctx->loop.spec_chains = 0;
+    if (!ctx->loop.specw.alloc((size_t)4 * (size_t)sk->fo_total * (size_t)C) || !ctx->loop.specy.alloc((size_t)2 * (size_t)d * (size_t)C))
       return bad(SI_ERR_NOMEM, ": allocation failed");
     // (the padding elements of the fragment-ordered vectors are never written by K4: they must be finite)
-    if (hipMemsetAsync(ctx->d_specw, 0, (size_t)4 * (size_t)sk->fo_total * (size_t)C * sizeof(double), ctx->stream) != hipSuccess)
+    if (hipMemsetAsync(ctx->loop.specw, 0, (size_t)4 * (size_t)sk->fo_total * (size_t)C * sizeof(double), ctx->stream) != hipSuccess)
       return bad(SI_ERR_HIP, ": hipMemsetAsync failed");
-    ctx->spec_chains = C;
-    ctx->spec_fo = sk->fo_total;
+    ctx->loop.spec_chains = C;
+    ctx->loop.spec_fo = sk->fo_total;
   }
-  if (ctx->specperm_for != (const void*)sk) {
-    ctx->specperm_for = nullptr;
-    if (!ctx->d_specperm.alloc((size_t)N)) return bad(SI_ERR_NOMEM, ": allocation failed");
-    int* pp = ctx->d_specperm;
+  if (ctx->loop.specperm_for != (const void*)sk) {
+    ctx->loop.specperm_for = nullptr;
+    if (!ctx->loop.specperm.alloc((size_t)N)) return bad(SI_ERR_NOMEM, ": allocation failed");
+    int* pp = ctx->loop.specperm;
     void* pargs[] = {&pp};
     if (hipModuleLaunchKernel(sk->perm, (unsigned)((sk->max_wn + 255) / 256), 1, 1, 256, 1, 1, 0, ctx->stream, pargs, nullptr) != hipSuccess)
       return bad(SI_ERR_HIP, ": launch of the fragment-order permutation failed");
-    ctx->specperm_for = (const void*)sk;
+    ctx->loop.specperm_for = (const void*)sk;
   }
   return sk;
 }
@@ -217,18 +217,18 @@ static const SpecKernels* prepare_spec_loop(si_ctx* ctx, const RwmhCall& k, int 
 // chain, two bounded grid barriers per transition.  Same bits as the launch-per-step loop (tests/test_gpu_chain_grid.py).
 static int32_t rwmh_grid(si_ctx* ctx, const RwmhCall& k) {
   const int32_t C = k.C, M = ctx->iM;
-  if (!k.map_fits || !ctx->fused_ok || ctx->chain_mode != 1 || ctx->sigma_p > 0.0 || C > ctx->fw_slots || k.itr >= ((int64_t)1 << 24) ||
+  if (!k.map_fits || !ctx->setup.fused_ok || ctx->chain_mode != 1 || ctx->setup.sigma_p > 0.0 || C > ctx->fw.slots || k.itr >= ((int64_t)1 << 24) ||
       ctx->dec.on)   // (both grid loops, the run-time specialised one included, form W_swa + P z in their own K4)
     return SI_NOT_TAKEN;
   ChainGridArgs a{};
   const int L = (int)ctx->layers.size();
-  const int sf = ctx->fuse_tail ? dense_fused_slot_feats(ctx->layers[(size_t)L - 2].out) : 0;
+  const int sf = ctx->setup.fuse_tail ? dense_fused_slot_feats(ctx->layers[(size_t)L - 2].out) : 0;
   int nb = 0;
   size_t lds = 0;
   for (int cand : {1, 2, 4}) {   // the smallest tile whose grid is resident: one workgroup per CU
     const int64_t G = (ctx->B + 16 * cand - 1) / (16 * cand);
     if (G * C > ctx->num_cu) continue;
-    const size_t lf = chain_fused_plan(a.p, ctx->layers.data(), L, ctx->B, cand, ctx->fuse_tail, sf, ctx->fuse_slots);
+    const size_t lf = chain_fused_plan(a.p, ctx->layers.data(), L, ctx->B, cand, ctx->setup.fuse_tail, sf, ctx->fuse_slots);
     fused_fill_program(ctx, a.p);
     a.M = M;
     a.nblocks = ctx->sse_blocks;
@@ -246,25 +246,25 @@ static int32_t rwmh_grid(si_ctx* ctx, const RwmhCall& k) {
   const SpecKernels* sk = prepare_spec_loop(ctx, k, a.G, nb, sf, sa, &lds_spec, &rc);
   if (rc != SI_OK) return rc;
   const size_t sync_lines = sk ? (size_t)8 * (size_t)C + 1 : (size_t)C + 1;   // (the specialised loop shards each chain's counter over 8 lines)
-  if (!ctx->d_gridsync.reserve((size_t)32 * sync_lines)) return fail(ctx, SI_ERR_NOMEM, std::string(k.who) + ": allocation failed");
+  if (!ctx->loop.gridsync.reserve((size_t)32 * sync_lines)) return fail(ctx, SI_ERR_NOMEM, std::string(k.who) + ": allocation failed");
   fill_common_args(a, ctx, k);
-  a.wbuf = ctx->d_w; a.w_stride = pad_ld(ctx->iN);
-  a.ybuf = ctx->d_yhat; a.y_stride = (int64_t)ctx->out_dim * ctx->B;
-  a.cnt = ctx->d_gridsync; a.status = ctx->d_gridsync + (size_t)32 * (sync_lines - 1);
-  hipError_t e = hipMemsetAsync(ctx->d_gridsync, 0, (size_t)32 * sync_lines * sizeof(unsigned), ctx->stream);
+  a.wbuf = ctx->fw.w; a.w_stride = pad_ld(ctx->iN);
+  a.ybuf = ctx->fw.yhat; a.y_stride = (int64_t)ctx->out_dim * ctx->B;
+  a.cnt = ctx->loop.gridsync; a.status = ctx->loop.gridsync + (size_t)32 * (sync_lines - 1);
+  hipError_t e = hipMemsetAsync(ctx->loop.gridsync, 0, (size_t)32 * sync_lines * sizeof(unsigned), ctx->stream);
   if (e == hipSuccess) {
     const double fl = 2.0 * (double)ctx->iN * (double)ctx->B * (double)k.itr * C;
     ProfScope ps(ctx, SI_K_RWMH, fl, 0.0);
     if (sk) {
       fill_common_args(sa, ctx, k);
-      sa.perm = ctx->d_specperm;
-      sa.wbuf = ctx->d_specw; sa.w_stride = sk->fo_total;
-      sa.ybuf = ctx->d_specy; sa.y_stride = a.y_stride;
+      sa.perm = ctx->loop.specperm;
+      sa.wbuf = ctx->loop.specw; sa.w_stride = sk->fo_total;
+      sa.ybuf = ctx->loop.specy; sa.y_stride = a.y_stride;
       sa.cnt = a.cnt; sa.status = a.status;
       sa.M = M; sa.G = a.G; sa.B = (int)ctx->B; sa.nblocks = ctx->sse_blocks;
       void* gargs[] = {&sa};
       e = hipModuleLaunchKernel(sk->grid, (unsigned)(a.G * C), 1, 1, 256, 1, 1, (unsigned)lds_spec, ctx->stream, gargs, nullptr);
-      ctx->last_loop_spec = e == hipSuccess;
+      ctx->loop.last_loop_spec = e == hipSuccess;
     } else {
       e = launch_chain_grid(ctx->stream, a, nb, C, lds);
     }
@@ -287,7 +287,7 @@ static int32_t rwmh_grid(si_ctx* ctx, const RwmhCall& k) {
 struct WeightRing {
   si_ctx* ctx;
   const RwmhCall& k;
-  bool select_path;   // the proposal weights of ALL chains are still in d_w at accept time: one pass of launches carries them all
+  bool select_path;   // the proposal weights of ALL chains are still in fw.w at accept time: one pass of launches carries them all
   double* slot(int64_t t) const { return ctx->d_wring + (size_t)(t % SI_WRING) * (size_t)k.C * (size_t)pad_ld(ctx->iN); }
   hipError_t drain(int64_t u) const {   // sample u of every chain: pinned slot -> the caller's (pageable) N x itr x C array
     const int64_t N = ctx->iN;
@@ -307,9 +307,9 @@ struct WeightRing {
     {
       ProfScope ps(ctx, SI_K_RECON, 0.0, 16.0 * (double)N * C);
       if (select_path)
-        launch_weights_select(ctx->stream, ctx->d_accflag, ctx->d_w, ldw, t > 0 ? slot(t - 1) : nullptr, slot(t), ldw, N, C, ctx->num_cu);
+        launch_weights_select(ctx->stream, ctx->d_accflag, ctx->fw.w, ldw, t > 0 ? slot(t - 1) : nullptr, slot(t), ldw, N, C, ctx->num_cu);
       else  // more chains than one pass of launches carries: K4 on the current states (same kernel, same bits)
-        if (form_weights(ctx, ctx->d_zcur, C, slot(t), ldw) != SI_OK) return hipErrorOutOfMemory;
+        if (form_weights(ctx, ctx->chains.zcur, C, slot(t), ldw) != SI_OK) return hipErrorOutOfMemory;
     }
     e = hipEventRecord(ctx->ev_wcomp[r], ctx->stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream2, ctx->ev_wcomp[r], 0);
@@ -332,32 +332,32 @@ struct WeightRing {
 // transition is 3.3 ms of kernel time.
 static int32_t rwmh_per_step(si_ctx* ctx, const RwmhCall& k) {
   const int32_t C = k.C, M = ctx->iM;
-  double* const dZ = ctx->d_outZ;
-  double* const dlp = ctx->d_outlp;
+  double* const dZ = ctx->chains.outZ;
+  double* const dlp = ctx->chains.outlp;
   {
     ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-    launch_rwmh_init(ctx->stream, ctx->d_zcur, ctx->d_lpcur, ctx->d_nacc, ctx->d_steps, M, C);
+    launch_rwmh_init(ctx->stream, ctx->chains.zcur, ctx->chains.lpcur, ctx->chains.nacc, ctx->chains.steps, M, C);
   }
-  const WeightRing ring{ctx, k, k.W_out && C <= ctx->fw_slots};
+  const WeightRing ring{ctx, k, k.W_out && C <= ctx->fw.slots};
   int* const accflag = ring.select_path ? ctx->d_accflag.get() : nullptr;
-  const bool fused_tail = C <= ctx->fw_slots && !(ctx->sigma_p > 0.0) && ctx->chain_loop_enabled;
+  const bool fused_tail = C <= ctx->fw.slots && !(ctx->setup.sigma_p > 0.0) && ctx->chain_loop_enabled;
   const DensityView view = setup_view(ctx, /*defer_sse_final=*/fused_tail);   // the tail kernel sums the SSE block partials
   int32_t rc = SI_OK;
   hipError_t e = hipSuccess;
   for (int64_t t = 0; t < k.itr && rc == SI_OK && e == hipSuccess; ++t) {
     if (!fused_tail || t == 0) {
       ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-      launch_rwmh_propose(ctx->stream, ctx->d_zcur, ctx->d_zprop, M, C, k.sigma_z, k.seed, k.chain_id0, ctx->d_steps);
+      launch_rwmh_propose(ctx->stream, ctx->chains.zcur, ctx->chains.zprop, M, C, k.sigma_z, k.seed, k.chain_id0, ctx->chains.steps);
     }
     if ((rc = eval_density_all(ctx, view, C)) != SI_OK) break;
     {
       ProfScope ps(ctx, SI_K_RWMH, 0, 0);
       if (fused_tail)
-        launch_rwmh_tail(ctx->stream, ctx->d_ssepart, ctx->sse_blocks, ctx->d_sse, ctx->d_zcur, ctx->d_zprop, ctx->d_lpcur, ctx->d_nacc, M,
-                         C, k.c0, k.s2, k.sigma_z, k.seed, k.chain_id0, ctx->d_steps, dZ, dlp, k.itr, accflag, t + 1 < k.itr);
+        launch_rwmh_tail(ctx->stream, ctx->fw.ssepart, ctx->sse_blocks, ctx->chains.sse, ctx->chains.zcur, ctx->chains.zprop, ctx->chains.lpcur, ctx->chains.nacc, M,
+                         C, k.c0, k.s2, k.sigma_z, k.seed, k.chain_id0, ctx->chains.steps, dZ, dlp, k.itr, accflag, t + 1 < k.itr);
       else
-        launch_rwmh_accept(ctx->stream, ctx->d_zcur, ctx->d_zprop, ctx->d_lpcur, ctx->d_sse, ctx->d_nacc, M, C, k.c0, k.s2, k.seed,
-                           k.chain_id0, ctx->d_steps, dZ, dlp, k.itr, ctx->sigma_p > 0.0 ? ctx->d_wsq.get() : nullptr, prior_c0(ctx),
+        launch_rwmh_accept(ctx->stream, ctx->chains.zcur, ctx->chains.zprop, ctx->chains.lpcur, ctx->chains.sse, ctx->chains.nacc, M, C, k.c0, k.s2, k.seed,
+                           k.chain_id0, ctx->chains.steps, dZ, dlp, k.itr, ctx->setup.sigma_p > 0.0 ? ctx->chains.wsq.get() : nullptr, prior_c0(ctx),
                            prior_sp2(ctx), accflag);
     }
     if (k.W_out) e = ring.push(t);
@@ -378,18 +378,18 @@ static int32_t rwmh_per_step(si_ctx* ctx, const RwmhCall& k) {
 static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, double sigma_z, uint64_t seed, int32_t chain_id0,
                                 int32_t nchains, double* Z_out, double* lp_out, double* accept_rate_out, double* W_out) {
   CHECK_CTX(ctx);
-  ctx->last_density_spec = ctx->last_loop_spec = 0;   // (si_chain_kernel_info reports THIS call)
-  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_infer_setup first");
+  ctx->loop.last_density_spec = ctx->loop.last_loop_spec = 0;   // (si_chain_kernel_info reports THIS call)
+  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_infer_setup first");
   if (itr <= 0 || nchains <= 0 || chain_id0 < 0 || !(sigma_z > 0.0))
     return fail(ctx, SI_ERR_INVALID, std::string(who) + ": itr, nchains, sigma_z must be positive");
-  if (ctx->sw_Z) return fail(ctx, SI_ERR_STATE, std::string(who) + ": a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
+  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, std::string(who) + ": a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
   BIND(ctx);
   const int32_t C = nchains;
   int32_t rc = ensure_chains(ctx, C);
   if (rc != SI_OK) return rc;
   if (W_out && (rc = ensure_wstream(ctx, C)) != SI_OK) return rc;
   // the device-side output arrays stay with the ctx (grown on demand, released with the inference set-up)
-  if (!ctx->d_outZ.reserve((size_t)ctx->iM * itr * C) || !ctx->d_outlp.reserve((size_t)itr * C))
+  if (!ctx->chains.outZ.reserve((size_t)ctx->iM * itr * C) || !ctx->chains.outlp.reserve((size_t)itr * C))
     return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
   const double d = (double)ctx->out_dim * (double)ctx->B;
   const size_t wall_elems = (size_t)pad_ld(ctx->iN) * (size_t)itr * (size_t)C;
@@ -428,8 +428,8 @@ int32_t si_set_chain_loop(si_ctx* ctx, int32_t on) {
 
 int32_t si_chain_kernel_info(si_ctx* ctx, int32_t* density_specialised, int32_t* loop_specialised) {
   CHECK_CTX(ctx);
-  if (density_specialised) *density_specialised = ctx->last_density_spec;
-  if (loop_specialised) *loop_specialised = ctx->last_loop_spec;
+  if (density_specialised) *density_specialised = ctx->loop.last_density_spec;
+  if (loop_specialised) *loop_specialised = ctx->loop.last_loop_spec;
   return SI_OK;
 }
 
@@ -438,7 +438,7 @@ const char* si_chain_spec_message(si_ctx* ctx) { return ctx ? ctx->spec_message.
 int32_t si_rwmh_begin(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, int32_t chain_id0, int32_t nchains,
                       int64_t d_total) {
   CHECK_CTX(ctx);
-  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_rwmh_begin: call si_infer_setup first");
+  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, "si_rwmh_begin: call si_infer_setup first");
   if (itr <= 0 || nchains <= 0 || chain_id0 < 0 || !(sigma_z > 0.0) || d_total < 0)
     return fail(ctx, SI_ERR_INVALID, "si_rwmh_begin: itr, nchains, sigma_z must be positive");
   if (ctx->node.on && d_total > 0) return fail(ctx, SI_ERR_INVALID, "si_rwmh_begin: a data-sharded density (d_total > 0) is not available for NeuralODE models");
@@ -446,36 +446,36 @@ int32_t si_rwmh_begin(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, i
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   int32_t rc = ensure_chains(ctx, nchains);
   if (rc != SI_OK) return rc;
-  ctx->sw_Z.reset();
-  ctx->sw_lp.reset();
-  if (!ctx->sw_Z.alloc((size_t)ctx->iM * itr * nchains) || !ctx->sw_lp.alloc((size_t)itr * nchains)) {
-    ctx->sw_Z.reset();
-    ctx->sw_lp.reset();
+  ctx->chains.sw_Z.reset();
+  ctx->chains.sw_lp.reset();
+  if (!ctx->chains.sw_Z.alloc((size_t)ctx->iM * itr * nchains) || !ctx->chains.sw_lp.alloc((size_t)itr * nchains)) {
+    ctx->chains.sw_Z.reset();
+    ctx->chains.sw_lp.reset();
     return fail(ctx, SI_ERR_NOMEM, "si_rwmh_begin: output allocation failed");
   }
   ctx->sw_itr = itr; ctx->sw_sigma_z = sigma_z; ctx->sw_seed = seed; ctx->sw_chain0 = chain_id0; ctx->sw_C = nchains;
   ctx->sw_d = d_total > 0 ? (double)d_total : (double)ctx->out_dim * (double)ctx->B;
   ctx->sw_next = 0;
   ctx->sw_evaluated = false;
-  launch_rwmh_init(ctx->stream, ctx->d_zcur, ctx->d_lpcur, ctx->d_nacc, ctx->d_steps, ctx->iM, nchains);
+  launch_rwmh_init(ctx->stream, ctx->chains.zcur, ctx->chains.lpcur, ctx->chains.nacc, ctx->chains.steps, ctx->iM, nchains);
   SI_HIP(ctx, hipGetLastError());
   return SI_OK;
 }
 
 int32_t si_rwmh_step_eval(si_ctx* ctx, double* sse_local_out) {
   CHECK_CTX(ctx);
-  if (!ctx->sw_Z || ctx->sw_next >= ctx->sw_itr || ctx->sw_evaluated)
+  if (!ctx->chains.sw_Z || ctx->sw_next >= ctx->sw_itr || ctx->sw_evaluated)
     return fail(ctx, SI_ERR_STATE, "si_rwmh_step_eval: call si_rwmh_begin first / accept the pending step / chain finished");
   BIND(ctx);
   const int32_t C = ctx->sw_C;
-  launch_rwmh_propose(ctx->stream, ctx->d_zcur, ctx->d_zprop, ctx->iM, C, ctx->sw_sigma_z, ctx->sw_seed, ctx->sw_chain0,
-                      ctx->d_steps);
+  launch_rwmh_propose(ctx->stream, ctx->chains.zcur, ctx->chains.zprop, ctx->iM, C, ctx->sw_sigma_z, ctx->sw_seed, ctx->sw_chain0,
+                      ctx->chains.steps);
   {
-    const int32_t rc = eval_density_all(ctx, setup_view(ctx), C);   // (the deferred SSE stage off: d_sse goes to the caller)
+    const int32_t rc = eval_density_all(ctx, setup_view(ctx), C);   // (the deferred SSE stage off: chains.sse goes to the caller)
     if (rc != SI_OK) return rc;
   }
   if (sse_local_out) {  // NULL: the partial sums stay on the device (si_rwmh_sse_ptr) -- no copy, no synchronisation
-    SI_HIP(ctx, hipMemcpyAsync(sse_local_out, ctx->d_sse, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SI_HIP(ctx, hipMemcpyAsync(sse_local_out, ctx->chains.sse, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   ctx->sw_evaluated = true;
@@ -484,17 +484,17 @@ int32_t si_rwmh_step_eval(si_ctx* ctx, double* sse_local_out) {
 
 int32_t si_rwmh_step_accept(si_ctx* ctx, const double* sse_total) {
   CHECK_CTX(ctx);
-  if (!ctx->sw_Z || !ctx->sw_evaluated) return fail(ctx, SI_ERR_STATE, "si_rwmh_step_accept: no evaluated step pending");
+  if (!ctx->chains.sw_Z || !ctx->sw_evaluated) return fail(ctx, SI_ERR_STATE, "si_rwmh_step_accept: no evaluated step pending");
   BIND(ctx);
   const int32_t C = ctx->sw_C;
   if (sse_total) {  // NULL: the device buffer of si_rwmh_sse_ptr already holds the totals (all-reduced in place)
-    SI_HIP(ctx, hipMemcpyAsync(ctx->d_sse, sse_total, (size_t)C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    SI_HIP(ctx, hipMemcpyAsync(ctx->chains.sse, sse_total, (size_t)C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // sse_total is caller-owned
   }
   const double c0 = lik_c0(ctx, ctx->sw_d), s2 = lik_s2(ctx);
-  launch_rwmh_accept(ctx->stream, ctx->d_zcur, ctx->d_zprop, ctx->d_lpcur, ctx->d_sse, ctx->d_nacc, ctx->iM, C, c0, s2,
-                     ctx->sw_seed, ctx->sw_chain0, ctx->d_steps, ctx->sw_Z, ctx->sw_lp, ctx->sw_itr,
-                     ctx->sigma_p > 0.0 ? ctx->d_wsq : nullptr, prior_c0(ctx), prior_sp2(ctx));
+  launch_rwmh_accept(ctx->stream, ctx->chains.zcur, ctx->chains.zprop, ctx->chains.lpcur, ctx->chains.sse, ctx->chains.nacc, ctx->iM, C, c0, s2,
+                     ctx->sw_seed, ctx->sw_chain0, ctx->chains.steps, ctx->chains.sw_Z, ctx->chains.sw_lp, ctx->sw_itr,
+                     ctx->setup.sigma_p > 0.0 ? ctx->chains.wsq : nullptr, prior_c0(ctx), prior_sp2(ctx));
   SI_HIP(ctx, hipGetLastError());
   ctx->sw_next += 1;
   ctx->sw_evaluated = false;
@@ -503,8 +503,8 @@ int32_t si_rwmh_step_accept(si_ctx* ctx, const double* sse_total) {
 
 int32_t si_rwmh_sse_ptr(si_ctx* ctx, double** sse_dev_out, int32_t* nchains_out) {
   CHECK_CTX(ctx);
-  if (!ctx->sw_Z) return fail(ctx, SI_ERR_STATE, "si_rwmh_sse_ptr: call si_rwmh_begin first");
-  if (sse_dev_out) *sse_dev_out = ctx->d_sse;
+  if (!ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_rwmh_sse_ptr: call si_rwmh_begin first");
+  if (sse_dev_out) *sse_dev_out = ctx->chains.sse;
   if (nchains_out) *nchains_out = ctx->sw_C;
   return SI_OK;
 }
@@ -513,8 +513,8 @@ int32_t si_rwmh_abort(si_ctx* ctx) {
   CHECK_CTX(ctx);
   BIND(ctx);
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->sw_Z.reset();
-  ctx->sw_lp.reset();
+  ctx->chains.sw_Z.reset();
+  ctx->chains.sw_lp.reset();
   ctx->sw_evaluated = false;
   ctx->sw_next = ctx->sw_itr = 0;
   return SI_OK;
@@ -522,18 +522,18 @@ int32_t si_rwmh_abort(si_ctx* ctx) {
 
 int32_t si_rwmh_end(si_ctx* ctx, double* Z_out, double* lp_out, double* accept_rate_out) {
   CHECK_CTX(ctx);
-  if (!ctx->sw_Z || ctx->sw_next != ctx->sw_itr || ctx->sw_evaluated)
+  if (!ctx->chains.sw_Z || ctx->sw_next != ctx->sw_itr || ctx->sw_evaluated)
     return fail(ctx, SI_ERR_STATE, "si_rwmh_end: the chain is not complete");
   BIND(ctx);
   const int32_t C = ctx->sw_C, M = ctx->iM;
   const int64_t itr = ctx->sw_itr;
   std::vector<int64_t> nacc((size_t)C);
-  if (Z_out) SI_HIP(ctx, hipMemcpyAsync(Z_out, ctx->sw_Z, (size_t)M * itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (lp_out) SI_HIP(ctx, hipMemcpyAsync(lp_out, ctx->sw_lp, (size_t)itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  SI_HIP(ctx, hipMemcpyAsync(nacc.data(), ctx->d_nacc, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (Z_out) SI_HIP(ctx, hipMemcpyAsync(Z_out, ctx->chains.sw_Z, (size_t)M * itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (lp_out) SI_HIP(ctx, hipMemcpyAsync(lp_out, ctx->chains.sw_lp, (size_t)itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(nacc.data(), ctx->chains.nacc, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->sw_Z.reset();
-  ctx->sw_lp.reset();
+  ctx->chains.sw_Z.reset();
+  ctx->chains.sw_lp.reset();
   accept_rates(nacc, itr, accept_rate_out);
   return SI_OK;
 }
@@ -545,7 +545,7 @@ int32_t si_rwmh_end(si_ctx* ctx, double* Z_out, double* lp_out, double* accept_r
 // array (its first-touch page faults are spread over those threads too; a MADV_HUGEPAGE hint was tried and gained nothing).  A plain hipMemcpy into pageable memory does the last two steps on one thread: 0.79 ms per 8.4 MB sample.
 int32_t si_reconstruct(si_ctx* ctx, const double* Z, int64_t C, double* W_out) {
   CHECK_CTX(ctx);
-  if (!ctx->i_ready) return fail(ctx, SI_ERR_STATE, "si_reconstruct: call si_infer_setup first");
+  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, "si_reconstruct: call si_infer_setup first");
   if (!Z || C <= 0 || !W_out) return fail(ctx, SI_ERR_INVALID, "si_reconstruct: bad argument");
   BIND(ctx);
   const int64_t N = ctx->iN, ldw = pad_ld(N);

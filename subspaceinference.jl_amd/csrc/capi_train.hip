@@ -3,10 +3,11 @@
 //     gs = gradient(ps) do training_loss = cost(model, d...) end ;  Flux.update!(opt, ps, gs)
 // for `cost = (m, x, y) -> Flux.Losses.mse(m(x), y)` and opt in {Descent, Momentum, ADAM} (Flux 0.11.2 semantics:
 // Float32 parameters and Float32 optimiser state, Float64 arithmetic because the data are Float64).  The weights never
-// leave the GPU: si_train_push feeds K1 from the device-resident Float32 vector.  The gradient is one of the value-and-gradient
-// passes shared with si_logdensity_grad: dense_value_and_grad_f64 (capi.hip), dense_value_and_grad_f32 (below), net_value_and_grad
-// (capi_net.hip), each with the mse scale -2 / d -- or, after si_train_set_cost, with the tail of another cost (kernels_cost.hip) in
-// place of its launch_delta_out; or a NeuralODE's (si_train_setup_node, below).
+// leave the GPU: si_train_push feeds K1 from the device-resident Float32 vector.  The gradient is the value-and-gradient pass
+// shared with si_logdensity_grad -- one workspace (SweepWs, sized by sweep_ws_alloc) and one dispatch (chain_value_and_grad,
+// capi.hip) over dense_value_and_grad_f64, dense_value_and_grad_f32 (below) and net_value_and_grad (capi_net.hip) -- with the mse
+// scale -2 / d or, after si_train_set_cost, with the tail of another cost (kernels_cost.hip) in place of its launch_delta_out; or
+// a NeuralODE's (si_train_setup_node, below).  The step keeps the batch, the widened weights, net_input per batch and grad_ready.
 // One step is: the batch (train_batch), the gradient by the set-up's route (TrainState::route: train_gradient, node_gradient), the
 // update (optimiser_update.h: optimiser_kernel here, fused into the tail kernel on the NeuralODE route).
 #include <algorithm>
@@ -77,28 +78,6 @@ double train_denominator(const TrainState* t, int64_t nb) {
 }
 
 // ---- value and gradient in fp32 (dense_forward<float> + the fp32 reverse sweep), shared by the training step and si_logdensity_grad
-bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const si_layer* layers, int L, bool fuse_tail, int64_t N, int32_t in_dim, int32_t out_dim,
-                     int64_t Bmax) {
-  size_t maxpart32 = 1, maxwt = 1, maxin = (size_t)in_dim, maxw = 1;
-  for (int l = 0; l < L; ++l) {
-    maxpart32 = std::max(maxpart32, backward_weight_f32_part_elems(layers[l].out, layers[l].in, Bmax, ctx->num_cu));
-    maxwt = std::max(maxwt, (size_t)layers[l].out * (size_t)layers[l].in);
-    maxin = std::max(maxin, (size_t)layers[l].in);
-    maxw = std::max(maxw, (size_t)layers[l].out);
-  }
-  const size_t wide = std::max(maxin, maxw);
-  ws.hs32 = std::vector<DevBuf<float>>((size_t)L);
-  bool ok = ws.delta32[0].alloc(maxw * (size_t)Bmax) && ws.delta32[1].alloc(maxw * (size_t)Bmax) && ws.gw32.alloc((size_t)pad_ld(N)) &&
-            ws.wt32.alloc(maxwt) && ws.zero32.alloc(wide) && ws.part32.alloc(maxpart32) &&
-            ws.rspart64.alloc(rowsum_f32_part_elems((int)wide)) && ws.yhat64.alloc((size_t)out_dim * (size_t)Bmax) &&
-            (!fuse_tail || ws.tailpart64.alloc(tail_bwd_f32_part_elems(layers[L - 1].out, layers[L - 1].in)));
-  for (int l = 0; l < L && ok; ++l)   // (a fused head's own output lives in yhat64)
-    if (!(fuse_tail && l == L - 1)) ok = ws.hs32[(size_t)l].alloc((size_t)layers[l].out * (size_t)Bmax);
-  if (ok) ok = hipMemsetAsync(ws.zero32, 0, wide * sizeof(float), ctx->stream) == hipSuccess;
-  if (!ok) ws = SweepF32Ws();
-  return ok;
-}
-
 int32_t dense_value_and_grad_f32(Ctx* ctx, hipStream_t st, const DenseSweepF32& s) {
   SweepF32Ws& ws = *s.ws;
   const size_t nl = s.nl;
@@ -183,7 +162,7 @@ static int32_t train_setup_begin(si_ctx* ctx, TrainRoute route, const si_layer* 
   t->N = N; t->Btot = B_total; t->Bmax = batch_max; t->in_dim = in_dim; t->out_dim = out_dim;
   o.kind = opt_kind; o.eta = eta; o.p1 = p1; o.p2 = p2; o.bp1 = p1; o.bp2 = p2;  // ADAM: beta powers start at beta
   const size_t bm = (size_t)batch_max, nx = (size_t)in_dim * (size_t)B_total;
-  ok = (route == TrainRoute::DenseF32 ? t->f32.X.alloc(nx) && t->f32.Xb.alloc((size_t)in_dim * bm) : t->X.alloc(nx) && t->Xb.alloc((size_t)in_dim * bm)) &&
+  ok = (route == TrainRoute::DenseF32 ? t->X32.alloc(nx) && t->Xb32.alloc((size_t)in_dim * bm) : t->X.alloc(nx) && t->Xb.alloc((size_t)in_dim * bm)) &&
        t->Y.alloc((size_t)out_dim * (size_t)B_total) && t->Yb.alloc((size_t)out_dim * bm) && b.idx.alloc(bm) && b.pin[0].alloc(bm) &&
        b.pin[1].alloc(bm) && b.ev[0].create() && b.ev[1].create() && o.w32.alloc((size_t)N) && o.m32.alloc((size_t)N) &&
        o.v32.alloc((size_t)N) && o.w64.alloc((size_t)pad_ld(N)) && o.gw.alloc((size_t)pad_ld(N)) && t->sse.alloc(1);
@@ -216,19 +195,7 @@ static int32_t train_setup_impl(si_ctx* ctx, const si_layer* layers, int32_t L, 
     const int32_t prc = net_plan(ctx, "si_train_setup", layers, L, N, in_dim, out_dim, plan);
     if (prc != SI_OK) return prc;
   }
-  int64_t maxw = plan.max_elems;
-  size_t maxpart = 1;
-  if (!plan.has_conv) {
-    maxw = 1;
-    for (int l = 0; l < L; ++l) {
-      const si_layer& ly = layers[l];
-      maxw = std::max<int64_t>(maxw, ly.out);
-      maxpart = std::max(maxpart, backward_weight_part_elems(ly.out, ly.in, batch_max, ctx->num_cu));
-    }
-  }
-  const bool fuse_tail = !plan.has_conv && (L >= 2) && layers[L - 1].out <= SI_FUSE_MAX_OUT &&
-                         layers[L - 1].act < SI_ACT_LEAKYRELU && layers[L - 2].act < SI_ACT_LEAKYRELU;
-  if (fuse_tail) maxpart = std::max(maxpart, tail_bwd_part_elems(layers[L - 1].out, layers[L - 1].in));
+  const bool fuse_tail = head_fused(plan, layers, L);
   if (f32 && plan.has_conv)
     return fail(ctx, SI_ERR_INVALID, "si_train_setup_ex: compute_dtype = SI_F32 is implemented for Dense chains; Conv / MaxPool / flatten chains train in SI_F64");
   const TrainRoute route = plan.has_conv ? TrainRoute::Conv : f32 ? TrainRoute::DenseF32 : TrainRoute::DenseF64;
@@ -236,32 +203,15 @@ static int32_t train_setup_impl(si_ctx* ctx, const si_layer* layers, int32_t L, 
   const int32_t rcb = train_setup_begin(ctx, route, layers, L, N, in_dim, out_dim, B_total, batch_max, opt_kind, eta, p1, p2, ok);
   if (rcb != SI_OK) return rcb;
   TrainState* t = ctx->train;
-  TrainDenseWs& dn = t->dense;
-  TrainConvWs& cv = t->conv;
   t->sse_blocks = sse_num_blocks((int64_t)out_dim * batch_max, ctx->num_cu);
-  dn.fuse_tail = fuse_tail;
-  dn.fuse_slots = fuse_tail ? dense_fused_slots(layers[L - 2].out) : 0;
+  t->fuse_tail = fuse_tail;
+  t->fuse_slots = fuse_tail ? dense_fused_slots(layers[L - 2].out) : 0;
   if (f32 && fuse_tail)   // (w32 is 256-byte aligned: a layer's W is 16-byte aligned iff w_off % 4 == 0)
-    dn.fuse_slots = std::max(dn.fuse_slots, dense_f32_fused_slots(layers[L - 2].out, layers[L - 2].in, layers[L - 2].w_off % 4 == 0));
-  dn.hs = std::vector<DevBuf<double>>((size_t)L);
-  cv.plan = plan;
-  cv.pidx = std::vector<DevBuf<uint8_t>>((size_t)L);
-  cv.scratch.pidx = cv.pidx.data();
-  size_t nb = 1, nr = 1, nw = 1, nd = 1;
-  if (plan.has_conv) net_scratch_sizes(plan, batch_max, ctx->num_cu, &nb, &nr, &nw, &nd);
-  ok = ok && t->ssepart.alloc((size_t)t->sse_blocks) && (!fuse_tail || dn.part.alloc((size_t)dn.fuse_slots * out_dim * batch_max)) &&
-       (!plan.has_conv || (cv.wpack.alloc(plan.wpack_elems) && cv.scratch.bwpart.alloc(nb) && cv.scratch.rspart.alloc(nr) &&
-                           cv.scratch.wt.alloc(nw) && cv.scratch.dbtmp.alloc(nd))) &&
-       (!plan.input_spatial || cv.Xc.alloc((size_t)plan.in_elems * batch_max)) &&
-       (f32 ? sweep_f32_alloc(ctx, t->f32.ws, layers, L, fuse_tail, N, in_dim, out_dim, batch_max)
-            : dn.delta[0].alloc((size_t)maxw * batch_max) && dn.delta[1].alloc((size_t)maxw * batch_max) && dn.bwpart.alloc(maxpart) &&
-                  dn.rspart.alloc((size_t)rowsum_chunks() * maxw));
-  for (int l = 0; l < L && ok && !f32; ++l) {
-    if (plan.has_conv && net_grad_fused(plan, (size_t)l))   // Conv + MaxPool as one kernel: a byte index instead of the activation
-      ok = cv.pidx[(size_t)l].alloc(net_pidx_bytes(plan, (size_t)l, batch_max));
-    else
-      ok = dn.hs[(size_t)l].alloc((size_t)plan.L[(size_t)l].out_elems * batch_max);
-  }
+    t->fuse_slots = std::max(t->fuse_slots, dense_f32_fused_slots(layers[L - 2].out, layers[L - 2].in, layers[L - 2].w_off % 4 == 0));
+  t->plan = plan;
+  ok = ok && t->ssepart.alloc((size_t)t->sse_blocks) && (!fuse_tail || t->part.alloc((size_t)t->fuse_slots * out_dim * batch_max)) &&
+       (!plan.has_conv || t->wpack.alloc(plan.wpack_elems)) && (!plan.input_spatial || t->Xc.alloc((size_t)plan.in_elems * batch_max)) &&
+       sweep_ws_alloc(ctx, t->sweep, layers, L, plan, fuse_tail, N, in_dim, out_dim, batch_max, f32);
   if (!ok) return train_setup_failed(ctx, SI_ERR_NOMEM, "si_train_setup: device allocation failed");
   // the data in the element type the step computes in (X) / sums the loss in (Y: fp64 always); one conversion at set-up where
   // the caller's type differs (Float32 -> Float64 is exact; Float64 -> Float32 rounds once, as `Float32.(X)` would)
@@ -272,9 +222,9 @@ static int32_t train_setup_impl(si_ctx* ctx, const si_layer* layers, int32_t L, 
   if ((x_conv || y_conv) && !stage.alloc(std::max(nx, ny) * esz))
     return train_setup_failed(ctx, SI_ERR_NOMEM, "si_train_setup: device allocation failed");
   hipStream_t st = ctx->stream;
-  hipError_t e = hipMemcpyAsync(x_conv ? (void*)stage.get() : f32 ? (void*)t->f32.X.get() : (void*)t->X.get(), Xv, nx * esz, hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(x_conv ? (void*)stage.get() : f32 ? (void*)t->X32.get() : (void*)t->X.get(), Xv, nx * esz, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && x_conv) {
-    if (f32) launch_convert(st, reinterpret_cast<const double*>(stage.get()), (int64_t)nx, t->f32.X.get(), ctx->num_cu);
+    if (f32) launch_convert(st, reinterpret_cast<const double*>(stage.get()), (int64_t)nx, t->X32.get(), ctx->num_cu);
     else launch_widen_f32_to_f64(st, reinterpret_cast<const float*>(stage.get()), (int64_t)nx, t->X, ctx->num_cu);
   }
   if (e == hipSuccess && y_conv) e = hipStreamSynchronize(st);   // (the staging buffer is reused)
@@ -463,7 +413,7 @@ static int32_t train_batch(si_ctx* ctx, const char* who, const int64_t* idx, int
   }
   SI_HIP(ctx, hipSetDevice(ctx->device));
   if (prof) prof->emplace(ctx, SI_K_SSE, 0.0, 0.0);
-  v = TrainBatchView{t->X, t->f32.X, t->Y};
+  v = TrainBatchView{t->X, t->X32, t->Y};
   if (in_order) return SI_OK;
   const int s = b.slot;
   b.slot ^= 1;
@@ -473,11 +423,11 @@ static int32_t train_batch(si_ctx* ctx, const char* who, const int64_t* idx, int
   SI_HIP(ctx, hipEventRecord(b.ev[s], ctx->stream));
   b.busy[s] = true;
   if (t->route == TrainRoute::DenseF32)
-    launch_gather_cols(ctx->stream, t->f32.X.get(), t->in_dim, b.idx.get(), nb, t->f32.Xb.get(), ctx->num_cu);
+    launch_gather_cols(ctx->stream, t->X32.get(), t->in_dim, b.idx.get(), nb, t->Xb32.get(), ctx->num_cu);
   else
     launch_gather_cols(ctx->stream, t->X.get(), t->in_dim, b.idx.get(), nb, t->Xb.get(), ctx->num_cu);
   launch_gather_cols(ctx->stream, t->Y.get(), t->out_dim, b.idx.get(), nb, t->Yb.get(), ctx->num_cu);
-  v = TrainBatchView{t->Xb, t->f32.Xb, t->Yb};
+  v = TrainBatchView{t->Xb, t->Xb32, t->Yb};
   return SI_OK;
 }
 
@@ -532,41 +482,21 @@ static int32_t train_gradient(si_ctx* ctx, const char* who, const int64_t* idx, 
   if (!t) return fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_train_setup first");
   if (t->route == TrainRoute::Node) return node_gradient(ctx, who, idx, nb, node_apply);
   TrainOpt& o = t->opt;
-  TrainDenseWs& dn = t->dense;
   TrainBatchView v;
   const int32_t rcb = train_batch(ctx, who, idx, nb, v);
   if (rcb != SI_OK) return rcb;
   hipStream_t st = ctx->stream;
-  const int64_t N = t->N;
-  const size_t nl = t->layers.size();
-  launch_widen_f32_to_f64(st, o.w32, N, o.w64, ctx->num_cu);
-  const int sse_blocks = sse_num_blocks((int64_t)t->out_dim * nb, ctx->num_cu);
-  const double scale = -2.0 / d_total;   // d mse / d yhat = 2 (yhat - y) / d
+  launch_widen_f32_to_f64(st, o.w32, t->N, o.w64, ctx->num_cu);
+  const NetPlan& p = t->plan;
+  if (p.input_spatial) net_input(ctx, p, v.X, t->Xc, nb);
   const CostTail tail{t->cost, t->cost_param, 1.0 / d_total, t->costpart};
-  const CostTail* cost = t->cost != SI_COST_MSE ? &tail : nullptr;
-  int32_t rc = SI_OK;
-  if (t->route == TrainRoute::DenseF32) {
-    // ---- the step in the caller's precision: a Float32 model on Float32 data is a Float32 Zygote pass in the reference
-    // (src/subspace_construction.jl:39-43).  fp32 operands and activations on v_mfma_f32_32x32x2_f32; fp64 for the head's
-    // partial sums, the loss and every sum over the batch (rounded once into the Float32 gradient).
-    DenseSweepF32 sw{t->layers.data(), nl, dn.fuse_tail, o.w32, o.w64, v.X32, v.Y, &t->f32.ws, dn.part, t->ssepart, t->sse, sse_blocks, nb, N,
-                     scale, cost};
-    if ((rc = dense_value_and_grad_f32(ctx, st, sw)) != SI_OK) return rc;
-    // the gradient as the optimiser and the data-parallel all-reduce see it: fp64 words holding the Float32 values
-    launch_widen_f32_to_f64(st, t->f32.ws.gw32, N, o.gw, ctx->num_cu);
-  } else if (t->route == TrainRoute::Conv) {
-    // chains with Conv / MaxPool / flatten layers: the generic forward / reverse sweep of capi_net.hip
-    const NetPlan& p = t->conv.plan;
-    if (p.input_spatial) net_input(ctx, p, v.X, t->conv.Xc, nb);
-    const NetValueGrad vg{&p, o.w64, p.input_spatial ? t->conv.Xc.get() : v.X, v.Y, nb, dn.hs.data(), t->conv.wpack, t->ssepart, sse_blocks, t->sse,
-                          {dn.delta[0], dn.delta[1]}, o.gw, &t->conv.scratch, N, scale, 0.0, cost};
-    if ((rc = net_value_and_grad(ctx, vg)) != SI_OK) return rc;
-  } else {
-    const DenseValueGrad vg{{t->layers.data(), nl, dn.fuse_tail, o.w64, v.X, dn.hs.data(), {dn.delta[0], dn.delta[1]}, o.gw, dn.rspart,
-                             dn.bwpart, nb},
-                            v.Y, dn.fuse_slots, dn.part, t->ssepart, t->sse, sse_blocks, N, scale, false, cost};
-    if ((rc = dense_value_and_grad_f64(ctx, st, vg)) != SI_OK) return rc;
-  }
+  // (DenseF32: a Float32 model on Float32 data is a Float32 Zygote pass in the reference, src/subspace_construction.jl:39-43)
+  const ChainValueGrad in{t->layers.data(), t->layers.size(), &p, t->fuse_tail, o.w64, o.w32, v.X, t->Xc, v.X32, v.Y, nb, t->N,
+                          t->part, t->fuse_slots, t->ssepart, t->sse, sse_num_blocks((int64_t)t->out_dim * nb, ctx->num_cu), o.gw,
+                          t->wpack, -2.0 / d_total /* d mse / d yhat = 2 (yhat - y) / d */, t->cost != SI_COST_MSE ? &tail : nullptr,
+                          false, 0.0};
+  const int32_t rc = chain_value_and_grad(ctx, st, t->sweep, in);
+  if (rc != SI_OK) return rc;
   SI_HIP(ctx, hipGetLastError());
   o.grad_ready = true;
   return SI_OK;

@@ -70,16 +70,29 @@ struct NetPlan {
 };
 struct NetScratch {             // reverse-sweep workspaces (sized by net_scratch_sizes)
   DevBuf<double> bwpart, rspart, wt, dbtmp;
-  // gradient mode: pidx[l] = byte index tensor of conv layer l whose MaxPool ran fused with it (net_grad_fused), else empty
-  // (a view of the owning vector beside it: TrainConvWs::pidx / InferState::d_pidx)
+  // gradient mode, a view of SweepWs::pidx: pidx[l] = byte index tensor of conv layer l whose MaxPool ran fused with it (net_grad_fused), else empty
   const DevBuf<uint8_t>* pidx = nullptr;
 };
-// workspace of one fp32 sweep at up to Bmax observations (sweep_f32_alloc; see dense_value_and_grad_f32 below)
+// workspace of one fp32 sweep at up to Bmax observations (see dense_value_and_grad_f32 below)
 struct SweepF32Ws {
   std::vector<DevBuf<float>> hs32;
   DevBuf<float> delta32[2];
   DevBuf<float> gw32, wt32, zero32, part32;
   DevBuf<double> rspart64, tailpart64, yhat64;
+};
+// The training step's gradient routes; the first three: those of every value-and-gradient pass through a Chain (chain_value_and_grad)
+enum class TrainRoute { DenseF64, DenseF32, Conv, Node };
+// What such a pass keeps between calls for up to Bmax observations, on the route its chain takes (the rest stays empty); sized
+// and allocated by sweep_ws_alloc (capi.hip) and nowhere else.
+struct SweepWs {
+  TrainRoute route = TrainRoute::DenseF64;
+  bool ready = false;                  // allocated in full
+  std::vector<DevBuf<double>> hs;      // DenseF64, Conv: post-activation output of every layer, out_elems x Bmax (empty where pidx[l] stands in)
+  DevBuf<double> delta[2];             // DenseF64, Conv: widest layer (Conv: largest activation) x Bmax
+  DevBuf<double> bwpart, rspart;       // DenseF64: split-K partials of dW (or the narrow head's), row-sum partials
+  SweepF32Ws f32;                      // DenseF32
+  NetScratch net;                      // Conv
+  std::vector<DevBuf<uint8_t>> pidx;   // Conv, per layer: window-index bytes of a Conv layer fused with its MaxPool (net_grad_fused)
 };
 
 // ---- training of the autoencoder on the device (si_ae_train_*; capi_ae_train.hip, kernels_ae_train.hip; autoencoder.py:
@@ -189,7 +202,7 @@ struct CtxCore {
   int64_t B = 0;
   double sigma_m = 1.0;
   int wsq_blocks = 0;
-  int64_t act_elems = 0, max_stored = 0;  // act_elems = pad_ld(max_stored * B): slot stride of d_act
+  int64_t act_elems = 0, max_stored = 0;  // act_elems = pad_ld(max_stored * B): slot stride of fw.act
   int fuse_slots = 0;
   int sse_blocks = 0;
   int main_layer = 0;
@@ -311,7 +324,7 @@ struct DecoderState {
 };
 
 // The NeuralODE route (si_infer_setup_node; reference src/space_inference.jl:96-101): the set-up's layers are the right-hand
-// side d -> ... -> d, d_X holds the initial states (d x f), d_Y the observed trajectories (d*S x f).  The kernel's arguments
+// side d -> ... -> d, setup.X holds the initial states (d x f), setup.Y the observed trajectories (d*S x f).  The kernel's arguments
 // (kernels_node.hip), by value:
 constexpr int SI_NODE_MAX_LAYERS = 8, SI_NODE_MAX_D = 8, SI_NODE_MAX_WIDTH = 256, SI_NODE_MAX_S = 4096, SI_NODE_MAX_STEPS = 1000000;
 constexpr int64_t SI_NODE_MAX_N = 8192;
@@ -405,7 +418,6 @@ struct CostTail {
   double inv_denom;   // 1 / (out * nb_total), SI_COST_LOGITCE: 1 / nb_total
   double* part;       // workgroup partials of the numerator (SI_COST_MAX_BLOCKS doubles)
 };
-enum class TrainRoute { DenseF64, DenseF32, Conv, Node };
 // batch indices travel through two pinned buffers (copy in, async H2D, event): a step never synchronises the stream, so the
 // caller's work between two steps (its next batch, the K1 push) overlaps the GPU's
 struct TrainBatch {
@@ -423,32 +435,14 @@ struct TrainOpt {
   double eta = 0.0, p1 = 0.0, p2 = 0.0, bp1 = 0.0, bp2 = 0.0;
   bool grad_ready = false;  // gw holds a gradient that has not been applied yet
 };
-struct TrainDenseWs {       // Dense chains in fp64 (dense_value_and_grad_f64); hs and delta also carry a Conv chain's sweep
-  std::vector<DevBuf<double>> hs;
-  DevBuf<double> delta[2];
-  DevBuf<double> bwpart, rspart;
-  bool fuse_tail = false;   // (both Dense routes) narrow head: folded into the epilogue of the layer in front of it
-  int fuse_slots = 0;
-  DevBuf<double> part;      // [fuse_slots][out_last][Bmax] partial head products
-};
-// compute_dtype = SI_F32 (Dense chains; reference src/subspace_construction.jl:39-43 with a Float32 model AND Float32 data):
-// fp32 data, activations, deltas and gradient; fp64 only for the loss, the head's partial sums and the sums over the batch
-struct TrainF32Ws {
-  DevBuf<float> X, Xb;
-  SweepF32Ws ws;            // kept outputs, deltas, gradient, scratch of the fp32 sweep
-};
-struct TrainConvWs {        // chains with Conv / MaxPool / flatten layers (net_value_and_grad, capi_net.hip)
-  NetPlan plan;
-  DevBuf<double> Xc, wpack;
-  NetScratch scratch;
-  std::vector<DevBuf<uint8_t>> pidx;   // per layer: window-index bytes of a Conv layer fused with its MaxPool (net_grad_fused)
-};
 struct TrainState {
   TrainRoute route = TrainRoute::DenseF64;
   std::vector<si_layer> layers;
   int64_t N = 0, Btot = 0, Bmax = 0;
   int32_t in_dim = 0, out_dim = 0;   // (Node: X = U0 (d x f), Y = the trajectories (d*S x f), in_dim = d, out_dim = d*S)
-  DevBuf<double> X, Y, Xb, Yb;       // the data and the gathered batch (DenseF32: X is f32.X)
+  DevBuf<double> X, Y, Xb, Yb;       // the data and the gathered batch (DenseF32: X is X32)
+  // compute_dtype = SI_F32 (Dense chains; reference src/subspace_construction.jl:39-43 with a Float32 model AND Float32 data):
+  DevBuf<float> X32, Xb32;           // fp32 data, activations, deltas, gradient; fp64 for the loss, the head's partials, the batch sums
   DevBuf<double> ssepart, sse;       // the loss word and its block partials
   int sse_blocks = 0;
   int cost = 0;                      // SI_COST_* (si_train_set_cost; every set-up starts with mse)
@@ -456,116 +450,122 @@ struct TrainState {
   DevBuf<double> costpart;           // workgroup partials of a cost other than mse
   TrainBatch batch;
   TrainOpt opt;
-  TrainDenseWs dense;                // what a route does not use stays empty
-  TrainF32Ws f32;
-  TrainConvWs conv;
+  bool fuse_tail = false;            // (both Dense routes) narrow head: folded into the epilogue of the layer in front of it
+  int fuse_slots = 0;
+  DevBuf<double> part;               // [fuse_slots][out_last][Bmax] partial head products
+  NetPlan plan;                      // Conv route (net_value_and_grad, capi_net.hip): X re-laid channel-fastest, the packed weights
+  DevBuf<double> Xc, wpack;
+  SweepWs sweep;                     // the Chain routes' reverse-sweep workspace for Bmax observations; what a route does not use stays empty
   NodeTrain node;
 };
 double train_denominator(const TrainState* t, int64_t nb);   // (capi_train.hip) what the cost's numerator of nb observations is divided by
 
-// ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops
+// ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops, grouped by the entry points
+// that allocate and use each part; a group that grows on demand carries its own capacity counter.  InferSetup: the set-up's data
+// and the chain's properties, written by infer_setup_common (sigma_p: si_infer_set_prior), read by everything
+struct InferSetup {
+  bool ready = false;
+  const double *swa = nullptr, *P = nullptr;   // device (P: ldP x M); borrowed (the construction's, the caller's) or the owned copies
+  DevBuf<double> swa_own, P_own, X, Y;         // W_swa / P when set from host; the data
+  double sigma_p = 0.0;           // > 0: the prior term the reference leaves dead is added (si_infer_set_prior; non-default)
+  bool fuse_tail = false;         // last layer folded into the epilogue of the layer in front of it (head_fused)
+  bool f32 = false;               // compute_dtype = SI_F32 (Dense chains): X rounded once (X32), weights once per evaluation, fp32 activations
+  int fuse_slots32 = 0;           // feature slots of the fp32 fused head (fuse_slots stays the fp64 path's count)
+  DevBuf<float> X32;
+  NetPlan plan;                   // chains with Conv / MaxPool / flatten layers take the generic path (capi_net.hip)
+  DevBuf<double> Xc;              // X re-laid channel-fastest (input_spatial)
+  bool fused_ok = false;          // narrow Dense chain: the chain set up is of the fused class
+};
+// Forward workspace of eval_density for `slots` chain slots: alloc_forward (1 at set-up; grown by ensure_chains for multi-chain calls)
+struct InferForward {
+  int slots = 0;
+  DevBuf<double> w, act[2];       // reconstructed weights, slots x pad_ld(N); ping-pong activations, slots x act_elems (maxwidth x B padded)
+  DevBuf<double> ssepart, wsqpart;   // block partials of the SSE (slots x sse_blocks) and of ||w||^2 for the prior (slots x wsq_blocks)
+  DevBuf<double> part, yhat;      // slots x [fuse slots][out_last][B] partial last-layer products; slots x out_dim x B, filled on request
+  DevBuf<float> w32, act32[2];    // (f32) slots x pad_ld(N), slots x act_elems
+  DevBuf<double> wpack;           // packed conv weights of the current evaluation (set-up; one chain at a time)
+  DevBuf<float> wpack32;          // the same in fp32 (compute_dtype = SI_F32 on a Conv chain)
+};
+// Gradient workspace of si_logdensity_grad: ensure_grad allocates it whole on the first call (ws.ready), drop_grad drops it whole
+struct InferGrad {
+  SweepWs ws;                     // the reverse sweep's, for the set-up's B observations
+  DevBuf<double> gw, ptgpart, gz; // gradient w.r.t. the weights, partials of P' g, gradient w.r.t. z (gw, gz: si_decode_vjp's too; ptgpart: capi_node.hip's)
+};
+// si_logdensity_grad_batch and StackedVgrad, fused route (kernels_chain_grad.hip): vgrad_ensure allocates it for `cap` points per pass
+struct InferStacked {
+  int cls = -1;                   // -1: not looked at yet; 0: the chain is not of the fused class; 1 / 2: it is, with batch tiles of 16 * cls
+  int cap = 0, last_fused = 0;    // (last_fused: si_grad_kernel_info)
+  DevBuf<double> z, w, part, ssepart, gw, lp, gz;
+};
+// Per-chain state of the density entry points and the RWMH samplers for `cap` chains (ensure_chains), the step-wise session
+// (si_rwmh_begin .. si_rwmh_end) and the device-side sample arrays that every sampler's call reserves and keeps
+struct InferChains {
+  int32_t cap = 0;
+  DevBuf<double> zcur, zprop, lpcur, sse;   // M x C twice, C twice
+  DevBuf<double> wsq;             // ||W_swa + P z_c||^2 per chain, only with the prior on
+  DevBuf<int64_t> nacc;           // C
+  DevBuf<uint64_t> steps;         // C: transition counter of every chain (device-resident)
+  DevBuf<double> sw_Z, sw_lp, outZ, outlp;   // sample / lp arrays: the session's; si_sample_*'s, kept (an allocation per call was 0.4 ms of 20 transitions)
+};
+// The narrow chain's one-launch kernels (capi_sample.hip; cgprog: infer_setup_common): the grid loop's buffers and those of the same
+// kernels specialised to the chain's shapes at run time (chain_spec_rtc.cpp), for spec_chains chains
+struct InferLoops {
+  DevBuf<unsigned> gridsync;      // grid loop: one 128-byte counter line per chain + the status line (size() = 32 words per line)
+  DevBuf<CgTileD> cgprog;         // the chain's tile program (chain_fused_program)
+  DevBuf<double> specw, specy;    // per chain: 4 weight vectors in fragment order ([parity][accepted, rejected]), 2 output vectors ([parity])
+  DevBuf<int> specperm;           // natural weight index -> fragment order
+  const void* specperm_for = nullptr;   // (the SpecKernels the permutation was generated by)
+  int spec_chains = 0, spec_fo = 0, last_density_spec = 0, last_loop_spec = 0;   // last_*: si_chain_kernel_info, did the last call run them
+};
+// si_sample_mala (capi_mala.hip), on top of the chain state: the accept counts and the device-side gradient samples
+struct InferMala {
+  int cap = 0;
+  DevBuf<int64_t> nacc;           // C
+  DevBuf<double> outG;            // M x itr x C, kept between calls like outZ (si_sample_hmc and si_sample_nuts use it too)
+  CallInfo info;                  // si_mala_kernel_info: what the last call took (likewise in the three groups below)
+};
+// si_sample_hmc (capi_hmc.hip, kernels_hmc.hip), on top of the chain state: the half-kicked momentum of the proposal, the metric
+// with its Welford window, the per-chain scalars (HmcChain) and the device-side alpha / eps / Minv samples
+struct InferHmc {
+  int cap = 0;
+  DevBuf<double> rh, minv, wmean, wm2;        // M x C each
+  DevBuf<HmcChain> chain;                     // C
+  DevBuf<int32_t> open;                       // 1: chains still searching / building (synced_round)
+  DevBuf<double> outalpha, outeps, outMinv;   // (itr+1) x C twice, M x (itr+1) x C; kept between calls like outZ
+  CallInfo info;
+};
+// si_sample_nuts (capi_nuts.hip, kernels_nuts.hip), on top of si_sample_hmc's state: both ends of the tree (z, r, g), the sum of its
+// momenta, the candidate (z, g), the stack of sub-tree summaries, the per-chain scalars, the device-side samples and the leaf log
+struct InferNuts {
+  int cap = 0;
+  DevBuf<double> zm, rm, gm, zq, rq, gq, rho, zc, gc, stack;   // M x C each; stack: 4 M x NUTS_MAX_DEPTH x C
+  DevBuf<NutsChain> tree;                               // C
+  DevBuf<int32_t> outdepth, outnleaf, outsel;           // (itr+1) x C each, kept between calls like outZ
+  DevBuf<double> outleaf;                               // (3M+1) x leaf_cap x C, only when asked for
+  CallInfo info;
+};
+// si_fit_advi (capi_advi.hip, kernels_advi.hip): theta = [mu; omega] of R runs, the optimiser's ring of squared gradients, the draws eta,
+// their points, values and gradients, the traces (grown on demand, kept; every call ends synchronised, so none is in use when replaced)
+struct InferAdvi {
+  DevBuf<double> theta, ring;     // 2M x R, W x 2M x R (component fastest, then slot)
+  DevBuf<double> eta, z, g, lp;   // M x S x R three times, S x R
+  DevBuf<double> trace, pts;      // 2M x (T+1) x R, M x S x T x R: only when asked for, kept between calls
+  CallInfo info;
+};
 struct InferState {
-  bool i_ready = false;
+  InferSetup setup;
   NodeState node;                 // on: the set-up is a NeuralODE's; the density integrates instead of evaluating a Chain
   DecoderState dec;               // set: every density entry point forms W_swa + decoder(z); the stored P is ignored
-  const double* i_swa = nullptr;  // device; borrowed (the construction's, the caller's) or d_iswa
-  const double* i_P = nullptr;    // device, ldP x M; likewise
-  DevBuf<double> d_iswa;          // owned copies when set from host
-  DevBuf<double> d_iP;
-  DevBuf<double> d_X;
-  DevBuf<double> d_Y;
-  double sigma_p = 0.0;          // > 0: the prior term the reference leaves dead is added (si_infer_set_prior; non-default)
-  DevBuf<double> d_wsq;          // ||W_swa + P z_c||^2 per chain (chains_cap), only with the prior on
-  DevBuf<double> d_wsqpart;      // its block partials (fw_slots x wsq_blocks)
-  // forward workspace: `fw_slots` chain slots (1 after si_infer_setup; grown by ensure_batch for multi-chain calls)
-  int fw_slots = 0;
-  DevBuf<double> d_w;          // reconstructed weights, fw_slots x pad_ld(N)
-  DevBuf<double> d_act[2];     // ping-pong activations, fw_slots x act_elems (maxwidth x B padded)
-  DevBuf<double> d_ssepart;    // per-block SSE partials, fw_slots x sse_blocks
-  bool fuse_tail = false;      // last layer folded into the epilogue of the layer in front of it
-  DevBuf<double> d_part;       // fw_slots x [slots][out_last][B] partial last-layer products
-  DevBuf<double> d_yhat;       // fw_slots x out_dim x B, only filled on request (si_forward)
-  // compute_dtype = SI_F32 (Dense chains): X rounded once, weights rounded once per evaluation (K4 writes both), fp32 activations
-  bool f32 = false;
-  int fuse_slots32 = 0;                      // feature slots of the fp32 fused head (fuse_slots stays the fp64 path's count)
-  DevBuf<float> d_X32;
-  DevBuf<float> d_w32;                       // fw_slots x pad_ld(N)
-  DevBuf<float> d_act32[2];                  // fw_slots x act_elems
-  // gradient workspace (allocated on the first si_logdensity_grad)
-  bool g_ready = false;
-  std::vector<DevBuf<double>> d_hs;   // post-activation output of every layer, out_l x B
-  DevBuf<double> d_delta[2];
-  DevBuf<double> d_gw;      // gradient w.r.t. the flat weight vector
-  DevBuf<double> d_bwpart;  // split-K partials of dW
-  DevBuf<double> d_rspart;  // row-sum partials
-  DevBuf<double> d_ptgpart;
-  DevBuf<double> d_gz;
-  SweepF32Ws g_ws32;        // compute_dtype = SI_F32: the fp32 sweep's workspace (si_logdensity_grad)
-  // chains with Conv / MaxPool / flatten layers (generic path, capi_net.hip)
-  NetPlan plan;
-  DevBuf<double> d_Xc;      // X re-laid channel-fastest (input_spatial)
-  DevBuf<double> d_wpack;   // packed conv weights of the current evaluation
-  DevBuf<float> d_wpack32;  // the same in fp32 (compute_dtype = SI_F32 on a Conv chain)
-  NetScratch g_scratch;
-  std::vector<DevBuf<uint8_t>> d_pidx;  // per layer: window-index bytes of a Conv layer fused with its MaxPool (gradient workspace)
-  // sampler state (device)
-  DevBuf<double> d_zcur;   // M x C
-  DevBuf<double> d_zprop;  // M x C
-  DevBuf<double> d_lpcur;  // C
-  DevBuf<double> d_sse;    // C
-  DevBuf<int64_t> d_nacc;  // C
-  DevBuf<uint64_t> d_steps;  // C: transition counter of every chain (device-resident)
-  int32_t chains_cap = 0;
-  DevBuf<double> sw_Z, sw_lp;     // step-wise sampler session (si_rwmh_begin .. si_rwmh_end): its sample / lp arrays
-  DevBuf<double> d_outZ, d_outlp;   // device-side sample / lp arrays of si_sample_rwmh*, kept between calls
-                                    // (a hipMalloc / hipFree pair per call was 0.4 ms of a 20-transition call)
-  bool fused_ok = false;            // narrow Dense chain: the chain set up is of the fused class (infer_setup_common)
-  DevBuf<unsigned> d_gridsync;      // grid loop: one 128-byte counter line per chain + the status line (size() = 32 words per line)
-  DevBuf<CgTileD> d_cgprog;         // the chain's tile program (chain_fused_program)
-  // the same two kernels specialised to the chain's shapes at run time (chain_spec_rtc.cpp); buffers of the specialised loop
-  DevBuf<double> d_specw;           // 4 weight vectors in fragment order per chain ([parity][accepted, rejected])
-  DevBuf<double> d_specy;           // 2 output vectors per chain ([parity])
-  DevBuf<int> d_specperm;           // natural weight index -> fragment order
-  const void* specperm_for = nullptr;   // (the SpecKernels the permutation was generated by)
-  int spec_chains = 0, spec_fo = 0;
-  int last_density_spec = 0, last_loop_spec = 0;   // si_chain_kernel_info: did the last density / sampling call run specialised kernels
-  // si_logdensity_grad_batch, fused route (kernels_chain_grad.hip): workspace for vg_cap points, allocated on the first call
-  int vg_class = -1;                // -1: not looked at yet; 0: the chain is not of the fused class; 1 / 2: it is, with batch tiles of 16 * vg_class
-  int vg_cap = 0;
-  DevBuf<double> d_vg_z, d_vg_w, d_vg_part, d_vg_ssepart, d_vg_gw, d_vg_lp, d_vg_gz;
-  int last_grad_fused = 0;          // si_grad_kernel_info
-  // si_sample_mala / si_sample_hmc / si_sample_nuts: the chains' state with the proposals' (pending points') values and gradients
-  // (ChainState: one for the three, every call rewrites all of it); its own buffers, so that the per-point gradient path may use
-  // d_zprop between two kernels.  On top of it MALA has the accept counts and the device-side gradient samples
-  ChainState chain_state;
-  int mala_cap = 0;
-  DevBuf<int64_t> d_mala_nacc;                               // C
-  DevBuf<double> d_outG;                                     // M x itr x C, kept between calls like d_outZ
-  CallInfo info_mala, info_hmc, info_nuts, info_advi;        // si_*_kernel_info: what the last call of each took
-  // si_sample_hmc (capi_hmc.hip, kernels_hmc.hip), on top of the chain state: the half-kicked momentum of the proposal, the metric
-  // with its Welford window, the per-chain scalars (HmcChain) and the device-side alpha / eps / Minv samples
-  int hmc_cap = 0;
-  DevBuf<double> d_hmc_rh, d_hmc_minv, d_hmc_wmean, d_hmc_wm2;     // M x C each
-  DevBuf<HmcChain> d_hmc_chain;                                    // C
-  DevBuf<int32_t> d_hmc_open;                                      // 1: chains still searching / building (synced_round)
-  DevBuf<double> d_outalpha, d_outeps, d_outMinv;                  // (itr+1) x C twice, M x (itr+1) x C; kept between calls like d_outZ
-  // si_sample_nuts (capi_nuts.hip, kernels_nuts.hip), on top of si_sample_hmc's state: both ends of the tree (z, r, g), the sum of its
-  // momenta, the candidate (z, g), the stack of sub-tree summaries (4 M doubles per entry, NUTS_MAX_DEPTH entries per chain), the
-  // per-chain scalars, the device-side depth / leaf count / selected leaf samples and, when asked for, the leaf log
-  int nuts_cap = 0;
-  DevBuf<double> d_nuts_zm, d_nuts_rm, d_nuts_gm, d_nuts_zq, d_nuts_rq, d_nuts_gq, d_nuts_rho, d_nuts_zc, d_nuts_gc;   // M x C each
-  DevBuf<double> d_nuts_stack;                                     // 4 M x NUTS_MAX_DEPTH x C
-  DevBuf<NutsChain> d_nuts_tree;                                   // C
-  DevBuf<int32_t> d_outdepth, d_outnleaf, d_outsel;                // (itr+1) x C each, kept between calls like d_outZ
-  DevBuf<double> d_outleaf;                                        // (3M+1) x leaf_cap x C, only when asked for
-  // si_fit_advi (capi_advi.hip, kernels_advi.hip): the state theta = [mu; omega] of R runs, the optimiser's ring of squared
-  // gradients, the step's draws eta with the points made from them, the points' values and gradients, and the device-side traces
-  // (grown on demand and kept between calls; every call ends synchronised, so none is in use when it is replaced)
-  DevBuf<double> d_advi_theta;                              // 2M x R
-  DevBuf<double> d_advi_ring;                                // W x 2M x R (component fastest, then slot)
-  DevBuf<double> d_advi_eta, d_advi_z, d_advi_g;             // M x S x R each
-  DevBuf<double> d_advi_lp;                                  // S x R
-  DevBuf<double> d_advi_trace, d_advi_pts;                   // 2M x (T+1) x R, M x S x T x R: only when asked for, kept between calls
+  InferForward fw;
+  InferGrad grad;
+  InferStacked vg;
+  InferChains chains;
+  InferLoops loop;
+  ChainState chain_state;         // si_sample_mala / _hmc / _nuts (its own buffers: the per-point gradient path uses chains.zprop between two kernels)
+  InferMala mala;
+  InferHmc hmc;
+  InferNuts nuts;
+  InferAdvi advi;
 };
 
 struct Ctx : CtxCore, ConstructState, InferState {};
@@ -779,8 +779,6 @@ int32_t dense_value_and_grad_f64(Ctx* ctx, hipStream_t st, const DenseValueGrad&
 // The same in fp32 (capi_train.hip; kernels_gemm_f32.hip + kernels_bwd_f32.hip): dense_forward<float> with every output kept, the
 // SSE (fp64), Delta_L, the fp32 reverse sweep; on return gw32 holds the gradient rounded to fp32 and *sse the sum of squared
 // errors.  Shared by the training step and si_logdensity_grad with compute_dtype = SI_F32.
-bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const si_layer* layers, int L, bool fuse_tail, int64_t N, int32_t in_dim, int32_t out_dim,
-                     int64_t Bmax);
 struct DenseSweepF32 {
   const si_layer* layers;
   size_t nl;

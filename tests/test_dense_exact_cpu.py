@@ -72,16 +72,18 @@ DISPATCH_TEXT = {
         "switch ((in + 15) / 16) { case 1: launch_panel_inst<1>(", "case 7: launch_panel_inst<7>(", "default: launch_panel_inst<8>(",
     ),
     "si_internal.h": ("constexpr int SI_FUSE_MAX_OUT = 4;", "constexpr int64_t LD_ALIGN = 64;", "int n = 1; int64_t w = 0, hin = 0, hout = 0, part = 0;"),
+    "capi_common.h": (   # head_fused: the one statement of the narrow-head rule
+        """return !plan.has_conv && (L >= 2) && layers[L - 1].out <= SI_FUSE_MAX_OUT &&
+           layers[L - 1].act < SI_ACT_LEAKYRELU && layers[L - 2].act < SI_ACT_LEAKYRELU;""",),
     "capi_infer.hip": (
-        """ctx->fuse_tail = !plan.has_conv && (L >= 2) && layers[L - 1].out <= SI_FUSE_MAX_OUT &&
-           layers[L - 1].act < SI_ACT_LEAKYRELU && layers[L - 2].act < SI_ACT_LEAKYRELU;""",
-        "for (int l = 0; l < (ctx->fuse_tail ? L - 2 : L); ++l) maxstored = std::max<int64_t>(maxstored, plan.L[(size_t)l].out_elems);",
+        "ctx->setup.fuse_tail = node_d == 0 && head_fused(plan, layers, L);",
+        "for (int l = 0; l < (ctx->setup.fuse_tail ? L - 2 : L); ++l) maxstored = std::max<int64_t>(maxstored, plan.L[(size_t)l].out_elems);",
         "ctx->act_elems = pad_ld(maxstored * B);",
-        "static constexpr int SI_FUSED_MAX_WIDTH = 256;", "if (ctx->fused_ok && ctx->chain_mode != 0 && !yhat_out) {",
+        "static constexpr int SI_FUSED_MAX_WIDTH = 256;", "if (ctx->setup.fused_ok && ctx->chain_mode != 0 && !yhat_out) {",
         "cb.n = nc; cb.w = ldw; cb.hout = v.act_elems;",
-        "ctx->d_part, ctx->d_yhat, ctx->act_elems, ctx->f32, defer_sse_final, true};",   # setup_view: the set-up's own stride and type
-        """const double per = (ctx->f32 ? 4.0 : 8.0) * 2.0 * (double)ctx->act_elems +
-           8.0 * ((pslots + 1.0) * (double)ctx->out_dim * (double)ctx->B + (ctx->f32 ? 1.5 : 1.0) * (double)pad_ld(ctx->iN) +
+        "ctx->fw.part, ctx->fw.yhat, ctx->act_elems, ctx->setup.f32, defer_sse_final, true};",   # setup_view: the set-up's own stride and type
+        """const double per = (ctx->setup.f32 ? 4.0 : 8.0) * 2.0 * (double)ctx->act_elems +
+           8.0 * ((pslots + 1.0) * (double)ctx->out_dim * (double)ctx->B + (ctx->setup.f32 ? 1.5 : 1.0) * (double)pad_ld(ctx->iN) +
            (double)ctx->sse_blocks);
            const double fit = std::floor(SI_BATCH_BYTES / per);
            return (int)std::max(1.0, std::min({(double)C, fit, 1024.0}));""",
@@ -194,8 +196,8 @@ DISPATCH_TEXT = {
            else
            launch_mul_dact_rowsum_f32(st, ws.delta32[cur ^ 1], ws.hs32[li - 1], ly.in, nb, lq.act, ws.delta32[cur ^ 1], ws.rspart64,
            ws.gw32 + lq.b_off);""",
-        "v = TrainBatchView{t->X, t->f32.X, t->Y}; if (in_order) return SI_OK;",   # A4: an in-order batch uses X in place (train_batch)
-        "const bool fuse_tail = !plan.has_conv && (L >= 2) && layers[L - 1].out <= SI_FUSE_MAX_OUT &&",
+        "v = TrainBatchView{t->X, t->X32, t->Y}; if (in_order) return SI_OK;",   # A4: an in-order batch uses X in place (train_batch)
+        "const bool fuse_tail = head_fused(plan, layers, L);",
     ),
 }
 

@@ -262,6 +262,26 @@ int32_t si_infer_setup_dev(si_ctx* ctx, const si_layer* layers, int32_t L, int64
  * reference's behaviour and the default after every si_infer_setup).  Applies to si_logdensity, its gradient and the
  * RWMH samplers.                                                                                                   */
 int32_t si_infer_set_prior(si_ctx* ctx, double sigma_p);
+/* NON-DEFAULT option: the likelihood of a classifier in place of the Gaussian on its outputs.  With yhat = f_W(X) (out x B, the
+ * model's outputs read as logits whatever the last activation is) and Y (out x B):
+ *   SI_LIK_GAUSSIAN     lp = logpdf(MvNormal(vec(yhat), sigma_m), vec(Y))                      (the reference; every set-up starts here)
+ *   SI_LIK_CATEGORICAL  lp = sum_b sum_i Y_ib (yhat_ib - lse_b), lse_b the log-sum-exp of column b about its maximum
+ *   SI_LIK_BERNOULLI    lp = -sum((1 - Y) yhat + softplus(-yhat)), softplus(-x) = max(-x, 0) + log1p(exp(-|x|))
+ * i.e. minus the numerators of SI_COST_LOGITCE / SI_COST_LOGITBCE (costs.py of the Python package is the definition); soft
+ * labels are kept as written.  sigma_m is accepted and unused, as for a NeuralODE; the prior term of si_infer_set_prior is added
+ * as for the Gaussian.  [upstream, from memory, unverifiable offline]: the reference has no such likelihood -- it is the density
+ * that its users' classification cost implies.  Called after a set-up, like si_infer_set_prior.  Applies to si_logdensity, its
+ * gradients, every sampler and si_fit_advi; si_forward / si_predict keep returning the model's outputs.  While kind != 0 the routes
+ * that form the squared error inside a kernel of their own (the device-resident RWMH loops, the one-launch narrow-chain density,
+ * the fused stacked gradient) are not taken: the per-layer launches and the per-point gradient run, and si_chain_kernel_info /
+ * si_grad_kernel_info say so.  SI_ERR_STATE before a set-up and while a step-wise RWMH session is open; SI_ERR_INVALID for an
+ * unknown kind and for a NeuralODE set-up; a refusal changes nothing.  si_rwmh_begin with d_total > 0 (the data-sharded
+ * session) returns SI_ERR_INVALID while kind != 0.                                                                  */
+#define SI_LIK_GAUSSIAN 0
+#define SI_LIK_CATEGORICAL 1
+#define SI_LIK_BERNOULLI 2
+int32_t si_infer_set_likelihood(si_ctx* ctx, int32_t kind);
+int32_t si_infer_likelihood_info(si_ctx* ctx, int32_t* kind_out);
 /* The autoencoder route (src/space_inference.jl:238-318, auto_inference): the density at W_swa + decoder(z) instead of
  * W_swa + P z.  The decoder is a Dense-only chain M -> h_1 -> ... -> h_{D-1} -> N given as a layer table whose w_off / b_off
  * index the flat parameter vector wdec_host (Nd elements of wdec_dtype, Flux.destructure order: [vec(W_l); b_l] per layer).  Call

@@ -19,6 +19,8 @@ SI_ERR_COMM = -7
 SI_COMM_ID_BYTES, SI_COMM_SUM, SI_COMM_MAX = 128, 0, 1
 SI_F32, SI_F64 = 0, 1
 SI_DTYPE_OF_DATA = -1
+SI_LIK_GAUSSIAN, SI_LIK_CATEGORICAL, SI_LIK_BERNOULLI = 0, 1, 2
+LIKELIHOODS = {"gaussian": SI_LIK_GAUSSIAN, "categorical": SI_LIK_CATEGORICAL, "bernoulli": SI_LIK_BERNOULLI}
 ACT_IDENTITY, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
 ACT_LEAKYRELU, ACT_ELU, ACT_SOFTPLUS, ACT_SELU = 4, 5, 6, 7
 K_NAMES = ["push", "gram", "gram_reduce", "project", "reconstruct", "dense", "sse", "rwmh", "dense_main", "eig_host", "backward",
@@ -94,6 +96,8 @@ SIGNATURES = {
     "si_infer_setup_dev": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_int32, c_void_p, c_void_p, c_int64,
                                      c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_double, c_int32]),
     "si_infer_set_prior": (c_int32, [c_void_p, c_double]),
+    "si_infer_set_likelihood": (c_int32, [c_void_p, c_int32]),
+    "si_infer_likelihood_info": (c_int32, [c_void_p, POINTER(c_int32)]),
     "si_infer_set_decoder": (c_int32, [c_void_p, POINTER(SiLayer), c_int32, c_int64, c_void_p, c_int32]),
     "si_infer_decoder_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "si_decode": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
@@ -733,6 +737,18 @@ class Context:
     def set_prior(self, sigma_p):
         """non-default include_prior (Q4): sigma_p > 0 adds logpdf(MvNormal(zeros(N), sigma_p), W_swa + P z); 0 = off"""
         self._check(self.lib.si_infer_set_prior(self.h, float(sigma_p)))
+
+    def infer_set_likelihood(self, kind):
+        """si_infer_set_likelihood, after infer_setup: SI_LIK_GAUSSIAN (0, the reference and every set-up's start), SI_LIK_CATEGORICAL
+        (1: lp = -costs.numerator(LOGITCE, yhat, Y)) or SI_LIK_BERNOULLI (2: lp = -costs.numerator(LOGITBCE, yhat, Y)) on the model's
+        outputs; sigma_m is unused then, the prior term stays as set_prior set it"""
+        self._check(self.lib.si_infer_set_likelihood(self.h, int(kind)))
+
+    def infer_likelihood_info(self):
+        """the likelihood set: 0 gaussian, 1 categorical, 2 bernoulli"""
+        k = c_int32(0)
+        self._check(self.lib.si_infer_likelihood_info(self.h, byref(k)))
+        return int(k.value)
 
     def set_decoder(self, table, wdec):
         """si_infer_set_decoder, after infer_setup: the density at W_swa + decoder(z) (autoencoder.py is the definition).  `table` is

@@ -215,7 +215,7 @@ def _swa_construction(model, cost, data, opt, T, c, print_freq, finish, *, devic
 def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=100, M=3, alg="rwmh",
                   backend="forwarddiff", *, sigma_z=None, sigma_m=None, sigma_p=None, device=0, ctx=None,
                   seed=0, chain_id=0, return_z=False, nchains=1, include_prior=False, compute_dtype="f64",
-                  device_loop=False, device_sampler=False, device_nuts=False):
+                  device_loop=False, device_sampler=False, device_nuts=False, likelihood="gaussian"):
     """src/space_inference.jl:82-164 for a Chain model and alg = :rwmh.
 
     A `flux.NeuralODE` model (reference :96-101; docs/src/node_example.md) is accepted for alg = :rwmh / :mh: `data` holds the initial
@@ -256,15 +256,21 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
     device (si_sample_nuts; `Context.sample_nuts` / `Context.nuts_kernel_info`): the transition of `samplers.nuts_iter` on the
     Philox streams (seed, chain_id + c), n_adapts = round(itr / 2), max_depth = 10, max_dh = 1000; the initial state is dropped.
     It allows nchains > 1, with :hmc's shapes.  The default :nuts stays `samplers.nuts` on PCG64, bit for bit.
+
+    `likelihood` (non-default; not in the reference): "gaussian" is the reference's density.  "categorical" and "bernoulli" sample a
+    classifier under the likelihood its cost defines (si_infer_set_likelihood; costs.py is the definition): lp = -costs.numerator(
+    LOGITCE | LOGITBCE, model outputs, Y), the outputs read as logits, soft labels kept as written, σ_m unused, the prior term of
+    `include_prior` added as for the Gaussian.  Every algorithm works; the device-resident RWMH loops and the fused stacked
+    gradient are not taken, the launch-per-step loop and the per-point gradient run.  A NeuralODE is refused.
     """
     return _inference(in_model, data, W_swa, P, None, σ_z, σ_m, σ_p, itr, M, alg, sigma_z=sigma_z, sigma_m=sigma_m, sigma_p=sigma_p,
                       device=device, ctx=ctx, seed=seed, chain_id=chain_id, return_z=return_z, nchains=nchains,
                       include_prior=include_prior, compute_dtype=compute_dtype, device_loop=device_loop,
-                      device_sampler=device_sampler, device_nuts=device_nuts)
+                      device_sampler=device_sampler, device_nuts=device_nuts, likelihood=likelihood)
 
 
 def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg, *, sigma_z, sigma_m, sigma_p, device, ctx, seed, chain_id,
-               return_z, nchains, include_prior, compute_dtype, device_loop, device_sampler, device_nuts):
+               return_z, nchains, include_prior, compute_dtype, device_loop, device_sampler, device_nuts, likelihood="gaussian"):
     """What `sub_inference` and `auto_inference` share (reference :82-164 and :238-318, the same sampler calls twice): `decoder` is
     None (the density at W_swa + P*z) or the decoder's (layer table, flat parameters), set on the context right after the
     inference set-up (the density, its gradient and the output map at W_swa + decoder(z))."""
@@ -281,6 +287,11 @@ def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg,
     if not is_node and not isinstance(in_model, flux.Chain):
         raise SubspaceError("Error: density function is not avaliable for this model")  # [sic] reference :103
     x, y, in_size = flux.data_matrices(data)  # split_data, src/libs.jl:75-77 (full data, not the batches)
+    if likelihood not in _capi.LIKELIHOODS:
+        raise SubspaceError("likelihood must be \"gaussian\" (the reference's density), \"categorical\" or \"bernoulli\"")
+    if likelihood != "gaussian" and is_node:
+        raise SubspaceError("likelihood = \"%s\" is not available for NeuralODE models: their density is the sum of squared errors "
+                            "of the trajectories" % likelihood)
     if is_node:
         if a not in _RWMH_ALGS and in_model.sensealg is None:
             raise SubspaceError("alg = :%s needs the gradient of the density, and the gradient through the ODE solver is not built "
@@ -295,6 +306,11 @@ def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg,
     if compute_dtype not in ("f64", "f32"):
         raise SubspaceError("compute_dtype must be \"f64\" (the reference's arithmetic) or \"f32\"")
     cdt = _capi.SI_F32 if compute_dtype == "f32" else _capi.SI_F64
+    if likelihood != "gaussian":   # the labels are read element by element against the model's outputs
+        out = int(table[-1][1]) if len(table[-1]) == 5 else None   # (a Chain that ends in a Dense layer; else the set-up checks)
+        if np.ndim(y) != 2 or np.shape(y)[1] != np.shape(x)[1] or (out is not None and np.shape(y)[0] != out):
+            raise SubspaceError("DimensionMismatch: likelihood = \"%s\" needs Y of the shape of the model's outputs (out x B), got %s"
+                                % (likelihood, np.shape(y)))
     ctx, own = _get_ctx(ctx, device)
     def setup(w_swa, p):
         if is_node:   # σ_m and σ_p are accepted and unused, as in the reference (:96-101)
@@ -318,6 +334,8 @@ def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg,
         # include_prior=True adds the term the reference leaves dead after its `return` (quirk Q4); default: as the reference
         if not is_node:
             ctx.set_prior(σ_p if include_prior else 0.0)
+        if likelihood != "gaussian":   # (every set-up starts Gaussian)
+            ctx.infer_set_likelihood(_capi.LIKELIHOODS[likelihood])
         if device_sampler and a != "hmc":
             raise SubspaceError("device_sampler=True is available for alg = :hmc only" + (
                 " (alg = :%s runs on the device with device_loop=True)" % a if a in ("mala", "advi") else ""))
@@ -388,7 +406,7 @@ def inference(*args, **kwargs):
 def subspace_inference(model, cost, data, opt, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=1000, T=25, c=1, M=20,
                        print_freq=1, alg="rwmh", backend="forwarddiff", method="subspace", *, sigma_z=None,
                        sigma_m=None, sigma_p=None, device=0, ctx=None, seed=0, verbose=True, return_z=False,
-                       compute_dtype="f64", device_loop=False, device_sampler=False, device_nuts=False):
+                       compute_dtype="f64", device_loop=False, device_sampler=False, device_nuts=False, likelihood="gaussian"):
     """src/space_inference.jl:33-54: construction, then sampling; returns (chn, lp, W_swa).
     W_swa and P stay on the device between the two stages (no host round trip).  With a `flux.NeuralODE(...,
     sensealg="discrete_adjoint")` and `flux.node_sse` this is the NeuralODE tutorial's call (docs/src/node_example.md:285)."""
@@ -407,7 +425,7 @@ def subspace_inference(model, cost, data, opt, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr
         chn, lp = sub_inference(model, data, None, None, σ_z=σ_z, σ_m=σ_m, σ_p=σ_p, itr=itr, M=M, alg=alg,
                                 backend=backend, sigma_z=sigma_z, sigma_m=sigma_m, ctx=ctx, seed=seed,
                                 return_z=return_z, compute_dtype=compute_dtype, device_loop=device_loop,
-                                device_sampler=device_sampler, device_nuts=device_nuts)
+                                device_sampler=device_sampler, device_nuts=device_nuts, likelihood=likelihood)
         return chn, lp, w_swa
     finally:
         if own:
@@ -517,7 +535,8 @@ def auto_encoder_subspace(model, cost, data, opt, encoder, decoder, T=10, c=1, M
 
 def auto_inference(m, data, decoder, W_swa, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=100, M=3, alg="hmc", backend="forwarddiff", *,
                    sigma_z=None, sigma_m=None, sigma_p=None, device=0, ctx=None, seed=0, chain_id=0, return_z=False, nchains=1,
-                   include_prior=False, compute_dtype="f64", device_loop=False, device_sampler=False, device_nuts=False):
+                   include_prior=False, compute_dtype="f64", device_loop=False, device_sampler=False, device_nuts=False,
+                   likelihood="gaussian"):
     """src/space_inference.jl:238-318 for a Chain model: `sub_inference` with the density at `W_swa + decoder(z)` (:247) and the
     output map `W_swa + decoder(z)` (:278,291,314) -> (chn, lp).  The default algorithm is :hmc, as in the reference.
 
@@ -543,13 +562,13 @@ def auto_inference(m, data, decoder, W_swa, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
     return _inference(m, data, W_swa, np.zeros((n_par, M), order="F"), spec, σ_z, σ_m, σ_p, itr, M, alg, sigma_z=sigma_z,
                       sigma_m=sigma_m, sigma_p=sigma_p, device=device, ctx=ctx, seed=seed, chain_id=chain_id, return_z=return_z,
                       nchains=nchains, include_prior=include_prior, compute_dtype=compute_dtype, device_loop=device_loop,
-                      device_sampler=device_sampler, device_nuts=device_nuts)
+                      device_sampler=device_sampler, device_nuts=device_nuts, likelihood=likelihood)
 
 
 def autoencoder_inference(model, cost, data, opt, encoder, decoder, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=1000, T=25, c=1, M=20,
                           print_freq=1, alg="hmc", backend="forwarddiff", *, sigma_z=None, sigma_m=None, sigma_p=None, device=0,
                           ctx=None, seed=0, verbose=True, return_z=False, include_penalty=False, include_prior=False,
-                          device_loop=False, device_sampler=False, device_nuts=False, device_autoencoder=False):
+                          device_loop=False, device_sampler=False, device_nuts=False, device_autoencoder=False, likelihood="gaussian"):
     """src/space_inference.jl:198-210: `auto_encoder_subspace`, then `auto_inference`, on one context -> (chn, lp).  A NeuralODE
     with `flux.node_sse` trains as in `subspace_construction`.  device_autoencoder: as in `auto_encoder_subspace`."""
     _refuse_node_training(model, cost)
@@ -561,7 +580,7 @@ def autoencoder_inference(model, cost, data, opt, encoder, decoder, σ_z=1.0, σ
         return auto_inference(model, data, decoder, w_swa, σ_z=σ_z, σ_m=σ_m, σ_p=σ_p, itr=itr, M=M, alg=alg, backend=backend,
                               sigma_z=sigma_z, sigma_m=sigma_m, sigma_p=sigma_p, ctx=ctx, seed=seed, return_z=return_z,
                               include_prior=include_prior, device_loop=device_loop, device_sampler=device_sampler,
-                              device_nuts=device_nuts)
+                              device_nuts=device_nuts, likelihood=likelihood)
     finally:
         if own:
             ctx.close()

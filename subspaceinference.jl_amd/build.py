@@ -55,6 +55,7 @@ SOURCES = [
     ("kernels_bwd.hip", []),
     ("kernels_bwd_f32.hip", []),
     ("kernels_cost.hip", ["-ffp-contract=off"]),   # (the costs' summands and derivatives rounded as costs.py forms them)
+    ("kernels_lik.hip", ["-ffp-contract=off"]),    # (the likelihoods' summands rounded as costs.py forms them, and as kernels_cost.hip does)
     ("kernels_conv.hip", []),
     ("kernels_conv.hip", ["-DSI_CONV_F32"], "kernels_conv_f32"),   # same source on fp32 operands (forward kernels only)
     ("capi_net.hip", []),
@@ -64,7 +65,7 @@ SOURCES = [
     ("eig_dispatch.cpp", []),
     ("chain_spec_rtc.cpp", []),   # hiprtc front end of chain_spec.inc (the kernel text is embedded: _embed_spec_source)
 ]
-HEADERS = ["si_internal.h", "dev_buf.h", "philox.h", "kernels_gemm.h", "gemm_pipeline.h", "chain_common.h", "sampler_device.h", "capi_common.h", "node_tableau.h", "optimiser_update.h", "chain_spec.inc", "chain_spec_args.h",
+HEADERS = ["si_internal.h", "dev_buf.h", "philox.h", "kernels_gemm.h", "gemm_pipeline.h", "chain_common.h", "sampler_device.h", "capi_common.h", "node_tableau.h", "optimiser_update.h", "cost_reduce.h", "chain_spec.inc", "chain_spec_args.h",
            "chain_spec_rtc.h", os.path.join("..", "..", "include", "subspace_hip.h")]
 # the kernel text that chain_spec_rtc.cpp hands to hiprtc at run time, in this order
 SPEC_SOURCES = [("SI_SPEC_SRC_COMMON", "chain_common.h"), ("SI_SPEC_SRC_PHILOX", "philox.h"), ("SI_SPEC_SRC_ARGS", "chain_spec_args.h"),

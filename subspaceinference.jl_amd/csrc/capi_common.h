@@ -113,6 +113,9 @@ double prior_c0(const si_ctx* ctx);
 double lik_c0(const si_ctx* ctx, double d);
 double lik_s2(const si_ctx* ctx);
 double prior_sp2(const si_ctx* ctx);
+// a categorical / Bernoulli likelihood is set (si_infer_set_likelihood): the ONE predicate by which every route that forms the
+// SSE inside a kernel of its own steps aside (chain_loop_applies, rwmh_grid, density_fused, vgrad_route)
+inline bool lik_on(const si_ctx* ctx) { return ctx->setup.lik != 0; }
 // capi_node.hip: the NeuralODE route behind eval_density and si_predict (node.on), and the part of its set-up that
 // infer_setup_common carries (capi_infer.hip)
 int32_t node_density(si_ctx* ctx, const si::DensityView& v, int c0, int nc, const double** yhat_out);

@@ -375,6 +375,7 @@ static int32_t density_net(si_ctx* ctx, const DensityView& v, const T* w, const 
 // kernels (one squared error per thread: the same partial sums as tail_sse_kernel's).  Its plan and tile program were built for
 // the set-up's B, so a view of other data is refused.  SI_NOT_TAKEN: no LDS plan at this nc, nothing launched.
 static int32_t density_fused(si_ctx* ctx, const DensityView& v, int c0, int nc) {
+  if (lik_on(ctx)) return SI_NOT_TAKEN;   // (its SSE is the squared error's: the per-layer route hands the outputs to launch_lik)
   if (!v.is_setup_data) return fail(ctx, SI_ERR_STATE, "eval_density: the narrow-chain launch is built for the set-up's own data");
   const int64_t N = ctx->iN, B = v.B, ldw = pad_ld(N);
   const double dn = (double)nc;
@@ -454,6 +455,18 @@ static int32_t density_layers(si_ctx* ctx, const DensityView& v, int c0, int nc,
   return SI_OK;
 }
 
+// the route of the chain set up: Conv, the one-launch narrow chain, or the per-layer launches
+static int32_t density_route(si_ctx* ctx, const DensityView& v, int c0, int nc, const double** yhat_out) {
+  if (ctx->setup.plan.has_conv)
+    return v.f32 ? density_net<float>(ctx, v, ctx->fw.w32, v.X32, v.act32, ctx->fw.wpack32, c0, yhat_out)
+                 : density_net<double>(ctx, v, ctx->fw.w, ctx->setup.plan.input_spatial ? v.Xc : v.X, v.act, ctx->fw.wpack, c0, yhat_out);
+  if (ctx->setup.fused_ok && ctx->chain_mode != 0 && !yhat_out) {   // (never with compute_dtype = SI_F32: fused_chain_class)
+    const int32_t rc = density_fused(ctx, v, c0, nc);
+    if (rc != SI_NOT_TAKEN) return rc;
+  }
+  return density_layers(ctx, v, c0, nc, yhat_out);
+}
+
 // density evaluations for chain slots [c0, c0 + nc), nc <= fw.slots, in ONE pass of launches:
 // chains.zprop[:, c] -> chains.sse[c]; optionally leaves the model outputs at *yhat_out (slot j at + j * out_dim*B after the fused
 // tail, at + j * act_elems otherwise)
@@ -470,14 +483,25 @@ int32_t eval_density(si_ctx* ctx, const DensityView& v, int c0, int nc, const do
   }
   if (ctx->setup.sigma_p > 0.0)  // ||new_W||^2 per chain for the optional prior term (same fixed-order reduction as the SSE)
     launch_sse(ctx->stream, ctx->fw.w, nullptr, N, ctx->fw.wsqpart, ctx->wsq_blocks, ctx->chains.wsq + c0, nc, ldw);
-  if (ctx->setup.plan.has_conv)
-    return v.f32 ? density_net<float>(ctx, v, ctx->fw.w32, v.X32, v.act32, ctx->fw.wpack32, c0, yhat_out)
-                 : density_net<double>(ctx, v, ctx->fw.w, ctx->setup.plan.input_spatial ? v.Xc : v.X, v.act, ctx->fw.wpack, c0, yhat_out);
-  if (ctx->setup.fused_ok && ctx->chain_mode != 0 && !yhat_out) {   // (never with compute_dtype = SI_F32: fused_chain_class)
-    const int32_t rc = density_fused(ctx, v, c0, nc);
-    if (rc != SI_NOT_TAKEN) return rc;
+  // A categorical / Bernoulli likelihood (si_infer_set_likelihood) reads the model outputs of the set-up's data: the Conv route and
+  // the per-layer route run as they are with the outputs requested (which keeps density_fused away), and launch_lik overwrites the
+  // squared errors' partials and sum.
+  const bool lik = lik_on(ctx) && v.is_setup_data;
+  const double* yh_lik = nullptr;
+  const double** yo = lik && !yhat_out ? &yh_lik : yhat_out;
+  const int32_t rc = density_route(ctx, v, c0, nc, yo);
+  if (rc != SI_OK || !lik) return rc;
+  {
+    // where the outputs are: v.yhat, slots out_dim * B apart, behind the fused narrow tail and on the fp32 Dense route (the fp64
+    // copy); the last activation buffer, slots act_elems apart, on the fp64 Dense route otherwise; a Conv chain has one slot
+    const int64_t d = (int64_t)ctx->out_dim * v.B;
+    const int64_t stride = ctx->setup.plan.has_conv ? 0 : (ctx->setup.fuse_tail || v.f32) ? d : v.act_elems;
+    ProfScope ps(ctx, SI_K_SSE, 8.0 * (double)d * dn, 8.0 * (double)d * (dn + 1.0));
+    launch_lik(ctx->stream, ctx->setup.lik, v.Y, *yo, stride, ctx->out_dim, v.B, v.ssepart, v.sse_blocks, ctx->chains.sse + c0, nc,
+               !v.defer_sse_final);
   }
-  return density_layers(ctx, v, c0, nc, yhat_out);
+  SI_HIP(ctx, hipGetLastError());
+  return SI_OK;
 }
 
 // all C chain slots, fw.slots at a time
@@ -500,8 +524,10 @@ double prior_c0(const si_ctx* ctx) { return ctx->setup.sigma_p > 0.0 && !ctx->no
 // The constants of lp = c0 - (sse / s2) / 2 [+ prior_c0 - (wsq / sp2) / 2].  A NeuralODE set-up (reference
 // src/space_inference.jl:96-101: lp = -sse - ||W||^2, sigma_m and sigma_p unused) is c0 = 0, s2 = 1/2, the prior term on (the set-up
 // holds sigma_p at 1), prior_c0 = 0, sp2 = 1/2: every division is exact, so the RWMH kernels carry it with these constants alone.
-double lik_c0(const si_ctx* ctx, double d) { return ctx->node.on ? 0.0 : mvnormal_c0(d, ctx->sigma_m); }
-double lik_s2(const si_ctx* ctx) { return ctx->node.on ? 0.5 : ctx->sigma_m * ctx->sigma_m; }
+// A categorical / Bernoulli likelihood (si_infer_set_likelihood) likewise: chains.sse holds the negative log-likelihood, c0 = 0 and
+// s2 = 1/2 make lp = -nll exactly; sigma_m is unused, the prior term is the Chain's.
+double lik_c0(const si_ctx* ctx, double d) { return ctx->node.on || lik_on(ctx) ? 0.0 : mvnormal_c0(d, ctx->sigma_m); }
+double lik_s2(const si_ctx* ctx) { return ctx->node.on || lik_on(ctx) ? 0.5 : ctx->sigma_m * ctx->sigma_m; }
 double prior_sp2(const si_ctx* ctx) { return ctx->node.on ? 0.5 : ctx->setup.sigma_p * ctx->setup.sigma_p; }
 
 // the value of the log-density from the device's sums, as the host forms it: lp = c0 - (sse / s2) / 2 [+ prior_c0 - (wsq / sp2) / 2]
@@ -519,6 +545,23 @@ int32_t si_infer_set_prior(si_ctx* ctx, double sigma_p) {
   if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_infer_set_prior: a step-wise RWMH session is open");
   if (!(sigma_p >= 0.0)) return fail(ctx, SI_ERR_INVALID, "si_infer_set_prior: sigma_p must be >= 0 (0 = off, the reference's behaviour)");
   ctx->setup.sigma_p = sigma_p;
+  return SI_OK;
+}
+
+int32_t si_infer_set_likelihood(si_ctx* ctx, int32_t kind) {
+  CHECK_CTX(ctx);
+  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, "si_infer_set_likelihood: call si_infer_setup first");
+  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_infer_set_likelihood: a step-wise RWMH session is open");
+  if (kind < 0 || kind > 2) return fail(ctx, SI_ERR_INVALID, "si_infer_set_likelihood: kind must be 0 gaussian, 1 categorical or 2 bernoulli");
+  if (ctx->node.on) return fail(ctx, SI_ERR_INVALID, "si_infer_set_likelihood: not available for NeuralODE models (their density is the sum of squared errors of the trajectories)");
+  ctx->setup.lik = kind;
+  return SI_OK;
+}
+
+int32_t si_infer_likelihood_info(si_ctx* ctx, int32_t* kind_out) {
+  CHECK_CTX(ctx);
+  if (!kind_out) return fail(ctx, SI_ERR_INVALID, "si_infer_likelihood_info: bad argument");
+  *kind_out = ctx->setup.ready ? ctx->setup.lik : 0;
   return SI_OK;
 }
 
@@ -672,7 +715,8 @@ static int32_t ensure_grad(si_ctx* ctx) {
     return fail(ctx, SI_ERR_INVALID, "si_logdensity_grad: compute_dtype = SI_F32 has a reverse sweep for Dense chains only; set a Conv chain up with SI_F64 for gradients");
   if (!sweep_ws_alloc(ctx, g.ws, ctx->layers.data(), (int)ctx->layers.size(), ctx->setup.plan, ctx->setup.fuse_tail, ctx->iN, ctx->in_dim, ctx->out_dim,
                       ctx->B, ctx->setup.f32) ||
-      !g.gw.alloc((size_t)pad_ld(ctx->iN)) || !g.ptgpart.alloc((size_t)ptg_blocks() * ctx->iM) || !g.gz.alloc((size_t)ctx->iM))
+      !g.gw.alloc((size_t)pad_ld(ctx->iN)) || !g.ptgpart.alloc((size_t)ptg_blocks() * ctx->iM) || !g.gz.alloc((size_t)ctx->iM) ||
+      !g.likpart.alloc((size_t)SI_COST_MAX_BLOCKS))
     return drop_grad(ctx);
   return SI_OK;
 }
@@ -697,14 +741,17 @@ static int32_t logdensity_grad_point(si_ctx* ctx, const double* z, double* lp_ou
   const bool prior = ctx->setup.sigma_p > 0.0;
   if (prior) launch_sse(ctx->stream, ctx->fw.w, nullptr, N, ctx->fw.wsqpart, ctx->wsq_blocks, ctx->chains.wsq, 1, pad_ld(N));
   // d (-SSE / (2 sigma^2)) / dw into grad.gw and the SSE into chains.sse by the chain's route: Delta_L = d lp / d yhat = (y - yhat) / sigma^2.
-  // compute_dtype = SI_F32: on the fp32 density's own arithmetic (W_swa + P z rounded once); P' g and the prior term stay fp64
+  // compute_dtype = SI_F32: on the fp32 density's own arithmetic (W_swa + P z rounded once); P' g and the prior term stay fp64.
+  // A categorical / Bernoulli likelihood: the training step's cost tail with inv_denom = -1, so that Delta_L = -d nll / d yhat .*
+  // act' = d lp / d yhat and the numerator -- the negative log-likelihood -- lands in chains.sse (lp = -nll through lik_c0 / lik_s2)
+  const CostTail lik_tail{ctx->setup.lik == 1 ? SI_COST_LOGITCE : SI_COST_LOGITBCE, 0.0, -1.0, ctx->grad.likpart};
   double bflops = 0.0;   // (what a Conv chain reports for its SI_K_BACKWARD scope)
   for (const auto& q : ctx->setup.plan.L)
     bflops += q.kind == SI_LAYER_DENSE ? 4.0 * (double)q.in_feat * q.out_feat * (double)B
               : q.kind == SI_LAYER_CONV ? 4.0 * (double)q.KW * q.KH * q.C * q.Co * (double)q.Wo * q.Ho * (double)B : 0.0;
   const ChainValueGrad in{ctx->layers.data(), ctx->layers.size(), &ctx->setup.plan, ctx->setup.fuse_tail, ctx->fw.w, ctx->fw.w32, ctx->setup.X, ctx->setup.Xc, ctx->setup.X32,
                           ctx->setup.Y, B, N, ctx->fw.part, ctx->fuse_slots, ctx->fw.ssepart, ctx->chains.sse, ctx->sse_blocks, ctx->grad.gw, ctx->fw.wpack,
-                          1.0 / s2, nullptr, true, bflops};
+                          1.0 / s2, lik_on(ctx) ? &lik_tail : nullptr, true, bflops};
   if ((rc = chain_value_and_grad(ctx, ctx->stream, ctx->grad.ws, in)) != SI_OK) return rc;
   if (prior) launch_prior_grad(ctx->stream, ctx->grad.gw, ctx->fw.w, N, 1.0 / (ctx->setup.sigma_p * ctx->setup.sigma_p), ctx->num_cu);
   pull_back_to_z(ctx, ctx->grad.gw, ctx->grad.gz);
@@ -776,7 +823,9 @@ static int vgrad_class(si_ctx* ctx) {
 // the points one pass of launches may carry.
 static int vgrad_route(si_ctx* ctx, int64_t* G_out, int64_t* fit_out) {
   const int64_t B = ctx->B, ldw = pad_ld(ctx->iN);
-  const int nb = ctx->dec.on ? 0 : vgrad_class(ctx);   // (chain_vgrad_reduce_kernel forms P' g itself: not taken with a decoder)
+  // (chain_vgrad_reduce_kernel forms P' g itself: not taken with a decoder; chain_vgrad_kernel seeds the sweep with the squared
+  //  error's derivative: not taken with a categorical / Bernoulli likelihood)
+  const int nb = ctx->dec.on || lik_on(ctx) ? 0 : vgrad_class(ctx);
   const int64_t G = nb > 0 ? (B + 16 * nb - 1) / (16 * nb) : 0;
   // points per pass of launches: the workspace (weights, G partials of grad_w, grad_w per point) is capped like the forward
   // workspace of the stacked density (SI_BATCH_BYTES), and a launch carries at most 65535 points in grid.y

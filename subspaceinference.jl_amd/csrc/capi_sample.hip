@@ -58,7 +58,7 @@ static int32_t ensure_wstream(si_ctx* ctx, int32_t C) {
 // launches per transition spread over the chip (2 N B <= 3 MFLOP: the README toy is 0.14)
 static constexpr size_t SI_CHAIN_LDS_LIMIT = 160 * 1024 - 256;
 static bool chain_loop_applies(const si_ctx* ctx) {
-  if (ctx->setup.f32 || ctx->setup.plan.has_conv || !ctx->setup.fuse_tail || ctx->setup.sigma_p > 0.0 || ctx->dec.on) return false;   // (dec: the loop forms W_swa + P z itself)
+  if (ctx->setup.f32 || ctx->setup.plan.has_conv || !ctx->setup.fuse_tail || ctx->setup.sigma_p > 0.0 || ctx->dec.on || lik_on(ctx)) return false;   // (dec: the loop forms W_swa + P z itself; lik: it forms the squared errors itself)
   if (ctx->layers.size() > (size_t)SI_CHAIN_MAX_LAYERS || ctx->iN > (1 << 20) || ctx->B > (1 << 20)) return false;
   if (ctx->iM > 1024) return false;   // (rwmh_chain_kernel keeps z one element per thread of its 1024-thread workgroup)
   for (const auto& ly : ctx->layers)
@@ -218,7 +218,7 @@ static const SpecKernels* prepare_spec_loop(si_ctx* ctx, const RwmhCall& k, int 
 static int32_t rwmh_grid(si_ctx* ctx, const RwmhCall& k) {
   const int32_t C = k.C, M = ctx->iM;
   if (!k.map_fits || !ctx->setup.fused_ok || ctx->chain_mode != 1 || ctx->setup.sigma_p > 0.0 || C > ctx->fw.slots || k.itr >= ((int64_t)1 << 24) ||
-      ctx->dec.on)   // (both grid loops, the run-time specialised one included, form W_swa + P z in their own K4)
+      ctx->dec.on || lik_on(ctx))   // (both grid loops, the run-time specialised one included, form W_swa + P z in their own K4 and the squared errors in their own tail)
     return SI_NOT_TAKEN;
   ChainGridArgs a{};
   const int L = (int)ctx->layers.size();
@@ -442,6 +442,8 @@ int32_t si_rwmh_begin(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, i
   if (itr <= 0 || nchains <= 0 || chain_id0 < 0 || !(sigma_z > 0.0) || d_total < 0)
     return fail(ctx, SI_ERR_INVALID, "si_rwmh_begin: itr, nchains, sigma_z must be positive");
   if (ctx->node.on && d_total > 0) return fail(ctx, SI_ERR_INVALID, "si_rwmh_begin: a data-sharded density (d_total > 0) is not available for NeuralODE models");
+  if (lik_on(ctx) && d_total > 0)
+    return fail(ctx, SI_ERR_INVALID, "si_rwmh_begin: a data-sharded density (d_total > 0) is not available with a categorical or bernoulli likelihood (si_infer_set_likelihood)");
   BIND(ctx);
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   int32_t rc = ensure_chains(ctx, nchains);

@@ -10,18 +10,10 @@
 // inputs give the same bits.
 #include <algorithm>
 
+#include "cost_reduce.h"
 #include "kernels_gemm.h"
 
 namespace si {
-
-// the block's 256 values, summed in a fixed order: a butterfly within each wave (every lane ends with the same bits), then the
-// four wave sums in ascending order
-__device__ __forceinline__ double cost_block_sum(double v, double* red) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 // kinds 1, 2, 4: elementwise summand l(yhat, y) and its derivative
 template <class TY, class TD>
@@ -58,17 +50,6 @@ __global__ __launch_bounds__(256) void cost_elem_kernel(const double* __restrict
   }
   acc = cost_block_sum(acc, red);
   if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-
-// reductions over the `seg` lanes of a column's segment (seg a power of two <= 64; segments are aligned): every lane of the
-// segment ends with the same bits
-__device__ __forceinline__ double seg_sum(double v, int seg) {
-  for (int off = seg >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double seg_max(double v, int seg) {
-  for (int off = seg >> 1; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
 }
 
 // kind 3: a wave64 owns 64 / seg columns at a time; seg = next_pow2(out) for out <= 32 (a 10-class head: four columns per wave),

@@ -468,6 +468,7 @@ struct InferSetup {
   const double *swa = nullptr, *P = nullptr;   // device (P: ldP x M); borrowed (the construction's, the caller's) or the owned copies
   DevBuf<double> swa_own, P_own, X, Y;         // W_swa / P when set from host; the data
   double sigma_p = 0.0;           // > 0: the prior term the reference leaves dead is added (si_infer_set_prior; non-default)
+  int lik = 0;                    // si_infer_set_likelihood: 0 gaussian, 1 categorical, 2 bernoulli (every set-up starts Gaussian)
   bool fuse_tail = false;         // last layer folded into the epilogue of the layer in front of it (head_fused)
   bool f32 = false;               // compute_dtype = SI_F32 (Dense chains): X rounded once (X32), weights once per evaluation, fp32 activations
   int fuse_slots32 = 0;           // feature slots of the fp32 fused head (fuse_slots stays the fp64 path's count)
@@ -490,6 +491,7 @@ struct InferForward {
 struct InferGrad {
   SweepWs ws;                     // the reverse sweep's, for the set-up's B observations
   DevBuf<double> gw, ptgpart, gz; // gradient w.r.t. the weights, partials of P' g, gradient w.r.t. z (gw, gz: si_decode_vjp's too; ptgpart: capi_node.hip's)
+  DevBuf<double> likpart;         // a categorical / Bernoulli likelihood: the CostTail's workgroup partials (SI_COST_MAX_BLOCKS doubles)
 };
 // si_logdensity_grad_batch and StackedVgrad, fused route (kernels_chain_grad.hip): vgrad_ensure allocates it for `cap` points per pass
 struct InferStacked {
@@ -810,6 +812,11 @@ constexpr int SI_COST_MAX_BLOCKS = 256;   // doubles in CostTail::part
 template <class TD>
 void launch_cost_tail(hipStream_t st, const CostTail& c, const double* Y, const double* Yhat64, const float* Yhat32, int32_t out, int64_t B,
                       int act, TD* delta, double* loss);
+// the summed negative log-likelihood of a classifier's outputs (kernels_lik.hip; si_infer_set_likelihood), forward only: kind 1
+// categorical, 2 Bernoulli on the fp64 outputs of nc chain slots (slot j at Yhat + j * yhat_stride) against Y (out x B), in ONE
+// launch; `nparts` partials per slot into part (launch_sse's layout, unused ones zero), then launch_sse_final unless !with_final
+void launch_lik(hipStream_t st, int kind, const double* Y, const double* Yhat, int64_t yhat_stride, int32_t out, int64_t B, double* part,
+                int nparts, double* nll_out, int nc, bool with_final);
 void launch_rowsum(hipStream_t st, const double* D, int32_t out, int64_t B, double* part, double* db);
 // reverse sweep through a narrow last layer (out_last <= SI_FUSE_MAX_OUT) in one pass over its input H (F x B):
 // DeltaPrev = (W' Delta) .* act_prev'(H), dW = Delta H', dbprev = rowsum(DeltaPrev); part: tail_bwd_part_elems doubles

@@ -689,10 +689,21 @@ end
 # state is dropped; the default keeps the reference's own AdvancedHMC calls
 # device_nuts = true (alg = :nuts; non-default): NUTS runs with its tree and adaptation on the device (sample_nuts), max_depth 10 and
 # max_dh 1000, and the initial state is dropped; the default keeps the reference's own AdvancedHMC calls
+# likelihood = :categorical / :bernoulli (non-default; not in the reference): the classifier's likelihood on the model's outputs in
+# place of the Gaussian (si_infer_set_likelihood): lp = sum(Y .* logsoftmax(ŷ; dims = 1)) / -sum((1 .- Y) .* ŷ .+ softplus.(-ŷ));
+# σ_m is unused then
+const SI_LIK = Dict(:gaussian => Int32(0), :categorical => Int32(1), :bernoulli => Int32(2))
+set_likelihood(ctx::Ctx, kind::Integer) = check(ctx, ccall((:si_infer_set_likelihood, LIB), Int32, (Ptr{Cvoid}, Int32), ctx.h, kind))
+function likelihood_info(ctx::Ctx)
+    k = Ref{Int32}(0)
+    check(ctx, ccall((:si_infer_likelihood_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), ctx.h, k))
+    return Int(k[])
+end
 function sub_inference(in_model, data, W_swa, P; σ_z = 1.0, σ_m = 1.0, σ_p = 1.0, itr = 100, M = 3, alg = :rwmh,
                        backend = :forwarddiff, device = 0, ctx = Ctx(device), seed = 0, chain_id = 0, include_prior = false,
-                       compute_dtype = :f64, device_loop = false, device_sampler = false, device_nuts = false)
+                       compute_dtype = :f64, device_loop = false, device_sampler = false, device_nuts = false, likelihood = :gaussian)
     alg == :mh && (alg = :rwmh)                                     # README.md:153-154
+    haskey(SI_LIK, likelihood) || throw("likelihood must be :gaussian (the reference's density), :categorical or :bernoulli")
     (device_nuts && alg != :nuts) && throw("device_nuts = true is available for alg = :nuts only")
     (device_sampler && alg != :hmc) && throw("device_sampler = true is available for alg = :hmc only" *
         (alg in (:mala, :advi) ? " (alg = :$alg runs on the device with device_loop = true)" : ""))
@@ -710,6 +721,7 @@ function sub_inference(in_model, data, W_swa, P; σ_z = 1.0, σ_m = 1.0, σ_p = 
          Int32, Int32, Int64, Float64, Int32),
         ctx.h, tbl, length(tbl), N, M, Wp, Pp, X, Y, size(X, 1), size(Y, 1), size(X, 2), σ_m, compute_dtype == :f32 ? SI_F32 : SI_F64))
     check(ctx, ccall((:si_infer_set_prior, LIB), Int32, (Ptr{Cvoid}, Float64), ctx.h, include_prior ? Float64(σ_p) : 0.0))
+    likelihood == :gaussian || set_likelihood(ctx, SI_LIK[likelihood])   # (every set-up starts Gaussian)
     if alg == :rwmh
         # :111-116 on the device: chain state, proposals (Philox) and accept decisions never leave the GPU
         # ... and the output map (:125) streams out while the chain runs (K4's own output, selected on accept; the DMA and

@@ -18,6 +18,23 @@ HEADS = [1, 2, 3, 4, 5, 10, 64, 65, 130, 1000]
 BATCHES = [1, 3, 5, 257]
 B_TOTAL = 300
 
+# (out, nb) of logitcrossentropy beyond one lap of cost_logitce_kernel: its grid is capped at SI_COST_MAX_BLOCKS = 256 workgroups of
+# four waves, a wave owns one group of 64 / seg columns at a time (seg = next_pow2(out) up to 32, 64 above) and walks on with
+# grp += 1024.  (33, 1100): seg 64, 1100 groups; (10, 4103): seg 16, 1026 groups, the last of three columns -- a ragged second lap
+# in both.  BATCHES ends at 257 groups.
+COST_MAX_BLOCKS = 256       # SI_COST_MAX_BLOCKS of csrc/si_internal.h (tests/test_costs_cpu.py reads it there)
+LOGITCE_LAP_SHAPES = [(33, 1100), (10, 4103)]
+
+
+def logitce_geometry(out, nb):
+    """(seg, column groups) of cost_logitce_kernel -- and of lik_logitce_kernel -- at out classes and nb columns"""
+    seg = 64
+    if out <= 32:
+        seg = 1
+        while seg < out:
+            seg *= 2
+    return seg, -(-nb // (64 // seg))
+
 
 def cost_id(c):
     return costs.NAMES[c[0]]

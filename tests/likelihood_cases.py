@@ -9,7 +9,8 @@ then minus the cost's numerator as subspaceinference_jl_amd/costs.py forms it,
 
 plus the oracle's log-prior when sigma_p > 0.  Its gradient is costs.dvalue (denominator 1, sign flipped) pulled back through the
 oracle's reverse pass and P' (or the decoder's vjp).  tests/test_likelihood_cpu.py holds the definition to finite differences and
-certifies the RWMH cases below on it alone; tests/test_gpu_likelihood.py holds the device to it.
+certifies the RWMH cases and the gradient samplers' cases below on it alone; tests/test_gpu_likelihood.py and
+tests/test_gpu_likelihood_samplers.py hold the device to it.
 """
 import functools
 from dataclasses import dataclass
@@ -19,11 +20,16 @@ import numpy as np
 from oracle import subspace_oracle as so
 from subspaceinference_jl_amd import autoencoder as ae
 from subspaceinference_jl_amd import costs
+from tests import advi_audit as aa
+from tests import cost_cases as cc
+from tests import hmc_audit as ha
+from tests import mala_audit as ma
+from tests import nuts_audit as na
 from tests import rwmh_audit as ra
 
 GAUSSIAN, CATEGORICAL, BERNOULLI = 0, 1, 2
 COST = {CATEGORICAL: costs.LOGITCE, BERNOULLI: costs.LOGITBCE}
-I, R, T = so.ACT_IDENTITY, so.ACT_RELU, so.ACT_TANH
+I, R, T, S, SP = so.ACT_IDENTITY, so.ACT_RELU, so.ACT_TANH, so.ACT_SIGMOID, so.ACT_SOFTPLUS
 
 # the Conv chain of tests/test_gpu_train_f32.py with a 3-class head: 3 x 3 x 4 relu on 6 x 6 x 1, flatten, Dense 3
 CONV_INPUT, CONV_SPEC = (6, 6, 1), [("conv", (3, 3), 4, R, (1, 1), (1, 1)), ("flatten",), ("dense", 3, I)]
@@ -111,10 +117,10 @@ def _freeze(*arrays):
 
 
 @functools.lru_cache(maxsize=None)
-def dense_problem(out, b, kind, m=3, soft=False, hidden=6, act=T, wscale=0.5, pscale=0.3):
-    """Dense 4 -> hidden -> out with an identity head, B observations"""
+def dense_problem(out, b, kind, m=3, soft=False, hidden=6, act=T, wscale=0.5, pscale=0.3, head_act=I):
+    """Dense 4 -> hidden -> out with an identity head (head_act: another one, on the same draws), B observations"""
     rng = np.random.default_rng(1000 * out + 10 * b + kind + (500 if soft else 0))
-    table, n = so.layer_table([4, hidden, out], [act, I])
+    table, n = so.layer_table([4, hidden, out], [act, head_act])
     x = np.asfortranarray(rng.standard_normal((4, b)))
     y = labels(kind, out, b, rng, soft)
     w = wscale * rng.standard_normal(n)
@@ -184,6 +190,119 @@ def rwmh_problem(case):
     if case.model[0] == "conv":
         return conv_problem(case.model[1])
     return dense_problem(case.model[1], case.model[2], CATEGORICAL)
+
+
+# ---- the loop branches of the likelihood kernels and of the cost tail's logitcrossentropy kernel (csrc/kernels_lik.hip,
+# kernels_cost.hip), by arithmetic on their launch geometry:
+#   lik_elem_kernel / lik_logitce_kernel run on sse_blocks = min(ceil(out B / 256), 4 num_cu) workgroups of 256 threads.  Below the
+#   cap a thread of lik_elem_kernel owns at most one element; above it, its grid-stride loop takes a second lap.
+#   cost_logitce_kernel runs on min(ceil(groups / 4), COST_MAX_BLOCKS) workgroups of four waves, a wave owning one group of
+#   64 / seg columns at a time (seg = next_pow2(out) up to 32, 64 above): more than 4 COST_MAX_BLOCKS groups make a second lap.
+COST_MAX_BLOCKS, logitce_geometry = cc.COST_MAX_BLOCKS, cc.logitce_geometry
+CAPPED_OUT = 10
+
+
+def capped_batch(num_cu):
+    """a B with CAPPED_OUT B > 256 * 4 num_cu, whatever the part: floor(1024 num_cu / 10) + 86.  26300 on 256 CUs, where
+    lik_elem_kernel's second lap holds 856 of 263000 elements (ragged: most workgroups own none) and lik_logitce_kernel walks 6575
+    groups on 4096 waves"""
+    return (1024 * num_cu) // CAPPED_OUT + 86
+
+
+# (out, B): seg 64, 1100 groups of one column on 1024 waves, a ragged second lap; seg 16, 1026 groups of four columns, the last
+# group of the second lap holding three
+COST_LAP_SHAPES = tuple(cc.LOGITCE_LAP_SHAPES)
+
+# (kind, out, head): the last layer's activation enters the gradient through dact_full(yhat, act) in the cost tail; out <= 4 is
+# the fused narrow tail, above it the generic one
+HEAD_CASES = ((CATEGORICAL, 3, S), (CATEGORICAL, 5, T), (CATEGORICAL, 7, SP), (BERNOULLI, 2, R), (BERNOULLI, 3, T))
+HEAD_B = 7
+
+
+def head_problem(kind, out, head):
+    return dense_problem(out, HEAD_B, kind, head_act=head)
+
+
+# ---- the gradient samplers (si_sample_mala, si_sample_hmc, si_sample_nuts, si_fit_advi) under a likelihood.  The problems are the
+# builders above; the sampler settings are the same for every problem (MALA's sigma_z aside: at 0.8 several problems never accept,
+# cat65 never rejects at 0.3).  tests/test_likelihood_cpu.py certifies every (sampler, problem) pair on the definition alone, also
+# with the definition moved to 0.9 of the stated tolerances; tests/test_gpu_likelihood_samplers.py holds the device's traces to the
+# same audits under the same conditions.
+SAMPLER_SEED, SAMPLER_CHAIN_ID0, SAMPLER_CHAINS = 31, 2, 2
+
+
+@dataclass(frozen=True)
+class SamplerProblem:
+    name: str
+    build: object           # () -> Problem
+    mala_sigma: float
+    f32: bool = False
+    # ADVI's audit holds the ELBO relative to the ELBO itself, and the entropy cancels part of the mean lp: on cat65, ber1 and conv
+    # an lp moved by 0.9 lp_rtol lands at 1.0 .. 1.3e-10 relative to the ELBO, so those three are not ADVI cases
+    advi: bool = True
+
+
+def _cat3_decoder():
+    from tests import decoder_cases as dc
+    pb = dense_problem(3, 37, CATEGORICAL)
+    return pb.with_(decoder=dc.random_decoder((pb.m, 4, pb.n), (T, I), seed=43, dtype=np.float64))
+
+
+SAMPLER_PROBLEMS = [
+    SamplerProblem("cat3", lambda: dense_problem(3, 37, CATEGORICAL), 0.3),                    # the fused narrow tail
+    SamplerProblem("cat3-f32", lambda: dense_problem(3, 37, CATEGORICAL), 0.3, f32=True),
+    SamplerProblem("cat10", lambda: dense_problem(10, 37, CATEGORICAL), 0.3),                  # the generic tail, seg 16
+    SamplerProblem("cat65", lambda: dense_problem(65, 7, CATEGORICAL), 0.5, advi=False),       # the lanes stride the column
+    SamplerProblem("cat3-soft", lambda: dense_problem(3, 37, CATEGORICAL, soft=True), 0.3),
+    SamplerProblem("ber1", lambda: dense_problem(1, 37, BERNOULLI), 0.5, advi=False),
+    SamplerProblem("ber10", lambda: dense_problem(10, 37, BERNOULLI), 0.3),
+    SamplerProblem("ber10-f32", lambda: dense_problem(10, 37, BERNOULLI), 0.3, f32=True),
+    SamplerProblem("cat3-prior", lambda: dense_problem(3, 37, CATEGORICAL).with_(prior=0.7), 0.3),
+    SamplerProblem("cat3-decoder", _cat3_decoder, 0.3),
+    SamplerProblem("conv", lambda: conv_problem(7), 0.3, advi=False),
+]
+SAMPLER_BY_NAME = {sp.name: sp for sp in SAMPLER_PROBLEMS}
+ADVI_PROBLEMS = [sp for sp in SAMPLER_PROBLEMS if sp.advi]
+
+
+def cached(f):
+    """f memoised by the bytes of z: the audits and the oracle traces ask for the same points many times"""
+    memo = {}
+
+    def g(z):
+        k = np.ascontiguousarray(z, dtype=np.float64).tobytes()
+        if k not in memo:
+            memo[k] = f(z)
+        return memo[k]
+    return g
+
+
+@functools.lru_cache(maxsize=None)
+def sampler_problem(name):
+    """(the Problem, its density_grad memoised) of a SamplerProblem's name"""
+    pb = SAMPLER_BY_NAME[name].build()
+    return pb, cached(pb.density_grad)
+
+
+# the audit modules' own cases with model = None: their oracle_trace / audit_case never touch `model` when value_grad is given
+def mala_case(sp):
+    return ma.Case(sp.name, None, sampler_problem(sp.name)[0].m, sp.mala_sigma, False, nchains=SAMPLER_CHAINS, itr=40, seed=SAMPLER_SEED,
+                   chain_id0=SAMPLER_CHAIN_ID0, f32=sp.f32)
+
+
+def hmc_case(sp):
+    return ha.Case(sp.name, None, sampler_problem(sp.name)[0].m, 0.5, False, nchains=SAMPLER_CHAINS, itr=40, delta=0.8, seed=SAMPLER_SEED,
+                   chain_id0=SAMPLER_CHAIN_ID0, f32=sp.f32)
+
+
+def nuts_case(sp):
+    return na.Case(sp.name, None, sampler_problem(sp.name)[0].m, 0.5, False, nchains=SAMPLER_CHAINS, itr=10, max_depth=4, seed=SAMPLER_SEED,
+                   chain_id0=SAMPLER_CHAIN_ID0, f32=sp.f32)
+
+
+def advi_case(sp):
+    return aa.Case(sp.name, None, sampler_problem(sp.name)[0].m, False, 6, s=3, w=4, nruns=SAMPLER_CHAINS, chain_id0=SAMPLER_CHAIN_ID0,
+                   ndraws=3, sigma_z=0.3, seed=SAMPLER_SEED, f32=sp.f32)
 
 
 def rwmh_oracle_trace(case, density):

@@ -33,6 +33,21 @@ def test_dvalue_is_the_derivative_of_value(cost):
     assert np.allclose(costs.dvalue(kind, yhat, y, param, denom=2 * costs.denominator(kind, out, nb)), 0.5 * g, rtol=1e-15)
 
 
+def test_the_lap_shapes_pass_the_grid_of_the_logitcrossentropy_kernel():
+    """arithmetic on cost_logitce_kernel's launch: min(ceil(groups / 4), SI_COST_MAX_BLOCKS) workgroups of four waves, so more than
+    4 SI_COST_MAX_BLOCKS column groups send some waves on a second lap -- which cc.BATCHES never does"""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    raw = open(os.path.join(root, "subspaceinference.jl_amd", "csrc", "si_internal.h")).read()
+    assert int(re.search(r"constexpr\s+int\s+SI_COST_MAX_BLOCKS\s*=\s*(\d+)\s*;", raw).group(1)) == cc.COST_MAX_BLOCKS
+    waves = 4 * cc.COST_MAX_BLOCKS
+    assert max(cc.logitce_geometry(out, max(cc.BATCHES))[1] for out in cc.HEADS) <= waves
+    assert [cc.logitce_geometry(o, nb) for o, nb in cc.LOGITCE_LAP_SHAPES] == [(64, 1100), (16, 1026)]
+    assert all(waves < cc.logitce_geometry(o, nb)[1] < 2 * waves for o, nb in cc.LOGITCE_LAP_SHAPES)
+    assert 4103 % 4 == 3                                        # the last group of (10, 4103) holds three columns
+
+
 def test_denominator():
     assert costs.denominator(costs.LOGITCE, 10, 32) == 32.0
     for kind in (costs.MSE, costs.MAE, costs.HUBER, costs.LOGITBCE):

@@ -77,6 +77,10 @@ def _check_grad(ctx, pb, z, lp_value, lp_rtol, tag, f32=False):
     lpb, gb = ctx.logdensity_grad_batch(z)
     assert ctx.grad_kernel_info() == 0                          # the fused stacked value-and-gradient steps aside
     assert lpb[0] == lp1 and np.array_equal(gb[:, 0], g1)       # the batch walks si_logdensity_grad's own path
+    gref = np.stack([r[1] for r in ref], axis=1)
+    scale = np.max(np.abs(gref), axis=0)
+    bound = G32 * scale[None, :] if f32 else G_RTOL * np.abs(gref) + G_ATOL * np.maximum(1.0, scale)[None, :]
+    print("%s: gradient lp rel %.2e, worst |g - g_ref| / bound %.2e" % (tag, _rel(lpb, [r[0] for r in ref]), np.max(np.abs(gb - gref) / bound)))
     for c in range(z.shape[1]):
         assert abs(lpb[c] - ref[c][0]) <= lp_rtol * abs(ref[c][0]), (tag, c, lpb[c], ref[c][0])
         assert abs(lpb[c] - lp_value[c]) <= lp_rtol * abs(lp_value[c]), (tag, c)     # (within the lp tolerance: the module's docstring)
@@ -125,6 +129,15 @@ def test_value_and_gradient_with_f32_compute(si, ctx, out):
     _check_value(ctx, pb, LP32, "f32 bernoulli out %d" % out)
 
 
+@pytest.mark.parametrize("out", lc.F32_DIMS)
+def test_bernoulli_gradient_with_f32_compute(si, ctx, out):
+    for b in (7, 37):
+        pb = lc.dense_problem(out, b, lc.BERNOULLI)
+        _setup(si, ctx, pb, f32=True)
+        z, lp, _ = _check_value(ctx, pb, LP32, "f32 bernoulli out %d B %d" % (out, b))
+        _check_grad(ctx, pb, z, lp, LP32, "f32 bernoulli out %d B %d" % (out, b), f32=True)
+
+
 def test_value_and_gradient_of_the_conv_chain(si, ctx):
     pb = lc.conv_problem(7)
     _setup(si, ctx, pb)
@@ -135,6 +148,64 @@ def test_value_and_gradient_of_the_conv_chain(si, ctx):
     with pytest.raises(si.SubspaceError, match="Dense chains only"):     # the existing refusal of SI_F32 gradients on Conv chains stays
         ctx.logdensity_grad(z[:, 0])
     assert np.all(np.isfinite(ctx.logdensity(z)))
+
+
+def test_value_and_gradient_of_the_conv_chain_with_the_bernoulli_likelihood(si, ctx):
+    pb = lc.conv_problem(7, kind=lc.BERNOULLI)
+    assert set(np.unique(pb.y)) == {0.0, 1.0} and not np.all(np.sum(pb.y, axis=0) == 1.0)
+    _setup(si, ctx, pb)
+    z, lp, _ = _check_value(ctx, pb, LP64, "conv bernoulli fp64")
+    _check_grad(ctx, pb, z, lp, LP64, "conv bernoulli fp64")
+    _setup(si, ctx, pb, f32=True)
+    _check_value(ctx, pb, LP32, "conv bernoulli f32")
+
+
+# ---- loop branches by launch geometry (tests/likelihood_cases.py holds the arithmetic, tests/test_likelihood_cpu.py checks it) ---------
+def _num_cu():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+@pytest.mark.parametrize("kind", (lc.CATEGORICAL, lc.BERNOULLI))
+def test_the_capped_grid_of_the_likelihood_kernels(si, ctx, kind):
+    """Dense 4 -> 6 -> 10 at out B > 256 * 4 num_cu: the likelihood kernels' grid is sse_blocks = 4 num_cu workgroups, no longer one
+    thread per element.  On 256 CUs B = 26300: lik_elem_kernel's grid-stride loop takes a second, ragged lap (856 of 263000
+    elements), lik_logitce_kernel walks 6575 column groups on 4096 waves; the gradient's cost tail walks them on its own 1024.
+    Every nll summand is non-negative, so the device's fixed-order sum and NumPy's pairwise sum of the definition agree far inside
+    the lp tolerance at this size."""
+    b = lc.capped_batch(_num_cu())
+    assert lc.CAPPED_OUT * b > 256 * 4 * _num_cu()
+    pb = lc.dense_problem(lc.CAPPED_OUT, b, kind)
+    _setup(si, ctx, pb)
+    tag = "capped grid kind %d B %d" % (kind, b)
+    z, lp, _ = _check_value(ctx, pb, LP64, tag)
+    _check_grad(ctx, pb, z, lp, LP64, tag)
+
+
+@pytest.mark.parametrize("out,b,f32", [(o, b, False) for o, b in lc.COST_LAP_SHAPES] + [lc.COST_LAP_SHAPES[0] + (True,)], ids=lambda v: str(v))
+def test_the_second_lap_of_the_cost_tail_through_the_likelihood_gradient(si, ctx, out, b, f32):
+    """cost_logitce_kernel runs on at most 256 workgroups = 1024 waves: (33, 1100) gives seg 64 and 1100 column groups, (10, 4103)
+    seg 16 and 1026 groups whose last holds three columns -- a ragged second lap of `grp += nwaves` in both, as <double, double> and
+    with SI_F32 as <float, float>"""
+    groups = lc.logitce_geometry(out, b)[1]
+    assert 4 * lc.COST_MAX_BLOCKS < groups < 8 * lc.COST_MAX_BLOCKS
+    pb = lc.dense_problem(out, b, lc.CATEGORICAL)
+    _setup(si, ctx, pb, f32=f32)
+    tag = "cost lap out %d B %d%s" % (out, b, " f32" if f32 else "")
+    z, lp, _ = _check_value(ctx, pb, LP32 if f32 else LP64, tag)
+    _check_grad(ctx, pb, z, lp, LP32 if f32 else LP64, tag, f32=f32)
+
+
+@pytest.mark.parametrize("kind,out,head", lc.HEAD_CASES, ids=lambda v: str(v))
+def test_value_and_gradient_with_a_head_activation(si, ctx, kind, out, head):
+    """the last layer's activation enters the gradient through dact_full(yhat, act) in the cost tail: sigmoid on the fused narrow tail,
+    tanh and softplus on the generic one, relu and tanh under the Bernoulli likelihood"""
+    pb = lc.head_problem(kind, out, head)
+    assert pb.table[-1][2] == head != lc.I
+    _setup(si, ctx, pb)
+    tag = "head kind %d out %d act %d" % (kind, out, head)
+    z, lp, _ = _check_value(ctx, pb, LP64, tag)
+    _check_grad(ctx, pb, z, lp, LP64, tag)
 
 
 @pytest.mark.parametrize("out", (3, 10))

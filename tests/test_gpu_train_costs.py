@@ -183,6 +183,42 @@ def test_f32_dense_step(gpu_ctx, si, cost, dims, acts, b, bmax):
         assert err <= bound, (err, bound)
 
 
+# ---- 5b. the second lap of cost_logitce_kernel ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("out,nb", cc.LOGITCE_LAP_SHAPES)
+def test_f64_logitcrossentropy_beyond_one_lap(gpu_ctx, out, nb):
+    """more column groups than the kernel's 1024 waves (cc.LOGITCE_LAP_SHAPES): `grp += nwaves` takes a ragged second lap in
+    cost_logitce_kernel<double, double>; the bounds of test_f64_dense_gradient"""
+    assert cc.logitce_geometry(out, nb)[1] > 4 * cc.COST_MAX_BLOCKS
+    cost = (costs.LOGITCE, 0.0)
+    btot = nb + 40
+    table, n, w0, x, y, rng = _dense_problem(cc.head_dims(out), [cc.T, cc.I], btot, costs.LOGITCE, 7000 + out)
+    gpu_ctx.train_setup(table, n, w0, x, y, nb, 0, 0.1)
+    gpu_ctx.train_set_cost(*cost)
+    _check_against_definition(gpu_ctx, table, w0, x, y, rng.permutation(btot)[:nb], cost, "logitce lap out %d nb %d" % (out, nb))
+
+
+@pytest.mark.parametrize("out,nb", cc.LOGITCE_LAP_SHAPES)
+def test_f32_logitcrossentropy_beyond_one_lap(gpu_ctx, si, out, nb):
+    """the same shapes on the Float32 route, cost_logitce_kernel<float, float>; the bounds of test_f32_dense_step"""
+    assert cc.logitce_geometry(out, nb)[1] > 4 * cc.COST_MAX_BLOCKS
+    kind = costs.LOGITCE
+    dims = cc.head_dims(out)
+    btot = nb + 40
+    table, n, w0, x, y, rng = _dense_problem(dims, [cc.T, cc.I], btot, kind, 7100 + out, dtype=np.float32)
+    ids = rng.permutation(btot)[:nb]
+    gpu_ctx.train_setup(table, n, w0, x, y, nb, 0, 1.0)
+    assert gpu_ctx.train_compute_dtype() == si._capi.SI_F32
+    gpu_ctx.train_set_cost(kind, 0.0)
+    loss = gpu_ctx.train_step(ids)
+    g_dev = w0.astype(np.float64) - gpu_ctx.train_get_weights().astype(np.float64)
+    num, g64 = cc.reference(table, w0.astype(np.float64), x[:, ids].astype(np.float64), y[:, ids].astype(np.float64), kind)
+    l64 = num / costs.denominator(kind, out, nb)
+    err, bound = np.abs(g_dev - g64).max(), 3e-6 * np.abs(g64).max() + 1.2e-7 * np.abs(w0).max()
+    print("logitce lap f32", dims, nb, "loss", loss, l64, "err", err, "bound", bound)
+    assert np.isclose(loss, l64, rtol=2e-6), (loss, l64)
+    assert err <= bound, (err, bound)
+
+
 # ---- 6. determinism and the data-parallel scaling ----------------------------------------------------------------------------
 @pytest.mark.parametrize("out", [3, 10])
 @pytest.mark.parametrize("cost", cc.NEW_COSTS, ids=cc.cost_id)

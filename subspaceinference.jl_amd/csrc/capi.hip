@@ -113,6 +113,31 @@ void construct_install(Ctx* c, int64_t N, int32_t M, double* w_swa, double* P) {
   c->c_finished = true;
 }
 
+// ---- what a layer table means (ChainModel), decided here for the inference and the training set-up alike --------------------------
+int32_t chain_model_build(Ctx* ctx, const char* who, const si_layer* layers, int L, int64_t N, int32_t in_dim, int32_t out_dim, bool f32,
+                          int32_t node_d, ChainModel& m) {
+  m = ChainModel();
+  const int32_t rc = net_plan(ctx, who, layers, L, N, in_dim, node_d > 0 ? node_d : out_dim, m.plan);
+  if (rc != SI_OK) return rc;
+  m.layers.assign(layers, layers + L), m.N = N, m.in_dim = in_dim, m.out_dim = out_dim, m.f32 = f32;
+  m.fuse_tail = node_d == 0 && head_fused(m.plan, layers, L);
+  if (m.fuse_tail) {
+    const si_layer& lf = layers[L - 2];
+    m.fuse_slots = dense_fused_slots(lf.out);
+    // (the fp32 weight vector is 256-byte aligned and its slots are pad_ld(N) apart: a layer's W is 16-byte aligned iff w_off % 4 == 0)
+    if (f32) m.fuse_slots32 = dense_f32_fused_slots(lf.out, lf.in, lf.w_off % 4 == 0);
+  }
+  double main_flops = -1.0;
+  for (int l = 0; l < L; ++l) {
+    const LayerPlan& q = m.plan.L[(size_t)l];
+    const double fl = q.kind == SI_LAYER_DENSE ? 2.0 * q.in_feat * (double)q.out_feat
+                      : q.kind == SI_LAYER_CONV ? 2.0 * q.KW * q.KH * q.C * (double)q.Co * q.Wo * q.Ho : 0.0;
+    if (fl > main_flops) main_flops = fl, m.main_layer = l;
+    if (l < (m.fuse_tail ? L - 2 : L)) m.max_stored = std::max<int64_t>(m.max_stored, q.out_elems);
+  }
+  return SI_OK;
+}
+
 // ---- Dense chains: the forward pass, the reverse sweep and value + gradient, each written once for every entry point ------------
 // flops / bytes of one Dense launch over n chain slots in element type T; head: the narrow last layer computed in this layer's
 // epilogue (the layer then writes `slots` fp64 partial products per output instead of its activation, unless it is kept as well)
@@ -131,18 +156,21 @@ static DenseCost dense_cost(const si_layer& ly, const si_layer* head, int slots,
 template <typename T>
 const T* dense_forward(Ctx* ctx, hipStream_t st, const DenseForward<T>& a) {
   constexpr bool f64 = std::is_same<T, double>::value;
-  const size_t nl = a.nl, nplain = a.fuse_tail ? nl - 2 : nl;
+  const si_layer* layers = a.m->lay();
+  const bool fuse_tail = a.m->fuse_tail;
+  const size_t nl = a.m->layers.size(), nplain = fuse_tail ? nl - 2 : nl;
+  const int main_layer = a.count_main ? a.m->main_layer : -1;
   const int64_t B = a.B;
   ChainBatch cb = a.cb;
   cb.hin = 0;
   const T* h = a.X;
   for (size_t l = 0; l < nplain; ++l) {
-    const si_layer& ly = a.layers[l];
+    const si_layer& ly = layers[l];
     T* o = a.kept ? a.kept[l].get() : a.pingpong[l & 1];
     const DenseCost c = dense_cost<T>(ly, nullptr, 0, false, B, cb.n);
     {
       ProfScope ps(ctx, SI_K_DENSE, c.flops, a.traffic ? c.bytes : 0.0);
-      ProfScope pm((int)l == a.main_layer ? ctx : nullptr, SI_K_DENSE_MAIN, c.flops, c.bytes);
+      ProfScope pm((int)l == main_layer ? ctx : nullptr, SI_K_DENSE_MAIN, c.flops, c.bytes);
       if constexpr (f64)
         launch_dense_f64(st, a.w + ly.w_off, a.w + ly.b_off, h, o, ly.out, ly.in, B, ly.act, cb);
       else
@@ -151,16 +179,16 @@ const T* dense_forward(Ctx* ctx, hipStream_t st, const DenseForward<T>& a) {
     h = o;
     cb.hin = cb.hout;
   }
-  const si_layer& ll = a.layers[nl - 1];
+  const si_layer& ll = layers[nl - 1];
   const int64_t di = (int64_t)ll.out * B;
   const double d = (double)di, dn = (double)cb.n;
   Ctx* sse_prof = a.traffic ? ctx : nullptr;
-  if (a.fuse_tail) {
-    const si_layer& ly = a.layers[nl - 2];
+  if (fuse_tail) {
+    const si_layer& ly = layers[nl - 2];
     const DenseCost c = dense_cost<T>(ly, &ll, a.slots, a.kept != nullptr, B, cb.n);
     {
       ProfScope ps(ctx, SI_K_DENSE, c.flops, a.traffic ? c.bytes : 0.0);
-      ProfScope pm(((int)nl - 2 == a.main_layer || (int)nl - 1 == a.main_layer) ? ctx : nullptr, SI_K_DENSE_MAIN, c.flops, c.bytes);
+      ProfScope pm(((int)nl - 2 == main_layer || (int)nl - 1 == main_layer) ? ctx : nullptr, SI_K_DENSE_MAIN, c.flops, c.bytes);
       T* keep = a.kept ? a.kept[nl - 2].get() : nullptr;
       if constexpr (f64)
         launch_dense_f64_fused(st, a.w + ly.w_off, a.w + ly.b_off, h, ly.out, ly.in, B, ly.act, a.w + ll.w_off, ll.out, a.part, cb, keep);
@@ -187,28 +215,30 @@ template const float* dense_forward<float>(Ctx*, hipStream_t, const DenseForward
 // -- 3 % SLOWER at cfg2 (10.2-10.9 -> 10.5-11.1 ms per value + gradient): two GEMMs sharing the CUs lose more in the
 // caches than the idle slots and the fill / drain phases return.
 int32_t dense_reverse_sweep(Ctx* ctx, hipStream_t st, const DenseSweep& s) {
+  const si_layer* layers = s.m->lay();
+  const size_t nl = s.m->layers.size();
   int cur = 0;
-  size_t top = s.nl;          // layers [0, top) go through the generic sweep
+  size_t top = nl;            // layers [0, top) go through the generic sweep
   bool have_db = false;       // db of layer top-1 already produced by the fused tail
-  if (s.fuse_tail) {
+  if (s.m->fuse_tail) {
     // narrow head: Delta_{L-1}, dW_L and db_{L-1} in one pass over H_{L-1}
-    const si_layer& ll = s.layers[s.nl - 1];
-    const si_layer& lp = s.layers[s.nl - 2];
+    const si_layer& ll = layers[nl - 1];
+    const si_layer& lp = layers[nl - 2];
     launch_rowsum(st, s.delta[cur], ll.out, s.B, s.rspart, s.gw + ll.b_off);
-    launch_tail_bwd(st, s.w + ll.w_off, s.delta[cur], s.hs[s.nl - 2], ll.out, ll.in, s.B, lp.act, s.delta[cur ^ 1], s.bwpart,
+    launch_tail_bwd(st, s.w + ll.w_off, s.delta[cur], s.hs[nl - 2], ll.out, ll.in, s.B, lp.act, s.delta[cur ^ 1], s.bwpart,
                     s.gw + ll.w_off, s.gw + lp.b_off);
     cur ^= 1;
-    top = s.nl - 1;
+    top = nl - 1;
     have_db = true;
   }
   for (size_t li = top; li-- > 0;) {
-    const si_layer& ly = s.layers[li];
+    const si_layer& ly = layers[li];
     const double* hprev = li > 0 ? s.hs[li - 1] : s.X;
     // (db of this layer rides along with its weight gradient unless the fused tail has produced it already)
     launch_backward_weight(st, s.delta[cur], hprev, s.bwpart, ly.out, ly.in, s.B, ctx->num_cu, s.gw + ly.w_off,
                            (have_db && li + 1 == top) ? nullptr : s.gw + ly.b_off);
     if (li > 0) {
-      launch_backward_data(st, s.w + ly.w_off, s.delta[cur], hprev, s.delta[cur ^ 1], ly.out, ly.in, s.B, s.layers[li - 1].act);
+      launch_backward_data(st, s.w + ly.w_off, s.delta[cur], hprev, s.delta[cur ^ 1], ly.out, ly.in, s.B, layers[li - 1].act);
       cur ^= 1;
     }
   }
@@ -217,27 +247,30 @@ int32_t dense_reverse_sweep(Ctx* ctx, hipStream_t st, const DenseSweep& s) {
 
 int32_t dense_value_and_grad_f64(Ctx* ctx, hipStream_t st, const DenseValueGrad& s) {
   const DenseSweep& sw = s.sw;
-  const size_t nl = sw.nl;
+  const si_layer* layers = sw.m->lay();
+  const size_t nl = sw.m->layers.size();
   // a narrow head is fed from the epilogue of the layer in front of it, which stores its own output as well; the head's
   // outputs land in hs[nl - 1] either way
-  const DenseForward<double> fw{sw.layers, nl, sw.fuse_tail, sw.w, sw.w, sw.X, s.Y, sw.B, sw.hs, {nullptr, nullptr}, ChainBatch(), s.slots,
-                                s.part, sw.hs[nl - 1], s.ssepart, s.sse_blocks, s.sse, false, -1, s.traffic};
+  const DenseForward<double> fw{sw.m, sw.w, sw.w, sw.X, s.Y, sw.B, sw.hs, {nullptr, nullptr}, ChainBatch(), sw.m->fuse_slots,
+                                s.part, sw.hs[nl - 1], s.ssepart, s.sse_blocks, s.sse, false, false, s.traffic};
   dense_forward(ctx, st, fw);
   double bflops = 0.0;
-  for (size_t l = 0; l < nl; ++l) bflops += 4.0 * (double)sw.layers[l].in * sw.layers[l].out * (double)sw.B;
+  for (size_t l = 0; l < nl; ++l) bflops += 4.0 * (double)layers[l].in * layers[l].out * (double)sw.B;
   ProfScope ps(ctx, SI_K_BACKWARD, bflops, 0.0);
-  SI_HIP(ctx, hipMemsetAsync(sw.gw, 0, (size_t)pad_ld(s.N) * sizeof(double), st));
+  SI_HIP(ctx, hipMemsetAsync(sw.gw, 0, (size_t)pad_ld(sw.m->N) * sizeof(double), st));
   if (s.cost)   // (the head's outputs are in hs[nl - 1], fused or not)
-    launch_cost_tail<double>(st, *s.cost, s.Y, sw.hs[nl - 1], nullptr, sw.layers[nl - 1].out, sw.B, sw.layers[nl - 1].act, sw.delta[0], s.sse);
+    launch_cost_tail<double>(st, *s.cost, s.Y, sw.hs[nl - 1], nullptr, layers[nl - 1].out, sw.B, layers[nl - 1].act, sw.delta[0], s.sse);
   else
-    launch_delta_out(st, s.Y, sw.hs[nl - 1], (int64_t)sw.layers[nl - 1].out * sw.B, s.scale, sw.layers[nl - 1].act, sw.delta[0]);
+    launch_delta_out(st, s.Y, sw.hs[nl - 1], (int64_t)layers[nl - 1].out * sw.B, s.scale, layers[nl - 1].act, sw.delta[0]);
   return dense_reverse_sweep(ctx, st, sw);
 }
 
 // ---- the reverse-sweep workspace of a chain, sized here and nowhere else, and the dispatch over its three routes ---------------
-static bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const si_layer* layers, int L, bool fuse_tail, int64_t N, int32_t in_dim,
-                            int32_t out_dim, int64_t Bmax) {
-  size_t maxpart32 = 1, maxwt = 1, maxin = (size_t)in_dim, maxw = 1;
+static bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const ChainModel& m, int64_t Bmax) {
+  const si_layer* layers = m.lay();
+  const int L = m.L();
+  const bool fuse_tail = m.fuse_tail;
+  size_t maxpart32 = 1, maxwt = 1, maxin = (size_t)m.in_dim, maxw = 1;
   for (int l = 0; l < L; ++l) {
     maxpart32 = std::max(maxpart32, backward_weight_f32_part_elems(layers[l].out, layers[l].in, Bmax, ctx->num_cu));
     maxwt = std::max(maxwt, (size_t)layers[l].out * (size_t)layers[l].in);
@@ -246,23 +279,25 @@ static bool sweep_f32_alloc(Ctx* ctx, SweepF32Ws& ws, const si_layer* layers, in
   }
   const size_t wide = std::max(maxin, maxw);
   ws.hs32 = std::vector<DevBuf<float>>((size_t)L);
-  bool ok = ws.delta32[0].alloc(maxw * (size_t)Bmax) && ws.delta32[1].alloc(maxw * (size_t)Bmax) && ws.gw32.alloc((size_t)pad_ld(N)) &&
+  bool ok = ws.delta32[0].alloc(maxw * (size_t)Bmax) && ws.delta32[1].alloc(maxw * (size_t)Bmax) && ws.gw32.alloc((size_t)pad_ld(m.N)) &&
             ws.wt32.alloc(maxwt) && ws.zero32.alloc(wide) && ws.part32.alloc(maxpart32) &&
-            ws.rspart64.alloc(rowsum_f32_part_elems((int)wide)) && ws.yhat64.alloc((size_t)out_dim * (size_t)Bmax) &&
+            ws.rspart64.alloc(rowsum_f32_part_elems((int)wide)) && ws.yhat64.alloc((size_t)m.out_dim * (size_t)Bmax) &&
             (!fuse_tail || ws.tailpart64.alloc(tail_bwd_f32_part_elems(layers[L - 1].out, layers[L - 1].in)));
   for (int l = 0; l < L && ok; ++l)   // (a fused head's own output lives in yhat64)
     if (!(fuse_tail && l == L - 1)) ok = ws.hs32[(size_t)l].alloc((size_t)layers[l].out * (size_t)Bmax);
   return ok && hipMemsetAsync(ws.zero32, 0, wide * sizeof(float), ctx->stream) == hipSuccess;
 }
 
-bool sweep_ws_alloc(Ctx* ctx, SweepWs& ws, const si_layer* layers, int L, const NetPlan& plan, bool fuse_tail, int64_t N, int32_t in_dim,
-                    int32_t out_dim, int64_t Bmax, bool f32) {
+bool sweep_ws_alloc(Ctx* ctx, SweepWs& ws, const ChainModel& m, int64_t Bmax) {
+  const si_layer* layers = m.lay();
+  const NetPlan& plan = m.plan;
+  const int L = m.L();
   ws = SweepWs();
-  ws.route = plan.has_conv ? TrainRoute::Conv : f32 ? TrainRoute::DenseF32 : TrainRoute::DenseF64;
+  ws.route = plan.has_conv ? TrainRoute::Conv : m.f32 ? TrainRoute::DenseF32 : TrainRoute::DenseF64;
   const size_t bm = (size_t)Bmax;
   bool ok = true;
   if (ws.route == TrainRoute::DenseF32) {
-    ok = sweep_f32_alloc(ctx, ws.f32, layers, L, fuse_tail, N, in_dim, out_dim, Bmax);
+    ok = sweep_f32_alloc(ctx, ws.f32, m, Bmax);
   } else {
     size_t maxw = (size_t)plan.max_elems;   // rows of the two Delta buffers: the largest activation (Conv), the widest layer (Dense)
     if (ws.route == TrainRoute::Conv) {
@@ -278,7 +313,7 @@ bool sweep_ws_alloc(Ctx* ctx, SweepWs& ws, const si_layer* layers, int L, const 
         maxw = std::max(maxw, (size_t)layers[l].out);
         maxpart = std::max(maxpart, backward_weight_part_elems(layers[l].out, layers[l].in, Bmax, ctx->num_cu));
       }
-      if (fuse_tail) maxpart = std::max(maxpart, tail_bwd_part_elems(layers[L - 1].out, layers[L - 1].in));
+      if (m.fuse_tail) maxpart = std::max(maxpart, tail_bwd_part_elems(layers[L - 1].out, layers[L - 1].in));
       ok = ws.bwpart.alloc(maxpart) && ws.rspart.alloc((size_t)rowsum_chunks() * maxw);
     }
     ok = ok && ws.delta[0].alloc(maxw * bm) && ws.delta[1].alloc(maxw * bm);
@@ -299,21 +334,19 @@ int32_t chain_value_and_grad(Ctx* ctx, hipStream_t st, SweepWs& ws, const ChainV
   if (ws.route == TrainRoute::DenseF32) {
     // fp32 operands and activations on v_mfma_f32_32x32x2_f32; fp64 for the head's partial sums, the SSE and every sum over the
     // batch (rounded once into the fp32 gradient).  Behind it the gradient as every reader sees it: fp64 words holding fp32 values
-    const DenseSweepF32 sw{in.layers, in.nl, in.fuse_tail, in.w32, in.w64, in.X32, in.Y, &ws.f32, in.part, in.ssepart, in.sse, in.sse_blocks,
-                           in.B, in.N, in.scale, in.cost};
+    const DenseSweepF32 sw{in.m, in.w32, in.w64, in.X32, in.Y, &ws.f32, in.part, in.ssepart, in.sse, in.sse_blocks, in.B, in.scale, in.cost};
     const int32_t rc = dense_value_and_grad_f32(ctx, st, sw);
     if (rc != SI_OK) return rc;
-    launch_widen_f32_to_f64(st, ws.f32.gw32, in.N, in.gw, ctx->num_cu);
+    launch_widen_f32_to_f64(st, ws.f32.gw32, in.m->N, in.gw, ctx->num_cu);
     return SI_OK;
   }
   if (ws.route == TrainRoute::Conv) {   // Conv / MaxPool / flatten layers: the generic forward / reverse sweep of capi_net.hip
-    const NetValueGrad vg{in.plan, in.w64, in.plan->input_spatial ? in.Xc : in.X, in.Y, in.B, ws.hs.data(), in.wpack, in.ssepart, in.sse_blocks,
-                          in.sse, {ws.delta[0], ws.delta[1]}, in.gw, &ws.net, in.N, in.scale, in.bwd_flops, in.cost};
+    const NetValueGrad vg{&in.m->plan, in.w64, in.m->plan.input_spatial ? in.Xc : in.X, in.Y, in.B, ws.hs.data(), in.wpack, in.ssepart, in.sse_blocks,
+                          in.sse, {ws.delta[0], ws.delta[1]}, in.gw, &ws.net, in.m->N, in.scale, in.bwd_flops, in.cost};
     return net_value_and_grad(ctx, vg);
   }
-  const DenseValueGrad vg{{in.layers, in.nl, in.fuse_tail, in.w64, in.X, ws.hs.data(), {ws.delta[0], ws.delta[1]}, in.gw, ws.rspart, ws.bwpart,
-                           in.B},
-                          in.Y, in.fuse_slots, in.part, in.ssepart, in.sse, in.sse_blocks, in.N, in.scale, in.traffic, in.cost};
+  const DenseValueGrad vg{{in.m, in.w64, in.X, ws.hs.data(), {ws.delta[0], ws.delta[1]}, in.gw, ws.rspart, ws.bwpart, in.B},
+                          in.Y, in.part, in.ssepart, in.sse, in.sse_blocks, in.scale, in.traffic, in.cost};
   return dense_value_and_grad_f64(ctx, st, vg);
 }
 

@@ -21,9 +21,9 @@ int32_t si_fit_advi(si_ctx* ctx, int64_t max_iters, int32_t samples_per_step, do
   // (the comparisons are written so that a NaN refuses; S nblk < 2^24: the Philox block field of the step draws)
   const bool args_ok = T >= 1 && S >= 1 && W >= 1 && W <= 1024 && R >= 1 && chain_id0 >= 0 && sigma_z > 0.0 && tau > 0.0 && eta > 0.0 &&
                        D >= 0 && theta_out && (D == 0 || Z_out);
-  int32_t rc = grad_entry_check(ctx, who, args_ok);
+  int32_t rc = infer_entry_check(ctx, who, bad_if(!args_ok), SESSION_SHARED, true);
   if (rc != SI_OK) return rc;
-  const int32_t M = ctx->iM;
+  const int32_t M = ctx->setup.M;
   if ((int64_t)S * ((M + 1) / 2) >= ((int64_t)1 << 24) || (int64_t)R * S > INT32_MAX)
     return fail(ctx, SI_ERR_INVALID, std::string(who) + ": bad argument (samples_per_step * ceil(M / 2) must stay below 2^24)");
   BIND(ctx);

@@ -33,8 +33,7 @@ inline void accept_rates(const std::vector<int64_t>& nacc, int64_t itr, double* 
 namespace si {
 
 // What a density evaluation reads that depends on WHICH data set and WHICH workspace the call is for.  What belongs to the chain
-// set up stays on the context: layers and plan, fuse_tail, the slot counts, fw.w / fw.w32 / fw.wpack*, chains.zprop, chains.sse, chains.wsq, the
-// tile program.  setup_view is the view of the set-up's own data; si_predict builds one over its temporaries.
+// set up stays on the context: setup.model, fw.w / fw.w32 / fw.wpack*, chains.zprop, chains.sse, chains.wsq, the tile program.  setup_view is the view of the set-up's own data; si_predict builds one over its temporaries.
 struct DensityView {
   const double *X, *Xc;           // Xc: X re-laid channel-fastest (spatial input), else null
   const float* X32;               // X rounded to fp32 (f32), else null
@@ -50,33 +49,33 @@ struct DensityView {
   bool defer_sse_final;           // the SSE block partials stay in ssepart (the RWMH tail kernel sums them)
   bool is_setup_data;             // X, Y, B are the set-up's: what the narrow chain's plan and tile program were built for
 };
-// the rule, for si_infer_setup and si_train_setup alike: a narrow last layer (regression heads: out = 1) of a Dense chain is
-// folded into the epilogue of the layer before it (kernels_gemm.h carries the four MFMA-epilogue activations)
+struct DensityOutputs { const double* p = nullptr; int64_t stride = 0; };   // the fp64 model outputs of one pass of eval_density: chain slot j at p + j * stride
+// the narrow-head rule: a narrow last layer (regression heads: out = 1) of a Dense chain is folded into the epilogue of the layer
+// before it (kernels_gemm.h carries the four MFMA-epilogue activations)
 inline bool head_fused(const NetPlan& plan, const si_layer* layers, int L) {
   return !plan.has_conv && (L >= 2) && layers[L - 1].out <= SI_FUSE_MAX_OUT &&
          layers[L - 1].act < SI_ACT_LEAKYRELU && layers[L - 2].act < SI_ACT_LEAKYRELU;
 }
+// The ONE place a layer table becomes a ChainModel (capi.hip), for si_infer_setup* and si_train_setup* alike: net_plan, head_fused, the two kernels' slot
+// counts, the main layer, the widest stored output.  node_d > 0: a NeuralODE's right-hand side d -> ... -> d (no fused head; out_dim = the trajectories' d*S rows)
+int32_t chain_model_build(Ctx* ctx, const char* who, const si_layer* layers, int L, int64_t N, int32_t in_dim, int32_t out_dim, bool f32,
+                          int32_t node_d, ChainModel& out);
 // ---- the three value-and-gradient passes (dense_value_and_grad_f64 / _f32, net_value_and_grad) behind one workspace and one
 // dispatch (capi.hip), for si_logdensity_grad and the training step.  sweep_ws_alloc is the ONE place that decides how large a
 // reverse-sweep buffer is: the route follows from plan.has_conv and f32 (never both); on any failure ws is left empty.
-bool sweep_ws_alloc(Ctx* ctx, SweepWs& ws, const si_layer* layers, int L, const NetPlan& plan, bool fuse_tail, int64_t N, int32_t in_dim,
-                    int32_t out_dim, int64_t Bmax, bool f32);
+bool sweep_ws_alloc(Ctx* ctx, SweepWs& ws, const ChainModel& m, int64_t Bmax);
 // What differs between the callers of the pass.  chain_value_and_grad runs the route of `ws` on `st` (the context's stream) over
 // B <= Bmax observations and, on the fp32 route, widens gw32 into gw behind it: gw holds the gradient, *sse the sum of squared
 // errors (another cost: its numerator).
 struct ChainValueGrad {
-  const si_layer* layers;
-  size_t nl;
-  const NetPlan* plan;
-  bool fuse_tail;
+  const ChainModel* m;
   const double* w64;      // flat weights, and rounded to fp32 (DenseF32)
   const float* w32;
   const double *X, *Xc;   // input of layer 0; Xc: re-laid channel-fastest (a Conv chain on spatial input: net_input)
   const float* X32;       // (DenseF32)
   const double* Y;
-  int64_t B, N;
-  double* part;           // the forward pass's head partials and feature slots (the fp32 pass counts its own slots)
-  int fuse_slots;
+  int64_t B;
+  double* part;           // the forward pass's head partials (m->part_slots() feature slots)
   double *ssepart, *sse;
   int sse_blocks;
   double *gw, *wpack;     // wpack: packed conv weights (Conv)
@@ -98,7 +97,8 @@ extern "C" {   // (defined inside the extern "C" blocks of their translation uni
 int32_t ensure_chains(si_ctx* ctx, int32_t C);   // forward workspace + sampler state for C chains
 si::DensityView setup_view(const si_ctx* ctx, bool defer_sse_final = false);
 // chains.zprop[:, c0 .. c0+nc) -> chains.sse, nc <= the view's chain slots; eval_density_all: all C chains, fw.slots at a time
-int32_t eval_density(si_ctx* ctx, const si::DensityView& v, int c0, int nc, const double** yhat_out);
+// (out: where the pass left the fp64 model outputs, decided by the route that produced them; nullptr: not asked for)
+int32_t eval_density(si_ctx* ctx, const si::DensityView& v, int c0, int nc, si::DensityOutputs* out);
 int32_t eval_density_all(si_ctx* ctx, const si::DensityView& v, int C);
 // "form the weights of these points": w[:, c] = W_swa + P z_c (K4), or W_swa + decoder(z_c) while a decoder is set
 // (si_infer_set_decoder), for the n points z_dev[M x n] (device).  The one place the C ABI forms weights outside a sampler
@@ -118,7 +118,7 @@ double prior_sp2(const si_ctx* ctx);
 inline bool lik_on(const si_ctx* ctx) { return ctx->setup.lik != 0; }
 // capi_node.hip: the NeuralODE route behind eval_density and si_predict (node.on), and the part of its set-up that
 // infer_setup_common carries (capi_infer.hip)
-int32_t node_density(si_ctx* ctx, const si::DensityView& v, int c0, int nc, const double** yhat_out);
+int32_t node_density(si_ctx* ctx, const si::DensityView& v, int c0, int nc, si::DensityOutputs* out);
 int32_t node_predict(si_ctx* ctx, const double* Z, int32_t C, const double* U0new, int64_t Bn, double* U_out);
 int32_t infer_setup_node_base(si_ctx* ctx, const si_layer* layers, int32_t L, int64_t N, int32_t M, const double* W_swa, const double* P,
                               const double* U0, const double* Y, int32_t d, int32_t S, int64_t f);
@@ -133,7 +133,15 @@ int32_t node_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double* lp_out,
 // stream, reads the failure record back and returns SI_ERR_INVALID naming step, trajectory and status, once; SI_OK otherwise
 int32_t train_node_report(si_ctx* ctx, const char* who);
 void fused_fill_program(const si_ctx* ctx, si::ChainFusedPlan& fp);
-int32_t grad_entry_check(si_ctx* ctx, const char* who, bool args_ok);   // the gradient entry points' state rules and error texts
+// The state rules and error texts of the inference entry points, each sentence in one place.  need_setup: "call si_infer_setup first".
+// no_session: no step-wise session may be open (SESSION_SHARED names the shared proposal / SSE buffers, SESSION_SETTING is the setters'
+// shorter sentence, SESSION_ANY: not checked).  infer_entry_check is the sequence most entry points run: the set-up, with `grad` the gradient
+// entries' NeuralODE rule, the arguments (bad_args: nullptr when fine, else the text behind "who: "), the session; another order: the pieces.
+enum SessionRule { SESSION_ANY, SESSION_SHARED, SESSION_SETTING };
+int32_t need_setup(si_ctx* ctx, const char* who);
+int32_t no_session(si_ctx* ctx, const char* who, SessionRule rule);
+int32_t infer_entry_check(si_ctx* ctx, const char* who, const char* bad_args, SessionRule rule = SESSION_SHARED, bool grad = false);
+inline const char* bad_if(bool bad, const char* text = "bad argument") { return bad ? text : nullptr; }
 }
 
 namespace si {
@@ -181,7 +189,7 @@ int32_t reserve_state(si_ctx* ctx, const char* who, int& cap, int32_t C, Alloc&&
 // the context's ChainState for C chains: what si_sample_mala, si_sample_hmc and si_sample_nuts reserve first
 inline int32_t reserve_chain_state(si_ctx* ctx, const char* who, int32_t C) {
   ChainState& s = ctx->chain_state;
-  const size_t mc = (size_t)ctx->iM * (size_t)C;
+  const size_t mc = (size_t)ctx->setup.M * (size_t)C;
   return reserve_state(ctx, who, s.cap, C, [&] {
     return s.z.alloc(mc) && s.g.alloc(mc) && s.zp.alloc(mc) && s.gp.alloc(mc) && s.lp.alloc((size_t)C) && s.lpp.alloc((size_t)C);
   });
@@ -191,7 +199,7 @@ inline void chain_run_args(ChainRun& r, si_ctx* ctx, int64_t itr, double sigma_z
   ChainState& s = ctx->chain_state;
   r.z = s.z, r.lp = s.lp, r.g = s.g, r.zp = s.zp, r.lpp = s.lpp, r.gp = s.gp;
   r.Z_out = ctx->chains.outZ, r.lp_out = ctx->chains.outlp, r.G_out = want_G ? ctx->mala.outG.get() : nullptr;
-  r.M = ctx->iM, r.chain_id0 = chain_id0, r.itr = itr, r.seed = seed, r.sigma_z = sigma_z;
+  r.M = ctx->setup.M, r.chain_id0 = chain_id0, r.itr = itr, r.seed = seed, r.sigma_z = sigma_z;
 }
 
 // the value and gradient at the chains' proposals / pending points: (lpp, gp) at zp

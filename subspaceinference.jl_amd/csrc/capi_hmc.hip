@@ -47,7 +47,7 @@ int32_t hmc_windows(int64_t n_adapts, int64_t* window_start, int64_t* window_end
 }
 
 int32_t hmc_reserve_state(si_ctx* ctx, const char* who, int32_t C, bool nuts) {
-  const size_t mc = (size_t)ctx->iM * (size_t)C;
+  const size_t mc = (size_t)ctx->setup.M * (size_t)C;
   int32_t rc = reserve_chain_state(ctx, who, C);
   if (rc == SI_OK)
     rc = reserve_state(ctx, who, ctx->hmc.cap, C, [&] {
@@ -117,11 +117,11 @@ int32_t si_sample_hmc(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_z
   const char* who = "si_sample_hmc";
   ctx->hmc.info = CallInfo();   // (si_hmc_kernel_info reports THIS call)
   // (every comparison is false for a NaN: refused)
-  int32_t rc = grad_entry_check(ctx, who, itr > 0 && n_adapts >= 0 && n_adapts <= itr && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0 &&
-                                              delta > 0.0 && delta < 1.0);
+  int32_t rc = infer_entry_check(ctx, who, bad_if(!(itr > 0 && n_adapts >= 0 && n_adapts <= itr && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0 &&
+                                                  delta > 0.0 && delta < 1.0)), SESSION_SHARED, true);
   if (rc != SI_OK) return rc;
   BIND(ctx);
-  const int32_t C = nchains, M = ctx->iM;
+  const int32_t C = nchains, M = ctx->setup.M;
   const int64_t cols = itr + 1;
   if ((rc = hmc_reserve_state(ctx, who, C, false)) != SI_OK) return rc;
   const size_t zelems = (size_t)M * (size_t)cols * (size_t)C, selems = (size_t)cols * (size_t)C;

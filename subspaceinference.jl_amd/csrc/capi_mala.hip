@@ -14,10 +14,10 @@ int32_t si_sample_mala(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, 
   CHECK_CTX(ctx);
   const char* who = "si_sample_mala";
   ctx->mala.info = CallInfo();   // (si_mala_kernel_info reports THIS call)
-  int32_t rc = grad_entry_check(ctx, who, itr > 0 && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0);
+  int32_t rc = infer_entry_check(ctx, who, bad_if(!(itr > 0 && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0)), SESSION_SHARED, true);
   if (rc != SI_OK) return rc;
   BIND(ctx);
-  const int32_t C = nchains, M = ctx->iM;
+  const int32_t C = nchains, M = ctx->setup.M;
   if ((rc = reserve_chain_state(ctx, who, C)) != SI_OK) return rc;
   if ((rc = reserve_state(ctx, who, ctx->mala.cap, C, [&] { return ctx->mala.nacc.alloc((size_t)C); })) != SI_OK) return rc;
   const size_t zelems = (size_t)M * (size_t)itr * (size_t)C;

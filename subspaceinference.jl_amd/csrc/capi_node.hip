@@ -57,7 +57,7 @@ namespace {
 NodeArgs node_args(const si_ctx* ctx, const double* w, const double* U0, const double* Y, int64_t f, double* sse_p, double* U_out,
                    int32_t* nacc, int32_t* nrej, int32_t* status) {
   NodeArgs a = ctx->node.args;
-  a.w = w, a.ldw = pad_ld(ctx->iN);
+  a.w = w, a.ldw = pad_ld(ctx->setup.model.N);
   a.U0 = U0, a.Y = Y, a.f = f;
   a.ts = ctx->node.ts;
   a.sse_p = sse_p, a.U_out = U_out, a.nacc = nacc, a.nrej = nrej, a.status = status;
@@ -77,25 +77,28 @@ int32_t node_reserve(si_ctx* ctx, size_t ssep, size_t uout) {
 
 extern "C" {
 
-int32_t node_density(si_ctx* ctx, const DensityView& v, int c0, int nc, const double** yhat_out) {
-  const int64_t N = ctx->iN, ldw = pad_ld(N), f = v.B;
-  const int32_t M = ctx->iM;
+static int32_t need_node_setup(si_ctx* ctx, const char* who) {
+  return ctx->setup.ready && ctx->node.on ? SI_OK : fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_infer_setup_node first");
+}
+int32_t node_density(si_ctx* ctx, const DensityView& v, int c0, int nc, DensityOutputs* out) {
+  const int64_t N = ctx->setup.model.N, ldw = pad_ld(N), f = v.B;
+  const int32_t M = ctx->setup.M;
   const size_t traj = (size_t)ctx->node.d * (size_t)ctx->node.S * (size_t)f;
-  int32_t rc = node_reserve(ctx, (size_t)f * (size_t)nc, yhat_out ? traj * (size_t)nc : 0);
+  int32_t rc = node_reserve(ctx, (size_t)f * (size_t)nc, out ? traj * (size_t)nc : 0);
   if (rc != SI_OK) return rc;
   {
     ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)N * M * nc, (double)N * (M + 1 + nc) * 8.0);
     if ((rc = form_weights(ctx, ctx->chains.zprop + (size_t)c0 * M, nc, ctx->fw.w, ldw)) != SI_OK) return rc;
   }
-  launch_sse(ctx->stream, ctx->fw.w, nullptr, N, ctx->fw.wsqpart, ctx->wsq_blocks, ctx->chains.wsq + c0, nc, ldw);   // ||W||^2 per chain
+  launch_sse(ctx->stream, ctx->fw.w, nullptr, N, ctx->fw.wsqpart, ctx->setup.wsq_blocks, ctx->chains.wsq + c0, nc, ldw);   // ||W||^2 per chain
   {
     ProfScope ps(ctx, SI_K_DENSE, 0.0, 0.0);
-    const NodeArgs a = node_args(ctx, ctx->fw.w, v.X, v.Y, f, ctx->node.ssep, yhat_out ? ctx->node.uout.get() : nullptr, nullptr, nullptr, nullptr);
+    const NodeArgs a = node_args(ctx, ctx->fw.w, v.X, v.Y, f, ctx->node.ssep, out ? ctx->node.uout.get() : nullptr, nullptr, nullptr, nullptr);
     SI_HIP(ctx, launch_node_solve(ctx->stream, a, nc));
     launch_node_sum(ctx->stream, ctx->node.ssep, f, ctx->chains.sse + c0, nc);
   }
   SI_HIP(ctx, hipGetLastError());
-  if (yhat_out) *yhat_out = ctx->node.uout;
+  if (out) *out = {ctx->node.uout, (int64_t)traj};
   return SI_OK;
 }
 
@@ -129,14 +132,12 @@ int32_t si_infer_setup_node(si_ctx* ctx, const si_layer* layers, int32_t L, int6
 int32_t si_node_solve(si_ctx* ctx, const double* Z, int32_t C, double* U_out, double* sse_out, int32_t* naccept_out,
                       int32_t* nreject_out, int32_t* status_out) {
   CHECK_CTX(ctx);
-  if (!ctx->setup.ready || !ctx->node.on) return fail(ctx, SI_ERR_STATE, "si_node_solve: call si_infer_setup_node first");
-  if (!Z || C <= 0) return fail(ctx, SI_ERR_INVALID, "si_node_solve: bad argument");
-  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_node_solve: a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
+  int32_t rc = need_node_setup(ctx, "si_node_solve");
+  if (rc != SI_OK || (rc = infer_entry_check(ctx, "si_node_solve", bad_if(!Z || C <= 0))) != SI_OK) return rc;
   BIND(ctx);
-  int32_t rc = ensure_chains(ctx, C);
-  if (rc != SI_OK) return rc;
-  const int64_t N = ctx->iN, ldw = pad_ld(N), f = ctx->B;
-  const int32_t M = ctx->iM;
+  if ((rc = ensure_chains(ctx, C)) != SI_OK) return rc;
+  const int64_t N = ctx->setup.model.N, ldw = pad_ld(N), f = ctx->setup.B;
+  const int32_t M = ctx->setup.M;
   const size_t traj = (size_t)ctx->node.d * (size_t)ctx->node.S * (size_t)f;
   // an audit read-back, not a hot path: fw.slots chains per pass (at most 256 MB of saved states), one synchronisation per pass
   int wb = std::max(1, std::min<int>(ctx->fw.slots, C));
@@ -165,8 +166,8 @@ int32_t si_node_solve(si_ctx* ctx, const double* Z, int32_t C, double* U_out, do
 
 // si_predict in a node set-up: the saved states from new initial conditions U0new (d x Bn) at Z[:, c], d*S x Bn x C
 int32_t node_predict(si_ctx* ctx, const double* Z, int32_t C, const double* U0new, int64_t Bn, double* U_out) {
-  const int64_t N = ctx->iN, ldw = pad_ld(N);
-  const int32_t M = ctx->iM, d = ctx->node.d;
+  const int64_t N = ctx->setup.model.N, ldw = pad_ld(N);
+  const int32_t M = ctx->setup.M, d = ctx->node.d;
   const size_t traj = (size_t)d * (size_t)ctx->node.S * (size_t)Bn;
   const int wb = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min<int>(ctx->fw.slots, C), ((size_t)32 << 20) / traj));
   DevBuf<double> dX, dU, dS;
@@ -190,7 +191,7 @@ int32_t node_predict(si_ctx* ctx, const double* Z, int32_t C, const double* U0ne
 // the bytes one chain of a pass needs: its record (f * max_steps * (d + 2) doubles) and its per-trajectory gradient slices (f * N)
 static double node_grad_chain_bytes(const si_ctx* ctx) {
   const NodeArgs& a = ctx->node.args;
-  return 8.0 * (double)ctx->B * ((double)a.max_steps * (double)(a.d + 2) + (double)ctx->iN);
+  return 8.0 * (double)ctx->setup.B * ((double)a.max_steps * (double)(a.d + 2) + (double)ctx->setup.model.N);
 }
 
 static void node_grad_drop(NodeState& n) {
@@ -201,8 +202,8 @@ static void node_grad_drop(NodeState& n) {
 
 int32_t si_node_set_grad(si_ctx* ctx, int32_t on) {
   CHECK_CTX(ctx);
-  if (!ctx->setup.ready || !ctx->node.on) return fail(ctx, SI_ERR_STATE, "si_node_set_grad: call si_infer_setup_node first");
-  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_node_set_grad: a step-wise RWMH session is open");
+  int32_t rc0 = need_node_setup(ctx, "si_node_set_grad");
+  if (rc0 != SI_OK || (rc0 = no_session(ctx, "si_node_set_grad", SESSION_SETTING)) != SI_OK) return rc0;
   if (on != 0 && on != 1) return fail(ctx, SI_ERR_INVALID, "si_node_set_grad: on must be 0 or 1");
   BIND(ctx);
   NodeState& n = ctx->node;
@@ -237,9 +238,9 @@ int32_t node_grad_ensure(si_ctx* ctx, const char* who, int32_t C) {
   if (n.g_cap >= cap) return SI_OK;
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   node_grad_drop(n);
-  const size_t S = (size_t)cap, f = (size_t)ctx->B, N = (size_t)ctx->iN, ldw = (size_t)pad_ld(ctx->iN), M = (size_t)ctx->iM;
+  const size_t S = (size_t)cap, f = (size_t)ctx->setup.B, N = (size_t)ctx->setup.model.N, ldw = (size_t)pad_ld(ctx->setup.model.N), M = (size_t)ctx->setup.M;
   const bool ok = n.g_z.alloc(S * M) && n.g_w.alloc(S * ldw) && n.g_ssep.alloc(S * f) && n.g_sse.alloc(S) && n.g_wsq.alloc(S) &&
-                  n.g_wsqpart.alloc(S * (size_t)ctx->wsq_blocks) && n.g_rec.alloc(S * f * (size_t)n.args.max_steps * (size_t)(n.d + 2)) &&
+                  n.g_wsqpart.alloc(S * (size_t)ctx->setup.wsq_blocks) && n.g_rec.alloc(S * f * (size_t)n.args.max_steps * (size_t)(n.d + 2)) &&
                   n.g_slices.alloc(S * f * N) && n.g_gw.alloc(S * ldw) && n.g_lp.alloc(S) && n.g_gz.alloc(S * M) && n.g_cnt.alloc(3 * S * f) &&
                   ctx->grad.ptgpart.reserve((size_t)ptg_blocks() * M);
   if (!ok) {
@@ -256,9 +257,9 @@ int32_t node_grad_ensure(si_ctx* ctx, const char* who, int32_t C) {
 // the weights are in g_w: ||W||^2, the forward with record, the reverse kernel, the sums (gw without the prior term, lp)
 static int32_t node_grad_launches(si_ctx* ctx, int32_t nc, double* lp_dev) {
   NodeState& n = ctx->node;
-  const int64_t N = ctx->iN, ldw = pad_ld(N), f = ctx->B;
+  const int64_t N = ctx->setup.model.N, ldw = pad_ld(N), f = ctx->setup.B;
   const size_t fc = (size_t)f * (size_t)n.g_cap;
-  launch_sse(ctx->stream, n.g_w, nullptr, N, n.g_wsqpart, ctx->wsq_blocks, n.g_wsq, nc, ldw);
+  launch_sse(ctx->stream, n.g_w, nullptr, N, n.g_wsqpart, ctx->setup.wsq_blocks, n.g_wsq, nc, ldw);
   SI_HIP(ctx, hipMemsetAsync(n.g_slices, 0, (size_t)nc * (size_t)f * (size_t)N * sizeof(double), ctx->stream));   // "from 0.0"
   NodeArgs a = node_args(ctx, n.g_w, ctx->setup.X, ctx->setup.Y, f, n.g_ssep, nullptr, n.g_cnt, n.g_cnt + fc, n.g_cnt + 2 * fc);
   a.rec = n.g_rec, a.gsl = n.g_slices;
@@ -279,21 +280,21 @@ static int32_t node_grad_launches(si_ctx* ctx, int32_t nc, double* lp_dev) {
 
 int32_t node_value_and_grad(si_ctx* ctx, const double* z_dev, int32_t nc, double* lp_dev, double* gz_dev) {
   NodeState& n = ctx->node;
-  const int64_t ldw = pad_ld(ctx->iN);
+  const int64_t ldw = pad_ld(ctx->setup.model.N);
   int32_t rc;
   {
-    ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)ctx->iN * ctx->iM * nc, (double)ctx->iN * (ctx->iM + 1 + nc) * 8.0);
+    ProfScope ps(ctx, SI_K_RECON, 2.0 * (double)ctx->setup.model.N * ctx->setup.M * nc, (double)ctx->setup.model.N * (ctx->setup.M + 1 + nc) * 8.0);
     if ((rc = form_weights(ctx, z_dev, nc, n.g_w, ldw, nullptr, /*keep_y=*/ctx->dec.on)) != SI_OK) return rc;
   }
   if ((rc = node_grad_launches(ctx, nc, lp_dev)) != SI_OK) return rc;
-  for (int32_t c = 0; c < nc; ++c) pull_back_to_z(ctx, n.g_gw + (size_t)ldw * c, gz_dev + (size_t)ctx->iM * c);   // queued per point
+  for (int32_t c = 0; c < nc; ++c) pull_back_to_z(ctx, n.g_gw + (size_t)ldw * c, gz_dev + (size_t)ctx->setup.M * c);   // queued per point
   SI_HIP(ctx, hipGetLastError());
   return SI_OK;
 }
 
 int32_t node_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* grad_out) {
   NodeState& n = ctx->node;
-  const size_t M = (size_t)ctx->iM;
+  const size_t M = (size_t)ctx->setup.M;
   int32_t rc = node_grad_ensure(ctx, "si_logdensity_grad", 1);
   if (rc != SI_OK) return rc;
   SI_HIP(ctx, hipMemcpyAsync(n.g_z, z, M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -306,7 +307,7 @@ int32_t node_grad_point(si_ctx* ctx, const double* z, double* lp_out, double* gr
 
 int32_t node_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double* lp_out, double* grad_out) {
   NodeState& n = ctx->node;
-  const size_t M = (size_t)ctx->iM;
+  const size_t M = (size_t)ctx->setup.M;
   int32_t rc = node_grad_ensure(ctx, "si_logdensity_grad_batch", C);
   if (rc != SI_OK) return rc;
   for (int32_t c0 = 0; c0 < C; c0 += n.g_cap) {
@@ -323,12 +324,13 @@ int32_t node_grad_batch(si_ctx* ctx, const double* Z, int32_t C, double* lp_out,
 // the audit read-back: lp (C), d lp / dW (N x C, the prior term included) and its pull-back (M x C) at Z[:, c]; either seam
 int32_t si_node_grad(si_ctx* ctx, const double* Z, int32_t C, double* lp_out, double* gw_out, double* gz_out) {
   CHECK_CTX(ctx);
-  if (!ctx->setup.ready || !ctx->node.on) return fail(ctx, SI_ERR_STATE, "si_node_grad: call si_infer_setup_node first");
-  int32_t rc = grad_entry_check(ctx, "si_node_grad", Z && C >= 1);
+  int32_t rc = need_node_setup(ctx, "si_node_grad");
+  if (rc != SI_OK) return rc;
+  rc = infer_entry_check(ctx, "si_node_grad", bad_if(!Z || C < 1), SESSION_SHARED, true);
   if (rc != SI_OK) return rc;
   BIND(ctx);
   NodeState& n = ctx->node;
-  const size_t M = (size_t)ctx->iM, N = (size_t)ctx->iN, ldw = (size_t)pad_ld(ctx->iN);
+  const size_t M = (size_t)ctx->setup.M, N = (size_t)ctx->setup.model.N, ldw = (size_t)pad_ld(ctx->setup.model.N);
   const int32_t want = ctx->dec.on ? 1 : C;   // (the decoder's reverse holds one point: column by column)
   if ((rc = node_grad_ensure(ctx, "si_node_grad", want)) != SI_OK) return rc;
   const int32_t step = ctx->dec.on ? 1 : n.g_cap;
@@ -370,7 +372,7 @@ int32_t si_node_info(si_ctx* ctx, int32_t* active_out, int32_t* d_out, int32_t* 
   if (active_out) *active_out = on ? 1 : 0;
   if (d_out) *d_out = on ? ctx->node.d : 0;
   if (S_out) *S_out = on ? ctx->node.S : 0;
-  if (f_out) *f_out = on ? ctx->B : 0;
+  if (f_out) *f_out = on ? ctx->setup.B : 0;
   if (G_out) *G_out = on ? ctx->node.args.G : 0;
   return SI_OK;
 }

@@ -20,12 +20,12 @@ int32_t si_sample_nuts(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_
   const char* who = "si_sample_nuts";
   ctx->nuts.info = CallInfo();   // (si_nuts_kernel_info reports THIS call)
   // (every comparison is false for a NaN: refused)
-  int32_t rc = grad_entry_check(ctx, who, itr > 0 && n_adapts >= 0 && n_adapts <= itr && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0 &&
-                                              delta > 0.0 && delta < 1.0 && max_depth >= 1 && max_depth <= NUTS_MAX_DEPTH && max_dh > 0.0 &&
-                                              (!leaf_out || leaf_cap >= 1));
+  int32_t rc = infer_entry_check(ctx, who, bad_if(!(itr > 0 && n_adapts >= 0 && n_adapts <= itr && nchains > 0 && chain_id0 >= 0 && sigma_z > 0.0 &&
+                                                  delta > 0.0 && delta < 1.0 && max_depth >= 1 && max_depth <= NUTS_MAX_DEPTH && max_dh > 0.0 &&
+                                                  (!leaf_out || leaf_cap >= 1))), SESSION_SHARED, true);
   if (rc != SI_OK) return rc;
   BIND(ctx);
-  const int32_t C = nchains, M = ctx->iM;
+  const int32_t C = nchains, M = ctx->setup.M;
   const int64_t cols = itr + 1;
   if ((rc = hmc_reserve_state(ctx, who, C, true)) != SI_OK) return rc;
   const size_t zelems = (size_t)M * (size_t)cols * (size_t)C, selems = (size_t)cols * (size_t)C;

@@ -36,19 +36,19 @@ static void free_wstream(si_ctx* ctx) {
 }
 
 static int32_t ensure_wstream(si_ctx* ctx, int32_t C) {
-  const size_t need = (size_t)C * (size_t)pad_ld(ctx->iN);
+  const size_t need = (size_t)C * (size_t)pad_ld(ctx->setup.model.N);
   if (!ctx->stream2) SI_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-  if (ctx->wring_N == ctx->iN && ctx->wring_C >= C) return SI_OK;
+  if (ctx->wring_N == ctx->setup.model.N && ctx->wring_C >= C) return SI_OK;
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   free_wstream(ctx);
   bool ok = ctx->d_wring.alloc(need * SI_WRING) && ctx->d_accflag.alloc((size_t)C);
   for (int r = 0; r < SI_WRING && ok; ++r)
-    ok = ctx->h_wring[r].alloc((size_t)C * (size_t)ctx->iN) && ctx->ev_wcomp[r].create() && ctx->ev_wcopy[r].create();
+    ok = ctx->h_wring[r].alloc((size_t)C * (size_t)ctx->setup.model.N) && ctx->ev_wcomp[r].create() && ctx->ev_wcopy[r].create();
   if (!ok) {
     free_wstream(ctx);
     return fail(ctx, SI_ERR_NOMEM, "si_sample_rwmh_weights: allocation of the weight ring / pinned staging failed");
   }
-  ctx->wring_N = ctx->iN;
+  ctx->wring_N = ctx->setup.model.N;
   ctx->wring_C = C;
   return SI_OK;
 }
@@ -58,12 +58,12 @@ static int32_t ensure_wstream(si_ctx* ctx, int32_t C) {
 // launches per transition spread over the chip (2 N B <= 3 MFLOP: the README toy is 0.14)
 static constexpr size_t SI_CHAIN_LDS_LIMIT = 160 * 1024 - 256;
 static bool chain_loop_applies(const si_ctx* ctx) {
-  if (ctx->setup.f32 || ctx->setup.plan.has_conv || !ctx->setup.fuse_tail || ctx->setup.sigma_p > 0.0 || ctx->dec.on || lik_on(ctx)) return false;   // (dec: the loop forms W_swa + P z itself; lik: it forms the squared errors itself)
-  if (ctx->layers.size() > (size_t)SI_CHAIN_MAX_LAYERS || ctx->iN > (1 << 20) || ctx->B > (1 << 20)) return false;
-  if (ctx->iM > 1024) return false;   // (rwmh_chain_kernel keeps z one element per thread of its 1024-thread workgroup)
-  for (const auto& ly : ctx->layers)
+  if (ctx->setup.model.f32 || ctx->setup.model.plan.has_conv || !ctx->setup.model.fuse_tail || ctx->setup.sigma_p > 0.0 || ctx->dec.on || lik_on(ctx)) return false;   // (dec: the loop forms W_swa + P z itself; lik: it forms the squared errors itself)
+  if (ctx->setup.model.layers.size() > (size_t)SI_CHAIN_MAX_LAYERS || ctx->setup.model.N > (1 << 20) || ctx->setup.B > (1 << 20)) return false;
+  if (ctx->setup.M > 1024) return false;   // (rwmh_chain_kernel keeps z one element per thread of its 1024-thread workgroup)
+  for (const auto& ly : ctx->setup.model.layers)
     if (ly.kind != SI_LAYER_DENSE || ly.act >= SI_ACT_LEAKYRELU) return false;
-  return 2.0 * (double)ctx->iN * (double)ctx->B <= 3.0e6;
+  return 2.0 * (double)ctx->setup.model.N * (double)ctx->setup.B <= 3.0e6;
 }
 
 // The common end of the three sampler forms.  `e` is the state of what the form has queued so far.  Z / lp (from chains.outZ /
@@ -73,8 +73,8 @@ static bool chain_loop_applies(const si_ctx* ctx) {
 // of the grid loop (grid_status) is one; the accept rates are filled in.
 static int32_t finish_chains(si_ctx* ctx, const char* who, hipError_t e, int64_t itr, int32_t C, double* Z_out, double* lp_out,
                              double* accept_rate_out, double* W_out, size_t wall_elems, char* stage, const unsigned* grid_status) {
-  const int32_t M = ctx->iM;
-  const int64_t N = ctx->iN, ldw = pad_ld(N);
+  const int32_t M = ctx->setup.M;
+  const int64_t N = ctx->setup.model.N, ldw = pad_ld(N);
   const size_t zbytes = Z_out ? (size_t)M * itr * C * sizeof(double) : 0, lbytes = lp_out ? (size_t)itr * C * sizeof(double) : 0;
   std::vector<int64_t> nacc((size_t)C);
   if (e == hipSuccess && Z_out) e = hipMemcpyAsync(stage ? (void*)stage : (void*)Z_out, ctx->chains.outZ, zbytes, hipMemcpyDeviceToHost, ctx->stream);
@@ -127,8 +127,8 @@ extern "C++" template <typename Args>
 static void fill_common_args(Args& a, const si_ctx* ctx, const RwmhCall& k) {
   a.swa = ctx->setup.swa; a.P = ctx->setup.P; a.X = ctx->setup.X; a.Y = ctx->setup.Y;
   a.Z_out = ctx->chains.outZ; a.lp_out = ctx->chains.outlp; a.nacc_out = reinterpret_cast<decltype(a.nacc_out)>(ctx->chains.nacc.get());
-  a.ldP = ctx->ldP; a.itr = k.itr; a.seed = k.seed; a.sigma_z = k.sigma_z; a.c0 = k.c0; a.sigma2 = k.s2;
-  a.N = (int)ctx->iN; a.chain_id0 = k.chain_id0;
+  a.ldP = ctx->setup.ldP; a.itr = k.itr; a.seed = k.seed; a.sigma_z = k.sigma_z; a.c0 = k.c0; a.sigma2 = k.s2;
+  a.N = (int)ctx->setup.model.N; a.chain_id0 = k.chain_id0;
 }
 
 // ---- K6 as a device-resident loop (kernels_chain.hip): small Dense chains whose weights, data and activations fit one
@@ -139,16 +139,16 @@ static void fill_common_args(Args& a, const si_ctx* ctx, const RwmhCall& k) {
 static int32_t rwmh_one_workgroup(si_ctx* ctx, const RwmhCall& k) {
   if (!k.map_fits || !chain_loop_applies(ctx) || ctx->chain_mode != 1) return SI_NOT_TAKEN;
   ChainLoopArgs a{};
-  const int L = (int)ctx->layers.size();
-  for (int l = 0; l < L; ++l) a.lay[l] = ctx->layers[(size_t)l];
+  const int L = (int)ctx->setup.model.layers.size();
+  for (int l = 0; l < L; ++l) a.lay[l] = ctx->setup.model.layers[(size_t)l];
   fill_common_args(a, ctx, k);
-  a.M = ctx->iM; a.B = (int)ctx->B; a.L = L;
-  a.slot_feats = dense_fused_slot_feats(ctx->layers[(size_t)L - 2].out);
-  a.fuse_slots = ctx->fuse_slots;
+  a.M = ctx->setup.M; a.B = (int)ctx->setup.B; a.L = L;
+  a.slot_feats = dense_fused_slot_feats(ctx->setup.model.layers[(size_t)L - 2].out);
+  a.fuse_slots = ctx->setup.model.fuse_slots;
   const size_t lds = chain_loop_plan(a, SI_CHAIN_LDS_LIMIT);
   if (lds == 0) return SI_NOT_TAKEN;
   {
-    const double fl = 2.0 * (double)ctx->iN * (double)ctx->B * (double)k.itr * k.C;
+    const double fl = 2.0 * (double)ctx->setup.model.N * (double)ctx->setup.B * (double)k.itr * k.C;
     ProfScope ps(ctx, SI_K_RWMH, fl, 0.0);
     launch_chain_loop(ctx->stream, a, k.C, lds);
   }
@@ -162,16 +162,16 @@ static int32_t rwmh_one_workgroup(si_ctx* ctx, const RwmhCall& k) {
 // SI_OK (not of the class: the generic loop runs) or the call's error.
 static const SpecKernels* prepare_spec_loop(si_ctx* ctx, const RwmhCall& k, int G, int nb, int sf, SiSpecGridArgs& sa, size_t* lds_spec,
                                             int32_t* rc) {
-  const int32_t C = k.C, M = ctx->iM;
-  const int64_t N = ctx->iN, d = (int64_t)ctx->out_dim * ctx->B;
+  const int32_t C = k.C, M = ctx->setup.M;
+  const int64_t N = ctx->setup.model.N, d = (int64_t)ctx->setup.model.out_dim * ctx->setup.B;
   *rc = SI_OK;
   auto bad = [&](int32_t code, const char* what) {
     *rc = fail(ctx, code, std::string(k.who) + what);
     return (const SpecKernels*)nullptr;
   };
-  if (!ctx->chain_spec || !ctx->setup.fuse_tail || d > 1024 || M > 256) return nullptr;
+  if (!ctx->chain_spec || !ctx->setup.model.fuse_tail || d > 1024 || M > 256) return nullptr;
   const int rs = (int)((((N + G - 1) / G) + 15) & ~(int64_t)15);
-  const SpecKernels* sk = spec_kernels(ctx->layers.data(), (int)ctx->layers.size(), nb, sf, M, rs <= 256 && M <= 32, &ctx->spec_message);
+  const SpecKernels* sk = spec_kernels(ctx->setup.model.layers.data(), (int)ctx->setup.model.layers.size(), nb, sf, M, rs <= 256 && M <= 32, &ctx->spec_message);
   if (!sk) return nullptr;
   auto even = [](int64_t v) { return (v + 1) & ~(int64_t)1; };
   int64_t off = sk->lds_doubles;
@@ -179,7 +179,7 @@ static const SpecKernels* prepare_spec_loop(si_ctx* ctx, const RwmhCall& k, int 
   sa.o_y = (int)off;
   off += even(d);
   sa.o_blk = (int)off;
-  off += even(ctx->sse_blocks);
+  off += even(ctx->setup.sse_blocks);
   sa.o_z = (int)off;
   off += even(5 * (int64_t)M);
   sa.o_red = (int)off;
@@ -216,22 +216,22 @@ static const SpecKernels* prepare_spec_loop(si_ctx* ctx, const RwmhCall& k, int 
 // workgroup (docs/src/nn_example.md's MLP) runs all transitions in one launch, G = ceil(B / tile) resident workgroups per
 // chain, two bounded grid barriers per transition.  Same bits as the launch-per-step loop (tests/test_gpu_chain_grid.py).
 static int32_t rwmh_grid(si_ctx* ctx, const RwmhCall& k) {
-  const int32_t C = k.C, M = ctx->iM;
+  const int32_t C = k.C, M = ctx->setup.M;
   if (!k.map_fits || !ctx->setup.fused_ok || ctx->chain_mode != 1 || ctx->setup.sigma_p > 0.0 || C > ctx->fw.slots || k.itr >= ((int64_t)1 << 24) ||
       ctx->dec.on || lik_on(ctx))   // (both grid loops, the run-time specialised one included, form W_swa + P z in their own K4 and the squared errors in their own tail)
     return SI_NOT_TAKEN;
   ChainGridArgs a{};
-  const int L = (int)ctx->layers.size();
-  const int sf = ctx->setup.fuse_tail ? dense_fused_slot_feats(ctx->layers[(size_t)L - 2].out) : 0;
+  const int L = (int)ctx->setup.model.layers.size();
+  const int sf = ctx->setup.model.fuse_tail ? dense_fused_slot_feats(ctx->setup.model.layers[(size_t)L - 2].out) : 0;
   int nb = 0;
   size_t lds = 0;
   for (int cand : {1, 2, 4}) {   // the smallest tile whose grid is resident: one workgroup per CU
-    const int64_t G = (ctx->B + 16 * cand - 1) / (16 * cand);
+    const int64_t G = (ctx->setup.B + 16 * cand - 1) / (16 * cand);
     if (G * C > ctx->num_cu) continue;
-    const size_t lf = chain_fused_plan(a.p, ctx->layers.data(), L, ctx->B, cand, ctx->setup.fuse_tail, sf, ctx->fuse_slots);
+    const size_t lf = chain_fused_plan(a.p, ctx->setup.model.layers.data(), L, ctx->setup.B, cand, ctx->setup.model.fuse_tail, sf, ctx->setup.model.fuse_slots);
     fused_fill_program(ctx, a.p);
     a.M = M;
-    a.nblocks = ctx->sse_blocks;
+    a.nblocks = ctx->setup.sse_blocks;
     a.G = (int)G;
     lds = chain_grid_plan(a, lf);
     if (lds != 0) {
@@ -248,12 +248,12 @@ static int32_t rwmh_grid(si_ctx* ctx, const RwmhCall& k) {
   const size_t sync_lines = sk ? (size_t)8 * (size_t)C + 1 : (size_t)C + 1;   // (the specialised loop shards each chain's counter over 8 lines)
   if (!ctx->loop.gridsync.reserve((size_t)32 * sync_lines)) return fail(ctx, SI_ERR_NOMEM, std::string(k.who) + ": allocation failed");
   fill_common_args(a, ctx, k);
-  a.wbuf = ctx->fw.w; a.w_stride = pad_ld(ctx->iN);
-  a.ybuf = ctx->fw.yhat; a.y_stride = (int64_t)ctx->out_dim * ctx->B;
+  a.wbuf = ctx->fw.w; a.w_stride = pad_ld(ctx->setup.model.N);
+  a.ybuf = ctx->fw.yhat; a.y_stride = (int64_t)ctx->setup.model.out_dim * ctx->setup.B;
   a.cnt = ctx->loop.gridsync; a.status = ctx->loop.gridsync + (size_t)32 * (sync_lines - 1);
   hipError_t e = hipMemsetAsync(ctx->loop.gridsync, 0, (size_t)32 * sync_lines * sizeof(unsigned), ctx->stream);
   if (e == hipSuccess) {
-    const double fl = 2.0 * (double)ctx->iN * (double)ctx->B * (double)k.itr * C;
+    const double fl = 2.0 * (double)ctx->setup.model.N * (double)ctx->setup.B * (double)k.itr * C;
     ProfScope ps(ctx, SI_K_RWMH, fl, 0.0);
     if (sk) {
       fill_common_args(sa, ctx, k);
@@ -261,7 +261,7 @@ static int32_t rwmh_grid(si_ctx* ctx, const RwmhCall& k) {
       sa.wbuf = ctx->loop.specw; sa.w_stride = sk->fo_total;
       sa.ybuf = ctx->loop.specy; sa.y_stride = a.y_stride;
       sa.cnt = a.cnt; sa.status = a.status;
-      sa.M = M; sa.G = a.G; sa.B = (int)ctx->B; sa.nblocks = ctx->sse_blocks;
+      sa.M = M; sa.G = a.G; sa.B = (int)ctx->setup.B; sa.nblocks = ctx->setup.sse_blocks;
       void* gargs[] = {&sa};
       e = hipModuleLaunchKernel(sk->grid, (unsigned)(a.G * C), 1, 1, 256, 1, 1, (unsigned)lds_spec, ctx->stream, gargs, nullptr);
       ctx->loop.last_loop_spec = e == hipSuccess;
@@ -288,9 +288,9 @@ struct WeightRing {
   si_ctx* ctx;
   const RwmhCall& k;
   bool select_path;   // the proposal weights of ALL chains are still in fw.w at accept time: one pass of launches carries them all
-  double* slot(int64_t t) const { return ctx->d_wring + (size_t)(t % SI_WRING) * (size_t)k.C * (size_t)pad_ld(ctx->iN); }
+  double* slot(int64_t t) const { return ctx->d_wring + (size_t)(t % SI_WRING) * (size_t)k.C * (size_t)pad_ld(ctx->setup.model.N); }
   hipError_t drain(int64_t u) const {   // sample u of every chain: pinned slot -> the caller's (pageable) N x itr x C array
-    const int64_t N = ctx->iN;
+    const int64_t N = ctx->setup.model.N;
     const int r = (int)(u % SI_WRING);
     hipError_t w = hipEventSynchronize(ctx->ev_wcopy[r]);
     for (int c = 0; c < k.C && w == hipSuccess; ++c)
@@ -298,7 +298,7 @@ struct WeightRing {
     return w;
   }
   hipError_t push(int64_t t) const {
-    const int64_t N = ctx->iN, ldw = pad_ld(N);
+    const int64_t N = ctx->setup.model.N, ldw = pad_ld(N);
     const int32_t C = k.C;
     const int r = (int)(t % SI_WRING);
     hipError_t e = hipSuccess;
@@ -331,7 +331,7 @@ struct WeightRing {
 // 25.7 us eager -- it is bound by the serial latency of its 8 dependent small kernels, not by host launches -- and at cfg2 a
 // transition is 3.3 ms of kernel time.
 static int32_t rwmh_per_step(si_ctx* ctx, const RwmhCall& k) {
-  const int32_t C = k.C, M = ctx->iM;
+  const int32_t C = k.C, M = ctx->setup.M;
   double* const dZ = ctx->chains.outZ;
   double* const dlp = ctx->chains.outlp;
   {
@@ -353,7 +353,7 @@ static int32_t rwmh_per_step(si_ctx* ctx, const RwmhCall& k) {
     {
       ProfScope ps(ctx, SI_K_RWMH, 0, 0);
       if (fused_tail)
-        launch_rwmh_tail(ctx->stream, ctx->fw.ssepart, ctx->sse_blocks, ctx->chains.sse, ctx->chains.zcur, ctx->chains.zprop, ctx->chains.lpcur, ctx->chains.nacc, M,
+        launch_rwmh_tail(ctx->stream, ctx->fw.ssepart, ctx->setup.sse_blocks, ctx->chains.sse, ctx->chains.zcur, ctx->chains.zprop, ctx->chains.lpcur, ctx->chains.nacc, M,
                          C, k.c0, k.s2, k.sigma_z, k.seed, k.chain_id0, ctx->chains.steps, dZ, dlp, k.itr, accflag, t + 1 < k.itr);
       else
         launch_rwmh_accept(ctx->stream, ctx->chains.zcur, ctx->chains.zprop, ctx->chains.lpcur, ctx->chains.sse, ctx->chains.nacc, M, C, k.c0, k.s2, k.seed,
@@ -379,20 +379,17 @@ static int32_t sample_rwmh_impl(si_ctx* ctx, const char* who, int64_t itr, doubl
                                 int32_t nchains, double* Z_out, double* lp_out, double* accept_rate_out, double* W_out) {
   CHECK_CTX(ctx);
   ctx->loop.last_density_spec = ctx->loop.last_loop_spec = 0;   // (si_chain_kernel_info reports THIS call)
-  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, std::string(who) + ": call si_infer_setup first");
-  if (itr <= 0 || nchains <= 0 || chain_id0 < 0 || !(sigma_z > 0.0))
-    return fail(ctx, SI_ERR_INVALID, std::string(who) + ": itr, nchains, sigma_z must be positive");
-  if (ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, std::string(who) + ": a step-wise RWMH session is open; its proposal / SSE buffers are shared (si_rwmh_end or si_rwmh_abort first)");
+  int32_t rc = infer_entry_check(ctx, who, bad_if(itr <= 0 || nchains <= 0 || chain_id0 < 0 || !(sigma_z > 0.0), "itr, nchains, sigma_z must be positive"));
+  if (rc != SI_OK) return rc;
   BIND(ctx);
   const int32_t C = nchains;
-  int32_t rc = ensure_chains(ctx, C);
-  if (rc != SI_OK) return rc;
+  if ((rc = ensure_chains(ctx, C)) != SI_OK) return rc;
   if (W_out && (rc = ensure_wstream(ctx, C)) != SI_OK) return rc;
   // the device-side output arrays stay with the ctx (grown on demand, released with the inference set-up)
-  if (!ctx->chains.outZ.reserve((size_t)ctx->iM * itr * C) || !ctx->chains.outlp.reserve((size_t)itr * C))
+  if (!ctx->chains.outZ.reserve((size_t)ctx->setup.M * itr * C) || !ctx->chains.outlp.reserve((size_t)itr * C))
     return fail(ctx, SI_ERR_NOMEM, std::string(who) + ": output allocation failed");
-  const double d = (double)ctx->out_dim * (double)ctx->B;
-  const size_t wall_elems = (size_t)pad_ld(ctx->iN) * (size_t)itr * (size_t)C;
+  const double d = (double)ctx->setup.model.out_dim * (double)ctx->setup.B;
+  const size_t wall_elems = (size_t)pad_ld(ctx->setup.model.N) * (size_t)itr * (size_t)C;
   const RwmhCall k{who, itr, sigma_z, seed, chain_id0, C, Z_out, lp_out, accept_rate_out, W_out, lik_c0(ctx, d),
                    lik_s2(ctx), wall_elems, !W_out || wall_elems <= ((size_t)512 << 20) / sizeof(double)};
   if ((rc = rwmh_one_workgroup(ctx, k)) != SI_NOT_TAKEN) return rc;
@@ -438,39 +435,35 @@ const char* si_chain_spec_message(si_ctx* ctx) { return ctx ? ctx->spec_message.
 int32_t si_rwmh_begin(si_ctx* ctx, int64_t itr, double sigma_z, uint64_t seed, int32_t chain_id0, int32_t nchains,
                       int64_t d_total) {
   CHECK_CTX(ctx);
-  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, "si_rwmh_begin: call si_infer_setup first");
-  if (itr <= 0 || nchains <= 0 || chain_id0 < 0 || !(sigma_z > 0.0) || d_total < 0)
-    return fail(ctx, SI_ERR_INVALID, "si_rwmh_begin: itr, nchains, sigma_z must be positive");
+  int32_t rc = infer_entry_check(ctx, "si_rwmh_begin", bad_if(itr <= 0 || nchains <= 0 || chain_id0 < 0 || !(sigma_z > 0.0) || d_total < 0, "itr, nchains, sigma_z must be positive"), SESSION_ANY);   // (an open session is replaced)
+  if (rc != SI_OK) return rc;
   if (ctx->node.on && d_total > 0) return fail(ctx, SI_ERR_INVALID, "si_rwmh_begin: a data-sharded density (d_total > 0) is not available for NeuralODE models");
   if (lik_on(ctx) && d_total > 0)
     return fail(ctx, SI_ERR_INVALID, "si_rwmh_begin: a data-sharded density (d_total > 0) is not available with a categorical or bernoulli likelihood (si_infer_set_likelihood)");
   BIND(ctx);
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  int32_t rc = ensure_chains(ctx, nchains);
-  if (rc != SI_OK) return rc;
-  ctx->chains.sw_Z.reset();
-  ctx->chains.sw_lp.reset();
-  if (!ctx->chains.sw_Z.alloc((size_t)ctx->iM * itr * nchains) || !ctx->chains.sw_lp.alloc((size_t)itr * nchains)) {
-    ctx->chains.sw_Z.reset();
-    ctx->chains.sw_lp.reset();
+  if ((rc = ensure_chains(ctx, nchains)) != SI_OK) return rc;
+  StepSession& s = ctx->chains.session;
+  s = StepSession();
+  if (!s.Z.alloc((size_t)ctx->setup.M * itr * nchains) || !s.lp.alloc((size_t)itr * nchains)) {
+    s = StepSession();
     return fail(ctx, SI_ERR_NOMEM, "si_rwmh_begin: output allocation failed");
   }
-  ctx->sw_itr = itr; ctx->sw_sigma_z = sigma_z; ctx->sw_seed = seed; ctx->sw_chain0 = chain_id0; ctx->sw_C = nchains;
-  ctx->sw_d = d_total > 0 ? (double)d_total : (double)ctx->out_dim * (double)ctx->B;
-  ctx->sw_next = 0;
-  ctx->sw_evaluated = false;
-  launch_rwmh_init(ctx->stream, ctx->chains.zcur, ctx->chains.lpcur, ctx->chains.nacc, ctx->chains.steps, ctx->iM, nchains);
+  s.itr = itr, s.sigma_z = sigma_z, s.seed = seed, s.chain0 = chain_id0, s.C = nchains;
+  s.d = d_total > 0 ? (double)d_total : (double)ctx->setup.model.out_dim * (double)ctx->setup.B;
+  launch_rwmh_init(ctx->stream, ctx->chains.zcur, ctx->chains.lpcur, ctx->chains.nacc, ctx->chains.steps, ctx->setup.M, nchains);
   SI_HIP(ctx, hipGetLastError());
   return SI_OK;
 }
 
 int32_t si_rwmh_step_eval(si_ctx* ctx, double* sse_local_out) {
   CHECK_CTX(ctx);
-  if (!ctx->chains.sw_Z || ctx->sw_next >= ctx->sw_itr || ctx->sw_evaluated)
+  StepSession& s = ctx->chains.session;
+  if (!s.open() || s.next >= s.itr || s.evaluated)
     return fail(ctx, SI_ERR_STATE, "si_rwmh_step_eval: call si_rwmh_begin first / accept the pending step / chain finished");
   BIND(ctx);
-  const int32_t C = ctx->sw_C;
-  launch_rwmh_propose(ctx->stream, ctx->chains.zcur, ctx->chains.zprop, ctx->iM, C, ctx->sw_sigma_z, ctx->sw_seed, ctx->sw_chain0,
+  const int32_t C = s.C;
+  launch_rwmh_propose(ctx->stream, ctx->chains.zcur, ctx->chains.zprop, ctx->setup.M, C, s.sigma_z, s.seed, s.chain0,
                       ctx->chains.steps);
   {
     const int32_t rc = eval_density_all(ctx, setup_view(ctx), C);   // (the deferred SSE stage off: chains.sse goes to the caller)
@@ -480,34 +473,36 @@ int32_t si_rwmh_step_eval(si_ctx* ctx, double* sse_local_out) {
     SI_HIP(ctx, hipMemcpyAsync(sse_local_out, ctx->chains.sse, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
-  ctx->sw_evaluated = true;
+  s.evaluated = true;
   return SI_OK;
 }
 
 int32_t si_rwmh_step_accept(si_ctx* ctx, const double* sse_total) {
   CHECK_CTX(ctx);
-  if (!ctx->chains.sw_Z || !ctx->sw_evaluated) return fail(ctx, SI_ERR_STATE, "si_rwmh_step_accept: no evaluated step pending");
+  StepSession& s = ctx->chains.session;
+  if (!s.open() || !s.evaluated) return fail(ctx, SI_ERR_STATE, "si_rwmh_step_accept: no evaluated step pending");
   BIND(ctx);
-  const int32_t C = ctx->sw_C;
+  const int32_t C = s.C;
   if (sse_total) {  // NULL: the device buffer of si_rwmh_sse_ptr already holds the totals (all-reduced in place)
     SI_HIP(ctx, hipMemcpyAsync(ctx->chains.sse, sse_total, (size_t)C * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     SI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // sse_total is caller-owned
   }
-  const double c0 = lik_c0(ctx, ctx->sw_d), s2 = lik_s2(ctx);
-  launch_rwmh_accept(ctx->stream, ctx->chains.zcur, ctx->chains.zprop, ctx->chains.lpcur, ctx->chains.sse, ctx->chains.nacc, ctx->iM, C, c0, s2,
-                     ctx->sw_seed, ctx->sw_chain0, ctx->chains.steps, ctx->chains.sw_Z, ctx->chains.sw_lp, ctx->sw_itr,
+  const double c0 = lik_c0(ctx, s.d), s2 = lik_s2(ctx);
+  launch_rwmh_accept(ctx->stream, ctx->chains.zcur, ctx->chains.zprop, ctx->chains.lpcur, ctx->chains.sse, ctx->chains.nacc, ctx->setup.M, C, c0, s2,
+                     s.seed, s.chain0, ctx->chains.steps, s.Z, s.lp, s.itr,
                      ctx->setup.sigma_p > 0.0 ? ctx->chains.wsq : nullptr, prior_c0(ctx), prior_sp2(ctx));
   SI_HIP(ctx, hipGetLastError());
-  ctx->sw_next += 1;
-  ctx->sw_evaluated = false;
+  s.next += 1;
+  s.evaluated = false;
   return SI_OK;
 }
 
 int32_t si_rwmh_sse_ptr(si_ctx* ctx, double** sse_dev_out, int32_t* nchains_out) {
   CHECK_CTX(ctx);
-  if (!ctx->chains.sw_Z) return fail(ctx, SI_ERR_STATE, "si_rwmh_sse_ptr: call si_rwmh_begin first");
+  const StepSession& s = ctx->chains.session;
+  if (!s.open()) return fail(ctx, SI_ERR_STATE, "si_rwmh_sse_ptr: call si_rwmh_begin first");
   if (sse_dev_out) *sse_dev_out = ctx->chains.sse;
-  if (nchains_out) *nchains_out = ctx->sw_C;
+  if (nchains_out) *nchains_out = s.C;
   return SI_OK;
 }
 
@@ -515,27 +510,24 @@ int32_t si_rwmh_abort(si_ctx* ctx) {
   CHECK_CTX(ctx);
   BIND(ctx);
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->chains.sw_Z.reset();
-  ctx->chains.sw_lp.reset();
-  ctx->sw_evaluated = false;
-  ctx->sw_next = ctx->sw_itr = 0;
+  ctx->chains.session = StepSession();
   return SI_OK;
 }
 
 int32_t si_rwmh_end(si_ctx* ctx, double* Z_out, double* lp_out, double* accept_rate_out) {
   CHECK_CTX(ctx);
-  if (!ctx->chains.sw_Z || ctx->sw_next != ctx->sw_itr || ctx->sw_evaluated)
+  StepSession& s = ctx->chains.session;
+  if (!s.open() || s.next != s.itr || s.evaluated)
     return fail(ctx, SI_ERR_STATE, "si_rwmh_end: the chain is not complete");
   BIND(ctx);
-  const int32_t C = ctx->sw_C, M = ctx->iM;
-  const int64_t itr = ctx->sw_itr;
+  const int32_t C = s.C, M = ctx->setup.M;
+  const int64_t itr = s.itr;
   std::vector<int64_t> nacc((size_t)C);
-  if (Z_out) SI_HIP(ctx, hipMemcpyAsync(Z_out, ctx->chains.sw_Z, (size_t)M * itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (lp_out) SI_HIP(ctx, hipMemcpyAsync(lp_out, ctx->chains.sw_lp, (size_t)itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (Z_out) SI_HIP(ctx, hipMemcpyAsync(Z_out, s.Z, (size_t)M * itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (lp_out) SI_HIP(ctx, hipMemcpyAsync(lp_out, s.lp, (size_t)itr * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipMemcpyAsync(nacc.data(), ctx->chains.nacc, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->chains.sw_Z.reset();
-  ctx->chains.sw_lp.reset();
+  s = StepSession();
   accept_rates(nacc, itr, accept_rate_out);
   return SI_OK;
 }
@@ -547,11 +539,11 @@ int32_t si_rwmh_end(si_ctx* ctx, double* Z_out, double* lp_out, double* accept_r
 // array (its first-touch page faults are spread over those threads too; a MADV_HUGEPAGE hint was tried and gained nothing).  A plain hipMemcpy into pageable memory does the last two steps on one thread: 0.79 ms per 8.4 MB sample.
 int32_t si_reconstruct(si_ctx* ctx, const double* Z, int64_t C, double* W_out) {
   CHECK_CTX(ctx);
-  if (!ctx->setup.ready) return fail(ctx, SI_ERR_STATE, "si_reconstruct: call si_infer_setup first");
-  if (!Z || C <= 0 || !W_out) return fail(ctx, SI_ERR_INVALID, "si_reconstruct: bad argument");
+  const int32_t rc0 = infer_entry_check(ctx, "si_reconstruct", bad_if(!Z || C <= 0 || !W_out), SESSION_ANY);
+  if (rc0 != SI_OK) return rc0;
   BIND(ctx);
-  const int64_t N = ctx->iN, ldw = pad_ld(N);
-  const int32_t M = ctx->iM;
+  const int64_t N = ctx->setup.model.N, ldw = pad_ld(N);
+  const int32_t M = ctx->setup.M;
   // samples per pipeline stage: ~32 MB of output, at most 64 samples, and at least four stages when C allows it
   const int64_t group_cap = std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)32 << 20) / (N * 8)));   // sizes the buffers once per N
   const int64_t group = std::max<int64_t>(1, std::min<int64_t>((C + 3) / 4, group_cap));

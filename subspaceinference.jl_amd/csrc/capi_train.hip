@@ -74,36 +74,37 @@ CtxCore::~CtxCore() { delete train; }
 // what the cost's numerator is divided by for a batch of nb observations: out_dim * nb, SI_COST_LOGITCE: nb (agg = mean over the
 // columns of a dims = 1 sum)
 double train_denominator(const TrainState* t, int64_t nb) {
-  return t->cost == SI_COST_LOGITCE ? (double)nb : (double)t->out_dim * (double)nb;
+  return t->cost == SI_COST_LOGITCE ? (double)nb : (double)t->model.out_dim * (double)nb;
 }
 
 // ---- value and gradient in fp32 (dense_forward<float> + the fp32 reverse sweep), shared by the training step and si_logdensity_grad
 int32_t dense_value_and_grad_f32(Ctx* ctx, hipStream_t st, const DenseSweepF32& s) {
   SweepF32Ws& ws = *s.ws;
-  const size_t nl = s.nl;
+  const si_layer* layers = s.m->lay();
+  const bool fuse_tail = s.m->fuse_tail;
+  const size_t nl = s.m->layers.size();
   const int64_t nb = s.B;
   const float* w = s.w32;
-  const si_layer& ll = s.layers[nl - 1];
+  const si_layer& ll = layers[nl - 1];
   const int64_t d = (int64_t)ll.out * nb;
-  // (a fused head's own output lives in yhat64; its slot count follows the alignment of the fused layer's W in w32)
-  const int slots = s.fuse_tail ? dense_f32_fused_slots(s.layers[nl - 2].out, s.layers[nl - 2].in, s.layers[nl - 2].w_off % 4 == 0) : 0;
-  const DenseForward<float> fw{s.layers, nl, s.fuse_tail, w, s.w64, s.X32, s.Y, nb, ws.hs32.data(), {nullptr, nullptr}, ChainBatch(), slots,
-                               s.part, s.fuse_tail ? ws.yhat64.get() : nullptr, s.ssepart, s.sse_blocks, s.sse, false, -1, false};
+  // (a fused head's own output lives in yhat64)
+  const DenseForward<float> fw{s.m, w, s.w64, s.X32, s.Y, nb, ws.hs32.data(), {nullptr, nullptr}, ChainBatch(), s.m->fuse_slots32,
+                               s.part, fuse_tail ? ws.yhat64.get() : nullptr, s.ssepart, s.sse_blocks, s.sse, false, false, false};
   const float* h = dense_forward(ctx, st, fw);
   double bflops = 0.0;
-  for (size_t l = 0; l < nl; ++l) bflops += 4.0 * (double)s.layers[l].in * s.layers[l].out * (double)nb;
+  for (size_t l = 0; l < nl; ++l) bflops += 4.0 * (double)layers[l].in * layers[l].out * (double)nb;
   ProfScope ps(ctx, SI_K_BACKWARD, bflops, 0.0);
-  SI_HIP(ctx, hipMemsetAsync(ws.gw32, 0, (size_t)pad_ld(s.N) * sizeof(float), st));
+  SI_HIP(ctx, hipMemsetAsync(ws.gw32, 0, (size_t)pad_ld(s.m->N) * sizeof(float), st));
   int cur = 0;
   if (s.cost)
-    launch_cost_tail<float>(st, *s.cost, s.Y, s.fuse_tail ? ws.yhat64.get() : nullptr, s.fuse_tail ? nullptr : h, ll.out, nb, ll.act,
+    launch_cost_tail<float>(st, *s.cost, s.Y, fuse_tail ? ws.yhat64.get() : nullptr, fuse_tail ? nullptr : h, ll.out, nb, ll.act,
                             ws.delta32[cur].get(), s.sse);
   else
-    launch_delta_out_f32(st, s.Y, s.fuse_tail ? ws.yhat64 : nullptr, s.fuse_tail ? nullptr : h, d, s.scale, ll.act, ws.delta32[cur]);
+    launch_delta_out_f32(st, s.Y, fuse_tail ? ws.yhat64 : nullptr, fuse_tail ? nullptr : h, d, s.scale, ll.act, ws.delta32[cur]);
   size_t top = nl;
   bool have_db = false;   // db of layer top-1 already produced (by the pass that formed its Delta)
-  if (s.fuse_tail) {
-    const si_layer& lp = s.layers[nl - 2];
+  if (fuse_tail) {
+    const si_layer& lp = layers[nl - 2];
     launch_mul_dact_rowsum_f32(st, ws.delta32[cur], nullptr, ll.out, nb, SI_ACT_IDENTITY, nullptr, ws.rspart64, ws.gw32 + ll.b_off);
     launch_tail_bwd_f32(st, w + ll.w_off, ws.delta32[cur], ws.hs32[nl - 2], ll.out, ll.in, nb, lp.act, ws.delta32[cur ^ 1], ws.tailpart64,
                         ws.gw32 + ll.w_off, ws.gw32 + lp.b_off);
@@ -112,7 +113,7 @@ int32_t dense_value_and_grad_f32(Ctx* ctx, hipStream_t st, const DenseSweepF32& 
     have_db = true;
   }
   for (size_t li = top; li-- > 0;) {
-    const si_layer& ly = s.layers[li];
+    const si_layer& ly = layers[li];
     const float* hprev = li > 0 ? ws.hs32[li - 1] : s.X32;
     launch_backward_weight_f32(st, ws.delta32[cur], hprev, ws.part32, ly.out, ly.in, nb, ctx->num_cu, ws.gw32 + ly.w_off);
     if (!have_db)
@@ -121,7 +122,7 @@ int32_t dense_value_and_grad_f32(Ctx* ctx, hipStream_t st, const DenseSweepF32& 
       // Delta_{l-1} = (W_l' Delta_l) .* act'(H_{l-1}): the forward kernel on W_l' (out' = in, in' = out, zero bias) with the
       // multiply in its store, then the row sums (db of layer l-1); shapes the LDS-DMA kernel does not take: one elementwise pass
       // behind the GEMM does both
-      const si_layer& lq = s.layers[li - 1];
+      const si_layer& lq = layers[li - 1];
       launch_transpose_f32(st, w + ly.w_off, ly.out, ly.in, ws.wt32);
       if (launch_dense_f32_dx(st, ws.wt32, ws.zero32, ws.delta32[cur], ws.delta32[cur ^ 1], ly.in, ly.out, nb, ws.hs32[li - 1], lq.act))
         launch_mul_dact_rowsum_f32(st, ws.delta32[cur ^ 1], nullptr, ly.in, nb, SI_ACT_IDENTITY, nullptr, ws.rspart64, ws.gw32 + lq.b_off);
@@ -149,8 +150,8 @@ static int32_t train_setup_failed(si_ctx* ctx, int32_t code, const std::string& 
 
 // What every set-up does first: the stream drains, the old state goes, the new one gets its route, its sizes, the optimiser's
 // parameters and the buffers every route has.  ok: those allocations succeeded (the caller adds its own and reports them together)
-static int32_t train_setup_begin(si_ctx* ctx, TrainRoute route, const si_layer* layers, int32_t L, int64_t N, int32_t in_dim, int32_t out_dim,
-                                 int64_t B_total, int64_t batch_max, int32_t opt_kind, double eta, double p1, double p2, bool& ok) {
+static int32_t train_setup_begin(si_ctx* ctx, TrainRoute route, ChainModel&& model, int64_t B_total, int64_t batch_max, int32_t opt_kind,
+                                 double eta, double p1, double p2, bool& ok) {
   SI_HIP(ctx, hipSetDevice(ctx->device));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   free_train(ctx);
@@ -158,8 +159,9 @@ static int32_t train_setup_begin(si_ctx* ctx, TrainRoute route, const si_layer* 
   TrainOpt& o = t->opt;
   TrainBatch& b = t->batch;
   t->route = route;
-  t->layers.assign(layers, layers + L);
-  t->N = N; t->Btot = B_total; t->Bmax = batch_max; t->in_dim = in_dim; t->out_dim = out_dim;
+  t->model = std::move(model); t->Btot = B_total; t->Bmax = batch_max;
+  const int64_t N = t->model.N;
+  const int32_t in_dim = t->model.in_dim, out_dim = t->model.out_dim;
   o.kind = opt_kind; o.eta = eta; o.p1 = p1; o.p2 = p2; o.bp1 = p1; o.bp2 = p2;  // ADAM: beta powers start at beta
   const size_t bm = (size_t)batch_max, nx = (size_t)in_dim * (size_t)B_total;
   ok = (route == TrainRoute::DenseF32 ? t->X32.alloc(nx) && t->Xb32.alloc((size_t)in_dim * bm) : t->X.alloc(nx) && t->Xb.alloc((size_t)in_dim * bm)) &&
@@ -172,11 +174,11 @@ static int32_t train_setup_begin(si_ctx* ctx, TrainRoute route, const si_layer* 
 // ... and last, behind the route's own uploads: the weights, zero moments, a zero Float64 copy (queued)
 static hipError_t train_setup_upload(si_ctx* ctx, const float* w0) {
   TrainOpt& o = ctx->train->opt;
-  const size_t n = (size_t)ctx->train->N;
+  const size_t n = (size_t)ctx->train->model.N;
   hipError_t e = hipMemcpyAsync(o.w32, w0, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(o.m32, 0, n * sizeof(float), ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(o.v32, 0, n * sizeof(float), ctx->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(o.w64, 0, (size_t)pad_ld(ctx->train->N) * sizeof(double), ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(o.w64, 0, (size_t)pad_ld(ctx->train->model.N) * sizeof(double), ctx->stream);
   return e;
 }
 
@@ -190,28 +192,23 @@ static int32_t train_setup_impl(si_ctx* ctx, const si_layer* layers, int32_t L, 
   if ((data_dtype != SI_F32 && data_dtype != SI_F64) || (compute_dtype != SI_F32 && compute_dtype != SI_F64 && compute_dtype != SI_DTYPE_OF_DATA))
     return fail(ctx, SI_ERR_INVALID, "si_train_setup_ex: data_dtype is SI_F32 / SI_F64, compute_dtype SI_F32 / SI_F64 / SI_DTYPE_OF_DATA");
   const bool f32 = (compute_dtype == SI_DTYPE_OF_DATA ? data_dtype : compute_dtype) == SI_F32;
-  NetPlan plan;
-  {
-    const int32_t prc = net_plan(ctx, "si_train_setup", layers, L, N, in_dim, out_dim, plan);
-    if (prc != SI_OK) return prc;
-  }
-  const bool fuse_tail = head_fused(plan, layers, L);
-  if (f32 && plan.has_conv)
+  ChainModel model;
+  const int32_t prc = chain_model_build(ctx, "si_train_setup", layers, L, N, in_dim, out_dim, f32, 0, model);
+  if (prc != SI_OK) return prc;
+  const bool has_conv = model.plan.has_conv;
+  if (f32 && has_conv)
     return fail(ctx, SI_ERR_INVALID, "si_train_setup_ex: compute_dtype = SI_F32 is implemented for Dense chains; Conv / MaxPool / flatten chains train in SI_F64");
-  const TrainRoute route = plan.has_conv ? TrainRoute::Conv : f32 ? TrainRoute::DenseF32 : TrainRoute::DenseF64;
+  const TrainRoute route = has_conv ? TrainRoute::Conv : f32 ? TrainRoute::DenseF32 : TrainRoute::DenseF64;
   bool ok = false;
-  const int32_t rcb = train_setup_begin(ctx, route, layers, L, N, in_dim, out_dim, B_total, batch_max, opt_kind, eta, p1, p2, ok);
+  const int32_t rcb = train_setup_begin(ctx, route, std::move(model), B_total, batch_max, opt_kind, eta, p1, p2, ok);
   if (rcb != SI_OK) return rcb;
   TrainState* t = ctx->train;
+  const ChainModel& m = t->model;
+  const NetPlan& plan = m.plan;
   t->sse_blocks = sse_num_blocks((int64_t)out_dim * batch_max, ctx->num_cu);
-  t->fuse_tail = fuse_tail;
-  t->fuse_slots = fuse_tail ? dense_fused_slots(layers[L - 2].out) : 0;
-  if (f32 && fuse_tail)   // (w32 is 256-byte aligned: a layer's W is 16-byte aligned iff w_off % 4 == 0)
-    t->fuse_slots = std::max(t->fuse_slots, dense_f32_fused_slots(layers[L - 2].out, layers[L - 2].in, layers[L - 2].w_off % 4 == 0));
-  t->plan = plan;
-  ok = ok && t->ssepart.alloc((size_t)t->sse_blocks) && (!fuse_tail || t->part.alloc((size_t)t->fuse_slots * out_dim * batch_max)) &&
+  ok = ok && t->ssepart.alloc((size_t)t->sse_blocks) && (!m.fuse_tail || t->part.alloc((size_t)m.part_slots() * out_dim * batch_max)) &&
        (!plan.has_conv || t->wpack.alloc(plan.wpack_elems)) && (!plan.input_spatial || t->Xc.alloc((size_t)plan.in_elems * batch_max)) &&
-       sweep_ws_alloc(ctx, t->sweep, layers, L, plan, fuse_tail, N, in_dim, out_dim, batch_max, f32);
+       sweep_ws_alloc(ctx, t->sweep, m, batch_max);
   if (!ok) return train_setup_failed(ctx, SI_ERR_NOMEM, "si_train_setup: device allocation failed");
   // the data in the element type the step computes in (X) / sums the loss in (Y: fp64 always); one conversion at set-up where
   // the caller's type differs (Float32 -> Float64 is exact; Float64 -> Float32 rounds once, as `Float32.(X)` would)
@@ -310,7 +307,10 @@ int32_t si_train_setup_node(si_ctx* ctx, const si_layer* layers, int32_t L, int6
     return bad("the step record (batch_max * max_steps * (d + 2) doubles) and the gradient slices (batch_max * N) do not fit the "
                "2 GiB workspace budget: lower max_steps or the batch size");
   bool ok = false;
-  const int32_t rcb = train_setup_begin(ctx, TrainRoute::Node, layers, L, N, d, d * S, f, batch_max, opt_kind, eta, p1, p2, ok);
+  ChainModel model;   // (a right-hand side is validated by node_plan above; it has no NetPlan and no fused head)
+  model.layers.assign(layers, layers + L);
+  model.N = N, model.in_dim = d, model.out_dim = d * S;
+  const int32_t rcb = train_setup_begin(ctx, TrainRoute::Node, std::move(model), f, batch_max, opt_kind, eta, p1, p2, ok);
   if (rcb != SI_OK) return rcb;
   TrainState* t = ctx->train;
   NodeTrain* nt = &t->node;
@@ -325,7 +325,7 @@ int32_t si_train_setup_node(si_ctx* ctx, const si_layer* layers, int32_t L, int6
     return train_setup_failed(ctx, SI_ERR_NOMEM, "si_train_setup_node: device allocation failed (the step record: lower max_steps or the batch size)");
   hipStream_t st = ctx->stream;
   hipError_t e = hipMemcpyAsync(t->X, U0, (size_t)d * (size_t)f * sizeof(double), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(t->Y, Y, (size_t)t->out_dim * (size_t)f * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(t->Y, Y, (size_t)t->model.out_dim * (size_t)f * sizeof(double), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(nt->ts, ts, (size_t)S * sizeof(double), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = train_setup_upload(ctx, w0);
   if (e == hipSuccess) e = hipMemsetAsync(t->opt.gw, 0, (size_t)pad_ld(N) * sizeof(double), st);
@@ -423,10 +423,10 @@ static int32_t train_batch(si_ctx* ctx, const char* who, const int64_t* idx, int
   SI_HIP(ctx, hipEventRecord(b.ev[s], ctx->stream));
   b.busy[s] = true;
   if (t->route == TrainRoute::DenseF32)
-    launch_gather_cols(ctx->stream, t->X32.get(), t->in_dim, b.idx.get(), nb, t->Xb32.get(), ctx->num_cu);
+    launch_gather_cols(ctx->stream, t->X32.get(), t->model.in_dim, b.idx.get(), nb, t->Xb32.get(), ctx->num_cu);
   else
-    launch_gather_cols(ctx->stream, t->X.get(), t->in_dim, b.idx.get(), nb, t->Xb.get(), ctx->num_cu);
-  launch_gather_cols(ctx->stream, t->Y.get(), t->out_dim, b.idx.get(), nb, t->Yb.get(), ctx->num_cu);
+    launch_gather_cols(ctx->stream, t->X.get(), t->model.in_dim, b.idx.get(), nb, t->Xb.get(), ctx->num_cu);
+  launch_gather_cols(ctx->stream, t->Y.get(), t->model.out_dim, b.idx.get(), nb, t->Yb.get(), ctx->num_cu);
   v = TrainBatchView{t->Xb, t->Xb32, t->Yb};
   return SI_OK;
 }
@@ -440,7 +440,7 @@ static int32_t node_gradient(si_ctx* ctx, const char* who, const int64_t* idx, i
   // (a failure the caller has been told about: the set-up takes no further steps, the device's would be no-ops)
   if (nt->reported) return fail(ctx, SI_ERR_INVALID, std::string(who) + ": an earlier NeuralODE training step failed (si_train_node_info): set up again");
   hipStream_t st = ctx->stream;
-  const int64_t N = t->N, Bmax = t->Bmax;
+  const int64_t N = t->model.N, Bmax = t->Bmax;
   TrainBatchView v;
   {
     std::optional<ProfScope> ps;
@@ -486,14 +486,13 @@ static int32_t train_gradient(si_ctx* ctx, const char* who, const int64_t* idx, 
   const int32_t rcb = train_batch(ctx, who, idx, nb, v);
   if (rcb != SI_OK) return rcb;
   hipStream_t st = ctx->stream;
-  launch_widen_f32_to_f64(st, o.w32, t->N, o.w64, ctx->num_cu);
-  const NetPlan& p = t->plan;
+  launch_widen_f32_to_f64(st, o.w32, t->model.N, o.w64, ctx->num_cu);
+  const NetPlan& p = t->model.plan;
   if (p.input_spatial) net_input(ctx, p, v.X, t->Xc, nb);
   const CostTail tail{t->cost, t->cost_param, 1.0 / d_total, t->costpart};
   // (DenseF32: a Float32 model on Float32 data is a Float32 Zygote pass in the reference, src/subspace_construction.jl:39-43)
-  const ChainValueGrad in{t->layers.data(), t->layers.size(), &p, t->fuse_tail, o.w64, o.w32, v.X, t->Xc, v.X32, v.Y, nb, t->N,
-                          t->part, t->fuse_slots, t->ssepart, t->sse, sse_num_blocks((int64_t)t->out_dim * nb, ctx->num_cu), o.gw,
-                          t->wpack, -2.0 / d_total /* d mse / d yhat = 2 (yhat - y) / d */, t->cost != SI_COST_MSE ? &tail : nullptr,
+  const ChainValueGrad in{&t->model, o.w64, o.w32, v.X, t->Xc, v.X32, v.Y, nb, t->part, t->ssepart, t->sse,
+                          sse_num_blocks((int64_t)t->model.out_dim * nb, ctx->num_cu), o.gw, t->wpack, -2.0 / d_total /* d mse / d yhat = 2 (yhat - y) / d */, t->cost != SI_COST_MSE ? &tail : nullptr,
                           false, 0.0};
   const int32_t rc = chain_value_and_grad(ctx, st, t->sweep, in);
   if (rc != SI_OK) return rc;
@@ -506,7 +505,7 @@ static int32_t train_gradient(si_ctx* ctx, const char* who, const int64_t* idx, 
 static int32_t train_apply(si_ctx* ctx) {
   TrainState* t = ctx->train;
   TrainOpt& o = t->opt;
-  hipLaunchKernelGGL(optimiser_kernel, dim3(grid_for(t->N, ctx->num_cu)), dim3(256), 0, ctx->stream, o.w32, o.m32, o.v32, o.gw, t->N,
+  hipLaunchKernelGGL(optimiser_kernel, dim3(grid_for(t->model.N, ctx->num_cu)), dim3(256), 0, ctx->stream, o.w32, o.m32, o.v32, o.gw, t->model.N,
                      o.kind, o.eta, o.p1, o.p2, o.bp1, o.bp2, t->route == TrainRoute::DenseF32 ? 1 : 0);
   SI_HIP(ctx, hipGetLastError());
   advance_beta_powers(o);
@@ -555,7 +554,7 @@ int32_t si_train_grad(si_ctx* ctx, const int64_t* idx, int64_t nb, int64_t nb_to
   const double d_total = t ? train_denominator(t, nb_total) : 1.0;
   if (t && nb == 0 && nb_total > 0) {  // a rank without a share of a small batch contributes a zero gradient
     SI_HIP(ctx, hipSetDevice(ctx->device));
-    SI_HIP(ctx, hipMemsetAsync(t->opt.gw, 0, (size_t)pad_ld(t->N) * sizeof(double), ctx->stream));
+    SI_HIP(ctx, hipMemsetAsync(t->opt.gw, 0, (size_t)pad_ld(t->model.N) * sizeof(double), ctx->stream));
     SI_HIP(ctx, hipMemsetAsync(t->sse, 0, sizeof(double), ctx->stream));
     t->opt.grad_ready = true;
     if (sse_local_out) *sse_local_out = 0.0;
@@ -575,7 +574,7 @@ int32_t si_train_grad_ptr(si_ctx* ctx, double** grad_dev_out, int64_t* n_out) {
   if (!ctx) return SI_ERR_INVALID;
   if (!ctx->train || !grad_dev_out || !n_out) return fail(ctx, SI_ERR_STATE, "si_train_grad_ptr: no training state / NULL output");
   *grad_dev_out = ctx->train->opt.gw;
-  *n_out = ctx->train->N;
+  *n_out = ctx->train->model.N;
   return SI_OK;
 }
 
@@ -585,7 +584,7 @@ int32_t si_train_grad_get(si_ctx* ctx, double* g_out) {
   const bool node_gw = is_node(ctx) && ctx->train->node.steps > 0 && !ctx->train->node.reported;
   if (!ctx->train || !(ctx->train->opt.grad_ready || node_gw) || !g_out) return fail(ctx, SI_ERR_STATE, "si_train_grad_get: no gradient pending / NULL output");
   SI_HIP(ctx, hipSetDevice(ctx->device));
-  SI_HIP(ctx, hipMemcpyAsync(g_out, ctx->train->opt.gw, (size_t)ctx->train->N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(g_out, ctx->train->opt.gw, (size_t)ctx->train->model.N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SI_OK;
 }
@@ -594,7 +593,7 @@ int32_t si_train_grad_set(si_ctx* ctx, const double* g_in) {
   if (!ctx) return SI_ERR_INVALID;
   if (!ctx->train || !ctx->train->opt.grad_ready || !g_in) return fail(ctx, SI_ERR_STATE, "si_train_grad_set: no gradient pending / NULL input");
   SI_HIP(ctx, hipSetDevice(ctx->device));
-  SI_HIP(ctx, hipMemcpyAsync(ctx->train->opt.gw, g_in, (size_t)ctx->train->N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(ctx->train->opt.gw, g_in, (size_t)ctx->train->model.N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SI_OK;
 }
@@ -605,14 +604,14 @@ int32_t si_train_apply(si_ctx* ctx) {
   SI_HIP(ctx, hipSetDevice(ctx->device));
   const int32_t rc = train_apply(ctx);
   if (rc == SI_OK && is_node(ctx))   // the next step's solve reads the Float64 copy (si_train_step refreshes it in its tail kernel)
-    launch_widen_f32_to_f64(ctx->stream, ctx->train->opt.w32, ctx->train->N, ctx->train->opt.w64, ctx->num_cu);
+    launch_widen_f32_to_f64(ctx->stream, ctx->train->opt.w32, ctx->train->model.N, ctx->train->opt.w64, ctx->num_cu);
   return rc;
 }
 
 int32_t si_train_push(si_ctx* ctx, double n) {
   if (!ctx) return SI_ERR_INVALID;
   if (!ctx->train) return fail(ctx, SI_ERR_STATE, "si_train_push: call si_train_setup first");
-  if (ctx->train->N != ctx->N) return fail(ctx, SI_ERR_INVALID, "si_train_push: construction and training sizes differ");
+  if (ctx->train->model.N != ctx->N) return fail(ctx, SI_ERR_INVALID, "si_train_push: construction and training sizes differ");
   return si_construct_push_dev(ctx, ctx->train->opt.w32, SI_F32, n);
 }
 
@@ -620,7 +619,7 @@ int32_t si_train_get_weights(si_ctx* ctx, float* w_out) {
   if (!ctx) return SI_ERR_INVALID;
   if (!ctx->train || !w_out) return fail(ctx, SI_ERR_STATE, "si_train_get_weights: no training state / NULL output");
   SI_HIP(ctx, hipSetDevice(ctx->device));
-  SI_HIP(ctx, hipMemcpyAsync(w_out, ctx->train->opt.w32, (size_t)ctx->train->N * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  SI_HIP(ctx, hipMemcpyAsync(w_out, ctx->train->opt.w32, (size_t)ctx->train->model.N * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return train_node_report(ctx, "si_train_get_weights");
 }
@@ -630,7 +629,7 @@ int32_t si_train_get_opt_state(si_ctx* ctx, float* m_out, float* v_out, double* 
   if (!ctx->train) return fail(ctx, SI_ERR_STATE, "si_train_get_opt_state: no training state");
   SI_HIP(ctx, hipSetDevice(ctx->device));
   TrainOpt& o = ctx->train->opt;
-  const size_t nbytes = (size_t)ctx->train->N * sizeof(float);
+  const size_t nbytes = (size_t)ctx->train->model.N * sizeof(float);
   if (m_out && o.m32) SI_HIP(ctx, hipMemcpyAsync(m_out, o.m32, nbytes, hipMemcpyDeviceToHost, ctx->stream));
   if (v_out && o.v32) SI_HIP(ctx, hipMemcpyAsync(v_out, o.v32, nbytes, hipMemcpyDeviceToHost, ctx->stream));
   SI_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -285,9 +285,9 @@ int32_t si_rwmh_allreduce_sse(si_ctx* ctx) {
   if (!ctx) return SI_ERR_INVALID;
   int32_t rc = need_comm(ctx, "si_rwmh_allreduce_sse");
   if (rc != SI_OK) return rc;
-  if (!ctx->chains.sw_Z || !ctx->sw_evaluated) return fail(ctx, SI_ERR_STATE, "si_rwmh_allreduce_sse: no evaluated step pending (si_rwmh_step_eval first)");
+  if (!ctx->chains.session.Z || !ctx->chains.session.evaluated) return fail(ctx, SI_ERR_STATE, "si_rwmh_allreduce_sse: no evaluated step pending (si_rwmh_step_eval first)");
   SI_HIP(ctx, hipSetDevice(ctx->device));
-  SI_NCCL(ctx, rccl().AllReduce(ctx->chains.sse, ctx->chains.sse, (size_t)ctx->sw_C, ncclFloat64, ncclSum, comm_of(ctx), ctx->stream));
+  SI_NCCL(ctx, rccl().AllReduce(ctx->chains.sse, ctx->chains.sse, (size_t)ctx->chains.session.C, ncclFloat64, ncclSum, comm_of(ctx), ctx->stream));
   return SI_OK;
 }
 
@@ -302,7 +302,7 @@ int32_t si_train_allreduce_grad(si_ctx* ctx, double* sse_total_out) {
   if (!t || !t->opt.grad_ready) return fail(ctx, SI_ERR_STATE, "si_train_allreduce_grad: no gradient pending (call si_train_grad)");
   SI_HIP(ctx, hipSetDevice(ctx->device));
   SI_NCCL(ctx, rccl().GroupStart());
-  const ncclResult_t r1 = rccl().AllReduce(t->opt.gw, t->opt.gw, (size_t)t->N, ncclFloat64, ncclSum, comm_of(ctx), ctx->stream);
+  const ncclResult_t r1 = rccl().AllReduce(t->opt.gw, t->opt.gw, (size_t)t->model.N, ncclFloat64, ncclSum, comm_of(ctx), ctx->stream);
   const ncclResult_t r2 = rccl().AllReduce(t->sse, t->sse, 1, ncclFloat64, ncclSum, comm_of(ctx), ctx->stream);
   SI_NCCL(ctx, rccl().GroupEnd());
   SI_NCCL(ctx, r1);
@@ -457,7 +457,7 @@ int32_t si_sample_rwmh_sharded(si_ctx* ctx, int64_t itr, double sigma_z, uint64_
   if (rc != SI_OK) return rc;
   // (set-up state, arguments and the output allocation are local: agree before the first per-transition all-reduce)
   if ((rc = comm_agree(ctx, si_rwmh_begin(ctx, itr, sigma_z, seed, chain_id0, nchains, d_total), "si_sample_rwmh_sharded")) != SI_OK) {
-    if (ctx->chains.sw_Z) {
+    if (ctx->chains.session.Z) {
       const std::string msg = ctx->err;
       (void)si_rwmh_abort(ctx);
       ctx->err = msg;

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <vector>
@@ -67,6 +68,21 @@ struct NetPlan {
   size_t wpack_elems = 1;       // forward packs of all conv layers
   size_t wt_elems = 1;          // largest transposed pack (data gradient), one layer at a time
   int max_rows = 1;             // largest row count handed to the row-sum kernels
+};
+// What a layer table means, for the inference set-up and the training set-up alike: built by chain_model_build (capi.hip) and by
+// nothing else; every pass over a chain takes it instead of its fields.
+struct ChainModel {
+  std::vector<si_layer> layers;
+  NetPlan plan;                 // validation + geometry; has_conv: the generic path of capi_net.hip runs the chain
+  int64_t N = 0;                // length of the flat weight vector
+  int32_t in_dim = 0, out_dim = 0;   // (NeuralODE: in_dim = d, out_dim = the d*S rows of the observed trajectories)
+  bool f32 = false;             // compute_dtype = SI_F32: fp32 X / weights / activations; the head's partials, the SSE and the batch sums stay fp64
+  bool fuse_tail = false;       // narrow last layer of a Dense chain: folded into the epilogue of the layer in front of it
+  int fuse_slots = 0, fuse_slots32 = 0;   // feature slots of the fused head on the fp64 / the fp32 kernel (fuse_slots32: only with f32)
+  int main_layer = 0;           // the layer with the most flops (its launch also counts as SI_K_DENSE_MAIN)
+  int64_t max_stored = 1;       // widest output the forward pass stores, per observation (not the fused layer's, not the head's)
+  const si_layer* lay() const { return layers.data(); }   int L() const { return (int)layers.size(); }
+  int part_slots() const { return std::max(fuse_slots, fuse_slots32); }   // what one buffer of head partials for either kernel holds
 };
 struct NetScratch {             // reverse-sweep workspaces (sized by net_scratch_sizes)
   DevBuf<double> bwpart, rspart, wt, dbtmp;
@@ -142,7 +158,8 @@ void launch_ae_loss_chunk(hipStream_t st, const AeArgs& a, int32_t dtype, bool l
 struct TrainState;   // on-device training (below, after NodeTrain)
 
 // ---- the context.  Its members are split by WHO RELEASES THEM: assigning a fresh ConstructState / InferState is
-// free_construct / free_infer, everything in CtxCore lives until si_destroy deletes the context.
+// free_construct / free_infer, everything in CtxCore lives until si_destroy deletes the context: nothing in it describes a set-up or
+// a step-wise session -- of inference it holds the caller's settings (si_set_chain_loop) and why the specialised kernels last stayed out.
 struct CtxCore {
   int device = -1;
   TrainState* train = nullptr;
@@ -194,28 +211,9 @@ struct CtxCore {
   std::vector<double> svals;
   std::vector<double> vfull;      // K x K eigenvectors of A'A, columns DESCENDING by eigenvalue (host)
 
-  // inference: the shapes and settings that a new si_infer_setup overwrites or keeps, never frees
-  std::vector<si_layer> layers;
-  int64_t iN = 0, ldP = 0;
-  int32_t iM = 0;
-  int32_t in_dim = 0, out_dim = 0;
-  int64_t B = 0;
-  double sigma_m = 1.0;
-  int wsq_blocks = 0;
-  int64_t act_elems = 0, max_stored = 0;  // act_elems = pad_ld(max_stored * B): slot stride of fw.act
-  int fuse_slots = 0;
-  int sse_blocks = 0;
-  int main_layer = 0;
-  // step-wise sampler session (si_rwmh_begin .. si_rwmh_end)
-  int64_t sw_itr = 0, sw_next = 0;
-  double sw_sigma_z = 0.0, sw_d = 0.0;
-  uint64_t sw_seed = 0;
-  int32_t sw_chain0 = 0, sw_C = 0;
-  bool sw_evaluated = false;
+  // inference: the caller's settings, kept across set-ups
   bool chain_loop_enabled = true;   // si_set_chain_loop: 0 forces the launch-per-step loop (the parity tests compare the two)
-  // narrow Dense chains (kernels_chain_grid.hip): every layer of the density in ONE launch, and K6 as a persistent grid loop
   int chain_mode = 1;               // si_set_chain_loop: 0 per-layer launches, 1 automatic, 2 the fused forward without the persistent loops
-  int cg_start[5] = {0}, cg_count[5] = {0}, cg_chunks[5] = {0};
   bool chain_spec = true;           // si_set_chain_loop 3 / 4: generic kernels only
   std::string spec_message;         // why the specialised kernels did not run, when they did not (hiprtc log, class limits)
 
@@ -437,9 +435,8 @@ struct TrainOpt {
 };
 struct TrainState {
   TrainRoute route = TrainRoute::DenseF64;
-  std::vector<si_layer> layers;
-  int64_t N = 0, Btot = 0, Bmax = 0;
-  int32_t in_dim = 0, out_dim = 0;   // (Node: X = U0 (d x f), Y = the trajectories (d*S x f), in_dim = d, out_dim = d*S)
+  ChainModel model;                  // (Node: layers, N, in_dim = d, out_dim = d*S alone; X = U0 (d x f), Y = the trajectories (d*S x f))
+  int64_t Btot = 0, Bmax = 0;
   DevBuf<double> X, Y, Xb, Yb;       // the data and the gathered batch (DenseF32: X is X32)
   // compute_dtype = SI_F32 (Dense chains; reference src/subspace_construction.jl:39-43 with a Float32 model AND Float32 data):
   DevBuf<float> X32, Xb32;           // fp32 data, activations, deltas, gradient; fp64 for the loss, the head's partials, the batch sums
@@ -450,30 +447,30 @@ struct TrainState {
   DevBuf<double> costpart;           // workgroup partials of a cost other than mse
   TrainBatch batch;
   TrainOpt opt;
-  bool fuse_tail = false;            // (both Dense routes) narrow head: folded into the epilogue of the layer in front of it
-  int fuse_slots = 0;
-  DevBuf<double> part;               // [fuse_slots][out_last][Bmax] partial head products
-  NetPlan plan;                      // Conv route (net_value_and_grad, capi_net.hip): X re-laid channel-fastest, the packed weights
-  DevBuf<double> Xc, wpack;
+  DevBuf<double> part;               // [model.part_slots()][out_last][Bmax] partial head products
+  DevBuf<double> Xc, wpack;          // Conv route (net_value_and_grad, capi_net.hip): X re-laid channel-fastest, the packed weights
   SweepWs sweep;                     // the Chain routes' reverse-sweep workspace for Bmax observations; what a route does not use stays empty
   NodeTrain node;
 };
 double train_denominator(const TrainState* t, int64_t nb);   // (capi_train.hip) what the cost's numerator of nb observations is divided by
 
 // ---- inference state (reference src/space_inference.jl:88-95,111-116,125): what free_infer drops, grouped by the entry points
-// that allocate and use each part; a group that grows on demand carries its own capacity counter.  InferSetup: the set-up's data
-// and the chain's properties, written by infer_setup_common (sigma_p: si_infer_set_prior), read by everything
+// that allocate and use each part; a group that grows on demand carries its own capacity counter.  Every fact about the set-up -- its
+// chain, its shapes and the sizes derived from them, the tile program's ranges, the step-wise session -- lives in here: zero or empty after
+// free_infer.  InferSetup: the set-up's data, the chain (ChainModel) and the shapes, written by infer_setup_common (sigma_p: si_infer_set_prior), read by everything
 struct InferSetup {
   bool ready = false;
+  ChainModel model;
+  int32_t M = 0;                  // columns of P
+  int64_t ldP = 0, B = 0;         // pitch of P; observations
+  double sigma_m = 1.0;
+  int64_t act_elems = 0;          // pad_ld(model.max_stored * B): slot stride of fw.act
+  int sse_blocks = 0, wsq_blocks = 0;   // block partials of the SSE over out_dim * B and of ||w||^2 over N
   const double *swa = nullptr, *P = nullptr;   // device (P: ldP x M); borrowed (the construction's, the caller's) or the owned copies
   DevBuf<double> swa_own, P_own, X, Y;         // W_swa / P when set from host; the data
   double sigma_p = 0.0;           // > 0: the prior term the reference leaves dead is added (si_infer_set_prior; non-default)
   int lik = 0;                    // si_infer_set_likelihood: 0 gaussian, 1 categorical, 2 bernoulli (every set-up starts Gaussian)
-  bool fuse_tail = false;         // last layer folded into the epilogue of the layer in front of it (head_fused)
-  bool f32 = false;               // compute_dtype = SI_F32 (Dense chains): X rounded once (X32), weights once per evaluation, fp32 activations
-  int fuse_slots32 = 0;           // feature slots of the fp32 fused head (fuse_slots stays the fp64 path's count)
-  DevBuf<float> X32;
-  NetPlan plan;                   // chains with Conv / MaxPool / flatten layers take the generic path (capi_net.hip)
+  DevBuf<float> X32;              // (model.f32) X rounded once
   DevBuf<double> Xc;              // X re-laid channel-fastest (input_spatial)
   bool fused_ok = false;          // narrow Dense chain: the chain set up is of the fused class
 };
@@ -499,21 +496,32 @@ struct InferStacked {
   int cap = 0, last_fused = 0;    // (last_fused: si_grad_kernel_info)
   DevBuf<double> z, w, part, ssepart, gw, lp, gz;
 };
-// Per-chain state of the density entry points and the RWMH samplers for `cap` chains (ensure_chains), the step-wise session
-// (si_rwmh_begin .. si_rwmh_end) and the device-side sample arrays that every sampler's call reserves and keeps
+// The step-wise sampler session (si_rwmh_begin .. si_rwmh_end): its sample arrays and scalars; open while Z is allocated
+struct StepSession {
+  DevBuf<double> Z, lp;           // M x itr x C, itr x C
+  int64_t itr = 0, next = 0;
+  double sigma_z = 0.0, d = 0.0;
+  uint64_t seed = 0;
+  int32_t chain0 = 0, C = 0;
+  bool evaluated = false;
+  bool open() const { return Z != nullptr; }
+};
+// Per-chain state of the density entry points and the RWMH samplers for `cap` chains (ensure_chains), the session, the kept sample arrays
 struct InferChains {
   int32_t cap = 0;
   DevBuf<double> zcur, zprop, lpcur, sse;   // M x C twice, C twice
   DevBuf<double> wsq;             // ||W_swa + P z_c||^2 per chain, only with the prior on
   DevBuf<int64_t> nacc;           // C
   DevBuf<uint64_t> steps;         // C: transition counter of every chain (device-resident)
-  DevBuf<double> sw_Z, sw_lp, outZ, outlp;   // sample / lp arrays: the session's; si_sample_*'s, kept (an allocation per call was 0.4 ms of 20 transitions)
+  StepSession session;
+  DevBuf<double> outZ, outlp;     // sample / lp arrays of si_sample_*, kept (an allocation per call was 0.4 ms of 20 transitions)
 };
 // The narrow chain's one-launch kernels (capi_sample.hip; cgprog: infer_setup_common): the grid loop's buffers and those of the same
 // kernels specialised to the chain's shapes at run time (chain_spec_rtc.cpp), for spec_chains chains
 struct InferLoops {
   DevBuf<unsigned> gridsync;      // grid loop: one 128-byte counter line per chain + the status line (size() = 32 words per line)
   DevBuf<CgTileD> cgprog;         // the chain's tile program (chain_fused_program)
+  int cg_start[5] = {0}, cg_count[5] = {0}, cg_chunks[5] = {0};   // ... and its five tile lists' ranges
   DevBuf<double> specw, specy;    // per chain: 4 weight vectors in fragment order ([parity][accepted, rejected]), 2 output vectors ([parity])
   DevBuf<int> specperm;           // natural weight index -> fragment order
   const void* specperm_for = nullptr;   // (the SpecKernels the permutation was generated by)
@@ -721,9 +729,7 @@ void launch_backward_data(hipStream_t st, const double* W, const double* Delta, 
 // plain layer's output (X when there is none): without a fused head these are the model outputs in T.
 template <typename T>
 struct DenseForward {
-  const si_layer* layers;
-  size_t nl;
-  bool fuse_tail;
+  const ChainModel* m;    // layers, fuse_tail, main_layer
   const T* w;             // flat weights in the compute type
   const double* w64;      // the same in fp64 (the head's bias is added in fp64; == w for T = double)
   const T* X;             // input of layer 0, in_0 x B, shared by the chain slots
@@ -741,7 +747,7 @@ struct DenseForward {
   int sse_blocks;
   double* sse;            // cb.n sums of squared errors
   bool defer_sse_final;   // the block partials stay in ssepart (the caller's next kernel sums them)
-  int main_layer;         // the layer whose launch is also counted as SI_K_DENSE_MAIN (the head counts with its fused layer), or -1
+  bool count_main;        // m->main_layer's launch is also counted as SI_K_DENSE_MAIN (the head counts with its fused layer)
   bool traffic;           // profile: bytes of the SI_K_DENSE scopes and the SI_K_SSE scope (false: flops of SI_K_DENSE only)
 };
 template <typename T>
@@ -749,9 +755,7 @@ const T* dense_forward(Ctx* ctx, hipStream_t st, const DenseForward<T>& a);
 // Reverse sweep through a Dense chain.  On entry delta[0] holds Delta_L (launch_delta_out) and gw is zeroed, both on `st`; on
 // return every dW / db of the chain is in gw.
 struct DenseSweep {
-  const si_layer* layers;
-  size_t nl;
-  bool fuse_tail;
+  const ChainModel* m;
   const double* w;          // flat fp64 weights
   const double* X;          // input of layer 0, in_0 x B
   const DevBuf<double>* hs;  // kept outputs of every layer
@@ -768,11 +772,9 @@ int32_t dense_reverse_sweep(Ctx* ctx, hipStream_t st, const DenseSweep& s);
 struct DenseValueGrad {
   DenseSweep sw;
   const double* Y;
-  int slots;            // feature slots of the fused head
-  double* part;         // head partials [slots][out_last][B]
+  double* part;         // head partials [m->fuse_slots][out_last][B]
   double *ssepart, *sse;
   int sse_blocks;
-  int64_t N;
   double scale;         // of Delta_L: -2 / d for the mse loss, 1 / sigma^2 for the log-density
   bool traffic;         // as DenseForward::traffic
   const CostTail* cost = nullptr;   // training with another cost: its tail in place of launch_delta_out (scale unused)
@@ -782,18 +784,16 @@ int32_t dense_value_and_grad_f64(Ctx* ctx, hipStream_t st, const DenseValueGrad&
 // SSE (fp64), Delta_L, the fp32 reverse sweep; on return gw32 holds the gradient rounded to fp32 and *sse the sum of squared
 // errors.  Shared by the training step and si_logdensity_grad with compute_dtype = SI_F32.
 struct DenseSweepF32 {
-  const si_layer* layers;
-  size_t nl;
-  bool fuse_tail;
+  const ChainModel* m;
   const float* w32;     // flat fp32 weights
   const double* w64;    // the same in fp64 (the head's bias is added in fp64)
   const float* X32;     // input of layer 0, in_0 x B
   const double* Y;
   SweepF32Ws* ws;
-  double* part;         // head partials [slots][out_last][B]
+  double* part;         // head partials [m->fuse_slots32][out_last][B]
   double *ssepart, *sse;
   int sse_blocks;
-  int64_t B, N;
+  int64_t B;
   double scale;         // of Delta_L: -2 / d for the mse loss, 1 / sigma^2 for the log-density
   const CostTail* cost = nullptr;   // as DenseValueGrad::cost
 };

@@ -76,25 +76,27 @@ DISPATCH_TEXT = {
         """return !plan.has_conv && (L >= 2) && layers[L - 1].out <= SI_FUSE_MAX_OUT &&
            layers[L - 1].act < SI_ACT_LEAKYRELU && layers[L - 2].act < SI_ACT_LEAKYRELU;""",),
     "capi_infer.hip": (
-        "ctx->setup.fuse_tail = node_d == 0 && head_fused(plan, layers, L);",
-        "for (int l = 0; l < (ctx->setup.fuse_tail ? L - 2 : L); ++l) maxstored = std::max<int64_t>(maxstored, plan.L[(size_t)l].out_elems);",
-        "ctx->act_elems = pad_ld(maxstored * B);",
-        "static constexpr int SI_FUSED_MAX_WIDTH = 256;", "if (ctx->setup.fused_ok && ctx->chain_mode != 0 && !yhat_out) {",
+        "su.act_elems = pad_ld(su.model.max_stored * B);",
+        "static constexpr int SI_FUSED_MAX_WIDTH = 256;", "if (ctx->setup.fused_ok && ctx->chain_mode != 0 && !out) {",
         "cb.n = nc; cb.w = ldw; cb.hout = v.act_elems;",
-        "ctx->fw.part, ctx->fw.yhat, ctx->act_elems, ctx->setup.f32, defer_sse_final, true};",   # setup_view: the set-up's own stride and type
-        """const double per = (ctx->setup.f32 ? 4.0 : 8.0) * 2.0 * (double)ctx->act_elems +
-           8.0 * ((pslots + 1.0) * (double)ctx->out_dim * (double)ctx->B + (ctx->setup.f32 ? 1.5 : 1.0) * (double)pad_ld(ctx->iN) +
-           (double)ctx->sse_blocks);
+        "ctx->fw.part, ctx->fw.yhat, ctx->setup.act_elems, ctx->setup.model.f32, defer_sse_final, true};",   # setup_view: the set-up's own stride and type
+        """const double per = (cm.f32 ? 4.0 : 8.0) * 2.0 * (double)su.act_elems +
+           8.0 * (((double)cm.part_slots() + 1.0) * (double)cm.out_dim * (double)su.B + (cm.f32 ? 1.5 : 1.0) * (double)pad_ld(cm.N) +
+           (double)su.sse_blocks);
            const double fit = std::floor(SI_BATCH_BYTES / per);
            return (int)std::max(1.0, std::min({(double)C, fit, 1024.0}));""",
         # si_predict: fp64, its own workspace, through a view of its own
-        "const int64_t act_elems = pad_ld(ctx->max_stored * Bn);",
+        "const int64_t act_elems = pad_ld(ctx->setup.model.max_stored * Bn);",
         "const DensityView v{tX, tXc, nullptr, tY, Bn, tA, nullptr, tS, sse_blocks, tP, tYh, act_elems, /*f32=*/false,",
     ),
     "capi.hip": (
         "hipError_t raw_dev_malloc(void** out, size_t bytes) { return hipMalloc(out, bytes); }",   # A1: every buffer its own allocation
+        # chain_model_build: where the narrow-head rule is applied (off for a NeuralODE), the widest stored output
+        "m.fuse_tail = node_d == 0 && head_fused(m.plan, layers, L);",
+        "if (l < (m.fuse_tail ? L - 2 : L)) m.max_stored = std::max<int64_t>(m.max_stored, q.out_elems);",
+        "if (f32) m.fuse_slots32 = dense_f32_fused_slots(lf.out, lf.in, lf.w_off % 4 == 0);",
         # dense_forward
-        "const size_t nl = a.nl, nplain = a.fuse_tail ? nl - 2 : nl;",
+        "const size_t nl = a.m->layers.size(), nplain = fuse_tail ? nl - 2 : nl;",
         "launch_dense_f64(st, a.w + ly.w_off, a.w + ly.b_off, h, o, ly.out, ly.in, B, ly.act, cb);",
         "launch_dense_f64_fused(st, a.w + ly.w_off, a.w + ly.b_off, h, ly.out, ly.in, B, ly.act, a.w + ll.w_off, ll.out, a.part, cb, keep);",
         "launch_tail_sse(st, a.part, a.slots, ll.out, B, a.w64 + ll.b_off, ll.act, a.Y, a.yhat, a.ssepart, a.sse_blocks, cb);",
@@ -102,11 +104,11 @@ DISPATCH_TEXT = {
         "launch_sse_f32(st, h, a.Y, di, a.ssepart, a.sse_blocks, a.sse, cb.n, cb.hout, a.yhat, a.yhat ? di : 0, !a.defer_sse_final);",
         # dense_reverse_sweep
         "launch_rowsum(st, s.delta[cur], ll.out, s.B, s.rspart, s.gw + ll.b_off);",
-        """launch_tail_bwd(st, s.w + ll.w_off, s.delta[cur], s.hs[s.nl - 2], ll.out, ll.in, s.B, lp.act, s.delta[cur ^ 1], s.bwpart,
+        """launch_tail_bwd(st, s.w + ll.w_off, s.delta[cur], s.hs[nl - 2], ll.out, ll.in, s.B, lp.act, s.delta[cur ^ 1], s.bwpart,
            s.gw + ll.w_off, s.gw + lp.b_off);""",
         """launch_backward_weight(st, s.delta[cur], hprev, s.bwpart, ly.out, ly.in, s.B, ctx->num_cu, s.gw + ly.w_off,
            (have_db && li + 1 == top) ? nullptr : s.gw + ly.b_off);
-           if (li > 0) { launch_backward_data(st, s.w + ly.w_off, s.delta[cur], hprev, s.delta[cur ^ 1], ly.out, ly.in, s.B, s.layers[li - 1].act);""",
+           if (li > 0) { launch_backward_data(st, s.w + ly.w_off, s.delta[cur], hprev, s.delta[cur ^ 1], ly.out, ly.in, s.B, layers[li - 1].act);""",
     ),
     "kernels_bwd.hip": (
         "enum { EPI_DACT = 1, EPI_RAW = 2 };",
@@ -185,7 +187,7 @@ DISPATCH_TEXT = {
         "case 3: hipLaunchKernelGGL((tail_bwd_f32_kernel<3>),", "default: hipLaunchKernelGGL((tail_bwd_f32_kernel<4>),",
     ),
     "capi_train.hip": (
-        "launch_delta_out_f32(st, s.Y, s.fuse_tail ? ws.yhat64 : nullptr, s.fuse_tail ? nullptr : h, d, s.scale, ll.act, ws.delta32[cur]);",
+        "launch_delta_out_f32(st, s.Y, fuse_tail ? ws.yhat64 : nullptr, fuse_tail ? nullptr : h, d, s.scale, ll.act, ws.delta32[cur]);",
         "launch_mul_dact_rowsum_f32(st, ws.delta32[cur], nullptr, ll.out, nb, SI_ACT_IDENTITY, nullptr, ws.rspart64, ws.gw32 + ll.b_off);",
         "launch_backward_weight_f32(st, ws.delta32[cur], hprev, ws.part32, ly.out, ly.in, nb, ctx->num_cu, ws.gw32 + ly.w_off);",
         """if (!have_db)
@@ -197,7 +199,7 @@ DISPATCH_TEXT = {
            launch_mul_dact_rowsum_f32(st, ws.delta32[cur ^ 1], ws.hs32[li - 1], ly.in, nb, lq.act, ws.delta32[cur ^ 1], ws.rspart64,
            ws.gw32 + lq.b_off);""",
         "v = TrainBatchView{t->X, t->X32, t->Y}; if (in_order) return SI_OK;",   # A4: an in-order batch uses X in place (train_batch)
-        "const bool fuse_tail = head_fused(plan, layers, L);",
+        "const int32_t prc = chain_model_build(ctx, \"si_train_setup\", layers, L, N, in_dim, out_dim, f32, 0, model);",
     ),
 }
 

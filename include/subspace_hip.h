@@ -469,6 +469,38 @@ int32_t si_sample_nuts(si_ctx* ctx, int64_t itr, int64_t n_adapts, double sigma_
  * leaves_out = sum of nleaf over chains and transitions (rounds x nchains - leaves = the lock-step waste)                        */
 int32_t si_nuts_kernel_info(si_ctx* ctx, int32_t* fused_out, int32_t* passes_out, int32_t* search_rounds_out, int64_t* rounds_out,
                             int64_t* leaves_out);
+/* NOT IN THE REFERENCE: elliptical slice sampling (Murray, Adams, MacKay 2010), the sampler Izmailov et al. ("Subspace Inference for
+ * Bayesian Deep Learning") run in the subspace, with the chain state on the device.  THE DEFINITION is samplers.ess_iter on the
+ * Philox streams.  The target is p(z) ~ exp(density(z)) N(z; 0, sigma_z^2 I), where density is what si_logdensity returns for the
+ * current set-up (likelihood, si_infer_set_prior term, decoder and NeuralODE as set).  sigma_z IS HERE THE PRIOR'S STANDARD
+ * DEVIATION ON z, NOT A STEP SIZE.  lp[t] = density(z_t): the prior on z is never evaluated and is not added.  The sampler has no
+ * proposal scale, never rejects and needs values only, no gradients: it runs at full speed -- si_logdensity's stacked path,
+ * fw.slots chains per pass of launches -- on every density the library evaluates, a NeuralODE without si_node_set_grad included.
+ * Chain c draws from Philox chain chain_id0 + c: purpose 0 at step 0 = the initial point's normals n_0 (si_sample_mala's z_0);
+ * purpose 1 at step t = e_t, si_sample_rwmh's Exp(1) draw; purpose 9 at step t = the M normals n_t; purpose 10 at step t, block j =
+ * v_j = u53(x1, x0).
+ *     t = 0:   z = sigma_z n_0;  lp = density(z);  nev = 1, theta = 0
+ *     t >= 1:  nu = sigma_z n_t;  logy = lp - e_t
+ *              theta = 2 pi v_0;  lo = theta - 2 pi;  hi = theta;  k = 0
+ *              repeat:  zp = z cos theta + nu sin theta;  lpp = density(zp);  k += 1
+ *                       lpp > logy (a NaN compares false)  -> (z, lp) = (zp, lpp);  nev[t] = k;  theta[t] = theta;  stop
+ *                       k == max_evals                     -> state kept;  nev[t] = -max_evals;  theta[t] = 0;  stop
+ *                       theta < 0 ? lo = theta : hi = theta;   theta = lo + (hi - lo) v_k
+ *              column t = (z, lp)
+ * `itr` counts the initial state, as in si_sample_rwmh and si_sample_mala; shapes, layout and chain ids are theirs.  Every angle is
+ * plain IEEE arithmetic on exact uniforms, formed without contraction.  Only a discontinuous or all-NaN density reaches max_evals.
+ * nev_out and theta_out (the audit's trace) may be NULL.  A chain's bits depend on M alone, not on nchains, its column or the run.
+ * SI_ERR_INVALID unless itr > 0, nchains > 0, chain_id0 >= 0, sigma_z > 0 and 1 <= max_evals <= 2^24 (a NaN is refused);
+ * SI_ERR_STATE while a step-wise session is open.  EVERY ROUND SYNCHRONISES: one evaluation at the chains' pending points, a memset,
+ * one kernel, one 4-byte read-back of the chains still shrinking.  Chains advance in lock-step within a transition (a chain that
+ * has kept a point waits; its slot is evaluated and ignored); a transition takes at most max_evals rounds.                        */
+int32_t si_sample_ess(si_ctx* ctx, int64_t itr, double sigma_z, int32_t max_evals, uint64_t seed, int32_t chain_id0, int32_t nchains,
+                      double* Z_out /* M x itr x C */, double* lp_out /* itr x C */, int32_t* nev_out /* itr x C or NULL */,
+                      double* theta_out /* itr x C or NULL */);
+/* the last si_sample_ess call: passes_out = ceil(nchains / chains per pass of launches) per evaluation; rounds_out and evals_out =
+ * the rounds of all transitions and the sum of |nev| over chains and transitions, column 0 left out (rounds x nchains - evals =
+ * the lock-step waste).  All zero after a refused call.                                                                         */
+int32_t si_ess_kernel_info(si_ctx* ctx, int32_t* passes_out, int64_t* rounds_out, int64_t* evals_out);
 /* :126-138  ADVI with its state on the device.  Restates
  *     AdvancedVI.vi(density, ADVI(S, T), theta -> TuringDiagMvNormal(theta[1:M], exp.(theta[M+1:2M])), rand(MvNormal(zeros(2M), sigma_z)))
  * followed by rand(q, D) (AdvancedVI 0.1.3), with that version's default optimiser TruncatedADAGrad(eta = 0.1, tau = 1.0,

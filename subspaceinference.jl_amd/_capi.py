@@ -131,6 +131,9 @@ SIGNATURES = {
                                  c_int64]),
     "si_nuts_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int64),
                                       POINTER(c_int64)]),
+    "si_sample_ess": (c_int32, [c_void_p, c_int64, c_double, c_int32, c_uint64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
+    "si_ess_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int64), POINTER(c_int64)]),
     "si_fit_advi": (c_int32, [c_void_p, c_int64, c_int32, c_double, c_double, c_double, c_int32, c_uint64, c_int32, c_int32, c_int64,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "si_advi_kernel_info": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
@@ -1011,6 +1014,28 @@ class Context:
         n, lv = c_int64(0), c_int64(0)
         self._check(self.lib.si_nuts_kernel_info(self.h, byref(f), byref(p), byref(r), byref(n), byref(lv)))
         return int(f.value), int(p.value), int(r.value), int(n.value), int(lv.value)
+
+    def sample_ess(self, itr, sigma_z, seed, chain_id0=0, nchains=1, max_evals=128, trace=False):
+        """si_sample_ess (not in the reference): elliptical slice sampling with the chain state on the device, on the library's
+        Philox streams -- the transition of `samplers.ess_iter`.  The target is exp(logdensity(z)) N(z; 0, sigma_z^2 I): sigma_z is
+        here the PRIOR's standard deviation on z, not a step size; lp[t] = logdensity(z[:, t]), the prior on z is not added.  `itr`
+        counts the initial state.  Returns (z [M, itr, C], lp [itr, C]) and with trace=True also (nev, theta) [itr, C]: the
+        evaluations transition t took (-max_evals: the cap was reached and the state kept) and the angle of the kept point."""
+        itr, c = int(itr), int(nchains)
+        z = np.empty((self._m, max(itr, 0), max(c, 0)), dtype=np.float64, order="F")
+        lp = np.empty((max(itr, 0), max(c, 0)), dtype=np.float64, order="F")
+        nev = np.zeros(lp.shape, dtype=np.int32, order="F") if trace else None
+        theta = np.empty_like(lp, order="F") if trace else None
+        self._check(self.lib.si_sample_ess(self.h, itr, float(sigma_z), int(max_evals), int(seed), int(chain_id0), c, _ptr(z), _ptr(lp),
+                                           _ptr(nev), _ptr(theta)))
+        return (z, lp, nev, theta) if trace else (z, lp)
+
+    def ess_kernel_info(self):
+        """(passes, rounds, evals) of the last sample_ess: passes of launches per evaluation, the synchronised rounds of all
+        transitions and the density evaluations of all chains -- rounds * nchains - evals is the lock-step waste"""
+        p, r, n = c_int32(0), c_int64(0), c_int64(0)
+        self._check(self.lib.si_ess_kernel_info(self.h, byref(p), byref(r), byref(n)))
+        return int(p.value), int(r.value), int(n.value)
 
     def fit_advi(self, max_iters, sigma_z, seed, samples_per_step=10, eta=0.1, tau=1.0, window=100, chain_id0=0, nruns=1,
                  ndraws=None, trace=False):

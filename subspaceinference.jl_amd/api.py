@@ -257,6 +257,13 @@ def sub_inference(in_model, data, W_swa, P, σ_z=1.0, σ_m=1.0, σ_p=1.0, itr=10
     Philox streams (seed, chain_id + c), n_adapts = round(itr / 2), max_depth = 10, max_dh = 1000; the initial state is dropped.
     It allows nchains > 1, with :hmc's shapes.  The default :nuts stays `samplers.nuts` on PCG64, bit for bit.
 
+    alg = "ess" (not in the reference; Murray, Adams, MacKay 2010, the sampler of Izmailov et al.'s subspace inference) is elliptical
+    slice sampling of exp(density(z)) N(z; 0, σ_z² I) with the chain state on the device (si_sample_ess; `samplers.ess_iter` is the
+    definition, on the Philox streams (seed, chain_id + c)).  σ_z is here the PRIOR's standard deviation on z, not a step size: the
+    sampler has no proposal scale and never rejects.  lp is the density at every sample; the prior on z is not added.  It needs
+    values only, so it always runs on the device and accepts nchains > 1 (with :mala's shapes), return_z, every likelihood,
+    include_prior, compute_dtype="f32" (Conv included) and a NeuralODE with or without `sensealg`.  itr counts the initial state.
+
     `likelihood` (non-default; not in the reference): "gaussian" is the reference's density.  "categorical" and "bernoulli" sample a
     classifier under the likelihood its cost defines (si_infer_set_likelihood; costs.py is the definition): lp = -costs.numerator(
     LOGITCE | LOGITBCE, model outputs, Y), the outputs read as logits, soft labels kept as written, σ_m unused, the prior term of
@@ -281,7 +288,7 @@ def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg,
     if a == "advi" and (not device_loop or nchains != 1):
         # (this build has no host ADVI loop for a default to fall back to: the fit exists as the device loop only, one run per call)
         raise SubspaceError("alg = :advi is available with device_loop=True and nchains = 1 only (si_fit_advi; DESIGN section 13)")
-    if a not in _RWMH_ALGS and a not in ("mala", "hmc", "nuts", "advi"):
+    if a not in _RWMH_ALGS and a not in ("mala", "hmc", "nuts", "advi", "ess"):
         raise SubspaceError("%s is not available" % a)  # reference :162
     is_node = isinstance(in_model, flux.NeuralODE)   # reference :96-101: the density integrates the model instead of evaluating it
     if not is_node and not isinstance(in_model, flux.Chain):
@@ -293,7 +300,7 @@ def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg,
         raise SubspaceError("likelihood = \"%s\" is not available for NeuralODE models: their density is the sum of squared errors "
                             "of the trajectories" % likelihood)
     if is_node:
-        if a not in _RWMH_ALGS and in_model.sensealg is None:
+        if a not in _RWMH_ALGS and a != "ess" and in_model.sensealg is None:
             raise SubspaceError("alg = :%s needs the gradient of the density, and the gradient through the ODE solver is not built "
                                 "for this model: a NeuralODE model is sampled with alg = :rwmh / :mh, or constructed with "
                                 "sensealg=\"discrete_adjoint\"" % a)
@@ -315,7 +322,7 @@ def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg,
     def setup(w_swa, p):
         if is_node:   # σ_m and σ_p are accepted and unused, as in the reference (:96-101)
             ctx.infer_setup_node(table, n_par, M, w_swa, p, x, y, in_model.saveat, **in_model.options())
-            if in_model.sensealg == "discrete_adjoint" and a not in _RWMH_ALGS:
+            if in_model.sensealg == "discrete_adjoint" and a not in _RWMH_ALGS and a != "ess":
                 ctx.node_set_grad(True)
         else:
             ctx.infer_setup(table, n_par, M, w_swa, p, x, y, σ_m, compute_dtype=cdt)
@@ -343,9 +350,9 @@ def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg,
             raise SubspaceError("device_nuts=True is available for alg = :nuts only")
         if device_loop and a not in ("mala", "advi"):
             raise SubspaceError("device_loop=True is available for alg = :mala and :advi only")
-        if nchains != 1 and a not in _RWMH_ALGS and a != "mala" and not (a == "hmc" and device_sampler) and not (
+        if nchains != 1 and a not in _RWMH_ALGS and a not in ("mala", "ess") and not (a == "hmc" and device_sampler) and not (
                 a == "nuts" and device_nuts):
-            raise SubspaceError("nchains > 1 is available for alg = :rwmh / :mh / :mala (and :hmc with device_sampler=True, "
+            raise SubspaceError("nchains > 1 is available for alg = :rwmh / :mh / :mala / :ess (and :hmc with device_sampler=True, "
                                 ":nuts with device_nuts=True) only")
         if a in _RWMH_ALGS:
             if return_z:
@@ -364,8 +371,11 @@ def _inference(in_model, data, W_swa, P, decoder, σ_z, σ_m, σ_p, itr, M, alg,
                 # :126-138: vi(density, ADVI(10, itr), q, theta_0), then rand(q, itr); the reference returns zeros(itr) for lp
                 _, z, _ = ctx.fit_advi(itr, σ_z, seed, chain_id0=chain_id)
                 z, lp = z[:, :, 0], np.zeros(itr)
-            elif (a == "mala" and device_loop) or (a == "hmc" and device_sampler) or (a == "nuts" and device_nuts):
-                if a == "nuts":
+            elif a == "ess" or (a == "mala" and device_loop) or (a == "hmc" and device_sampler) or (a == "nuts" and device_nuts):
+                if a == "ess":
+                    # not in the reference: elliptical slice sampling under z ~ N(0, σ_z² I), always on the device (si_sample_ess)
+                    z, lp = ctx.sample_ess(itr, σ_z, seed, chain_id, nchains)
+                elif a == "nuts":
                     z, lp = (np.asfortranarray(v[..., 1:, :]) for v in ctx.sample_nuts(itr, σ_z, seed, chain_id, nchains, tree=False)[:2])
                 elif a == "hmc":
                     # :139-160 with the state on the device; column 0 (the initial state) is not a sample of the reference's

@@ -22,6 +22,7 @@ SOURCES = [
     ("capi_advi.hip", []),
     ("capi_hmc.hip", []),
     ("capi_nuts.hip", []),
+    ("capi_ess.hip", []),
     ("capi_train.hip", []),
     ("capi_diffmap.hip", []),
     ("capi_node.hip", []),
@@ -34,6 +35,7 @@ SOURCES = [
     ("kernels_hmc.hip", ["-ffp-contract=off"]),    # (likewise: the leapfrog step, the energies and the adaptor's recursions)
     ("kernels_nuts.hip", ["-ffp-contract=off"]),   # (likewise: the leaves, the energies, the U-turn sums and the tree's weights)
     ("kernels_advi.hip", ["-ffp-contract=off"]),   # (likewise: the update's sums, products and quotients, for the bit-for-bit test)
+    ("kernels_ess.hip", ["-ffp-contract=off"]),    # (likewise: the bracket's angles and the ellipse's two products and sum)
     # (-amdgpu-mfma-vgpr-form: accumulators stay in VGPRs; the default moved them between the two register files at every
     #  block boundary of the layer loops, 32 copies + a pipeline drain per 16 MFMAs)
     ("kernels_chain_grid.hip", ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]),

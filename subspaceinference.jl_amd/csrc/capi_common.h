@@ -211,19 +211,32 @@ inline void eval_pending(si_ctx* ctx, StackedVgrad& vg, hipError_t& e, int32_t& 
 // One synchronised round of a data-dependent loop (the step-size search, a NUTS leaf): one evaluation at the chains' pending
 // points, the open word cleared, launch(open word) -- the kernel counts the chains that go on into it -- a 4-byte read-back into
 // `open` and a synchronisation.  e / rc as StackedVgrad::eval treats them; returns whether the round was completed.
+// What follows the evaluation in either kind of round: the open word `d_open` cleared, launch(d_open), the read-back, the synchronisation
+template <class Launch>
+bool round_tail(si_ctx* ctx, int32_t* d_open, int32_t& open, hipError_t& e, Launch&& launch) {
+  if ((e = hipMemsetAsync(d_open, 0, sizeof(int32_t), ctx->stream)) != hipSuccess) return false;
+  {
+    ProfScope ps(ctx, SI_K_RWMH, 0, 0);
+    launch(d_open);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&open, d_open, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  return e == hipSuccess;
+}
 template <class Launch>
 bool synced_round(si_ctx* ctx, StackedVgrad& vg, int32_t& open, hipError_t& e, int32_t& rc, Launch&& launch) {
   if (e == hipSuccess && rc == SI_OK) eval_pending(ctx, vg, e, rc);
   if (e != hipSuccess || rc != SI_OK) return false;
-  if ((e = hipMemsetAsync(ctx->hmc.open, 0, sizeof(int32_t), ctx->stream)) != hipSuccess) return false;
-  {
-    ProfScope ps(ctx, SI_K_RWMH, 0, 0);
-    launch(ctx->hmc.open.get());
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(&open, ctx->hmc.open, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  return e == hipSuccess;
+  return round_tail(ctx, ctx->hmc.open.get(), open, e, launch);
+}
+// The same round on values alone (an elliptical slice's shrink loop): the evaluation is eval_density_all at the C pending points in
+// chains.zprop, fw.slots per pass of launches, and leaves the density's sums in chains.sse / chains.wsq; the open word is ess.open
+template <class Launch>
+bool value_round(si_ctx* ctx, int32_t C, int32_t& open, hipError_t& e, int32_t& rc, Launch&& launch) {
+  if (e == hipSuccess && rc == SI_OK) rc = eval_density_all(ctx, setup_view(ctx), C);
+  if (e != hipSuccess || rc != SI_OK) return false;
+  return round_tail(ctx, ctx->ess.open.get(), open, e, launch);
 }
 
 // capi_hmc.hip: what si_sample_hmc and si_sample_nuts share.  The chains' state on top of ChainState (nuts: the tree's too); the

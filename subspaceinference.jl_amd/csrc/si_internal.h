@@ -562,6 +562,20 @@ struct InferAdvi {
   DevBuf<double> trace, pts;      // 2M x (T+1) x R, M x S x T x R: only when asked for, kept between calls
   CallInfo info;
 };
+// si_sample_ess (capi_ess.hip, kernels_ess.hip), on top of the RWMH samplers' state (InferChains: z, lp, the pending point and the
+// density's sums): the ellipse's second point, the slice and the bracket, the per-chain counters, the open word of value_round and
+// the device-side nev / theta samples.  Not in the reference.
+struct EssState {
+  int cap = 0;
+  DevBuf<double> nu;                       // M x C
+  DevBuf<double> logy, theta, lo, hi;      // C each
+  DevBuf<int32_t> k, closed;               // C each
+  DevBuf<int32_t> open;                    // 1: chains still shrinking (value_round)
+  DevBuf<int32_t> outnev;                  // itr x C, kept between calls like outZ
+  DevBuf<double> outtheta;                 // itr x C
+  int32_t passes = 0;                      // si_ess_kernel_info: what the last call took (zero after a refused one)
+  int64_t rounds = 0, evals = 0;
+};
 struct InferState {
   InferSetup setup;
   NodeState node;                 // on: the set-up is a NeuralODE's; the density integrates instead of evaluating a Chain
@@ -576,6 +590,7 @@ struct InferState {
   InferHmc hmc;
   InferNuts nuts;
   InferAdvi advi;
+  EssState ess;
 };
 
 struct Ctx : CtxCore, ConstructState, InferState {};
@@ -1075,6 +1090,25 @@ void launch_advi_draw(hipStream_t st, const AdviRun& a, int32_t R, double sigma_
 // step t given (lp, g) at its points: elbo_t, d, the ring, s, theta_{t+1}, the traces and (form_next) the points of step t + 1
 void launch_advi_update(hipStream_t st, const AdviRun& a, int32_t R, const double* lp, const double* g, double eta_opt, double tau,
                         int64_t t, double* elbo_out, bool form_next);
+// kernels_ess.hip (the transition is defined in its header comment): C chains, one workgroup each.  The state (z, lp) and the
+// pending point zp are the RWMH samplers' buffers (chains.zcur, chains.lpcur, chains.zprop: what eval_density_all evaluates), the
+// density's sums at zp are chains.sse / chains.wsq (wsq NULL: no prior term); the constants are rwmh_accept_kernel's
+struct EssRun {
+  double *z, *lp, *zp, *nu;                            // M x C (lp: C)
+  const double *sse, *wsq;                             // C each
+  double *logy, *theta, *lo, *hi;                      // C each: the slice's level, the pending angle, the bracket
+  int32_t *k, *closed;                                 // C each: evaluations of the transition so far; the transition is decided
+  double *Z_out, *lp_out, *theta_out;                  // M x itr x C, itr x C twice
+  int32_t* nev_out;                                    // itr x C
+  int32_t M, chain_id0, max_evals;
+  int64_t itr;
+  uint64_t seed;
+  double sigma_z, c0, s2, c0p, sp2;
+};
+void launch_ess_init(hipStream_t st, const EssRun& a, int32_t C);                    // zp = sigma_z n_0
+void launch_ess_begin(hipStream_t st, const EssRun& a, int32_t C, uint64_t step);    // nu, logy, the first angle and point of transition `step`
+// one round given the sums at zp: keep / cap / shrink for every open chain; the chains that go on are counted into open
+void launch_ess_round(hipStream_t st, const EssRun& a, int32_t C, uint64_t step, int32_t* open);
 void launch_rwmh_init(hipStream_t st, double* zcur, double* lpcur, int64_t* nacc, uint64_t* steps, int32_t M, int32_t C);
 void launch_rwmh_propose(hipStream_t st, const double* zcur, double* zprop, int32_t M, int32_t C,
                          double sigma_z, uint64_t seed, int32_t chain_id0, const uint64_t* steps);

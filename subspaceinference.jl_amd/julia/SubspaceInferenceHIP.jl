@@ -410,6 +410,30 @@ function mala_kernel_info(ctx::Ctx)
     return fused[] != 0, Int(passes[])
 end
 
+# not in the reference: elliptical slice sampling (Murray, Adams, MacKay 2010) of exp(density(z)) N(z; 0, σ_z^2 I) with the chain state
+# on the device (si_sample_ess), on the library's Philox streams (seed, chain_id + c).  σ_z is here the PRIOR's standard deviation
+# on z, not a step size; lp is the density at every sample, the prior on z is not added; itr counts the initial state.  Returns Z
+# (M x itr x nchains) and lp (itr x nchains), and with trace = true nev and theta (itr x nchains): the evaluations a transition took
+# (-max_evals: the cap was reached, the state kept) and the angle of the kept point.
+function sample_ess(ctx::Ctx, itr, σ_z, M; seed = 0, chain_id = 0, nchains = 1, max_evals = 128, trace = false)
+    Z = Array{Float64}(undef, M, itr, nchains); lp = Matrix{Float64}(undef, itr, nchains)
+    nev = trace ? Matrix{Int32}(undef, itr, nchains) : nothing
+    theta = trace ? Matrix{Float64}(undef, itr, nchains) : nothing
+    GC.@preserve Z lp nev theta check(ctx, ccall((:si_sample_ess, LIB), Int32,
+        (Ptr{Cvoid}, Int64, Float64, Int32, UInt64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+        ctx.h, itr, σ_z, max_evals, seed, chain_id, nchains, Z, lp, nev === nothing ? C_NULL : pointer(nev),
+        theta === nothing ? C_NULL : pointer(theta)))
+    return trace ? (Z, lp, nev, theta) : (Z, lp)
+end
+
+# (passes, rounds, evals) of the last sample_ess: passes of launches per evaluation, the synchronised rounds of all transitions, the
+# density evaluations of all chains (rounds * nchains - evals = the lock-step waste)
+function ess_kernel_info(ctx::Ctx)
+    passes = Ref{Int32}(0); rounds = Ref{Int64}(0); evals = Ref{Int64}(0)
+    check(ctx, ccall((:si_ess_kernel_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}, Ref{Int64}), ctx.h, passes, rounds, evals))
+    return Int(passes[]), Int(rounds[]), Int(evals[])
+end
+
 # :139-160 (alg = :hmc) with position, momentum, step size, metric and adaptor state on the device (si_sample_hmc): the one-step HMC,
 # StanHMCAdaptor and find_good_stepsize restated on the library's Philox streams (seed, chain_id + c).  Returns Z (M x (itr+1) x
 # nchains), lp, alpha and eps ((itr+1) x nchains): column 1 is the initial state, alpha[t] / eps[t] the acceptance probability and the
@@ -692,6 +716,8 @@ end
 # likelihood = :categorical / :bernoulli (non-default; not in the reference): the classifier's likelihood on the model's outputs in
 # place of the Gaussian (si_infer_set_likelihood): lp = sum(Y .* logsoftmax(ŷ; dims = 1)) / -sum((1 .- Y) .* ŷ .+ softplus.(-ŷ));
 # σ_m is unused then
+# alg = :ess (not in the reference): elliptical slice sampling under the prior z ~ N(0, σ_z^2 I), always on the device (sample_ess);
+# σ_z is the prior's standard deviation on z there, not a step size
 const SI_LIK = Dict(:gaussian => Int32(0), :categorical => Int32(1), :bernoulli => Int32(2))
 set_likelihood(ctx::Ctx, kind::Integer) = check(ctx, ccall((:si_infer_set_likelihood, LIB), Int32, (Ptr{Cvoid}, Int32), ctx.h, kind))
 function likelihood_info(ctx::Ctx)
@@ -709,7 +735,7 @@ function sub_inference(in_model, data, W_swa, P; σ_z = 1.0, σ_m = 1.0, σ_p = 
         (alg in (:mala, :advi) ? " (alg = :$alg runs on the device with device_loop = true)" : ""))
     (device_loop && !(alg in (:mala, :advi))) && throw("device_loop = true is available for alg = :mala and :advi only")
     (alg == :advi && !device_loop) && throw("alg = :advi is available with device_loop = true only (fit_advi)")
-    alg in (:rwmh, :mala, :hmc, :nuts, :advi) || throw("$alg is not available")       # :162
+    alg in (:rwmh, :mala, :hmc, :nuts, :advi, :ess) || throw("$alg is not available")       # :162
     in_model isa Chain || throw("Error: density function is not avaliable for this model")
     compute_dtype in (:f64, :f32) || throw("compute_dtype must be :f64 (the reference's arithmetic) or :f32")
     X, Y, insize = data_matrices(data)                              # split_data (src/libs.jl:75-77)
@@ -732,6 +758,10 @@ function sub_inference(in_model, data, W_swa, P; σ_z = 1.0, σ_m = 1.0, σ_p = 
             (Ptr{Cvoid}, Int64, Float64, UInt64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}),
             ctx.h, itr, σ_z, seed, chain_id, 1, Z, lp, acc, Wm))
         return [Wm[:, t] for t in 1:itr], lp
+    end
+    if alg == :ess
+        Z, lp = sample_ess(ctx, itr, σ_z, M; seed = seed, chain_id = chain_id)
+        return reconstruct(ctx, Z[:, :, 1], N), lp[:, 1]
     end
     if alg == :mala && device_loop
         Z, lp, _ = sample_mala(ctx, itr, σ_z, M; seed = seed, chain_id = chain_id)

@@ -441,3 +441,70 @@ def nuts_iter(logdensity_grad, m, itr, sigma_z, draw, delta=0.8, max_depth=10, m
             stats.append((ndoub, nleaf, sel))
         ad.adapt(z, a)
     return zs, lps, float(acc.mean())
+
+
+# the kinds of draw of `ess_iter`, the first argument of its callback
+ESS_DRAW_INITIAL, ESS_DRAW_NU, ESS_DRAW_LEVEL, ESS_DRAW_ANGLE = "initial", "nu", "level", "angle"
+ESS_TWO_PI = 2.0 * math.pi
+
+
+def ess_sequential_draw(rng, m):
+    """the callback of `ess_iter` that ignores the address and pulls from `rng` in call order: m standard normals for the two vector
+    kinds, an Exp(1) variate for the level, a uniform of [0, 1) for an angle"""
+    def draw(kind, t, j):
+        if kind in (ESS_DRAW_INITIAL, ESS_DRAW_NU):
+            return rng.standard_normal(m)
+        return rng.exponential() if kind == ESS_DRAW_LEVEL else rng.random()
+    return draw
+
+
+def ess_iter(logdensity, m, itr, sigma_z, draw, max_evals=128, stats=None):
+    """Elliptical slice sampling (Murray, Adams, MacKay 2010) -- NOT IN THE REFERENCE; the sampler Izmailov et al. ("Subspace
+    Inference for Bayesian Deep Learning") run in the subspace -- of the target exp(logdensity(z)) N(z; 0, sigma_z^2 I).  sigma_z is
+    here the PRIOR's standard deviation on z, not a step size.  lps[t] = logdensity(zs[:, t]): the prior on z is never evaluated and
+    is not added.  `itr` counts the initial state, as `mala`'s.  THE DEFINITION of si_sample_ess (csrc/kernels_ess.hip), which
+    tests/ess_audit.py holds to it on the Philox streams.
+
+    Every random number comes through `draw(kind, t, j)`: ESS_DRAW_INITIAL (t = 0) and ESS_DRAW_NU (transition t) give m standard
+    normals, ESS_DRAW_LEVEL an Exp(1) variate e_t, ESS_DRAW_ANGLE the uniform v_j of transition t (j = 0: the first angle, j = k:
+    the shrink after evaluation k).  A transition that has not found a point on the slice after max_evals evaluations keeps its
+    state (only a discontinuous or all-NaN density gets there).  stats: a list that receives per column (nev, theta) -- the
+    evaluations taken (-max_evals: the cap) and the kept angle (0 for column 0 and at the cap)."""
+    z = sigma_z * draw(ESS_DRAW_INITIAL, 0, 0)
+    lp = logdensity(z)
+    zs = np.empty((m, itr), order="F")
+    lps = np.empty(itr)
+    zs[:, 0], lps[0] = z, lp
+    if stats is not None:
+        stats.append((1, 0.0))
+    for t in range(1, itr):
+        nu = sigma_z * draw(ESS_DRAW_NU, t, 0)
+        logy = lp - draw(ESS_DRAW_LEVEL, t, 0)
+        theta = ESS_TWO_PI * draw(ESS_DRAW_ANGLE, t, 0)
+        lo, hi = theta - ESS_TWO_PI, theta
+        k = 0
+        while True:
+            zp = z * math.cos(theta) + nu * math.sin(theta)
+            lpp = logdensity(zp)
+            k += 1
+            if lpp > logy:                       # (a NaN compares false)
+                z, lp = zp, lpp
+                nev = k
+                break
+            if k == max_evals:
+                nev, theta = -max_evals, 0.0
+                break
+            if theta < 0.0:
+                lo = theta
+            else:
+                hi = theta
+            theta = lo + (hi - lo) * draw(ESS_DRAW_ANGLE, t, k)
+        zs[:, t], lps[t] = z, lp
+        if stats is not None:
+            stats.append((nev, theta))
+    return zs, lps
+
+
+def ess(logdensity, m, itr, sigma_z, rng, max_evals=128):
+    """`ess_iter` on a NumPy generator: (zs [m, itr], lps [itr])"""
+    return ess_iter(logdensity, m, itr, sigma_z, ess_sequential_draw(rng, m), max_evals)
